@@ -17,8 +17,11 @@ script is a rank as before.  `--launcher-dry-run` runs the same N-rank protocol 
 on the CPU (tests/test_launcher_cpu.py).
 
 Rank 0 prints ONE JSON line.  The timed region -- exactly --steps steps between two barrier + synchronize fences,
-starting and ending with an empty engine, MAX over ranks -- is run --repeats times back to back; `value` is the MEDIAN
-region and every region's figure is listed (a 50-step region lasts ~0.1 s: one shot of it has a few percent of noise).
+starting and ending with an empty engine, MAX over ranks -- is run once, so --steps is the number of timed steps and
+`ms_per_step` the time of one of them; --repeats R runs R such regions back to back, `value` is then the MEDIAN region
+and every region's figure is listed (a 50-step region lasts ~0.1 s: one shot of it has a few percent of noise).
+`--dump-outputs DIR` writes what the last timed step returned (the last pair's feats_f / scores_overlap /
+scores_saliency) as DIR/<name>.npy, float32; inputs and weights are seeded, so two builds can be compared output for output.
 `roofline` is measured live with HIP start/stop events of every launch of the dominant kernel (the KPConv
 neighbour-gather/aggregate kernel) inside those regions; `roofline.gemm` and `roofline.radius` do the same for the GEMM
 family and the radius searches in one extra region of the same engine; `secondary` carries bounded runs of configs[4]
@@ -30,11 +33,6 @@ import json
 import os
 import sys
 import time
-
-# The HIP runtime multiplexes streams onto GPU_MAX_HW_QUEUES hardware queues (default 4).  The pair engine
-# uses a front-end stream + three model streams (+ the default stream): with 4 queues two of them share
-# one and serialise (measured: 260 vs 338 pairs/s).  Must be set before the first HIP call.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 
 REPO = os.path.dirname(os.path.abspath(__file__))
 if REPO not in sys.path:
@@ -108,6 +106,22 @@ def make_pair(recipe, seed):
     if INPUT_ORDER == "morton":      # experiment (--input-order morton): spatially coherent point order, DESIGN.md 5
         pr = tuple(np.ascontiguousarray(c[_morton_order(c)]) for c in pr)
     return pr
+
+
+DUMP_CAP_BYTES = 64 << 20
+
+
+def dump_outputs(out, dirname):
+    """--dump-outputs: the arrays the engine hands its caller for one pair, as DIR/<name>.npy in float32.  The largest
+    workload (K120k: 240 000 x 32 descriptors) writes ~32 MB, inside the cap."""
+    arrays = {k: v.detach().to(torch.float32).cpu().numpy() for k, v in sorted(out.items())
+              if isinstance(v, torch.Tensor) and not k.startswith("_")}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_CAP_BYTES:
+        raise RuntimeError("--dump-outputs: %d bytes of outputs exceed the %d-byte cap" % (total, DUMP_CAP_BYTES))
+    os.makedirs(dirname, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(dirname, k + ".npy"), a)
 
 
 def _gemm_mode():
@@ -563,8 +577,10 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=480)     # (whole groups of four pairs on three model streams; 0.8 s regions: fill and drain of the engine are ~1 % of them)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--repeats", type=int, default=5,
+    ap.add_argument("--repeats", type=int, default=1,
                     help="timed regions of --steps steps each, run back to back; `value` is the median region")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step (the engine's result for its last pair) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true",
                     help="skip the secondary regions (GEMM / radius events, HBM-resident inputs, one-column upsample tables, "
@@ -607,6 +623,8 @@ def main():
                     help="the N-rank protocol (launcher, process group, fences, MAX over ranks, rank 0's line) over gloo "
                          "on the CPU with a stand-in workload: what tests/test_launcher_cpu.py runs; never a measurement")
     args = ap.parse_args()
+    if args.dump_outputs and (args.isolated_only or args.image129_only or args.launcher_dry_run):
+        ap.error("--dump-outputs writes the pair engine's outputs: not with --isolated-only, --image129-only or --launcher-dry-run")
     global RECIPE, INPUT_ORDER
     RECIPE = args.workload
     INPUT_ORDER = args.input_order
@@ -744,6 +762,7 @@ def main():
         torch.cuda.synchronize()
 
     HEAD_FROM_HOST = args.inputs == "host"
+    last_out = [None]        # the engine's result for the last pair of the latest region
 
     def region(pipe, from_host=HEAD_FROM_HOST):
         """EXACTLY --steps steps from an empty engine to an empty engine; -> seconds (MAX over ranks), submit seconds."""
@@ -754,6 +773,7 @@ def main():
         fence(pipe)
         elapsed = time.perf_counter() - t0
         assert out["feats_f"].shape[1] == cfg.final_feats_dim
+        last_out[0] = out
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         if dist is not None:
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -782,6 +802,8 @@ def main():
     cpu_s_per_pair = ((cpu1.user - cpu0.user) + (cpu1.system - cpu0.system)) / max(R * args.steps, 1)
     events = ops.kpconv_profile_stop()
     stats = pipe.stats_snapshot()
+    if args.dump_outputs and rank == 0:       # before the extra regions: the headline's last step, copied off the device
+        dump_outputs(last_out[0], args.dump_outputs)
     own = sorted(r[2] for r in regions)[len(regions) // 2]      # this rank's own clock, median region
     per_rank = launcher.rank_fields(dist, world, rank, round(args.steps / own, 3), RANK_CPUS, device=dev)
     times = sorted(r[0] for r in regions)

@@ -28,11 +28,11 @@ to one, and a dispatcher hands out the workgroups of one kernel at a time, so tw
 kernel by kernel (profiles/r06_queue_pipes.txt).  The engine therefore CHOOSES its streams: it classifies a dozen
 candidates by measurement (pcrcg_stream_pipe_classes, ~50 ms at construction) and takes the front-end streams from one
 class and the three model streams from the other three (_pick_streams; `pipe_classes` records the choice, a
-RuntimeWarning says when it could not be made).  That holds with the runtime's default of four hardware queues and with
-GPU_MAX_HW_QUEUES=8 alike; rounds 1-5 took streams in creation order and needed the variable set before the first HIP
-call.  It also lifted the "one engine per process" rule of those rounds (a fresh engine 453 pairs/s, the third one created
-in the same process 355): four engines created one after the other in one process run at 586-592 pairs/s each
-(scripts/engines_in_one_process.py).  Two engines ACTIVE at once still share the four dispatchers."""
+RuntimeWarning says when it could not be made).  That holds whenever the process's hardware queues reach all four
+dispatchers: the runtime's default of four queues does, and eight did alike (round 6); rounds 1-5 took streams in
+creation order and needed more queues set before the first HIP call.  It also lifted the "one engine per process" rule
+of those rounds (a fresh engine 453 pairs/s, the third one created in the same process 355): four engines created one
+after the other in one process run at 586-592 pairs/s each (scripts/engines_in_one_process.py).  Two engines ACTIVE at once still share the four dispatchers."""
 import os
 import queue
 import threading
@@ -230,10 +230,11 @@ class PairStreams:
             take[c] += 1
         mcls = [others[m % len(others)] for m in range(n_model)]
         # the engine's premise, verified: the front end and every model stream on a dispatcher of its own (with up to three
-        # model streams).  It holds with the runtime's default of four hardware queues as well as with GPU_MAX_HW_QUEUES=8
-        # (tests/test_pairstream_gpu.py runs both in fresh processes) -- the streams are CHOSEN by class, not taken in creation
-        # order, which is what made rounds 1-5 depend on that variable (448 against 536 pairs/s).  If the probe finds fewer
-        # classes than the engine needs streams, two of them will take turns: say so instead of running slowly in silence.
+        # model streams).  It holds with the runtime's default of four hardware queues, and held with eight in round 6
+        # (tests/test_pairstream_gpu.py checks it in a fresh process with the queues it is given) -- the streams are
+        # CHOSEN by class, not taken in creation order, which is what made rounds 1-5 depend on the queue count (448 against
+        # 536 pairs/s).  If the probe finds fewer classes than the engine needs streams, two of them will take turns: say so
+        # instead of running slowly in silence.
         distinct = len(set(mcls)) == min(n_model, 3) and front_class not in mcls
         if not distinct:
             import warnings

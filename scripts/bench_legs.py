@@ -1,5 +1,4 @@
 import os, sys
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 R = os.environ.get("GRAFT_REPO_ROOT", "/root/repo")
 sys.path.insert(0, R)
 import torch

@@ -1,5 +1,4 @@
 import os, sys, time, json
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
 import numpy as np, torch
 from pcrcg_amd import indoor_config, synthetic

@@ -5,7 +5,6 @@
 R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-export GPU_MAX_HW_QUEUES=8
 P1="SQ_WAVES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE"
 P2="TCC_HIT_sum TCC_MISS_sum"
 {

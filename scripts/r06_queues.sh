@@ -2,12 +2,7 @@
 R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out; mkdir -p $O
 cd $R
-{
-for Q in 4 8 16; do
-  GPU_MAX_HW_QUEUES=$Q timeout 120 scripts/micro/queue_pipes 8
-done
-GPU_MAX_HW_QUEUES=16 timeout 200 scripts/micro/queue_pipes 12
-} > $O/r06_queue_pipes.txt 2>&1
+timeout 120 scripts/micro/queue_pipes 8 > $O/r06_queue_pipes.txt 2>&1
 cat $O/r06_queue_pipes.txt
 # the 20-step region's timeline with the new front end
 cd /tmp && export TMPDIR=/tmp

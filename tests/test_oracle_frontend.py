@@ -1,6 +1,5 @@
 """CPU: the oracle's C front end (oracle/front_end.c) against the golden vectors generated from the
-unmodified reference C++ (scripts/make_golden_frontend.py) and, when the prebuilt reference checker
-library oracle/_ref is present, against the reference itself."""
+unmodified reference C++ (scripts/make_golden_frontend.py, scripts/make_golden_reflib.py)."""
 import hashlib
 import json
 import os
@@ -10,7 +9,7 @@ import pytest
 
 from oracle import frontend as OF
 from pcrcg_amd import synthetic
-from tests.tieutil import assert_tables_equal_mod_ties, canonicalise_table
+from tests.tieutil import assert_tables_equal_mod_ties, canonicalise_table, row_d2
 
 
 def _sha(a):
@@ -81,47 +80,116 @@ def test_properties_and_errors():
         OF.oracle_batch_query(pts, pts, lens, lens[:1], 0.1)
 
 
-@pytest.mark.skipif(not OF.have_ref(), reason="oracle/_ref (reference checker library) not built")
-def test_against_reference_library():
+# ---- against the unmodified reference C++: its answers on these fixed inputs are stored in tests/golden/reflib_digests.json
+# (scripts/make_golden_reflib.py runs the same *_records functions over oracle/_ref/libpcrcg_ref.so)
+def _fns(lib):
+    """(umap_order, subsample_batch, batch_query) of "ref" (the reference C++) or "oracle" (the restatement)."""
+    if lib == "ref":
+        return OF.ref_umap_order, OF.ref_subsample_batch, OF.ref_batch_query
+    return OF.oracle_umap_order, OF.oracle_subsample_batch, OF.oracle_batch_query
+
+
+def _table_record(t, q, s, exact=False):
+    """What is compared of a neighbour table: its shape, the SHA-256 of the table as returned (exact) or with the order
+    inside groups of exactly equal distance canonicalised (assert_tables_equal_mod_ties), and whether every row is sorted
+    by distance."""
+    with np.errstate(invalid="ignore"):
+        d2 = np.where(t >= s.shape[0], np.float32(np.inf), row_d2(t, q, s))
+    return {"shape": list(t.shape), "sha256": _sha(t if exact else canonicalise_table(t, q, s)[0]),
+            "rows_sorted": bool(((d2[:, 1:] >= d2[:, :-1]) | np.isinf(d2[:, 1:])).all())}
+
+
+def _subsample_record(p, l):
+    return {"points": _sha(_bits(p)), "lens": _sha(np.asarray(l, np.int32))}
+
+
+def library_records(lib):
+    """Hash-map order, subsampling (with and without max_p) and the searches over the subsampled points."""
+    order, subsample, query = _fns(lib)
     rng = np.random.RandomState(2)
+    rec = {"umap_order": []}
     for n in (1, 13, 14, 700, 30000):
         k = np.unique(rng.randint(0, 1 << 50, size=2 * n).astype(np.uint64))
         rng.shuffle(k)
-        assert (OF.oracle_umap_order(k[:n]) == OF.ref_umap_order(k[:n])).all()
+        rec["umap_order"].append(_sha(np.asarray(order(k[:n]), np.int32)))
     a = (rng.rand(900, 3) - 0.5).astype(np.float32) * 3
     b = (rng.rand(400, 3)).astype(np.float32) + 5
     pts, lens = np.concatenate([a, b]), np.array([900, 400], np.int32)
+    rec["subsample"] = []
     for dl in (0.11, 0.4):
-        rp, rl = OF.ref_subsample_batch(pts, lens, dl)
-        op, ol = OF.oracle_subsample_batch(pts, lens, dl)
-        assert (rl == ol).all() and (_bits(rp) == _bits(op)).all()
-        assert_tables_equal_mod_ties(OF.oracle_batch_query(rp, pts, rl, lens, 2.5 * dl),
-                                     OF.ref_batch_query(rp, pts, rl, lens, 2.5 * dl), rp, pts)
-    rp, rl = OF.ref_subsample_batch(pts, lens, 0.11, max_p=50)
-    op, ol = OF.oracle_subsample_batch(pts, lens, 0.11, max_p=50)
-    assert (rl == ol).all() and (_bits(rp) == _bits(op)).all()
+        p, l = subsample(pts, lens, dl)
+        rec["subsample"].append(dict(_subsample_record(p, l), query=_table_record(query(p, pts, l, lens, 2.5 * dl), p, pts)))
+    rec["subsample_max_p"] = _subsample_record(*subsample(pts, lens, 0.11, max_p=50))
+    return rec
 
 
-@pytest.mark.skipif(not OF.have_ref(), reason="oracle/_ref (reference checker library) not built")
-def test_random_lattice_clouds_against_reference_library():
-    """Property test (hypothesis): tiny clouds on coarse lattices -- duplicates, exact distance ties, points on
-    cell boundaries, one-point clouds, negative coordinates -- oracle C front end vs the reference C++."""
-    from hypothesis import given, settings, strategies as st
-
-    @settings(max_examples=60, deadline=None, derandomize=True)
-    @given(st.integers(1, 120), st.integers(1, 90), st.integers(2, 9), st.sampled_from([0.25, 0.5, 1.0, 1.7]),
-           st.integers(0, 2 ** 31 - 1))
-    def check(n0, n1, lattice, dl, seed):
+def lattice_records(lib, cases):
+    """Tiny clouds on coarse lattices -- duplicates, exact distance ties, points on cell boundaries, one-point clouds,
+    negative coordinates: cases = [(n0, n1, lattice, dl, seed), ...]."""
+    _, subsample, query = _fns(lib)
+    out = []
+    for n0, n1, lattice, dl, seed in cases:
         rng = np.random.RandomState(seed)
         pts = (rng.randint(-lattice, lattice + 1, size=(n0 + n1, 3)) / np.float32(4)).astype(np.float32)
         lens = np.array([n0, n1], np.int32)
-        rp, rl = OF.ref_subsample_batch(pts, lens, dl)
-        op, ol = OF.oracle_subsample_batch(pts, lens, dl)
-        assert (rl == ol).all() and (_bits(rp) == _bits(op)).all()
-        for q, s_, ql, sl, r in ((pts, pts, lens, lens, 1.2 * dl), (rp, pts, rl, lens, 1.2 * dl), (pts, rp, lens, rl, 2.4 * dl)):
-            assert_tables_equal_mod_ties(OF.oracle_batch_query(q, s_, ql, sl, r), OF.ref_batch_query(q, s_, ql, sl, r), q, s_)
+        p, l = subsample(pts, lens, dl)
+        out.append(dict(_subsample_record(p, l), tables=[
+            _table_record(query(q, s_, ql, sl, r), q, s_)
+            for q, s_, ql, sl, r in ((pts, pts, lens, lens, 1.2 * dl), (p, pts, l, lens, 1.2 * dl), (pts, p, lens, l, 2.4 * dl))]))
+    return out
 
-    check()
+
+def tie_order_records(lib):
+    """Coarse lattices (deep groups of equal distance, duplicates), 1-3 clouds, empty support clouds; plus two cases whose
+    rows are long enough for the introsort partition loop and hold thousands of equal keys.  Tables exactly as returned
+    (the oracle in the reference's tie order); "RuntimeError" where the call raises."""
+    if lib == "ref":
+        query = OF.ref_batch_query
+    else:
+        def query(*a):
+            return OF.oracle_batch_query(*a, tie_order="reference")
+    rng = np.random.default_rng(2)
+    out = []
+    for _ in range(150):
+        nb = int(rng.integers(1, 4))
+        sl = rng.integers(0, 400, nb).astype(np.int32)
+        ql = rng.integers(1, 200, nb).astype(np.int32)     # an EMPTY query cloud before a non-empty one is outside the
+        if sl.sum() == 0:                                  # contract: the reference advances one cloud per query (:270)
+            continue
+        step = float(rng.choice([1 / 4, 1 / 8, 1 / 16, 1 / 64, 1 / 1024]))
+        s = (np.round(rng.random((sl.sum(), 3)) / step) * step).astype(np.float32)
+        q = (np.round(rng.random((ql.sum(), 3)) / step) * step).astype(np.float32)
+        r = float(rng.choice([0.2, 0.35, 0.5, 1.0]))
+        try:
+            out.append(_table_record(query(q, s, ql, sl, r), q, s, exact=True))
+        except RuntimeError:
+            out.append("RuntimeError")
+    s = np.zeros((5000, 3), np.float32)
+    s[:2500, 0] = 0.25
+    q = np.zeros((7, 3), np.float32)
+    out.append(_table_record(query(q, s, [7], [5000], 1.0), q, s, exact=True))
+    s = (rng.integers(0, 6, (20000, 3)) / 8).astype(np.float32)
+    out.append(_table_record(query(s[:100], s, [100], [20000], 0.4), s[:100], s, exact=True))
+    return out
+
+
+@pytest.fixture(scope="module")
+def reflib(golden_dir):
+    return json.load(open(os.path.join(golden_dir, "reflib_digests.json")))
+
+
+def test_against_reference_library(reflib):
+    got = library_records("oracle")
+    for key, want in reflib["library"].items():
+        assert got[key] == want, key
+
+
+def test_random_lattice_clouds_against_reference_library(reflib):
+    """The cases a derandomised property test (hypothesis, 60 examples) drew, oracle C front end vs the reference C++."""
+    cases = reflib["lattice"]["cases"]
+    assert len(cases) >= 50
+    for case, got, want in zip(cases, lattice_records("oracle", cases), reflib["lattice"]["records"]):
+        assert got == want, case
 
 
 # ---- the reference's own order inside tie groups (nanoflann traversal + libstdc++ std::sort restated) ----------
@@ -152,36 +220,13 @@ def test_reference_tie_order_digests(golden_dir, recipe):
         assert list(t.shape) == dig[name]["shape"] and _sha(t) == dig[name]["sha256"], name
 
 
-@pytest.mark.skipif(not OF.have_ref(), reason="oracle/_ref (reference checker library) not built")
-def test_reference_tie_order_against_reference_library():
-    """Coarse lattices (deep groups of equal distance, duplicates), 1-3 clouds, empty support clouds; plus two
-    cases whose rows are long enough for the introsort partition loop and hold thousands of equal keys."""
-    rng = np.random.default_rng(2)
-    for _ in range(150):
-        nb = int(rng.integers(1, 4))
-        sl = rng.integers(0, 400, nb).astype(np.int32)
-        ql = rng.integers(1, 200, nb).astype(np.int32)     # an EMPTY query cloud before a non-empty one is outside the
-        if sl.sum() == 0:                                  # contract: the reference advances one cloud per query (:270)
-            continue
-        step = float(rng.choice([1 / 4, 1 / 8, 1 / 16, 1 / 64, 1 / 1024]))
-        s = (np.round(rng.random((sl.sum(), 3)) / step) * step).astype(np.float32)
-        q = (np.round(rng.random((ql.sum(), 3)) / step) * step).astype(np.float32)
-        r = float(rng.choice([0.2, 0.35, 0.5, 1.0]))
-        try:
-            want = OF.ref_batch_query(q, s, ql, sl, r)
-        except RuntimeError:
-            with pytest.raises(RuntimeError):
-                OF.oracle_batch_query(q, s, ql, sl, r, tie_order="reference")
-            continue
-        got = OF.oracle_batch_query(q, s, ql, sl, r, tie_order="reference")
-        assert got.shape == want.shape and (got == want).all()
-    s = np.zeros((5000, 3), np.float32)
-    s[:2500, 0] = 0.25
-    q = np.zeros((7, 3), np.float32)
-    assert (OF.oracle_batch_query(q, s, [7], [5000], 1.0, tie_order="reference") == OF.ref_batch_query(q, s, [7], [5000], 1.0)).all()
-    s = (rng.integers(0, 6, (20000, 3)) / 8).astype(np.float32)
-    assert (OF.oracle_batch_query(s[:100], s, [100], [20000], 0.4, tie_order="reference")
-            == OF.ref_batch_query(s[:100], s, [100], [20000], 0.4)).all()
+def test_reference_tie_order_against_reference_library(reflib):
+    """The oracle in the reference's tie order returns the reference's tables entry for entry (tie_order_records)."""
+    want = reflib["tie_order"]
+    got = tie_order_records("oracle")
+    assert len(got) == len(want)
+    for i, (g, w) in enumerate(zip(got, want)):
+        assert g == w, i
 
 
 def test_sanitizer_job_of_the_cpu_checkers():
