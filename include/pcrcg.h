@@ -527,7 +527,8 @@ typedef struct pcrcg_batch {
     const float* points[PCRCG_MAX_LEVELS];
     int n_points[PCRCG_MAX_LEVELS];
     pcrcg_table neighbors[PCRCG_MAX_LEVELS], pools[PCRCG_MAX_LEVELS], upsamples[PCRCG_MAX_LEVELS];
-    const float* features; /* [n_points[0], feat_dim] */
+    const float* features; /* [n_points[0], feat_dim]; feat_dim = the first block's in_dim, or its cin_pad when it carries
+                              kp_w_pad (features handed over already zero-padded); anything else is PCRCG_EBADARG */
     int feat_dim;
     int len_src_c;         /* stack_lengths[-1][0] */
     const int* stack_lengths[PCRCG_MAX_LEVELS]; /* [nb] i32 per level (device); filled by pcrcg_pyramid_build,
@@ -574,7 +575,9 @@ int pcrcg_kpfcnn_forward_group(const pcrcg_model* model, const pcrcg_batch* batc
  *              sizes every buffer, table and launch of the level.  A cloud that keeps more rows than the bound allows is
  *              reported as PCRCG_EWORKSPACE at the end of the call -- nothing is corrupted, call again with a larger
  *              shrink (and the arena that goes with it).
- *   h_scratch  HOST scratch of >= 256 ints, pinned for best latency; h_lengths HOST [n_levels * nb] receives the
+ *   h_scratch  HOST scratch of >= 256 ints, pinned for best latency: the call writes 2 + 3 n_levels (P + 2) + n_levels
+ *              + n_levels nb of them (P = nb / group, or 1), at most 254 under the argument checks (n_levels <= 4,
+ *              P <= 14, n_levels nb <= 64), and rejects anything above 256; h_lengths HOST [n_levels * nb] receives the
  *              per-level cloud lengths (stack_lengths); h_status HOST int (pinned; may be NULL) receives the tie-order
  *              restore status word ASYNCHRONOUSLY -- valid once `stream` has drained, 0 = fine, else as documented at
  *              pcrcg_radius_reorder_jobs.

@@ -161,7 +161,9 @@ int pcrcg_edgeconv_backward(const float* ctr, const float* nbr, const int* idx, 
 /* ---- the train step's network part in two calls (csrc/train_runner.hip) ---------------------------------------
  * KPFCNN.forward with a tape, and its backward (ref:lib/trainer.py:216-265 runs ref:models/architectures.py:181-191,
  * 516-610 under torch.autograd).  `model` as for pcrcg_kpfcnn_forward, with these differences in what the fields hold:
- *   kp_w [15*cin, cout] is used as stored (kp_wt, kp_w_pad, mlp_skip are ignored; cin must be 1 or a multiple of 4);
+ *   kp_w [15*cin, cout] is used as stored; for the first block cin is its cin_pad when that is set (kp_w then holds the
+ *   input channels zero-padded to cin_pad), else its in_dim, and batch.feat_dim must equal it and be 1 or a multiple of 4
+ *   (else PCRCG_EBADARG); kp_wt ([cout, 15*cin] or NULL) only serves the forward contraction; kp_w_pad, mlp_skip are ignored;
  *   gnn[].edge1 / edge2 are the packed [2*cout, cin] = [Wa - Wb ; Wb] form and the attention weights head-major,
  *   exactly as the inference descriptor holds them.
  * `grads` is a second pcrcg_model whose POINTER fields hold, for every weight of `model`, the buffer its gradient is

@@ -221,6 +221,16 @@ struct EnqueueLocks {
 };
 static EnqueueLocks g_enqueue;
 
+// ints the call copies into the caller's h_scratch: the flag word, (P + 2) metadata words for each of the 3 L tables, the L
+// subsampled row counts, the overflow word and the L nb cloud lengths (P = output batches).  The argument checks of
+// pyramid_build_checked (L <= 4 from 3 L <= PCRCG_MAX_REORDER_JOBS, P + 2 <= 16, L nb <= 64) bound it by 254 (L = 4, nb = 14,
+// group = 1): within the 256 ints include/pcrcg.h asks for.
+constexpr int kHostScratchInts = 256;
+static int host_scratch_ints(int nb, const pcrcg_pyramid_cfg* cfg) {
+    const int L = cfg->n_levels, P = cfg->group > 0 ? nb / cfg->group : 1;
+    return 1 + (P + 2) * 3 * L + L + 1 + L * nb;
+}
+
 static int pyramid_run(const Parts& in, int n0, int nb, const pcrcg_pyramid_cfg* cfg, Arena& A,
                        int* h_scratch, pcrcg_batch* out, int* h_lengths, int* h_status, pcrcg_pyramid_restore* deferred,
                        hipStream_t st, std::unique_lock<std::mutex>* enqueue = nullptr) {
@@ -418,7 +428,7 @@ static int pyramid_run(const Parts& in, int n0, int nb, const pcrcg_pyramid_cfg*
 
     // ---- the ONE round trip of the call: column counts, capacity status, rows holding ties, row counts, cloud lengths ----
     const int nt = (int)tables.size();
-    const int meta_words = MS * max_tables + L + 1;
+    const int meta_words = MS * max_tables + L + 1;       // (+ the flag and the L nb lengths: host_scratch_ints)
     PCRCG_PROPAGATE(fetch(h_scratch, metas, meta_words, lens_all, L * nb, st, enqueue));
     // whatever follows on `st` (the reorder step, the caller's readers, a second attempt in the same arena) comes after the forests
     if (forests_done) PCRCG_CHECK_HIP(hipStreamWaitEvent(st, forests_done, 0));
@@ -619,6 +629,7 @@ static int pyramid_build_checked(const Parts& in, int n0, int nb, const pcrcg_py
     PCRCG_CHECK_ARG(cfg->n_levels >= 1 && cfg->n_levels <= PCRCG_MAX_LEVELS && 3 * cfg->n_levels <= PCRCG_MAX_REORDER_JOBS);
     for (int l = 0; l < cfg->n_levels; ++l)
         PCRCG_CHECK_ARG(cfg->limit[l] >= 1 && cfg->r_conv[l] > 0.f && (l + 1 == cfg->n_levels || (cfg->dl[l] > 0.f && cfg->r_pool[l] > 0.f)));
+    PCRCG_CHECK_ARG(host_scratch_ints(nb, cfg) <= kHostScratchInts);     // (implied by the checks above; kept next to them)
     Arena A(ws, ws_bytes, false);
     hipStream_t st = as_stream(stream);
     const double t0 = g_trace.on ? now_us() : 0.0, w0 = g_trace.wait;

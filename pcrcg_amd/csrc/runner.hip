@@ -355,6 +355,14 @@ bool linear_norm(Ctx& c, const Mat& x, Stat* xs, float slope, const float* w, in
 
 struct Batches { const pcrcg_batch* b[GMAX]; };
 
+// input channels of the block's KPConv as the gather kernel sees them (padded to a multiple of 4)
+int kp_cin(const pcrcg_block& blk, const Mat& x) { return (blk.kp_w_pad && blk.cin_pad > x.cols) ? blk.cin_pad : x.cols; }
+// the k-major weights [15 * kp_cin, cout] that match those channels: the zero-padded copy whenever the gather sees cin_pad
+// of them -- features padded by kpconv() below (x.cols < cin_pad) or handed over padded by the caller (x.cols == cin_pad)
+const float* kp_weight(const pcrcg_block& blk, const Mat& x) {
+    return (blk.kp_w_pad && blk.cin_pad > 0 && kp_cin(blk, x) == blk.cin_pad) ? blk.kp_w_pad : blk.kp_w;
+}
+
 void kpconv(Ctx& c, const Batches& B, const pcrcg_block& blk, const Mat& x, const Mat& y, Stat* st = nullptr,
             void* const* packed_ws = nullptr) {
     const int l = blk.layer;
@@ -363,10 +371,9 @@ void kpconv(Ctx& c, const Batches& B, const pcrcg_block& blk, const Mat& x, cons
     // features + zero-padded weights, so that the MFMA gather kernel applies (zeros change neither the sums nor
     // the neighbour count of the normaliser)
     Mat xin = x;
-    const float* w = blk.kp_w;
-    int cin = x.cols;
-    if (blk.kp_w_pad && blk.cin_pad > x.cols) {
-        cin = blk.cin_pad;
+    const float* const w = kp_weight(blk, x);
+    const int cin = kp_cin(blk, x);
+    if (cin > x.cols) {
         xin = c.mat(x.rows, cin);
         if (c.live())
             for (int g = 0; g < c.G; ++g) {
@@ -374,7 +381,6 @@ void kpconv(Ctx& c, const Batches& B, const pcrcg_block& blk, const Mat& x, cons
                                                                                                                    : PCRCG_ELAUNCH);
                 c.check(pcrcg_copy2d(x.p[g], x.ld, xin.p[g], cin, x.rows[g], x.cols, c.st));
             }
-        w = blk.kp_w_pad;
     }
     int nq[GMAX], ns[GMAX];
     const float* q[GMAX];
@@ -451,8 +457,6 @@ void kpconv(Ctx& c, const Batches& B, const pcrcg_block& blk, const Mat& x, cons
     c.release(m);
 }
 
-// input channels of the block's KPConv as the gather kernel sees them (padded to a multiple of 4)
-int kp_cin(const pcrcg_block& blk, const Mat& x) { return (blk.kp_w_pad && blk.cin_pad > x.cols) ? blk.cin_pad : x.cols; }
 // length of a wf row (the contraction's K)
 int kp_k(const pcrcg_block& blk, const Mat& x) {
     return (x.cols == 1 && blk.kp_wt && debug_opts().c1_rows16) ? 16 : PCRCG_KPOINTS * kp_cin(blk, x);
@@ -998,6 +1002,13 @@ int validate(const pcrcg_model* m, const pcrcg_batch* b) {
     PCRCG_CHECK_ARG(b->len_src_c >= 1 && b->len_src_c < b->n_points[b->n_levels - 1]);
     PCRCG_CHECK_ARG(m->heads >= 1 && m->gnn_dim % m->heads == 0 && m->temperature > 0.0f);
     for (int i = 0; i < m->n_enc; ++i) PCRCG_CHECK_ARG(m->enc[i].layer >= 0 && m->enc[i].layer + m->enc[i].strided < b->n_levels);
+    // the first KPConv reads the features with their own width: the block's in_dim, or the cin_pad its kp_w_pad holds
+    const pcrcg_block& b0 = m->enc[0];
+    if (b->feat_dim != b0.in_dim && !(b0.kp_w_pad && b0.cin_pad > 0 && b->feat_dim == b0.cin_pad)) {
+        set_error("pcrcg_kpfcnn_forward: bad argument: batch feat_dim %d is neither the first block's in_dim %d nor its cin_pad %d "
+                  "(with kp_w_pad)", b->feat_dim, b0.in_dim, b0.kp_w_pad ? b0.cin_pad : 0);
+        return PCRCG_EBADARG;
+    }
     return PCRCG_OK;
 }
 

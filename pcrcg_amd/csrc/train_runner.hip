@@ -657,6 +657,16 @@ int validate(const pcrcg_model* m, const pcrcg_model* g, const pcrcg_batch* b) {
         PCRCG_CHECK_ARG(m->enc[i].layer >= 0 && m->enc[i].layer + m->enc[i].strided < b->n_levels);
         PCRCG_CHECK_ARG(m->enc[i].kp && m->enc[i].kp_w);
     }
+    // the first KPConv contracts the features against kp_w as stored: the features have the width kp_w was given -- cin_pad
+    // when the caller declares one (its kp_w then holds the zero-padded channels), else in_dim -- and that width is 1 or a
+    // multiple of 4 (include/pcrcg_train.h)
+    const pcrcg_block& b0 = m->enc[0];
+    const int cin = b0.cin_pad > 0 ? b0.cin_pad : b0.in_dim;
+    if (b->feat_dim != cin || (cin != 1 && cin % 4 != 0)) {
+        set_error("pcrcg_kpfcnn_train: bad argument: batch feat_dim %d, first block in_dim %d / cin_pad %d (kp_w holds %d input "
+                  "channels; 1 or a multiple of 4)", b->feat_dim, b0.in_dim, b0.cin_pad, cin);
+        return PCRCG_EBADARG;
+    }
     return PCRCG_OK;
 }
 

@@ -154,6 +154,7 @@ class TrainRunner:
                 ix = torch.full((kk, cp, cout), -1, dtype=torch.int32, device=dev)
                 ix[:, :cin] = index_of(kp.weights)
                 derived(bv, bg, "kp_w", kp.weights, ix)
+                bv.cin_pad = cp                     # the width kp_w holds and the features must have
                 derived(bv, bg, "kp_wt", kp.weights, ix.reshape(kk * cp, cout).t().contiguous(), with_grad=False)
                 return
             direct(bv, bg, "kp_w", kp.weights, lambda t: t.reshape(-1, t.shape[-1]))

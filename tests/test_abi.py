@@ -4,6 +4,8 @@ import ctypes
 import os
 import re
 
+import pytest
+
 from pcrcg_amd import _lib
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -93,3 +95,61 @@ def test_pyramid_workspace_follows_the_row_bound():
     assert 0 < sizes[0.25] < sizes[0.5] < sizes[1.0]
     assert sizes[0.0] == sizes[1.0] == sizes[7.0]
     assert lib.pcrcg_pyramid_ws_bytes(60000, 0, ctypes.byref(c)) == 0
+
+
+def _descriptors_with_a_129_channel_first_block(feat_dim):
+    """A model / batch pair that passes every other argument check: one encoder block whose KPConv declares in_dim = 129
+    with a zero-padded copy of cin_pad = 132 (PCR-CG's image input), fake non-null device pointers (nothing launches)."""
+    from pcrcg_amd.runner import BLK_LAST_UNARY, BLK_SIMPLE, Batch, Model, Outputs
+    fake = ctypes.c_void_p(4096)
+    m = Model()
+    m.n_enc, m.n_dec, m.n_gnn = 1, 1, 0
+    e = m.enc[0]
+    e.type, e.layer, e.strided, e.in_dim, e.out_dim, e.mid_dim, e.extent = BLK_SIMPLE, 0, 0, 129, 32, 32, 0.06
+    e.kp, e.kp_w, e.kp_wt, e.kp_w_pad, e.cin_pad = fake, fake, fake, fake, 132
+    d = m.dec[0]
+    d.type, d.in_dim, d.out_dim, d.mlp, d.mlp_ld = BLK_LAST_UNARY, 34, 34, fake, 36
+    m.enc_out_dim, m.gnn_dim, m.heads, m.knn_k, m.final_dim, m.temperature = 32, 32, 4, 10, 32, 1.03
+    b = Batch()
+    b.n_levels = 1
+    b.points[0], b.n_points[0] = fake, 100
+    b.features, b.feat_dim, b.len_src_c = fake, feat_dim, 50
+    return m, b, Outputs(fake, fake, fake)
+
+
+@pytest.mark.parametrize("feat_dim", [1, 128, 130])
+def test_feature_width_must_match_the_first_block(feat_dim):
+    """batch.feat_dim is the width the first KPConv reads: its in_dim, or the cin_pad of its kp_w_pad (include/pcrcg.h).
+    Any other width is rejected by the size queries and the forward entry points before anything launches (a wider
+    matrix would have been read against weights of another row length)."""
+    lib = _lib.lib()
+    m, b, o = _descriptors_with_a_129_channel_first_block(feat_dim)
+    assert lib.pcrcg_kpfcnn_ws_bytes(ctypes.byref(m), ctypes.byref(b)) == 0
+    assert b"feat_dim" in lib.pcrcg_last_error()
+    assert lib.pcrcg_kpfcnn_group_ws_bytes(ctypes.byref(m), ctypes.byref(b), 1) == 0
+    assert lib.pcrcg_kpfcnn_forward(ctypes.byref(m), ctypes.byref(b), ctypes.byref(o), ctypes.c_void_p(4096), 1 << 30,
+                                    None) == -1
+    assert b"feat_dim" in lib.pcrcg_last_error()
+    two = (type(b) * 2)(b, b)
+    outs = (type(o) * 2)(o, o)
+    assert lib.pcrcg_kpfcnn_forward_group(ctypes.byref(m), two, outs, 2, ctypes.c_void_p(4096), 1 << 30, None) == -1
+    assert b"feat_dim" in lib.pcrcg_last_error()
+
+
+@pytest.mark.parametrize("feat_dim", [1, 128, 129, 130])
+def test_train_step_feature_width_must_match_its_kp_w(feat_dim):
+    """The train-step runner contracts the features against kp_w as stored (include/pcrcg_train.h): a first block that
+    declares cin_pad = 132 holds kp_w in 132-channel rows, so only 132-wide features are accepted -- the 129-wide ones too
+    are refused rather than read against rows of another length."""
+    from pcrcg_amd.train_runner import TrainOutputs
+    lib = _lib.lib()
+    m, b, _ = _descriptors_with_a_129_channel_first_block(feat_dim)
+    g = type(m).from_buffer_copy(m)
+    sizes = [ctypes.c_size_t() for _ in range(3)]
+    assert lib.pcrcg_kpfcnn_train_ws_bytes(ctypes.byref(m), ctypes.byref(g), ctypes.byref(b),
+                                           *[ctypes.byref(s) for s in sizes]) == -1
+    assert b"feat_dim" in lib.pcrcg_last_error()
+    out, tape = TrainOutputs(), ctypes.c_void_p()
+    assert lib.pcrcg_kpfcnn_train_forward(ctypes.byref(m), ctypes.byref(g), ctypes.byref(b), ctypes.c_void_p(4096), 1 << 20,
+                                          1 << 20, 1 << 20, ctypes.byref(out), ctypes.byref(tape), None) == -1
+    assert b"feat_dim" in lib.pcrcg_last_error() and not tape.value
