@@ -57,15 +57,8 @@ int pcrcg_abi_version(void);
  * the defaults, or what PCRCG_DEBUG made of them).  The same string is
  * read once from the environment variable PCRCG_DEBUG at first use; nothing else in the library reads the environment
  * except PCRCG_GEMM_MODE (pcrcg_gemm_set_mode).  Every switch defaults to the product behaviour:
- *   zero_arena=1 stat_sums=1 stat_sums_rows=2^30 fuse_norm=1 fuse_pack=1 fuse_upsample=1 gnn_merge=1 edge_rows=1 att_mfma=1 c1_rows16=1   network runner fusions
- *                  (gnn_merge: the source and target clouds of a self-attention layer through one pass and both query
- *                  projections of a cross layer in one launch -- applies to forward calls of ONE or TWO pairs: the merged
- *                  pass holds 2 x pairs clouds and the multi-cloud kernels take four; with four pairs per call the two
- *                  sides run as two passes of four clouds.  The fused key / value projection and the once-per-forward kNN
- *                  graphs apply at every group size.)
- *   radius_blocks=0 radius_eager_redo=0 radius_cells=1 radius_prof=0 pyr_wait=1 pyr_trace=0 kd_spin_limit=0 kd_blocks=0   front end
- *   pyr_morton=0   1: MEASUREMENT AID -- every subsampled level sorted along a Z curve before anything reads it; the level rows
- *                  are then not the reference's (a knock-out that prices an internal spatial order: csrc/morton_knock.hip)
+ *   stat_sums=1 stat_sums_rows=2^30 att_mfma=1                                             network runner
+ *   radius_blocks=0 kd_spin_limit=0 kd_blocks=0                                            front end
  *   att_tq=16                                                                              attention tile
  *   gemm_log=0 x6_tile=-1 x6_splitk=0 x6_t1=1 x6_t2=1 x6_order=-1 x6_big=0 x6_h2=1 gemm_tile=-1 gemm_splitk=0 gemm_split_target=768   GEMM plans
  *   train_side_stream=1 bwd_mfma=1                                                         train-step backward
@@ -73,7 +66,8 @@ int pcrcg_abi_version(void);
  *                      split order by a second pass, InstanceNorm statistics from stored partials, fixed-point scatter sums
  *                      in the train step); implies stat_sums=0 gemm_splitk=1; allocates its scratch itself.  Together with a fixed pairing of the pair engine (PairStreams(adaptive_jobs=False))
  *                      outputs are a function of the inputs alone.
- * Returns PCRCG_EBADARG (and changes nothing) on an unknown name. */
+ * Returns PCRCG_EBADARG (and changes nothing) on an unknown name.  A switch that has been retired -- its default is now the
+ * only behaviour, or its measurement aid is gone (DESIGN.md section 5 names them) -- is an unknown name like any other. */
 int pcrcg_debug_set(const char* spec);
 /* deterministic=1 allocates its scratch itself (partial tiles of split-K products, 64-bit fixed-point sums of the train
  * step's scatters): one buffer per stream it has run on, keyed by the stream handle, grown on demand and kept until the
@@ -575,7 +569,7 @@ int pcrcg_kpfcnn_forward_group(const pcrcg_model* model, const pcrcg_batch* batc
  *              sizes every buffer, table and launch of the level.  A cloud that keeps more rows than the bound allows is
  *              reported as PCRCG_EWORKSPACE at the end of the call -- nothing is corrupted, call again with a larger
  *              shrink (and the arena that goes with it).
- *   h_scratch  HOST scratch of >= 256 ints, pinned for best latency: the call writes 2 + 3 n_levels (P + 2) + n_levels
+ *   h_scratch  HOST scratch of >= 256 ints, pinned for best latency: the call uses 2 + 3 n_levels (P + 2) + n_levels
  *              + n_levels nb of them (P = nb / group, or 1), at most 254 under the argument checks (n_levels <= 4,
  *              P <= 14, n_levels nb <= 64), and rejects anything above 256; h_lengths HOST [n_levels * nb] receives the
  *              per-level cloud lengths (stack_lengths); h_status HOST int (pinned; may be NULL) receives the tie-order

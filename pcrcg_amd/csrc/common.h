@@ -51,10 +51,6 @@ int instnorm_apply_pack(const float* x, int n, int c, int ldx, const float* stat
 // kpconv.hip: where the support records live inside a pcrcg_kpconv_ws_bytes(ns) workspace
 float4* kpconv_pk_ptr(void* ws, size_t ws_bytes, int ns);
 
-// morton_knock.hip (measurement aid, DebugOpts::pyr_morton): a subsampled level's rows into Z order, in place
-size_t morton_knock_ws_bytes(int cap);
-int morton_knock_level(float* pts, int cap, const int* len, int nb, void* ws, size_t ws_bytes, hipStream_t st);
-
 // the deterministic debug mode's scratch (gemm_x6.hip, trainops.hip): freed by pcrcg_debug_release()
 void gemm_x6_release_det();
 void trainops_release_det();
@@ -168,28 +164,11 @@ int attention_bwd_mfma(const float* q, int ldq, const float* k, int ldk, const f
 // syntax) -- include/pcrcg.h lists the names.  Nothing else in csrc/ reads the environment, except PCRCG_GEMM_MODE
 // (the documented arithmetic selector, pcrcg_gemm_set_mode).
 struct DebugOpts {
-    int zero_arena = 1;        // runner: split-K outputs from one pre-zeroed arena (0: each product clears its own C)
     int stat_sums = 1;         // runner: InstanceNorm statistics as fp64 column sums added by the GEMM epilogues
     int stat_sums_rows = 1 << 30;   //   ... only for outputs of up to that many rows (above: deterministic partials)
-    int fuse_norm = 1;         // runner: normalise-on-load inside the consuming product
-    int fuse_pack = 1;         // runner: the normalisation that feeds a KPConv also packs its support records
-    int fuse_upsample = 1;     // runner: nearest_upsample -> cat(skip) -> unary as two products into one output
-    int knock_tail = 0;        // MEASUREMENT AID (wrong results): resnet blocks of layers < knock_tail skip the shortcut product and its half of the closing pass -- the traffic a fused block tail would save
-    int c1_rows16 = 1;         // runner: the first layer's (cin = 1) aggregate in rows of 16 floats, its contraction the grouped A B^T
-                               // product with epilogue statistics (round 6); 0: rows of 15, one k-major launch per pair + a column-sum pass
-    int gnn_merge = 1;         // runner: source and target clouds of a self-attention layer through ONE pass (round 5); needs
-                               // 2 x pairs <= 4 clouds per launch, i.e. forward calls of one or two pairs (include/pcrcg.h)
-    int edge_rows = 1;         // edge convolution: the row-parallel multi-cloud kernel (0: the per-cloud chunked kernel)
     int att_mfma = 1;          // attention: the fp32-MFMA kernel, all clouds of a call in one launch (0: the VALU kernel per cloud)
     int radius_blocks = 0;     // radius search grid (0: 512 workgroups)
-    int radius_eager_redo = 0; // pyramid builder: launch the >256-hit redo pass unconditionally
     int kd_blocks = 0;
-    int radius_prof = 0;       // cell-cooperative search: per-phase shader-cycle counters, printed at exit (measurement aid)
-    int radius_cells = 1;      // pyramid builder: cell-cooperative LDS-staged search (0: the per-query kernel of rounds 1-3)
-    int pyr_wait = 1;          // pyramid builder host round trip: 0 stream sync, 1 event, 2 device-posted flag
-    int pyr_trace = 0;         // pyramid builder: host enqueue / wait microseconds at exit
-    int pyr_morton = 0;        // MEASUREMENT AID: every subsampled level sorted along a Z curve before anything reads it (the level
-                               // rows are then not the reference's: a knock-out that prices an internal spatial order, morton_knock.hip)
     int att_tq = 16;           // attention kernel: queries per workgroup (8 or 16)
     int kd_spin_limit = 0;     // KD-forest task queue: spin bound (0: default)
     int gemm_log = 0;          // print every GEMM's shape and grid

@@ -885,7 +885,7 @@ __global__ void __launch_bounds__(256) k_softmax_matvec(const float* __restrict_
 
 // the layout rules of k_edgeconv_rows: four channels per lane as one 16-byte access, the row's indices on one wavefront
 bool edgeconv_rows_ok(const EdgeCloud* cl, int count, int ld_ctr, int ld_nbr, int ld_emax, int c) {
-    if (!debug_opts().edge_rows || count < 1 || count > 4 || c % 4 != 0 || ld_ctr % 4 != 0 || ld_nbr % 4 != 0 || ld_emax % 4 != 0) return false;
+    if (count < 1 || count > 4 || c % 4 != 0 || ld_ctr % 4 != 0 || ld_nbr % 4 != 0 || ld_emax % 4 != 0) return false;
     for (int i = 0; i < count; ++i) {
         if (cl[i].k < 1 || cl[i].k > 64 || cl[i].n < 1) return false;
         if ((reinterpret_cast<uintptr_t>(cl[i].ctr) | reinterpret_cast<uintptr_t>(cl[i].nbr) | reinterpret_cast<uintptr_t>(cl[i].emax)) & 15)

@@ -16,7 +16,6 @@
 // so nothing is concatenated later --, lengths [levels][nb], features, tables, per-table counts / tie rows, cell
 // grids), transient subsampling scratch with stack discipline.  Everything the returned pcrcg_batch points to lives
 // in the arena (except level 0's points when they are used in place).
-#include <sched.h>
 #include <time.h>
 
 #include <cmath>
@@ -28,32 +27,6 @@
 namespace pcrcg {
 namespace {
 
-// Host round trip, three ways (DebugOpts::pyr_wait): 0 = async copy + hipStreamSynchronize, 1 = async copy + event (default:
-// waits for the caller's own work only, so several host threads can share one stream),
-// 2 = a one-wavefront kernel stores the words straight into the caller's pinned scratch (system-scope release of a
-// sequence tag last) and the host polls the tag -- no runtime call, no runtime lock held while waiting.
-__global__ void k_post(int* __restrict__ h_dst, const int* __restrict__ src, int n, const int* __restrict__ src2, int n2,
-                       int tag) {
-    for (int i = threadIdx.x; i < n; i += 64) __hip_atomic_store(h_dst + 1 + i, src[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    for (int i = threadIdx.x; i < n2; i += 64)
-        __hip_atomic_store(h_dst + 1 + n + i, src2[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
-    __syncthreads();
-    if (threadIdx.x == 0) __hip_atomic_store(h_dst, tag, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
-// DebugOpts::pyr_trace = 1: host microseconds spent enqueueing vs waiting, per call, printed at exit (tuning aid)
-struct Trace {
-    bool on = debug_opts().pyr_trace != 0;
-    double enq = 0, wait = 0;
-    long calls = 0, waits = 0;
-    ~Trace() {
-        if (on && calls)
-            fprintf(stderr, "pcrcg_pyramid_build: %ld calls, per call: enqueue %.1f us, waiting %.1f us in %.1f round trips\n",
-                    calls, enq / calls, wait / calls, (double)waits / calls);
-    }
-};
-Trace g_trace;
 inline double now_us() {
     timespec ts;
     clock_gettime(CLOCK_MONOTONIC, &ts);
@@ -76,53 +49,20 @@ __global__ void k_probe_tiny(int* sink) {
     if (threadIdx.x == 1234567) sink[1] = 1;
 }
 
-int wait_mode() {
-    return debug_opts().pyr_wait;
-}
-
-// words src[0..n) (+ src2[0..n2)) -> h_scratch[1..]; returns when they are there
-// (`enqueue`: the stream's enqueue lock held by the caller, released once the transfer is in the stream, before the wait)
-int fetch_(int* h_scratch, const int* src, int n, const int* src2, int n2, hipStream_t st, std::unique_lock<std::mutex>* enqueue);
+// words src[0..n) (+ src2[0..n2)) -> h_scratch[1..]: async copies and an event on the stream, so the call waits for its
+// own work only and several host threads can share one stream.  Returns when the words are there.  (`enqueue`: the
+// stream's enqueue lock held by the caller, released once the transfer is in the stream, before the wait.)
 int fetch(int* h_scratch, const int* src, int n, const int* src2, int n2, hipStream_t st,
           std::unique_lock<std::mutex>* enqueue = nullptr) {
-    if (!g_trace.on) return fetch_(h_scratch, src, n, src2, n2, st, enqueue);
-    const double t0 = now_us();
-    const int rc = fetch_(h_scratch, src, n, src2, n2, st, enqueue);
-    g_trace.wait += now_us() - t0;      // (racy across threads: a tuning aid)
-    g_trace.waits += 1;
-    return rc;
-}
-int fetch_(int* h_scratch, const int* src, int n, const int* src2, int n2, hipStream_t st, std::unique_lock<std::mutex>* enqueue) {
-    const int mode = wait_mode();
-    auto let_go = [&] { if (enqueue && enqueue->owns_lock()) enqueue->unlock(); };
-    if (mode == 2) {
-        volatile int* flag = h_scratch;
-        const int tag = (*flag & 0x7fffffff) + 1;
-        hipLaunchKernelGGL(k_post, dim3(1), dim3(64), 0, st, h_scratch, src, n, src2, n2, tag);
-        PCRCG_CHECK_LAUNCH();
-        let_go();
-        long spins = 0;
-        while (*flag != tag) {
-            if (++spins > 64) sched_yield();
-            if (spins > 200000000L) { set_error("pcrcg_pyramid_build: device never posted its counts"); return PCRCG_ELAUNCH; }
-        }
-        __sync_synchronize();
-        return PCRCG_OK;
-    }
     PCRCG_CHECK_HIP(hipMemcpyAsync(h_scratch + 1, src, sizeof(int) * n, hipMemcpyDeviceToHost, st));
     if (n2 > 0) PCRCG_CHECK_HIP(hipMemcpyAsync(h_scratch + 1 + n, src2, sizeof(int) * n2, hipMemcpyDeviceToHost, st));
-    if (mode == 1) {
-        hipEvent_t ev;
-        PCRCG_CHECK_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-        hipError_t e = hipEventRecord(ev, st);
-        let_go();
-        if (e == hipSuccess) e = hipEventSynchronize(ev);
-        (void)hipEventDestroy(ev);
-        PCRCG_CHECK_HIP(e);
-    } else {
-        let_go();
-        PCRCG_CHECK_HIP(hipStreamSynchronize(st));      // (waits for everything in the stream: a later call's chain too)
-    }
+    hipEvent_t ev;
+    PCRCG_CHECK_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    hipError_t e = hipEventRecord(ev, st);
+    if (enqueue && enqueue->owns_lock()) enqueue->unlock();
+    if (e == hipSuccess) e = hipEventSynchronize(ev);
+    (void)hipEventDestroy(ev);
+    PCRCG_CHECK_HIP(e);
     return PCRCG_OK;
 }
 
@@ -221,10 +161,10 @@ struct EnqueueLocks {
 };
 static EnqueueLocks g_enqueue;
 
-// ints the call copies into the caller's h_scratch: the flag word, (P + 2) metadata words for each of the 3 L tables, the L
-// subsampled row counts, the overflow word and the L nb cloud lengths (P = output batches).  The argument checks of
-// pyramid_build_checked (L <= 4 from 3 L <= PCRCG_MAX_REORDER_JOBS, P + 2 <= 16, L nb <= 64) bound it by 254 (L = 4, nb = 14,
-// group = 1): within the 256 ints include/pcrcg.h asks for.
+// ints the call uses of the caller's h_scratch: a reserved word (h_scratch[0], not written), (P + 2) metadata words for each
+// of the 3 L tables, the L subsampled row counts, the overflow word and the L nb cloud lengths (P = output batches).  The
+// argument checks of pyramid_build_checked (L <= 4 from 3 L <= PCRCG_MAX_REORDER_JOBS, P + 2 <= 16, L nb <= 64) bound it
+// by 254 (L = 4, nb = 14, group = 1): within the 256 ints include/pcrcg.h asks for.
 constexpr int kHostScratchInts = 256;
 static int host_scratch_ints(int nb, const pcrcg_pyramid_cfg* cfg) {
     const int L = cfg->n_levels, P = cfg->group > 0 ? nb / cfg->group : 1;
@@ -263,7 +203,6 @@ static int pyramid_run(const Parts& in, int n0, int nb, const pcrcg_pyramid_cfg*
     int* tie_status = overflow + 1;
     if (!A.ok()) return PCRCG_EWORKSPACE;
 
-    const bool eager = debug_opts().radius_eager_redo != 0;   // A/B aid
     std::vector<TableRec> tables;
     tables.reserve(max_tables);
     if (!dry) {
@@ -327,7 +266,6 @@ static int pyramid_run(const Parts& in, int n0, int nb, const pcrcg_pyramid_cfg*
                                      last > first ? nb : 0, level_base, forest[slot], forest_b[slot], f_st);
     };
 
-    const bool use_cells = debug_opts().radius_cells != 0;
     // nq / ns are the BOUNDS of the query / support level (grids and tables are carved for them)
     auto add_table = [&](int kind, int level, int q_level, const void* grid, const void* qgrid, float radius, const float* q,
                          const int* qlen, int nq, int ns, const int* slen, int limit, int sup_level) -> int {
@@ -338,17 +276,14 @@ static int pyramid_run(const Parts& in, int n0, int nb, const pcrcg_pyramid_cfg*
         t.ties = want_ties ? A.take<int>((size_t)nq) : nullptr;
         t.meta = metas + MS * tables.size();
         t.q = q; t.qlen = qlen; t.nq = nq; t.limit = limit; t.sup_level = sup_level; t.radius = radius;
-        t.grid = grid; t.ns = ns; t.slen = slen; t.qgrid = use_cells ? qgrid : nullptr;
+        t.grid = grid; t.ns = ns; t.slen = slen; t.qgrid = qgrid;
         if (!A.ok()) return PCRCG_EWORKSPACE;
-        // first pass only: rows with more than 128 hits (kCellListCap; 256 = kListCapFast for the per-query kernel) (and, from the cell-cooperative search, rows of a cell whose
-        // neighbourhood does not fit LDS) are marked and announced in the metadata; whether any table has one is known
+        // first pass only (the cell-cooperative search): rows with more than 128 hits (kCellListCap) and rows of a cell whose
+        // neighbourhood does not fit LDS are marked and announced in the metadata; whether any table has one is known
         // with the metadata round trip below, and only then (normally never) the redo pass runs
-        if (!dry && t.qgrid)
+        if (!dry)
             PCRCG_PROPAGATE(radius_cells_pass(t.qgrid, q, nq, qlen, grid, ns, slen, nb, group, radius, limit, t.idx, t.counts,
-                                              t.meta, t.meta + P, t.ties, want_ties ? t.meta + P + 1 : nullptr, st, eager ? 0 : 1));
-        else if (!dry)
-            PCRCG_PROPAGATE(radius_query_pass(q, nq, qlen, ns, slen, nb, group, radius, grid, limit, t.idx, t.counts, t.meta,
-                                              t.meta + P, t.ties, want_ties ? t.meta + P + 1 : nullptr, st, eager ? 0 : 1));
+                                              t.meta, t.meta + P, t.ties, want_ties ? t.meta + P + 1 : nullptr, st, 1));
         tables.push_back(t);
         return PCRCG_OK;
     };
@@ -364,9 +299,6 @@ static int pyramid_run(const Parts& in, int n0, int nb, const pcrcg_pyramid_cfg*
     // most).  It is NOT handed back to the arena: beside the searches on another stream nothing may share its memory.
     const size_t sub_wsb = L > 1 ? pcrcg_grid_subsample_ws_bytes(cap[0], nb) : 0;
     void* sub_ws = L > 1 ? A.raw(sub_wsb) : nullptr;
-    const bool knock_morton = debug_opts().pyr_morton != 0 && L > 1;       // measurement aid (morton_knock.hip)
-    const size_t mk_wsb = knock_morton ? morton_knock_ws_bytes(cap[1]) : 0;
-    void* mk_ws = knock_morton ? A.raw(mk_wsb) : nullptr;
     if (!A.ok()) return PCRCG_EWORKSPACE;
 
     void* carried = nullptr;
@@ -391,8 +323,6 @@ static int pyramid_run(const Parts& in, int n0, int nb, const pcrcg_pyramid_cfg*
         if (pooled && !dry)
             PCRCG_PROPAGATE(grid_subsample_bound(pts, n, lens, nb, cfg->dl[l], 0, level_pts[l + 1], lens + nb, m_dev + l, cap[l + 1],
                                                  overflow, sub_ws, sub_wsb, sub_st));
-        if (pooled && !dry && knock_morton)
-            PCRCG_PROPAGATE(morton_knock_level(level_pts[l + 1], cap[l + 1], lens + nb, nb, mk_ws, mk_wsb, sub_st));
         if (pooled && l + 2 == L) PCRCG_PROPAGATE(build_forest(one_forest ? 2 : 1));      // the last subsampled level exists
         if (cfg->has_conv[l]) {
             if (carried && carried_r == r_conv) { grid = carried; grid_r = carried_r; }
@@ -428,7 +358,7 @@ static int pyramid_run(const Parts& in, int n0, int nb, const pcrcg_pyramid_cfg*
 
     // ---- the ONE round trip of the call: column counts, capacity status, rows holding ties, row counts, cloud lengths ----
     const int nt = (int)tables.size();
-    const int meta_words = MS * max_tables + L + 1;       // (+ the flag and the L nb lengths: host_scratch_ints)
+    const int meta_words = MS * max_tables + L + 1;       // (+ the reserved word and the L nb lengths: host_scratch_ints)
     PCRCG_PROPAGATE(fetch(h_scratch, metas, meta_words, lens_all, L * nb, st, enqueue));
     // whatever follows on `st` (the reorder step, the caller's readers, a second attempt in the same arena) comes after the forests
     if (forests_done) PCRCG_CHECK_HIP(hipStreamWaitEvent(st, forests_done, 0));
@@ -450,7 +380,7 @@ static int pyramid_run(const Parts& in, int n0, int nb, const pcrcg_pyramid_cfg*
             int widest = 0;
             for (int p = 0; p < P; ++p) widest = hm[MS * i + p] > widest ? hm[MS * i + p] : widest;
             const bool handed_over = (hm[MS * i + P] & kRadiusRedoStatus) != 0;     // (the redo pass clears the bit)
-            if ((widest <= radius_fast_cap() && !handed_over) || eager) continue;
+            if (widest <= radius_fast_cap() && !handed_over) continue;
             const TableRec& t = tables[i];
             PCRCG_PROPAGATE(radius_query_pass(t.q, t.nq, t.qlen, t.ns, t.slen, nb, group, t.radius, t.grid, t.limit, t.idx,
                                               t.counts, t.meta, t.meta + P, t.ties, want_ties ? t.meta + P + 1 : nullptr, st,
@@ -632,10 +562,8 @@ static int pyramid_build_checked(const Parts& in, int n0, int nb, const pcrcg_py
     PCRCG_CHECK_ARG(host_scratch_ints(nb, cfg) <= kHostScratchInts);     // (implied by the checks above; kept next to them)
     Arena A(ws, ws_bytes, false);
     hipStream_t st = as_stream(stream);
-    const double t0 = g_trace.on ? now_us() : 0.0, w0 = g_trace.wait;
     std::unique_lock<std::mutex> enqueue(*g_enqueue.of(st));
     const int rc = pyramid_run(in, n0, nb, cfg, A, h_scratch, out, h_lengths, h_status, deferred, st, &enqueue);
-    if (g_trace.on) { g_trace.enq += now_us() - t0 - (g_trace.wait - w0); g_trace.calls += 1; }
     if (rc == PCRCG_EWORKSPACE)
         if (A.off > ws_bytes) set_error("pcrcg_pyramid_build: arena too small (%zu needed so far, %zu given): size it with pcrcg_pyramid_ws_bytes for this cfg", A.off, ws_bytes);
     return rc;

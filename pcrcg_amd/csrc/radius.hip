@@ -477,7 +477,6 @@ struct CellArgs {
     double reach;
     float r2;
     int nb, cols, group;
-    long long* prof;              // measurement aid (PROF kernels only)
 };
 
 struct CellState {                // what wave 0 hands to the other waves of the workgroup, per cell
@@ -488,7 +487,7 @@ struct CellState {                // what wave 0 hands to the other waves of the
 // workgroup barrier that waits for this wave's LDS operations only (global loads / stores stay in flight)
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
-template <int SC, int CAP, int WAVES, bool PROF = false>
+template <int SC, int CAP, int WAVES>
 __global__ void __launch_bounds__(WAVES * 64) k_radius_cells(const CellArgs a) {
     __shared__ float4 s_cand[SC];                    // (SC is a multiple of 64: the padded tail of the last step fits)
     __shared__ float4 s_q[kCellQ];
@@ -500,17 +499,6 @@ __global__ void __launch_bounds__(WAVES * 64) k_radius_cells(const CellArgs a) {
     __shared__ int s_tie[kCellTieCap];
     __shared__ CellState s_state;
     __shared__ int s_ntie, s_tie_base;
-    // PROF (measurement aid, DebugOpts::radius_prof): shader-clock cycles per phase, summed over wavefronts
-    int pcells = 0, pqueries = 0;
-    long long pt[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    long long pt_last = PROF ? (long long)__builtin_readcyclecounter() : 0;
-    auto stamp = [&](int phase) {
-        if (PROF) {
-            const long long now = (long long)__builtin_readcyclecounter();
-            pt[phase] += now - pt_last;
-            pt_last = now;
-        }
-    };
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int cols = a.cols;
     const float r2 = a.r2;
@@ -572,7 +560,6 @@ __global__ void __launch_bounds__(WAVES * 64) k_radius_cells(const CellArgs a) {
             }
         }
         lds_barrier();                               // A: the cell's state is out; the previous cell's readers are done
-        stamp(0);
         if (!s_state.more) break;
         nqc = s_state.nqc;
         qstart = s_state.qstart;
@@ -631,7 +618,6 @@ __global__ void __launch_bounds__(WAVES * 64) k_radius_cells(const CellArgs a) {
         }
         if (WAVES == 1 && lane < kCellQ && lane < nqc) s_q[lane] = a.qspts[qstart + lane];
         lds_barrier();                               // B
-        stamp(1);
         const int total = s_state.total, log2p = s_state.log2p;
         const bool fits = s_state.fits != 0;
         if (fits) {
@@ -641,14 +627,12 @@ __global__ void __launch_bounds__(WAVES * 64) k_radius_cells(const CellArgs a) {
             if ((int)threadIdx.x < 64 && total + (int)threadIdx.x < ((total + 63) & ~63))      // far-away tail: never a hit
                 s_cand[total + threadIdx.x] = make_float4(3.0e18f, 3.0e18f, 3.0e18f, 0.0f);
         }
-        stamp(2);
         for (int q0 = 0; q0 < nqc; q0 += kCellQ) {
             if (q0 > 0) {
                 lds_barrier();
                 if ((int)threadIdx.x < kCellQ && q0 + (int)threadIdx.x < nqc) s_q[threadIdx.x] = a.qspts[qstart + q0 + threadIdx.x];
             }
             lds_barrier();                           // C
-            stamp(3);
             const int nbatch = min(kCellQ, nqc - q0);
             for (int k = wave; k < nbatch; k += WAVES) {
                 const float4 qr = s_q[k];
@@ -680,8 +664,6 @@ __global__ void __launch_bounds__(WAVES * 64) k_radius_cells(const CellArgs a) {
                     idx[pos] = __float_as_int(p.w);
                     nhit += __builtin_popcountll(mask);
                 }
-                stamp(4);
-                if (PROF) ++pqueries;
                 wave_max = nhit > wave_max ? nhit : wave_max;
                 if (nhit > CAP) {                    // leave the row to pass 2
                     if (lane == 0) { row[0] = kRedoMark; if (a.status) atomicOr(a.status, kRedoStatus); }
@@ -735,7 +717,6 @@ __global__ void __launch_bounds__(WAVES * 64) k_radius_cells(const CellArgs a) {
                         idx[dst] = midx;
                     }
                     __builtin_amdgcn_wave_barrier();
-                    stamp(5);
                     // the row: lane e writes column e
                     const int e = lane < CAP ? lane : 0;
                     const unsigned ke = key[e], kn = key[e + 1];
@@ -753,7 +734,6 @@ __global__ void __launch_bounds__(WAVES * 64) k_radius_cells(const CellArgs a) {
                     }
                     if (a.out_count) a.out_count[qi] = nhit;    // (every lane, one address, one value)
                     __builtin_amdgcn_wave_barrier();
-                    stamp(6);
                     continue;
                 }
                 // ---- rank sort (rows of 65..CAP hits, tables of more than 64 columns); the sorted hits go back in place ----
@@ -818,7 +798,6 @@ __global__ void __launch_bounds__(WAVES * 64) k_radius_cells(const CellArgs a) {
                         if (lane + 64 * u < nl) { key[rank[u]] = mk[u]; idx[rank[u]] = mi[u]; }
                 }
                 __builtin_amdgcn_wave_barrier();
-                stamp(5);
                 bool tie = false;
                 for (int e = lane; e < cols; e += 64) {
                     long long vout = (long long)ns_out;
@@ -835,7 +814,6 @@ __global__ void __launch_bounds__(WAVES * 64) k_radius_cells(const CellArgs a) {
                 }
                 if (lane == 0 && a.out_count) a.out_count[qi] = nhit;
                 __builtin_amdgcn_wave_barrier();
-                stamp(6);
             }
         }
         if (wave == 0) {                             // next cell: its record and the ticket behind it have arrived meanwhile
@@ -843,13 +821,6 @@ __global__ void __launch_bounds__(WAVES * 64) k_radius_cells(const CellArgs a) {
             rec = rec1;
             c1 = __builtin_amdgcn_readfirstlane(ticket);
         }
-        stamp(7);
-        if (PROF) ++pcells;
-    }
-    if (PROF && lane == 0 && a.prof) {
-        for (int k = 0; k < 8; ++k) atomicAdd(reinterpret_cast<unsigned long long*>(a.prof) + k, (unsigned long long)pt[k]);
-        atomicAdd(reinterpret_cast<unsigned long long*>(a.prof) + 8, (unsigned long long)pcells);
-        atomicAdd(reinterpret_cast<unsigned long long*>(a.prof) + 9, (unsigned long long)pqueries);
     }
     flush_max();
     __syncthreads();
@@ -1132,36 +1103,13 @@ int radius_cells_pass(const void* qgrid, const float* q, int nq, const int* qlen
     ca.out_idx = reinterpret_cast<long long*>(out_idx); ca.out_count = out_count; ca.out_max = out_max_count;
     ca.status = status; ca.tie_rows = out_tie_rows; ca.tie_count = out_tie_count;
     ca.reach = reach; ca.r2 = r2; ca.nb = nb; ca.cols = cols; ca.group = group;
-    ca.prof = nullptr;
     // The ticket block lives in the QUERY grid and cleans itself (the last workgroup of a shard to leave zeroes it), which
     // is enough for the pyramid builder: it owns its grids, rebuilds them per call and walks them on one stream.  A caller
     // of the public entry point may have aborted an earlier walk or may hand over a grid some other walk left mid-way, so
     // here the block is reset on the launch stream first (4 KB; walks of ONE query grid must still not overlap in time:
     // include/pcrcg.h, and pcrcg_amd/ops.py orders them by event).
     if (pass != 1) PCRCG_CHECK_HIP(hipMemsetAsync(gq.qtick, 0, 16 * kTickStride * sizeof(int), st));
-    if (debug_opts().radius_prof) {       // measurement aid: per-phase shader cycles, printed when the process exits
-        static long long* prof = nullptr;
-        if (!prof) {
-            (void)hipMalloc(&prof, 16 * sizeof(long long));
-            (void)hipMemset(prof, 0, 16 * sizeof(long long));
-            static struct Dump {
-                ~Dump() {
-                    long long h[16];
-                    if (hipMemcpy(h, prof, sizeof(h), hipMemcpyDeviceToHost) != hipSuccess) return;
-                    static const char* nm[8] = {"barrier A (state out, previous readers done)", "probes | query staging, barrier B",
-                                                "candidate staging", "barrier C", "sweep", "rank sort", "row store", "hand-over"};
-                    fprintf(stderr, "k_radius_cells: %lld wave-cells, %lld queries\n", h[8], h[9]);
-                    double tot = 0;
-                    for (int k = 0; k < 8; ++k) tot += (double)h[k];
-                    for (int k = 0; k < 8; ++k)
-                        fprintf(stderr, "k_radius_cells phase %d %-46s %6.2f %%  %9.0f cycles per %s\n", k, nm[k], 100.0 * h[k] / (tot > 0 ? tot : 1),
-                                (double)h[k] / (double)((k >= 4 && k <= 6) ? (h[9] ? h[9] : 1) : (h[8] ? h[8] : 1)), (k >= 4 && k <= 6) ? "query" : "wave-cell");
-                }
-            } dump;
-        }
-        ca.prof = prof;
-        hipLaunchKernelGGL((k_radius_cells<kCellCand, kCellListCap, kQueryWaves, true>), dim3(blocks), dim3(kQueryWaves * 64), 0, st, ca);
-    } else {
+    {
         KpProfScope ev(st, nq, cols, ns, 1, 4);        // bench.py's radius roofline: the kernel's own start / stop events
         hipExtLaunchKernelGGL((k_radius_cells<kCellCand, kCellListCap, kQueryWaves>), dim3(blocks), dim3(kQueryWaves * 64), 0, st,
                               ev.a, ev.b, 0, ca);

@@ -101,7 +101,7 @@ struct Ctx {
     Mat gemm_out(const int* rows, int cols, int k) {
         long total = 0;
         for (int g = 0; g < G; ++g) total += rows[g];
-        if (!debug_opts().zero_arena || !gemm_bt_accumulates(max_rows(rows), cols, k, total)) return mat(rows, cols);
+        if (!gemm_bt_accumulates(max_rows(rows), cols, k, total)) return mat(rows, cols);
         Mat m;
         m.cols = cols; m.ld = cols;
         for (int g = 0; g < G; ++g) {
@@ -340,7 +340,6 @@ void linear_extra(Ctx& c, const Mat& a, const float* w, int ldw, const float* bi
 // y = lrelu(IN(x), slope) @ w^T (+ bias) with the normalisation done inside the product's A loads (GemmExtra::a_sums):
 // x is the RAW output of the producing product and xs its column sums.  Returns false when that form does not apply
 // (the caller then normalises into a matrix of its own and calls linear()).
-bool norm_fuse_on() { return debug_opts().fuse_norm && gemm_extra_ok(); }
 bool lazy_stats_ready(Ctx& c, const Mat& x, Stat* xs) {
     if (!xs || !xs->sums || x.ld % 4 != 0 || x.cols > 4096) return false;
     fill_sums(c, x, xs);              // nobody left the sums yet (split-K or accumulated output): one pass
@@ -348,7 +347,7 @@ bool lazy_stats_ready(Ctx& c, const Mat& x, Stat* xs) {
 }
 bool linear_norm(Ctx& c, const Mat& x, Stat* xs, float slope, const float* w, int ldw, const float* bias, const Mat& y,
                  Stat* st = nullptr) {
-    if (!norm_fuse_on() || !lazy_stats_ready(c, x, xs)) return false;
+    if (!gemm_extra_ok() || !lazy_stats_ready(c, x, xs)) return false;
     linear_extra(c, x, w, ldw, bias, y, 0, nullptr, nullptr, xs, slope, false, y.zeroed, st);
     return true;
 }
@@ -402,8 +401,8 @@ void kpconv(Ctx& c, const Batches& B, const pcrcg_block& blk, const Mat& x, cons
     // floats (the 16th zero, pcrcg_amd/runner.py) and the gather kernel writes wf in rows of 16 -- whole k-steps, so the
     // contraction is the grouped fp16 A B^T product with the statistics in its epilogue like every other layer's (round 6;
     // before: one k-major six-product launch per pair and a column-sum pass over its output)
-    const bool c1_16 = cin == 1 && blk.kp_wt != nullptr && debug_opts().c1_rows16 != 0;
-    const float* const kp_wt = (cin == 1 && !c1_16) ? nullptr : blk.kp_wt;     // (cin = 1: the copy is the 16-float form or nothing)
+    const bool c1_16 = cin == 1 && blk.kp_wt != nullptr;
+    const float* const kp_wt = blk.kp_wt;     // (cin = 1: the copy is the 16-float form or nothing)
     const int kk = c1_16 ? 16 : PCRCG_KPOINTS * cin;
     // bf16 feature storage (pcrcg_model.feature_bf16): the gathers read a bf16 copy of x and wf is bf16 in HBM -- half
     // the bytes of the two streams that bound the encoder; the contraction takes wf as the (single-term) bf16 operand
@@ -459,7 +458,7 @@ void kpconv(Ctx& c, const Batches& B, const pcrcg_block& blk, const Mat& x, cons
 
 // length of a wf row (the contraction's K)
 int kp_k(const pcrcg_block& blk, const Mat& x) {
-    return (x.cols == 1 && blk.kp_wt && debug_opts().c1_rows16) ? 16 : PCRCG_KPOINTS * kp_cin(blk, x);
+    return (x.cols == 1 && blk.kp_wt) ? 16 : PCRCG_KPOINTS * kp_cin(blk, x);
 }
 
 void out_rows(const Ctx& c, const Batches& B, const pcrcg_block& blk, int* rows) {
@@ -486,7 +485,7 @@ Mat simple_block(Ctx& c, const Batches& B, const pcrcg_block& blk, const Mat& x)
 // pass over u of its own (10 launches per S30k forward: +4 % pairs/s with them knocked out).  False: not applicable.
 bool norm_act_pack(Ctx& c, const Batches& B, int layer, const Mat& t, float slope, const Mat& u, Stat* ts, void* const* kp_ws,
                    const size_t* kp_ws_bytes) {
-    if (!debug_opts().fuse_pack || c.bf16 || !instnorm_pack_ok(t.cols, t.ld, u.ld) || u.ld != u.cols) return false;
+    if (c.bf16 || !instnorm_pack_ok(t.cols, t.ld, u.ld) || u.ld != u.cols) return false;
     const size_t m = c.mark();
     float* stats = static_cast<float*>(c.raw(sizeof(float) * 2 * t.cols));
     const size_t wsb = pcrcg_instnorm_ws_bytes(t.cols);
@@ -576,9 +575,7 @@ Mat resnet_block(Ctx& c, const Batches& B, const pcrcg_block& blk, const Mat& fe
                 c.check(pcrcg_gather_max(feats.p[g], feats.rows[g], feats.cols, t.idx, nq[g], t.cols, t.ld, sc.p[g], c.st));
             }
     }
-    if (blk.shortcut && blk.layer < debug_opts().knock_tail) {
-        norm_act(c, u2, 0.1f, y, &u2s);
-    } else if (blk.shortcut) {
+    if (blk.shortcut) {
         Mat s2 = c.gemm_out(nq, blk.out_dim, sc.cols);
         Stat s2s = stat_buffer(c, nq, blk.out_dim);
         linear(c, sc, blk.shortcut, sc.cols, nullptr, s2, &s2s);
@@ -693,7 +690,7 @@ Mat cross_attention(Ctx& c, const pcrcg_model& mdl, const pcrcg_gnn_layer& gl, c
     const size_t m = c.mark();
     // the key and value projections read the same rows: ONE product of width 2 ch when the caller packed the two weight
     // matrices (and biases) behind each other (pcrcg_amd/runner.py does), k and v are then column blocks of its output
-    const bool kv_fused = gl.wv == gl.wk + (size_t)ch * ch && gl.bv == gl.bk + ch && debug_opts().gnn_merge;
+    const bool kv_fused = gl.wv == gl.wk + (size_t)ch * ch && gl.bv == gl.bk + ch;
     Mat q = q_given ? *q_given : c.gemm_out(x.rows, ch, ch), kk, v, msg = c.mat(x.rows, ch);
     if (kv_fused) {
         Mat kv = c.gemm_out(src.rows, 2 * ch, ch);
@@ -799,7 +796,7 @@ void forward(Ctx& c, const pcrcg_model& mdl, const Batches& B, const pcrcg_outpu
     int* knn1[GMAX] = {};
     int n_self = 0;
     for (int i = 0; i < mdl.n_gnn; ++i) n_self += mdl.gnn[i].cross ? 0 : 1;
-    const bool knn_once = n_self >= 2 && debug_opts().gnn_merge;
+    const bool knn_once = n_self >= 2;
     if (knn_once)
         for (int g = 0; g < c.G; ++g) {
             const int k0 = mdl.knn_k < ns[g] - 1 ? mdl.knn_k : ns[g] - 1, k1 = mdl.knn_k < nt[g] - 1 ? mdl.knn_k : nt[g] - 1;
@@ -812,7 +809,7 @@ void forward(Ctx& c, const pcrcg_model& mdl, const Batches& B, const pcrcg_outpu
         }
     for (int i = 0; i < mdl.n_gnn; ++i) {
         const pcrcg_gnn_layer& gl = mdl.gnn[i];
-        if (gl.cross && 2 * c.G <= GMAX && c.paired_ok() && debug_opts().gnn_merge) {
+        if (gl.cross && 2 * c.G <= GMAX && c.paired_ok()) {
             // the second direction's queries come from d1, which the first direction does not change: both query
             // projections in one launch (2 G products sharing wq)
             const int G0 = c.G, ch = d0.cols;
@@ -835,11 +832,12 @@ void forward(Ctx& c, const pcrcg_model& mdl, const Batches& B, const pcrcg_outpu
         } else if (gl.cross) {
             d0 = cross_attention(c, mdl, gl, d0, d1);
             d1 = cross_attention(c, mdl, gl, d1, d0);   // sees the updated d0 (:214)
-        } else if (2 * c.G <= GMAX && c.paired_ok() && debug_opts().gnn_merge) {
+        } else if (2 * c.G <= GMAX && c.paired_ok()) {
             // The layer is applied to the source cloud and to the target cloud of every pair with the SAME weights and no
             // exchange between them (ref:models/gcn.py:207-211): 2 G independent clouds through ONE pass -- every weight
             // product of the layer once for all of them (round 5: three launches per layer instead of six; the
-            // per-cloud kernels are unchanged)
+            // per-cloud kernels are unchanged).  The multi-cloud kernels take four clouds, so this applies to calls of one
+            // or two pairs; with four pairs per call the two sides run as two passes of four clouds.
             const int G0 = c.G;
             Mat f2;
             const float* cc[GMAX];
@@ -899,7 +897,6 @@ void forward(Ctx& c, const pcrcg_model& mdl, const Batches& B, const pcrcg_outpu
     }
     x = xc;
     // 4. decoder (:567-570)
-    const bool fuse_off = !debug_opts().fuse_upsample;
     // `x` may be LAZY between two decoder stages: the raw output of a unary's products whose InstanceNorm + LeakyReLU the
     // next stage's gathering product applies on load (xs = its column sums); materialise() applies it for anyone else
     Stat xs;
@@ -924,14 +921,14 @@ void forward(Ctx& c, const pcrcg_model& mdl, const Batches& B, const pcrcg_outpu
             // of x gathered through the table (closest_pool, the shadow index reads a zero row), plus its skip columns on
             // the skip features.  Neither the upsampled matrix nor the concatenation is written: at level 0 that is
             // 31 + 61 MB of stores and 92 MB of loads that the product no longer waits for.
-            if (!fuse_off && concat && next && next->mlp_skip && next->skip_dim == cs && gemm_extra_ok() &&
+            if (concat && next && next->mlp_skip && next->skip_dim == cs && gemm_extra_ok() &&
                 (next->type == PCRCG_BLK_UNARY || next->type == PCRCG_BLK_LAST_UNARY) && x.ld % 4 == 0 &&
                 skips.back().ld % 4 == 0) {
                 const Mat& sk = skips.back();
                 const bool last = next->type == PCRCG_BLK_LAST_UNARY;
                 Mat tt = c.mat(trows, next->out_dim, pad4(next->out_dim));    // rows 16-byte aligned: it may be gathered next
                 float* zero_row = static_cast<float*>(c.zraw(sizeof(float) * (size_t)(x.cols + 8)));
-                if (lazy && !(norm_fuse_on() && lazy_stats_ready(c, x, &xs))) materialise();
+                if (lazy && !(gemm_extra_ok() && lazy_stats_ready(c, x, &xs))) materialise();
                 // the producer's normalisation (when lazy) applied to the gathered rows; then the skip part on top
                 linear_extra(c, x, next->mlp, next->mlp_ld, nullptr, tt, 0, tabs, zero_row, lazy ? &xs : nullptr, 0.1f, false, false);
                 linear_extra(c, sk, next->mlp_skip, next->mlp_skip_ld, nullptr, tt, 0, nullptr, nullptr, nullptr, 1.0f, true, true);

@@ -1,6 +1,8 @@
-"""Per-kernel-family counters of the pair engine under `rocprofv3 --pmc` (scripts/r06_counters.sh): L2 hit rate, waves, busy
-cycles, for the run alone (--isolated-only), with three and with four model streams; and whether kernels still ran beside
-each other under counter collection (mean number of kernels in flight from the kernel trace of the same run).
+"""Per-kernel-family counters of the pair engine under `rocprofv3 --pmc`: L2 hit rate, waves, busy cycles, for the run
+alone (--isolated-only), with three and with four model streams; and whether kernels still ran beside each other under
+counter collection (mean number of kernels in flight from the kernel trace of the same run).  Each dir holds the csv
+output of `rocprofv3 --kernel-trace --pmc ... -- python3 bench.py ...` runs, one per counter group
+(profiles/r06_concurrency_counters.txt was made this way).
 python scripts/pmc_engine_summary.py label=dir ..."""
 import collections
 import csv

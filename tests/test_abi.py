@@ -153,3 +153,43 @@ def test_train_step_feature_width_must_match_its_kp_w(feat_dim):
     assert lib.pcrcg_kpfcnn_train_forward(ctypes.byref(m), ctypes.byref(g), ctypes.byref(b), ctypes.c_void_p(4096), 1 << 20,
                                           1 << 20, 1 << 20, ctypes.byref(out), ctypes.byref(tape), None) == -1
     assert b"feat_dim" in lib.pcrcg_last_error() and not tape.value
+
+
+_RETIRED_DEBUG_NAMES = ("zero_arena", "fuse_norm", "fuse_pack", "fuse_upsample", "c1_rows16", "gnn_merge", "edge_rows",
+                        "knock_tail", "radius_cells", "radius_eager_redo", "radius_prof", "pyr_wait", "pyr_trace", "pyr_morton")
+
+
+def _listed_debug_switches():
+    """name -> documented default of every switch the pcrcg_debug_set comment in include/pcrcg.h lists."""
+    text = open(os.path.join(REPO, "include", "pcrcg.h")).read()
+    block = text[text.index("Every switch defaults to the product behaviour:"):text.index("int pcrcg_debug_set(")]
+    return dict(re.findall(r"\b([a-z][a-z0-9_]*)=(-?[0-9^]+)", block))
+
+
+def test_debug_switch_names():
+    """pcrcg_debug_set accepts every name include/pcrcg.h lists and rejects a retired one like any unknown name: it returns
+    PCRCG_EBADARG and changes nothing, not even the items of the same call that come before it.  No GPU: setting options
+    touches no device, and the forward's workspace size (a dry run) shows whether stat_sums is in force."""
+    lib = _lib.lib()
+    listed = _listed_debug_switches()
+    assert len(listed) == 21 and "deterministic" in listed and "stat_sums_rows" in listed
+    assert not set(listed) & set(_RETIRED_DEBUG_NAMES)
+    m, b, _ = _descriptors_with_a_129_channel_first_block(129)
+    ws = lambda: lib.pcrcg_kpfcnn_ws_bytes(ctypes.byref(m), ctypes.byref(b))
+    try:
+        for name, value in listed.items():
+            value = str(1 << 30) if value == "2^30" else value
+            assert lib.pcrcg_debug_set(f"{name}={value}".encode()) == 0, (name, lib.pcrcg_last_error())
+            assert lib.pcrcg_debug_set(None) == 0
+        assert lib.pcrcg_debug_set(b"deterministic=0,stat_sums=1") == 0
+        with_sums = ws()
+        assert lib.pcrcg_debug_set(b"stat_sums=0") == 0
+        without_sums = ws()
+        assert without_sums != with_sums > 0
+        for name in _RETIRED_DEBUG_NAMES:
+            for value in (0, 1):
+                assert lib.pcrcg_debug_set(f"stat_sums=1,{name}={value}".encode()) == -1, name      # PCRCG_EBADARG
+                assert name.encode() in lib.pcrcg_last_error()
+                assert ws() == without_sums, name
+    finally:
+        assert lib.pcrcg_debug_set(None) == 0
