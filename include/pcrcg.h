@@ -49,7 +49,9 @@ const char* pcrcg_last_error(void);
  *                pcrcg_gemm_set_mode); deterministic=1 debug switch
  *   4 (round 6)  pyramid builder: levels sized from pcrcg_pyramid_cfg::shrink, ONE host round trip per call, the KD-forests
  *                (level 0's, and one over the subsampled levels) on pcrcg_pyramid_cfg::side_stream (new cfg fields; pcrcg_pyramid_ws_bytes lost its `shrink`
- *                argument; pcrcg_pyramid_restore and pcrcg_reorder_job changed layout) */
+ *                argument; pcrcg_pyramid_restore and pcrcg_reorder_job changed layout)
+ *   The registration back end (pcrcg_ransac_ws_bytes, pcrcg_feature_match, pcrcg_ransac, pcrcg_ransac_trace) was added
+ *   under version 4: it is additive -- no existing signature, layout or arithmetic changed. */
 #define PCRCG_ABI_VERSION 4
 int pcrcg_abi_version(void);
 
@@ -656,6 +658,62 @@ int pcrcg_stream_destroy(void* stream);
  * (pcrcg_amd/pairstream.py) picks them from different classes, and puts streams of small, latency-bound kernels that should
  * not wait for each other's resources -- the front-end chain and its KD-forests -- into one. */
 int pcrcg_stream_pipe_classes(void* const* streams, int n, int* cls, void* scratch);
+
+/* ------------------------------------------------------------------------------------------------
+ * Registration back end
+ * Replaces ransac_pose_estimation (ref:lib/benchmark_utils.py:187-224): open3d 0.10's
+ * registration_ransac_based_on_feature_matching (mutual = False) and _based_on_correspondence on the mutual pairs of the
+ * inner-product score (mutual = True).  open3d seeds its RANSAC per OpenMP thread, so this is a deterministic algorithm of
+ * the same structure rather than a bit-for-bit copy; DESIGN.md section 10 defines it and tests/ransac_ref.py restates it.
+ *
+ * pcrcg_feature_match: the correspondence list corr [k_max, 2] int32 = (source index, target index) and its length k (ONE
+ * device int) for source / target descriptors [n, c] / [m, c] (row strides ld_src, ld_tgt >= c).
+ *   mutual = 0: row i = (i, nn(i)), nn(i) = the target nearest in L2 feature distance (the arg-max of <a_i, b_j> - |b_j|^2/2
+ *               in fp32, lowest index on ties); k = n, so k_max = n.
+ *   mutual = 1: the pairs (i, j) with j = argmax_j <a_i, b_j> and i = argmax_i <a_i, b_j> (first index on ties), in
+ *               ascending source index; k <= min(n, m), give k_max = n.
+ * pcrcg_ransac: src [n, 3], tgt [m, 3] f32 points; grid = pcrcg_cellgrid_build over the m target points as ONE cloud with
+ * radius = (float)threshold; corr / k as above (k is clamped to k_max).  With P = k:
+ *   hypothesis h < max_iteration draws rows ((r >> 32) * P) >> 32, r = splitmix64((seed << 40) + 8 h + s), s < ransac_n,
+ *     splitmix64(x): z = x + 0x9E3779B97F4A7C15; z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB;
+ *     return z ^ z >> 31   (all mod 2^64; seed < 2^24);
+ *   and passes iff, in this order: its source ids are distinct; (edge_similarity > 0) every pair of samples has float64
+ *   edge lengths ds, dt with ds >= dt * sim and dt >= ds * sim; the float64 Kabsch fit without scaling (reflection fixed by
+ *   diag(1, 1, det)) has sigma_2 > 1e-12 sigma_1 of the 3 x 3 cross-covariance; (distance_check) |T p_s - p_t| <= threshold
+ *   for every sample, in float64.
+ *   The first max_validation passing hypotheses are evaluated: R|t rounded to fp32, every source point moved with unfused
+ *   fp32 arithmetic ((r0 x + r1 y) + r2 z) + t0, its nearest target point within the threshold looked up; an inlier iff
+ *   d2 < (float)(threshold^2), d2 = ((dx dx + dy dy) + dz dz) in fp32; count = inliers, sum = float64 sum of their d2.
+ *   The best has the highest count, then the lowest sum, then the lowest h.
+ *   out_transform [16] f64 (row-major 4 x 4) = its float64 fit, not refined; identity when no hypothesis passes or none
+ *   has an inlier.  out_stats [6] f64 = (fitness = count / n, inlier_rmse = sqrt(sum / count), k, iterations = max_iteration,
+ *   validations, chosen h or -1); fitness and rmse are 0 for the identity.
+ * trace (NULL, or any member NULL: not written) receives the stages for tests:
+ *   samples [max_iteration, ransac_n] i32 rows drawn, pass [max_iteration] i32, xf32 / xf64 [max_iteration, 12] the fit as
+ *   R (row-major) then t (zero where a check before the fit failed), valid_ids [max_validation] i32, counts
+ *   [max_validation] i32, sums [max_validation] f64 (the first `validations` entries are written).
+ * Both entries take a workspace of pcrcg_ransac_ws_bytes(n, m, max_iteration, max_validation) bytes (one size serves both,
+ * reused on the same stream), allocate nothing and synchronise nothing.  Bad arguments (null pointers, ransac_n outside
+ * 3..8, k_max < ransac_n, max_validation > max_iteration, threshold <= 0, edge_similarity outside [0, 1]) are rejected
+ * before anything launches.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct pcrcg_ransac_trace {
+    int* samples;
+    int* pass;
+    float* xf32;
+    double* xf64;
+    int* valid_ids;
+    int* counts;
+    double* sums;
+} pcrcg_ransac_trace;
+
+size_t pcrcg_ransac_ws_bytes(int n, int m, int max_iteration, int max_validation);
+int pcrcg_feature_match(const float* src_feat, int ld_src, int n, const float* tgt_feat, int ld_tgt, int m, int c, int mutual,
+                        int* corr, int* k, void* ws, size_t ws_bytes, void* stream);
+int pcrcg_ransac(const float* src, int n, const float* tgt, int m, const void* grid, const int* corr, int k_max, const int* k,
+                 int ransac_n, double threshold, double edge_similarity, int distance_check, int max_iteration,
+                 int max_validation, uint64_t seed, double* out_transform, double* out_stats, const pcrcg_ransac_trace* trace,
+                 void* ws, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

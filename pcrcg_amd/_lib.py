@@ -117,6 +117,13 @@ SIGNATURES = {
     "pcrcg_thread_shares_gpu": (None, [c_int]),
     "pcrcg_stream_create": (c_int, [c_void_p, c_int]),
     "pcrcg_stream_destroy": (c_int, [c_void_p]),
+    # registration back end (pcrcg_amd/registration.py)
+    "pcrcg_ransac_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "pcrcg_feature_match": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                    c_void_p, c_size_t, c_void_p]),
+    "pcrcg_ransac": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, ctypes.c_double,
+                             ctypes.c_double, c_int, c_int, c_int, ctypes.c_uint64, c_void_p, c_void_p, c_void_p, c_void_p,
+                             c_size_t, c_void_p]),
     # include/pcrcg_train.h -- the "next" rows
     "pcrcg_gemm_f32_ex": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int,
                                   c_void_p, c_void_p, c_void_p]),

@@ -1,0 +1,602 @@
+// register.hip -- the registration back end on gfx950: feature matching and RANSAC over the correspondences.
+// ABI: include/pcrcg.h, section "Registration back end".
+//
+// Replaces ransac_pose_estimation (ref:lib/benchmark_utils.py:187-224), i.e. open3d 0.10's
+// registration_ransac_based_on_feature_matching / _based_on_correspondence, with a deterministic algorithm of the same
+// structure (DESIGN.md section 10 states it in full; tests/ransac_ref.py restates it in numpy):
+//
+//   match     : non-mutual -- every source point i is paired with its nearest target in L2 feature distance, the
+//               arg-max over j of <a_i, b_j> - |b_j|^2 / 2 (fp32; lowest j on ties); mutual -- the pairs that are the
+//               arg-max of <a_i, b_j> along both their row and their column (pcrcg_feature_argmax both ways + one
+//               compaction), in ascending source order.  The count K stays on the device.
+//   hypotheses: one thread per hypothesis h, float64 -- ransac_n rows drawn from the list by splitmix64, distinct source
+//               ids, edge-length check, Kabsch fit with the reflection fix (one-sided Jacobi SVD of the 3 x 3
+//               cross-covariance), degeneracy test, distance check; a pass flag and the fp32-rounded R|t.
+//   compaction: the first max_validation passing hypotheses in index order (device-wide scan of the flags).
+//   evaluation: one workgroup per validated hypothesis; every source point is moved with unfused fp32 arithmetic and
+//               looked up in the target's cell grid (27 cells around it); count and float64 sum of the nearest d2 over the
+//               inliers (d2 < thr2), reduced in a fixed order -- bit-reproducible.
+//   selection : highest count, then lowest sum, then lowest h; the float64 transform of the winner is re-fitted from its
+//               samples (the same device function) and written with the statistics.
+//
+// Compiled with -ffp-contract=off: every fp32 and fp64 operation rounds where the source says, so the numpy restatement
+// reproduces the evaluation's counts exactly.
+#include "block_scan.h"
+#include "cellgrid.h"
+#include "common.h"
+#include "pcrcg_train.h"
+
+namespace pcrcg {
+namespace {
+
+constexpr int kMaxSample = 8;         // ransac_n <= 8: the draws of hypothesis h are 8 h .. 8 h + 7
+constexpr int kEvalThreads = 512;     // evaluation workgroup: one validated hypothesis
+
+// splitmix64 (Steele, Lea & Flood 2014; the generator of java.util.SplittableRandom): the state x advanced by the golden
+// gamma 0x9E3779B97F4A7C15, then the variant-13 finaliser.  include/pcrcg.h documents the same constants.
+__host__ __device__ inline u64 splitmix64(u64 x) {
+    u64 z = x + 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
+// (score, column) as one orderable word: a larger score wins, an equal score keeps the smaller column
+__device__ inline u64 pack_max(float v, int j) {
+    const unsigned b = __float_as_uint(v);
+    const unsigned key = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+    return ((u64)key << 32) | (u64)(0xFFFFFFFFu - (unsigned)j);
+}
+
+// ---- L2 nearest neighbour in feature space -------------------------------------------------------------------------
+// argmin_j |a - b_j|^2 = argmax_j <a, b_j> - |b_j|^2 / 2.  hb[j] = |b_j|^2 / 2, summed in order.
+__global__ void __launch_bounds__(256) k_half_norms(const float* __restrict__ b, int ldb, int m, int c, float* __restrict__ hb) {
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= m) return;
+    float s = 0.f;
+    for (int k = 0; k < c; ++k) {
+        const float v = b[(long)j * ldb + k];
+        s = s + v * v;
+    }
+    hb[j] = 0.5f * s;
+}
+
+// C = 32 or 64 on the fp32 matrix cores, laid out like k_feature_argmax_mfma32 (trainops.hip): a wavefront holds 32 rows of
+// A as its operand (lane (row, half) keeps A[row][C/2 half + s]) and walks its column range 32 columns at a time, C/2
+// v_mfma_f32_32x32x2_f32 per 32 x 32 block of dot products; each lane keeps the best (dot - hb) of its 16 rows over the
+// columns congruent to its lane index (strictly greater: the smaller column survives a tie), the 32 lanes of a row meet by
+// shuffles, and the column ranges (grid.y) by a 64-bit atomicMax.
+typedef float rg_f16 __attribute__((ext_vector_type(16)));
+template <int C>
+__global__ void __launch_bounds__(256) k_l2nn_mfma(const float* __restrict__ a, int lda, int n, const float* __restrict__ b,
+                                                   int ldb, int m, const float* __restrict__ hb, int cols_per,
+                                                   u64* __restrict__ packed) {
+    constexpr int NV = C / 2;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int l31 = lane & 31, half = lane >> 5;
+    const int row0 = (blockIdx.x * 4 + wave) * 32;
+    if (row0 >= n) return;
+    const int jbeg = blockIdx.y * cols_per, jend = min(m, jbeg + cols_per);
+    if (jbeg >= jend) return;
+    float av[NV];
+    {
+        const float* ap = a + (long)min(row0 + l31, n - 1) * lda + NV * half;
+#pragma unroll
+        for (int q = 0; q < NV / 4; ++q) {
+            const float4 t = *reinterpret_cast<const float4*>(ap + 4 * q);
+            av[4 * q] = t.x; av[4 * q + 1] = t.y; av[4 * q + 2] = t.z; av[4 * q + 3] = t.w;
+        }
+    }
+    float best[16];
+    int bj[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { best[r] = -INFINITY; bj[r] = 0; }
+    for (int j0 = jbeg; j0 < jend; j0 += 32) {
+        const int col = j0 + l31;
+        const int cc = min(col, m - 1);
+        float bv[NV];
+        const float* bp = b + (long)cc * ldb + NV * half;
+#pragma unroll
+        for (int q = 0; q < NV / 4; ++q) {
+            const float4 t = *reinterpret_cast<const float4*>(bp + 4 * q);
+            bv[4 * q] = t.x; bv[4 * q + 1] = t.y; bv[4 * q + 2] = t.z; bv[4 * q + 3] = t.w;
+        }
+        const float h = hb[cc];
+        rg_f16 acc;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+#pragma unroll
+        for (int s2 = 0; s2 < NV; ++s2) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[s2], bv[s2], acc, 0, 0, 0);
+        if (col < jend) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const float s = acc[r] - h;
+                if (s > best[r]) { best[r] = s; bj[r] = col; }
+            }
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        u64 p = pack_max(best[r], bj[r]);
+#pragma unroll
+        for (int sh = 16; sh >= 1; sh >>= 1) {
+            const u64 o = __shfl_xor(p, sh, 64);
+            p = o > p ? o : p;
+        }
+        const int row = row0 + (r & 3) + 8 * (r >> 2) + 4 * half;
+        if (l31 == 0 && row < n) atomicMax(&packed[row], p);
+    }
+}
+
+// any width (and unaligned operands): one thread per row of A, a column range per grid.y
+__global__ void __launch_bounds__(256) k_l2nn_any(const float* __restrict__ a, int lda, int n, const float* __restrict__ b,
+                                                  int ldb, int m, int c, const float* __restrict__ hb, int cols_per,
+                                                  u64* __restrict__ packed) {
+    const int row = blockIdx.x * 256 + threadIdx.x;
+    if (row >= n) return;
+    const int jbeg = blockIdx.y * cols_per, jend = min(m, jbeg + cols_per);
+    if (jbeg >= jend) return;
+    float bv = -INFINITY;
+    int bj = jbeg;
+    for (int j = jbeg; j < jend; ++j) {
+        float s = 0.f;
+        for (int k = 0; k < c; ++k) s = fmaf(a[(long)row * lda + k], b[(long)j * ldb + k], s);
+        s = s - hb[j];
+        if (s > bv) { bv = s; bj = j; }
+    }
+    atomicMax(&packed[row], pack_max(bv, bj));
+}
+
+// non-mutual list: row i = (i, nn(i)), K = n
+__global__ void __launch_bounds__(256) k_nn_emit(const u64* __restrict__ packed, int n, int* __restrict__ corr, int* __restrict__ k) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i == 0) *k = n;
+    if (i >= n) return;
+    corr[2 * i] = i;
+    corr[2 * i + 1] = (int)(0xFFFFFFFFu - (unsigned)(packed[i] & 0xFFFFFFFFull));
+}
+
+// mutual list: i is kept iff the arg-max of its row points at a column whose arg-max is i
+__global__ void __launch_bounds__(256) k_mutual_flags(const long long* __restrict__ arg_s, int n, const long long* __restrict__ arg_t,
+                                                      int* __restrict__ flags) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    flags[i] = arg_t[arg_s[i]] == i ? 1 : 0;
+}
+
+__global__ void __launch_bounds__(256) k_mutual_emit(const int* __restrict__ flags, const int* __restrict__ offs, int n,
+                                                     const long long* __restrict__ arg_s, int* __restrict__ corr) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n || !flags[i]) return;
+    const int o = offs[i];
+    corr[2 * o] = i;
+    corr[2 * o + 1] = (int)arg_s[i];
+}
+
+// ---- hypotheses ----------------------------------------------------------------------------------------------------
+struct HypArgs {
+    const float* src;
+    const float* tgt;
+    const int* corr;
+    const int* k;
+    int k_max, ransac_n, dist_check, max_iteration;
+    double thr, sim;
+    u64 seed;
+};
+
+__device__ inline int list_size(const HypArgs& a) {
+    const int k = *a.k;
+    return k < 0 ? 0 : (k > a.k_max ? a.k_max : k);
+}
+
+__device__ inline void load3(const float* p, int i, double* v) {
+    v[0] = p[3 * (long)i]; v[1] = p[3 * (long)i + 1]; v[2] = p[3 * (long)i + 2];
+}
+
+__device__ inline double dist3(const double* p, const double* q) {
+    const double dx = p[0] - q[0], dy = p[1] - q[1], dz = p[2] - q[2];
+    return sqrt((dx * dx + dy * dy) + dz * dz);
+}
+
+// Hypothesis h: the drawn rows (rows[]), then every check in the documented order; R (row-major) and t receive the fit
+// (zero when the hypothesis fails before it).  Returns the pass flag.
+__device__ bool hypothesis(const HypArgs& a, int h, int K, int* rows, double* R, double* t) {
+    for (int e = 0; e < 9; ++e) R[e] = 0.0;
+    t[0] = t[1] = t[2] = 0.0;
+    const int ns = a.ransac_n;
+    for (int s = 0; s < ns; ++s) {
+        const u64 r = splitmix64((a.seed << 40) + 8ull * (u64)h + (u64)s);
+        rows[s] = (int)(((r >> 32) * (u64)K) >> 32);
+    }
+    if (K < ns) return false;
+    double ps[kMaxSample][3], pt[kMaxSample][3];
+    int sid[kMaxSample];
+    for (int s = 0; s < ns; ++s) {
+        sid[s] = a.corr[2 * rows[s]];
+        load3(a.src, sid[s], ps[s]);
+        load3(a.tgt, a.corr[2 * rows[s] + 1], pt[s]);
+    }
+    for (int i = 0; i < ns; ++i)
+        for (int j = i + 1; j < ns; ++j)
+            if (sid[i] == sid[j]) return false;
+    if (a.sim > 0.0) {
+        for (int i = 0; i < ns; ++i)
+            for (int j = i + 1; j < ns; ++j) {
+                const double ds = dist3(ps[i], ps[j]), dt = dist3(pt[i], pt[j]);
+                if (ds < dt * a.sim || dt < ds * a.sim) return false;
+            }
+    }
+    // Kabsch: centroids, H = sum (ps - cs)(pt - ct)^T, H = U S V^T, R = V diag(1, 1, det(V U^T)) U^T, t = ct - R cs
+    double cs[3] = {0.0, 0.0, 0.0}, ct[3] = {0.0, 0.0, 0.0};
+    for (int s = 0; s < ns; ++s)
+        for (int d = 0; d < 3; ++d) { cs[d] += ps[s][d]; ct[d] += pt[s][d]; }
+    for (int d = 0; d < 3; ++d) { cs[d] /= ns; ct[d] /= ns; }
+    double H[3][3] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}};
+    for (int s = 0; s < ns; ++s)
+        for (int r = 0; r < 3; ++r)
+            for (int c = 0; c < 3; ++c) H[r][c] += (ps[s][r] - cs[r]) * (pt[s][c] - ct[c]);
+    // one-sided Jacobi: rotate the columns of B = H V until they are orthogonal; then sigma_c = |B[:, c]|, u_c = B[:, c] / sigma_c
+    double V[3][3] = {{1.0, 0.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, 1.0}};
+    for (int sweep = 0; sweep < 30; ++sweep) {
+        bool rotated = false;
+        for (int p = 0; p < 2; ++p)
+            for (int q = p + 1; q < 3; ++q) {
+                double al = 0.0, be = 0.0, ga = 0.0;
+                for (int r = 0; r < 3; ++r) { al += H[r][p] * H[r][p]; be += H[r][q] * H[r][q]; ga += H[r][p] * H[r][q]; }
+                if (ga == 0.0 || fabs(ga) <= 1e-17 * sqrt(al * be)) continue;
+                rotated = true;
+                const double zeta = (be - al) / (2.0 * ga);
+                const double tt = (zeta >= 0.0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
+                const double cc = 1.0 / sqrt(1.0 + tt * tt), sn = cc * tt;
+                for (int r = 0; r < 3; ++r) {
+                    const double hp = H[r][p], hq = H[r][q];
+                    H[r][p] = cc * hp - sn * hq;
+                    H[r][q] = sn * hp + cc * hq;
+                    const double vp = V[r][p], vq = V[r][q];
+                    V[r][p] = cc * vp - sn * vq;
+                    V[r][q] = sn * vp + cc * vq;
+                }
+            }
+        if (!rotated) break;
+    }
+    double sg[3];
+    for (int c = 0; c < 3; ++c) sg[c] = sqrt((H[0][c] * H[0][c] + H[1][c] * H[1][c]) + H[2][c] * H[2][c]);
+    int i1 = 0;
+    for (int c = 1; c < 3; ++c) if (sg[c] > sg[i1]) i1 = c;
+    int i2 = i1 == 0 ? 1 : 0;
+    for (int c = 0; c < 3; ++c) if (c != i1 && sg[c] > sg[i2]) i2 = c;
+    if (!(sg[i2] > 1e-12 * sg[i1])) return false;                 // degenerate sample (also catches sigma_1 = 0)
+    double u1[3], u2[3], v1[3], v2[3];
+    for (int r = 0; r < 3; ++r) {
+        u1[r] = H[r][i1] / sg[i1]; u2[r] = H[r][i2] / sg[i2];
+        v1[r] = V[r][i1]; v2[r] = V[r][i2];
+    }
+    // R u1 = v1, R u2 = v2 and R proper: R (u1 x u2) = v1 x v2 -- the reflection fix without a third singular vector
+    const double u3[3] = {u1[1] * u2[2] - u1[2] * u2[1], u1[2] * u2[0] - u1[0] * u2[2], u1[0] * u2[1] - u1[1] * u2[0]};
+    const double v3[3] = {v1[1] * v2[2] - v1[2] * v2[1], v1[2] * v2[0] - v1[0] * v2[2], v1[0] * v2[1] - v1[1] * v2[0]};
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) R[3 * r + c] = (v1[r] * u1[c] + v2[r] * u2[c]) + v3[r] * u3[c];
+    for (int r = 0; r < 3; ++r) t[r] = ct[r] - ((R[3 * r] * cs[0] + R[3 * r + 1] * cs[1]) + R[3 * r + 2] * cs[2]);
+    if (a.dist_check) {
+        for (int s = 0; s < ns; ++s) {
+            double q[3];
+            for (int r = 0; r < 3; ++r) q[r] = ((R[3 * r] * ps[s][0] + R[3 * r + 1] * ps[s][1]) + R[3 * r + 2] * ps[s][2]) + t[r];
+            if (!(dist3(q, pt[s]) <= a.thr)) return false;
+        }
+    }
+    return true;
+}
+
+__global__ void __launch_bounds__(256) k_hypotheses(HypArgs a, int* __restrict__ pass, float* __restrict__ xf,
+                                                    int* __restrict__ tr_samples, int* __restrict__ tr_pass,
+                                                    float* __restrict__ tr_xf32, double* __restrict__ tr_xf64) {
+    const int h = blockIdx.x * 256 + threadIdx.x;
+    if (h >= a.max_iteration) return;
+    int rows[kMaxSample];
+    double R[9], t[3];
+    const bool ok = hypothesis(a, h, list_size(a), rows, R, t);
+    pass[h] = ok ? 1 : 0;
+    float f[12];
+    for (int e = 0; e < 9; ++e) f[e] = (float)R[e];
+    for (int e = 0; e < 3; ++e) f[9 + e] = (float)t[e];
+    for (int e = 0; e < 12; ++e) xf[12 * (long)h + e] = f[e];
+    if (tr_samples)
+        for (int s = 0; s < a.ransac_n; ++s) tr_samples[(long)h * a.ransac_n + s] = rows[s];
+    if (tr_pass) tr_pass[h] = ok ? 1 : 0;
+    if (tr_xf32)
+        for (int e = 0; e < 12; ++e) tr_xf32[12 * (long)h + e] = f[e];
+    if (tr_xf64) {
+        for (int e = 0; e < 9; ++e) tr_xf64[12 * (long)h + e] = R[e];
+        for (int e = 0; e < 3; ++e) tr_xf64[12 * (long)h + 9 + e] = t[e];
+    }
+}
+
+// the first max_validation passing hypotheses (offs = exclusive scan of the flags)
+__global__ void __launch_bounds__(256) k_compact(const int* __restrict__ pass, const int* __restrict__ offs, int max_iteration,
+                                                 int max_validation, int* __restrict__ vid, int* __restrict__ tr_vid) {
+    const int h = blockIdx.x * 256 + threadIdx.x;
+    if (h >= max_iteration || !pass[h]) return;
+    const int o = offs[h];
+    if (o < max_validation) {
+        vid[o] = h;
+        if (tr_vid) tr_vid[o] = h;
+    }
+}
+
+// ---- evaluation: one workgroup per validated hypothesis ----------------------------------------------------------
+__global__ void __launch_bounds__(kEvalThreads) k_evaluate(const float* __restrict__ src, int n, GridView g, float thr2,
+                                                           const int* __restrict__ npass, int max_validation,
+                                                           const int* __restrict__ vid, const float* __restrict__ xf,
+                                                           int* __restrict__ counts, double* __restrict__ sums,
+                                                           int* __restrict__ tr_counts, double* __restrict__ tr_sums) {
+    __shared__ int s_c[kEvalThreads];
+    __shared__ double s_s[kEvalThreads];
+    const int v = blockIdx.x;
+    const int nv = min(*npass, max_validation);
+    if (v >= nv) return;
+    const int h = vid[v];
+    float T[12];
+#pragma unroll
+    for (int e = 0; e < 12; ++e) T[e] = xf[12 * (long)h + e];
+    const double inv_cell = g.hdr->inv_cell;
+    const int m = g.hdr->ns;
+    const unsigned tsize = 2u * (unsigned)m;
+    int cnt = 0;
+    double sum = 0.0;
+    for (int i = threadIdx.x; i < n && m > 0; i += kEvalThreads) {
+        const float x = src[3 * (long)i], y = src[3 * (long)i + 1], z = src[3 * (long)i + 2];
+        const float px = ((T[0] * x + T[1] * y) + T[2] * z) + T[9];
+        const float py = ((T[3] * x + T[4] * y) + T[5] * z) + T[10];
+        const float pz = ((T[6] * x + T[7] * y) + T[8] * z) + T[11];
+        int cx, cy, cz;
+        if (!cell_coords(px, py, pz, inv_cell, &cx, &cy, &cz)) continue;
+        float best = thr2;
+        for (int c = 0; c < 27; ++c) {
+            const u64 key = cell_key(cx + c % 3 - 1, cy + (c / 3) % 3 - 1, cz + c / 9 - 1);
+            unsigned s = __umulhi(mix32(key), tsize);
+            int cnt_c = 0, start = 0;
+            for (unsigned probe = 0; probe < tsize; ++probe) {
+                const Slot sl = load_slot(&g.tab[s]);
+                if (sl.key == key) { cnt_c = sl.cnt; start = sl.start; break; }
+                if (sl.key == kEmptyKey) break;
+                s = s + 1 == tsize ? 0 : s + 1;
+            }
+            for (int e = 0; e < cnt_c; ++e) {
+                const float4 p = g.spts[start + e];
+                const float dx = p.x - px, dy = p.y - py, dz = p.z - pz;
+                const float d2 = (dx * dx + dy * dy) + dz * dz;
+                best = d2 < best ? d2 : best;
+            }
+        }
+        if (best < thr2) { ++cnt; sum += (double)best; }
+    }
+    s_c[threadIdx.x] = cnt;
+    s_s[threadIdx.x] = sum;
+    __syncthreads();
+    for (int w = kEvalThreads / 2; w >= 1; w >>= 1) {              // fixed tree: the same additions in the same order every run
+        if (threadIdx.x < w) {
+            s_c[threadIdx.x] += s_c[threadIdx.x + w];
+            s_s[threadIdx.x] = s_s[threadIdx.x] + s_s[threadIdx.x + w];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        counts[v] = s_c[0];
+        sums[v] = s_s[0];
+        if (tr_counts) tr_counts[v] = s_c[0];
+        if (tr_sums) tr_sums[v] = s_s[0];
+    }
+}
+
+// ---- selection -----------------------------------------------------------------------------------------------------
+__device__ inline bool better(int c1, double s1, int h1, int c2, double s2, int h2) {
+    return c1 > c2 || (c1 == c2 && (s1 < s2 || (s1 == s2 && h1 < h2)));
+}
+
+__global__ void __launch_bounds__(256) k_select(HypArgs a, int n, const int* __restrict__ npass, int max_validation,
+                                                const int* __restrict__ vid, const int* __restrict__ counts,
+                                                const double* __restrict__ sums, double* __restrict__ out_t,
+                                                double* __restrict__ out_stats) {
+    __shared__ int s_c[256], s_h[256];
+    __shared__ double s_s[256];
+    const int nv = min(*npass, max_validation);
+    int bc = -1, bh = 0x7FFFFFFF;
+    double bs = 0.0;
+    for (int v = threadIdx.x; v < nv; v += 256) {
+        const int c = counts[v], h = vid[v];
+        const double s = sums[v];
+        if (better(c, s, h, bc, bs, bh)) { bc = c; bs = s; bh = h; }
+    }
+    s_c[threadIdx.x] = bc; s_s[threadIdx.x] = bs; s_h[threadIdx.x] = bh;
+    __syncthreads();
+    for (int w = 128; w >= 1; w >>= 1) {
+        if (threadIdx.x < w) {
+            const int o = threadIdx.x + w;
+            if (better(s_c[o], s_s[o], s_h[o], s_c[threadIdx.x], s_s[threadIdx.x], s_h[threadIdx.x])) {
+                s_c[threadIdx.x] = s_c[o]; s_s[threadIdx.x] = s_s[o]; s_h[threadIdx.x] = s_h[o];
+            }
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x != 0) return;
+    const int K = list_size(a);
+    double T[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+    double fitness = 0.0, rmse = 0.0, chosen = -1.0;
+    if (nv > 0 && s_c[0] > 0) {                 // a hypothesis without inliers does not beat open3d's default result
+        int rows[kMaxSample];
+        double R[9], t[3];
+        hypothesis(a, s_h[0], K, rows, R, t);
+        for (int r = 0; r < 3; ++r) {
+            for (int c = 0; c < 3; ++c) T[4 * r + c] = R[3 * r + c];
+            T[4 * r + 3] = t[r];
+        }
+        fitness = (double)s_c[0] / (double)n;
+        rmse = sqrt(s_s[0] / (double)s_c[0]);
+        chosen = (double)s_h[0];
+    }
+    for (int e = 0; e < 16; ++e) out_t[e] = T[e];
+    out_stats[0] = fitness;
+    out_stats[1] = rmse;
+    out_stats[2] = (double)K;
+    out_stats[3] = (double)a.max_iteration;
+    out_stats[4] = (double)nv;
+    out_stats[5] = chosen;
+}
+
+struct RansacWs {
+    int* pass;
+    int* offs;
+    int* npass;
+    int* vid;
+    float* xf;
+    int* counts;
+    double* sums;
+    void* scan;
+};
+
+RansacWs carve_ransac(Carver& cv, int max_iteration, int max_validation) {
+    RansacWs w;
+    w.pass = cv.take<int>((size_t)max_iteration);
+    w.offs = cv.take<int>((size_t)max_iteration);
+    w.npass = cv.take<int>(1);
+    w.vid = cv.take<int>((size_t)max_validation);
+    w.xf = cv.take<float>((size_t)max_iteration * 12);
+    w.counts = cv.take<int>((size_t)max_validation);
+    w.sums = cv.take<double>((size_t)max_validation);
+    w.scan = cv.take<char>(scan_ws_bytes(max_iteration));
+    return w;
+}
+
+struct MatchWs {
+    u64* packed;       // [n]  (also pcrcg_feature_argmax's workspace)
+    float* hb;         // [m]
+    long long* arg_s;  // [n]
+    long long* arg_t;  // [m]
+    int* flags;        // [n]
+    int* offs;         // [n]
+    void* scan;
+};
+
+MatchWs carve_match(Carver& cv, int n, int m) {
+    MatchWs w;
+    const int nm = n > m ? n : m;
+    w.packed = cv.take<u64>((size_t)(nm > 0 ? nm : 1));
+    w.hb = cv.take<float>((size_t)(m > 0 ? m : 1));
+    w.arg_s = cv.take<long long>((size_t)(n > 0 ? n : 1));
+    w.arg_t = cv.take<long long>((size_t)(m > 0 ? m : 1));
+    w.flags = cv.take<int>((size_t)(n > 0 ? n : 1));
+    w.offs = cv.take<int>((size_t)(n > 0 ? n : 1));
+    w.scan = cv.take<char>(scan_ws_bytes(n));
+    return w;
+}
+
+}  // namespace
+}  // namespace pcrcg
+
+using namespace pcrcg;
+
+extern "C" {
+
+size_t pcrcg_ransac_ws_bytes(int n, int m, int max_iteration, int max_validation) {
+    if (n < 0 || m < 0 || max_iteration < 0 || max_validation < 0) return 0;
+    Carver a(nullptr, 0), b(nullptr, 0);
+    carve_match(a, n, m);
+    carve_ransac(b, max_iteration > 0 ? max_iteration : 1, max_validation > 0 ? max_validation : 1);
+    return a.off > b.off ? a.off : b.off;
+}
+
+int pcrcg_feature_match(const float* src_feat, int ld_src, int n, const float* tgt_feat, int ld_tgt, int m, int c, int mutual,
+                        int* corr, int* k, void* ws, size_t ws_bytes, void* stream) {
+    PCRCG_CHECK_ARG(src_feat && tgt_feat && corr && k && ws);
+    PCRCG_CHECK_ARG(n >= 1 && m >= 1 && c >= 1 && ld_src >= c && ld_tgt >= c);
+    PCRCG_CHECK_ARG(mutual == 0 || mutual == 1);
+    Carver cv(ws, ws_bytes);
+    MatchWs w = carve_match(cv, n, m);
+    PCRCG_CHECK_WS(cv);
+    hipStream_t st = as_stream(stream);
+    const int gx = (n + 255) / 256;
+    if (mutual) {
+        const size_t abytes = carve_bytes((size_t)(n > m ? n : m), 8);
+        PCRCG_PROPAGATE(pcrcg_feature_argmax(src_feat, ld_src, n, tgt_feat, ld_tgt, m, c,
+                                             reinterpret_cast<int64_t*>(w.arg_s), nullptr, w.packed, abytes, stream));
+        PCRCG_PROPAGATE(pcrcg_feature_argmax(tgt_feat, ld_tgt, m, src_feat, ld_src, n, c,
+                                             reinterpret_cast<int64_t*>(w.arg_t), nullptr, w.packed, abytes, stream));
+        hipLaunchKernelGGL(k_mutual_flags, dim3(gx), dim3(256), 0, st, w.arg_s, n, w.arg_t, w.flags);
+        PCRCG_CHECK_LAUNCH();
+        PCRCG_PROPAGATE(exclusive_scan_i32(w.flags, w.offs, n, k, w.scan, st));
+        hipLaunchKernelGGL(k_mutual_emit, dim3(gx), dim3(256), 0, st, w.flags, w.offs, n, w.arg_s, corr);
+        PCRCG_CHECK_LAUNCH();
+        return PCRCG_OK;
+    }
+    PCRCG_CHECK_HIP(hipMemsetAsync(w.packed, 0, (size_t)n * 8, st));
+    hipLaunchKernelGGL(k_half_norms, dim3((m + 255) / 256), dim3(256), 0, st, tgt_feat, ld_tgt, m, c, w.hb);
+    const bool aligned = ld_src % 4 == 0 && ld_tgt % 4 == 0 &&
+                         ((reinterpret_cast<uintptr_t>(src_feat) | reinterpret_cast<uintptr_t>(tgt_feat)) & 15) == 0;
+    if ((c == 32 || c == 64) && aligned) {
+        const int gxm = (n + 127) / 128;               // 128 rows per workgroup, column ranges for ~1k workgroups in flight
+        int splits = (1024 + gxm - 1) / gxm;
+        const int max_splits = (m + 255) / 256;
+        if (splits > max_splits) splits = max_splits;
+        if (splits < 1) splits = 1;
+        const int cols_per = ((m + splits - 1) / splits + 31) / 32 * 32;
+        const dim3 grid(gxm, (m + cols_per - 1) / cols_per);
+        if (c == 32)
+            hipLaunchKernelGGL(k_l2nn_mfma<32>, grid, dim3(256), 0, st, src_feat, ld_src, n, tgt_feat, ld_tgt, m, w.hb, cols_per,
+                               w.packed);
+        else
+            hipLaunchKernelGGL(k_l2nn_mfma<64>, grid, dim3(256), 0, st, src_feat, ld_src, n, tgt_feat, ld_tgt, m, w.hb, cols_per,
+                               w.packed);
+    } else {
+        int splits = (2048 + gx - 1) / gx;
+        const int max_splits = (m + 127) / 128;
+        if (splits > max_splits) splits = max_splits;
+        if (splits < 1) splits = 1;
+        const int cols_per = (m + splits - 1) / splits;
+        hipLaunchKernelGGL(k_l2nn_any, dim3(gx, (m + cols_per - 1) / cols_per), dim3(256), 0, st, src_feat, ld_src, n, tgt_feat,
+                           ld_tgt, m, c, w.hb, cols_per, w.packed);
+    }
+    hipLaunchKernelGGL(k_nn_emit, dim3(gx), dim3(256), 0, st, w.packed, n, corr, k);
+    PCRCG_CHECK_LAUNCH();
+    return PCRCG_OK;
+}
+
+int pcrcg_ransac(const float* src, int n, const float* tgt, int m, const void* grid, const int* corr, int k_max, const int* k,
+                 int ransac_n, double threshold, double edge_similarity, int distance_check, int max_iteration,
+                 int max_validation, uint64_t seed, double* out_transform, double* out_stats, const pcrcg_ransac_trace* trace,
+                 void* ws, size_t ws_bytes, void* stream) {
+    PCRCG_CHECK_ARG(src && tgt && grid && corr && k && out_transform && out_stats && ws);
+    PCRCG_CHECK_ARG(n >= 1 && m >= 1 && k_max >= 0);
+    PCRCG_CHECK_ARG(ransac_n >= 3 && ransac_n <= kMaxSample);
+    PCRCG_CHECK_ARG(k_max >= ransac_n);
+    PCRCG_CHECK_ARG(threshold > 0.0 && edge_similarity >= 0.0 && edge_similarity <= 1.0);
+    PCRCG_CHECK_ARG(distance_check == 0 || distance_check == 1);
+    PCRCG_CHECK_ARG(max_iteration >= 1 && max_iteration <= (1 << 27));
+    PCRCG_CHECK_ARG(max_validation >= 1 && max_validation <= max_iteration);
+    PCRCG_CHECK_ARG(seed < (1ull << 24));
+    Carver cv(ws, ws_bytes);
+    RansacWs w = carve_ransac(cv, max_iteration, max_validation);
+    PCRCG_CHECK_WS(cv);
+    bool ok;
+    GridView g = grid_view(const_cast<void*>(grid), grid_bytes(m, 1), m, 1, &ok);
+    hipStream_t st = as_stream(stream);
+    pcrcg_ransac_trace tr = {};
+    if (trace) tr = *trace;
+    HypArgs a;
+    a.src = src; a.tgt = tgt; a.corr = corr; a.k = k;
+    a.k_max = k_max; a.ransac_n = ransac_n; a.dist_check = distance_check; a.max_iteration = max_iteration;
+    a.thr = threshold; a.sim = edge_similarity; a.seed = seed;
+    const int gh = (max_iteration + 255) / 256;
+    hipLaunchKernelGGL(k_hypotheses, dim3(gh), dim3(256), 0, st, a, w.pass, w.xf, tr.samples, tr.pass, tr.xf32, tr.xf64);
+    PCRCG_CHECK_LAUNCH();
+    PCRCG_PROPAGATE(exclusive_scan_i32(w.pass, w.offs, max_iteration, w.npass, w.scan, st));
+    hipLaunchKernelGGL(k_compact, dim3(gh), dim3(256), 0, st, w.pass, w.offs, max_iteration, max_validation, w.vid, tr.valid_ids);
+    const float thr2 = (float)(threshold * threshold);
+    hipLaunchKernelGGL(k_evaluate, dim3(max_validation), dim3(kEvalThreads), 0, st, src, n, g, thr2, w.npass, max_validation, w.vid,
+                       w.xf, w.counts, w.sums, tr.counts, tr.sums);
+    hipLaunchKernelGGL(k_select, dim3(1), dim3(256), 0, st, a, n, w.npass, max_validation, w.vid, w.counts, w.sums, out_transform,
+                       out_stats);
+    PCRCG_CHECK_LAUNCH();
+    return PCRCG_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,214 @@
+"""Registration back end on the device: the step after the tester's probabilistic sampling
+(ref:lib/benchmark_utils.py:187-267, ref:lib/tester.py:152-169).
+
+  * `ransac_pose_estimation` -- the reference's entry point with its signature and defaults: feature matching +
+                                RANSAC, a float64 numpy [4,4] back.  open3d is not needed.
+  * `register`               -- the same with every result on the device (`RegistrationResult`), optionally the trace
+                                of every stage (`trace=True`, what tests/test_registration_gpu.py checks).
+  * `mutual_correspondences` -- the mutual pairs of the inner-product score ([K,2] int64 device tensor).
+  * `get_inlier_ratio`       -- device version of ref:lib/benchmark_utils.py:226-267 (same `w` / `wo` dict).
+  * `get_angle_deviation`    -- numpy, as ref:lib/benchmark_utils.py:175-185.
+
+The algorithm (csrc/register.hip, include/pcrcg.h "Registration back end") is deterministic: a
+seed fixes every draw, and two runs give the same bits.  `register` reads the device ONCE, after the selection
+(the transform and the statistics in one buffer); every call before it is enqueued on the current stream.
+"""
+import ctypes
+
+import numpy as np
+import torch
+
+from . import _lib
+
+# device -> host reads made by this module (one per `register` call; tests/test_registration_gpu.py counts them)
+D2H_READS = 0
+
+_N_STATS = 6   # fitness, inlier_rmse, K, iterations, validations, chosen hypothesis (-1: none)
+
+
+def _stream():
+    return torch.cuda.current_stream().cuda_stream
+
+
+def _device(*xs):
+    for x in xs:
+        if isinstance(x, torch.Tensor) and x.is_cuda:
+            return x.device
+    if not torch.cuda.is_available():
+        raise RuntimeError("pcrcg_amd.registration: no HIP device is visible (there is no CPU implementation)")
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+def _f32(x, dev, name, cols=None):
+    t = torch.as_tensor(np.asarray(x) if not isinstance(x, torch.Tensor) else x)
+    t = t.to(device=dev, dtype=torch.float32)
+    if t.dim() != 2 or (cols is not None and t.shape[1] != cols):
+        raise ValueError(f"{name} must be a [N, {cols or 'C'}] array, got shape {tuple(t.shape)}")
+    return t.contiguous()
+
+
+def _read(t):
+    """The module's one way to the host (counted)."""
+    global D2H_READS
+    D2H_READS += 1
+    return t.cpu().numpy()
+
+
+class RegistrationResult:
+    """transformation: float64 [4,4] device tensor; fitness, inlier_rmse, n_correspondences, iterations, validations:
+    host numbers; matrix: the transform on the host (from the same read); trace: dict of device tensors or None."""
+
+    def __init__(self, buf, host, trace):
+        self.transformation = buf[:16].view(4, 4)
+        self.matrix = host[:16].reshape(4, 4).copy()
+        self.fitness = float(host[16])
+        self.inlier_rmse = float(host[17])
+        self.n_correspondences = int(host[18])
+        self.iterations = int(host[19])
+        self.validations = int(host[20])
+        self.chosen = int(host[21])
+        self.trace = trace
+
+    def __repr__(self):
+        return (f"RegistrationResult(fitness={self.fitness:.6g}, inlier_rmse={self.inlier_rmse:.6g}, "
+                f"n_correspondences={self.n_correspondences}, iterations={self.iterations}, validations={self.validations})")
+
+
+class _Trace(ctypes.Structure):
+    """Mirror of pcrcg_ransac_trace (include/pcrcg.h)."""
+    _fields_ = [(f, ctypes.c_void_p) for f in ("samples", "pass_", "xf32", "xf64", "valid_ids", "counts", "sums")]
+
+
+def _workspace(n, m, max_iteration, max_validation, dev):
+    nbytes = _lib.lib().pcrcg_ransac_ws_bytes(n, m, max_iteration, max_validation)
+    return torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev), nbytes
+
+
+def feature_match(src_feat, tgt_feat, mutual=False, ws=None):
+    """-> (corr [n,2] int32 device, k [1] int32 device): the first k rows are the correspondence list (pcrcg_feature_match).
+    mutual=False: row i = (i, nearest target in L2 feature distance), k = n; mutual=True: the mutual arg-max pairs of
+    <src, tgt> in ascending source order."""
+    dev = _device(src_feat, tgt_feat)
+    a = _f32(src_feat, dev, "src_feat")
+    b = _f32(tgt_feat, dev, "tgt_feat", a.shape[1])
+    n, m, c = a.shape[0], b.shape[0], a.shape[1]
+    if n == 0 or m == 0:
+        raise ValueError("feature_match: empty descriptor set")
+    if ws is None:
+        ws = _workspace(n, m, 1, 1, dev)
+    corr = torch.empty((n, 2), dtype=torch.int32, device=dev)
+    k = torch.empty(1, dtype=torch.int32, device=dev)
+    L = _lib.lib()
+    _lib.check(L.pcrcg_feature_match(a.data_ptr(), c, n, b.data_ptr(), c, m, c, int(bool(mutual)), corr.data_ptr(),
+                                     k.data_ptr(), ws[0].data_ptr(), ws[1], _stream()), "pcrcg_feature_match")
+    return corr, k
+
+
+def mutual_correspondences(src_feat, tgt_feat):
+    """[K,2] int64 device tensor of (source, target): j = argmax_j <f_i, g_j> and i = argmax_i <f_i, g_j> (the
+    reference's mutual_selection on torch.matmul(src_feat, tgt_feat.T); first index on ties), ascending source index.
+    Slicing to K reads K back."""
+    corr, k = feature_match(src_feat, tgt_feat, mutual=True)
+    return corr[:int(_read(k)[0])].to(torch.int64)
+
+
+def register(src_pcd, tgt_pcd, src_feat, tgt_feat, mutual=False, distance_threshold=0.05, ransac_n=3, *,
+             max_iteration=50000, max_validation=1000, seed=0, edge_similarity=None, distance_check=None, trace=False):
+    """Feature matching + RANSAC (include/pcrcg.h "Registration back end") -> RegistrationResult.
+
+    Inputs: [N,3] / [M,3] points and [N,C] / [M,C] descriptors as HIP tensors, or CPU tensors / numpy arrays (uploaded).
+    mutual=False: nearest-neighbour correspondences, the checkers of the reference (edge length 0.9, distance) unless
+    overridden; mutual=True: mutual pairs, no checkers.  One device-to-host read (at the end)."""
+    dev = _device(src_pcd, tgt_pcd, src_feat, tgt_feat)
+    src = _f32(src_pcd, dev, "src_pcd", 3)
+    tgt = _f32(tgt_pcd, dev, "tgt_pcd", 3)
+    n, m = src.shape[0], tgt.shape[0]
+    if n < ransac_n:
+        raise ValueError(f"register: {n} source points, fewer than ransac_n = {ransac_n}")
+    if m == 0:
+        raise ValueError("register: empty target cloud")
+    thr = float(distance_threshold)
+    if edge_similarity is None:
+        edge_similarity = 0.0 if mutual else 0.9
+    if distance_check is None:
+        distance_check = not mutual
+    if len(src_feat) != n or len(tgt_feat) != m:
+        raise ValueError("register: the descriptors must have one row per point")
+    ws = _workspace(n, m, int(max_iteration), int(max_validation), dev)
+    corr, k = feature_match(src_feat, tgt_feat, mutual, ws)
+    L = _lib.lib()
+    gbytes = L.pcrcg_cellgrid_ws_bytes(m, 1)
+    grid = torch.empty(gbytes, dtype=torch.uint8, device=dev)
+    lengths = torch.tensor([m], dtype=torch.int32, device=dev)
+    _lib.check(L.pcrcg_cellgrid_build(tgt.data_ptr(), m, lengths.data_ptr(), 1, thr, grid.data_ptr(), gbytes, _stream()),
+               "pcrcg_cellgrid_build")
+    out = torch.empty(16 + _N_STATS, dtype=torch.float64, device=dev)
+    tr, tr_ptr = None, None
+    if trace:
+        mi, mv = int(max_iteration), int(max_validation)
+        tr = {"samples": torch.full((mi, ransac_n), -1, dtype=torch.int32, device=dev),
+              "pass": torch.zeros(mi, dtype=torch.int32, device=dev),
+              "xf32": torch.zeros((mi, 12), dtype=torch.float32, device=dev),
+              "xf64": torch.zeros((mi, 12), dtype=torch.float64, device=dev),
+              "valid_ids": torch.full((mv,), -1, dtype=torch.int32, device=dev),
+              "counts": torch.full((mv,), -1, dtype=torch.int32, device=dev),
+              "sums": torch.zeros(mv, dtype=torch.float64, device=dev),
+              "corr": corr, "k": k}
+        tr_ptr = ctypes.byref(_Trace(*[tr[f].data_ptr() for f in ("samples", "pass", "xf32", "xf64", "valid_ids", "counts",
+                                                                    "sums")]))
+    _lib.check(L.pcrcg_ransac(src.data_ptr(), n, tgt.data_ptr(), m, grid.data_ptr(), corr.data_ptr(), n, k.data_ptr(),
+                              int(ransac_n), thr, float(edge_similarity), int(bool(distance_check)), int(max_iteration),
+                              int(max_validation), int(seed), out.data_ptr(), out[16:].data_ptr(), tr_ptr, ws[0].data_ptr(),
+                              ws[1], _stream()), "pcrcg_ransac")
+    res = RegistrationResult(out, _read(out), tr)
+    if res.n_correspondences < ransac_n:
+        raise ValueError(f"register: {res.n_correspondences} correspondences, fewer than ransac_n = {ransac_n}")
+    return res
+
+
+def ransac_pose_estimation(src_pcd, tgt_pcd, src_feat, tgt_feat, mutual=False, distance_threshold=0.05, ransac_n=3, *,
+                           max_iteration=50000, max_validation=1000, seed=0):
+    """ref:lib/benchmark_utils.py:187-224 -> float64 numpy [4,4].  As in the reference, the mutual branch runs with
+    ransac_n = 4 and no checkers, the other one with the edge-length (0.9) and distance checkers."""
+    if mutual:
+        ransac_n = 4
+    return register(src_pcd, tgt_pcd, src_feat, tgt_feat, mutual, distance_threshold, ransac_n,
+                    max_iteration=max_iteration, max_validation=max_validation, seed=seed).matrix
+
+
+def get_inlier_ratio(src_pcd, tgt_pcd, src_feat, tgt_feat, rot, trans, inlier_distance_threshold=0.1):
+    """ref:lib/benchmark_utils.py:226-267 on the device: {'wo': {'distance', 'inlier_ratio'}, 'w': {...}} for the
+    arg-max matches without and with the mutual check (distances as numpy arrays, ratios as 0-d tensors)."""
+    dev = _device(src_pcd, tgt_pcd, src_feat, tgt_feat)
+    src = _f32(src_pcd, dev, "src_pcd", 3)
+    tgt = _f32(tgt_pcd, dev, "tgt_pcd", 3)
+    a = _f32(src_feat, dev, "src_feat")
+    b = _f32(tgt_feat, dev, "tgt_feat", a.shape[1])
+    rot = torch.as_tensor(np.asarray(rot) if not isinstance(rot, torch.Tensor) else rot).to(dev, torch.float32).reshape(3, 3)
+    trans = torch.as_tensor(np.asarray(trans) if not isinstance(trans, torch.Tensor) else trans).to(dev, torch.float32)
+    moved = (rot @ src.t() + trans.reshape(3, 1)).t()
+    n, m, c = a.shape[0], b.shape[0], a.shape[1]
+    L = _lib.lib()
+    arg = torch.empty(n, dtype=torch.int64, device=dev)
+    wsb = L.pcrcg_feature_argmax_ws_bytes(n)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    _lib.check(L.pcrcg_feature_argmax(a.data_ptr(), c, n, b.data_ptr(), c, m, c, arg.data_ptr(), None, ws.data_ptr(), wsb,
+                                      _stream()), "pcrcg_feature_argmax")
+    results = {"w": {}, "wo": {}}
+    dist = torch.linalg.norm(moved - tgt[arg], dim=1)
+    results["wo"]["distance"] = _read(dist)
+    results["wo"]["inlier_ratio"] = torch.as_tensor((results["wo"]["distance"] < inlier_distance_threshold).mean(),
+                                                    dtype=torch.float32)
+    pairs = mutual_correspondences(a, b)
+    dist = torch.linalg.norm(moved[pairs[:, 0]] - tgt[pairs[:, 1]], dim=1)
+    results["w"]["distance"] = _read(dist)
+    results["w"]["inlier_ratio"] = torch.as_tensor((results["w"]["distance"] < inlier_distance_threshold).mean(),
+                                                   dtype=torch.float32)
+    return results
+
+
+def get_angle_deviation(R_pred, R_gt):
+    """Rotation error in degrees of batches [B,3,3] (ref:lib/benchmark_utils.py:175-185): arccos((tr(R_pred R_gt^T) - 1)/2)."""
+    R = np.matmul(R_pred, np.transpose(R_gt, (0, 2, 1)))
+    tr = np.trace(R, 0, 1, 2)
+    return np.arccos(np.clip((tr - 1) / 2, -1, 1)) / np.pi * 180

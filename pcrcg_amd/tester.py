@@ -8,7 +8,8 @@ registration back end.
                        replacement that precedes RANSAC (ref:lib/tester.py:152-164).  It draws from the HOST numpy
                        generator exactly as the reference does (np.random.choice), so a seeded run picks the same
                        points; only the scores cross the bus (two [N] vectors).
-RANSAC itself (open3d) is downstream of the path and out of scope."""
+  * `register_record` -- the loop of the 3DMatch evaluation and of KITTITester (ref:lib/tester.py:140-169): sampling on
+                       both sides, then RANSAC on the device (pcrcg_amd/registration.py; open3d is not needed)."""
 import numpy as np
 import torch
 
@@ -54,3 +55,16 @@ def probabilistic_sample(pcd, feats, scores, n_points):
     idx = np.random.choice(np.arange(pcd.shape[0]), size=n_points, replace=False, p=probs)
     sel = torch.from_numpy(idx).to(pcd.device)
     return pcd[sel], feats[sel], idx
+
+
+def register_record(record, n_points=5000, distance_threshold=0.05, ransac_n=3, seed=0):
+    """-> float64 numpy [4,4]: the estimated pose of one `test_record` -- probabilistic_sample of each side on
+    overlap x saliency, then ransac_pose_estimation (3DMatch: 5000 points, 0.05, n = 3; KITTI: 0.3, n = 4)."""
+    from .registration import ransac_pose_estimation
+    ls = record["len_src"]
+    pcd, feats = record["pcd"], record["feats"]
+    scores = record["overlaps"] * record["saliency"]
+    src_pcd, src_feats, _ = probabilistic_sample(pcd[:ls], feats[:ls], scores[:ls], n_points)
+    tgt_pcd, tgt_feats, _ = probabilistic_sample(pcd[ls:], feats[ls:], scores[ls:], n_points)
+    return ransac_pose_estimation(src_pcd, tgt_pcd, src_feats, tgt_feats, mutual=False,
+                                  distance_threshold=distance_threshold, ransac_n=ransac_n, seed=seed)
