@@ -51,7 +51,8 @@ const char* pcrcg_last_error(void);
  *                (level 0's, and one over the subsampled levels) on pcrcg_pyramid_cfg::side_stream (new cfg fields; pcrcg_pyramid_ws_bytes lost its `shrink`
  *                argument; pcrcg_pyramid_restore and pcrcg_reorder_job changed layout)
  *   The registration back end (pcrcg_ransac_ws_bytes, pcrcg_feature_match, pcrcg_ransac, pcrcg_ransac_trace) was added
- *   under version 4: it is additive -- no existing signature, layout or arithmetic changed. */
+ *   under version 4: it is additive -- no existing signature, layout or arithmetic changed.  So are its several-pairs
+ *   entries (pcrcg_ransac_batch_ws_bytes, pcrcg_feature_match_batch, pcrcg_ransac_batch), added later under version 4. */
 #define PCRCG_ABI_VERSION 4
 int pcrcg_abi_version(void);
 
@@ -714,6 +715,40 @@ int pcrcg_ransac(const float* src, int n, const float* tgt, int m, const void* g
                  int ransac_n, double threshold, double edge_similarity, int distance_check, int max_iteration,
                  int max_validation, uint64_t seed, double* out_transform, double* out_stats, const pcrcg_ransac_trace* trace,
                  void* ws, size_t ws_bytes, void* stream);
+
+/* Several pairs per call: B independent pairs in one set of launches.  Pair b's result is exactly (bit for bit: transform,
+ * statistics) that of pcrcg_feature_match with mutual = 0 followed by pcrcg_ransac on that pair alone with seed = seeds[b];
+ * no pair affects another, and nothing depends on the order of the pairs or on B (no floating-point atomics).
+ * Mutual correspondences are not offered here (every reference tester uses mutual = False).
+ *   Layout: the pairs are ragged and concatenated.  src [n_total, 3], tgt [m_total, 3] f32; src_off / tgt_off [B + 1] i32
+ *   DEVICE arrays of row offsets (src_off[0] = 0, non-decreasing, src_off[B] = n_total; likewise tgt_off); descriptors
+ *   [n_total, c] / [m_total, c] with row strides ld_src / ld_tgt.  corr [n_total, 2] i32: pair b's rows start at
+ *   src_off[b] and hold indices local to the pair; k [B] i32 its list lengths (= n_b).  seeds [B] u64 (DEVICE, each
+ *   < 2^24), out_transform [B, 16] f64, out_stats [B, 6] f64 as pcrcg_ransac's, pair by pair.
+ *   grid = pcrcg_cellgrid_build over the m_total concatenated targets with nb = B, slen = the pair lengths and
+ *   radius = (float)threshold; pair b is looked up in its own hash table (the 2 m_b slots at 2 tgt_off[b]).
+ *   n_max / m_max (host) must be >= every pair's source / target length; they only size the launch grids of
+ *   pcrcg_feature_match_batch;
+ *   pcrcg_ransac_batch needs m_total instead, because the grid's layout depends on it.  ransac_n, threshold, the checkers
+ *   and the iteration and validation caps are the same for every pair of one call.
+ *   The offsets and seeds live on the device and are not read by the host: a pair with n_b < ransac_n or m_b = 0 gets the
+ *   identity (as when nothing passes), and a pair whose seed is >= 2^24 gets NaN in all of its 22 outputs.
+ * Workspace: pcrcg_ransac_batch_ws_bytes(B, n_total, m_total, max_iteration, max_validation) bytes, one size for both
+ * entries (reused on the same stream) = max(8 n_total + 4 m_total,
+ *   8 B max_iteration + 64 B max_validation + scan(B max_iteration)) plus alignment padding, with scan(x) the device-wide
+ *   scan's scratch -- about 0.47 MB per pair at 50 000 / 1 000.  Unlike pcrcg_ransac, the fp32 R|t is kept for the
+ *   validated hypotheses only (re-fitted after the compaction), not for all of them.  B <= 65535 and
+ *   B * max_iteration < 2^31; 0 is returned for arguments out of range.  Both entries allocate nothing and synchronise
+ *   nothing; bad arguments (null pointers, B outside 1..65535, and every rule of the single-pair entries that the host can
+ *   check) are rejected with PCRCG_EBADARG before anything launches. */
+size_t pcrcg_ransac_batch_ws_bytes(int B, int n_total, int m_total, int max_iteration, int max_validation);
+int pcrcg_feature_match_batch(const float* src_feat, int ld_src, const int* src_off, int n_total, int n_max,
+                              const float* tgt_feat, int ld_tgt, const int* tgt_off, int m_total, int m_max, int c, int B,
+                              int* corr, int* k, void* ws, size_t ws_bytes, void* stream);
+int pcrcg_ransac_batch(const float* src, const int* src_off, const float* tgt, const int* tgt_off, int m_total, const void* grid,
+                       const int* corr, const int* k, int B, int ransac_n, double threshold, double edge_similarity,
+                       int distance_check, int max_iteration, int max_validation, const uint64_t* seeds,
+                       double* out_transform, double* out_stats, void* ws, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -19,6 +19,10 @@
 //   selection : highest count, then lowest sum, then lowest h; the float64 transform of the winner is re-fitted from its
 //               samples (the same device function) and written with the statistics.
 //
+// Several pairs per call (pcrcg_feature_match_batch, pcrcg_ransac_batch): the same stages with the pair as a grid
+// dimension, each kernel running the single-pair device code (the inline bodies below and hypothesis()) on a per-pair
+// view, one device-wide scan over all pairs' flags; so pair b's result is the single-pair result bit for bit.
+//
 // Compiled with -ffp-contract=off: every fp32 and fp64 operation rounds where the source says, so the numpy restatement
 // reproduces the evaluation's counts exactly.
 #include "block_scan.h"
@@ -67,16 +71,17 @@ __global__ void __launch_bounds__(256) k_half_norms(const float* __restrict__ b,
 // columns congruent to its lane index (strictly greater: the smaller column survives a tie), the 32 lanes of a row meet by
 // shuffles, and the column ranges (grid.y) by a 64-bit atomicMax.
 typedef float rg_f16 __attribute__((ext_vector_type(16)));
+// The body is shared with the batch kernel (pair = grid.z): bx / by are the row block and the column range.
 template <int C>
-__global__ void __launch_bounds__(256) k_l2nn_mfma(const float* __restrict__ a, int lda, int n, const float* __restrict__ b,
-                                                   int ldb, int m, const float* __restrict__ hb, int cols_per,
-                                                   u64* __restrict__ packed) {
+__device__ __forceinline__ void l2nn_mfma_tile(const float* a, int lda, int n, const float* b, int ldb,
+                                               int m, const float* hb, int cols_per, u64* packed,
+                                               unsigned bx, unsigned by) {
     constexpr int NV = C / 2;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int l31 = lane & 31, half = lane >> 5;
-    const int row0 = (blockIdx.x * 4 + wave) * 32;
+    const int row0 = (bx * 4 + wave) * 32;
     if (row0 >= n) return;
-    const int jbeg = blockIdx.y * cols_per, jend = min(m, jbeg + cols_per);
+    const int jbeg = by * cols_per, jend = min(m, jbeg + cols_per);
     if (jbeg >= jend) return;
     float av[NV];
     {
@@ -128,13 +133,31 @@ __global__ void __launch_bounds__(256) k_l2nn_mfma(const float* __restrict__ a, 
     }
 }
 
+template <int C>
+__global__ void __launch_bounds__(256) k_l2nn_mfma(const float* __restrict__ a, int lda, int n, const float* __restrict__ b,
+                                                   int ldb, int m, const float* __restrict__ hb, int cols_per,
+                                                   u64* __restrict__ packed) {
+    l2nn_mfma_tile<C>(a, lda, n, b, ldb, m, hb, cols_per, packed, blockIdx.x, blockIdx.y);
+}
+
+// several pairs: pair p = blockIdx.z owns source rows a_off[p] .. a_off[p+1] and target rows b_off[p] .. b_off[p+1]; its
+// column indices are local to the pair
+template <int C>
+__global__ void __launch_bounds__(256) k_l2nn_mfma_batch(const float* __restrict__ a, int lda, const int* __restrict__ a_off,
+                                                         const float* __restrict__ b, int ldb, const int* __restrict__ b_off,
+                                                         const float* __restrict__ hb, int cols_per, u64* __restrict__ packed) {
+    const int p = blockIdx.z;
+    const int i0 = a_off[p], j0 = b_off[p];
+    l2nn_mfma_tile<C>(a + (long)i0 * lda, lda, a_off[p + 1] - i0, b + (long)j0 * ldb, ldb, b_off[p + 1] - j0, hb + j0, cols_per,
+                      packed + i0, blockIdx.x, blockIdx.y);
+}
+
 // any width (and unaligned operands): one thread per row of A, a column range per grid.y
-__global__ void __launch_bounds__(256) k_l2nn_any(const float* __restrict__ a, int lda, int n, const float* __restrict__ b,
-                                                  int ldb, int m, int c, const float* __restrict__ hb, int cols_per,
-                                                  u64* __restrict__ packed) {
-    const int row = blockIdx.x * 256 + threadIdx.x;
+__device__ __forceinline__ void l2nn_any_row(const float* a, int lda, int n, const float* b, int ldb,
+                                             int m, int c, const float* hb, int cols_per, u64* packed,
+                                             int row, unsigned by) {
     if (row >= n) return;
-    const int jbeg = blockIdx.y * cols_per, jend = min(m, jbeg + cols_per);
+    const int jbeg = by * cols_per, jend = min(m, jbeg + cols_per);
     if (jbeg >= jend) return;
     float bv = -INFINITY;
     int bj = jbeg;
@@ -147,6 +170,21 @@ __global__ void __launch_bounds__(256) k_l2nn_any(const float* __restrict__ a, i
     atomicMax(&packed[row], pack_max(bv, bj));
 }
 
+__global__ void __launch_bounds__(256) k_l2nn_any(const float* __restrict__ a, int lda, int n, const float* __restrict__ b,
+                                                  int ldb, int m, int c, const float* __restrict__ hb, int cols_per,
+                                                  u64* __restrict__ packed) {
+    l2nn_any_row(a, lda, n, b, ldb, m, c, hb, cols_per, packed, blockIdx.x * 256 + threadIdx.x, blockIdx.y);
+}
+
+__global__ void __launch_bounds__(256) k_l2nn_any_batch(const float* __restrict__ a, int lda, const int* __restrict__ a_off,
+                                                        const float* __restrict__ b, int ldb, const int* __restrict__ b_off, int c,
+                                                        const float* __restrict__ hb, int cols_per, u64* __restrict__ packed) {
+    const int p = blockIdx.z;
+    const int i0 = a_off[p], j0 = b_off[p];
+    l2nn_any_row(a + (long)i0 * lda, lda, a_off[p + 1] - i0, b + (long)j0 * ldb, ldb, b_off[p + 1] - j0, c, hb + j0, cols_per,
+                 packed + i0, blockIdx.x * 256 + threadIdx.x, blockIdx.y);
+}
+
 // non-mutual list: row i = (i, nn(i)), K = n
 __global__ void __launch_bounds__(256) k_nn_emit(const u64* __restrict__ packed, int n, int* __restrict__ corr, int* __restrict__ k) {
     const int i = blockIdx.x * 256 + threadIdx.x;
@@ -154,6 +192,17 @@ __global__ void __launch_bounds__(256) k_nn_emit(const u64* __restrict__ packed,
     if (i >= n) return;
     corr[2 * i] = i;
     corr[2 * i + 1] = (int)(0xFFFFFFFFu - (unsigned)(packed[i] & 0xFFFFFFFFull));
+}
+
+// the same per pair (grid.y): rows of pair p at off[p] .., indices local to the pair, k[p] = its length
+__global__ void __launch_bounds__(256) k_nn_emit_batch(const u64* __restrict__ packed, const int* __restrict__ off,
+                                                       int* __restrict__ corr, int* __restrict__ k) {
+    const int p = blockIdx.y, i0 = off[p], n = off[p + 1] - i0;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i == 0) k[p] = n;
+    if (i >= n) return;
+    corr[2 * (long)(i0 + i)] = i;
+    corr[2 * (long)(i0 + i) + 1] = (int)(0xFFFFFFFFu - (unsigned)(packed[i0 + i] & 0xFFFFFFFFull));
 }
 
 // mutual list: i is kept iff the arg-max of its row points at a column whose arg-max is i
@@ -324,22 +373,15 @@ __global__ void __launch_bounds__(256) k_compact(const int* __restrict__ pass, c
 }
 
 // ---- evaluation: one workgroup per validated hypothesis ----------------------------------------------------------
-__global__ void __launch_bounds__(kEvalThreads) k_evaluate(const float* __restrict__ src, int n, GridView g, float thr2,
-                                                           const int* __restrict__ npass, int max_validation,
-                                                           const int* __restrict__ vid, const float* __restrict__ xf,
-                                                           int* __restrict__ counts, double* __restrict__ sums,
-                                                           int* __restrict__ tr_counts, double* __restrict__ tr_sums) {
-    __shared__ int s_c[kEvalThreads];
-    __shared__ double s_s[kEvalThreads];
-    const int v = blockIdx.x;
-    const int nv = min(*npass, max_validation);
-    if (v >= nv) return;
-    const int h = vid[v];
+// The workgroup's count and float64 sum of the inliers of transform xf[0..11] over src [n, 3]; the target cloud is m
+// supports whose hash table is the 2 m slots at tab.  Shared by k_evaluate and k_evaluate_batch; the totals are left in
+// s_c[0] / s_s[0].
+__device__ __forceinline__ void evaluate_block(const float* src, int n, const GridView& g, const Slot* tab, int m,
+                                               float thr2, const float* xf, int* s_c, double* s_s) {
     float T[12];
 #pragma unroll
-    for (int e = 0; e < 12; ++e) T[e] = xf[12 * (long)h + e];
+    for (int e = 0; e < 12; ++e) T[e] = xf[e];
     const double inv_cell = g.hdr->inv_cell;
-    const int m = g.hdr->ns;
     const unsigned tsize = 2u * (unsigned)m;
     int cnt = 0;
     double sum = 0.0;
@@ -356,7 +398,7 @@ __global__ void __launch_bounds__(kEvalThreads) k_evaluate(const float* __restri
             unsigned s = __umulhi(mix32(key), tsize);
             int cnt_c = 0, start = 0;
             for (unsigned probe = 0; probe < tsize; ++probe) {
-                const Slot sl = load_slot(&g.tab[s]);
+                const Slot sl = load_slot(&tab[s]);
                 if (sl.key == key) { cnt_c = sl.cnt; start = sl.start; break; }
                 if (sl.key == kEmptyKey) break;
                 s = s + 1 == tsize ? 0 : s + 1;
@@ -380,6 +422,20 @@ __global__ void __launch_bounds__(kEvalThreads) k_evaluate(const float* __restri
         }
         __syncthreads();
     }
+}
+
+__global__ void __launch_bounds__(kEvalThreads) k_evaluate(const float* __restrict__ src, int n, GridView g, float thr2,
+                                                           const int* __restrict__ npass, int max_validation,
+                                                           const int* __restrict__ vid, const float* __restrict__ xf,
+                                                           int* __restrict__ counts, double* __restrict__ sums,
+                                                           int* __restrict__ tr_counts, double* __restrict__ tr_sums) {
+    __shared__ int s_c[kEvalThreads];
+    __shared__ double s_s[kEvalThreads];
+    const int v = blockIdx.x;
+    const int nv = min(*npass, max_validation);
+    if (v >= nv) return;
+    const int h = vid[v];
+    evaluate_block(src, n, g, g.tab, g.hdr->ns, thr2, xf + 12 * (long)h, s_c, s_s);
     if (threadIdx.x == 0) {
         counts[v] = s_c[0];
         sums[v] = s_s[0];
@@ -393,13 +449,13 @@ __device__ inline bool better(int c1, double s1, int h1, int c2, double s2, int 
     return c1 > c2 || (c1 == c2 && (s1 < s2 || (s1 == s2 && h1 < h2)));
 }
 
-__global__ void __launch_bounds__(256) k_select(HypArgs a, int n, const int* __restrict__ npass, int max_validation,
-                                                const int* __restrict__ vid, const int* __restrict__ counts,
-                                                const double* __restrict__ sums, double* __restrict__ out_t,
-                                                double* __restrict__ out_stats) {
+// The best of the nv validated hypotheses vid[0..nv) of one pair (one workgroup of 256), re-fitted, and the statistics.
+// Shared by k_select and k_select_batch.
+__device__ __forceinline__ void select_block(const HypArgs& a, int n, int nv, const int* vid,
+                                             const int* counts, const double* sums,
+                                             double* out_t, double* out_stats) {
     __shared__ int s_c[256], s_h[256];
     __shared__ double s_s[256];
-    const int nv = min(*npass, max_validation);
     int bc = -1, bh = 0x7FFFFFFF;
     double bs = 0.0;
     for (int v = threadIdx.x; v < nv; v += 256) {
@@ -441,6 +497,116 @@ __global__ void __launch_bounds__(256) k_select(HypArgs a, int n, const int* __r
     out_stats[3] = (double)a.max_iteration;
     out_stats[4] = (double)nv;
     out_stats[5] = chosen;
+}
+
+__global__ void __launch_bounds__(256) k_select(HypArgs a, int n, const int* __restrict__ npass, int max_validation,
+                                                const int* __restrict__ vid, const int* __restrict__ counts,
+                                                const double* __restrict__ sums, double* __restrict__ out_t,
+                                                double* __restrict__ out_stats) {
+    select_block(a, n, min(*npass, max_validation), vid, counts, sums, out_t, out_stats);
+}
+
+// ---- several pairs per call -----------------------------------------------------------------------------------------
+// Pair p is the single-pair problem on src[src_off[p] ..], tgt[tgt_off[p] ..], corr rows from src_off[p] (local indices),
+// k[p] and seeds[p]; every kernel below takes the pair from a grid dimension and runs the single-pair device code on it.
+struct BatchArgs {
+    const float* src;
+    const int* src_off;
+    const float* tgt;
+    const int* tgt_off;
+    const int* corr;
+    const int* k;
+    const u64* seeds;
+    int ransac_n, dist_check, max_iteration, max_validation;
+    double thr, sim;
+};
+
+__device__ inline HypArgs pair_args(const BatchArgs& b, int p) {
+    const int i0 = b.src_off[p], j0 = b.tgt_off[p];
+    HypArgs a;
+    a.src = b.src + 3 * (long)i0; a.tgt = b.tgt + 3 * (long)j0; a.corr = b.corr + 2 * (long)i0; a.k = b.k + p;
+    a.k_max = b.src_off[p + 1] - i0; a.ransac_n = b.ransac_n; a.dist_check = b.dist_check; a.max_iteration = b.max_iteration;
+    a.thr = b.thr; a.sim = b.sim; a.seed = b.seeds[p];
+    return a;
+}
+
+// passing hypotheses of pair p before the pair's first flag (offs = exclusive scan of all B * max_iteration flags, total =
+// its grand total) -> the pair's count
+__device__ inline int pair_npass(const int* offs, const int* total, int p, int B, int max_iteration) {
+    const int end = p + 1 < B ? offs[(long)(p + 1) * max_iteration] : *total;
+    return end - offs[(long)p * max_iteration];
+}
+
+// grid (hypothesis blocks, pair): the pass flag only; a pair with an empty target passes nothing (its corr rows point at
+// target 0, which it does not have)
+__global__ void __launch_bounds__(256) k_hypotheses_batch(BatchArgs b, int* __restrict__ pass) {
+    const int p = blockIdx.y, h = blockIdx.x * 256 + threadIdx.x;
+    if (h >= b.max_iteration) return;
+    const HypArgs a = pair_args(b, p);
+    int rows[kMaxSample];
+    double R[9], t[3];
+    const bool ok = b.tgt_off[p + 1] > b.tgt_off[p] && hypothesis(a, h, list_size(a), rows, R, t);
+    pass[(long)p * b.max_iteration + h] = ok ? 1 : 0;
+}
+
+// vid[p, o] = the pair-local h of the pair's o-th passing hypothesis, o < max_validation
+__global__ void __launch_bounds__(256) k_compact_batch(const int* __restrict__ pass, const int* __restrict__ offs, int max_iteration,
+                                                       int max_validation, int* __restrict__ vid) {
+    const int p = blockIdx.y, h = blockIdx.x * 256 + threadIdx.x;
+    const long g = (long)p * max_iteration + h;
+    if (h >= max_iteration || !pass[g]) return;
+    const int o = offs[g] - offs[(long)p * max_iteration];
+    if (o < max_validation) vid[(long)p * max_validation + o] = h;
+}
+
+// the fp32 R|t of the validated hypotheses only (the single-pair path keeps it for every hypothesis): hypothesis() is
+// deterministic, so the refit is the same bits as the fit of k_hypotheses_batch
+__global__ void __launch_bounds__(256) k_refit_batch(BatchArgs b, const int* __restrict__ offs, const int* __restrict__ total, int B,
+                                                     const int* __restrict__ vid, float* __restrict__ xf) {
+    const int p = blockIdx.y, v = blockIdx.x * 256 + threadIdx.x;
+    if (v >= min(pair_npass(offs, total, p, B, b.max_iteration), b.max_validation)) return;
+    const long slot = (long)p * b.max_validation + v;
+    const HypArgs a = pair_args(b, p);
+    int rows[kMaxSample];
+    double R[9], t[3];
+    hypothesis(a, vid[slot], list_size(a), rows, R, t);
+    for (int e = 0; e < 9; ++e) xf[12 * slot + e] = (float)R[e];
+    for (int e = 0; e < 3; ++e) xf[12 * slot + 9 + e] = (float)t[e];
+}
+
+// grid (validated hypothesis, pair); pair p's table in the grid over all targets is the 2 m_p slots at 2 tgt_off[p]
+__global__ void __launch_bounds__(kEvalThreads) k_evaluate_batch(BatchArgs b, GridView g, float thr2, const int* __restrict__ offs,
+                                                                 const int* __restrict__ total, int B, const float* __restrict__ xf,
+                                                                 int* __restrict__ counts, double* __restrict__ sums) {
+    __shared__ int s_c[kEvalThreads];
+    __shared__ double s_s[kEvalThreads];
+    const int p = blockIdx.y, v = blockIdx.x;
+    if (v >= min(pair_npass(offs, total, p, B, b.max_iteration), b.max_validation)) return;
+    const long slot = (long)p * b.max_validation + v;
+    const int i0 = b.src_off[p], j0 = b.tgt_off[p];
+    evaluate_block(b.src + 3 * (long)i0, b.src_off[p + 1] - i0, g, g.tab + 2 * (long)j0, b.tgt_off[p + 1] - j0, thr2,
+                   xf + 12 * slot, s_c, s_s);
+    if (threadIdx.x == 0) {
+        counts[slot] = s_c[0];
+        sums[slot] = s_s[0];
+    }
+}
+
+// one workgroup per pair; a seed >= 2^24 (not checkable on the host: seeds live on the device) gives NaN outputs
+__global__ void __launch_bounds__(256) k_select_batch(BatchArgs b, const int* __restrict__ offs, const int* __restrict__ total, int B,
+                                                      const int* __restrict__ vid, const int* __restrict__ counts,
+                                                      const double* __restrict__ sums, double* __restrict__ out_t,
+                                                      double* __restrict__ out_stats) {
+    const int p = blockIdx.x;
+    if (b.seeds[p] >= (1ull << 24)) {
+        if (threadIdx.x < 16) out_t[16 * (long)p + threadIdx.x] = __builtin_nan("");
+        if (threadIdx.x < 6) out_stats[6 * (long)p + threadIdx.x] = __builtin_nan("");
+        return;
+    }
+    const long base = (long)p * b.max_validation;
+    select_block(pair_args(b, p), b.src_off[p + 1] - b.src_off[p],
+                 min(pair_npass(offs, total, p, B, b.max_iteration), b.max_validation), vid + base, counts + base, sums + base,
+                 out_t + 16 * (long)p, out_stats + 6 * (long)p);
 }
 
 struct RansacWs {
@@ -489,6 +655,39 @@ MatchWs carve_match(Carver& cv, int n, int m) {
     w.scan = cv.take<char>(scan_ws_bytes(n));
     return w;
 }
+
+// Batch workspace: the match stage and the RANSAC stage reuse the same bytes (as in the single-pair path).
+struct BatchWs {
+    u64* packed;   // [n_total]
+    float* hb;     // [m_total]
+    int* pass;     // [B * max_iteration]
+    int* offs;     // [B * max_iteration]
+    int* npass;    // [1]  grand total of the scan
+    int* vid;      // [B * max_validation]
+    float* xf;     // [B * max_validation * 12]
+    int* counts;   // [B * max_validation]
+    double* sums;  // [B * max_validation]
+    void* scan;
+};
+
+void carve_batch_match(Carver& cv, BatchWs& w, int n_total, int m_total) {
+    w.packed = cv.take<u64>((size_t)(n_total > 0 ? n_total : 1));
+    w.hb = cv.take<float>((size_t)(m_total > 0 ? m_total : 1));
+}
+
+void carve_batch_ransac(Carver& cv, BatchWs& w, int B, int max_iteration, int max_validation) {
+    const size_t hi = (size_t)B * (size_t)max_iteration, hv = (size_t)B * (size_t)max_validation;
+    w.pass = cv.take<int>(hi);
+    w.offs = cv.take<int>(hi);
+    w.npass = cv.take<int>(1);
+    w.vid = cv.take<int>(hv);
+    w.xf = cv.take<float>(hv * 12);
+    w.counts = cv.take<int>(hv);
+    w.sums = cv.take<double>(hv);
+    w.scan = cv.take<char>(scan_ws_bytes((int)hi));
+}
+
+constexpr int kMaxBatch = 65535;      // pairs ride on a grid dimension
 
 }  // namespace
 }  // namespace pcrcg
@@ -594,6 +793,103 @@ int pcrcg_ransac(const float* src, int n, const float* tgt, int m, const void* g
     hipLaunchKernelGGL(k_evaluate, dim3(max_validation), dim3(kEvalThreads), 0, st, src, n, g, thr2, w.npass, max_validation, w.vid,
                        w.xf, w.counts, w.sums, tr.counts, tr.sums);
     hipLaunchKernelGGL(k_select, dim3(1), dim3(256), 0, st, a, n, w.npass, max_validation, w.vid, w.counts, w.sums, out_transform,
+                       out_stats);
+    PCRCG_CHECK_LAUNCH();
+    return PCRCG_OK;
+}
+
+size_t pcrcg_ransac_batch_ws_bytes(int B, int n_total, int m_total, int max_iteration, int max_validation) {
+    if (B < 1 || B > kMaxBatch || n_total < 0 || m_total < 0 || max_iteration < 1 || max_validation < 1) return 0;
+    if ((long long)B * max_iteration > 0x7FFFFFFF) return 0;
+    Carver a(nullptr, 0), b(nullptr, 0);
+    BatchWs w;
+    carve_batch_match(a, w, n_total, m_total);
+    carve_batch_ransac(b, w, B, max_iteration, max_validation);
+    return a.off > b.off ? a.off : b.off;
+}
+
+int pcrcg_feature_match_batch(const float* src_feat, int ld_src, const int* src_off, int n_total, int n_max,
+                              const float* tgt_feat, int ld_tgt, const int* tgt_off, int m_total, int m_max, int c, int B,
+                              int* corr, int* k, void* ws, size_t ws_bytes, void* stream) {
+    PCRCG_CHECK_ARG(src_feat && src_off && tgt_feat && tgt_off && corr && k && ws);
+    PCRCG_CHECK_ARG(B >= 1 && B <= kMaxBatch);
+    PCRCG_CHECK_ARG(n_max >= 1 && m_max >= 1 && n_total >= n_max && m_total >= m_max);
+    PCRCG_CHECK_ARG(c >= 1 && ld_src >= c && ld_tgt >= c);
+    Carver cv(ws, ws_bytes);
+    BatchWs w;
+    carve_batch_match(cv, w, n_total, m_total);
+    PCRCG_CHECK_WS(cv);
+    hipStream_t st = as_stream(stream);
+    PCRCG_CHECK_HIP(hipMemsetAsync(w.packed, 0, (size_t)n_total * 8, st));
+    hipLaunchKernelGGL(k_half_norms, dim3((m_total + 255) / 256), dim3(256), 0, st, tgt_feat, ld_tgt, m_total, c, w.hb);
+    const bool aligned = ld_src % 4 == 0 && ld_tgt % 4 == 0 &&
+                         ((reinterpret_cast<uintptr_t>(src_feat) | reinterpret_cast<uintptr_t>(tgt_feat)) & 15) == 0;
+    // the single-pair launch shapes with the pair count folded into the workgroup target; the arg-max does not depend on
+    // how the columns are split, so every pair gets the single-pair result
+    if ((c == 32 || c == 64) && aligned) {
+        const int gxm = (n_max + 127) / 128;
+        long splits = (1024 + (long)gxm * B - 1) / ((long)gxm * B);
+        const int max_splits = (m_max + 255) / 256;
+        if (splits > max_splits) splits = max_splits;
+        if (splits < 1) splits = 1;
+        const int cols_per = ((m_max + (int)splits - 1) / (int)splits + 31) / 32 * 32;
+        const dim3 grid(gxm, (m_max + cols_per - 1) / cols_per, B);
+        if (c == 32)
+            hipLaunchKernelGGL(k_l2nn_mfma_batch<32>, grid, dim3(256), 0, st, src_feat, ld_src, src_off, tgt_feat, ld_tgt, tgt_off,
+                               w.hb, cols_per, w.packed);
+        else
+            hipLaunchKernelGGL(k_l2nn_mfma_batch<64>, grid, dim3(256), 0, st, src_feat, ld_src, src_off, tgt_feat, ld_tgt, tgt_off,
+                               w.hb, cols_per, w.packed);
+    } else {
+        const int gx = (n_max + 255) / 256;
+        long splits = (2048 + (long)gx * B - 1) / ((long)gx * B);
+        const int max_splits = (m_max + 127) / 128;
+        if (splits > max_splits) splits = max_splits;
+        if (splits < 1) splits = 1;
+        const int cols_per = (m_max + (int)splits - 1) / (int)splits;
+        hipLaunchKernelGGL(k_l2nn_any_batch, dim3(gx, (m_max + cols_per - 1) / cols_per, B), dim3(256), 0, st, src_feat, ld_src,
+                           src_off, tgt_feat, ld_tgt, tgt_off, c, w.hb, cols_per, w.packed);
+    }
+    hipLaunchKernelGGL(k_nn_emit_batch, dim3((n_max + 255) / 256, B), dim3(256), 0, st, w.packed, src_off, corr, k);
+    PCRCG_CHECK_LAUNCH();
+    return PCRCG_OK;
+}
+
+int pcrcg_ransac_batch(const float* src, const int* src_off, const float* tgt, const int* tgt_off, int m_total, const void* grid, const int* corr, const int* k, int B, int ransac_n, double threshold,
+                       double edge_similarity, int distance_check, int max_iteration, int max_validation,
+                       const uint64_t* seeds, double* out_transform, double* out_stats, void* ws, size_t ws_bytes,
+                       void* stream) {
+    PCRCG_CHECK_ARG(src && src_off && tgt && tgt_off && grid && corr && k && seeds && out_transform && out_stats && ws);
+    PCRCG_CHECK_ARG(B >= 1 && B <= kMaxBatch);
+    PCRCG_CHECK_ARG(ransac_n >= 3 && ransac_n <= kMaxSample);
+    PCRCG_CHECK_ARG(m_total >= 1);
+    PCRCG_CHECK_ARG(threshold > 0.0 && edge_similarity >= 0.0 && edge_similarity <= 1.0);
+    PCRCG_CHECK_ARG(distance_check == 0 || distance_check == 1);
+    PCRCG_CHECK_ARG(max_iteration >= 1 && max_iteration <= (1 << 27));
+    PCRCG_CHECK_ARG(max_validation >= 1 && max_validation <= max_iteration);
+    PCRCG_CHECK_ARG((long long)B * max_iteration <= 0x7FFFFFFF);
+    Carver cv(ws, ws_bytes);
+    BatchWs w;
+    carve_batch_ransac(cv, w, B, max_iteration, max_validation);
+    PCRCG_CHECK_WS(cv);
+    bool ok;
+    GridView g = grid_view(const_cast<void*>(grid), grid_bytes(m_total, B), m_total, B, &ok);
+    hipStream_t st = as_stream(stream);
+    BatchArgs a;
+    a.src = src; a.src_off = src_off; a.tgt = tgt; a.tgt_off = tgt_off; a.corr = corr; a.k = k;
+    a.seeds = reinterpret_cast<const u64*>(seeds);
+    a.ransac_n = ransac_n; a.dist_check = distance_check; a.max_iteration = max_iteration; a.max_validation = max_validation;
+    a.thr = threshold; a.sim = edge_similarity;
+    const int gh = (max_iteration + 255) / 256;
+    hipLaunchKernelGGL(k_hypotheses_batch, dim3(gh, B), dim3(256), 0, st, a, w.pass);
+    PCRCG_CHECK_LAUNCH();
+    PCRCG_PROPAGATE(exclusive_scan_i32(w.pass, w.offs, B * max_iteration, w.npass, w.scan, st));
+    hipLaunchKernelGGL(k_compact_batch, dim3(gh, B), dim3(256), 0, st, w.pass, w.offs, max_iteration, max_validation, w.vid);
+    hipLaunchKernelGGL(k_refit_batch, dim3((max_validation + 255) / 256, B), dim3(256), 0, st, a, w.offs, w.npass, B, w.vid, w.xf);
+    const float thr2 = (float)(threshold * threshold);
+    hipLaunchKernelGGL(k_evaluate_batch, dim3(max_validation, B), dim3(kEvalThreads), 0, st, a, g, thr2, w.offs, w.npass, B, w.xf,
+                       w.counts, w.sums);
+    hipLaunchKernelGGL(k_select_batch, dim3(B), dim3(256), 0, st, a, w.offs, w.npass, B, w.vid, w.counts, w.sums, out_transform,
                        out_stats);
     PCRCG_CHECK_LAUNCH();
     return PCRCG_OK;

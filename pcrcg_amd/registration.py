@@ -5,13 +5,18 @@
                                 RANSAC, a float64 numpy [4,4] back.  open3d is not needed.
   * `register`               -- the same with every result on the device (`RegistrationResult`), optionally the trace
                                 of every stage (`trace=True`, what tests/test_registration_gpu.py checks).
+  * `register_batch`         -- many pairs in one set of launches (`BatchRegistrationResult`); pair b's result is
+                                `register(..., mutual=False, seed=seeds[b])`'s, bit for bit.
+  * `ransac_pose_estimation_batch` -- the same as numpy [B,4,4] (the reference's mutual=False branch, pair by pair).
+  * `feature_match_batch`    -- the nearest-neighbour lists of many pairs in one launch set.
   * `mutual_correspondences` -- the mutual pairs of the inner-product score ([K,2] int64 device tensor).
   * `get_inlier_ratio`       -- device version of ref:lib/benchmark_utils.py:226-267 (same `w` / `wo` dict).
   * `get_angle_deviation`    -- numpy, as ref:lib/benchmark_utils.py:175-185.
 
 The algorithm (csrc/register.hip, include/pcrcg.h "Registration back end") is deterministic: a
 seed fixes every draw, and two runs give the same bits.  `register` reads the device ONCE, after the selection
-(the transform and the statistics in one buffer); every call before it is enqueued on the current stream.
+(the transform and the statistics in one buffer); every call before it is enqueued on the current stream.  So does
+`register_batch`, however many chunks of pairs it launches.
 """
 import ctypes
 
@@ -174,6 +179,176 @@ def ransac_pose_estimation(src_pcd, tgt_pcd, src_feat, tgt_feat, mutual=False, d
         ransac_n = 4
     return register(src_pcd, tgt_pcd, src_feat, tgt_feat, mutual, distance_threshold, ransac_n,
                     max_iteration=max_iteration, max_validation=max_validation, seed=seed).matrix
+
+
+# register_batch's default chunking: as many consecutive pairs per call as keep pcrcg_ransac_batch_ws_bytes within this
+# (576 pairs at 5 000 points and 50 000 / 1 000)
+BATCH_WS_BUDGET = 256 << 20
+_MAX_BATCH = 65535     # pairs per call (include/pcrcg.h)
+
+
+class BatchRegistrationResult:
+    """Results of `register_batch` for B pairs.  transformations: float64 [B,4,4] device tensor; matrices: the same as
+    numpy (from the one read); fitness, inlier_rmse, n_correspondences, iterations, validations, chosen: numpy [B]
+    (the fields of RegistrationResult, pair by pair)."""
+
+    def __init__(self, buf, host, B):
+        self.transformations = buf[:16 * B].view(B, 4, 4)
+        self.matrices = host[:16 * B].reshape(B, 4, 4).copy()
+        st = host[16 * B:].reshape(B, _N_STATS)
+        self.fitness = st[:, 0].copy()
+        self.inlier_rmse = st[:, 1].copy()
+        self.n_correspondences = st[:, 2].astype(np.int64)
+        self.iterations = st[:, 3].astype(np.int64)
+        self.validations = st[:, 4].astype(np.int64)
+        self.chosen = st[:, 5].astype(np.int64)
+
+    def __len__(self):
+        return len(self.matrices)
+
+    def __repr__(self):
+        return f"BatchRegistrationResult(pairs={len(self)}, mean fitness={float(np.mean(self.fitness)):.6g})"
+
+
+def _rows(x):
+    return x.shape[0] if hasattr(x, "shape") else len(x)
+
+
+def _cat(xs, dev, name, cols=None):
+    """Concatenate per-pair [N_b, cols] arrays into one float32 [sum N_b, cols] device tensor: host inputs are joined on
+    the host and uploaded once."""
+    ts = [x if isinstance(x, torch.Tensor) else torch.from_numpy(np.asarray(x)) for x in xs]
+    if all(not t.is_cuda for t in ts):
+        t = torch.cat([t.to(torch.float32) for t in ts]).to(dev)
+    else:
+        t = torch.cat([t.to(device=dev, dtype=torch.float32) for t in ts])
+    if t.dim() != 2 or (cols is not None and t.shape[1] != cols):
+        raise ValueError(f"{name} must be [N, {cols or 'C'}] arrays, got {tuple(t.shape)} concatenated")
+    return t.contiguous()
+
+
+def _match_batch(fa, src_off, n_max, fb, tgt_off, m_max, ws):
+    n_tot, m_tot, c, nb = fa.shape[0], fb.shape[0], fa.shape[1], src_off.shape[0] - 1
+    corr = torch.empty((n_tot, 2), dtype=torch.int32, device=fa.device)
+    k = torch.empty(nb, dtype=torch.int32, device=fa.device)
+    _lib.check(_lib.lib().pcrcg_feature_match_batch(fa.data_ptr(), c, src_off.data_ptr(), n_tot, n_max, fb.data_ptr(), c,
+                                                    tgt_off.data_ptr(), m_tot, m_max, c, nb, corr.data_ptr(), k.data_ptr(),
+                                                    ws[0].data_ptr(), ws[1], _stream()), "pcrcg_feature_match_batch")
+    return corr, k
+
+
+def feature_match_batch(src_feats, tgt_feats):
+    """-> (corr [sum N_b, 2] int32 device, k [B] int32 device): pcrcg_feature_match_batch over lists of per-pair
+    descriptors; pair b's rows start at sum(N_0 .. N_b-1) and equal feature_match(src_feats[b], tgt_feats[b])[0]."""
+    ns, ms = [_rows(x) for x in src_feats], [_rows(x) for x in tgt_feats]
+    if len(ns) != len(ms) or not ns or min(ns) == 0 or min(ms) == 0:
+        raise ValueError("feature_match_batch: need two equally long lists of non-empty descriptor sets")
+    dev = _device(*src_feats, *tgt_feats)
+    fa = _cat(src_feats, dev, "src_feats")
+    fb = _cat(tgt_feats, dev, "tgt_feats", fa.shape[1])
+    offs = torch.tensor(np.concatenate([np.cumsum([0] + ns), np.cumsum([0] + ms)]), dtype=torch.int32, device=dev)
+    wsb = _lib.lib().pcrcg_ransac_batch_ws_bytes(len(ns), sum(ns), sum(ms), 1, 1)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    return _match_batch(fa, offs[:len(ns) + 1], max(ns), fb, offs[len(ns) + 1:], max(ms), (ws, wsb))
+
+
+def register_batch(src_pcds, tgt_pcds, src_feats, tgt_feats, distance_threshold=0.05, ransac_n=3, *, max_iteration=50000,
+                   max_validation=1000, seeds=0, edge_similarity=0.9, distance_check=True, mutual=False,
+                   pairs_per_call=None):
+    """Feature matching + RANSAC for B pairs at once (pcrcg_feature_match_batch, pcrcg_ransac_batch) ->
+    BatchRegistrationResult.  Pair b's result equals register(src_pcds[b], tgt_pcds[b], src_feats[b], tgt_feats[b],
+    mutual=False, seed=seeds[b], ...) bit for bit; threshold, ransac_n, checkers and caps are shared by all pairs.
+
+    Inputs: four lists of per-pair [N_b,3] / [M_b,3] points and [N_b,C] / [M_b,C] descriptors (numpy, CPU or HIP tensors;
+    one C for the whole batch).  seeds: an int (every pair) or a sequence of B ints in [0, 2^24).  Only the L2
+    nearest-neighbour correspondences are offered (mutual=True raises).  pairs_per_call bounds the pairs per launch set
+    and so the workspace; by default it is the largest count whose pcrcg_ransac_batch_ws_bytes, sized with the largest
+    pair, stays within BATCH_WS_BUDGET.  Every size is checked on the host before anything is uploaded or launched; all
+    chunks write into one device buffer, read ONCE at the end."""
+    if mutual:
+        raise ValueError("register_batch: mutual correspondences are only offered by register (one pair per call)")
+    B = len(src_pcds)
+    if not (len(tgt_pcds) == len(src_feats) == len(tgt_feats) == B):
+        raise ValueError(f"register_batch: list lengths differ ({B}, {len(tgt_pcds)}, {len(src_feats)}, {len(tgt_feats)})")
+    if B == 0:
+        raise ValueError("register_batch: no pairs")
+    ransac_n = int(ransac_n)
+    if not 3 <= ransac_n <= 8:
+        raise ValueError(f"register_batch: ransac_n = {ransac_n} is outside 3..8")
+    if int(max_iteration) < 1 or not 1 <= int(max_validation) <= int(max_iteration):
+        raise ValueError("register_batch: need 1 <= max_validation <= max_iteration")
+    if not float(distance_threshold) > 0.0:
+        raise ValueError("register_batch: distance_threshold must be positive")
+    if not 0.0 <= float(edge_similarity) <= 1.0:
+        raise ValueError("register_batch: edge_similarity must lie in [0, 1]")
+    seeds = [int(seeds)] * B if np.ndim(seeds) == 0 else [int(x) for x in seeds]
+    if len(seeds) != B:
+        raise ValueError(f"register_batch: {len(seeds)} seeds for {B} pairs")
+    if any(not 0 <= x < (1 << 24) for x in seeds):
+        raise ValueError("register_batch: every seed must lie in [0, 2^24)")
+    ns = [_rows(x) for x in src_pcds]
+    ms = [_rows(x) for x in tgt_pcds]
+    c = None
+    for b in range(B):
+        if ns[b] < ransac_n:
+            raise ValueError(f"register_batch: pair {b} has {ns[b]} source points, fewer than ransac_n = {ransac_n}")
+        if ms[b] == 0:
+            raise ValueError(f"register_batch: pair {b} has an empty target cloud")
+        fs, ft = src_feats[b], tgt_feats[b]
+        if _rows(fs) != ns[b] or _rows(ft) != ms[b]:
+            raise ValueError(f"register_batch: pair {b}: the descriptors must have one row per point")
+        cb = (fs.shape[1], ft.shape[1])
+        if c is None:
+            c = cb[0]
+        if cb != (c, c):
+            raise ValueError(f"register_batch: pair {b}: descriptor width {cb}, the batch uses {c}")
+    mi, mv = int(max_iteration), int(max_validation)
+    L = _lib.lib()
+    if pairs_per_call is None:
+        per_pair = L.pcrcg_ransac_batch_ws_bytes(1, max(ns), max(ms), mi, mv)
+        pairs_per_call = max(1, BATCH_WS_BUDGET // max(per_pair, 1))
+    P = max(1, min(int(pairs_per_call), B, _MAX_BATCH, (0x7FFFFFFF // mi)))
+    dev = _device(*src_pcds, *tgt_pcds, *src_feats, *tgt_feats)
+    thr = float(distance_threshold)
+    chunks = [(b0, min(B, b0 + P)) for b0 in range(0, B, P)]
+    wsb = max(L.pcrcg_ransac_batch_ws_bytes(b1 - b0, sum(ns[b0:b1]), sum(ms[b0:b1]), mi, mv) for b0, b1 in chunks)
+    if wsb == 0:
+        raise ValueError("register_batch: sizes out of range for the batch workspace")
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    out = torch.empty(B * (16 + _N_STATS), dtype=torch.float64, device=dev)
+    seeds_d = torch.tensor(seeds, dtype=torch.int64, device=dev)
+    for b0, b1 in chunks:
+        nb = b1 - b0
+        n_tot, m_tot = sum(ns[b0:b1]), sum(ms[b0:b1])
+        src = _cat(src_pcds[b0:b1], dev, "src_pcds", 3)
+        tgt = _cat(tgt_pcds[b0:b1], dev, "tgt_pcds", 3)
+        fa = _cat(src_feats[b0:b1], dev, "src_feats", c)
+        fb = _cat(tgt_feats[b0:b1], dev, "tgt_feats", c)
+        offs = torch.tensor(np.concatenate([np.cumsum([0] + ns[b0:b1]), np.cumsum([0] + ms[b0:b1]), ms[b0:b1]]),
+                            dtype=torch.int32, device=dev)
+        src_off, tgt_off, lengths = offs[:nb + 1], offs[nb + 1:2 * nb + 2], offs[2 * nb + 2:]
+        corr, k = _match_batch(fa, src_off, max(ns[b0:b1]), fb, tgt_off, max(ms[b0:b1]), (ws, wsb))
+        gbytes = L.pcrcg_cellgrid_ws_bytes(m_tot, nb)
+        grid = torch.empty(gbytes, dtype=torch.uint8, device=dev)
+        _lib.check(L.pcrcg_cellgrid_build(tgt.data_ptr(), m_tot, lengths.data_ptr(), nb, thr, grid.data_ptr(), gbytes,
+                                          _stream()), "pcrcg_cellgrid_build")
+        _lib.check(L.pcrcg_ransac_batch(src.data_ptr(), src_off.data_ptr(), tgt.data_ptr(), tgt_off.data_ptr(), m_tot,
+                                        grid.data_ptr(), corr.data_ptr(), k.data_ptr(), nb, ransac_n, thr,
+                                        float(edge_similarity), int(bool(distance_check)), mi, mv, seeds_d[b0:].data_ptr(),
+                                        out[16 * b0:].data_ptr(), out[16 * B + _N_STATS * b0:].data_ptr(), ws.data_ptr(),
+                                        wsb, _stream()), "pcrcg_ransac_batch")
+    return BatchRegistrationResult(out, _read(out), B)
+
+
+def ransac_pose_estimation_batch(src_pcds, tgt_pcds, src_feats, tgt_feats, mutual=False, distance_threshold=0.05,
+                                 ransac_n=3, *, max_iteration=50000, max_validation=1000, seeds=0, pairs_per_call=None):
+    """ransac_pose_estimation's mutual=False branch (edge-length 0.9 and distance checkers) for a list of pairs ->
+    float64 numpy [B,4,4].  The mutual branch stays on ransac_pose_estimation."""
+    if mutual:
+        raise ValueError("ransac_pose_estimation_batch: mutual=True is only offered one pair at a time")
+    return register_batch(src_pcds, tgt_pcds, src_feats, tgt_feats, distance_threshold, ransac_n,
+                          max_iteration=max_iteration, max_validation=max_validation, seeds=seeds,
+                          pairs_per_call=pairs_per_call).matrices
 
 
 def get_inlier_ratio(src_pcd, tgt_pcd, src_feat, tgt_feat, rot, trans, inlier_distance_threshold=0.1):

@@ -9,7 +9,8 @@ registration back end.
                        generator exactly as the reference does (np.random.choice), so a seeded run picks the same
                        points; only the scores cross the bus (two [N] vectors).
   * `register_record` -- the loop of the 3DMatch evaluation and of KITTITester (ref:lib/tester.py:140-169): sampling on
-                       both sides, then RANSAC on the device (pcrcg_amd/registration.py; open3d is not needed)."""
+                       both sides, then RANSAC on the device (pcrcg_amd/registration.py; open3d is not needed).
+  * `register_records` -- the same loop over many records with ONE batched RANSAC (registration.register_batch)."""
 import numpy as np
 import torch
 
@@ -68,3 +69,21 @@ def register_record(record, n_points=5000, distance_threshold=0.05, ransac_n=3, 
     tgt_pcd, tgt_feats, _ = probabilistic_sample(pcd[ls:], feats[ls:], scores[ls:], n_points)
     return ransac_pose_estimation(src_pcd, tgt_pcd, src_feats, tgt_feats, mutual=False,
                                   distance_threshold=distance_threshold, ransac_n=ransac_n, seed=seed)
+
+
+def register_records(records, n_points=5000, distance_threshold=0.05, ransac_n=3, seeds=0):
+    """-> list of float64 numpy [4,4]: `register_record` over `records`, with the RANSAC of all pairs batched.  The
+    samples are drawn on the host generator in the reference loop's order (record by record, source then target), so
+    under the same np.random state the result equals [register_record(r, ...) for r in records] exactly.  seeds: one int
+    for every record, or one per record."""
+    from .registration import register_batch
+    src_pcds, tgt_pcds, src_feats, tgt_feats = [], [], [], []
+    for record in records:
+        ls = record["len_src"]
+        pcd, feats = record["pcd"], record["feats"]
+        scores = record["overlaps"] * record["saliency"]
+        sp, sf, _ = probabilistic_sample(pcd[:ls], feats[:ls], scores[:ls], n_points)
+        tp, tf, _ = probabilistic_sample(pcd[ls:], feats[ls:], scores[ls:], n_points)
+        src_pcds.append(sp); src_feats.append(sf); tgt_pcds.append(tp); tgt_feats.append(tf)
+    res = register_batch(src_pcds, tgt_pcds, src_feats, tgt_feats, distance_threshold, ransac_n, seeds=seeds)
+    return list(res.matrices)
