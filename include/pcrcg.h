@@ -52,7 +52,9 @@ const char* pcrcg_last_error(void);
  *                argument; pcrcg_pyramid_restore and pcrcg_reorder_job changed layout)
  *   The registration back end (pcrcg_ransac_ws_bytes, pcrcg_feature_match, pcrcg_ransac, pcrcg_ransac_trace) was added
  *   under version 4: it is additive -- no existing signature, layout or arithmetic changed.  So are its several-pairs
- *   entries (pcrcg_ransac_batch_ws_bytes, pcrcg_feature_match_batch, pcrcg_ransac_batch), added later under version 4. */
+ *   entries (pcrcg_ransac_batch_ws_bytes, pcrcg_feature_match_batch, pcrcg_ransac_batch), added later under version 4, and
+ *   the projection entries (pcrcg_project_depth_ws_bytes, pcrcg_project_depth, pcrcg_inject_frames with its
+ *   pcrcg_image_frame, pcrcg_superglue_valid_maps), added after them. */
 #define PCRCG_ABI_VERSION 4
 int pcrcg_abi_version(void);
 
@@ -390,6 +392,61 @@ int pcrcg_fill2d(float* dst, int ld, int rows, int cols, float value, void* stre
 int pcrcg_inject_image_features(const float* fmap, int c, int h, int w, const float* valid, const int64_t* inds2d,
                                 const int64_t* inds3d, int n, long row_offset, long n_rows, float* x, int ldx,
                                 void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The projections and valid maps themselves, computed on the device from raw frames (the reference computes them on
+ * the CPU in its data loader, ref:datasets/indoor.py:284-299,587-616).
+ *
+ * pcrcg_project_depth: Projection.projection(points, depth_map, world2camera) (ref:projection.py) for one cloud and one
+ *   depth map.  points [n, 3] f32, depth [h, w] f32; h_world2camera and h_intrinsics are 16 row-major floats in HOST
+ *   memory (a 3x3 intrinsic matrix is embedded in the identity first, as the reference does).  Writes inds2d [k, 2] i64
+ *   (column, row) and inds3d [k] i64 (ascending point index, as the reference's boolean masks leave it), k <= n, and the
+ *   count k as one int32 on the device -- no host round trip.  Point p is kept iff, with (u, v, z) = K [W p; 1] rounded
+ *   like the reference's two CPU torch.mm calls (the k-ordered fused chain fma(m3, 1, fma(m2, p2, fma(m1, p1, m0 p0)))),
+ *   u / z and v / z (IEEE division) lie in (-1, w) and (-1, h) -- .long() truncates toward zero -- and
+ *   |z - depth[trunc(v/z), trunc(u/z)]| < thresh.  Points at or behind the camera are not rejected (the reference does
+ *   not either).  Workspace: pcrcg_project_depth_ws_bytes(n).
+ *
+ * pcrcg_inject_frames: the fused form of pcrcg_fill2d + pcrcg_project_depth + pcrcg_inject_image_features for one pair:
+ *   x [n_points, ldx] (rows of the source cloud then the target cloud, len_src of them source) gets, per point, the
+ *   features of the LAST frame of its side (frames in the reference's write order, as for pcrcg_inject_image_features)
+ *   whose projection keeps it: columns 0..c-1 = fmap[:, row, column] * valid[column, row], column c = 1, columns
+ *   c+1..ldx-1 = 0; a point no frame keeps gets ones in columns 0..c and zeros after.  Every row is written once, bit for
+ *   bit what the unfused sequence writes.  h_frames: n_frames <= 6 host structs, at most 3 per side; fmap [c, h, w] and
+ *   depth [depth_h, depth_w] must have the same size.  One launch; nothing is allocated or synchronised.
+ *
+ * pcrcg_superglue_valid_maps: the two valid maps of one image pair from SuperGlue's output (ref:datasets/indoor.py:
+ *   284-299): keypoints0 [n0, 2], keypoints1 [n1, 2] f32 (x, y), matches [n0] i64 (-1: unmatched), confidence [n0] f32.
+ *   src_valid / tgt_valid [map_w, map_h] f32 (the reference's [160, 120]: first index the column x) = 0, then for every
+ *   valid match i in order map[int(kx - window) : int(kx + window), int(ky - window) : int(ky + window)] = confidence[i]
+ *   with (kx, ky) = keypoints0[i] (source) and keypoints1[matches[i]] (target); int() of the exact value, the bounds under
+ *   numpy's slice rules (negative counts from the end, then clamps at 0; past the end clamps; start >= stop paints
+ *   nothing).  A match with matches[i] >= n1 or a non-finite keypoint paints nothing.
+ *
+ * Bad arguments (null pointers, sizes <= 0, h * w >= 2^31, ldx < c + 1, more than 3 frames of a side, a depth / fmap
+ * size mismatch) are rejected with PCRCG_EBADARG before anything launches.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct pcrcg_image_frame {
+    const float* fmap;      /* [c, h, w] f32: the 2-D backbone's output for this image */
+    const float* depth;     /* [depth_h, depth_w] f32 */
+    const float* valid;     /* [w, h] f32 or NULL (no valid map) */
+    float world2camera[16]; /* row-major, by value */
+    float intrinsics[16];   /* row-major, by value */
+    float thresh;           /* depth test bound (Projection's thresh, 0.1) */
+    int h, w;               /* fmap's size */
+    int depth_h, depth_w;   /* must equal h, w */
+    int target;             /* 0: the frame of the source cloud, 1: of the target cloud */
+} pcrcg_image_frame;
+
+size_t pcrcg_project_depth_ws_bytes(int n);
+int pcrcg_project_depth(const float* points, int n, const float* depth, int h, int w, const float* h_world2camera,
+                        const float* h_intrinsics, float thresh, int64_t* inds2d, int64_t* inds3d, int* k, void* ws,
+                        size_t ws_bytes, void* stream);
+int pcrcg_inject_frames(const float* points, long n_points, long len_src, const pcrcg_image_frame* h_frames, int n_frames,
+                        int c, float* x, int ldx, void* stream);
+int pcrcg_superglue_valid_maps(const float* keypoints0, int n0, const float* keypoints1, int n1, const int64_t* matches,
+                               const float* confidence, int window, int map_w, int map_h, float* src_valid, float* tgt_valid,
+                               void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * GNN head helpers (ref:models/gcn.py)

@@ -86,6 +86,12 @@ SIGNATURES = {
     "pcrcg_fill2d": (c_int, [c_void_p, c_int, c_int, c_int, c_float, c_void_p]),
     "pcrcg_inject_image_features": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, ctypes.c_long,
                                             ctypes.c_long, c_void_p, c_int, c_void_p]),
+    "pcrcg_project_depth_ws_bytes": (c_size_t, [c_int]),
+    "pcrcg_project_depth": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_float, c_void_p, c_void_p,
+                                    c_void_p, c_void_p, c_size_t, c_void_p]),
+    "pcrcg_inject_frames": (c_int, [c_void_p, ctypes.c_long, ctypes.c_long, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p]),
+    "pcrcg_superglue_valid_maps": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
+                                           c_void_p, c_void_p]),
     "pcrcg_knn": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "pcrcg_edgeconv_ws_bytes": (c_size_t, [c_int]),
     "pcrcg_edgeconv_reduce": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_float,

@@ -112,7 +112,10 @@ class KPFCNN(nn.Module):
     IMAGE_WIDTH = 132      # the 129-channel input as the runners take it: rows of whole float4s, three zero columns
 
     def image_list(self, batch, backbone2d=None):
-        """The projections of a batch as ops.inject_image_features takes them, in the reference's write order."""
+        """The images of a batch in the reference's write order: projections as ops.inject_image_features takes them
+        (batch['{side}{i}_inds2d' / '_inds3d']) or raw frames as ops.inject_frames takes them (batch['{side}{i}_depth' /
+        '_world2camera' / '_intrinsics'; every dict then has a 'depth' key).  A batch is either all projections or all
+        frames."""
         n = int(batch["points"][0].shape[0])
         len_src = int(batch["src_pcd_raw"].shape[0])
         dev = batch["points"][0].device
@@ -128,17 +131,32 @@ class KPFCNN(nn.Module):
                 else:
                     raise RuntimeError(f"pcrcg_amd.KPFCNN: image_feature needs backbone2d or batch['{key}']")
                 valid = batch.get(f"{side}_valid_map{i}") if self.img_num < 3 else None   # :196-252 has no valid maps
-                images.append(dict(fmap=fmap.detach().to(dev, torch.float32), inds2d=batch[f"{side}{i}_inds2d"].to(dev),
-                                   inds3d=batch[f"{side}{i}_inds3d"].to(dev), target=side == "tgt",
-                                   valid=None if valid is None else valid.to(dev)))
+                im = dict(fmap=fmap.detach().to(dev, torch.float32), target=side == "tgt",
+                          valid=None if valid is None else valid.to(dev))
+                if f"{side}{i}_inds2d" in batch:
+                    im.update(inds2d=batch[f"{side}{i}_inds2d"].to(dev), inds3d=batch[f"{side}{i}_inds3d"].to(dev))
+                elif f"{side}{i}_depth" in batch:
+                    # raw frames: the projection runs inside the input build (pcrcg_inject_frames); the two matrices stay
+                    # on the host, where the kernel reads them
+                    im.update(depth=batch[f"{side}{i}_depth"].to(dev, torch.float32),
+                              world2camera=batch[f"{side}{i}_world2camera"], intrinsics=batch[f"{side}{i}_intrinsics"])
+                else:
+                    raise RuntimeError(f"pcrcg_amd.KPFCNN: image_feature needs batch['{side}{i}_inds2d'/'_inds3d'] or "
+                                       f"batch['{side}{i}_depth'/'_world2camera'/'_intrinsics']")
+                images.append(im)
+        if len({"depth" in im for im in images}) > 1:
+            raise RuntimeError("pcrcg_amd.KPFCNN: a batch carries either projections or raw frames for every image, not both")
         return n, len_src, images
 
     def image_features(self, batch, backbone2d=None, width=None):
         """ref:models/architectures.py:195-514: x = ones [N, 129] with the 2-D features of the projected points
-        scattered in (pcrcg_inject_image_features).  The 2-D feature maps come from `backbone2d` applied to
-        batch['{src,tgt}_color{i}'] as in the reference, or -- precomputed -- from batch['{src,tgt}{i}_feature2d'].
-        width=IMAGE_WIDTH: rows padded with zero columns (what the C++ runners take)."""
+        scattered in (pcrcg_inject_image_features; from raw frames: pcrcg_inject_frames, the projection included).  The
+        2-D feature maps come from `backbone2d` applied to batch['{src,tgt}_color{i}'] as in the reference, or --
+        precomputed -- from batch['{src,tgt}{i}_feature2d'].  width=IMAGE_WIDTH: rows padded with zero columns (what the
+        C++ runners take)."""
         n, len_src, images = self.image_list(batch, backbone2d)
+        if images and "depth" in images[0]:
+            return ops.inject_frames(batch["points"][0], len_src, images, channels=128, width=width)
         return ops.inject_image_features(n, len_src, images, channels=128, width=width)
 
     def forward(self, batch, backbone2d=None):

@@ -456,6 +456,78 @@ def inject_image_features(n_points, len_src, images, channels=128, width=None):
     return x
 
 
+class ImageFrame(ctypes.Structure):
+    """include/pcrcg.h pcrcg_image_frame."""
+    _fields_ = [("fmap", ctypes.c_void_p), ("depth", ctypes.c_void_p), ("valid", ctypes.c_void_p),
+                ("world2camera", ctypes.c_float * 16), ("intrinsics", ctypes.c_float * 16), ("thresh", ctypes.c_float),
+                ("h", ctypes.c_int), ("w", ctypes.c_int), ("depth_h", ctypes.c_int), ("depth_w", ctypes.c_int),
+                ("target", ctypes.c_int)]
+
+
+def matrix16(m):
+    """A 4x4 (or 3x3, embedded in the identity as ref:projection.py matrix_multiplication does) matrix -> 16 row-major
+    float32 values on the host.  A device tensor costs a synchronising copy: pass host tensors on a hot path."""
+    m = torch.as_tensor(m).detach().to("cpu", _F32)
+    if m.shape == (3, 3):
+        e = torch.eye(4, dtype=_F32)
+        e[:3, :3] = m
+        m = e
+    if m.shape != (4, 4):
+        raise RuntimeError("pcrcg_amd: a projection matrix must be 4x4 or 3x3")
+    return (ctypes.c_float * 16)(*m.reshape(16).tolist())
+
+
+def frame_struct(frame, channels=128):
+    """One dict of inject_frames' `frames` -> (ImageFrame, the tensors it points into: hold them until the launch)."""
+    fmap = _dev(frame["fmap"], _F32, "fmap").contiguous()
+    if fmap.dim() != 3 or fmap.shape[0] != channels:
+        raise RuntimeError("pcrcg_amd.inject_frames: fmap must be [channels, H, W]")
+    depth = _dev(frame["depth"], _F32, "depth")
+    if depth.dim() == 3 and depth.shape[0] == 1:             # Projection.projection squeezes a [1, H, W] map
+        depth = depth.squeeze(0)
+    if depth.dim() != 2:
+        raise RuntimeError("pcrcg_amd.inject_frames: depth must be [H, W]")
+    depth = depth.contiguous()
+    valid = frame.get("valid")
+    if valid is not None:
+        valid = _dev(valid.to(_F32), _F32, "valid").contiguous()
+        if tuple(valid.shape) != (fmap.shape[2], fmap.shape[1]):
+            raise RuntimeError("pcrcg_amd.inject_frames: valid must be [W, H] (the reference's layout)")
+    f = ImageFrame(fmap.data_ptr(), depth.data_ptr(), _ptr(valid), matrix16(frame["world2camera"]),
+                   matrix16(frame["intrinsics"]), float(frame.get("thresh", 0.1)), fmap.shape[1], fmap.shape[2],
+                   depth.shape[0], depth.shape[1], 1 if frame.get("target") else 0)
+    return f, (fmap, depth, valid)
+
+
+def inject_frames(points, len_src, frames, channels=128, width=None):
+    """The fused form of the projections + inject_image_features: -> x [N, width or channels + 1] f32 built straight from
+    raw frames (pcrcg_inject_frames, one launch): each point gets the features of the LAST frame of its cloud (frames in
+    the reference's write order) whose projection (ref:projection.py Projection.projection) keeps it, times that frame's
+    valid map; column `channels` is 1, wider columns 0; points no frame keeps get ones.  Bit for bit what the
+    projections fed to inject_image_features give.  points [N, 3] f32 (source rows, then target rows; len_src of them
+    source); frames: dicts with fmap [channels, H, W] f32, depth [H, W] f32, world2camera and intrinsics (4x4 or 3x3, read
+    on the host), target (bool), optionally valid [W, H] f32 and thresh (default 0.1)."""
+    L = _lib.lib()
+    pts = _dev(points, _F32, "points").contiguous()
+    if pts.dim() != 2 or pts.shape[1] != 3:
+        raise RuntimeError("pcrcg_amd.inject_frames: points must be [N, 3]")
+    n = int(pts.shape[0])
+    width = channels + 1 if width is None else int(width)
+    if width < channels + 1:
+        raise RuntimeError("pcrcg_amd.inject_frames: width must be at least channels + 1")
+    if len(frames) > 6:
+        raise RuntimeError("pcrcg_amd.inject_frames: at most 3 frames per cloud")
+    arr = (ImageFrame * max(len(frames), 1))()
+    keep = []                    # contiguous copies made above stay allocated until the kernel is enqueued
+    for j, fr in enumerate(frames):
+        arr[j], ts = frame_struct(fr, channels)
+        keep.append(ts)
+    x = torch.empty((n, width), dtype=_F32, device=pts.device)
+    _lib.check(L.pcrcg_inject_frames(pts.data_ptr(), n, int(len_src), ctypes.cast(arr, ctypes.c_void_p), len(frames),
+                                     channels, x.data_ptr(), width, _stream()), "pcrcg_inject_frames")
+    return x
+
+
 def kpconv_bf16(q_pts, s_pts, idx, x, kernel_points, weights, extent, intermediates=False):
     """KPConv.forward of the bf16 feature-storage VARIANT (pcrcg_model.feature_bf16): the gathers read a bf16 copy of
     x, the aggregate is bf16 in memory, the contraction takes it as the bf16 operand against the exactly split fp32

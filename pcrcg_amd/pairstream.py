@@ -367,7 +367,7 @@ class PairStreams:
                 start = 0
                 for j, n in enumerate(sizes):
                     seqs = [it[0] for it in items[start:start + n]]
-                    imgs = [it[4] for it in items[start:start + n]]
+                    imgs = [(it[4], it[1], it[3]) for it in items[start:start + n]]     # (images, points, ready)
                     self._mid[(job0 + j) % len(self.models)].put(job0 + j, (seqs, (batches, start, n), arena, built, pyr, slot,
                                                                              deferred, f, a, (lens_h, imgs)))
                     start += n
@@ -449,21 +449,39 @@ class PairStreams:
     def _image_inputs(self, batches, start, n, lens_h, imgs):
         """PCR-CG's shipped configuration (image_feature: ref:configs/test/indoor.yaml:21-34, ref:models/architectures.py:
         195-514): the [N, 129] input of every pair of a forward job, injected on the job's model stream from the pair's
-        2-D feature maps and projections (pcrcg_inject_image_features) in rows of KPFCNN.IMAGE_WIDTH floats, and handed to
-        the runner in place of the pyramid's all-ones [N, 1] features.  -> the tensors (kept alive with the outputs)."""
+        2-D feature maps and projections (pcrcg_inject_image_features) or raw frames (pcrcg_inject_frames, from the
+        pair's points) in rows of KPFCNN.IMAGE_WIDTH floats, and handed to the runner in place of the pyramid's all-ones
+        [N, 1] features.  The model stream waits for the pair's `ready` event (the caller's producers of these tensors)
+        and is recorded on every tensor it reads, so the caller may drop them right after submit().
+        -> the tensors (kept alive with the outputs)."""
         if not getattr(self.net, "image_feature", False):
-            if any(im is not None for im in imgs):
+            if any(im is not None for im, _, _ in imgs):
                 raise RuntimeError("PairStreams.submit(images=...): the network was built without image_feature")
             return None
         from . import ops
+        stream = torch.cuda.current_stream(self.device)
         keep = []
         for g in range(n):
-            im = imgs[g]
+            im, points, ready = imgs[g]
             if im is None:
                 raise RuntimeError("PairStreams.submit(): this network takes image features -- pass images=[...] with every pair")
+            stream.wait_event(ready)
+            for d in im:
+                for t in d.values():
+                    if isinstance(t, torch.Tensor) and t.is_cuda:
+                        t.record_stream(stream)
             bt = batches[start + g]
             first = 2 * (start + g) if len(lens_h[0]) > 2 else 0       # the pair's first cloud in a grouped build
-            x = ops.inject_image_features(int(bt.n_points[0]), int(lens_h[0][first]), im, channels=128, width=self.net.IMAGE_WIDTH)
+            len_src = int(lens_h[0][first])
+            if len({"depth" in d for d in im}) > 1:
+                raise RuntimeError("PairStreams.submit(images=...): either projections or raw frames for every image, not both")
+            if im and "depth" in im[0]:
+                if int(points.shape[0]) != int(bt.n_points[0]):
+                    raise RuntimeError("PairStreams.submit(): the pair's points and its pyramid's level 0 differ in size")
+                points.record_stream(stream)
+                x = ops.inject_frames(points, len_src, im, channels=128, width=self.net.IMAGE_WIDTH)
+            else:
+                x = ops.inject_image_features(int(bt.n_points[0]), len_src, im, channels=128, width=self.net.IMAGE_WIDTH)
             bt.features, bt.feat_dim = x.data_ptr(), int(x.shape[1])
             keep.append(x)
         return keep
@@ -473,7 +491,10 @@ class PairStreams:
         images: for a network with image_feature (PCR-CG's shipped configuration) the pair's projections as
         ops.inject_image_features takes them -- a list, in the reference's write order (KPFCNN.image_list builds it from a
         reference batch dict), of dicts with fmap [128,H,W] f32, inds2d [n,2] i64, inds3d [n] i64, target (bool) and
-        optionally valid [W,H] f32, all on the device.  The 2-D backbone that produces the maps is the caller's."""
+        optionally valid [W,H] f32, all on the device -- or raw frames as ops.inject_frames takes them: dicts with fmap,
+        depth [H,W] f32 (device), world2camera and intrinsics (4x4 / 3x3, host tensors: the kernel reads them by value),
+        target and optionally valid; the projection then runs on the device (pcrcg_inject_frames).  The 2-D backbone
+        that produces the maps is the caller's.  The caller may drop every tensor right after this call."""
         seq = self._submitted
         self._submitted += 1
         ready = torch.cuda.Event()

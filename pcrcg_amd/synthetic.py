@@ -118,3 +118,89 @@ def image_inputs(n_src, n_tgt, seed=0, img_num=2, h=120, w=160, frac=0.45, chann
             if img_num < 3:
                 out[f"{side}_valid_map{i}"] = (rng.rand(w, h) > 0.2).astype(np.float32)
     return out
+
+
+# the 3DMatch intrinsics (fx = fy = 585, cx = 320, cy = 240 at 640 x 480) scaled to the 160 x 120 frames the 2-D branch uses
+INTRINSICS_160 = np.array([[146.25, 0.0, 80.0], [0.0, 146.25, 60.0], [0.0, 0.0, 1.0]], np.float32)
+
+
+def render_depth(points, world2camera, intrinsics=INTRINSICS_160, h=120, w=160, rng=None, noise=0.04, drop=0.05):
+    """A z-buffered depth map [h, w] f32 of `points` seen through world2camera (4x4) and intrinsics (3x3): the nearest
+    point per pixel, 0 where none lands (a missing depth pixel), then Gaussian noise of `noise` m on the filled pixels and
+    a `drop` share of them zeroed -- so that the depth test of a projection rejects some of the points."""
+    p = points.astype(np.float64) @ world2camera[:3, :3].astype(np.float64).T + world2camera[:3, 3].astype(np.float64)
+    z = p[:, 2]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        u = intrinsics[0, 0] * p[:, 0] / z + intrinsics[0, 2]
+        v = intrinsics[1, 1] * p[:, 1] / z + intrinsics[1, 2]
+    ok = (z > 0.05) & (u >= 0) & (u < w) & (v >= 0) & (v < h)
+    flat = v[ok].astype(np.int64) * w + u[ok].astype(np.int64)
+    depth = np.full(h * w, np.inf)
+    np.minimum.at(depth, flat, z[ok])
+    depth[np.isinf(depth)] = 0.0
+    if rng is not None:
+        filled = depth > 0
+        depth[filled] += rng.normal(0.0, noise, int(filled.sum()))
+        depth[filled & (rng.rand(h * w) < drop)] = 0.0
+    return depth.reshape(h, w).astype(np.float32)
+
+
+def _pose(rng, angle=0.12, shift=0.15):
+    """A camera pose (4x4 f64): a rotation of up to `angle` rad about a random axis and a shift of up to `shift` m."""
+    ax = rng.randn(3)
+    ax /= np.linalg.norm(ax)
+    a = (rng.rand() * 2 - 1) * angle
+    k = np.array([[0, -ax[2], ax[1]], [ax[2], 0, -ax[0]], [-ax[1], ax[0], 0]])
+    pose = np.eye(4)
+    pose[:3, :3] = np.eye(3) + np.sin(a) * k + (1 - np.cos(a)) * (k @ k)
+    pose[:3, 3] = (rng.rand(3) * 2 - 1) * shift
+    return pose
+
+
+def second_world2camera(pose1, pose2, world2camera1):
+    """Image 2's world2camera as the reference composes it (ref:datasets/indoor.py:587-592): pose2^-1 . pose1 .
+    world2camera1, the inverse in float64 numpy, the products in float32 torch."""
+    import torch
+    return torch.mm(torch.from_numpy(np.linalg.inv(pose2)).float(),
+                    torch.mm(torch.from_numpy(pose1).float(), torch.from_numpy(world2camera1).float())).numpy()
+
+
+def superglue_like(rng, n0=400, n1=450, unmatched=0.3, h=120, w=160):
+    """SuperGlue-shaped output of one image pair: keypoints0 [n0, 2], keypoints1 [n1, 2] f32 (x, y), matches [n0] i64
+    (-1: unmatched), match_confidence [n0] f32."""
+    kp0 = (rng.rand(n0, 2) * [w, h]).astype(np.float32)
+    kp1 = (rng.rand(n1, 2) * [w, h]).astype(np.float32)
+    m = min(n0, n1)
+    matches = np.full(n0, -1, np.int64)
+    matches[rng.permutation(n0)[:m]] = rng.permutation(n1)[:m]     # one-to-one, as SuperGlue's mutual matches are
+    matches[rng.rand(n0) < unmatched] = -1
+    return dict(keypoints0=kp0, keypoints1=kp1, matches=matches, confidence=rng.rand(n0).astype(np.float32))
+
+
+def frame_inputs(src, tgt, seed=0, img_num=2, h=120, w=160, channels=128):
+    """Raw frames for the device projection (pcrcg_inject_frames): per cloud and image a random [channels, h, w] feature
+    map, a depth map z-buffer-rendered from the cloud (render_depth: noise and dropped pixels, so the depth test rejects a
+    share of the points), world2camera [4, 4] and the 3DMatch intrinsics at 160 x 120 [3, 3].  Image 1 looks at the cloud
+    from in front of its centre; images 2 and 3 from a pose offset, their world2camera composed the way the reference
+    composes it (second_world2camera).  For img_num < 3, SuperGlue-like matches per image under 'sg{i}_{keypoints0,
+    keypoints1,matches,confidence}' (superglue_valid_maps paints the valid maps from them).  Keys as in the reference's
+    batch dict ('{side}{i}_depth', '{side}{i}_world2camera', '{side}{i}_intrinsics'; maps under '{side}{i}_feature2d').
+    numpy arrays, seeded."""
+    rng = np.random.RandomState(2000 + seed)
+    out = {}
+    for side, pts in (("src", src), ("tgt", tgt)):
+        w2c1 = np.eye(4, dtype=np.float32)
+        lo, hi = pts.min(0), pts.max(0)
+        w2c1[:3, 3] = [-(lo[0] + hi[0]) / 2, -(lo[1] + hi[1]) / 2, 0.8 - lo[2] + 0.5 * (hi[0] - lo[0])]
+        pose1 = np.eye(4)
+        for i in range(1, img_num + 1):
+            w2c = w2c1 if i == 1 else second_world2camera(pose1, _pose(rng), w2c1)
+            out[f"{side}{i}_feature2d"] = rng.rand(channels, h, w).astype(np.float32)
+            out[f"{side}{i}_depth"] = render_depth(pts, w2c, h=h, w=w, rng=rng)
+            out[f"{side}{i}_world2camera"] = w2c.astype(np.float32)
+            out[f"{side}{i}_intrinsics"] = INTRINSICS_160.copy()
+    if img_num < 3:
+        for i in range(1, img_num + 1):
+            for k, v in superglue_like(rng, h=h, w=w).items():
+                out[f"sg{i}_{k}"] = v
+    return out
