@@ -54,7 +54,8 @@ const char* pcrcg_last_error(void);
  *   under version 4: it is additive -- no existing signature, layout or arithmetic changed.  So are its several-pairs
  *   entries (pcrcg_ransac_batch_ws_bytes, pcrcg_feature_match_batch, pcrcg_ransac_batch), added later under version 4, and
  *   the projection entries (pcrcg_project_depth_ws_bytes, pcrcg_project_depth, pcrcg_inject_frames with its
- *   pcrcg_image_frame, pcrcg_superglue_valid_maps), added after them. */
+ *   pcrcg_image_frame, pcrcg_superglue_valid_maps), added after them, and the inlier statistics
+ *   (pcrcg_inlier_stats_batch_ws_bytes, pcrcg_inlier_stats_batch), added after those. */
 #define PCRCG_ABI_VERSION 4
 int pcrcg_abi_version(void);
 
@@ -806,6 +807,34 @@ int pcrcg_ransac_batch(const float* src, const int* src_off, const float* tgt, c
                        const int* corr, const int* k, int B, int ransac_n, double threshold, double edge_similarity,
                        int distance_check, int max_iteration, int max_validation, const uint64_t* seeds,
                        double* out_transform, double* out_stats, void* ws, size_t ws_bytes, void* stream);
+
+/* Inlier statistics of many pairs: the inlier ratio and its mutual variant (ref:lib/benchmark_utils.py:226-267,
+ * get_inlier_ratio) of B ragged pairs in one set of launches, the inputs of feature-match recall.
+ *   Layout: as pcrcg_feature_match_batch's -- src [n_total, 3], tgt [m_total, 3] f32, descriptors [n_total, c] /
+ *   [m_total, c] with row strides ld_src / ld_tgt, src_off / tgt_off [B + 1] i32 DEVICE row offsets, n_max / m_max (host)
+ *   >= every pair's source / target length.  rt [B, 12] f32 DEVICE: pair b's ground-truth R (row-major) then t.
+ *   thr [n_thr] f32 HOST: the distance thresholds, 1 <= n_thr <= 32.
+ *   For pair b, both arg-max directions of <a_i, b_j>: arg_s[i] = argmax_j, arg_t[j] = argmax_i, lowest index on ties --
+ *   each row bit for bit what pcrcg_feature_argmax gives on that pair alone (the same device code and kernel choice).
+ *   Then for every source row i: p = R src_i + t in unfused fp32, ((r0 x + r1 y) + r2 z) + t0 (RANSAC's evaluation
+ *   arithmetic), d_i = sqrtf((dx dx + dy dy) + dz dz) with dx = p - tgt[arg_s[i]] and a correctly rounded square root,
+ *   mutual_i = (arg_t[arg_s[i]] == i) (the reference's mutual_selection);
+ *     counts [B, 2, n_thr] i32: [b, 0, k] = #{i : d_i < thr[k]} ("wo"), [b, 1, k] = #{i : mutual_i and d_i < thr[k]} ("w");
+ *     k_mutual [B] i32 = #{i : mutual_i}.
+ *   The comparison is in fp32 against the fp32 threshold.  All counts are integers, so the result does not depend on
+ *   the order of the pairs, on B or on the schedule.  Optional outputs (NULL: not written), pair b's rows at src_off[b] /
+ *   tgt_off[b], indices local to the pair: dist [n_total] f32 = d_i (NaN for a pair without targets), mutual [n_total]
+ *   i32 0/1, arg_s [n_total] i32, arg_t [m_total] i32.
+ * Workspace: pcrcg_inlier_stats_batch_ws_bytes(B, n_total, m_total) = 8 (n_total + m_total) bytes plus alignment padding;
+ * 0 for B outside 1..65535 or an empty total.  The entry zeroes counts and k_mutual itself, allocates nothing and
+ * synchronises nothing.  Bad arguments (null pointers, B outside 1..65535, n_thr outside 1..32, a NaN threshold, sizes
+ * that contradict each other) are rejected with PCRCG_EBADARG and a short workspace with PCRCG_EWORKSPACE, before
+ * anything launches; the offsets live on the device and are not read by the host. */
+size_t pcrcg_inlier_stats_batch_ws_bytes(int B, int n_total, int m_total);
+int pcrcg_inlier_stats_batch(const float* src, const float* src_feat, int ld_src, const int* src_off, int n_total, int n_max,
+                             const float* tgt, const float* tgt_feat, int ld_tgt, const int* tgt_off, int m_total, int m_max,
+                             int c, int B, const float* rt, const float* thr, int n_thr, int* counts, int* k_mutual,
+                             float* dist, int* mutual, int* arg_s, int* arg_t, void* ws, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -3,13 +3,19 @@
   * 3DMatch / 3DLoMatch registration recall -- ref:lib/benchmark.py: the Redwood trajectory files (`gt.log`, `gt.info`,
     `est.log`), the transformation error under the gt information matrix, and `benchmark`, which writes the reference's
     `result` file and per-scene `flag.npy`;
+  * feature-match recall -- ref:lib/benchmark_utils.py:18-54 and 297-311 (`fmr_wrt_distance`, `fmr_wrt_inlier_ratio`,
+    `get_scene_split`), and `feature_match_recall`, the per-scene summary the evaluation script reports (this project's
+    definition: DESIGN.md section 10);
   * the KITTI recall -- ref:lib/tester.py:171-206 (`kitti_metrics`).
 
 scripts/evaluate_registration.py runs the whole evaluation: sample, batched RANSAC (tester.register_records), `est.log`
-per scene, `benchmark`.
+per scene, `benchmark`; with --inlier_ratio also the inlier ratios (registration.inlier_ratio_batch) and
+`feature_match_recall`.
 """
+import glob
 import math
 import os
+import warnings
 
 import numpy as np
 
@@ -194,6 +200,87 @@ def benchmark(est_folder, gt_folder):
                mean_recall=float(np.mean(recall)), mean_median_rre=float(np.mean(re_med)),
                mean_median_rte=float(np.mean(te_med)))
     return out
+
+
+# ---- feature-match recall (ref:lib/benchmark_utils.py:18-54, 297-311) -----------------------------------------------
+# The distance thresholds of fmr_wrt_distance: 0.01 .. 0.20 m, computed as the reference does (k / 100.0).
+FMR_DISTANCES = tuple(k / 100.0 for k in range(1, 21))
+
+
+def get_scene_split(gt_folder):
+    """ref:lib/benchmark_utils.py:297-311 on a given folder (the reference globs configs/benchmarks/<name>): for the
+    sorted `{gt_folder}/*/gt.log`, the [start, end) rows of each scene's pairs in the concatenation of the scenes."""
+    split, count = [], 0
+    for eachfile in sorted(glob.glob(os.path.join(gt_folder, '*', 'gt.log'))):
+        gt_pairs, _ = read_trajectory(eachfile)
+        split.append([count, count + len(gt_pairs)])
+        count += len(gt_pairs)
+    return split
+
+
+def _inlier_ratios(data, distance_threshold, which):
+    """Per-pair inlier ratios at one distance threshold.  data: the reference's form -- one array of match distances per
+    pair, ratio = (d < threshold).mean() -- or the kernel's counts (an InlierRatioResult, registration.inlier_ratio_batch)
+    computed with that threshold among its thresholds; `which` picks its "wo" or "w" ratios.  The two agree exactly:
+    the counts are the same fp32 comparisons, and count / n is the mean of the 0/1 array."""
+    if hasattr(data, 'counts') and hasattr(data, 'thresholds'):
+        hit = np.flatnonzero(data.thresholds == np.float32(distance_threshold))
+        if hit.size == 0:
+            raise ValueError(f"the counts were not computed at the distance threshold {distance_threshold}")
+        return list(getattr(data, which)[:, hit[0]])
+    with warnings.catch_warnings():
+        warnings.simplefilter('ignore', RuntimeWarning)      # an empty array (no mutual match): NaN, as in the reference
+        return [(data[idx] < distance_threshold).mean() for idx in range(len(data))]
+
+
+def fmr_wrt_distance(data, split, inlier_ratio_threshold=0.05, which='wo'):
+    """ref:lib/benchmark_utils.py:18-34: the feature-match recall (in %) at the distance thresholds FMR_DISTANCES, kept
+    as written -- the scene sum is divided by 8, the number of 3DMatch scenes, whatever `split` holds.  data: see
+    _inlier_ratios (counts computed at FMR_DISTANCES)."""
+    fmr_wrt_distance = []
+    for distance_threshold in FMR_DISTANCES:
+        inlier_ratios = _inlier_ratios(data, distance_threshold, which)
+        fmr = 0
+        for ele in split:
+            fmr += (np.array(inlier_ratios[ele[0]:ele[1]]) > inlier_ratio_threshold).mean()
+        fmr /= 8
+        fmr_wrt_distance.append(fmr * 100)
+    return fmr_wrt_distance
+
+
+def fmr_wrt_inlier_ratio(data, split, distance_threshold=0.1, which='wo'):
+    """ref:lib/benchmark_utils.py:36-54: the feature-match recall (in %) at the inlier-ratio thresholds 0.01 .. 0.20 for
+    one distance threshold, kept as written (the /8 included).  data: see _inlier_ratios."""
+    inlier_ratios = _inlier_ratios(data, distance_threshold, which)
+    fmr_wrt_inlier = []
+    for inlier_ratio_threshold in range(1, 21):
+        inlier_ratio_threshold /= 100.0
+        fmr = 0
+        for ele in split:
+            fmr += (np.array(inlier_ratios[ele[0]:ele[1]]) > inlier_ratio_threshold).mean()
+        fmr /= 8
+        fmr_wrt_inlier.append(fmr * 100)
+    return fmr_wrt_inlier
+
+
+def feature_match_recall(inlier_ratios, split, threshold=0.05):
+    """This project's summary of the paper's IR and FMR columns (the reference's evaluation script
+    for them is not in its tree).  inlier_ratios [B]: one ratio per pair in the order of `split` (get_scene_split).
+    Per scene: IR = mean of the pairs' ratios, a NaN ratio (a pair without a mutual match) left out; FMR = fraction of
+    the scene's pairs with ratio > threshold, a NaN ratio counted as a miss.  -> {'scene_ir', 'scene_fmr': [S] lists,
+    'ir_mean', 'ir_std', 'fmr_mean', 'fmr_std': mean and population std over the scenes}."""
+    r = np.asarray(inlier_ratios, dtype=np.float64)
+    if not split or split[-1][1] != len(r):
+        raise ValueError(f"feature_match_recall: {len(r)} ratios for a split of {split[-1][1] if split else 0} pairs")
+    scene_ir, scene_fmr = [], []
+    for start, end in split:
+        x = r[start:end]
+        ok = x[~np.isnan(x)]
+        scene_ir.append(float(ok.mean()) if ok.size else float('nan'))
+        scene_fmr.append(float((x > threshold).mean()) if x.size else float('nan'))
+    return {'scene_ir': scene_ir, 'scene_fmr': scene_fmr,
+            'ir_mean': float(np.mean(scene_ir)), 'ir_std': float(np.std(scene_ir)),
+            'fmr_mean': float(np.mean(scene_fmr)), 'fmr_std': float(np.std(scene_fmr))}
 
 
 # ---- KITTI ---------------------------------------------------------------------------------------------------------

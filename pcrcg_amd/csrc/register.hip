@@ -25,6 +25,7 @@
 //
 // Compiled with -ffp-contract=off: every fp32 and fp64 operation rounds where the source says, so the numpy restatement
 // reproduces the evaluation's counts exactly.
+#include "argmax.h"
 #include "block_scan.h"
 #include "cellgrid.h"
 #include "common.h"
@@ -687,6 +688,162 @@ void carve_batch_ransac(Carver& cv, BatchWs& w, int B, int max_iteration, int ma
     w.scan = cv.take<char>(scan_ws_bytes((int)hi));
 }
 
+// ---- inlier statistics of many pairs (pcrcg_inlier_stats_batch) ----------------------------------------------------
+// Both arg-max directions of <a_i, b_j> for every pair, then one pass over every source row: the ground-truth distance of
+// the row's match and the threshold counts.  The arg-max kernels run the bodies of pcrcg_feature_argmax (argmax.h) on
+// the pair p = blockIdx.z (rows a_off[p] .., columns b_off[p] .., indices local to the pair); a workgroup that lies past
+// its pair's rows or columns leaves at once (the whole workgroup: the VALU body synchronises).
+template <int C>
+__global__ void __launch_bounds__(256) k_feature_argmax_batch(const float* __restrict__ a, int lda, const int* __restrict__ a_off,
+                                                              const float* __restrict__ b, int ldb, const int* __restrict__ b_off,
+                                                              int cols_per, u64* __restrict__ packed) {
+    __shared__ __attribute__((aligned(16))) float bs[kArgmaxTB * C];
+    const int p = blockIdx.z;
+    const int i0 = a_off[p], j0 = b_off[p];
+    const int n = a_off[p + 1] - i0, m = b_off[p + 1] - j0;
+    if ((int)blockIdx.x * 256 >= n || (int)blockIdx.y * cols_per >= m) return;
+    feature_argmax_valu_tile<C>(a + (long)i0 * lda, lda, n, b + (long)j0 * ldb, ldb, m, cols_per, packed + i0, bs, blockIdx.x,
+                                blockIdx.y);
+}
+
+__global__ void __launch_bounds__(256) k_feature_argmax_mfma32_batch(const float* __restrict__ a, int lda,
+                                                                     const int* __restrict__ a_off, const float* __restrict__ b,
+                                                                     int ldb, const int* __restrict__ b_off, int cols_per,
+                                                                     u64* __restrict__ packed) {
+    const int p = blockIdx.z;
+    const int i0 = a_off[p], j0 = b_off[p];
+    feature_argmax_mfma32_tile(a + (long)i0 * lda, lda, a_off[p + 1] - i0, b + (long)j0 * ldb, ldb, b_off[p + 1] - j0, cols_per,
+                               packed + i0, blockIdx.x, blockIdx.y);
+}
+
+__global__ void __launch_bounds__(256) k_feature_argmax_any_batch(const float* __restrict__ a, int lda, const int* __restrict__ a_off,
+                                                                  const float* __restrict__ b, int ldb, const int* __restrict__ b_off,
+                                                                  int c, int cols_per, u64* __restrict__ packed) {
+    const int p = blockIdx.z;
+    const int i0 = a_off[p], j0 = b_off[p];
+    feature_argmax_any_row(a + (long)i0 * lda, lda, a_off[p + 1] - i0, b + (long)j0 * ldb, ldb, b_off[p + 1] - j0, c, cols_per,
+                           packed + i0, blockIdx.x * 256 + threadIdx.x, blockIdx.y);
+}
+
+// packed winners -> pair-local int32 columns, over all rows of all pairs at once
+__global__ void __launch_bounds__(256) k_packed_cols(const u64* __restrict__ packed, int n, int* __restrict__ arg) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n) arg[i] = packed_col(packed[i]);
+}
+
+// pcrcg_feature_argmax's launch shapes with the pair count folded into the workgroup target (the arg-max does not depend
+// on how the columns are split): packed [n_total] receives the winners of every row of A against its pair's rows of B
+int feature_argmax_batch(const float* a, int lda, const int* a_off, int n_total, int n_max, const float* b, int ldb,
+                         const int* b_off, int m_max, int c, int B, u64* packed, hipStream_t st) {
+    PCRCG_CHECK_HIP(hipMemsetAsync(packed, 0, (size_t)n_total * 8, st));
+    if (c == 32 && lda % 4 == 0 && ldb % 4 == 0 && ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15) == 0 &&
+        debug_opts().bwd_mfma) {
+        const int gxm = (n_max + 127) / 128;
+        long splits = (1024 + (long)gxm * B - 1) / ((long)gxm * B);
+        const int max_splits = (m_max + 255) / 256;
+        if (splits > max_splits) splits = max_splits;
+        if (splits < 1) splits = 1;
+        const int cols_per = ((m_max + (int)splits - 1) / (int)splits + 31) / 32 * 32;
+        hipLaunchKernelGGL(k_feature_argmax_mfma32_batch, dim3(gxm, (m_max + cols_per - 1) / cols_per, B), dim3(256), 0, st, a, lda,
+                           a_off, b, ldb, b_off, cols_per, packed);
+        PCRCG_CHECK_LAUNCH();
+        return PCRCG_OK;
+    }
+    const int gx = (n_max + 255) / 256;
+    long splits = (2048 + (long)gx * B - 1) / ((long)gx * B);
+    const int max_splits = (m_max + 127) / 128;
+    if (splits > max_splits) splits = max_splits;
+    if (splits < 1) splits = 1;
+    const int cols_per = ((m_max + (int)splits - 1) / (int)splits + 127) / 128 * 128;
+    const dim3 grid(gx, (m_max + cols_per - 1) / cols_per, B);
+    if (c == 32) hipLaunchKernelGGL(k_feature_argmax_batch<32>, grid, dim3(256), 0, st, a, lda, a_off, b, ldb, b_off, cols_per, packed);
+    else if (c == 64) hipLaunchKernelGGL(k_feature_argmax_batch<64>, grid, dim3(256), 0, st, a, lda, a_off, b, ldb, b_off, cols_per, packed);
+    else hipLaunchKernelGGL(k_feature_argmax_any_batch, grid, dim3(256), 0, st, a, lda, a_off, b, ldb, b_off, c, cols_per, packed);
+    PCRCG_CHECK_LAUNCH();
+    return PCRCG_OK;
+}
+
+constexpr int kMaxThresholds = 32;
+
+struct InlierArgs {
+    const float* src;
+    const int* src_off;
+    const float* tgt;
+    const int* tgt_off;
+    const u64* ps;      // [n_total] winners of the source rows (column = target, local)
+    const u64* pt;      // [m_total] winners of the target rows (column = source, local)
+    const float* rt;    // [B, 12] R (row-major) then t
+    int* counts;        // [B, 2, n_thr]: "wo" then "w"
+    int* k_mutual;      // [B]
+    float* dist;        // [n_total] or null
+    int* mutual;        // [n_total] or null
+    int n_thr;
+    float thr[kMaxThresholds];
+};
+
+// grid (row blocks, pair): one thread per source row i of pair p.  The row's match j = arg_s[i] (local), the source point
+// moved with unfused fp32 ((r0 x + r1 y) + r2 z) + t (the arithmetic of RANSAC's evaluation), d = sqrtf(((dx dx + dy dy) +
+// dz dz)) correctly rounded (this file is compiled without contraction and with HIP's correctly rounded fp32 sqrt), and
+// for every threshold "wo" += d < thr, "w" += (arg_t[j] == i) && d < thr.  Integer counts: the workgroup's wavefronts
+// meet by ballots in LDS and the workgroups by atomicAdd, so the totals do not depend on the order.
+__global__ void __launch_bounds__(256) k_inlier_stats(InlierArgs s) {
+    __shared__ int s_cnt[2 * kMaxThresholds + 1];
+    __shared__ float s_thr[kMaxThresholds];
+    const int p = blockIdx.y;
+    const int i0 = s.src_off[p], n = s.src_off[p + 1] - i0;
+    const int j0 = s.tgt_off[p], m = s.tgt_off[p + 1] - j0;
+    if ((int)blockIdx.x * 256 >= n) return;
+    const int nt = s.n_thr;
+    if (threadIdx.x < 2 * nt + 1) s_cnt[threadIdx.x] = 0;
+    if (threadIdx.x < nt) s_thr[threadIdx.x] = s.thr[threadIdx.x];
+    __syncthreads();
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    float d = __builtin_nanf("");
+    bool live = false, mut = false;
+    if (i < n) {
+        const int j = packed_col(s.ps[i0 + i]);
+        if (j >= 0 && j < m) {                       // always, unless the pair has no target (m = 0): no match, NaN
+            live = true;
+            const float* T = s.rt + 12 * (long)p;
+            const float* q = s.src + 3 * (long)(i0 + i);
+            const float* t = s.tgt + 3 * (long)(j0 + j);
+            const float x = q[0], y = q[1], z = q[2];
+            const float px = ((T[0] * x + T[1] * y) + T[2] * z) + T[9];
+            const float py = ((T[3] * x + T[4] * y) + T[5] * z) + T[10];
+            const float pz = ((T[6] * x + T[7] * y) + T[8] * z) + T[11];
+            const float dx = px - t[0], dy = py - t[1], dz = pz - t[2];
+            d = sqrtf((dx * dx + dy * dy) + dz * dz);
+            mut = packed_col(s.pt[j0 + j]) == i;
+        }
+        if (s.dist) s.dist[i0 + i] = d;
+        if (s.mutual) s.mutual[i0 + i] = mut ? 1 : 0;
+    }
+    const bool lane0 = (threadIdx.x & 63) == 0;
+    const u64 km = __ballot(live && mut);
+    if (lane0 && km) atomicAdd(&s_cnt[2 * nt], (int)__popcll(km));
+    for (int k = 0; k < nt; ++k) {
+        const bool in = live && d < s_thr[k];
+        const u64 wo = __ballot(in), w = __ballot(in && mut);
+        if (lane0 && wo) atomicAdd(&s_cnt[k], (int)__popcll(wo));
+        if (lane0 && w) atomicAdd(&s_cnt[nt + k], (int)__popcll(w));
+    }
+    __syncthreads();
+    if (threadIdx.x < 2 * nt && s_cnt[threadIdx.x]) atomicAdd(&s.counts[2 * nt * (long)p + threadIdx.x], s_cnt[threadIdx.x]);
+    if (threadIdx.x == 2 * nt && s_cnt[2 * nt]) atomicAdd(&s.k_mutual[p], s_cnt[2 * nt]);
+}
+
+struct InlierWs {
+    u64* ps;   // [n_total]
+    u64* pt;   // [m_total]
+};
+
+InlierWs carve_inlier(Carver& cv, int n_total, int m_total) {
+    InlierWs w;
+    w.ps = cv.take<u64>((size_t)(n_total > 0 ? n_total : 1));
+    w.pt = cv.take<u64>((size_t)(m_total > 0 ? m_total : 1));
+    return w;
+}
+
 constexpr int kMaxBatch = 65535;      // pairs ride on a grid dimension
 
 }  // namespace
@@ -891,6 +1048,46 @@ int pcrcg_ransac_batch(const float* src, const int* src_off, const float* tgt, c
                        w.counts, w.sums);
     hipLaunchKernelGGL(k_select_batch, dim3(B), dim3(256), 0, st, a, w.offs, w.npass, B, w.vid, w.counts, w.sums, out_transform,
                        out_stats);
+    PCRCG_CHECK_LAUNCH();
+    return PCRCG_OK;
+}
+
+size_t pcrcg_inlier_stats_batch_ws_bytes(int B, int n_total, int m_total) {
+    if (B < 1 || B > kMaxBatch || n_total < 1 || m_total < 1) return 0;
+    Carver cv(nullptr, 0);
+    carve_inlier(cv, n_total, m_total);
+    return cv.off;
+}
+
+int pcrcg_inlier_stats_batch(const float* src, const float* src_feat, int ld_src, const int* src_off, int n_total, int n_max,
+                             const float* tgt, const float* tgt_feat, int ld_tgt, const int* tgt_off, int m_total, int m_max,
+                             int c, int B, const float* rt, const float* thr, int n_thr, int* counts, int* k_mutual,
+                             float* dist, int* mutual, int* arg_s, int* arg_t, void* ws, size_t ws_bytes, void* stream) {
+    PCRCG_CHECK_ARG(src && src_feat && src_off && tgt && tgt_feat && tgt_off && rt && thr && counts && k_mutual && ws);
+    PCRCG_CHECK_ARG(B >= 1 && B <= kMaxBatch);
+    PCRCG_CHECK_ARG(n_thr >= 1 && n_thr <= kMaxThresholds);
+    PCRCG_CHECK_ARG(n_max >= 1 && m_max >= 1 && n_total >= n_max && m_total >= m_max);
+    PCRCG_CHECK_ARG(c >= 1 && ld_src >= c && ld_tgt >= c);
+    Carver cv(ws, ws_bytes);
+    InlierWs w = carve_inlier(cv, n_total, m_total);
+    PCRCG_CHECK_WS(cv);
+    InlierArgs a;
+    for (int k = 0; k < n_thr; ++k) {
+        PCRCG_CHECK_ARG(!(thr[k] != thr[k]));        // a NaN threshold
+        a.thr[k] = thr[k];
+    }
+    for (int k = n_thr; k < kMaxThresholds; ++k) a.thr[k] = 0.f;
+    hipStream_t st = as_stream(stream);
+    PCRCG_PROPAGATE(feature_argmax_batch(src_feat, ld_src, src_off, n_total, n_max, tgt_feat, ld_tgt, tgt_off, m_max, c, B, w.ps, st));
+    PCRCG_PROPAGATE(feature_argmax_batch(tgt_feat, ld_tgt, tgt_off, m_total, m_max, src_feat, ld_src, src_off, n_max, c, B, w.pt, st));
+    PCRCG_CHECK_HIP(hipMemsetAsync(counts, 0, (size_t)B * 2 * n_thr * sizeof(int), st));
+    PCRCG_CHECK_HIP(hipMemsetAsync(k_mutual, 0, (size_t)B * sizeof(int), st));
+    a.src = src; a.src_off = src_off; a.tgt = tgt; a.tgt_off = tgt_off; a.ps = w.ps; a.pt = w.pt; a.rt = rt;
+    a.counts = counts; a.k_mutual = k_mutual; a.dist = dist; a.mutual = mutual; a.n_thr = n_thr;
+    hipLaunchKernelGGL(k_inlier_stats, dim3((n_max + 255) / 256, B), dim3(256), 0, st, a);
+    PCRCG_CHECK_LAUNCH();
+    if (arg_s) hipLaunchKernelGGL(k_packed_cols, dim3((n_total + 255) / 256), dim3(256), 0, st, w.ps, n_total, arg_s);
+    if (arg_t) hipLaunchKernelGGL(k_packed_cols, dim3((m_total + 255) / 256), dim3(256), 0, st, w.pt, m_total, arg_t);
     PCRCG_CHECK_LAUNCH();
     return PCRCG_OK;
 }

@@ -11,12 +11,14 @@
   * `feature_match_batch`    -- the nearest-neighbour lists of many pairs in one launch set.
   * `mutual_correspondences` -- the mutual pairs of the inner-product score ([K,2] int64 device tensor).
   * `get_inlier_ratio`       -- device version of ref:lib/benchmark_utils.py:226-267 (same `w` / `wo` dict).
+  * `inlier_ratio_batch`     -- the same ratios for many pairs and thresholds in one set of launches
+                                (`InlierRatioResult`), the inputs of feature-match recall (benchmark.py).
   * `get_angle_deviation`    -- numpy, as ref:lib/benchmark_utils.py:175-185.
 
 The algorithm (csrc/register.hip, include/pcrcg.h "Registration back end") is deterministic: a
 seed fixes every draw, and two runs give the same bits.  `register` reads the device ONCE, after the selection
-(the transform and the statistics in one buffer); every call before it is enqueued on the current stream.  So does
-`register_batch`, however many chunks of pairs it launches.
+(the transform and the statistics in one buffer); every call before it is enqueued on the current stream.  So do
+`register_batch` and `inlier_ratio_batch`, however many chunks of pairs they launch.
 """
 import ctypes
 
@@ -380,6 +382,155 @@ def get_inlier_ratio(src_pcd, tgt_pcd, src_feat, tgt_feat, rot, trans, inlier_di
     results["w"]["inlier_ratio"] = torch.as_tensor((results["w"]["distance"] < inlier_distance_threshold).mean(),
                                                    dtype=torch.float32)
     return results
+
+
+_MAX_THRESHOLDS = 32   # thresholds per inlier_ratio_batch call (include/pcrcg.h)
+
+
+class InlierRatioResult:
+    """Results of `inlier_ratio_batch` for B pairs and T thresholds (numpy, from the one read).
+
+    thresholds [T] float32; n_points [B] (source rows); counts [B, 2, T] int64 -- rows with d < thr without ("wo") and
+    with ("w") the mutual check; k_mutual [B] -- mutual rows; wo [B, T] = counts[:, 0] / n_points and w [B, T] =
+    counts[:, 1] / k_mutual (float64; NaN where a pair has no mutual row, as torch's mean of an empty tensor).
+    With distances=True: distances -- per pair the [n_b] float32 distance of every source row to its match (the
+    reference's results['wo']['distance']) -- and mutual -- per pair the [n_b] bool mask of the mutual rows, so
+    distances[b][mutual[b]] is results['w']['distance'].  With matches=True: arg_s / arg_t -- per pair the [n_b] / [m_b]
+    int64 arg-max of <a_i, b_j> along rows / columns (pcrcg_feature_argmax's, pair-local indices).  Otherwise None."""
+
+    def __init__(self, thresholds, ns, counts, k_mutual, distances=None, mutual=None, arg_s=None, arg_t=None):
+        self.thresholds = thresholds
+        self.n_points = np.asarray(ns, dtype=np.int64)
+        self.counts = counts.astype(np.int64)
+        self.k_mutual = k_mutual.astype(np.int64)
+        self.wo = self.counts[:, 0] / self.n_points[:, None]
+        with np.errstate(invalid="ignore", divide="ignore"):
+            self.w = np.where(self.k_mutual[:, None] > 0, self.counts[:, 1] / np.maximum(self.k_mutual, 1)[:, None], np.nan)
+        self.distances, self.mutual, self.arg_s, self.arg_t = distances, mutual, arg_s, arg_t
+
+    def __len__(self):
+        return len(self.n_points)
+
+    def __repr__(self):
+        return (f"InlierRatioResult(pairs={len(self)}, thresholds={list(map(float, self.thresholds))}, "
+                f"mean wo={np.nanmean(self.wo, 0)}, mean w={np.nanmean(self.w, 0)})")
+
+
+def _pose_rows(rots, trans, B, dev):
+    """[B, 12] float32 device tensor of R (row-major) then t from per-pair [3,3] rotations and [3] / [3,1] translations
+    (numpy, CPU or HIP tensors, or one [B,3,3] / [B,3(,1)] array each); rounded to fp32 as get_inlier_ratio does."""
+    def stack(xs, k):
+        if isinstance(xs, torch.Tensor):
+            t = xs.to(device=dev, dtype=torch.float32)
+        elif isinstance(xs, np.ndarray):
+            t = torch.from_numpy(np.ascontiguousarray(xs, dtype=np.float32)).to(dev)
+        else:
+            t = torch.stack([(x if isinstance(x, torch.Tensor) else torch.from_numpy(np.asarray(x))).to(dev, torch.float32)
+                             .reshape(-1) for x in xs])
+        return t.reshape(B, k)
+    return torch.cat([stack(rots, 9), stack(trans, 3)], 1).contiguous()
+
+
+def _numel(xs):
+    """Elements of an array, or summed over a list of arrays (nothing is copied)."""
+    if isinstance(xs, torch.Tensor):
+        return xs.numel()
+    if isinstance(xs, np.ndarray):
+        return xs.size
+    return sum(_numel(x) if isinstance(x, (torch.Tensor, np.ndarray)) else int(np.size(x)) for x in xs)
+
+
+def inlier_ratio_batch(src_pcds, tgt_pcds, src_feats, tgt_feats, rots, trans, thresholds=(0.1,), *, pairs_per_call=None,
+                       distances=False, matches=False):
+    """get_inlier_ratio for B pairs and up to 32 distance thresholds at once (pcrcg_inlier_stats_batch) ->
+    InlierRatioResult.  At a threshold of 0.1, pair b's wo / w equal get_inlier_ratio(src_pcds[b], ..., rots[b],
+    trans[b])'s inlier ratios, but for a point whose distance lies on the threshold (the kernel moves the points with
+    unfused fp32 arithmetic, get_inlier_ratio with a torch matmul).
+
+    Inputs: the four lists of register_batch (per-pair [N_b,3] / [M_b,3] points and [N_b,C] / [M_b,C] descriptors, one C
+    for the batch) and per-pair ground truth rots [3,3] / trans [3] or [3,1] (lists, or [B,3,3] / [B,3] arrays).  Every
+    size is checked on the host before anything is uploaded or launched.  pairs_per_call bounds the pairs per launch set;
+    by default it is the largest count whose workspace, sized with the largest pair, stays within BATCH_WS_BUDGET.  All
+    chunks write into one device buffer, read ONCE at the end."""
+    B = len(src_pcds)
+    if not (len(tgt_pcds) == len(src_feats) == len(tgt_feats) == len(rots) == len(trans) == B):
+        raise ValueError(f"inlier_ratio_batch: list lengths differ ({B}, {len(tgt_pcds)}, {len(src_feats)}, "
+                         f"{len(tgt_feats)}, {len(rots)}, {len(trans)})")
+    if B == 0:
+        raise ValueError("inlier_ratio_batch: no pairs")
+    thr = np.asarray(thresholds, dtype=np.float32).reshape(-1)
+    if not 1 <= thr.size <= _MAX_THRESHOLDS:
+        raise ValueError(f"inlier_ratio_batch: {thr.size} thresholds, the kernel takes 1..{_MAX_THRESHOLDS}")
+    if not np.isfinite(thr).all():
+        raise ValueError("inlier_ratio_batch: every threshold must be finite")
+    ns = [_rows(x) for x in src_pcds]
+    ms = [_rows(x) for x in tgt_pcds]
+    c = None
+    for b in range(B):
+        if ns[b] == 0 or ms[b] == 0:
+            raise ValueError(f"inlier_ratio_batch: pair {b} has an empty cloud ({ns[b]}, {ms[b]} points)")
+        fs, ft = src_feats[b], tgt_feats[b]
+        if _rows(fs) != ns[b] or _rows(ft) != ms[b]:
+            raise ValueError(f"inlier_ratio_batch: pair {b}: the descriptors must have one row per point")
+        cb = (fs.shape[1], ft.shape[1])
+        if c is None:
+            c = cb[0]
+        if cb != (c, c):
+            raise ValueError(f"inlier_ratio_batch: pair {b}: descriptor width {cb}, the batch uses {c}")
+    if _numel(rots) != 9 * B or _numel(trans) != 3 * B:
+        raise ValueError("inlier_ratio_batch: need a [3,3] rotation and a [3] translation per pair")
+    L = _lib.lib()
+    if pairs_per_call is None:
+        per_pair = L.pcrcg_inlier_stats_batch_ws_bytes(1, max(ns), max(ms))
+        pairs_per_call = max(1, BATCH_WS_BUDGET // max(per_pair, 1))
+    P = max(1, min(int(pairs_per_call), B, _MAX_BATCH))
+    chunks = [(b0, min(B, b0 + P)) for b0 in range(0, B, P)]
+    if any(max(sum(ns[b0:b1]), sum(ms[b0:b1])) > 0x7FFFFFFF for b0, b1 in chunks):
+        raise ValueError("inlier_ratio_batch: more than 2^31 - 1 rows per call; lower pairs_per_call")
+    dev = _device(*src_pcds, *tgt_pcds, *src_feats, *tgt_feats)
+    wsb = max(L.pcrcg_inlier_stats_batch_ws_bytes(b1 - b0, sum(ns[b0:b1]), sum(ms[b0:b1])) for b0, b1 in chunks)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    rt = _pose_rows(rots, trans, B, dev)
+    T, N, M = thr.size, sum(ns), sum(ms)
+    # one int32 buffer, read once: counts [B,2,T] | k_mutual [B] | dist [N] (f32 bits) | mutual [N] | arg_s [N] | arg_t [M]
+    o_k = 2 * T * B
+    o_d = o_k + B
+    o_m = o_d + (N if distances else 0)
+    o_as = o_m + (N if distances else 0)
+    o_at = o_as + (N if matches else 0)
+    out = torch.empty(o_at + (M if matches else 0), dtype=torch.int32, device=dev)
+    thr_h = (ctypes.c_float * T)(*thr.tolist())
+
+    def ptr(o, on):
+        return out[o:].data_ptr() if on else None
+
+    for b0, b1 in chunks:
+        nb = b1 - b0
+        r0, q0 = sum(ns[:b0]), sum(ms[:b0])
+        n_tot, m_tot = sum(ns[b0:b1]), sum(ms[b0:b1])
+        src = _cat(src_pcds[b0:b1], dev, "src_pcds", 3)
+        tgt = _cat(tgt_pcds[b0:b1], dev, "tgt_pcds", 3)
+        fa = _cat(src_feats[b0:b1], dev, "src_feats", c)
+        fb = _cat(tgt_feats[b0:b1], dev, "tgt_feats", c)
+        offs = torch.tensor(np.concatenate([np.cumsum([0] + ns[b0:b1]), np.cumsum([0] + ms[b0:b1])]), dtype=torch.int32,
+                            device=dev)
+        _lib.check(L.pcrcg_inlier_stats_batch(src.data_ptr(), fa.data_ptr(), c, offs.data_ptr(), n_tot, max(ns[b0:b1]),
+                                              tgt.data_ptr(), fb.data_ptr(), c, offs[nb + 1:].data_ptr(), m_tot,
+                                              max(ms[b0:b1]), c, nb, rt[b0:].data_ptr(), thr_h, T,
+                                              out[2 * T * b0:].data_ptr(), out[o_k + b0:].data_ptr(),
+                                              ptr(o_d + r0, distances), ptr(o_m + r0, distances), ptr(o_as + r0, matches),
+                                              ptr(o_at + q0, matches), ws.data_ptr(), wsb, _stream()),
+                   "pcrcg_inlier_stats_batch")
+    h = _read(out)
+    split_n, split_m = np.cumsum(ns)[:-1], np.cumsum(ms)[:-1]
+    dist = mut = arg_s = arg_t = None
+    if distances:
+        dist = np.split(h[o_d:o_d + N].view(np.float32).copy(), split_n)
+        mut = np.split(h[o_m:o_m + N] != 0, split_n)
+    if matches:
+        arg_s = np.split(h[o_as:o_as + N].astype(np.int64), split_n)
+        arg_t = np.split(h[o_at:o_at + M].astype(np.int64), split_m)
+    return InlierRatioResult(thr, ns, h[:o_k].reshape(B, 2, T), h[o_k:o_k + B], dist, mut, arg_s, arg_t)
 
 
 def get_angle_deviation(R_pred, R_gt):

@@ -10,7 +10,9 @@ registration back end.
                        points; only the scores cross the bus (two [N] vectors).
   * `register_record` -- the loop of the 3DMatch evaluation and of KITTITester (ref:lib/tester.py:140-169): sampling on
                        both sides, then RANSAC on the device (pcrcg_amd/registration.py; open3d is not needed).
-  * `register_records` -- the same loop over many records with ONE batched RANSAC (registration.register_batch)."""
+  * `register_records` -- the same loop over many records with ONE batched RANSAC (registration.register_batch).
+  * `evaluate_records` -- the same poses and, from the same samples, the inlier ratios against the records' ground
+                       truth (registration.inlier_ratio_batch): everything the 3DMatch table needs."""
 import numpy as np
 import torch
 
@@ -77,6 +79,14 @@ def register_records(records, n_points=5000, distance_threshold=0.05, ransac_n=3
     under the same np.random state the result equals [register_record(r, ...) for r in records] exactly.  seeds: one int
     for every record, or one per record."""
     from .registration import register_batch
+    src_pcds, tgt_pcds, src_feats, tgt_feats = _sample_records(records, n_points)
+    res = register_batch(src_pcds, tgt_pcds, src_feats, tgt_feats, distance_threshold, ransac_n, seeds=seeds)
+    return list(res.matrices)
+
+
+def _sample_records(records, n_points):
+    """The samples of register_record's loop over `records`: record by record, source then target, on the host
+    generator -> four lists (source points, target points, source descriptors, target descriptors)."""
     src_pcds, tgt_pcds, src_feats, tgt_feats = [], [], [], []
     for record in records:
         ls = record["len_src"]
@@ -85,5 +95,17 @@ def register_records(records, n_points=5000, distance_threshold=0.05, ransac_n=3
         sp, sf, _ = probabilistic_sample(pcd[:ls], feats[:ls], scores[:ls], n_points)
         tp, tf, _ = probabilistic_sample(pcd[ls:], feats[ls:], scores[ls:], n_points)
         src_pcds.append(sp); src_feats.append(sf); tgt_pcds.append(tp); tgt_feats.append(tf)
+    return src_pcds, tgt_pcds, src_feats, tgt_feats
+
+
+def evaluate_records(records, n_points=5000, distance_threshold=0.05, ransac_n=3, seeds=0, inlier_thresholds=(0.1,)):
+    """-> (poses, inliers): register_records' poses (list of float64 numpy [4,4]) and registration.inlier_ratio_batch on
+    the SAME samples against each record's ground truth (record["rot"], record["trans"]) at `inlier_thresholds`.  The
+    host generator is consumed exactly as register_records consumes it, so under the same np.random state the poses
+    equal register_records' bit for bit."""
+    from .registration import inlier_ratio_batch, register_batch
+    src_pcds, tgt_pcds, src_feats, tgt_feats = _sample_records(records, n_points)
     res = register_batch(src_pcds, tgt_pcds, src_feats, tgt_feats, distance_threshold, ransac_n, seeds=seeds)
-    return list(res.matrices)
+    inliers = inlier_ratio_batch(src_pcds, tgt_pcds, src_feats, tgt_feats, [r["rot"] for r in records],
+                                 [r["trans"] for r in records], inlier_thresholds)
+    return list(res.matrices), inliers

@@ -7,9 +7,13 @@ record is sampled on the host generator (overlap x saliency, source then target)
 batched RANSAC (tester.register_records -> registration.register_batch).  The poses are written per scene as
 `{exp_dir}/{n_points}/{scene}/est.log` -- the records taken in the order of the scenes of `--gt_folder` (sorted) and
 of the pairs of each scene's gt.log -- and scored with benchmark.benchmark, which writes `{exp_dir}/{n_points}/result`.
+With --inlier_ratio the same samples also give the inlier ratios against the records' ground truth
+(tester.evaluate_records -> registration.inlier_ratio_batch, one batched call); the inlier ratio (IR) and feature-match
+recall (FMR) lines of benchmark.feature_match_recall, without and with the mutual check, are appended to each `result`
+and added to the summary.
 
   python scripts/evaluate_registration.py --source_path snapshot/.../test/pth --gt_folder configs/benchmarks/3DMatch \\
-      --exp_dir snapshot/.../est_traj [--n_points 250 500 1000 2500 5000]
+      --exp_dir snapshot/.../est_traj [--n_points 250 500 1000 2500 5000] [--inlier_ratio]
 """
 import argparse
 import json
@@ -39,6 +43,9 @@ def main():
     ap.add_argument("--distance_threshold", type=float, default=0.05)
     ap.add_argument("--ransac_n", type=int, default=3)
     ap.add_argument("--seed", type=int, default=0, help="np.random seed before each sampling pass")
+    ap.add_argument("--inlier_ratio", action="store_true", help="also report the inlier ratio and feature-match recall")
+    ap.add_argument("--inlier_distance", type=float, default=0.1, help="inlier distance threshold of IR / FMR (m)")
+    ap.add_argument("--fmr_threshold", type=float, default=0.05, help="inlier ratio above which a pair counts for FMR")
     a = ap.parse_args()
 
     files = sorted((f for f in os.listdir(a.source_path) if f.endswith(".pth")), key=natural_key)
@@ -50,8 +57,12 @@ def main():
     summary = {}
     for n_points in a.n_points:
         np.random.seed(a.seed)
-        poses = tester.register_records(records, n_points=n_points, distance_threshold=a.distance_threshold,
-                                        ransac_n=a.ransac_n)
+        if a.inlier_ratio:
+            poses, inliers = tester.evaluate_records(records, n_points=n_points, distance_threshold=a.distance_threshold,
+                                                     ransac_n=a.ransac_n, inlier_thresholds=(a.inlier_distance,))
+        else:
+            poses = tester.register_records(records, n_points=n_points, distance_threshold=a.distance_threshold,
+                                            ransac_n=a.ransac_n)
         out_dir = os.path.join(a.exp_dir, str(n_points))
         o = 0
         for scene, k in zip(scenes, keys):
@@ -59,6 +70,15 @@ def main():
             o += len(k)
         res = BM.benchmark(out_dir, a.gt_folder)
         summary[n_points] = {"mean_recall": res["mean_recall"], "mean_precision": res["mean_precision"]}
+        if a.inlier_ratio:
+            split = BM.get_scene_split(a.gt_folder)
+            with open(os.path.join(out_dir, "result"), "a") as f:
+                for key, label in (("wo", ""), ("w", " (mutual)")):
+                    fm = BM.feature_match_recall(getattr(inliers, key)[:, 0], split, a.fmr_threshold)
+                    f.write("Inlier ratio{}: {:.3f}: +- {:.3f}\n".format(label, fm["ir_mean"], fm["ir_std"]))
+                    f.write("Feature match recall{}: {:.3f}: +- {:.3f}\n".format(label, fm["fmr_mean"], fm["fmr_std"]))
+                    summary[n_points][f"inlier_ratio_{key}"] = fm["ir_mean"]
+                    summary[n_points][f"feature_match_recall_{key}"] = fm["fmr_mean"]
         print(n_points, open(os.path.join(out_dir, "result")).read(), sep="\n")
     print(json.dumps(summary))
 
