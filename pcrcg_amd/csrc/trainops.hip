@@ -55,21 +55,28 @@ struct FixAcc {
     long long* acc;            // NULL: plain fp32 atomics (the default)
     const unsigned* maxbits;   // bit pattern of the largest |source gradient| (k_absmax_bits)
     int fan_log2;              // log2 of (contributions per element x the largest factor a contribution carries)
+    const unsigned* factorbits;  // NULL, or the bit pattern of the largest per-channel factor a contribution carries
+                                 // beyond the source gradient (edge conv: rstd), which then joins the magnitude
 };
 // An all-zero source gradient (maxbits == 0: e.g. an output nobody differentiated) has nothing to add: scale 0, every
-// contribution rounds to the integer 0 and the flush skips its (still zero) sums.  Tiny gradients would ask for a scale
-// beyond fp32's range: the exponent is clamped (the resolution is then coarser than 2^-39 of the magnitude but still far
-// below fp32's).  (Round 5 returned +inf for both: 0 * inf = NaN into __float2ll_rn.)
-__device__ __forceinline__ float fix_scale(const FixAcc& f) {
+// contribution rounds to the integer 0 and the flush skips its (still zero) sums.  The scale is a power of two held in
+// double: gradients down to fp32's subnormals keep the full 2^-(62 - fan_log2) resolution (an fp32 scale would have to
+// clamp its exponent at 126 -- ~1e-3 relative below magnitudes of 1e-26).  A contribution times the scale is exact in
+// double, so it rounds to the same integer as the fp32 product did wherever that product stayed in range.
+__device__ __forceinline__ double fix_scale(const FixAcc& f) {
     const unsigned bits = *f.maxbits;
-    if (bits == 0u) return 0.0f;
-    const int e = (int)((bits >> 23) & 0xff) - 127;                // largest magnitude < 2^(e + 1)
-    const int s = 62 - f.fan_log2 - (e + 1);
-    return ldexpf(1.0f, s > 126 ? 126 : s);
+    if (bits == 0u) return 0.0;
+    int e1 = (int)((bits >> 23) & 0xff) - 126;                     // largest magnitude < 2^e1
+    if (f.factorbits) {
+        const unsigned fb = *f.factorbits;
+        if (fb == 0u) return 0.0;
+        e1 += (int)((fb >> 23) & 0xff) - 126;
+    }
+    return ldexp(1.0, 62 - f.fan_log2 - e1);
 }
 template <bool DET>
-__device__ __forceinline__ void scatter_add(float* dst, long off, float v, const FixAcc& f, float scale) {
-    if constexpr (DET) atomicAdd(reinterpret_cast<unsigned long long*>(f.acc) + off, (unsigned long long)__float2ll_rn(v * scale));
+__device__ __forceinline__ void scatter_add(float* dst, long off, float v, const FixAcc& f, double scale) {
+    if constexpr (DET) atomicAdd(reinterpret_cast<unsigned long long*>(f.acc) + off, (unsigned long long)__double2ll_rn((double)v * scale));
     else atomicAdd(dst + off, v);
 }
 __global__ void __launch_bounds__(256) k_absmax_bits(const float* __restrict__ x, long rows, int cols, long ld, unsigned* __restrict__ out) {
@@ -89,7 +96,7 @@ __global__ void __launch_bounds__(256) k_fix_flush(long long* __restrict__ acc, 
     if (t >= n) return;
     const long long v = acc[t];
     if (v != 0) {                                                  // (a zero scale leaves only zero sums: never here)
-        dst[t] += (float)((double)v / (double)fix_scale(f));
+        dst[t] += (float)((double)v / fix_scale(f));
         acc[t] = 0;
     }
 }
@@ -112,7 +119,7 @@ __global__ void __launch_bounds__(256) k_kpconv_bwd_dx(const float* __restrict__
                                                         float* __restrict__ dx, int nchunk, FixAcc fx) {
     const int lane = threadIdx.x & 63;
     const int hsub = lane >> 4, j = lane & 15;
-    const float fscale = DET ? fix_scale(fx) : 1.0f;
+    const double fscale = DET ? fix_scale(fx) : 1.0;
     const long item = (long)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     if (item >= (long)nq * nchunk) return;
     const int q = (int)(item / nchunk), chunk = (int)(item - (long)q * nchunk);
@@ -176,7 +183,7 @@ __global__ void __launch_bounds__(256) k_kpconv_bwd_dx_mfma(const float* __restr
                                                              float* __restrict__ dx, int nchunk, FixAcc fx) {
     const int lane = threadIdx.x & 63;
     const int hsub = lane >> 4, j = lane & 15;
-    const float fscale = DET ? fix_scale(fx) : 1.0f;
+    const double fscale = DET ? fix_scale(fx) : 1.0;
     const long item = (long)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     if (item >= (long)nq * nchunk) return;
     const int q = (int)(item / nchunk), chunk = (int)(item - (long)q * nchunk);
@@ -249,7 +256,7 @@ __global__ void __launch_bounds__(256) k_gather_max_bwd(const float* __restrict_
     const int q = (int)(item / nchunk), chunk = (int)(item - (long)q * nchunk);
     const int cc = chunk * 64 + lane;
     if (cc >= c) return;
-    const float fscale = DET ? fix_scale(fx) : 1.0f;
+    const double fscale = DET ? fix_scale(fx) : 1.0;
     const float m = y[(long)q * c + cc], gq = dy[(long)q * c + cc];
     const long long* row = idx + (long)q * ld_idx;
     for (int jn = 0; jn < h; ++jn) {
@@ -276,7 +283,7 @@ __global__ void __launch_bounds__(256) k_gather_max_bwd4(const float* __restrict
     const int q = (int)(item / nchunk), chunk = (int)(item - (long)q * nchunk);
     const int cb = chunk * 64 + lane;
     if (cb >= (c >> 2)) return;
-    const float fscale = DET ? fix_scale(fx) : 1.0f;
+    const double fscale = DET ? fix_scale(fx) : 1.0;
     const float4 m = reinterpret_cast<const float4*>(y + (long)q * c)[cb], gq = reinterpret_cast<const float4*>(dy + (long)q * c)[cb];
     const long long* row = idx + (long)q * ld_idx;
     // where each channel meets its maximum FIRST (that row takes the gradient); the adds are issued after the walk, whole
@@ -322,7 +329,7 @@ __global__ void __launch_bounds__(256) k_gather_first_bwd(const float* __restric
     if (q >= nq) return;
     const long long i = idx[(long)q * ld_idx];
     if (i < 0 || i >= ns) return;
-    const float fscale = DET ? fix_scale(fx) : 1.0f;
+    const double fscale = DET ? fix_scale(fx) : 1.0;
     for (int cc = lane; cc < c; cc += 64) scatter_add<DET>(dx, i * c + cc, dy[(long)q * ld_dy + cc], fx, fscale);
 }
 
@@ -540,7 +547,7 @@ __global__ void __launch_bounds__(256) k_edge_bwd_apply(const float* __restrict_
     }
     const float nm = (m - mean) * rstd;
     const float dn = dy[(long)r * c + ch] * (nm > 0.f ? 1.0f : slope);
-    const float fscale = DET ? fix_scale(fx) : 1.0f;
+    const double fscale = DET ? fix_scale(fx) : 1.0;
     float acc = 0.f;
     for (int j = 0; j < k; ++j) {
         const int s = idx[(long)r * k + j];
@@ -562,8 +569,10 @@ namespace {
 struct DetScratch { long long* acc = nullptr; size_t elems = 0; unsigned* word = nullptr; };
 std::mutex g_det_lock;
 std::map<hipStream_t, DetScratch> g_det;
-// -> a FixAcc over a zeroed buffer of at least `elems` elements whose scale follows the largest |src| value; NULL acc on failure
-int det_begin(hipStream_t st, size_t elems, const float* src, long rows, int cols, long ld, int fan_log2, FixAcc* out) {
+// -> a FixAcc over a zeroed buffer of at least `elems` elements whose scale follows the largest |src| value (times the largest
+// |factor[r * factor_ld]|, r < factor_rows, when `factor` is given); NULL acc on failure
+int det_begin(hipStream_t st, size_t elems, const float* src, long rows, int cols, long ld, int fan_log2, FixAcc* out,
+              const float* factor = nullptr, long factor_rows = 0, long factor_ld = 1) {
     DetScratch d;
     {
         std::lock_guard<std::mutex> g(g_det_lock);
@@ -580,15 +589,19 @@ int det_begin(hipStream_t st, size_t elems, const float* src, long rows, int col
         if (!slot.word) PCRCG_CHECK_HIP(hipMalloc(&slot.word, 256));
         d = slot;
     }
-    PCRCG_CHECK_HIP(hipMemsetAsync(d.word, 0, sizeof(unsigned), st));
+    PCRCG_CHECK_HIP(hipMemsetAsync(d.word, 0, 2 * sizeof(unsigned), st));
     const long total = rows * cols;
     long blocks = (total + 255) / 256;
     if (blocks > 1024) blocks = 1024;
     if (total > 0) hipLaunchKernelGGL(k_absmax_bits, dim3((unsigned)blocks), dim3(256), 0, st, src, rows, cols, ld, d.word);
+    if (factor && factor_rows > 0)
+        hipLaunchKernelGGL(k_absmax_bits, dim3((unsigned)((factor_rows + 255) / 256 < 1024 ? (factor_rows + 255) / 256 : 1024)),
+                           dim3(256), 0, st, factor, factor_rows, 1, factor_ld, d.word + 1);
     PCRCG_CHECK_LAUNCH();
     out->acc = d.acc;
     out->maxbits = d.word;
     out->fan_log2 = fan_log2;
+    out->factorbits = factor ? d.word + 1 : nullptr;
     return PCRCG_OK;
 }
 }  // namespace
@@ -609,7 +622,7 @@ int det_end(hipStream_t st, const FixAcc& fx, float* dst, size_t elems) {
     PCRCG_CHECK_LAUNCH();
     return PCRCG_OK;
 }
-const FixAcc kNoFix{nullptr, nullptr, 0};
+const FixAcc kNoFix{nullptr, nullptr, 0, nullptr};
 }  // namespace
 
 extern "C" size_t pcrcg_feature_argmax_ws_bytes(int n) { return carve_bytes((size_t)(n > 0 ? n : 1), 8); }
@@ -817,10 +830,15 @@ extern "C" int pcrcg_edgeconv_backward(const float* ctr, const float* nbr, const
     hipLaunchKernelGGL(k_edge_bwd_sums, dim3(gx, (c + 63) / 64), dim3(256), 0, st, ctr, nbr, idx, n, k, c, stats, dy, slope,
                        sums);
     if (det) {
-        // |de| <= rstd (|dn| + |S1/E| + |n| |S2/E|) <= 2^9 max|dy| (2 + 2^11) (rstd <= eps^-1/2, |n| <= sqrt(E), mean|n| <= 1),
-        // at most n k <= 2^15 edges per neighbour row
+        // |de| <= rstd (|dn| + |S1/E| + |n| |S2/E|) <= max(rstd) max|dy| (2 + sqrt(E)) (|n| <= sqrt(E), mean|n| <= 1), at most
+        // E = n k edges per neighbour row: E (2 + sqrt(E)) < 2^36 for E < 2^23 (more edges widen the fan).  The scale follows
+        // max|dy| x max(rstd), the scale of the result: from max|dy| alone the resolution relative to dnbr was 2^-26 / rstd
+        // (1e-3 at a feature std of 1e4).
+        const double edges = (double)n * (double)k;
+        int fan = 36;
+        while (edges * (2.0 + sqrt(edges)) >= ldexp(1.0, fan)) ++fan;
         FixAcc fx;
-        PCRCG_PROPAGATE(det_begin(st, (size_t)n * c, dy, n, c, c, 36, &fx));
+        PCRCG_PROPAGATE(det_begin(st, (size_t)n * c, dy, n, c, c, fan, &fx, stats + 1, c, 2));
         hipLaunchKernelGGL(k_edge_bwd_apply<true>, dim3((n + 3) / 4, (c + 63) / 64), dim3(256), 0, st, ctr, nbr, idx, n, k, c, stats,
                            dy, slope, sums, dctr, dnbr, fx);
         PCRCG_CHECK_LAUNCH();

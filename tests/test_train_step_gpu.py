@@ -52,6 +52,26 @@ def _train_forward(net, batch, path):
 @pytest.mark.parametrize("path", ["cpp", "python"])
 def test_full_model_gradients_match_oracle_autograd(cuda, golden_dir, path):
     """d(scalar)/d(every parameter) through encoder, GNN, saliency head and decoder."""
+    _check_full_model_gradients(cuda, golden_dir, path)
+
+
+@pytest.mark.parametrize("path", ["cpp", "python"])
+def test_full_model_gradients_match_oracle_autograd_deterministic(cuda, golden_dir, path):
+    """The same check under deterministic=1 (include/pcrcg.h), against the same float64 oracle at the same bars: the
+    fixed-point scatters, stored-partial statistics, split-K-free products and the runner's own kernels of that mode."""
+    from pcrcg_amd import _lib
+    L = _lib.lib()
+    _lib.check(L.pcrcg_debug_set(b"deterministic=1"), "pcrcg_debug_set")
+    try:
+        assert L.pcrcg_attention_backward_supported(64, 64, 64, 256, 256, 256, 256) == 0      # the mode is on
+        _check_full_model_gradients(cuda, golden_dir, path)
+    finally:
+        torch.cuda.synchronize()
+        _lib.check(L.pcrcg_debug_set(None), "pcrcg_debug_set")
+        _lib.check(L.pcrcg_debug_release(), "pcrcg_debug_release")
+
+
+def _check_full_model_gradients(cuda, golden_dir, path):
     gold = torch.load(os.path.join(golden_dir, "model_mini.pt"))
     col = torch.load(os.path.join(golden_dir, "collate_mini.pt"))
     cfg = indoor_config(**{k: v for k, v in gold["config"].items() if k in ("first_feats_dim", "gnn_feats_dim")})
