@@ -266,9 +266,16 @@ __global__ void __launch_bounds__(256) k_gemm_f32(const float* __restrict__ A, i
         const int gn = n0 + wn * WN + j * 32 + l31;
         bv[j] = (bias && first_split) ? bias[min(gn, N - 1)] : 0.0f;
     }
-    float cs[TN], cq[TN];   // per-column sum / sum of squares over this wavefront's rows (InstanceNorm partials)
+    // per-column sum / sum of squares over this wavefront's rows (InstanceNorm partials), accumulated in fp32 about a pivot, the
+    // lane's first value of the column, and rebuilt in double (as k_gemm_x6: fp32 sums of v^2 lose (mean / std)^2 of var)
+    float cs[TN], cq[TN], piv[TN];
+    int cnt = 0;
 #pragma unroll
-    for (int j = 0; j < TN; ++j) { cs[j] = 0.f; cq[j] = 0.f; }
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) cnt += m0 + wm * WM + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * half < M ? 1 : 0;
+#pragma unroll
+    for (int j = 0; j < TN; ++j) { cs[j] = 0.f; cq[j] = 0.f; piv[j] = acc[0][j][0] * rs[0][0] + bv[j]; }
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -282,8 +289,9 @@ __global__ void __launch_bounds__(256) k_gemm_f32(const float* __restrict__ A, i
                     float* dst = C + (long)gm * ldc + gn;
                     if (atomic_out) atomicAdd(dst, v);
                     else *dst = v;
-                    cs[j] += v;
-                    cq[j] += v * v;
+                    const float d = v - piv[j];
+                    cs[j] += d;
+                    cq[j] += d * d;
                 }
             }
         }
@@ -293,11 +301,13 @@ __global__ void __launch_bounds__(256) k_gemm_f32(const float* __restrict__ A, i
         const int chunk = tile_y * WAVES_M + wm;
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
-            const float s = cs[j] + __shfl_xor(cs[j], 32, 64), q2 = cq[j] + __shfl_xor(cq[j], 32, 64);
+            const double p = cnt ? (double)piv[j] : 0.0, s1 = (double)cs[j];
+            const double ds = s1 + (double)cnt * p, dq = (double)cq[j] + p * (2.0 * s1 + (double)cnt * p);
+            const double s = ds + __shfl_xor(ds, 32, 64), q2 = dq + __shfl_xor(dq, 32, 64);
             const int gn = n0 + wn * WN + j * 32 + l31;
             if (half == 0 && gn < N) {
-                colp[(long)gn * colp_chunks + chunk] = (double)s;
-                colp[((long)N + gn) * colp_chunks + chunk] = (double)q2;
+                colp[(long)gn * colp_chunks + chunk] = s;
+                colp[((long)N + gn) * colp_chunks + chunk] = q2;
             }
         }
     }

@@ -826,9 +826,18 @@ __global__ void __launch_bounds__((x6_threads<BM, BN>()), MINB) k_gemm_x6(const 
         const int gn = n0 + wn * WN + j * 32 + l31;
         bv[j] = (bias && first_split) ? bias[min(gn, N - 1)] : 0.0f;
     }
-    float cs[TN], cq[TN];
+    // Column statistics: the lane's fp32 sums run over the deviations d = v - p from a pivot p, the lane's first value of the
+    // column, and become sum(v) = sum(d) + cnt p and sum(v^2) = sum(d^2) + p (2 sum(d) + cnt p) in double.  Summed directly in
+    // fp32, sum(v^2) carries a rounding of 2^-24 mean^2 per row, which var = sum(v^2)/n - mean^2 amplifies by (mean / std)^2
+    // (rstd off by 2e-5 at mean = 100 std, by 7e-3 at 1000 std); the deviations keep it at 2^-24 std^2.
+    float cs[TN], cq[TN], piv[TN];
+    int cnt = 0;
 #pragma unroll
-    for (int j = 0; j < TN; ++j) { cs[j] = 0.f; cq[j] = 0.f; }
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) cnt += m0 + wm * WM + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * half < M ? 1 : 0;
+#pragma unroll
+    for (int j = 0; j < TN; ++j) { cs[j] = 0.f; cq[j] = 0.f; piv[j] = acc[0][j][0] * rs[0][0] + bv[j]; }
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -842,19 +851,29 @@ __global__ void __launch_bounds__((x6_threads<BM, BN>()), MINB) k_gemm_x6(const 
                     float* dst = C + (long)gm * ldc + gn;
                     if (atomic_out) atomicAdd(dst, v);
                     else *dst = v;
-                    cs[j] += v;
-                    cq[j] += v * v;
+                    const float d = v - piv[j];
+                    cs[j] += d;
+                    cq[j] += d * d;
                 }
             }
         }
+    double ds[TN], dq[TN];          // this lane's sum(v), sum(v^2) per column
+    if (colp) {
+#pragma unroll
+        for (int j = 0; j < TN; ++j) {
+            const double p = cnt ? (double)piv[j] : 0.0, s1 = (double)cs[j];
+            ds[j] = s1 + (double)cnt * p;
+            dq[j] = (double)cq[j] + p * (2.0 * s1 + (double)cnt * p);
+        }
+    }
     if (colp && colp_chunks < 0) {
         // sums mode: [2][N] accumulators zeroed by the caller.  The workgroup's two row halves meet in LDS first (the operand
         // planes are free now), so a row tile costs one pair of atomics per column, not two
-        float* const red = reinterpret_cast<float*>(smem);
+        double* const red = reinterpret_cast<double*>(smem);
         __syncthreads();                                   // every wavefront is past its last operand read
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
-            const float s = cs[j] + __shfl_xor(cs[j], 32, 64), q2 = cq[j] + __shfl_xor(cq[j], 32, 64);
+            const double s = ds[j] + __shfl_xor(ds[j], 32, 64), q2 = dq[j] + __shfl_xor(dq[j], 32, 64);
             if (wm == 1 && half == 0) {
                 red[2 * (wn * WN + j * 32 + l31)] = s;
                 red[2 * (wn * WN + j * 32 + l31) + 1] = q2;
@@ -863,24 +882,22 @@ __global__ void __launch_bounds__((x6_threads<BM, BN>()), MINB) k_gemm_x6(const 
         __syncthreads();
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
-            const float s = cs[j] + __shfl_xor(cs[j], 32, 64), q2 = cq[j] + __shfl_xor(cq[j], 32, 64);
+            const double s = ds[j] + __shfl_xor(ds[j], 32, 64), q2 = dq[j] + __shfl_xor(dq[j], 32, 64);
             const int gn = n0 + wn * WN + j * 32 + l31;
             if (wm == 0 && half == 0 && gn < N) {
-                unsafeAtomicAdd(&colp[gn], (double)s + (double)red[2 * (wn * WN + j * 32 + l31)]);
-                unsafeAtomicAdd(&colp[(long)N + gn], (double)q2 + (double)red[2 * (wn * WN + j * 32 + l31) + 1]);
+                unsafeAtomicAdd(&colp[gn], s + red[2 * (wn * WN + j * 32 + l31)]);
+                unsafeAtomicAdd(&colp[(long)N + gn], q2 + red[2 * (wn * WN + j * 32 + l31) + 1]);
             }
         }
     } else if (colp) {
         const int chunk = tile_y * WAVES_M + wm;
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
-            const float s = cs[j] + __shfl_xor(cs[j], 32, 64), q2 = cq[j] + __shfl_xor(cq[j], 32, 64);
+            const double s = ds[j] + __shfl_xor(ds[j], 32, 64), q2 = dq[j] + __shfl_xor(dq[j], 32, 64);
             const int gn = n0 + wn * WN + j * 32 + l31;
             if (half == 0 && gn < N) {
-                {
-                    colp[(long)gn * colp_chunks + chunk] = (double)s;
-                    colp[((long)N + gn) * colp_chunks + chunk] = (double)q2;
-                }
+                colp[(long)gn * colp_chunks + chunk] = s;
+                colp[((long)N + gn) * colp_chunks + chunk] = q2;
             }
         }
     }

@@ -441,6 +441,9 @@ int instnorm_colsums_multi(const float* const* x, double* const* sums, const int
     // enough row chunks to fill the chip on tall inputs, few on short ones (each adds 2 atomics per channel)
     int chunks = (nmax + 63) / 64;
     if (chunks > kStatChunks) chunks = kStatChunks;
+    // deterministic=1: one chunk, so that every accumulator takes ONE atomic add per call (onto the caller's zero: the same bits
+    // every run) instead of up to 128 adds landing in any order
+    if (debug_opts().deterministic) chunks = 1;
     hipLaunchKernelGGL(k_colstats_partial<true>, dim3(chunks, (c + 63) / 64, count), dim3(256), 0, st, mm, c, ldx);
     PCRCG_CHECK_LAUNCH();
     return PCRCG_OK;
