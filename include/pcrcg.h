@@ -55,7 +55,8 @@ const char* pcrcg_last_error(void);
  *   entries (pcrcg_ransac_batch_ws_bytes, pcrcg_feature_match_batch, pcrcg_ransac_batch), added later under version 4, and
  *   the projection entries (pcrcg_project_depth_ws_bytes, pcrcg_project_depth, pcrcg_inject_frames with its
  *   pcrcg_image_frame, pcrcg_superglue_valid_maps), added after them, and the inlier statistics
- *   (pcrcg_inlier_stats_batch_ws_bytes, pcrcg_inlier_stats_batch), added after those. */
+ *   (pcrcg_inlier_stats_batch_ws_bytes, pcrcg_inlier_stats_batch), added after those, and the 2-D backbone
+ *   (pcrcg_res50unet_arena_bytes, pcrcg_res50unet_pack, pcrcg_res50unet_ws_bytes, pcrcg_res50unet_forward), added after those. */
 #define PCRCG_ABI_VERSION 4
 int pcrcg_abi_version(void);
 
@@ -835,6 +836,34 @@ int pcrcg_inlier_stats_batch(const float* src, const float* src_feat, int ld_src
                              const float* tgt, const float* tgt_feat, int ld_tgt, const int* tgt_off, int m_total, int m_max,
                              int c, int B, const float* rt, const float* thr, int n_thr, int* counts, int* k_mutual,
                              float* dist, int* mutual, int* arg_s, int* arg_t, void* ws, size_t ws_bytes, void* stream);
+
+
+/* PCR-CG's 2-D backbone Res50UNet(out_ch) (ref:models/resunet.py:163-188; the ResNet-50 encoder of ref:models/resnet.py and
+ * the four up-projections of the decoder), forward only (the reference detaches it), enqueued by ONE call for n images.
+ *   h_tensors / h_state: HOST array of n_tensors = 392 DEVICE pointers, the reference's state_dict order (every conv weight
+ *   fp32 [cout][cin][kh][kw]; per BatchNorm2d weight, bias, running_mean, running_var f32 [C] and num_batches_tracked i64;
+ *   decoder.conv0.bias last).
+ *   pcrcg_res50unet_pack: the derived weight arena (pcrcg_res50unet_arena_bytes(out_ch) bytes): every convolution
+ *   K-contiguous [cout][kh][kw][cin], the two 5x5 convolutions of each up-projection side by side as ONE [2 cout][25 cin]
+ *   operand, the 7x7 stem as [64][160] (taps (ky, kx, ci), zero-padded).  Repack whenever a weight changes.
+ *   pcrcg_res50unet_forward: images [n, 3, h, w] f32 (CHW) -> out [n, out_ch, 2 ceil(ceil(h/2)/2), 2 ceil(ceil(w/2)/2)]
+ *   f32 (CHW; 120 x 160 at 240 x 320).  Every convolution runs as an implicit GEMM on the matrix cores with the forward
+ *   products' arithmetic (pcrcg_gemm_set_mode, mode 1: the fp16 two-term split, and the three-term bf16 form for any tile
+ *   that leaves fp16's normal range at either end); BatchNorm statistics come from fp64 column sums of the products.
+ *     training = 1: batch statistics (biased variance, eps 1e-5) for the normalisation; running_mean / running_var are
+ *       updated in place with momentum 0.1 and the unbiased variance.  joint_stats = 0: every image is its own batch of
+ *       one (n updates, in image order; num_batches_tracked += n) -- PCR-CG's per-image calls; joint_stats = 1: one set of
+ *       statistics over all n images (torch's training-mode BatchNorm2d on the batch; num_batches_tracked += 1).
+ *     training = 0: the running statistics; nothing is written but out.
+ *   Workspace: pcrcg_res50unet_ws_bytes(n, h, w) (0 for an unsupported shape).  Nothing is allocated or synchronised.
+ *   Bad arguments (null pointers, n_tensors != 392, n outside 1..65535, h or w outside 1..8192, a training call in which a
+ *   statistics segment would hold a single value) are rejected with PCRCG_EBADARG before anything launches. */
+size_t pcrcg_res50unet_arena_bytes(int out_ch);
+int pcrcg_res50unet_pack(void* const* h_tensors, int n_tensors, int out_ch, float* arena, void* stream);
+size_t pcrcg_res50unet_ws_bytes(int n_images, int h, int w);
+int pcrcg_res50unet_forward(const float* arena, void* const* h_state, int n_tensors, int out_ch, const float* images,
+                            int n_images, int h, int w, int joint_stats, int training, float* out, void* ws, size_t ws_bytes,
+                            void* stream);
 
 #ifdef __cplusplus
 }

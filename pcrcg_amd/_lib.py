@@ -140,6 +140,12 @@ SIGNATURES = {
     "pcrcg_inlier_stats_batch": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p,
                                          c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                                          c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    # PCR-CG's 2-D backbone (pcrcg_amd/resunet.py)
+    "pcrcg_res50unet_arena_bytes": (c_size_t, [c_int]),
+    "pcrcg_res50unet_pack": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "pcrcg_res50unet_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "pcrcg_res50unet_forward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                        c_void_p, c_void_p, c_size_t, c_void_p]),
     # include/pcrcg_train.h -- the "next" rows
     "pcrcg_gemm_f32_ex": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int,
                                   c_void_p, c_void_p, c_void_p]),

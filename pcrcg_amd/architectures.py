@@ -119,15 +119,29 @@ class KPFCNN(nn.Module):
         n = int(batch["points"][0].shape[0])
         len_src = int(batch["src_pcd_raw"].shape[0])
         dev = batch["points"][0].device
+        # the backbone runs in the reference's call order, src1, src2[, src3], tgt1, ... (ref:models/architectures.py:278-281):
+        # a train-mode backbone's running statistics then end where the reference's do.  Our Res50UNet takes all of a
+        # pair's images in ONE call (forward_images: per-image statistics, running buffers updated in that order).
+        fmaps = {}
+        todo = [(side, i) for side in ("src", "tgt") for i in range(1, self.img_num + 1) if f"{side}{i}_feature2d" not in batch]
+        if todo and backbone2d is not None:
+            from .resunet import Res50UNet
+            with torch.no_grad():
+                if isinstance(backbone2d, Res50UNet):
+                    x = torch.stack([batch[f"{side}_color{i}"].to(dev) for side, i in todo])
+                    for k, fmap in zip(todo, backbone2d.forward_images(x)):
+                        fmaps[k] = fmap
+                else:
+                    for side, i in todo:
+                        fmaps[side, i] = backbone2d(batch[f"{side}_color{i}"].unsqueeze(0).to(dev)).squeeze(0)
         images = []
         for side in ("src", "tgt"):
             for i in range(self.img_num, 0, -1):              # the reference writes image 3, 2, 1: image 1 wins (:242-247)
                 key = f"{side}{i}_feature2d"
                 if key in batch:
                     fmap = batch[key]
-                elif backbone2d is not None:
-                    with torch.no_grad():
-                        fmap = backbone2d(batch[f"{side}_color{i}"].unsqueeze(0).to(dev)).squeeze(0)
+                elif (side, i) in fmaps:
+                    fmap = fmaps[side, i]
                 else:
                     raise RuntimeError(f"pcrcg_amd.KPFCNN: image_feature needs backbone2d or batch['{key}']")
                 valid = batch.get(f"{side}_valid_map{i}") if self.img_num < 3 else None   # :196-252 has no valid maps
