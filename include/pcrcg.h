@@ -71,13 +71,14 @@ int pcrcg_abi_version(void);
  *   train_side_stream=1 bwd_mfma=1                                                         train-step backward
  *   deterministic=0    1: bit-reproducible results -- no floating-point atomics (split-K partial tiles stored and added in
  *                      split order by a second pass, InstanceNorm statistics from stored partials, fixed-point scatter sums
- *                      in the train step); implies stat_sums=0 gemm_splitk=1; allocates its scratch itself.  Together with a fixed pairing of the pair engine (PairStreams(adaptive_jobs=False))
+ *                      in the train step, the 2-D backbone's BatchNorm sums stored per row tile and added in a fixed
+ *                      order by a finishing pass per product); implies stat_sums=0 gemm_splitk=1; allocates its scratch itself.  Together with a fixed pairing of the pair engine (PairStreams(adaptive_jobs=False))
  *                      outputs are a function of the inputs alone.
  * Returns PCRCG_EBADARG (and changes nothing) on an unknown name.  A switch that has been retired -- its default is now the
  * only behaviour, or its measurement aid is gone (DESIGN.md section 5 names them) -- is an unknown name like any other. */
 int pcrcg_debug_set(const char* spec);
 /* deterministic=1 allocates its scratch itself (partial tiles of split-K products, 64-bit fixed-point sums of the train
- * step's scatters): one buffer per stream it has run on, keyed by the stream handle, grown on demand and kept until the
+ * step's scatters, the backbone's per-tile BatchNorm sums -- pcrcg_res50unet_ws_bytes is the same in both modes): one buffer per stream it has run on, keyed by the stream handle, grown on demand and kept until the
  * process ends.  This frees all of it (after a device-wide synchronise): call it before destroying streams the mode has
  * used -- a recycled handle would otherwise inherit a stale entry -- or to get the memory back. */
 int pcrcg_debug_release(void);

@@ -51,9 +51,10 @@ int instnorm_apply_pack(const float* x, int n, int c, int ldx, const float* stat
 // kpconv.hip: where the support records live inside a pcrcg_kpconv_ws_bytes(ns) workspace
 float4* kpconv_pk_ptr(void* ws, size_t ws_bytes, int ns);
 
-// the deterministic debug mode's scratch (gemm_x6.hip, trainops.hip): freed by pcrcg_debug_release()
+// the deterministic debug mode's scratch (gemm_x6.hip, trainops.hip, conv2d.hip): freed by pcrcg_debug_release()
 void gemm_x6_release_det();
 void trainops_release_det();
+void conv2d_release_det();
 
 // tieorder.hip: pcrcg_kdforest_build over clouds that are LEVELS of per_level clouds each, level l's rows starting at row
 // level_base[l] of sup (per_level = 0: one contiguous stack, the public entry point)
@@ -179,7 +180,8 @@ struct DebugOpts {
     // atomics anywhere on the path: split-K products store their partial tiles and add them in split order (a second pass,
     // gemm_x6.hip; the fp32-MFMA kernel does not split: gemm_splitk = 1), InstanceNorm statistics come from stored partials
     // and a fixed-order finishing pass (stat_sums = 0), and the train step's scatter kernels accumulate in 64-bit fixed
-    // point (integer addition is associative; trainops.hip).  Slower (DESIGN.md has the price); the default keeps the
+    // point (integer addition is associative; trainops.hip).  The 2-D backbone's BatchNorm sums are stored per row tile
+    // and added by a fixed-order pass as well (conv2d.hip).  Slower (DESIGN.md has the price); the default keeps the
     // atomics.  Setting it overrides the two switches it implies.
     int deterministic = 0;
     int bwd_mfma = 1;               // KPConv backward's scatter on the matrix cores (k_kpconv_bwd_dx_mfma); 0: the VALU kernel

@@ -16,8 +16,12 @@
 // Statistics.  Training-mode BatchNorm2d wants per-channel sums over the rows of one statistics segment -- one image
 // (PCR-CG calls the backbone once per image) or all images (torch's batch statistics).  Row tiles never cross an image,
 // and the epilogue adds its fp64 column sums into [segment][2][N].  Products with too few tiles to fill the device are
-// split along K into partial planes; a reduction pass adds them in split order and takes the sums there.
+// split along K into partial planes; a reduction pass adds them in split order and takes the sums there.  Under
+// deterministic=1 (include/pcrcg.h) no sum is added atomically: each row tile (or reduction block) stores its column sums
+// as a partial, and a finishing pass adds the partials of a segment in a fixed order.
 #include <algorithm>
+#include <map>
+#include <mutex>
 #include <type_traits>
 #include <vector>
 
@@ -49,6 +53,8 @@ struct ConvArgs {
     float* part;             // split-K: partial planes [splits][n * mimg][N] (no statistics, no bias)
     long mtot;
     double* stats;           // [segments][2][N] column sums (sum, sum of squares); NULL: none
+    double* stat_part;       // deterministic: the sums stored per (image, row tile, wave row) [n * tiles_m * 2][2][N]
+                             // instead of added into stats (k_stats_finish adds them); NULL: atomics
     int per_image;           // segment = image (1) or one segment (0)
     const float* bias;       // [N] or NULL
     int chw;
@@ -276,17 +282,24 @@ __global__ void __launch_bounds__(CNT) k_conv2d(ConvArgs a) {
             s += __shfl_xor(s, 32, 64);
             q += __shfl_xor(q, 32, 64);
             if (half == 0 && gn < a.N) {
-                double* st = a.stats + (long)(a.per_image ? img : 0) * 2 * a.N;
-                unsafeAtomicAdd(&st[gn], s);
-                unsafeAtomicAdd(&st[a.N + gn], q);
+                if (a.stat_part) {
+                    double* sp = a.stat_part + ((long)blockIdx.y * 2 + wm) * 2 * a.N;   // blockIdx.y = image, row tile
+                    sp[gn] = s;
+                    sp[a.N + gn] = q;
+                } else {
+                    double* st = a.stats + (long)(a.per_image ? img : 0) * 2 * a.N;
+                    unsafeAtomicAdd(&st[gn], s);
+                    unsafeAtomicAdd(&st[a.N + gn], q);
+                }
             }
         }
     }
 }
 
 // split-K: y = the partial planes added in split order; statistics of the sums.  Block = (16 rows of one image, all columns).
+// stat_part (deterministic): the block's sums stored at [image][block][2][N] instead of added into stats.
 __global__ void k_splitk_reduce(const float* __restrict__ part, int splits, long mtot, int N, int mimg, float* __restrict__ y,
-                                double* __restrict__ stats, int per_image) {
+                                double* __restrict__ stats, int per_image, double* __restrict__ stat_part) {
     const int img = blockIdx.y, r0 = blockIdx.x * 16, r1 = min(mimg, r0 + 16);
     double* st = stats ? stats + (long)(per_image ? img : 0) * 2 * N : nullptr;
     for (int c = threadIdx.x; c < N; c += blockDim.x) {
@@ -299,11 +312,48 @@ __global__ void k_splitk_reduce(const float* __restrict__ part, int splits, long
             s += v;
             q += (double)v * v;
         }
-        if (st) {
+        if (stat_part) {
+            double* sp = stat_part + ((long)img * gridDim.x + blockIdx.x) * 2 * N;
+            sp[c] = s;
+            sp[N + c] = q;
+        } else if (st) {
             unsafeAtomicAdd(&st[c], s);
             unsafeAtomicAdd(&st[N + c], q);
         }
     }
+}
+
+// deterministic: stats [segments][2][N] = the stored partials [n][per_img][2][N] of each segment (one image, or all) added
+// in image, then partial order.  Grid (column blocks, segments).
+__global__ void k_stats_finish(const double* __restrict__ part, int per_img, int n, int N, int per_image, double* __restrict__ stats) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x, seg = blockIdx.y;
+    if (c >= N) return;
+    const long p0 = (long)(per_image ? seg : 0) * per_img, p1 = (long)(per_image ? seg + 1 : n) * per_img;
+    double s = 0.0, q = 0.0;
+    for (long p = p0; p < p1; ++p) {
+        s += part[p * 2 * N + c];
+        q += part[p * 2 * N + N + c];
+    }
+    stats[(long)seg * 2 * N + c] = s;
+    stats[(long)seg * 2 * N + N + c] = q;
+}
+
+// the deterministic mode's partial sums: one buffer per stream, grown on demand (a debugging mode: synchronous allocation)
+struct DetBuf { double* p = nullptr; size_t n = 0; };
+std::mutex g_det_mu;
+std::map<hipStream_t, DetBuf> g_det_bufs;
+double* det_stat_partials(hipStream_t st, size_t doubles) {
+    std::lock_guard<std::mutex> g(g_det_mu);
+    DetBuf& b = g_det_bufs[st];
+    if (b.n < doubles) {
+        if (hipStreamSynchronize(st) != hipSuccess) return nullptr;
+        if (b.p) (void)hipFree(b.p);
+        b.p = nullptr;
+        b.n = 0;
+        if (hipMalloc(&b.p, doubles * sizeof(double)) != hipSuccess) { b.p = nullptr; return nullptr; }
+        b.n = doubles;
+    }
+    return b.p;
 }
 
 // BatchNorm2d finalize, one thread per channel: (scale, shift) per segment into ss [segments][2][C].
@@ -552,6 +602,8 @@ struct Seq {
     std::vector<char*> ptr;
     int n;
     int training, per_image;           // per_image: statistics segments = images
+    size_t det_doubles;                // the deterministic mode's stored partial sums, largest product (dry pass)
+    double* det_part;                  // ... and their buffer (live pass, deterministic=1 only; NULL otherwise)
     int segs() const { return training && per_image ? n : 1; }
 };
 enum Buf { B_COL, B_STEM, B_POOL, B_XB1, B_XB2, B_XB3, B_XB4, B_PING, B_PONG, B_T1, B_T2, B_T3, B_DS, B_R, B_P, B_T, B_U, B_D,
@@ -598,16 +650,23 @@ static int conv(Seq& q, const float* w, int N, const ConvRef& c, int cin, const 
     const bool stats = q.training && !chw;
     double* st = buf<double>(q, B_STATS, (size_t)q.n * 2 * 2048);
     float* part = sp > 1 ? buf<float>(q, B_PART, (size_t)sp * q.n * mimg * N) : nullptr;
-    if (q.dry) return PCRCG_OK;
-    if (stats) PCRCG_CHECK_HIP(hipMemsetAsync(st, 0, sizeof(double) * q.segs() * 2 * N, q.st));
+    const int tiles_m = (mimg + CBM - 1) / CBM, red_blocks = (mimg + 15) / 16;
+    const int per_img = sp > 1 ? red_blocks : 2 * tiles_m;         // stored partial sums per image (deterministic)
+    if (q.dry) {
+        if (!chw) q.det_doubles = std::max(q.det_doubles, (size_t)q.n * per_img * 2 * N);
+        return PCRCG_OK;
+    }
+    double* det = stats ? q.det_part : nullptr;
+    if (stats && !det) PCRCG_CHECK_HIP(hipMemsetAsync(st, 0, sizeof(double) * q.segs() * 2 * N, q.st));
     ConvArgs a{};
     a.x = x; a.H = H; a.W = W; a.cin = cin;
     a.OH = OH; a.OW = OW; a.KH = c.k; a.KW = c.k; a.stride = c.stride; a.pad = c.pad;
     a.w = w; a.N = N; a.K = K;
-    a.y = y; a.mimg = mimg; a.tiles_m = (mimg + CBM - 1) / CBM;
+    a.y = y; a.mimg = mimg; a.tiles_m = tiles_m;
     a.k_per_split = kps;
     a.part = part; a.mtot = (long)q.n * mimg;
     a.stats = stats ? st : nullptr;
+    a.stat_part = sp > 1 ? nullptr : det;
     a.per_image = q.per_image;
     a.bias = bias; a.chw = chw;
     const dim3 grid((unsigned)((N + bnt - 1) / bnt), (unsigned)(q.n * a.tiles_m), (unsigned)sp);
@@ -615,8 +674,13 @@ static int conv(Seq& q, const float* w, int N, const ConvRef& c, int cin, const 
     else hipLaunchKernelGGL(k_conv2d<128>, grid, dim3(CNT), 0, q.st, a);
     PCRCG_CHECK_LAUNCH();
     if (sp > 1) {
-        hipLaunchKernelGGL(k_splitk_reduce, dim3((unsigned)((mimg + 15) / 16), (unsigned)q.n), dim3(256), 0, q.st, part, sp,
-                           a.mtot, N, mimg, y, stats ? st : nullptr, q.per_image);
+        hipLaunchKernelGGL(k_splitk_reduce, dim3((unsigned)red_blocks, (unsigned)q.n), dim3(256), 0, q.st, part, sp,
+                           a.mtot, N, mimg, y, stats ? st : nullptr, q.per_image, det);
+        PCRCG_CHECK_LAUNCH();
+    }
+    if (det) {
+        hipLaunchKernelGGL(k_stats_finish, dim3((unsigned)((N + 255) / 256), (unsigned)q.segs()), dim3(256), 0, q.st, det, per_img,
+                           q.n, N, q.per_image, st);
         PCRCG_CHECK_LAUNCH();
     }
     return PCRCG_OK;
@@ -780,6 +844,14 @@ static size_t plan_bytes(Seq& q, const Net& net, int h, int w, int out_ch) {
 }
 
 }  // namespace
+
+// pcrcg_debug_release(): the deterministic mode's partial sums of every stream (the caller has drained them)
+void conv2d_release_det() {
+    std::lock_guard<std::mutex> g(g_det_mu);
+    for (auto& kv : g_det_bufs)
+        if (kv.second.p) (void)hipFree(kv.second.p);
+    g_det_bufs.clear();
+}
 }  // namespace pcrcg
 
 using namespace pcrcg;
@@ -853,6 +925,13 @@ int pcrcg_res50unet_forward(const float* arena, void* const* h_state, int n_tens
     q.st = as_stream(stream);
     q.training = training;
     q.per_image = !joint_stats;
+    if (training && debug_opts().deterministic) {         // no floating-point atomics: the sums' partials, stored
+        q.det_part = det_stat_partials(q.st, q.det_doubles);
+        if (!q.det_part) {
+            set_error("pcrcg_res50unet_forward: deterministic=1 could not allocate %zu bytes of partial sums", q.det_doubles * 8);
+            return PCRCG_ELAUNCH;
+        }
+    }
     Dev d{arena, h_state, reinterpret_cast<float*>(q.ptr[B_SS]), 0};
     return sequence(q, net, d, images, h, w, out, out_ch);
 }

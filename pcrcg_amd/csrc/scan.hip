@@ -295,6 +295,7 @@ int pcrcg_debug_release(void) {
     PCRCG_CHECK_HIP(hipDeviceSynchronize());
     pcrcg::gemm_x6_release_det();
     pcrcg::trainops_release_det();
+    pcrcg::conv2d_release_det();
     return PCRCG_OK;
 }
 

@@ -96,6 +96,42 @@ def test_oracle_matches_reference_240x320():
     assert (y.mean(dim=(0, 2, 3)) - g["channel_means"]).abs().max() <= 1e-9
 
 
+def test_oracle_matches_reference_odd_and_one_pixel_high():
+    """17 x 33 (odd at every halving; layer4 holds 2 values) in training mode and 1 x 9 (every map 1 pixel high, the resize
+    at H == 1 and OH == 1) in eval mode: the shapes tests/test_resunet_edges_gpu.py runs the HIP path at."""
+    g = torch.load(os.path.join(GOLDEN, "res50unet_odd.pt"))
+    torch.manual_seed(0)
+    m = resunet.Res50UNet(128)
+    t = g["train"]
+    y, run = resunet_ref.resunet_forward(m.state_dict(), _image(t["image_seed"], t["h"], t["w"]), training=True)
+    assert list(y.shape) == t["shape"] == [1, 128, *resunet.output_size(t["h"], t["w"])] == [1, 128, 10, 18]
+    # layer4's BatchNorms see 2 values each, and the network is ill-conditioned there: moving the image by 1e-15 relative
+    # moves this output by 5.5e-8, so float64 rounding alone separates two correct runs by that much.  A wrong shape rule
+    # (a floor for a ceil, the resize's corners) is an O(1) change.
+    ref = t["out"]
+    assert (y.flatten()[::t["stride"]] - ref).abs().max() <= 1e-6 * max(1.0, ref.abs().max())
+    assert len(t["running"]) == 2 * len(run)
+    for k, v in t["running"].items():
+        name, which = k.rsplit(".", 1)
+        got = run[name][0 if which == "running_mean" else 1].float()
+        assert torch.allclose(got, v, rtol=1e-6, atol=1e-7), k
+    e = g["eval"]
+    resunet_ref.recipe(m, seed=e["recipe_seed"])
+    ye, _ = resunet_ref.resunet_forward(m.state_dict(), _image(e["image_seed"], e["h"], e["w"]), training=False)
+    assert ye.shape == e["out"].shape == (1, 128, *resunet.output_size(e["h"], e["w"])) == (1, 128, 2, 6)
+    assert (ye - e["out"]).abs().max() <= 1e-9 * max(1.0, e["out"].abs().max())
+
+
+def test_arena_bytes_follow_out_ch():
+    from pcrcg_amd import _lib
+    L = _lib.lib()
+    m = resunet.Res50UNet(128)
+    body = sum(v.numel() for k, v in m.state_dict().items() if v.dim() == 4 and not k.startswith("decoder.conv0"))
+    for oc in (1, 3, 64, 65, 200, 4096):
+        assert L.pcrcg_res50unet_arena_bytes(oc) == 4 * (body + 128 * oc + oc + 64 * 13), oc
+    assert L.pcrcg_res50unet_arena_bytes(4097) == 0
+
+
 def test_abi_rejects_bad_arguments_without_a_device():
     from pcrcg_amd import _lib
     L = _lib.lib()
@@ -131,5 +167,16 @@ def test_abi_rejects_bad_arguments_without_a_device():
     assert fwd(im=None) == EBADARG
     # one image of 8 x 8: layer4 is 1 x 1, a batch-of-one statistic of a single value (torch refuses it too)
     assert fwd(h=8, w=8) == EBADARG
+    # the statistics limit, just past it in each mode: layer4 is ceil(h / 32) x ceil(w / 32)
+    assert fwd(h=32, w=32, joint=1) == EBADARG             # joint, one image of one value
+    assert fwd(n=2, h=32, w=32, joint=0) == EBADARG        # per image: two images of one value each
+    assert fwd(n=3, h=1, w=32, joint=0) == EBADARG
+    # the size limits: h, w <= 8192, n <= 65535, n ceil(h / 2) ceil(w / 2) 160 < 2^31
+    assert L.pcrcg_res50unet_ws_bytes(1, 1, 8192) > 0 and L.pcrcg_res50unet_ws_bytes(1, 8192, 1) > 0
+    assert L.pcrcg_res50unet_ws_bytes(1, 1, 8193) == 0 and L.pcrcg_res50unet_ws_bytes(1, 8193, 1) == 0
+    assert L.pcrcg_res50unet_ws_bytes(1, 8192, 6552) > 0 and L.pcrcg_res50unet_ws_bytes(1, 8192, 6553) == 0
+    assert L.pcrcg_res50unet_ws_bytes(65535, 1, 1) > 0 and L.pcrcg_res50unet_ws_bytes(65536, 1, 1) == 0
+    assert fwd(h=1, w=8193, train=0) == EBADARG
+    assert fwd(n=65536, h=1, w=1, train=0) == EBADARG
     assert fwd(wsb=ws - 1) == -2          # PCRCG_EWORKSPACE, still before any launch
     assert "workspace" in L.pcrcg_last_error().decode()
