@@ -56,7 +56,8 @@ const char* pcrcg_last_error(void);
  *   the projection entries (pcrcg_project_depth_ws_bytes, pcrcg_project_depth, pcrcg_inject_frames with its
  *   pcrcg_image_frame, pcrcg_superglue_valid_maps), added after them, and the inlier statistics
  *   (pcrcg_inlier_stats_batch_ws_bytes, pcrcg_inlier_stats_batch), added after those, and the 2-D backbone
- *   (pcrcg_res50unet_arena_bytes, pcrcg_res50unet_pack, pcrcg_res50unet_ws_bytes, pcrcg_res50unet_forward), added after those. */
+ *   (pcrcg_res50unet_arena_bytes, pcrcg_res50unet_pack, pcrcg_res50unet_ws_bytes, pcrcg_res50unet_forward), added after those,
+ *   and the ModelNet evaluation's Chamfer distance (pcrcg_chamfer_batch_ws_bytes, pcrcg_chamfer_batch), added after those. */
 #define PCRCG_ABI_VERSION 4
 int pcrcg_abi_version(void);
 
@@ -838,6 +839,40 @@ int pcrcg_inlier_stats_batch(const float* src, const float* src_feat, int ld_src
                              int c, int B, const float* rt, const float* thr, int n_thr, int* counts, int* k_mutual,
                              float* dist, int* mutual, int* arg_s, int* arg_t, void* ws, size_t ws_bytes, void* stream);
 
+
+/* Modified Chamfer distance of many pairs: the heavy part of the ModelNet evaluation's compute_metrics
+ * (ref:lib/tester.py:280-286) for B ragged pairs in one set of launches, nothing materialised.
+ *   Layout: as pcrcg_inlier_stats_batch's -- src [n_total, 3] (points_src), ref [m_total, 3] (points_ref), raw
+ *   [r_total, 3] (points_raw, the clean cloud) f32; src_off / ref_off / raw_off [B + 1] i32 DEVICE row offsets; pred, gt
+ *   [B, 12] f32 DEVICE: pair b's predicted and ground-truth R (row-major) then t.  For pair b:
+ *     d_src[i] = min_j |pred src_i - raw_j|^2                 arg_src[i] = the j that attains it
+ *     d_ref[i] = min_j |ref_i - (pred o gt^-1) raw_j|^2       arg_ref[i] = the j that attains it
+ *     mean_src[b] = mean(d_src), mean_ref[b] = mean(d_ref), chamfer[b] = mean(d_src) + mean(d_ref).
+ *   Arithmetic: a point is moved in unfused fp32, ((r0 x + r1 y) + r2 z) + t0 (RANSAC's evaluation arithmetic; the source
+ *   points once each, the clean cloud once per query tile while it is staged).  pred o gt^-1 is composed ONCE per pair
+ *   the way the reference composes it -- R = Rp Rg^T, t = Rp (-(Rg^T tg)) + tp -- in float64 from the fp32 poses and
+ *   rounded to fp32 once.  The squared distance is (dx dx + dy dy) + dz dz in unfused fp32; the minimum over j is exact;
+ *   arg_* is the LOWEST j that attains it, local to the pair.  The means: the fp32 minima are added in float64 in a fixed
+ *   order (256 rows per workgroup by a fixed tree, the workgroups' partials in row order by a second kernel; no
+ *   floating-point atomics), divided by the row count in float64 and rounded to fp32; chamfer is the float64 sum of the two
+ *   float64 means rounded to fp32.  So pair b's three results and its per-point outputs are bit-identical whether the
+ *   pair is evaluated alone, at any position of a batch, or twice.
+ *   A row whose distances include a NaN (a NaN coordinate on either side after the transform, or infinities of one sign
+ *   in one coordinate on both) gets d = NaN (torch.min's rule) and arg = -1, and so do the rows of a pair whose
+ *   points_raw is empty.  A pair in which any of the three clouds is empty gets NaN in chamfer, mean_src and mean_ref.
+ *   NaNs stay inside their pair.  Optional (NULL: not written): mean_src, mean_ref [B]; d_src, arg_src [n_total]; d_ref,
+ *   arg_ref [m_total] (pair b's rows at src_off[b] / ref_off[b]).
+ * Workspace: pcrcg_chamfer_batch_ws_bytes(B, n_total, m_total, r_total) = 8 ((n_total >> 8) + (m_total >> 8) + 2 B + 2)
+ * bytes plus alignment padding (one float64 partial per workgroup); 0 for B outside 1..65535 or a negative total.  The
+ * entry allocates nothing and synchronises nothing.  Bad arguments (null pointers, B outside 1..65535, negative totals)
+ * are rejected with PCRCG_EBADARG and a short workspace with PCRCG_EWORKSPACE, before anything launches; the offsets live
+ * on the device and are not read by the host (the launch is sized from the totals; a pair whose offsets do not describe
+ * a range inside its stack reads as empty). */
+size_t pcrcg_chamfer_batch_ws_bytes(int B, int n_total, int m_total, int r_total);
+int pcrcg_chamfer_batch(const float* src, const int* src_off, int n_total, const float* ref, const int* ref_off, int m_total,
+                        const float* raw, const int* raw_off, int r_total, int B, const float* pred, const float* gt,
+                        float* chamfer, float* mean_src, float* mean_ref, float* d_src, int* arg_src, float* d_ref, int* arg_ref,
+                        void* ws, size_t ws_bytes, void* stream);
 
 /* PCR-CG's 2-D backbone Res50UNet(out_ch) (ref:models/resunet.py:163-188; the ResNet-50 encoder of ref:models/resnet.py and
  * the four up-projections of the decoder), forward only (the reference detaches it), enqueued by ONE call for n images.

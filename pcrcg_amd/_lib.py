@@ -140,6 +140,11 @@ SIGNATURES = {
     "pcrcg_inlier_stats_batch": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p,
                                          c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                                          c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    # ModelNet evaluation (pcrcg_amd/modelnet.py)
+    "pcrcg_chamfer_batch_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "pcrcg_chamfer_batch": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int,
+                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                    c_void_p, c_size_t, c_void_p]),
     # PCR-CG's 2-D backbone (pcrcg_amd/resunet.py)
     "pcrcg_res50unet_arena_bytes": (c_size_t, [c_int]),
     "pcrcg_res50unet_pack": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),

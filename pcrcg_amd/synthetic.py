@@ -204,3 +204,35 @@ def frame_inputs(src, tgt, seed=0, img_num=2, h=120, w=160, channels=128):
             for k, v in superglue_like(rng, h=h, w=w).items():
                 out[f"sg{i}_{k}"] = v
     return out
+
+
+def modelnet_pairs(B, seed, n=1024, keep=0.7, n_raw=2048):
+    """B ModelNet-shaped pairs (ref:datasets/modelnet.py through its transforms: a clean cloud, two resampled partial
+    views of it, the source view moved away by a rigid transform) -> list of dicts of float32 arrays:
+      points_raw [n_raw, 3]  the clean cloud: a torus with a wavy tube in the unit cube, no symmetry to speak of (the
+                             surface of scripts/make_golden_modelnet.py::modelnet_pair), in the reference frame;
+      points_ref [round(n keep), 3]  n of its points, jittered, cropped by a random half-space to `keep`;
+      points_src [round(n keep), 3]  the same with another jitter and half-space, moved by transform_gt^-1;
+      transform_gt [3, 4]    source -> reference: a rotation of up to 45 degrees about a random axis and a translation
+                             of up to 0.5 per axis (the range of the reference's RandomTransformSE3_euler).
+    So transform_gt * points_src lies on points_raw, as compute_metrics assumes."""
+    out = []
+    for b in range(B):
+        rng = np.random.RandomState([seed, b])
+        u, v = rng.rand(n_raw) * 2 * np.pi, rng.rand(n_raw) * 2 * np.pi
+        r_major, r_minor = 0.6, 0.25 + 0.08 * np.sin(3 * u)
+        raw = np.stack([(r_major + r_minor * np.cos(v)) * np.cos(u), (r_major + r_minor * np.cos(v)) * np.sin(u),
+                        r_minor * np.sin(v)], 1)
+        views = []
+        for _ in range(2):
+            p = raw[rng.permutation(n_raw)[:n]] if n <= n_raw else raw[rng.randint(0, n_raw, n)]
+            p = p + np.clip(rng.randn(n, 3) * 0.01, -0.05, 0.05)
+            d = rng.randn(3)
+            d /= np.linalg.norm(d)
+            views.append(p[np.argsort(p @ d)[:int(round(n * keep))]])
+        pose = _pose(rng, angle=np.pi / 4, shift=0.5)
+        rot, t = pose[:3, :3], pose[:3, 3]
+        src = (views[0] - t) @ rot                      # rot^T (p - t), row by row
+        out.append({"points_src": src.astype(np.float32), "points_ref": views[1].astype(np.float32),
+                    "points_raw": raw.astype(np.float32), "transform_gt": pose[:3].astype(np.float32)})
+    return out

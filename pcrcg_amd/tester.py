@@ -12,7 +12,9 @@ registration back end.
                        both sides, then RANSAC on the device (pcrcg_amd/registration.py; open3d is not needed).
   * `register_records` -- the same loop over many records with ONE batched RANSAC (registration.register_batch).
   * `evaluate_records` -- the same poses and, from the same samples, the inlier ratios against the records' ground
-                       truth (registration.inlier_ratio_batch): everything the 3DMatch table needs."""
+                       truth (registration.inlier_ratio_batch): everything the 3DMatch table needs.
+  * `evaluate_modelnet_records` -- ModelnetTester.test (ref:lib/tester.py:343-436): the same sampling at 450 points, ONE
+                       batched RANSAC at 0.02, ONE compute_metrics over all pairs (pcrcg_amd/modelnet.py) and its summary."""
 import numpy as np
 import torch
 
@@ -109,3 +111,39 @@ def evaluate_records(records, n_points=5000, distance_threshold=0.05, ransac_n=3
     inliers = inlier_ratio_batch(src_pcds, tgt_pcds, src_feats, tgt_feats, [r["rot"] for r in records],
                                  [r["trans"] for r in records], inlier_thresholds)
     return list(res.matrices), inliers
+
+
+def evaluate_modelnet_records(records, n_points=450, distance_threshold=0.02, ransac_n=3, seeds=0):
+    """-> (poses, metrics, summary): ModelnetTester.test (ref:lib/tester.py:343-436) over `records`.  A ModelNet record is
+    `test_record`'s dict plus 'sample': the dict of 'transform_gt' [3|4, 4] and 'points_src', 'points_ref', 'points_raw'
+    [n, >= 3] (a leading batch dimension of one, as the reference's loader leaves it, is accepted).
+
+    poses: register_records' (list of float64 numpy [4,4]; the host generator is consumed exactly as register_records
+    consumes it, so under the same np.random state they are equal bit for bit); metrics: modelnet.compute_metrics of the
+    poses (rounded to fp32 first, as the reference rounds them) over all pairs in one call; summary: modelnet.summarize_metrics
+    of them plus 'rotation_mean' / 'rotation_max', the reference's "rotation range in data" (the ground-truth rotation
+    angle in degrees)."""
+    from . import modelnet
+    from .registration import register_batch
+    if len(records) == 0:
+        raise ValueError("evaluate_modelnet_records: no records")
+    src_pcds, tgt_pcds, src_feats, tgt_feats = _sample_records(records, n_points)
+    res = register_batch(src_pcds, tgt_pcds, src_feats, tgt_feats, distance_threshold, ransac_n, seeds=seeds)
+    poses = list(res.matrices)
+
+    def one(x, dims):
+        x = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.asarray(x))
+        return x[0] if x.dim() == dims + 1 and x.shape[0] == 1 else x
+
+    samples = [r["sample"] for r in records]
+    gt = np.stack([one(s["transform_gt"], 2).detach().cpu().numpy()[:3].astype(np.float64) for s in samples])
+    data = {"transform_gt": gt}
+    for k in ("points_src", "points_ref", "points_raw"):
+        data[k] = [one(s[k], 2) for s in samples]
+    pred = torch.from_numpy(np.stack(poses)).float()          # ref:lib/tester.py:414
+    metrics = modelnet.compute_metrics(data, pred)
+    summary = modelnet.summarize_metrics(metrics)
+    trace = gt[:, 0, 0] + gt[:, 1, 1] + gt[:, 2, 2]
+    rotation = np.abs(np.degrees(np.arccos(np.clip(0.5 * (trace - 1.0), -1.0, 1.0))))
+    summary["rotation_mean"], summary["rotation_max"] = float(np.mean(rotation)), float(np.max(rotation))
+    return poses, metrics, summary
