@@ -5,6 +5,7 @@
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
+#include <map>
 #include <mutex>
 
 #include "pcrcg.h"
@@ -51,10 +52,23 @@ int instnorm_apply_pack(const float* x, int n, int c, int ldx, const float* stat
 // kpconv.hip: where the support records live inside a pcrcg_kpconv_ws_bytes(ns) workspace
 float4* kpconv_pk_ptr(void* ws, size_t ws_bytes, int ns);
 
-// the deterministic debug mode's scratch (gemm_x6.hip, trainops.hip, conv2d.hip): freed by pcrcg_debug_release()
-void gemm_x6_release_det();
+// The deterministic debug mode's scratch: one device buffer per stream, kept until pcrcg_debug_release() (scan.hip) frees
+// those of every instance.  An instance is a namespace-scope object of the file that uses it (gemm_x6.hip: the split-K
+// partial tiles, conv2d.hip: the BatchNorm partial sums).  trainops.hip keeps its own pair of buffers (one of them must be
+// zeroed whenever it grows): trainops_release_det().
+class StreamScratch {
+public:
+    StreamScratch();
+    // >= bytes of device memory for work enqueued on st.  Too small: the stream is drained, the old buffer freed and
+    // bytes + slack allocated (a debugging mode: synchronous allocation).  NULL: no memory / the stream failed.
+    void* get(hipStream_t st, size_t bytes, size_t slack = 0);
+    void release();
+private:
+    struct Buf { void* p = nullptr; size_t bytes = 0; };
+    std::mutex mu_;
+    std::map<hipStream_t, Buf> bufs_;
+};
 void trainops_release_det();
-void conv2d_release_det();
 
 // tieorder.hip: pcrcg_kdforest_build over clouds that are LEVELS of per_level clouds each, level l's rows starting at row
 // level_base[l] of sup (per_level = 0: one contiguous stack, the public entry point)
@@ -69,47 +83,10 @@ int radius_query_pass(const float* q, int nq, const int* qlen, int ns, const int
                       int* out_tie_rows, int* out_tie_count, hipStream_t st, int pass);
 
 // radius.hip: the cell-cooperative search over a query grid (pass 0: + the per-query second pass, 1: the cell kernel only)
-// gemm_x6.hip: the calling host thread enqueues beside other streams (see x6_plan_for; C ABI: pcrcg_thread_shares_gpu)
-bool gemm_x6_shared();
-void gemm_x6_set_shared(int on);
 int radius_cells_pass(const void* qgrid, const float* q, int nq, const int* qlen, const void* sgrid, int ns, const int* slen,
                       int nb, int group, float radius, int cols, int64_t* out_idx, int* out_count, int* out_max_count,
                       int* status, int* out_tie_rows, int* out_tie_count, hipStream_t st, int pass);
 constexpr int kRadiusRedoStatus = 4;   // status bit: rows were handed to the per-query second pass (cleared by that pass)
-
-// gemm_x6.hip: optional extras of a C = A * B^T product (the decoder's fused upsample + concat, runner.hip)
-struct GemmExtra {
-    const long long* a_idx = nullptr;   // != NULL: output row r reads A row a_idx[r * a_idx_ld] (first column of a table)
-    int a_idx_ld = 0, a_ns = 0;         // an index outside [0, a_ns) reads a_zero instead (the shadow row)
-    const float* a_zero = nullptr;      // >= k zero floats
-    bool accumulate = false;            // C += product (fp32 atomics) instead of C = product
-    const double* a_sums = nullptr;     // != NULL: A is normalised on load, a' = lrelu((a - mean_k) * rstd_k, a_slope), with
-    double a_count = 0.0;               // the statistics of its columns given as fp64 sums [2][k] over a_count rows
-    float a_eps = 1e-5f, a_slope = 1.0f;
-    int grad_operand = 0;               // train step: 1 = A holds gradients, 2 = B does (the fp16 form scales that operand by 2^16)
-};
-
-// gemm_x6.hip: a SECOND product C1 = f(A1) * B^T that shares B (and the bias, the leading dimensions, n, k and every
-// GemmExtra setting except the per-product pointers below) with the first and runs in the SAME launch: the same layer
-// of a second fragment pair (runner.hip, pcrcg_kpfcnn_forward_group).  Small products fill the chip twice as well
-// and every product costs one launch per two pairs.
-struct GemmPair {
-    const float* a = nullptr;
-    float* c = nullptr;
-    int m = 0;
-    const float* row_scale = nullptr;
-    void* colstats = nullptr;           // statistics of C1, same form and size as the first product's
-    int* h_chunks = nullptr;
-    bool c_zeroed = false;
-    const long long* a_idx = nullptr;   // gather form: its own table and source row count (A1 = its source matrix)
-    int a_ns = 0;
-    const double* a_sums = nullptr;     // normalise-on-load form: its own column sums and row count
-    double a_count = 0.0;
-};
-struct GemmGroup {                      // up to 3 further products in the launch (4 fragment pairs per call)
-    int n = 0;
-    GemmPair p[3];
-};
 
 // kpconv.hip: row-positive flags + packed (x, y, z, flag) support records into a pcrcg_kpconv_ws_bytes(ns) workspace
 // (x_bf16 != NULL: also the bf16 round-to-nearest-even copy of x, [ns, cin])

@@ -20,8 +20,6 @@
 // deterministic=1 (include/pcrcg.h) no sum is added atomically: each row tile (or reduction block) stores its column sums
 // as a partial, and a finishing pass adds the partials of a segment in a fixed order.
 #include <algorithm>
-#include <map>
-#include <mutex>
 #include <type_traits>
 #include <vector>
 
@@ -338,23 +336,8 @@ __global__ void k_stats_finish(const double* __restrict__ part, int per_img, int
     stats[(long)seg * 2 * N + N + c] = q;
 }
 
-// the deterministic mode's partial sums: one buffer per stream, grown on demand (a debugging mode: synchronous allocation)
-struct DetBuf { double* p = nullptr; size_t n = 0; };
-std::mutex g_det_mu;
-std::map<hipStream_t, DetBuf> g_det_bufs;
-double* det_stat_partials(hipStream_t st, size_t doubles) {
-    std::lock_guard<std::mutex> g(g_det_mu);
-    DetBuf& b = g_det_bufs[st];
-    if (b.n < doubles) {
-        if (hipStreamSynchronize(st) != hipSuccess) return nullptr;
-        if (b.p) (void)hipFree(b.p);
-        b.p = nullptr;
-        b.n = 0;
-        if (hipMalloc(&b.p, doubles * sizeof(double)) != hipSuccess) { b.p = nullptr; return nullptr; }
-        b.n = doubles;
-    }
-    return b.p;
-}
+// the deterministic mode's partial sums (exact size: no slack)
+StreamScratch g_det_stat_partials;
 
 // BatchNorm2d finalize, one thread per channel: (scale, shift) per segment into ss [segments][2][C].
 //   training: batch mean, biased variance (eps) for the normalisation; running_mean / running_var updated with momentum and
@@ -845,13 +828,6 @@ static size_t plan_bytes(Seq& q, const Net& net, int h, int w, int out_ch) {
 
 }  // namespace
 
-// pcrcg_debug_release(): the deterministic mode's partial sums of every stream (the caller has drained them)
-void conv2d_release_det() {
-    std::lock_guard<std::mutex> g(g_det_mu);
-    for (auto& kv : g_det_bufs)
-        if (kv.second.p) (void)hipFree(kv.second.p);
-    g_det_bufs.clear();
-}
 }  // namespace pcrcg
 
 using namespace pcrcg;
@@ -926,7 +902,7 @@ int pcrcg_res50unet_forward(const float* arena, void* const* h_state, int n_tens
     q.training = training;
     q.per_image = !joint_stats;
     if (training && debug_opts().deterministic) {         // no floating-point atomics: the sums' partials, stored
-        q.det_part = det_stat_partials(q.st, q.det_doubles);
+        q.det_part = static_cast<double*>(g_det_stat_partials.get(q.st, q.det_doubles * sizeof(double)));
         if (!q.det_part) {
             set_error("pcrcg_res50unet_forward: deterministic=1 could not allocate %zu bytes of partial sums", q.det_doubles * 8);
             return PCRCG_ELAUNCH;

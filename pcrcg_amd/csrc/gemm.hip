@@ -26,7 +26,7 @@
 
 #include <atomic>
 
-#include "common.h"
+#include "gemm.h"
 #include "pcrcg_train.h"
 
 namespace pcrcg {
@@ -313,49 +313,41 @@ __global__ void __launch_bounds__(256) k_gemm_f32(const float* __restrict__ A, i
     }
 }
 
-template <int BM, int BN, int WAVES_M, int WAVES_N, bool TRANS_A, bool TRANS_B, int BK>
-int launch_one(dim3 grid, hipStream_t st, const float* a, int lda, const float* b, int ldb, float* c, int ldc, int m,
-               int n, int k, const float* row_scale, const float* bias, int k_per_split, int vec_a, int vec_b,
-               int atomic_out, double* colp, int colp_chunks) {
+// k_gemm_f32's arguments, in its order
+struct F32Args {
+    const float* a; int lda;
+    const float* b; int ldb;
+    float* c; int ldc;
+    int m, n, k;
+    const float* row_scale; const float* bias;
+    int k_per_split, vec_a, vec_b, atomic_out;
+    double* colp; int colp_chunks;
+};
+
+constexpr int BK = 32;   // a 64-deep k-step (2 blocks/CU) measured 12 % slower on the path's shapes
+
+template <int BM, int BN, int WAVES_M, int WAVES_N, bool TRANS_A, bool TRANS_B>
+int launch_f32(const F32Args& p, dim3 grid, hipStream_t st) {
     constexpr size_t lds = 2 * sizeof(float) * stage_floats<BM, BN, TRANS_A, TRANS_B, BK>();
     auto kern = k_gemm_f32<BM, BN, WAVES_M, WAVES_N, TRANS_A, TRANS_B, BK>;
     PCRCG_GRANT_LDS(kern);   // > 64 KiB of dynamic LDS must be requested once per kernel
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, a, lda, b, ldb, c, ldc, m, n, k, row_scale, bias, k_per_split,
-                       vec_a, vec_b, atomic_out, colp, colp_chunks);
+    hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, p.a, p.lda, p.b, p.ldb, p.c, p.ldc, p.m, p.n, p.k, p.row_scale, p.bias,
+                       p.k_per_split, p.vec_a, p.vec_b, p.atomic_out, p.colp, p.colp_chunks);
     PCRCG_CHECK_LAUNCH();
     return PCRCG_OK;
 }
-
-template <int BM, int BN, int WAVES_M, int WAVES_N, int BK>
-int launch(bool trans_b, dim3 grid, hipStream_t st, const float* a, int lda, const float* b, int ldb, float* c,
-           int ldc, int m, int n, int k, const float* row_scale, const float* bias, int k_per_split, int vec_a,
-           int vec_b, int atomic_out, double* colp, int colp_chunks) {
-    if (trans_b)
-        return launch_one<BM, BN, WAVES_M, WAVES_N, false, true, BK>(grid, st, a, lda, b, ldb, c, ldc, m, n, k, row_scale, bias,
-                                                          k_per_split, vec_a, vec_b, atomic_out, colp, colp_chunks);
-    return launch_one<BM, BN, WAVES_M, WAVES_N, false, false, BK>(grid, st, a, lda, b, ldb, c, ldc, m, n, k, row_scale, bias,
-                                                       k_per_split, vec_a, vec_b, atomic_out, colp, colp_chunks);
+template <int BM, int BN, int WAVES_M, int WAVES_N>
+int launch_f32_tile(bool trans_b, const F32Args& p, dim3 grid, hipStream_t st) {
+    return trans_b ? launch_f32<BM, BN, WAVES_M, WAVES_N, false, true>(p, grid, st)
+                   : launch_f32<BM, BN, WAVES_M, WAVES_N, false, false>(p, grid, st);
 }
 
-}  // namespace
-}  // namespace pcrcg
-
-namespace pcrcg {
-int gemm_x6_dispatch(const float* a, int lda, const float* b, int ldb, float* c, int ldc, int m, int n, int k,
-                     const float* row_scale, const float* bias, void* colstats, size_t colstats_bytes, int* h_chunks,
-                     hipStream_t st, bool a_bf16, bool c_zeroed, int a_kmajor = 0, int b_kmajor = 0,
-                     bool colstats_sums = false, const GemmExtra* ex = nullptr, const GemmGroup* grp = nullptr);   // gemm_x6.hip
-int gemm_x6_splits(int m, int n, int k, long m_total = 0);
-}
-
-using namespace pcrcg;
-
-// Arithmetic of the C = A * B^T products: 0 = v_mfma_f32_32x32x2_f32 (fp32 operands), 1 = six
-// v_mfma_f32_32x32x16_bf16 on the exact three-term bf16 split of the fp32 operands (gemm_x6.hip; fp32-class
-// accuracy at 2.7x the matrix rate).  Default 1; PCRCG_GEMM_MODE / pcrcg_gemm_set_mode override.
+// Arithmetic of the products: 0 = v_mfma_f32_32x32x2_f32 (fp32 operands), 1 = six v_mfma_f32_32x32x16_bf16 on the exact
+// three-term bf16 split of the fp32 operands (gemm_x6.hip; fp32-class accuracy at 2.7x the matrix rate).  Default 1;
+// PCRCG_GEMM_MODE / pcrcg_gemm_set_mode override.
 // (One process-wide atomic word: read by every host thread that enqueues products, written by pcrcg_gemm_set_mode.)
-static std::atomic<int> g_gemm_mode{-1};
-static int gemm_mode() {
+std::atomic<int> g_gemm_mode{-1};
+int gemm_mode() {
     int mode = g_gemm_mode.load(std::memory_order_relaxed);
     if (mode < 0) {
         const char* e = getenv("PCRCG_GEMM_MODE");
@@ -365,117 +357,135 @@ static int gemm_mode() {
     }
     return mode;
 }
-extern "C" void pcrcg_gemm_set_mode(int mode) { g_gemm_mode.store(mode != 0, std::memory_order_relaxed); }
-extern "C" void pcrcg_thread_shares_gpu(int on) { gemm_x6_set_shared(on); }
-namespace pcrcg { int gemm_x6_redo_counts(unsigned long long* out, int reset); }
-extern "C" int pcrcg_gemm_redo_counts(unsigned long long* out2, int reset) { return gemm_x6_redo_counts(out2, reset); }
-extern "C" int pcrcg_gemm_get_mode(void) { return gemm_mode(); }
 
-static int gemm_dispatch(const float* a, int lda, int trans_a, const float* b, int ldb, int trans_b, float* c, int ldc,
-                         int m, int n, int k, const float* row_scale, const float* bias, void* colstats,
-                         size_t colstats_bytes, int* h_chunks, void* stream, bool c_zeroed = false,
-                         bool colstats_sums = false);
-
-namespace pcrcg {
-// For the network runner (runner.hip): does a C = A * B^T product of this shape accumulate split-K partial sums into C
-// (so that a C taken from the runner's pre-zeroed arena saves the product's own memset)?  Only the default arithmetic.
-// (m: rows of the largest product of a grouped launch, m_total: of all of them -- the plan looks at both)
-bool gemm_bt_accumulates(int m, int n, int k, long m_total) { return gemm_mode() == 1 && gemm_x6_splits(m, n, k, m_total) > 1; }
-// pcrcg_gemm_f32_colstats (trans_b = 1) / pcrcg_gemm_bf16a_f32_colstats with the promise that C is all zeros.
-// colstats_sums: `colstats` is a ZEROED [2][n] fp64 accumulator; when the product writes every element once, its epilogue
-// adds the column sums / sums of squares there with atomics and reports *h_chunks = -1 (else 0: nothing was added).
-bool gemm_colstats_sums_ok() { return gemm_mode() == 1; }
-// C (+)= A[gathered rows] * B^T for k-contiguous fp32 operands (GemmExtra, common.h); split-bf16 arithmetic only
-bool gemm_extra_ok() { return gemm_mode() == 1; }
-int gemm_bt_extra(const float* a, int lda, const float* b, int ldb, float* c, int ldc, int m, int n, int k, hipStream_t st,
-                  bool c_zeroed, const GemmExtra& ex, const float* bias, void* colstats, size_t colstats_bytes, int* h_chunks,
-                  bool colstats_sums) {
-    if (h_chunks) *h_chunks = 0;
-    PCRCG_CHECK_ARG(m >= 0 && n >= 0 && k >= 1 && lda >= k && ldb >= k && ldc >= n);
-    if (m == 0 || n == 0) return PCRCG_OK;
-    PCRCG_CHECK_ARG(a && b && c && gemm_mode() == 1);
-    return gemm_x6_dispatch(a, lda, b, ldb, c, ldc, m, n, k, nullptr, bias, colstats, colstats_bytes, h_chunks, st, false,
-                            c_zeroed, 0, 0, colstats_sums, &ex);
-}
-// The two forms above with an optional SECOND product in the same launch (GemmPair, common.h); pair == NULL: as above.
-bool gemm_pair_ok() { return gemm_mode() == 1; }
-int gemm_bt_colstats_pair(const float* a, int lda, const float* b, int ldb, float* c, int ldc, int m, int n, int k,
-                          const float* row_scale, const float* bias, void* colstats, size_t colstats_bytes, int* h_chunks,
-                          hipStream_t st, bool c_zeroed, bool colstats_sums, const GemmGroup* pair) {
-    if (!pair || pair->n == 0)
-        return gemm_dispatch(a, lda, 0, b, ldb, 1, c, ldc, m, n, k, row_scale, bias, colstats, colstats_bytes, h_chunks, st,
-                             c_zeroed, colstats_sums);
-    if (h_chunks) *h_chunks = 0;
-    PCRCG_CHECK_ARG(m >= 1 && n >= 1 && k >= 1 && lda >= k && ldb >= k && ldc >= n);
-    PCRCG_CHECK_ARG(a && b && c && gemm_mode() == 1);
-    return gemm_x6_dispatch(a, lda, b, ldb, c, ldc, m, n, k, row_scale, bias, colstats, colstats_bytes, h_chunks, st, false,
-                            c_zeroed, 0, 0, colstats_sums, nullptr, pair);
-}
-int gemm_bt_extra_pair(const float* a, int lda, const float* b, int ldb, float* c, int ldc, int m, int n, int k, hipStream_t st,
-                       bool c_zeroed, const GemmExtra& ex, const float* bias, void* colstats, size_t colstats_bytes,
-                       int* h_chunks, bool colstats_sums, const GemmGroup* pair) {
-    if (h_chunks) *h_chunks = 0;
-    PCRCG_CHECK_ARG(m >= 0 && n >= 0 && k >= 1 && lda >= k && ldb >= k && ldc >= n);
-    if (m == 0 || n == 0) return PCRCG_OK;
-    PCRCG_CHECK_ARG(a && b && c && gemm_mode() == 1);
-    return gemm_x6_dispatch(a, lda, b, ldb, c, ldc, m, n, k, nullptr, bias, colstats, colstats_bytes, h_chunks, st, false,
-                            c_zeroed, 0, 0, colstats_sums, &ex, pair);
-}
-// C (+)= (op(A) * op(B)) * row_scale[m] + bias[n] for the training runner (train_runner.hip): op = identity or transpose
-// as in pcrcg_gemm_f32_ex; accumulate adds the product onto C with fp32 atomics (gradients of tensors with several
-// consumers, parameter gradients of shared weights).  Split-bf16 arithmetic only.
-int gemm_general(const float* a, int lda, int trans_a, const float* b, int ldb, int trans_b, float* c, int ldc, int m, int n,
-                 int k, const float* row_scale, const float* bias, bool accumulate, hipStream_t st, int grad_operand) {
-    PCRCG_CHECK_ARG(m >= 0 && n >= 0 && k >= 0);
-    if (m == 0 || n == 0 || k == 0) return PCRCG_OK;
-    PCRCG_CHECK_ARG(a && b && c && !(trans_a && trans_b));
-    PCRCG_CHECK_ARG((trans_a ? lda >= m : lda >= k) && ldc >= n && (trans_b ? ldb >= k : ldb >= n));
-    if (gemm_mode() != 1) {
-        set_error("gemm_general: the training runner needs the split-bf16 arithmetic (pcrcg_gemm_set_mode(1))");
-        return PCRCG_EBADARG;
+// the fp32-MFMA path of gemm_run: a checked call without extras or group
+int gemm_f32_dispatch(const GemmCall& g) {
+    const int m = g.m, n = g.n, k = g.k;
+    const bool trans_a = g.a_form == GemmA::kmajor_f32, trans_b = g.b_form == GemmB::nk;
+    F32Args p{static_cast<const float*>(g.a), g.lda, g.b, g.ldb, g.c, g.ldc, m, n, k, g.row_scale, g.bias, 0, 0, 0, 0, nullptr, 0};
+    p.vec_a = (g.lda % 4 == 0) && ((reinterpret_cast<uintptr_t>(g.a) & 15) == 0);
+    p.vec_b = (g.ldb % 4 == 0) && ((reinterpret_cast<uintptr_t>(g.b) & 15) == 0);
+    // Tile / split selection (sweep in scripts/gemm_tune.py on the path's shapes): these GEMMs are skinny
+    // (N = 64..2048, K up to 7680) and each block streams its own slice of A from HBM, so many small
+    // blocks beat few large ones: 128x128 only when that still yields >= 1024 blocks, otherwise 64x64
+    // (128x64 for N <= 64 with a long M), with K split until ~1024 blocks are in flight.
+    struct Tile { int bm, bn; };
+    static const Tile tiles[4] = {{128, 128}, {128, 64}, {64, 128}, {64, 64}};
+    auto ntiles = [&](int t) {
+        return (long)((m + tiles[t].bm - 1) / tiles[t].bm) * ((n + tiles[t].bn - 1) / tiles[t].bn);
+    };
+    int pick = debug_opts().gemm_tile;                                       // tuning aid (-1: automatic)
+    if (pick < 0 || pick > 3) pick = (n > 64 && ntiles(0) >= 1024) ? 0 : 3;
+    if (trans_a) pick = 3;                                                   // only the 64x64 tile is built for A^T
+    const int BM = tiles[pick].bm, BN = tiles[pick].bn;
+    const int gx = (n + BN - 1) / BN, gy = (m + BM - 1) / BM;
+    int splits = 1;
+    const int ktiles = (k + BK - 1) / BK;
+    const int split_target = debug_opts().gemm_split_target;
+    const int max_splits = trans_a ? 256 : 32;   // A^T products reduce over the points: few tiles, very long K
+    while ((long)gx * gy * splits < split_target && k / (2 * splits) >= 192 && splits < max_splits) splits *= 2;
+    if (debug_opts().gemm_splitk > 0) splits = debug_opts().gemm_splitk;     // tuning aid
+    p.k_per_split = ((ktiles + splits - 1) / splits) * BK;
+    if (p.k_per_split < BK) p.k_per_split = BK;
+    splits = k > 0 ? (k + p.k_per_split - 1) / p.k_per_split : 1;
+    if (splits < 1) splits = 1;
+    p.atomic_out = splits > 1;
+    if (p.atomic_out) {
+        if (g.ldc == n) PCRCG_CHECK_HIP(hipMemsetAsync(g.c, 0, (size_t)m * n * sizeof(float), g.st));
+        else PCRCG_CHECK_HIP(hipMemset2DAsync(g.c, (size_t)g.ldc * sizeof(float), 0, (size_t)n * sizeof(float), m, g.st));
     }
-    GemmExtra ex;
-    ex.accumulate = accumulate;
-    ex.grad_operand = grad_operand;
-    return gemm_x6_dispatch(a, lda, b, ldb, c, ldc, m, n, k, row_scale, bias, nullptr, 0, nullptr, st, false, false,
-                            trans_a ? 1 : 0, trans_b ? 0 : 1, false, (accumulate || grad_operand) ? &ex : nullptr);
+    const dim3 grid(gx, gy, splits);
+    // column statistics ride along only when every output element is written exactly once, and only as partials
+    const bool want_partials = g.colstats && g.h_chunks && !g.colstats_sums;
+    if (debug_opts().gemm_log != 0)   // tuning aid
+        fprintf(stderr, "pcrcg_gemm m=%d n=%d k=%d lda=%d ldb=%d ldc=%d tb=%d grid=%dx%dx%d rs=%d bias=%d stats=%d\n", m, n, k,
+                g.lda, g.ldb, g.ldc, (int)trans_b, gx, gy, splits, g.row_scale != nullptr, g.bias != nullptr,
+                g.colstats != nullptr && !g.colstats_sums);
+    if (want_partials && !p.atomic_out) {
+        const int chunks = gy * (pick == 1 ? 4 : 2);   // WAVES_M of the chosen tile
+        if (carve_bytes(2 * (size_t)n * chunks, sizeof(double)) <= g.colstats_bytes) {
+            p.colp = static_cast<double*>(g.colstats);
+            p.colp_chunks = *g.h_chunks = chunks;
+        }
+    }
+    if (trans_a)
+        return trans_b ? launch_f32<64, 64, 2, 2, true, true>(p, grid, g.st) : launch_f32<64, 64, 2, 2, true, false>(p, grid, g.st);
+    if (pick == 0) return launch_f32_tile<128, 128, 2, 2>(trans_b, p, grid, g.st);
+    if (pick == 1) return launch_f32_tile<128, 64, 4, 1>(trans_b, p, grid, g.st);
+    if (pick == 2) return launch_f32_tile<64, 128, 2, 2>(trans_b, p, grid, g.st);
+    return launch_f32_tile<64, 64, 2, 2>(trans_b, p, grid, g.st);
 }
-int gemm_bt_colstats(const float* a, int lda, const float* b, int ldb, float* c, int ldc, int m, int n, int k,
-                     const float* row_scale, const float* bias, void* colstats, size_t colstats_bytes, int* h_chunks,
-                     hipStream_t st, bool c_zeroed, bool colstats_sums) {
-    return gemm_dispatch(a, lda, 0, b, ldb, 1, c, ldc, m, n, k, row_scale, bias, colstats, colstats_bytes, h_chunks, st,
-                         c_zeroed, colstats_sums);
+
+}  // namespace
+
+bool gemm_split_terms_on() { return gemm_mode() == 1; }
+
+// (both this answer and the product's own plan come from gemm_x6.hip's x6_plan: see gemm_x6_splits)
+bool gemm_bt_accumulates(int m, int n, int k, long m_total) { return gemm_split_terms_on() && gemm_x6_splits(m, n, k, m_total) > 1; }
+
+int gemm_run(const GemmCall& g) {
+    if (g.h_chunks) *g.h_chunks = 0;
+    const bool trans_a = g.a_form == GemmA::kmajor_f32, b_kn = g.b_form == GemmB::kn, bf16 = g.a_form == GemmA::row_bf16;
+    const bool grouped = g.grp && g.grp->n != 0;
+    const bool x6_form = g.ex || grouped || bf16;      // what only gemm_x6.hip implements
+    PCRCG_CHECK_ARG(g.m >= 0 && g.n >= 0 && g.k >= 0);
+    const bool ld_ok = (trans_a ? g.lda >= g.m : g.lda >= g.k) && (b_kn ? g.ldb >= g.n : g.ldb >= g.k) && g.ldc >= g.n;
+    // (those forms are checked in full before an empty product returns; a group's first product is never empty)
+    if (x6_form) PCRCG_CHECK_ARG(g.k >= 1 && ld_ok && !(trans_a && !b_kn));
+    if (grouped) PCRCG_CHECK_ARG(g.m >= 1 && g.n >= 1);
+    if (bf16) PCRCG_CHECK_ARG(g.k % 32 == 0 && g.lda % 8 == 0);
+    if (g.m == 0 || g.n == 0) return PCRCG_OK;
+    PCRCG_CHECK_ARG(g.a && g.b && g.c);
+    PCRCG_CHECK_ARG(ld_ok);
+    if (bf16) {
+        // the bf16-A kernel has no guarded A loads: every k-step must take the vector path, which also needs B aligned
+        PCRCG_CHECK_ARG((reinterpret_cast<uintptr_t>(g.a) & 15) == 0 && g.ldb % 4 == 0 && (reinterpret_cast<uintptr_t>(g.b) & 15) == 0);
+        return gemm_x6_dispatch(g);
+    }
+    if (x6_form) PCRCG_CHECK_ARG(gemm_split_terms_on());
+    // split-term arithmetic for A * B^T (the forward), A * B (dX = dY * W) and A^T * B (dW = X^T * dY); A^T * B^T stays fp32
+    if (gemm_split_terms_on() && !(trans_a && !b_kn)) return gemm_x6_dispatch(g);
+    return gemm_f32_dispatch(g);
 }
-int gemm_bf16a_bt_colstats(const void* a_bf16, int lda, const float* b, int ldb, float* c, int ldc, int m, int n, int k,
-                           const float* row_scale, const float* bias, void* colstats, size_t colstats_bytes,
-                           int* h_chunks, hipStream_t st, bool c_zeroed, bool colstats_sums) {
-    if (h_chunks) *h_chunks = 0;
-    PCRCG_CHECK_ARG(m >= 0 && n >= 0 && k >= 32 && k % 32 == 0 && lda >= k && lda % 8 == 0 && ldb >= k && ldc >= n);
-    if (m == 0 || n == 0) return PCRCG_OK;
-    PCRCG_CHECK_ARG(a_bf16 && b && c && (reinterpret_cast<uintptr_t>(a_bf16) & 15) == 0);
-    // the bf16-A kernel has no guarded A loads: every k-step must take the vector path, which also needs B aligned
-    PCRCG_CHECK_ARG(ldb % 4 == 0 && (reinterpret_cast<uintptr_t>(b) & 15) == 0);
-    return gemm_x6_dispatch(static_cast<const float*>(a_bf16), lda, b, ldb, c, ldc, m, n, k, row_scale, bias, colstats,
-                            colstats_bytes, h_chunks, st, true, c_zeroed, 0, 0, colstats_sums);
-}
+
 }  // namespace pcrcg
+
+using namespace pcrcg;
+
+extern "C" void pcrcg_gemm_set_mode(int mode) { g_gemm_mode.store(mode != 0, std::memory_order_relaxed); }
+extern "C" int pcrcg_gemm_get_mode(void) { return gemm_mode(); }
+extern "C" void pcrcg_thread_shares_gpu(int on) { gemm_x6_set_shared(on); }
+extern "C" int pcrcg_gemm_redo_counts(unsigned long long* out2, int reset) { return gemm_x6_redo_counts(out2, reset); }
 
 extern "C" size_t pcrcg_gemm_colstats_bytes(int m, int n) {
     const size_t chunks = (size_t)((m > 0 ? m : 1) + 31) / 32 + 4;
     return carve_bytes(2 * (size_t)(n > 0 ? n : 1) * chunks, sizeof(double));
 }
 
+// the arguments the plain entry points share, as a descriptor
+static GemmCall plain_call(const void* a, int lda, int trans_a, const float* b, int ldb, int trans_b, float* c, int ldc, int m,
+                           int n, int k, const float* row_scale, const float* bias, void* stream) {
+    GemmCall g;
+    g.a = a; g.lda = lda; g.b = b; g.ldb = ldb; g.c = c; g.ldc = ldc;
+    g.m = m; g.n = n; g.k = k;
+    g.a_form = trans_a ? GemmA::kmajor_f32 : GemmA::row_f32;
+    g.b_form = trans_b ? GemmB::nk : GemmB::kn;
+    g.row_scale = row_scale; g.bias = bias;
+    g.st = as_stream(stream);
+    return g;
+}
+
 extern "C" int pcrcg_gemm_f32(const float* a, int lda, const float* b, int ldb, int trans_b, float* c, int ldc,
                               int m, int n, int k, const float* row_scale, const float* bias, void* stream) {
-    return pcrcg_gemm_f32_colstats(a, lda, b, ldb, trans_b, c, ldc, m, n, k, row_scale, bias, nullptr, 0, nullptr,
-                                   stream);
+    return gemm_run(plain_call(a, lda, 0, b, ldb, trans_b, c, ldc, m, n, k, row_scale, bias, stream));
 }
 
 extern "C" int pcrcg_gemm_f32_colstats(const float* a, int lda, const float* b, int ldb, int trans_b, float* c,
                                        int ldc, int m, int n, int k, const float* row_scale, const float* bias,
                                        void* colstats, size_t colstats_bytes, int* h_chunks, void* stream) {
-    return gemm_dispatch(a, lda, 0, b, ldb, trans_b, c, ldc, m, n, k, row_scale, bias, colstats, colstats_bytes, h_chunks,
-                         stream);
+    GemmCall g = plain_call(a, lda, 0, b, ldb, trans_b, c, ldc, m, n, k, row_scale, bias, stream);
+    g.colstats = colstats; g.colstats_bytes = colstats_bytes; g.h_chunks = h_chunks;
+    return gemm_run(g);
 }
 
 // C = (A @ B^T) * row_scale + bias with A stored as bf16 ([m, k], lda in bf16 elements; 16-byte aligned rows, k % 32 == 0)
@@ -483,8 +493,10 @@ extern "C" int pcrcg_gemm_f32_colstats(const float* a, int lda, const float* b, 
 extern "C" int pcrcg_gemm_bf16a_f32_colstats(const void* a_bf16, int lda, const float* b, int ldb, float* c, int ldc, int m,
                                              int n, int k, const float* row_scale, const float* bias, void* colstats,
                                              size_t colstats_bytes, int* h_chunks, void* stream) {
-    return gemm_bf16a_bt_colstats(a_bf16, lda, b, ldb, c, ldc, m, n, k, row_scale, bias, colstats, colstats_bytes, h_chunks,
-                                  as_stream(stream), false, false);
+    GemmCall g = plain_call(a_bf16, lda, 0, b, ldb, 1, c, ldc, m, n, k, row_scale, bias, stream);
+    g.a_form = GemmA::row_bf16;
+    g.colstats = colstats; g.colstats_bytes = colstats_bytes; g.h_chunks = h_chunks;
+    return gemm_run(g);
 }
 
 // C (+)= f(A)[rows] * B^T + bias: the products of the runner that fold a neighbouring operator into their A loads.
@@ -499,7 +511,7 @@ extern "C" int pcrcg_gemm_f32_fused(const float* a, int lda, const int64_t* idx,
                                     const float* bias, float* c, int ldc, int m, int n, int k, int accumulate, void* stream) {
     PCRCG_CHECK_ARG(!idx || (ld_idx >= 1 && ns >= 0 && zero_row));
     PCRCG_CHECK_ARG(!a_sums || a_count >= 1.0);
-    if (gemm_mode() != 1) {
+    if (!gemm_split_terms_on()) {
         set_error("pcrcg_gemm_f32_fused: only the split-bf16 arithmetic (pcrcg_gemm_set_mode(1)) implements it");
         return PCRCG_EBADARG;
     }
@@ -513,104 +525,30 @@ extern "C" int pcrcg_gemm_f32_fused(const float* a, int lda, const int64_t* idx,
     ex.a_count = a_count;
     ex.a_eps = a_eps;
     ex.a_slope = a_slope;
-    return gemm_bt_extra(a, lda, b, ldb, c, ldc, m, n, k, as_stream(stream), false, ex, bias, nullptr, 0, nullptr, false);
+    GemmCall g = plain_call(a, lda, 0, b, ldb, 1, c, ldc, m, n, k, nullptr, bias, stream);
+    g.ex = &ex;
+    return gemm_run(g);
 }
 
 // Aop = A^T when trans_a (A stored [K, M] row-major): the weight-gradient products dW = X^T * dY of the
 // training rows (include/pcrcg_train.h), whose reduction dimension is the number of points.
 extern "C" int pcrcg_gemm_f32_ex(const float* a, int lda, int trans_a, const float* b, int ldb, int trans_b, float* c,
                                  int ldc, int m, int n, int k, const float* row_scale, const float* bias, void* stream) {
-    return gemm_dispatch(a, lda, trans_a, b, ldb, trans_b, c, ldc, m, n, k, row_scale, bias, nullptr, 0, nullptr, stream);
+    return gemm_run(plain_call(a, lda, trans_a, b, ldb, trans_b, c, ldc, m, n, k, row_scale, bias, stream));
 }
 
+// ... with the operand that holds gradients named (GemmExtra::grad_operand); without one, without the split-term arithmetic
+// and for A^T * B^T: pcrcg_gemm_f32_ex.  An empty reduction (k == 0) leaves C as it is.
 extern "C" int pcrcg_gemm_f32_grad(const float* a, int lda, int trans_a, const float* b, int ldb, int trans_b, float* c,
                                    int ldc, int m, int n, int k, const float* row_scale, const float* bias, int grad_operand,
                                    void* stream) {
     PCRCG_CHECK_ARG(grad_operand >= 0 && grad_operand <= 2);
-    if (grad_operand == 0 || pcrcg_gemm_get_mode() != 1 || (trans_a && trans_b))
-        return gemm_dispatch(a, lda, trans_a, b, ldb, trans_b, c, ldc, m, n, k, row_scale, bias, nullptr, 0, nullptr, stream);
-    return pcrcg::gemm_general(a, lda, trans_a, b, ldb, trans_b, c, ldc, m, n, k, row_scale, bias, false, as_stream(stream),
-                               grad_operand);
-}
-
-static int gemm_dispatch(const float* a, int lda, int trans_a, const float* b, int ldb, int trans_b, float* c, int ldc,
-                         int m, int n, int k, const float* row_scale, const float* bias, void* colstats,
-                         size_t colstats_bytes, int* h_chunks, void* stream, bool c_zeroed, bool colstats_sums) {
-    if (h_chunks) *h_chunks = 0;
+    GemmCall g = plain_call(a, lda, trans_a, b, ldb, trans_b, c, ldc, m, n, k, row_scale, bias, stream);
+    if (grad_operand == 0 || !gemm_split_terms_on() || (trans_a && trans_b)) return gemm_run(g);
     PCRCG_CHECK_ARG(m >= 0 && n >= 0 && k >= 0);
-    if (m == 0 || n == 0) return PCRCG_OK;
-    PCRCG_CHECK_ARG(a && b && c);
-    PCRCG_CHECK_ARG((trans_a ? lda >= m : lda >= k) && ldc >= n);
-    PCRCG_CHECK_ARG(trans_b ? ldb >= k : ldb >= n);
-    hipStream_t st = as_stream(stream);
-    // split-bf16 arithmetic for A * B^T (the forward), A * B (dX = dY * W) and A^T * B (dW = X^T * dY); A^T * B^T stays fp32
-    if (gemm_mode() == 1 && !(trans_a && trans_b))
-        return gemm_x6_dispatch(a, lda, b, ldb, c, ldc, m, n, k, row_scale, bias, colstats, colstats_bytes, h_chunks, st, false,
-                                c_zeroed, trans_a ? 1 : 0, trans_b ? 0 : 1, colstats_sums);
-    if (colstats_sums) { colstats = nullptr; colstats_bytes = 0; }     // (the fp32 kernels only know the partials layout)
-    const int vec_a = (lda % 4 == 0) && ((reinterpret_cast<uintptr_t>(a) & 15) == 0);
-    const int vec_b = (ldb % 4 == 0) && ((reinterpret_cast<uintptr_t>(b) & 15) == 0);
-    // Tile / split selection (sweep in scripts/gemm_tune.py on the path's shapes): these GEMMs are skinny
-    // (N = 64..2048, K up to 7680) and each block streams its own slice of A from HBM, so many small
-    // blocks beat few large ones: 128x128 only when that still yields >= 1024 blocks, otherwise 64x64
-    // (128x64 for N <= 64 with a long M), with K split until ~1024 blocks are in flight.
-    struct Tile { int bm, bn; };
-    static const Tile tiles[4] = {{128, 128}, {128, 64}, {64, 128}, {64, 64}};
-    auto ntiles = [&](int t) {
-        return (long)((m + tiles[t].bm - 1) / tiles[t].bm) * ((n + tiles[t].bn - 1) / tiles[t].bn);
-    };
-    int pick = -1;
-    pick = debug_opts().gemm_tile;                                           // tuning aid (-1: automatic)
-    if (pick < 0 || pick > 3) pick = (n > 64 && ntiles(0) >= 1024) ? 0 : 3;
-    if (trans_a) pick = 3;                                                   // only the 64x64 tile is built for A^T
-    const int BM = tiles[pick].bm, BN = tiles[pick].bn;
-    const int gx = (n + BN - 1) / BN, gy = (m + BM - 1) / BM;
-    constexpr int BK = 32;   // a 64-deep k-step (2 blocks/CU) measured 12 % slower on the path's shapes
-    int splits = 1;
-    const int ktiles = (k + BK - 1) / BK;
-    const int split_target = debug_opts().gemm_split_target;
-    const int max_splits = trans_a ? 256 : 32;   // A^T products reduce over the points: few tiles, very long K
-    while ((long)gx * gy * splits < split_target && k / (2 * splits) >= 192 && splits < max_splits) splits *= 2;
-    if (debug_opts().gemm_splitk > 0) splits = debug_opts().gemm_splitk;     // tuning aid
-    int k_per_split = ((ktiles + splits - 1) / splits) * BK;
-    if (k_per_split < BK) k_per_split = BK;
-    splits = k > 0 ? (k + k_per_split - 1) / k_per_split : 1;
-    if (splits < 1) splits = 1;
-    const int atomic_out = splits > 1;
-    if (atomic_out) {
-        if (ldc == n) PCRCG_CHECK_HIP(hipMemsetAsync(c, 0, (size_t)m * n * sizeof(float), st));
-        else PCRCG_CHECK_HIP(hipMemset2DAsync(c, (size_t)ldc * sizeof(float), 0, (size_t)n * sizeof(float), m, st));
-    }
-    dim3 grid(gx, gy, splits);
-    const bool log_shapes = debug_opts().gemm_log != 0;   // tuning aid
-    if (log_shapes)
-        fprintf(stderr, "pcrcg_gemm m=%d n=%d k=%d lda=%d ldb=%d ldc=%d tb=%d grid=%dx%dx%d rs=%d bias=%d stats=%d\n", m, n,
-                k, lda, ldb, ldc, trans_b, gx, gy, splits, row_scale != nullptr, bias != nullptr, colstats != nullptr);
-    // column statistics ride along only when every output element is written exactly once
-    double* colp = nullptr;
-    int colp_chunks = 0;
-    if (colstats && h_chunks && !atomic_out) {
-        colp_chunks = gy * (pick == 1 ? 4 : 2);   // WAVES_M of the chosen tile
-        if (carve_bytes(2 * (size_t)n * colp_chunks, sizeof(double)) <= colstats_bytes) {
-            colp = static_cast<double*>(colstats);
-            *h_chunks = colp_chunks;
-        } else {
-            colp_chunks = 0;
-        }
-    }
-#define GO(BMV, BNV, WMV, WNV)                                                                                   \
-    return launch<BMV, BNV, WMV, WNV, BK>(trans_b != 0, grid, st, a, lda, b, ldb, c, ldc, m, n, k, row_scale, bias, \
-                                      k_per_split, vec_a, vec_b, atomic_out, colp, colp_chunks)
-    if (trans_a) {
-        if (trans_b)
-            return launch_one<64, 64, 2, 2, true, true, BK>(grid, st, a, lda, b, ldb, c, ldc, m, n, k, row_scale, bias,
-                                                            k_per_split, vec_a, vec_b, atomic_out, colp, colp_chunks);
-        return launch_one<64, 64, 2, 2, true, false, BK>(grid, st, a, lda, b, ldb, c, ldc, m, n, k, row_scale, bias,
-                                                         k_per_split, vec_a, vec_b, atomic_out, colp, colp_chunks);
-    }
-    if (pick == 0) { GO(128, 128, 2, 2); }
-    if (pick == 1) { GO(128, 64, 4, 1); }
-    if (pick == 2) { GO(64, 128, 2, 2); }
-    GO(64, 64, 2, 2);
-#undef GO
+    if (m == 0 || n == 0 || k == 0) return PCRCG_OK;
+    GemmExtra ex;
+    ex.grad_operand = grad_operand;
+    g.ex = &ex;
+    return gemm_run(g);
 }

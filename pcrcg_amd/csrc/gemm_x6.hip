@@ -29,13 +29,11 @@
 // prefetch), and two or more co-resident blocks per CU overlap one block's split/write phase with the
 // others' MFMA phase.
 #include <cstdlib>
-#include <map>
-#include <mutex>
 #include <type_traits>
 
 #include <hip/hip_ext.h>
 
-#include "common.h"
+#include "gemm.h"
 #include "pcrcg_train.h"
 
 namespace pcrcg {
@@ -56,7 +54,7 @@ constexpr int BK = 32;
 // or because of a row below it [1] (one atomic per such tile; read and reset through pcrcg_gemm_redo_counts)
 __device__ unsigned long long g_x6_redo[2];
 
-// kernel-side form of GemmGroup (common.h): the operands of up to 3 further products; extra = 0: a single product.
+// kernel-side form of GemmGroup (gemm.h): the operands of up to 3 further products; extra = 0: a single product.
 // Product e's row tiles start at row off[e] of the launch's tile space.
 constexpr int kGroupExtra = 3;
 struct GemmPairArgs {
@@ -858,27 +856,8 @@ __global__ void __launch_bounds__((x6_threads<BM, BN>()), MINB) k_gemm_x6(const 
     }
 }
 
-// set by gemm_x6_dispatch around a launch whose splits store partial tiles (deterministic mode), 0 / false otherwise
-thread_local long g_split_stride = 0;
-thread_local bool g_det_pass = false;
-// the deterministic mode's partial-tile buffer: one per stream, grown on demand (a debugging mode: synchronous allocation)
-struct DetBuf { float* p = nullptr; size_t n = 0; };
-std::mutex g_det_mu;
-std::map<hipStream_t, DetBuf> g_det_bufs;
-float* det_partials(hipStream_t st, size_t floats) {
-    std::lock_guard<std::mutex> g(g_det_mu);
-    DetBuf& b = g_det_bufs[st];
-    if (b.n < floats) {
-        if (hipStreamSynchronize(st) != hipSuccess) return nullptr;
-        if (b.p) (void)hipFree(b.p);
-        b.p = nullptr;
-        b.n = 0;
-        const size_t want = floats + floats / 4;
-        if (hipMalloc(&b.p, want * sizeof(float)) != hipSuccess) { b.p = nullptr; return nullptr; }
-        b.n = want;
-    }
-    return b.p;
-}
+// the deterministic mode's partial tiles (grown with 25 % slack)
+StreamScratch g_det_partials;
 
 // C (+)= sum over the splits' partial tiles, in split order: the second pass of the deterministic mode's split-K
 __global__ void __launch_bounds__(256) k_split_reduce(const float* __restrict__ part, long stride, int splits, float* __restrict__ c,
@@ -893,32 +872,53 @@ __global__ void __launch_bounds__(256) k_split_reduce(const float* __restrict__ 
     *dst = accumulate ? *dst + sum : sum;
 }
 
+// k_gemm_x6's arguments, in its order, up to the TileMap, which launch_x6 builds from the grid and split_stride
+struct X6Args {
+    const float* a; int lda;
+    const float* b; int ldb;
+    float* c; int ldc;
+    int m, n, k;
+    const float* row_scale; const float* bias;
+    int k_per_split, vec_a, vec_b, atomic_out;
+    double* colp = nullptr; int colp_chunks = 0;
+    const long long* a_idx = nullptr; int a_idx_ld = 0, a_ns = 0;      // gather form
+    const float* a_zero = nullptr;
+    const double* a_sums = nullptr; double a_count = 0.0;              // normalise-on-load form
+    float a_eps = 0.f, a_slope = 1.f;
+    GemmPairArgs pr;
+    long split_stride = 0;                                             // TileMap::split_stride
+    float h2_sa = 1.f, h2_sb = 1.f;                                    // the lifted fp16 form's operand scales
+};
+
+// grid = (column tiles, row tiles, splits) as the caller counts them; launched 1-D (see the kernel's tile order)
 template <int BM, int BN, int MINB, int ATERMS, int ALAY, int BLAY, int ANORM = 0, int KNOCK = 0, int H2 = 0>
-int launch_x6(dim3 grid, hipStream_t st, const float* a, int lda, const float* b, int ldb, float* c, int ldc, int m, int n,
-              int k, const float* row_scale, const float* bias, int k_per_split, int vec_a, int vec_b, int atomic_out,
-              double* colp, int colp_chunks, const long long* a_idx = nullptr, int a_idx_ld = 0, int a_ns = 0,
-              const float* a_zero = nullptr, const double* a_sums = nullptr, double a_count = 0.0, float a_eps = 0.f,
-              float a_slope = 1.f, GemmPairArgs pr = GemmPairArgs(), float h2_sa = 1.f, float h2_sb = 1.f) {
-    // grid = (column tiles, row tiles, splits) as the caller counts them; launched 1-D (see the kernel's tile order)
+int launch_x6(const X6Args& p, dim3 grid, hipStream_t st) {
     TileMap tm;
-    tm.split_stride = g_split_stride;
+    tm.split_stride = p.split_stride;
     tm.gx = (int)grid.x;
     tm.gy = (int)grid.y;
     tm.gs = (int)grid.z;
-    tm.order = x6_tile_order(tm.gx, tm.gy, tm.gs, BM, BN, k_per_split);
-    const size_t lds = lds_bytes<BM, BN>() + (ANORM ? 2 * sizeof(float) * (size_t)(((k_per_split + BK - 1) / BK) * BK) : 0) + (H2 ? 16 : 0);
+    tm.order = x6_tile_order(tm.gx, tm.gy, tm.gs, BM, BN, p.k_per_split);
+    const size_t lds = lds_bytes<BM, BN>() + (ANORM ? 2 * sizeof(float) * (size_t)(((p.k_per_split + BK - 1) / BK) * BK) : 0) + (H2 ? 16 : 0);
     auto kern = k_gemm_x6<BM, BN, MINB, ATERMS, ALAY, BLAY, ANORM, KNOCK, H2>;
     PCRCG_GRANT_LDS(kern);
-    int m_all = m;                                             // a grouped launch's products all count
-    for (int e = 0; e < pr.extra; ++e) m_all += pr.m[e];
-    KpProfScope prof(st, m_all, n, k, (ATERMS == 1 || H2) ? 3 : 6, 3);  // bench.py's GEMM roofline: the kernel's own start / stop events
-    hipExtLaunchKernelGGL(kern, dim3(tm.gx * tm.gy * tm.gs), dim3(x6_threads<BM, BN>()), lds, st, prof.a, prof.b, 0, a, lda, b, ldb, c, ldc, m, n,
-                          k, row_scale, bias, k_per_split, vec_a, vec_b, atomic_out, colp, colp_chunks, a_idx, a_idx_ld, a_ns,
-                          a_zero, a_sums, a_count, a_eps, a_slope, pr, tm, h2_sa, h2_sb);
+    int m_all = p.m;                                           // a grouped launch's products all count
+    for (int e = 0; e < p.pr.extra; ++e) m_all += p.pr.m[e];
+    KpProfScope prof(st, m_all, p.n, p.k, (ATERMS == 1 || H2) ? 3 : 6, 3);  // bench.py's GEMM roofline: the kernel's own start / stop events
+    hipExtLaunchKernelGGL(kern, dim3(tm.gx * tm.gy * tm.gs), dim3(x6_threads<BM, BN>()), lds, st, prof.a, prof.b, 0, p.a, p.lda, p.b,
+                          p.ldb, p.c, p.ldc, p.m, p.n, p.k, p.row_scale, p.bias, p.k_per_split, p.vec_a, p.vec_b, p.atomic_out,
+                          p.colp, p.colp_chunks, p.a_idx, p.a_idx_ld, p.a_ns, p.a_zero, p.a_sums, p.a_count, p.a_eps, p.a_slope,
+                          p.pr, tm, p.h2_sa, p.h2_sb);
     PCRCG_CHECK_LAUNCH();
     return PCRCG_OK;
 }
-
+// the A * B^T instances of one tile: the fp16 two-term form, a bf16-stored A, the bf16 three-term form
+template <int BM, int BN, int MINB>
+int launch_x6_abt(bool h2, bool a_bf16, const X6Args& p, dim3 grid, hipStream_t st) {
+    if (h2) return launch_x6<BM, BN, MINB, 3, 0, 0, 0, 0, 1>(p, grid, st);
+    if (a_bf16) return launch_x6<BM, BN, MINB, 1, 0, 0>(p, grid, st);
+    return launch_x6<BM, BN, MINB, 3, 0, 0>(p, grid, st);
+}
 
 }  // namespace
 
@@ -994,26 +994,19 @@ int gemm_x6_redo_counts(unsigned long long* out, int reset) {
     return PCRCG_OK;
 }
 
-// the split-K factor gemm_x6_dispatch uses for an [m, n, k] product (> 1: it accumulates into a zeroed C)
+// the split-K factor the plan gives an [m, n, k] A * B^T product without extras (> 1: it accumulates into a zeroed C) -- the
+// same x6_plan() call x6_run() makes for such a product
 int gemm_x6_splits(int m, int n, int k, long m_total) { return (m > 0 && n > 0) ? x6_plan(m, n, k, false, false, m_total).splits : 1; }
 
-// pcrcg_debug_release(): the deterministic mode's partial-tile buffers of every stream (the caller has drained them)
-void gemm_x6_release_det() {
-    std::lock_guard<std::mutex> g(g_det_mu);
-    for (auto& kv : g_det_bufs)
-        if (kv.second.p) (void)hipFree(kv.second.p);
-    g_det_bufs.clear();
-}
-
-// Called by gemm_dispatch (gemm.hip) for C = A * B^T products when the split-bf16 mode is on.  c_zeroed: C is
-// already all zeros (the runner's zero arena), so a split-K product needs no memset of its own.
-int gemm_x6_dispatch(const float* a, int lda, const float* b, int ldb, float* c, int ldc, int m, int n, int k,
-                     const float* row_scale, const float* bias, void* colstats, size_t colstats_bytes, int* h_chunks,
-                     hipStream_t st, bool a_bf16, bool c_zeroed, int a_kmajor, int b_kmajor, bool colstats_sums,
-                     const GemmExtra* ex, const GemmGroup* grp) {
-    // k-major operands (a_kmajor: A stored [K, M]; b_kmajor: B stored [K, N]) are read with 4-byte loads: no alignment rule
-    const int vec_a = (a_bf16 || a_kmajor) ? 1 : (lda % 4 == 0) && ((reinterpret_cast<uintptr_t>(a) & 15) == 0);
-    const int vec_b = b_kmajor ? 1 : (ldb % 4 == 0) && ((reinterpret_cast<uintptr_t>(b) & 15) == 0);
+// split_stride != 0: the second pass of the deterministic mode's split-K -- the splits store their partial tiles at C +
+// s * split_stride with plain stores (no atomics, no memset); g.c is the partial buffer then
+static int x6_run(const GemmCall& g, long split_stride) {
+    const float* const a = static_cast<const float*>(g.a);
+    const int m = g.m, n = g.n, k = g.k, ldc = g.ldc;
+    const bool a_bf16 = g.a_form == GemmA::row_bf16, a_kmajor = g.a_form == GemmA::kmajor_f32, b_kmajor = g.b_form == GemmB::kn;
+    const GemmExtra* const ex = g.ex;
+    const GemmGroup* const grp = g.grp;
+    hipStream_t st = g.st;
     if (a_kmajor && !b_kmajor) { set_error("gemm_x6: A^T * B^T is not built"); return PCRCG_EBADARG; }
     // (further products in the same launch: the plan of the largest one serves all)
     int m_plan = m;
@@ -1025,38 +1018,50 @@ int gemm_x6_dispatch(const float* a, int lda, const float* b, int ldb, float* c,
     }
     long m_total = m;
     for (int e = 0; e < n_extra; ++e) m_total += grp->p[e].m;
-    // (the lifted fp16 form of the train step's products is built for the 64 x 64 tile only, like the k-major forms)
-    const bool lifted = ex && ex->grad_operand && debug_opts().x6_h2 != 0 && !a_bf16;
-    const X6Plan plan = x6_plan(m_plan, n, k, a_kmajor || b_kmajor || (ex && ex->a_sums) || lifted, a_kmajor != 0, m_total);
-    const int pick = plan.pick, BM = plan.bm, BN = plan.bn, gx = plan.gx, splits = plan.splits;
+    const bool accumulate = ex && ex->accumulate;
+    const bool gather = ex && ex->a_idx;
+    const bool anorm = ex && ex->a_sums;
+    const int grad_op = ex ? ex->grad_operand : 0;
+    const bool h2 = debug_opts().x6_h2 != 0 && !a_bf16;
+    // The train step tells which operand holds GRADIENTS (GemmExtra::grad_operand): the fp16 form lifts it by 2^16 (exactly):
+    // rows whose gradients reach 2^-30 = 9.3e-10 then split as normal fp16 values; rows entirely below that, and values
+    // beyond 1, send their tile to the bf16 redo (the kernel's two range checks) -- fp32-class at every scale, the lift only
+    // decides how often the cheap loop suffices.  A k-major product whose caller says nothing keeps the bf16 form.
+    const bool lifted = h2 && grad_op;
+    // (the k-major, normalise-on-load and lifted forms are built for the 64 x 64 tile only)
+    const X6Plan plan = x6_plan(m_plan, n, k, a_kmajor || b_kmajor || anorm || lifted, a_kmajor, m_total);
+    const int BM = plan.bm, gx = plan.gx, splits = plan.splits;
     const int gy0 = (m + BM - 1) / BM;
     int gy = gy0, gye[kGroupExtra] = {0, 0, 0};
     for (int e = 0; e < n_extra; ++e) { gye[e] = (grp->p[e].m + BM - 1) / BM; gy += gye[e]; }
     if (n_extra && (a_kmajor || b_kmajor)) { set_error("gemm_x6: grouped launches are built for the A * B^T form"); return PCRCG_EBADARG; }
-    const int k_per_split = plan.k_per_split;
-    const bool accumulate = ex && ex->accumulate;
-    const bool gather = ex && ex->a_idx;
     if ((gather && (a_bf16 || a_kmajor || b_kmajor)) || (accumulate && a_bf16)) {
         set_error("gemm_x6: gather is built for k-contiguous fp32 operands, accumulate for fp32 operands");
         return PCRCG_EBADARG;
     }
     if (gather && !ex->a_zero) { set_error("gemm_x6: gather needs a zero row"); return PCRCG_EBADARG; }
-    const bool anorm = ex && ex->a_sums;
-    if (anorm && (a_bf16 || a_kmajor || b_kmajor || pick != 3)) {
+    if (anorm && (a_bf16 || a_kmajor || b_kmajor || plan.pick != 3)) {
         set_error("gemm_x6: normalise-on-load is built for the 64 x 64 tile of k-contiguous fp32 operands");
         return PCRCG_EBADARG;
     }
     // ---- deterministic mode (PCRCG_DEBUG=deterministic=1): split-K WITHOUT atomics.  The splits store their partial tiles
-    // to a scratch buffer (this very function once more, with C redirected and g_det_pass set: plain stores, split s at
-    // s * split_stride), and k_split_reduce adds them up in split order -- onto C when the product accumulates.  Costs one
-    // extra pass over splits x M x N floats; the scratch is the library's own (per stream, grown on demand).
-    if (splits > 1 && debug_opts().deterministic && !g_det_pass) {
-        const size_t rows_all = (size_t)m_total;
-        float* part = det_partials(st, (size_t)splits * rows_all * (size_t)n);
+    // to a scratch buffer (this very function once more, with C redirected and the stride between the splits' tiles given),
+    // and k_split_reduce adds them up in split order -- onto C when the product accumulates.  Costs one extra pass over
+    // splits x M x N floats; the scratch is the library's own (per stream, grown on demand).
+    if (splits > 1 && debug_opts().deterministic && !split_stride) {
+        const size_t floats = (size_t)splits * (size_t)m_total * (size_t)n;
+        float* part = static_cast<float*>(g_det_partials.get(st, floats * sizeof(float), (floats / 4) * sizeof(float)));
         if (!part) { set_error("gemm_x6: no memory for the deterministic mode's partial tiles"); return PCRCG_ELAUNCH; }
+        GemmCall g2 = g;
+        g2.c = part;
+        g2.ldc = n;
+        g2.colstats = nullptr;
+        g2.colstats_bytes = 0;
+        g2.h_chunks = nullptr;
+        g2.colstats_sums = false;
+        g2.c_zeroed = true;
         GemmExtra ex2;
-        if (ex) ex2 = *ex;
-        ex2.accumulate = 0;
+        if (ex) { ex2 = *ex; ex2.accumulate = false; g2.ex = &ex2; }
         GemmGroup grp2;
         size_t row = (size_t)m;
         if (grp) {
@@ -1069,61 +1074,55 @@ int gemm_x6_dispatch(const float* a, int lda, const float* b, int ldb, float* c,
                 grp2.p[e].h_chunks = nullptr;
                 row += (size_t)grp->p[e].m;
             }
+            g2.grp = &grp2;
         }
-        g_det_pass = true;
-        g_split_stride = (long)(rows_all * (size_t)n);
-        const int rc = gemm_x6_dispatch(a, lda, b, ldb, part, n, m, n, k, row_scale, bias, nullptr, 0, nullptr, st, a_bf16, true,
-                                        a_kmajor, b_kmajor, false, ex ? &ex2 : nullptr, grp ? &grp2 : nullptr);
-        g_det_pass = false;
-        g_split_stride = 0;
-        if (rc != PCRCG_OK) return rc;
+        const long stride = (long)((size_t)m_total * (size_t)n);
+        PCRCG_PROPAGATE(x6_run(g2, stride));
         row = 0;
         for (int e = -1; e < n_extra; ++e) {
             const int me = e < 0 ? m : grp->p[e].m;
-            float* ce = e < 0 ? c : grp->p[e].c;
+            float* ce = e < 0 ? g.c : grp->p[e].c;
             const long total = (long)me * n;
             hipLaunchKernelGGL(k_split_reduce, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, part + row * (size_t)n,
-                               (long)(rows_all * (size_t)n), splits, ce, ldc, me, n, accumulate ? 1 : 0);
+                               stride, splits, ce, ldc, me, n, accumulate ? 1 : 0);
             row += (size_t)me;
         }
         PCRCG_CHECK_LAUNCH();
         return PCRCG_OK;
     }
-    const int atomic_out = g_det_pass ? 0 : (splits > 1 || accumulate);
-    if (splits > 1 && !c_zeroed && !accumulate) {
-        if (ldc == n) PCRCG_CHECK_HIP(hipMemsetAsync(c, 0, (size_t)m * n * sizeof(float), st));
-        else PCRCG_CHECK_HIP(hipMemset2DAsync(c, (size_t)ldc * sizeof(float), 0, (size_t)n * sizeof(float), m, st));
-    }
-    for (int e = 0; e < n_extra; ++e)
-        if (splits > 1 && !grp->p[e].c_zeroed && !accumulate) {
-            if (ldc == n) PCRCG_CHECK_HIP(hipMemsetAsync(grp->p[e].c, 0, (size_t)grp->p[e].m * n * sizeof(float), st));
-            else PCRCG_CHECK_HIP(hipMemset2DAsync(grp->p[e].c, (size_t)ldc * sizeof(float), 0, (size_t)n * sizeof(float), grp->p[e].m, st));
+    X6Args p{a, g.lda, g.b, g.ldb, g.c, ldc, m, n, k, g.row_scale, g.bias, plan.k_per_split};
+    // k-major operands (A stored [K, M], B stored [K, N]) are read with 4-byte loads: no alignment rule
+    p.vec_a = (a_bf16 || a_kmajor) ? 1 : (g.lda % 4 == 0) && ((reinterpret_cast<uintptr_t>(a) & 15) == 0);
+    p.vec_b = b_kmajor ? 1 : (g.ldb % 4 == 0) && ((reinterpret_cast<uintptr_t>(g.b) & 15) == 0);
+    p.split_stride = split_stride;
+    p.atomic_out = split_stride ? 0 : (splits > 1 || accumulate);
+    for (int e = -1; e < n_extra; ++e) {
+        float* ce = e < 0 ? g.c : grp->p[e].c;
+        const int me = e < 0 ? m : grp->p[e].m;
+        if (splits > 1 && !(e < 0 ? g.c_zeroed : grp->p[e].c_zeroed) && !accumulate) {
+            if (ldc == n) PCRCG_CHECK_HIP(hipMemsetAsync(ce, 0, (size_t)me * n * sizeof(float), st));
+            else PCRCG_CHECK_HIP(hipMemset2DAsync(ce, (size_t)ldc * sizeof(float), 0, (size_t)n * sizeof(float), me, st));
         }
-    dim3 grid(gx, gy, splits);
-    const bool log_shapes = debug_opts().gemm_log != 0;   // tuning aid
-    if (log_shapes)
+    }
+    const dim3 grid(gx, gy, splits);
+    if (debug_opts().gemm_log != 0)   // tuning aid
         fprintf(stderr, "pcrcg_gemm_x6 m=%d n=%d k=%d lda=%d ldb=%d ldc=%d tile=%dx%d grid=%dx%dx%d rs=%d bias=%d stats=%d\n", m,
-                n, k, lda, ldb, ldc, BM, BN, gx, gy, splits, row_scale != nullptr, bias != nullptr, colstats != nullptr);
-    double* colp = nullptr;
-    int colp_chunks = 0;
-    if (colstats && h_chunks && !atomic_out && colstats_sums) {
+                n, k, g.lda, g.ldb, ldc, BM, plan.bn, gx, gy, splits, g.row_scale != nullptr, g.bias != nullptr, g.colstats != nullptr);
+    if (g.colstats && g.h_chunks && !p.atomic_out && g.colstats_sums) {
         // column sums by fp64 atomics into [2][n] accumulators the caller has zeroed (few row tiles: no contention to
         // speak of); *h_chunks = -1 tells the caller that the buffer holds sums, not partials
-        if (2 * (size_t)n * sizeof(double) <= colstats_bytes) {
-            colp = static_cast<double*>(colstats);
-            colp_chunks = -1;
-            *h_chunks = -1;
+        if (2 * (size_t)n * sizeof(double) <= g.colstats_bytes) {
+            p.colp = static_cast<double*>(g.colstats);
+            p.colp_chunks = *g.h_chunks = -1;
         }
-    } else if (colstats && h_chunks && !atomic_out) {
-        colp_chunks = gy0 * 2;   // WAVES_M
-        if (carve_bytes(2 * (size_t)n * colp_chunks, sizeof(double)) <= colstats_bytes) {
-            colp = static_cast<double*>(colstats);
-            *h_chunks = colp_chunks;
-        } else {
-            colp_chunks = 0;
+    } else if (g.colstats && g.h_chunks && !p.atomic_out) {
+        const int chunks = gy0 * 2;   // WAVES_M
+        if (carve_bytes(2 * (size_t)n * chunks, sizeof(double)) <= g.colstats_bytes) {
+            p.colp = static_cast<double*>(g.colstats);
+            p.colp_chunks = *g.h_chunks = chunks;
         }
     }
-    GemmPairArgs pa;
+    GemmPairArgs& pa = p.pr;
     pa.extra = n_extra;
     int row_off = gy0 * BM;
     for (int e = 0; e < n_extra; ++e) {
@@ -1140,80 +1139,35 @@ int gemm_x6_dispatch(const float* a, int lda, const float* b, int ldb, float* c,
         pa.a_count[e] = q.a_count;
         if (q.h_chunks) *q.h_chunks = 0;
         // the product's statistics: the same form as the first one's, into its own buffer (same size rule)
-        if (colp && q.colstats && q.h_chunks) {
+        if (p.colp && q.colstats && q.h_chunks) {
             pa.colp[e] = static_cast<double*>(q.colstats);
-            pa.colp_chunks[e] = colp_chunks < 0 ? -1 : gye[e] * 2;
+            pa.colp_chunks[e] = p.colp_chunks < 0 ? -1 : gye[e] * 2;
             *q.h_chunks = pa.colp_chunks[e];
-            if (colp_chunks > 0 && carve_bytes(2 * (size_t)n * pa.colp_chunks[e], sizeof(double)) > colstats_bytes) {
+            if (p.colp_chunks > 0 && carve_bytes(2 * (size_t)n * pa.colp_chunks[e], sizeof(double)) > g.colstats_bytes) {
                 pa.colp[e] = nullptr;
                 pa.colp_chunks[e] = 0;
                 *q.h_chunks = 0;
             }
         }
     }
-    // The train step tells which operand holds GRADIENTS (GemmExtra::grad_operand): the fp16 form lifts it by 2^16 (exactly):
-    // rows whose gradients reach 2^-30 = 9.3e-10 then split as normal fp16 values; rows entirely below that, and values
-    // beyond 1, send their tile to the bf16 redo (the kernel's two range checks) -- fp32-class at every scale, the lift only
-    // decides how often the cheap loop suffices.  A k-major product whose caller says nothing keeps the bf16 form.
-    const int grad_op = ex ? ex->grad_operand : 0;
-    const float h2_sa = grad_op == 1 ? 65536.0f : 1.0f, h2_sb = grad_op == 2 ? 65536.0f : 1.0f;
-    const bool h2_on = debug_opts().x6_h2 != 0 && !a_bf16;
-    if (a_kmajor) {  // dW = X^T * dY
-        if (h2_on && grad_op)
-            return launch_x6<64, 64, 3, 3, 1, 1, 0, 0, 2>(grid, st, a, lda, b, ldb, c, ldc, m, n, k, row_scale, bias, k_per_split, vec_a,
-                                                          vec_b, atomic_out, colp, colp_chunks, nullptr, 0, 0, nullptr, nullptr, 0.0, 0.f,
-                                                          1.f, GemmPairArgs(), h2_sa, h2_sb);
-        return launch_x6<64, 64, 3, 3, 1, 1>(grid, st, a, lda, b, ldb, c, ldc, m, n, k, row_scale, bias, k_per_split, vec_a,
-                                             vec_b, atomic_out, colp, colp_chunks);
-    }
-    if (b_kmajor) {  // dX = dY * W
-        if (h2_on && grad_op)
-            return launch_x6<64, 64, 4, 3, 0, 1, 0, 0, 2>(grid, st, a, lda, b, ldb, c, ldc, m, n, k, row_scale, bias, k_per_split, vec_a,
-                                                          vec_b, atomic_out, colp, colp_chunks, nullptr, 0, 0, nullptr, nullptr, 0.0, 0.f,
-                                                          1.f, GemmPairArgs(), h2_sa, h2_sb);
-        return launch_x6<64, 64, 4, 3, 0, 1>(grid, st, a, lda, b, ldb, c, ldc, m, n, k, row_scale, bias, k_per_split, vec_a,
-                                             vec_b, atomic_out, colp, colp_chunks);
-    }
-    const bool h2 = h2_on;
-    if (h2 && grad_op && !anorm)      // the k-contiguous dX = dY W^T of the autograd mirror (pcrcg_gemm_f32_grad): the lifted 64 x 64 form
-        return launch_x6<64, 64, 4, 3, 0, 0, 0, 0, 2>(grid, st, a, lda, b, ldb, c, ldc, m, n, k, row_scale, bias, k_per_split, vec_a,
-                                                      vec_b, atomic_out, colp, colp_chunks, gather ? ex->a_idx : nullptr,
-                                                      gather ? ex->a_idx_ld : 0, gather ? ex->a_ns : 0,
-                                                      gather ? ex->a_zero : nullptr, nullptr, 0.0, 0.f, 1.f, pa, h2_sa, h2_sb);
-#define GO(BMV, BNV, MINB)                                                                                              \
-    do {                                                                                                                \
-        if (h2)                                                                                                         \
-            return launch_x6<BMV, BNV, MINB, 3, 0, 0, 0, 0, 1>(grid, st, a, lda, b, ldb, c, ldc, m, n, k, row_scale, bias,  \
-                                                      k_per_split, vec_a, vec_b, atomic_out, colp, colp_chunks,             \
-                                                      gather ? ex->a_idx : nullptr, gather ? ex->a_idx_ld : 0,              \
-                                                      gather ? ex->a_ns : 0, gather ? ex->a_zero : nullptr, nullptr, 0.0,   \
-                                                      0.f, 1.f, pa, h2_sa, h2_sb);                                          \
-        if (a_bf16)                                                                                                     \
-            return launch_x6<BMV, BNV, MINB, 1, 0, 0>(grid, st, a, lda, b, ldb, c, ldc, m, n, k, row_scale, bias,           \
-                                                      k_per_split, vec_a, vec_b, atomic_out, colp, colp_chunks, nullptr, 0, \
-                                                      0, nullptr, nullptr, 0.0, 0.f, 1.f, pa);                                \
-        return launch_x6<BMV, BNV, MINB, 3, 0, 0>(grid, st, a, lda, b, ldb, c, ldc, m, n, k, row_scale, bias, k_per_split,  \
-                                                  vec_a, vec_b, atomic_out, colp, colp_chunks, gather ? ex->a_idx : nullptr,\
-                                                  gather ? ex->a_idx_ld : 0, gather ? ex->a_ns : 0,                         \
-                                                  gather ? ex->a_zero : nullptr, nullptr, 0.0, 0.f, 1.f, pa);               \
-    } while (0)
-    if (anorm && h2)
-        return launch_x6<64, 64, 4, 3, 0, 0, 1, 0, 1>(grid, st, a, lda, b, ldb, c, ldc, m, n, k, row_scale, bias, k_per_split, vec_a,
-                                                      vec_b, atomic_out, colp, colp_chunks, gather ? ex->a_idx : nullptr,
-                                                      gather ? ex->a_idx_ld : 0, gather ? ex->a_ns : 0,
-                                                      gather ? ex->a_zero : nullptr, ex->a_sums, ex->a_count, ex->a_eps, ex->a_slope,
-                                                      pa);
-    if (anorm)
-        return launch_x6<64, 64, 4, 3, 0, 0, 1>(grid, st, a, lda, b, ldb, c, ldc, m, n, k, row_scale, bias, k_per_split, vec_a,
-                                                vec_b, atomic_out, colp, colp_chunks, gather ? ex->a_idx : nullptr,
-                                                gather ? ex->a_idx_ld : 0, gather ? ex->a_ns : 0,
-                                                gather ? ex->a_zero : nullptr, ex->a_sums, ex->a_count, ex->a_eps, ex->a_slope,
-                                                pa);
-    if (pick == 0) { GO(128, 128, 2); }
-    if (pick == 1) { GO(128, 64, 2); }
-    if (pick == 2) { GO(64, 128, 2); }
-    GO(64, 64, 4);
-#undef GO
+    if (gather) { p.a_idx = ex->a_idx; p.a_idx_ld = ex->a_idx_ld; p.a_ns = ex->a_ns; p.a_zero = ex->a_zero; }
+    if (anorm) { p.a_sums = ex->a_sums; p.a_count = ex->a_count; p.a_eps = ex->a_eps; p.a_slope = ex->a_slope; }
+    if (lifted && !anorm) { p.h2_sa = grad_op == 1 ? 65536.0f : 1.0f; p.h2_sb = grad_op == 2 ? 65536.0f : 1.0f; }
+    // ---- the template instance: the only thing left to choose
+    if (a_kmajor)   // dW = X^T * dY
+        return lifted ? launch_x6<64, 64, 3, 3, 1, 1, 0, 0, 2>(p, grid, st) : launch_x6<64, 64, 3, 3, 1, 1>(p, grid, st);
+    if (b_kmajor)   // dX = dY * W
+        return lifted ? launch_x6<64, 64, 4, 3, 0, 1, 0, 0, 2>(p, grid, st) : launch_x6<64, 64, 4, 3, 0, 1>(p, grid, st);
+    if (lifted && !anorm)   // the k-contiguous dX = dY W^T of the autograd mirror (pcrcg_gemm_f32_grad)
+        return launch_x6<64, 64, 4, 3, 0, 0, 0, 0, 2>(p, grid, st);
+    if (anorm) return h2 ? launch_x6<64, 64, 4, 3, 0, 0, 1, 0, 1>(p, grid, st) : launch_x6<64, 64, 4, 3, 0, 0, 1>(p, grid, st);
+    if (plan.pick == 0) return launch_x6_abt<128, 128, 2>(h2, a_bf16, p, grid, st);
+    if (plan.pick == 1) return launch_x6_abt<128, 64, 2>(h2, a_bf16, p, grid, st);
+    if (plan.pick == 2) return launch_x6_abt<64, 128, 2>(h2, a_bf16, p, grid, st);
+    return launch_x6_abt<64, 64, 4>(h2, a_bf16, p, grid, st);
 }
+
+// Called by gemm_run (gemm.hip) with a checked call when the split-term arithmetic is on
+int gemm_x6_dispatch(const GemmCall& g) { return x6_run(g, 0); }
 
 }  // namespace pcrcg

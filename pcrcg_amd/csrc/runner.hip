@@ -13,29 +13,9 @@
 
 #include <cstdlib>
 
-#include "common.h"
+#include "gemm.h"
 
 namespace pcrcg {
-// gemm.hip
-bool gemm_bt_accumulates(int m, int n, int k, long m_total = 0);
-int gemm_bt_colstats(const float* a, int lda, const float* b, int ldb, float* c, int ldc, int m, int n, int k,
-                     const float* row_scale, const float* bias, void* colstats, size_t colstats_bytes, int* h_chunks,
-                     hipStream_t st, bool c_zeroed, bool colstats_sums = false);
-int gemm_bf16a_bt_colstats(const void* a_bf16, int lda, const float* b, int ldb, float* c, int ldc, int m, int n, int k,
-                           const float* row_scale, const float* bias, void* colstats, size_t colstats_bytes,
-                           int* h_chunks, hipStream_t st, bool c_zeroed, bool colstats_sums);
-bool gemm_colstats_sums_ok();
-bool gemm_extra_ok();
-int gemm_bt_extra(const float* a, int lda, const float* b, int ldb, float* c, int ldc, int m, int n, int k, hipStream_t st,
-                  bool c_zeroed, const GemmExtra& ex, const float* bias = nullptr, void* colstats = nullptr,
-                  size_t colstats_bytes = 0, int* h_chunks = nullptr, bool colstats_sums = false);
-bool gemm_pair_ok();
-int gemm_bt_colstats_pair(const float* a, int lda, const float* b, int ldb, float* c, int ldc, int m, int n, int k,
-                          const float* row_scale, const float* bias, void* colstats, size_t colstats_bytes, int* h_chunks,
-                          hipStream_t st, bool c_zeroed, bool colstats_sums, const GemmGroup* grp);
-int gemm_bt_extra_pair(const float* a, int lda, const float* b, int ldb, float* c, int ldc, int m, int n, int k, hipStream_t st,
-                       bool c_zeroed, const GemmExtra& ex, const float* bias, void* colstats, size_t colstats_bytes,
-                       int* h_chunks, bool colstats_sums, const GemmGroup* grp);
 namespace {
 
 constexpr int GMAX = 4;   // fragment pairs one call can carry (pcrcg_kpfcnn_forward_group)
@@ -116,8 +96,7 @@ struct Ctx {
     bool live() const { return !dry && rc == PCRCG_OK; }
     void check(int r) { if (r != PCRCG_OK && rc == PCRCG_OK) rc = r; }
     // several pairs in one launch: only with the split-bf16 arithmetic (PCRCG_GEMM_MODE=0 runs the products pair by pair)
-    bool paired() const { return G >= 2 && gemm_pair_ok(); }
-    bool paired_ok() const { return gemm_pair_ok(); }
+    bool paired() const { return G >= 2 && gemm_split_terms_on(); }
 };
 
 inline int pad4(int v) { return (v + 3) & ~3; }
@@ -155,7 +134,7 @@ struct Stat {
 Stat stat_buffer(Ctx& c, const int* rows, int cols) {
     Stat s;
     const int mr = c.max_rows(rows);
-    if (debug_opts().stat_sums && mr <= debug_opts().stat_sums_rows && gemm_colstats_sums_ok()) {
+    if (debug_opts().stat_sums && mr <= debug_opts().stat_sums_rows && gemm_split_terms_on()) {
         s.sums = true;
         s.bytes = 2 * sizeof(double) * (size_t)cols;
         for (int g = 0; g < c.G; ++g) s.partials[g] = c.zraw(s.bytes);
@@ -249,92 +228,89 @@ void norm_act(Ctx& c, const Mat& x, float slope, const Mat& y, Stat* xs = nullpt
     c.release(m);
 }
 
+// where pair g's product leaves the column statistics of its output
+void stats_into(GemmCall& call, Stat* st, int g) {
+    if (!st) return;
+    call.colstats = st->partials[g];
+    call.colstats_bytes = st->bytes;
+    call.h_chunks = &st->chunks[g];
+    call.colstats_sums = st->sums;
+}
+// What a product may fold into its A loads, for all pairs.  tabs: per-pair gather table (first column; the source has
+// x.rows[g] rows, indices outside read zero_row); sums: per-pair column sums of the raw A (normalise-on-load), or NULL
+struct Fold {
+    const pcrcg_table* const* tabs = nullptr;
+    const float* zero_row = nullptr;
+    Stat* sums = nullptr;
+    float slope = 1.0f;
+    bool accumulate = false;
+};
+GemmExtra extra_of(const Fold& f, const Mat& x, int g) {
+    GemmExtra ex;
+    if (f.sums) {
+        ex.a_sums = static_cast<const double*>(f.sums->partials[g]);
+        ex.a_count = (double)x.rows[g];
+        ex.a_slope = f.slope;
+    }
+    if (f.tabs) {
+        ex.a_idx = reinterpret_cast<const long long*>(f.tabs[g]->idx);
+        ex.a_idx_ld = f.tabs[g]->ld;
+        ex.a_ns = x.rows[g];
+        ex.a_zero = f.zero_row;
+    }
+    ex.accumulate = f.accumulate;
+    return ex;
+}
 // the further pairs' sides of a product
-GemmGroup group_of(const Ctx& c, const Mat& x, const Mat& y, Stat* st, const float* const* row_scale = nullptr) {
+GemmGroup group_of(const Ctx& c, const Mat& x, const Mat& y, bool c_zeroed, Stat* st, const float* const* row_scale, const Fold* f) {
     GemmGroup grp;
     grp.n = c.G - 1;
     for (int g = 1; g < c.G; ++g) {
         GemmPair& p = grp.p[g - 1];
         p.a = x.p[g];
         p.c = y.p[g];
-        p.m = x.rows[g];
+        p.m = (f && f->tabs) ? f->tabs[g]->rows : x.rows[g];
         p.row_scale = row_scale ? row_scale[g] : nullptr;
         p.colstats = st ? st->partials[g] : nullptr;
         p.h_chunks = st ? &st->chunks[g] : nullptr;
-        p.c_zeroed = y.zeroed;
+        p.c_zeroed = c_zeroed;
+        if (f && f->tabs) { p.a_idx = reinterpret_cast<const long long*>(f->tabs[g]->idx); p.a_ns = x.rows[g]; }
+        if (f && f->sums) { p.a_sums = static_cast<const double*>(f->sums->partials[g]); p.a_count = (double)x.rows[g]; }
     }
     return grp;
 }
 
-// y = x @ w^T (+ bias); w is [out, in] with leading dimension ldw; optionally leaves the column statistics of y for the
-// InstanceNorm that follows.  row_scale: per-pair row factors (KPConv's 1 / neighbour count)
+// y (+)= f(x)[rows] @ w^T (+ bias); w is [out, in] with leading dimension ldw; optionally leaves the column statistics of y
+// for the InstanceNorm that follows.  row_scale: per-pair row factors (KPConv's 1 / neighbour count); f: the GemmExtra
+// forms (NULL: a plain product, which also runs without the split-term arithmetic); c_zeroed: y is known to be all zeros.
+// All pairs in one launch when they can share it.
+void linear(Ctx& c, const Mat& x, const float* w, int ldw, const float* bias, const Mat& y, bool c_zeroed, Stat* st = nullptr,
+            const float* const* row_scale = nullptr, const Fold* f = nullptr) {
+    if (!c.live()) return;
+    bool same_ld = true;
+    for (int g = 1; g < c.G && f && f->tabs; ++g) same_ld = same_ld && f->tabs[g]->ld == f->tabs[0]->ld;
+    const bool grouped = c.paired() && same_ld;
+    for (int g = 0; g < (grouped ? 1 : c.G); ++g) {
+        GemmCall call;
+        call.a = x.p[g]; call.lda = x.ld;
+        call.b = w; call.ldb = ldw;
+        call.c = y.p[g]; call.ldc = y.ld;
+        call.m = (f && f->tabs) ? f->tabs[g]->rows : x.rows[g]; call.n = y.cols; call.k = x.cols;
+        call.row_scale = row_scale ? row_scale[g] : nullptr;
+        call.bias = bias;
+        call.st = c.st;
+        stats_into(call, st, g);
+        call.c_zeroed = c_zeroed;
+        const GemmExtra ex = f ? extra_of(*f, x, g) : GemmExtra();
+        const GemmGroup grp = grouped ? group_of(c, x, y, c_zeroed, st, row_scale, f) : GemmGroup();
+        if (f) call.ex = &ex;
+        if (grouped) call.grp = &grp;
+        c.check(gemm_run(call));
+    }
+}
 void linear(Ctx& c, const Mat& x, const float* w, int ldw, const float* bias, const Mat& y, Stat* st = nullptr,
             const float* const* row_scale = nullptr) {
-    if (!c.live()) return;
-    if (c.paired()) {
-        GemmGroup p = group_of(c, x, y, st, row_scale);
-        c.check(gemm_bt_colstats_pair(x.p[0], x.ld, w, ldw, y.p[0], y.ld, x.rows[0], y.cols, x.cols, row_scale ? row_scale[0] : nullptr,
-                                      bias, st ? st->partials[0] : nullptr, st ? st->bytes : 0, st ? &st->chunks[0] : nullptr, c.st,
-                                      y.zeroed, st && st->sums, &p));
-        return;
-    }
-    for (int g = 0; g < c.G; ++g)
-        c.check(gemm_bt_colstats(x.p[g], x.ld, w, ldw, y.p[g], y.ld, x.rows[g], y.cols, x.cols, row_scale ? row_scale[g] : nullptr,
-                                 bias, st ? st->partials[g] : nullptr, st ? st->bytes : 0, st ? &st->chunks[g] : nullptr, c.st,
-                                 y.zeroed, st && st->sums));
-}
-
-// C (+)= f(A)[rows] @ w^T: the GemmExtra forms, for all pairs.  idx / ns: per-pair gather table (first column) and source
-// row count, sums: per-pair column sums of the raw A (normalise-on-load), or NULL
-void linear_extra(Ctx& c, const Mat& a, const float* w, int ldw, const float* bias, const Mat& y, int out_rows_of_table,
-                  const pcrcg_table* const* tabs, const float* zero_row, Stat* a_sums, float a_slope, bool accumulate,
-                  bool c_zeroed, Stat* st = nullptr) {
-    if (!c.live()) return;
-    (void)out_rows_of_table;
-    auto extra = [&](int g) {
-        GemmExtra ex;
-        if (a_sums) {
-            ex.a_sums = static_cast<const double*>(a_sums->partials[g]);
-            ex.a_count = (double)a.rows[g];
-            ex.a_slope = a_slope;
-        }
-        if (tabs) {
-            ex.a_idx = reinterpret_cast<const long long*>(tabs[g]->idx);
-            ex.a_idx_ld = tabs[g]->ld;
-            ex.a_ns = a.rows[g];
-            ex.a_zero = zero_row;
-        }
-        ex.accumulate = accumulate;
-        return ex;
-    };
-    auto m_of = [&](int g) { return tabs ? tabs[g]->rows : a.rows[g]; };
-    bool same_ld = true;
-    for (int g = 1; g < c.G && tabs; ++g) same_ld = same_ld && tabs[g]->ld == tabs[0]->ld;
-    if (c.paired() && same_ld) {
-        GemmExtra ex = extra(0);
-        GemmGroup p;
-        p.n = c.G - 1;
-        for (int g = 1; g < c.G; ++g) {
-            GemmPair& q = p.p[g - 1];
-            q.a = a.p[g];
-            q.c = y.p[g];
-            q.m = m_of(g);
-            q.colstats = st ? st->partials[g] : nullptr;
-            q.h_chunks = st ? &st->chunks[g] : nullptr;
-            q.c_zeroed = c_zeroed;
-            if (tabs) { q.a_idx = reinterpret_cast<const long long*>(tabs[g]->idx); q.a_ns = a.rows[g]; }
-            if (a_sums) { q.a_sums = static_cast<const double*>(a_sums->partials[g]); q.a_count = (double)a.rows[g]; }
-        }
-        c.check(gemm_bt_extra_pair(a.p[0], a.ld, w, ldw, y.p[0], y.ld, m_of(0), y.cols, a.cols, c.st, c_zeroed, ex, bias,
-                                   st ? st->partials[0] : nullptr, st ? st->bytes : 0, st ? &st->chunks[0] : nullptr,
-                                   st && st->sums, &p));
-        return;
-    }
-    for (int g = 0; g < c.G; ++g) {
-        GemmExtra ex = extra(g);
-        c.check(gemm_bt_extra(a.p[g], a.ld, w, ldw, y.p[g], y.ld, m_of(g), y.cols, a.cols, c.st, c_zeroed, ex, bias,
-                              st ? st->partials[g] : nullptr, st ? st->bytes : 0, st ? &st->chunks[g] : nullptr, st && st->sums));
-    }
+    linear(c, x, w, ldw, bias, y, y.zeroed, st, row_scale);
 }
 
 // y = lrelu(IN(x), slope) @ w^T (+ bias) with the normalisation done inside the product's A loads (GemmExtra::a_sums):
@@ -347,8 +323,11 @@ bool lazy_stats_ready(Ctx& c, const Mat& x, Stat* xs) {
 }
 bool linear_norm(Ctx& c, const Mat& x, Stat* xs, float slope, const float* w, int ldw, const float* bias, const Mat& y,
                  Stat* st = nullptr) {
-    if (!gemm_extra_ok() || !lazy_stats_ready(c, x, xs)) return false;
-    linear_extra(c, x, w, ldw, bias, y, 0, nullptr, nullptr, xs, slope, false, y.zeroed, st);
+    if (!gemm_split_terms_on() || !lazy_stats_ready(c, x, xs)) return false;
+    Fold f;
+    f.sums = xs;
+    f.slope = slope;
+    linear(c, x, w, ldw, bias, y, y.zeroed, st, nullptr, &f);
     return true;
 }
 
@@ -415,9 +394,16 @@ void kpconv(Ctx& c, const Batches& B, const pcrcg_block& blk, const Mat& x, cons
             if (c.live()) {
                 c.check(pcrcg_kpconv_aggregate_bf16(q[g], nq[g], b.points[l], ns[g], tab[g]->idx, tab[g]->cols, tab[g]->ld, xin.p[g],
                                                     cin, blk.kp, blk.extent, xb, wfb, inv_n[g], ws[g], wsb[g], c.st));
-                c.check(gemm_bf16a_bt_colstats(wfb, kk, kp_wt, kk, y.p[g], y.ld, nq[g], y.cols, kk, inv_n[g], nullptr,
-                                               st ? st->partials[g] : nullptr, st ? st->bytes : 0, st ? &st->chunks[g] : nullptr,
-                                               c.st, y.zeroed, st && st->sums));
+                GemmCall call;
+                call.a = wfb; call.lda = kk; call.a_form = GemmA::row_bf16;
+                call.b = kp_wt; call.ldb = kk;
+                call.c = y.p[g]; call.ldc = y.ld;
+                call.m = nq[g]; call.n = y.cols; call.k = kk;
+                call.row_scale = inv_n[g];
+                call.c_zeroed = y.zeroed;
+                call.st = c.st;
+                stats_into(call, st, g);
+                c.check(gemm_run(call));
             }
         }
         c.release(m);
@@ -657,8 +643,8 @@ Mat self_attention(Ctx& c, const pcrcg_model& mdl, const pcrcg_gnn_layer& gl, co
     // InstanceNorm2d statistics of the two edge convolutions as fp64 sums (zero arena) when that form applies
     void *sums1[GMAX], *sums2[GMAX];
     for (int g = 0; g < c.G; ++g) {
-        sums1[g] = gemm_colstats_sums_ok() ? c.zraw(2 * sizeof(double) * (size_t)ch) : nullptr;
-        sums2[g] = gemm_colstats_sums_ok() ? c.zraw(2 * sizeof(double) * (size_t)(2 * ch)) : nullptr;
+        sums1[g] = gemm_split_terms_on() ? c.zraw(2 * sizeof(double) * (size_t)ch) : nullptr;
+        sums2[g] = gemm_split_terms_on() ? c.zraw(2 * sizeof(double) * (size_t)(2 * ch)) : nullptr;
     }
     Mat cat1 = cols(cat, ch, ch), cat2 = cols(cat, 2 * ch, 2 * ch);
     const bool ok1 = sums_apply_ok(e1, cat1, nullptr), ok2 = sums_apply_ok(e2, cat2, nullptr);
@@ -809,7 +795,7 @@ void forward(Ctx& c, const pcrcg_model& mdl, const Batches& B, const pcrcg_outpu
         }
     for (int i = 0; i < mdl.n_gnn; ++i) {
         const pcrcg_gnn_layer& gl = mdl.gnn[i];
-        if (gl.cross && 2 * c.G <= GMAX && c.paired_ok()) {
+        if (gl.cross && 2 * c.G <= GMAX && gemm_split_terms_on()) {
             // the second direction's queries come from d1, which the first direction does not change: both query
             // projections in one launch (2 G products sharing wq)
             const int G0 = c.G, ch = d0.cols;
@@ -832,7 +818,7 @@ void forward(Ctx& c, const pcrcg_model& mdl, const Batches& B, const pcrcg_outpu
         } else if (gl.cross) {
             d0 = cross_attention(c, mdl, gl, d0, d1);
             d1 = cross_attention(c, mdl, gl, d1, d0);   // sees the updated d0 (:214)
-        } else if (2 * c.G <= GMAX && c.paired_ok()) {
+        } else if (2 * c.G <= GMAX && gemm_split_terms_on()) {
             // The layer is applied to the source cloud and to the target cloud of every pair with the SAME weights and no
             // exchange between them (ref:models/gcn.py:207-211): 2 G independent clouds through ONE pass -- every weight
             // product of the layer once for all of them (round 5: three launches per layer instead of six; the
@@ -921,17 +907,23 @@ void forward(Ctx& c, const pcrcg_model& mdl, const Batches& B, const pcrcg_outpu
             // of x gathered through the table (closest_pool, the shadow index reads a zero row), plus its skip columns on
             // the skip features.  Neither the upsampled matrix nor the concatenation is written: at level 0 that is
             // 31 + 61 MB of stores and 92 MB of loads that the product no longer waits for.
-            if (concat && next && next->mlp_skip && next->skip_dim == cs && gemm_extra_ok() &&
+            if (concat && next && next->mlp_skip && next->skip_dim == cs && gemm_split_terms_on() &&
                 (next->type == PCRCG_BLK_UNARY || next->type == PCRCG_BLK_LAST_UNARY) && x.ld % 4 == 0 &&
                 skips.back().ld % 4 == 0) {
                 const Mat& sk = skips.back();
                 const bool last = next->type == PCRCG_BLK_LAST_UNARY;
                 Mat tt = c.mat(trows, next->out_dim, pad4(next->out_dim));    // rows 16-byte aligned: it may be gathered next
                 float* zero_row = static_cast<float*>(c.zraw(sizeof(float) * (size_t)(x.cols + 8)));
-                if (lazy && !(gemm_extra_ok() && lazy_stats_ready(c, x, &xs))) materialise();
+                if (lazy && !(gemm_split_terms_on() && lazy_stats_ready(c, x, &xs))) materialise();
                 // the producer's normalisation (when lazy) applied to the gathered rows; then the skip part on top
-                linear_extra(c, x, next->mlp, next->mlp_ld, nullptr, tt, 0, tabs, zero_row, lazy ? &xs : nullptr, 0.1f, false, false);
-                linear_extra(c, sk, next->mlp_skip, next->mlp_skip_ld, nullptr, tt, 0, nullptr, nullptr, nullptr, 1.0f, true, true);
+                Fold up, add;
+                up.tabs = tabs;
+                up.zero_row = zero_row;
+                up.sums = lazy ? &xs : nullptr;
+                up.slope = 0.1f;
+                add.accumulate = true;
+                linear(c, x, next->mlp, next->mlp_ld, nullptr, tt, /*c_zeroed=*/false, nullptr, nullptr, &up);
+                linear(c, sk, next->mlp_skip, next->mlp_skip_ld, nullptr, tt, /*c_zeroed=*/true, nullptr, nullptr, &add);
                 skips.pop_back();
                 lazy = false;
                 x = tt;

@@ -3,6 +3,7 @@
 
 #include <atomic>
 #include <mutex>
+#include <vector>
 
 #include "common.h"
 
@@ -269,6 +270,35 @@ const DebugOpts& debug_opts() {
     return *g_debug.load(std::memory_order_acquire);
 }
 
+// ---- StreamScratch (common.h): every instance registers itself so that pcrcg_debug_release() reaches it
+static std::mutex g_scratch_lock;
+static std::vector<StreamScratch*>& scratch_registry() {
+    static std::vector<StreamScratch*> all;       // (function-local: built before the first instance of any file)
+    return all;
+}
+StreamScratch::StreamScratch() {
+    std::lock_guard<std::mutex> g(g_scratch_lock);
+    scratch_registry().push_back(this);
+}
+void* StreamScratch::get(hipStream_t st, size_t bytes, size_t slack) {
+    std::lock_guard<std::mutex> g(mu_);
+    Buf& b = bufs_[st];
+    if (b.bytes < bytes) {
+        if (hipStreamSynchronize(st) != hipSuccess) return nullptr;
+        if (b.p) (void)hipFree(b.p);
+        b = Buf();
+        if (hipMalloc(&b.p, bytes + slack) != hipSuccess) { b.p = nullptr; return nullptr; }
+        b.bytes = bytes + slack;
+    }
+    return b.p;
+}
+void StreamScratch::release() {
+    std::lock_guard<std::mutex> g(mu_);
+    for (auto& kv : bufs_)
+        if (kv.second.p) (void)hipFree(kv.second.p);
+    bufs_.clear();
+}
+
 }  // namespace pcrcg
 
 extern "C" {
@@ -293,9 +323,11 @@ int pcrcg_debug_set(const char* spec) {
 // a stale entry) or wants the memory back calls this with those streams DRAINED; the next deterministic call allocates anew.
 int pcrcg_debug_release(void) {
     PCRCG_CHECK_HIP(hipDeviceSynchronize());
-    pcrcg::gemm_x6_release_det();
+    {
+        std::lock_guard<std::mutex> g(pcrcg::g_scratch_lock);
+        for (pcrcg::StreamScratch* s : pcrcg::scratch_registry()) s->release();
+    }
     pcrcg::trainops_release_det();
-    pcrcg::conv2d_release_det();
     return PCRCG_OK;
 }
 

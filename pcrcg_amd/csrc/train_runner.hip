@@ -24,17 +24,11 @@
 #include <mutex>
 #include <vector>
 
-#include "common.h"
+#include "gemm.h"
 #include "pcrcg_train.h"
 
 namespace pcrcg {
-// gemm.hip / trainops.hip
-// grad_operand: 1 = A holds gradients, 2 = B does, 0 = neither (see GemmExtra::grad_operand, common.h)
-int gemm_general(const float* a, int lda, int trans_a, const float* b, int ldb, int trans_b, float* c, int ldc, int m, int n,
-                 int k, const float* row_scale, const float* bias, bool accumulate, hipStream_t st, int grad_operand = 0);
-int gemm_bt_colstats(const float* a, int lda, const float* b, int ldb, float* c, int ldc, int m, int n, int k,
-                     const float* row_scale, const float* bias, void* colstats, size_t colstats_bytes, int* h_chunks,
-                     hipStream_t st, bool c_zeroed, bool colstats_sums);
+// trainops.hip
 int tr_scale_rows(const float* src, int ld_src, const float* s, float* dst, int rows, int cols, hipStream_t st);
 int tr_add_lrelu(const float* a, int lda, const float* b, int ldb, float slope, float* y, int ldy, int rows, int cols,
                  hipStream_t st);
@@ -50,6 +44,37 @@ int instnorm_backward_sums(const float* x, int n, int c, int ldx, const float* s
                            float* dx, int ld_dx, double* sums, hipStream_t st);
 
 namespace {
+
+// c = (op(a) * op(b)) * row_scale[m] + bias[n] as a descriptor: op = identity or transpose as in pcrcg_gemm_f32_ex
+GemmCall product(const float* a, int lda, int trans_a, const float* b, int ldb, int trans_b, float* c, int ldc, int m, int n, int k,
+                 const float* row_scale, const float* bias, hipStream_t st) {
+    GemmCall g;
+    g.a = a; g.lda = lda; g.a_form = trans_a ? GemmA::kmajor_f32 : GemmA::row_f32;
+    g.b = b; g.ldb = ldb; g.b_form = trans_b ? GemmB::nk : GemmB::kn;
+    g.c = c; g.ldc = ldc;
+    g.m = m; g.n = n; g.k = k;
+    g.row_scale = row_scale; g.bias = bias;
+    g.st = st;
+    return g;
+}
+// ... run; accumulate adds the product onto c with fp32 atomics (gradients of tensors with several consumers, parameter
+// gradients of shared weights).  grad_operand: 1 = a holds gradients, 2 = b does, 0 = neither (GemmExtra::grad_operand).
+// Split-term arithmetic only; an empty reduction (k == 0) leaves c as it is.
+int matmul(const float* a, int lda, int trans_a, const float* b, int ldb, int trans_b, float* c, int ldc, int m, int n, int k,
+           const float* row_scale, const float* bias, bool accumulate, hipStream_t st, int grad_operand = 0) {
+    PCRCG_CHECK_ARG(m >= 0 && n >= 0 && k >= 0);
+    if (m == 0 || n == 0 || k == 0) return PCRCG_OK;
+    if (!gemm_split_terms_on()) {
+        set_error("train step: the training runner needs the split-bf16 arithmetic (pcrcg_gemm_set_mode(1))");
+        return PCRCG_EBADARG;
+    }
+    GemmCall g = product(a, lda, trans_a, b, ldb, trans_b, c, ldc, m, n, k, row_scale, bias, st);
+    GemmExtra ex;
+    ex.accumulate = accumulate;
+    ex.grad_operand = grad_operand;
+    if (accumulate || grad_operand) g.ex = &ex;
+    return gemm_run(g);
+}
 
 struct TT {                 // a tensor of the tape: value, gradient (NULL: not differentiable), row-major view
     float* p = nullptr;
@@ -229,6 +254,17 @@ inline TT rows(const TT& t, int r0, int n) {
 }
 inline size_t fbytes(long rows, long cols) { return sizeof(float) * (size_t)(rows > 0 ? rows : 1) * (size_t)cols + 256; }
 
+// run a product() with the fp64 column sums of c asked for: slot is a zeroed [2][n] accumulator; true when it left them
+bool run_with_sums(Tape& t, GemmCall g, double* slot) {
+    int chunks = 0;
+    g.colstats = slot;
+    g.colstats_bytes = (size_t)2 * g.n * sizeof(double);
+    g.h_chunks = &chunks;
+    g.colstats_sums = true;
+    t.check(gemm_run(g));
+    return chunks == -1;
+}
+
 // ---- operators: forward now, backward recorded ---------------------------------------------------------------------
 
 // y = x @ W^T (+ bias); W [out, in] with leading dimension ldw   (nn.Linear / 1x1 convolution on row-major features)
@@ -242,21 +278,19 @@ TT linear(Tape& t, const TT& x, Wt w, int ldw, Wt bias, int out, TT* into = null
     if (t.live()) {
         double* slot = sums_out ? t.sums_slot(out) : nullptr;
         if (slot) {
-            int chunks = 0;
-            t.check(gemm_bt_colstats(x.p, x.ld, w.p, ldw, y.p, y.ld, x.rows, out, x.cols, nullptr, bias.p, slot,
-                                     (size_t)2 * out * sizeof(double), &chunks, t.st, false, true));
-            if (chunks == -1) *sums_out = slot;
+            if (run_with_sums(t, product(x.p, x.ld, 0, w.p, ldw, 1, y.p, y.ld, x.rows, out, x.cols, nullptr, bias.p, t.st), slot))
+                *sums_out = slot;
         } else {
-            t.check(gemm_general(x.p, x.ld, 0, w.p, ldw, 1, y.p, y.ld, x.rows, out, x.cols, nullptr, bias.p, false, t.st));
+            t.check(matmul(x.p, x.ld, 0, w.p, ldw, 1, y.p, y.ld, x.rows, out, x.cols, nullptr, bias.p, false, t.st));
         }
     }
     t.record([x, y, w, ldw, bias, out](Tape& b) {
         if (x.g)     // dx += dy @ W
-            b.check(gemm_general(y.g, y.ld, 0, w.p, ldw, 0, x.g, x.ld, x.rows, x.cols, out, nullptr, nullptr, true, b.st, 1));
+            b.check(matmul(y.g, y.ld, 0, w.p, ldw, 0, x.g, x.ld, x.rows, x.cols, out, nullptr, nullptr, true, b.st, 1));
         if (w.g || bias.g) {
             hipStream_t side = b.off_path();
             if (w.g)     // dW += dy^T @ x
-                b.check(gemm_general(y.g, y.ld, 1, x.p, x.ld, 0, w.g, ldw, out, x.cols, x.rows, nullptr, nullptr, true, side, 1));
+                b.check(matmul(y.g, y.ld, 1, x.p, x.ld, 0, w.g, ldw, out, x.cols, x.rows, nullptr, nullptr, true, side, 1));
             if (bias.g) b.check(tr_bias_grad(y.g, y.ld, y.rows, out, bias.g, side));
         }
     });
@@ -267,10 +301,10 @@ TT linear(Tape& t, const TT& x, Wt w, int ldw, Wt bias, int out, TT* into = null
 TT matmul_bt(Tape& t, const TT& a, const TT& bm) {
     TT y = t.tensor(a.rows, bm.rows);
     if (t.live())
-        t.check(gemm_general(a.p, a.ld, 0, bm.p, bm.ld, 1, y.p, y.ld, a.rows, bm.rows, a.cols, nullptr, nullptr, false, t.st));
+        t.check(matmul(a.p, a.ld, 0, bm.p, bm.ld, 1, y.p, y.ld, a.rows, bm.rows, a.cols, nullptr, nullptr, false, t.st));
     t.record([a, bm, y](Tape& b) {
-        if (a.g) b.check(gemm_general(y.g, y.ld, 0, bm.p, bm.ld, 0, a.g, a.ld, a.rows, a.cols, bm.rows, nullptr, nullptr, true, b.st, 1));
-        if (bm.g) b.check(gemm_general(y.g, y.ld, 1, a.p, a.ld, 0, bm.g, bm.ld, bm.rows, a.cols, a.rows, nullptr, nullptr, true, b.st, 1));
+        if (a.g) b.check(matmul(y.g, y.ld, 0, bm.p, bm.ld, 0, a.g, a.ld, a.rows, a.cols, bm.rows, nullptr, nullptr, true, b.st, 1));
+        if (bm.g) b.check(matmul(y.g, y.ld, 1, a.p, a.ld, 0, bm.g, bm.ld, bm.rows, a.cols, a.rows, nullptr, nullptr, true, b.st, 1));
     });
     return y;
 }
@@ -279,10 +313,10 @@ TT matmul_bt(Tape& t, const TT& a, const TT& bm) {
 TT matmul_nn(Tape& t, const TT& p, const TT& v, TT* into = nullptr) {
     TT y = into ? *into : t.tensor(p.rows, v.cols);
     if (t.live())
-        t.check(gemm_general(p.p, p.ld, 0, v.p, v.ld, 0, y.p, y.ld, p.rows, v.cols, p.cols, nullptr, nullptr, false, t.st));
+        t.check(matmul(p.p, p.ld, 0, v.p, v.ld, 0, y.p, y.ld, p.rows, v.cols, p.cols, nullptr, nullptr, false, t.st));
     t.record([p, v, y](Tape& b) {
-        if (p.g) b.check(gemm_general(y.g, y.ld, 0, v.p, v.ld, 1, p.g, p.ld, p.rows, p.cols, v.cols, nullptr, nullptr, true, b.st, 1));
-        if (v.g) b.check(gemm_general(p.p, p.ld, 1, y.g, y.ld, 0, v.g, v.ld, p.cols, v.cols, p.rows, nullptr, nullptr, true, b.st, 2));
+        if (p.g) b.check(matmul(y.g, y.ld, 0, v.p, v.ld, 1, p.g, p.ld, p.rows, p.cols, v.cols, nullptr, nullptr, true, b.st, 1));
+        if (v.g) b.check(matmul(p.p, p.ld, 1, y.g, y.ld, 0, v.g, v.ld, p.cols, v.cols, p.rows, nullptr, nullptr, true, b.st, 2));
     });
     return y;
 }
@@ -377,14 +411,12 @@ TT kpconv(Tape& t, const pcrcg_batch& b, const pcrcg_block& blk, Wt w, const TT&
         // C = A B^T form with both operands k-contiguous -- the inference runner's product; without it the k-major form
         double* slot = (sums_out && blk.kp_wt && kc % 4 == 0) ? t.sums_slot(cout) : nullptr;
         if (slot) {
-            int chunks = 0;
-            t.check(gemm_bt_colstats(wf, kc, blk.kp_wt, kc, y.p, y.ld, nq, cout, kc, inv_n, nullptr, slot,
-                                     (size_t)2 * cout * sizeof(double), &chunks, t.st, false, true));
-            if (chunks == -1) *sums_out = slot;
+            if (run_with_sums(t, product(wf, kc, 0, blk.kp_wt, kc, 1, y.p, y.ld, nq, cout, kc, inv_n, nullptr, t.st), slot))
+                *sums_out = slot;
         } else if (blk.kp_wt && kc % 4 == 0)
-            t.check(gemm_general(wf, kc, 0, blk.kp_wt, kc, 1, y.p, y.ld, nq, cout, kc, inv_n, nullptr, false, t.st));
+            t.check(matmul(wf, kc, 0, blk.kp_wt, kc, 1, y.p, y.ld, nq, cout, kc, inv_n, nullptr, false, t.st));
         else
-            t.check(gemm_general(wf, kc, 0, w.p, cout, 0, y.p, y.ld, nq, cout, kc, inv_n, nullptr, false, t.st));
+            t.check(matmul(wf, kc, 0, w.p, cout, 0, y.p, y.ld, nq, cout, kc, inv_n, nullptr, false, t.st));
     }
     t.need_scratch(fbytes(nq, kc));
     float* dys = static_cast<float*>(t.value_bytes(fbytes(nq, cout)));          // dy / n: read by the off-path dW product
@@ -394,10 +426,10 @@ TT kpconv(Tape& t, const pcrcg_batch& b, const pcrcg_block& blk, Wt w, const TT&
     t.record([=](Tape& bk) {
         bk.check(tr_scale_rows(y.g, y.ld, inv_n, dys, nq, cout, bk.st));          // dy / n
         if (w.g)                                                                  // dW += wf^T @ (dy / n)
-            bk.check(gemm_general(wf, kc, 1, dys, cout, 0, w.g, cout, kc, cout, nq, nullptr, nullptr, true, bk.off_path(), 2));
+            bk.check(matmul(wf, kc, 1, dys, cout, 0, w.g, cout, kc, cout, nq, nullptr, nullptr, true, bk.off_path(), 2));
         if (x.g) {                                                                // d wf = (dy / n) @ W^T, scattered through w
             float* d_wf = bk.tmp((size_t)(nq > 0 ? nq : 1) * kc + 64);
-            bk.check(gemm_general(dys, cout, 0, w.p, cout, 1, d_wf, kc, nq, kc, cout, nullptr, nullptr, false, bk.st, 1));
+            bk.check(matmul(dys, cout, 0, w.p, cout, 1, d_wf, kc, nq, kc, cout, nullptr, nullptr, false, bk.st, 1));
             bk.check(pcrcg_kpconv_backward_dx(q, nq, s_pts, ns, tab.idx, tab.cols, tab.ld, d_wf, cin, kp, extent, x.g, bk.st));
         }
     });

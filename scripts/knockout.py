@@ -27,10 +27,12 @@ FAMILIES = [("pcrcg_copy2d(", "K_COPY"), ("pcrcg_gather_max(", "K_GMAX"), ("pcrc
 
 def build():
     src = open(os.path.join(CSRC, "runner.hip")).read()
-    src = src.replace("namespace pcrcg {\n// gemm.hip", '#include <cstring>\nthread_local int pcrcg_knock_forward_count = 0;\nstatic bool ko(const char* name) { static const char* e = '
+    anchor = "namespace pcrcg {\nnamespace {\n\nconstexpr int GMAX"
+    assert anchor in src
+    src = src.replace(anchor, '#include <cstring>\nthread_local int pcrcg_knock_forward_count = 0;\nstatic bool ko(const char* name) { static const char* e = '
                       'getenv("PCRCG_KNOCK"); static const int every = getenv("PCRCG_KNOCK_EVERY") ? atoi(getenv("PCRCG_KNOCK_EVERY")) : 1; '
                       'return e && strstr(e, name) && (every <= 1 || (pcrcg_knock_forward_count % every) == 1); }\n'
-                      'namespace pcrcg {\n// gemm.hip', 1)
+                      + anchor, 1)
     pat = "    PCRCG_PROPAGATE(validate_group(model, batches, n));\n    PCRCG_CHECK_ARG(outs && ws);"
     assert pat in src
     src = src.replace(pat, "    ++pcrcg_knock_forward_count;\n" + pat, 1)
@@ -39,21 +41,21 @@ def build():
         src = src.replace(pat, 'ko("%s") ? PCRCG_OK : %s' % (tok, pat))
         print("%-8s %d call sites" % (tok, n))
     # the KPConv contraction alone (the GEMM a one-kernel KPConv would absorb)
-    pat = "            linear(c, wf, blk.kp_wt, kk, nullptr, y, st, inv_n);"
+    pat = "            linear(c, wf, kp_wt, kk, nullptr, y, st, inv_n);"
     assert pat in src
-    src = src.replace(pat, '            if (!ko("K_KPGEMM")) linear(c, wf, blk.kp_wt, kk, nullptr, y, st, inv_n);')
+    src = src.replace(pat, '            if (!ko("K_KPGEMM")) linear(c, wf, kp_wt, kk, nullptr, y, st, inv_n);')
     tmp = os.path.join(CSRC, "build", "knock")
     os.makedirs(tmp, exist_ok=True)
     open(os.path.join(tmp, "runner_knock.hip"), "w").write(src)
     # GEMMs by row count: PCRCG_KNOCK_M="lo,hi" skips every split-bf16 product with lo <= M < hi
     g = open(os.path.join(CSRC, "gemm_x6.hip")).read()
-    pat = "    // k-major operands (a_kmajor: A stored [K, M]; b_kmajor: B stored [K, N]) are read with 4-byte loads"
+    pat = "static int x6_run(const GemmCall& g, long split_stride) {\n"
     assert pat in g
     # PCRCG_KNOCK_M="lo,hi" skips the products with lo <= M < hi; "lo,hi,2" skips them in every SECOND forward of a host
     # thread only: what launching them once for two stacked pairs could buy at most
-    g = g.replace(pat, '    { static const char* e = getenv("PCRCG_KNOCK_M"); int lo = 0, hi = 0, every = 1;\n'
-                       '      if (e && sscanf(e, "%d,%d,%d", &lo, &hi, &every) >= 2 && m >= lo && m < hi &&\n'
-                       '          (every <= 1 || (pcrcg_knock_forward_count % every) == 1)) return PCRCG_OK; }\n' + pat, 1)
+    g = g.replace(pat, pat + '    { static const char* e = getenv("PCRCG_KNOCK_M"); int lo = 0, hi = 0, every = 1;\n'
+                       '      if (e && sscanf(e, "%d,%d,%d", &lo, &hi, &every) >= 2 && g.m >= lo && g.m < hi &&\n'
+                       '          (every <= 1 || (pcrcg_knock_forward_count % every) == 1)) return PCRCG_OK; }\n', 1)
     g = g.replace("namespace pcrcg {\nnamespace {\n\ntypedef float f32x16", "extern thread_local int pcrcg_knock_forward_count;\nnamespace pcrcg {\nnamespace {\n\ntypedef float f32x16", 1)
     assert "pcrcg_knock_forward_count;" in g
     open(os.path.join(tmp, "gemm_x6_knock.hip"), "w").write(g)

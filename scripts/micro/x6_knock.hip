@@ -12,6 +12,9 @@ void set_error(const char*, ...) {}
 const DebugOpts& debug_opts() { static DebugOpts d; return d; }
 KpProfScope::KpProfScope(hipStream_t s, int, int, int, int, int) : st(s), a(nullptr), b(nullptr), on(false) {}
 KpProfScope::~KpProfScope() {}
+StreamScratch::StreamScratch() {}
+void* StreamScratch::get(hipStream_t, size_t, size_t) { return nullptr; }
+void StreamScratch::release() {}
 }  // namespace pcrcg
 using namespace pcrcg;
 
@@ -20,13 +23,14 @@ float run(const float* a, const float* b, float* c, int m, int n, int k, int spl
     const int ktiles = (k + 31) / 32;
     const int kps = ((ktiles + splits - 1) / splits) * 32;
     dim3 grid((n + BN - 1) / BN, (m + BM - 1) / BM, (k + kps - 1) / kps);
+    const X6Args args{a, k, b, k, c, n, m, n, k, nullptr, nullptr, kps, 1, 1, splits > 1};
     hipEvent_t e0, e1;
     hipEventCreate(&e0);
     hipEventCreate(&e1);
-    for (int i = 0; i < 3; ++i) launch_x6<BM, BN, MINB, 3, 0, 0, 0, KNOCK>(grid, 0, a, k, b, k, c, n, m, n, k, nullptr, nullptr, kps, 1, 1, splits > 1, nullptr, 0);
+    for (int i = 0; i < 3; ++i) launch_x6<BM, BN, MINB, 3, 0, 0, 0, KNOCK>(args, grid, 0);
     hipEventRecord(e0, 0);
     const int reps = 20;
-    for (int i = 0; i < reps; ++i) launch_x6<BM, BN, MINB, 3, 0, 0, 0, KNOCK>(grid, 0, a, k, b, k, c, n, m, n, k, nullptr, nullptr, kps, 1, 1, splits > 1, nullptr, 0);
+    for (int i = 0; i < reps; ++i) launch_x6<BM, BN, MINB, 3, 0, 0, 0, KNOCK>(args, grid, 0);
     hipEventRecord(e1, 0);
     hipEventSynchronize(e1);
     float ms = 0;
