@@ -49,26 +49,32 @@ int grid_subsample_bound(const float* pts, int n_bound, const int* len, int nb, 
 bool instnorm_pack_ok(int c, int ldx, int ldy);
 int instnorm_apply_pack(const float* x, int n, int c, int ldx, const float* stats, const double* sums, double count, float eps,
                         float slope, float* y, int ldy, const float* s_pts, float4* pk, hipStream_t st);
+// pointops.hip, for gnn.hip: finish a [chunks][2][c] fp64 partial buffer (colstats_ws_bytes(c), at most colstats_chunks()
+// chunks) into (mean, rstd) pairs
+size_t colstats_ws_bytes(int c);
+int colstats_finalize(const double* partial, int nchunks, int c, double count, float eps, float* stats,
+                      hipStream_t st);
+int colstats_chunks();
 // kpconv.hip: where the support records live inside a pcrcg_kpconv_ws_bytes(ns) workspace
 float4* kpconv_pk_ptr(void* ws, size_t ws_bytes, int ns);
 
 // The deterministic debug mode's scratch: one device buffer per stream, kept until pcrcg_debug_release() (scan.hip) frees
 // those of every instance.  An instance is a namespace-scope object of the file that uses it (gemm_x6.hip: the split-K
-// partial tiles, conv2d.hip: the BatchNorm partial sums).  trainops.hip keeps its own pair of buffers (one of them must be
-// zeroed whenever it grows): trainops_release_det().
+// partial tiles, conv2d.hip: the BatchNorm partial sums, trainops.hip: the fixed-point accumulators).
 class StreamScratch {
 public:
-    StreamScratch();
+    // cleared: a newly allocated buffer is handed out zeroed, by a memset enqueued on the stream it was asked for
+    explicit StreamScratch(bool cleared = false);
     // >= bytes of device memory for work enqueued on st.  Too small: the stream is drained, the old buffer freed and
     // bytes + slack allocated (a debugging mode: synchronous allocation).  NULL: no memory / the stream failed.
     void* get(hipStream_t st, size_t bytes, size_t slack = 0);
     void release();
 private:
     struct Buf { void* p = nullptr; size_t bytes = 0; };
+    const bool cleared_;
     std::mutex mu_;
     std::map<hipStream_t, Buf> bufs_;
 };
-void trainops_release_det();
 
 // tieorder.hip: pcrcg_kdforest_build over clouds that are LEVELS of per_level clouds each, level l's rows starting at row
 // level_base[l] of sup (per_level = 0: one contiguous stack, the public entry point)
@@ -108,6 +114,8 @@ struct NormJob {
 };
 int instnorm_apply_sums_multi(const NormJob* jobs, int count, int c, int ldx, float eps, int ldr, float slope, int ldy, bool pack,
                               hipStream_t st);
+// the widths and leading dimensions that kernel serves (ldr = 0: no residual); 16-byte aligned bases are the caller's to check
+bool instnorm_sums_ok(int c, int ldx, int ldy, int ldr = 0);
 
 struct GatherJob { const float* x; const int64_t* idx; float* out; int ns, nq, h, ld_idx; };
 int gather_max_multi(const GatherJob* jobs, int count, int c, hipStream_t st);

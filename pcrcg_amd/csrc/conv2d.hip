@@ -337,7 +337,7 @@ __global__ void k_stats_finish(const double* __restrict__ part, int per_img, int
 }
 
 // the deterministic mode's partial sums (exact size: no slack)
-StreamScratch g_det_stat_partials;
+StreamScratch g_bn_partials;
 
 // BatchNorm2d finalize, one thread per channel: (scale, shift) per segment into ss [segments][2][C].
 //   training: batch mean, biased variance (eps) for the normalisation; running_mean / running_var updated with momentum and
@@ -902,7 +902,7 @@ int pcrcg_res50unet_forward(const float* arena, void* const* h_state, int n_tens
     q.training = training;
     q.per_image = !joint_stats;
     if (training && debug_opts().deterministic) {         // no floating-point atomics: the sums' partials, stored
-        q.det_part = static_cast<double*>(g_det_stat_partials.get(q.st, q.det_doubles * sizeof(double)));
+        q.det_part = static_cast<double*>(g_bn_partials.get(q.st, q.det_doubles * sizeof(double)));
         if (!q.det_part) {
             set_error("pcrcg_res50unet_forward: deterministic=1 could not allocate %zu bytes of partial sums", q.det_doubles * 8);
             return PCRCG_ELAUNCH;

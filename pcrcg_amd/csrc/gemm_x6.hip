@@ -857,7 +857,7 @@ __global__ void __launch_bounds__((x6_threads<BM, BN>()), MINB) k_gemm_x6(const 
 }
 
 // the deterministic mode's partial tiles (grown with 25 % slack)
-StreamScratch g_det_partials;
+StreamScratch g_splitk_partials;
 
 // C (+)= sum over the splits' partial tiles, in split order: the second pass of the deterministic mode's split-K
 __global__ void __launch_bounds__(256) k_split_reduce(const float* __restrict__ part, long stride, int splits, float* __restrict__ c,
@@ -1050,7 +1050,7 @@ static int x6_run(const GemmCall& g, long split_stride) {
     // splits x M x N floats; the scratch is the library's own (per stream, grown on demand).
     if (splits > 1 && debug_opts().deterministic && !split_stride) {
         const size_t floats = (size_t)splits * (size_t)m_total * (size_t)n;
-        float* part = static_cast<float*>(g_det_partials.get(st, floats * sizeof(float), (floats / 4) * sizeof(float)));
+        float* part = static_cast<float*>(g_splitk_partials.get(st, floats * sizeof(float), (floats / 4) * sizeof(float)));
         if (!part) { set_error("gemm_x6: no memory for the deterministic mode's partial tiles"); return PCRCG_ELAUNCH; }
         GemmCall g2 = g;
         g2.c = part;

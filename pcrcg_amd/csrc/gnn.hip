@@ -14,12 +14,6 @@
 #include "pcrcg_train.h"
 
 namespace pcrcg {
-
-size_t colstats_ws_bytes(int c);
-int colstats_finalize(const double* partial, int nchunks, int c, double count, float eps, float* stats,
-                      hipStream_t st);
-int colstats_chunks();
-
 namespace {
 
 typedef unsigned long long u64;

@@ -325,9 +325,6 @@ __global__ void __launch_bounds__(256) k_instnorm_apply4_sums_pack(NormMulti mm,
 
 }  // namespace
 
-int instnorm_apply_sums_multi(const NormJob* jobs, int count, int c, int ldx, float eps, int ldr, float slope, int ldy, bool pack,
-                              hipStream_t st);
-
 // Normalise + LeakyReLU (no residual) and leave the KPConv support records of the output rows in `pk` (see the kernels).
 // Statistics as (mean, rstd) pairs (`stats`) or as fp64 column sums (`sums`, `count`); exactly one of the two.
 bool instnorm_pack_ok(int c, int ldx, int ldy) {
@@ -353,7 +350,13 @@ int instnorm_apply_pack(const float* x, int n, int c, int ldx, const float* stat
 }
 
 // lrelu(IN(x) [+ res | + IN(res)]) for up to four tensors of one width in ONE launch (the pairs of a forward call); pack: also
-// leave the KPConv support records (instnorm_apply_pack).  The caller has checked the layout rules of the single-tensor entry.
+// leave the KPConv support records (instnorm_apply_pack).  The caller has checked the layout rules of the single-tensor entry:
+// instnorm_sums_ok -- the kernel's thread -> channel-group map needs the groups of four channels to tile 256 threads (or be a
+// multiple of 256), and its float4 accesses rows that start on multiples of four floats -- and 16-byte aligned bases.
+bool instnorm_sums_ok(int c, int ldx, int ldy, int ldr) {
+    const int c4 = c / 4;
+    return c >= 4 && c % 4 == 0 && (c4 <= 256 ? 256 % c4 == 0 : c4 % 256 == 0) && ldx % 4 == 0 && ldy % 4 == 0 && ldr % 4 == 0;
+}
 int instnorm_apply_sums_multi(const NormJob* jobs, int count, int c, int ldx, float eps, int ldr, float slope, int ldy, bool pack,
                               hipStream_t st) {
     PCRCG_CHECK_ARG(jobs && count >= 1 && count <= 4 && c >= 4 && c % 4 == 0);
@@ -511,11 +514,8 @@ int pcrcg_instnorm_apply_sums(const float* x, int n, int c, int ldx, const void*
     PCRCG_CHECK_ARG(n >= 0 && c >= 4 && c % 4 == 0 && ldx >= c && ldy >= c && count >= 1.0);
     if (n == 0) return PCRCG_OK;
     PCRCG_CHECK_ARG(x && sums && y && (!res || ldr >= c) && (!res_sums || res));
-    const int c4 = c / 4;
     auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-    // the kernel's thread -> channel-group map needs the groups to tile 256 threads (or be a multiple of 256)
-    PCRCG_CHECK_ARG((c4 <= 256 ? 256 % c4 == 0 : c4 % 256 == 0) && ldx % 4 == 0 && ldy % 4 == 0 && al16(x) && al16(y) &&
-                    (!res || (ldr % 4 == 0 && al16(res))));
+    PCRCG_CHECK_ARG(instnorm_sums_ok(c, ldx, ldy, res ? ldr : 0) && al16(x) && al16(y) && (!res || al16(res)));
     NormJob one{x, static_cast<const double*>(sums), res, static_cast<const double*>(res_sums), y, nullptr, nullptr, n, count};
     return instnorm_apply_sums_multi(&one, 1, c, ldx, eps, ldr, slope, ldy, false, as_stream(stream));
 }

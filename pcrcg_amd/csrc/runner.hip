@@ -147,9 +147,7 @@ Stat stat_buffer(Ctx& c, const int* rows, int cols) {
 
 // widths the sums form of the normalisation kernel serves (its thread -> channel-group map)
 inline bool sums_apply_ok(const Mat& x, const Mat& y, const Mat* res) {
-    const int c4 = x.cols / 4;
-    return x.cols % 4 == 0 && x.cols >= 4 && (c4 <= 256 ? 256 % c4 == 0 : c4 % 256 == 0) && x.ld % 4 == 0 && y.ld % 4 == 0 &&
-           (!res || res->ld % 4 == 0);
+    return instnorm_sums_ok(x.cols, x.ld, y.ld, res ? res->ld : 0);
 }
 
 // (mean, rstd) of pair g's x: from the producing GEMM's partials when it left some, else by a pass over x

@@ -276,7 +276,7 @@ static std::vector<StreamScratch*>& scratch_registry() {
     static std::vector<StreamScratch*> all;       // (function-local: built before the first instance of any file)
     return all;
 }
-StreamScratch::StreamScratch() {
+StreamScratch::StreamScratch(bool cleared) : cleared_(cleared) {
     std::lock_guard<std::mutex> g(g_scratch_lock);
     scratch_registry().push_back(this);
 }
@@ -288,6 +288,11 @@ void* StreamScratch::get(hipStream_t st, size_t bytes, size_t slack) {
         if (b.p) (void)hipFree(b.p);
         b = Buf();
         if (hipMalloc(&b.p, bytes + slack) != hipSuccess) { b.p = nullptr; return nullptr; }
+        if (cleared_ && hipMemsetAsync(b.p, 0, bytes + slack, st) != hipSuccess) {
+            (void)hipFree(b.p);
+            b.p = nullptr;
+            return nullptr;
+        }
         b.bytes = bytes + slack;
     }
     return b.p;
@@ -323,11 +328,8 @@ int pcrcg_debug_set(const char* spec) {
 // a stale entry) or wants the memory back calls this with those streams DRAINED; the next deterministic call allocates anew.
 int pcrcg_debug_release(void) {
     PCRCG_CHECK_HIP(hipDeviceSynchronize());
-    {
-        std::lock_guard<std::mutex> g(pcrcg::g_scratch_lock);
-        for (pcrcg::StreamScratch* s : pcrcg::scratch_registry()) s->release();
-    }
-    pcrcg::trainops_release_det();
+    std::lock_guard<std::mutex> g(pcrcg::g_scratch_lock);
+    for (pcrcg::StreamScratch* s : pcrcg::scratch_registry()) s->release();
     return PCRCG_OK;
 }
 

@@ -26,23 +26,9 @@
 
 #include "gemm.h"
 #include "pcrcg_train.h"
+#include "trainops.h"
 
 namespace pcrcg {
-// trainops.hip
-int tr_scale_rows(const float* src, int ld_src, const float* s, float* dst, int rows, int cols, hipStream_t st);
-int tr_add_lrelu(const float* a, int lda, const float* b, int ldb, float slope, float* y, int ldy, int rows, int cols,
-                 hipStream_t st);
-int tr_add_lrelu_bwd(const float* y, int ldy, const float* dy, int ld_dy, float slope, float* ga, int lga, float* gb, int lgb,
-                     int rows, int cols, hipStream_t st);
-int tr_add2d(const float* src, int ld_src, float* dst, int ld_dst, int rows, int cols, hipStream_t st);
-int tr_bias_grad(const float* dy, int ld, int rows, int cols, float* db, hipStream_t st);
-int tr_l2norm_bwd(const float* x, int ldx, const float* dy, int ld_dy, float* dx, int ld_dx, int rows, int cols, hipStream_t st);
-int tr_sigmoid_bwd(const float* s, const float* ds, float* dx, int ld_dx, int rows, hipStream_t st);
-int tr_dot_acc(const float* a, const float* b, long n, float scale, float* out, hipStream_t st);
-bool instnorm_backward_sums_ok(const float* x, int n, int c, int ldx, const float* dy, int ld_dy, const float* dx, int ld_dx);
-int instnorm_backward_sums(const float* x, int n, int c, int ldx, const float* stats, const float* dy, int ld_dy, float slope,
-                           float* dx, int ld_dx, double* sums, hipStream_t st);
-
 namespace {
 
 // c = (op(a) * op(b)) * row_scale[m] + bias[n] as a descriptor: op = identity or transpose as in pcrcg_gemm_f32_ex
@@ -329,8 +315,7 @@ TT instnorm_lrelu(Tape& t, const TT& x, float slope, TT* into = nullptr, const d
     const size_t wsb = pcrcg_instnorm_ws_bytes(x.cols), bwb = pcrcg_instnorm_backward_ws_bytes(x.cols);
     void* ws = t.value_bytes(wsb);
     if (t.live()) {
-        const int c4 = x.cols / 4;
-        const bool tiles = x.cols % 4 == 0 && c4 >= 1 && (c4 <= 256 ? 256 % c4 == 0 : c4 % 256 == 0) && x.ld % 4 == 0 && y.ld % 4 == 0 &&
+        const bool tiles = instnorm_sums_ok(x.cols, x.ld, y.ld) &&
                            ((reinterpret_cast<uintptr_t>(x.p) | reinterpret_cast<uintptr_t>(y.p)) & 15) == 0;
         if (!sums && tiles && x.rows > 0) {
             // no sums from the producer (a product split over K, a row slice of a stacked tensor): ONE launch that leaves them

@@ -1,11 +1,10 @@
 // trainops.hip -- kernels of the training-side rows: loss labels and backward passes.
 // ABI: include/pcrcg_train.h.
-#include <map>
-#include <mutex>
+#include <type_traits>
 
 #include "argmax.h"
-#include "common.h"
 #include "pcrcg_train.h"
+#include "trainops.h"
 
 namespace pcrcg {
 namespace {
@@ -559,71 +558,66 @@ __global__ void __launch_bounds__(256) k_edge_bwd_apply(const float* __restrict_
     dctr[(long)r * c + ch] = acc;
 }
 
-}  // namespace
-}  // namespace pcrcg
-
-using namespace pcrcg;
-
-// ---- the deterministic mode's scratch (see FixAcc): one zeroed 64-bit buffer + one word per stream, grown on demand ----
-namespace {
-struct DetScratch { long long* acc = nullptr; size_t elems = 0; unsigned* word = nullptr; };
-std::mutex g_det_lock;
-std::map<hipStream_t, DetScratch> g_det;
+// ---- the host side of the deterministic accumulation (see FixAcc) -------------------------------------------------------
+// The scratch, per stream and grown on demand: the two magnitude words in its first 256 bytes, the 64-bit accumulators
+// behind them.  A new buffer comes zeroed (by a memset on the stream that asked); k_fix_flush leaves it zeroed after every use.
+StreamScratch g_fix_scratch(true);
+constexpr size_t kFixWords = 256;
+struct FView { const float* p = nullptr; long rows = 0; int cols = 0; long ld = 0; };   // rows x cols values, row r at p + r * ld
 // -> a FixAcc over a zeroed buffer of at least `elems` elements whose scale follows the largest |src| value (times the largest
-// |factor[r * factor_ld]|, r < factor_rows, when `factor` is given); NULL acc on failure
-int det_begin(hipStream_t st, size_t elems, const float* src, long rows, int cols, long ld, int fan_log2, FixAcc* out,
-              const float* factor = nullptr, long factor_rows = 0, long factor_ld = 1) {
-    DetScratch d;
-    {
-        std::lock_guard<std::mutex> g(g_det_lock);
-        DetScratch& slot = g_det[st];
-        if (slot.elems < elems) {
-            // (a debugging mode: synchronous allocation; the old buffer is idle once the stream has drained)
-            PCRCG_CHECK_HIP(hipStreamSynchronize(st));
-            if (slot.acc) (void)hipFree(slot.acc);
-            const size_t want = elems + elems / 4;
-            PCRCG_CHECK_HIP(hipMalloc(&slot.acc, want * sizeof(long long)));
-            PCRCG_CHECK_HIP(hipMemset(slot.acc, 0, want * sizeof(long long)));
-            slot.elems = want;
-        }
-        if (!slot.word) PCRCG_CHECK_HIP(hipMalloc(&slot.word, 256));
-        d = slot;
+// |factor| value when one is given)
+int det_begin(hipStream_t st, size_t elems, const FView& src, int fan_log2, const FView& factor, FixAcc* out) {
+    // (grown to a quarter more than asked: a slightly larger request does not drain the stream again)
+    char* buf = static_cast<char*>(g_fix_scratch.get(st, kFixWords + elems * sizeof(long long), elems / 4 * sizeof(long long)));
+    if (!buf) {
+        set_error("det_begin: StreamScratch::get failed for %zu fixed-point sums: no memory, or the stream failed", elems);
+        return PCRCG_ELAUNCH;
     }
-    PCRCG_CHECK_HIP(hipMemsetAsync(d.word, 0, 2 * sizeof(unsigned), st));
-    const long total = rows * cols;
-    long blocks = (total + 255) / 256;
-    if (blocks > 1024) blocks = 1024;
-    if (total > 0) hipLaunchKernelGGL(k_absmax_bits, dim3((unsigned)blocks), dim3(256), 0, st, src, rows, cols, ld, d.word);
-    if (factor && factor_rows > 0)
-        hipLaunchKernelGGL(k_absmax_bits, dim3((unsigned)((factor_rows + 255) / 256 < 1024 ? (factor_rows + 255) / 256 : 1024)),
-                           dim3(256), 0, st, factor, factor_rows, 1, factor_ld, d.word + 1);
+    unsigned* word = reinterpret_cast<unsigned*>(buf);
+    PCRCG_CHECK_HIP(hipMemsetAsync(word, 0, 2 * sizeof(unsigned), st));
+    auto absmax = [&](const FView& v, unsigned* to) {
+        const long total = v.rows * v.cols;
+        const long blocks = (total + 255) / 256 < 1024 ? (total + 255) / 256 : 1024;
+        if (v.p && total > 0) hipLaunchKernelGGL(k_absmax_bits, dim3((unsigned)blocks), dim3(256), 0, st, v.p, v.rows, v.cols, v.ld, to);
+    };
+    absmax(src, word);
+    absmax(factor, word + 1);
     PCRCG_CHECK_LAUNCH();
-    out->acc = d.acc;
-    out->maxbits = d.word;
+    out->acc = reinterpret_cast<long long*>(buf + kFixWords);
+    out->maxbits = word;
     out->fan_log2 = fan_log2;
-    out->factorbits = factor ? d.word + 1 : nullptr;
+    out->factorbits = factor.p ? word + 1 : nullptr;
     return PCRCG_OK;
 }
-}  // namespace
-namespace pcrcg {
-// pcrcg_debug_release(): the deterministic mode's fixed-point scratch of every stream (the caller has drained them)
-void trainops_release_det() {
-    std::lock_guard<std::mutex> g(g_det_lock);
-    for (auto& kv : g_det) {
-        if (kv.second.acc) (void)hipFree(kv.second.acc);
-        if (kv.second.word) (void)hipFree(kv.second.word);
-    }
-    g_det.clear();
-}
-}  // namespace pcrcg
-namespace {
 int det_end(hipStream_t st, const FixAcc& fx, float* dst, size_t elems) {
     hipLaunchKernelGGL(k_fix_flush, dim3((unsigned)((elems + 255) / 256)), dim3(256), 0, st, fx.acc, dst, (long)elems, fx);
     PCRCG_CHECK_LAUNCH();
     return PCRCG_OK;
 }
 const FixAcc kNoFix{nullptr, nullptr, 0, nullptr};
+
+// One scatter into dst [elems], in the mode the library is in.  launch(det, fx) enqueues the scatter kernel(s) instantiated
+// with decltype(det)::value: fp32 atomics onto dst (the default), or -- deterministic=1 -- fixed-point sums of the
+// contributions of `src` (each carrying at most 2^fan_log2 x the largest |factor|) that det_end then adds to dst.  Every
+// kernel's argument list is written once, for both modes.
+template <typename Launch>
+int scatter_launch(hipStream_t st, size_t elems, const FView& src, int fan_log2, const FView& factor, float* dst, Launch launch) {
+    if (debug_opts().deterministic) {
+        FixAcc fx;
+        PCRCG_PROPAGATE(det_begin(st, elems, src, fan_log2, factor, &fx));
+        launch(std::true_type(), fx);
+        PCRCG_CHECK_LAUNCH();
+        return det_end(st, fx, dst, elems);
+    }
+    launch(std::false_type(), kNoFix);
+    PCRCG_CHECK_LAUNCH();
+    return PCRCG_OK;
+}
+
 }  // namespace
+}  // namespace pcrcg
+
+using namespace pcrcg;
 
 extern "C" size_t pcrcg_feature_argmax_ws_bytes(int n) { return carve_bytes((size_t)(n > 0 ? n : 1), 8); }
 
@@ -676,26 +670,21 @@ extern "C" int pcrcg_kpconv_backward_dx(const float* q_pts, int nq, const float*
     PCRCG_CHECK_ARG(q_pts && s_pts && idx && d_wf && kp && dx);
     const int nchunk = (cin + 63) / 64;
     const long items = (long)nq * nchunk;
-    if (debug_opts().deterministic) {       // |contribution| <= 15 max|d_wf| (influence weights <= 1), at most nq of them per element
-        FixAcc fx;
-        PCRCG_PROPAGATE(det_begin(as_stream(stream), (size_t)ns * cin, d_wf, nq, PCRCG_KPOINTS * cin, (long)PCRCG_KPOINTS * cin, 22, &fx));
-        if (debug_opts().bwd_mfma)
-            hipLaunchKernelGGL(k_kpconv_bwd_dx_mfma<true>, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, as_stream(stream), q_pts,
-                               nq, s_pts, ns, reinterpret_cast<const long long*>(idx), h, ld_idx, d_wf, cin, kp, extent, dx, nchunk, fx);
+    const dim3 grid((unsigned)((items + 3) / 4));
+    const long long* ix = reinterpret_cast<const long long*>(idx);
+    const bool mfma = debug_opts().bwd_mfma != 0;
+    hipStream_t st = as_stream(stream);
+    // |contribution| <= 15 max|d_wf| (influence weights <= 1), at most nq of them per element
+    return scatter_launch(st, (size_t)ns * cin, {d_wf, nq, PCRCG_KPOINTS * cin, (long)PCRCG_KPOINTS * cin}, 22, {}, dx,
+                          [&](auto det, const FixAcc& fx) {
+        constexpr bool DET = decltype(det)::value;
+        if (mfma)
+            hipLaunchKernelGGL(k_kpconv_bwd_dx_mfma<DET>, grid, dim3(256), 0, st, q_pts, nq, s_pts, ns, ix, h, ld_idx, d_wf, cin, kp,
+                               extent, dx, nchunk, fx);
         else
-            hipLaunchKernelGGL(k_kpconv_bwd_dx<true>, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, as_stream(stream), q_pts, nq,
-                               s_pts, ns, reinterpret_cast<const long long*>(idx), h, ld_idx, d_wf, cin, kp, extent, dx, nchunk, fx);
-        PCRCG_CHECK_LAUNCH();
-        return det_end(as_stream(stream), fx, dx, (size_t)ns * cin);
-    }
-    if (debug_opts().bwd_mfma)
-        hipLaunchKernelGGL(k_kpconv_bwd_dx_mfma<false>, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, as_stream(stream), q_pts, nq,
-                           s_pts, ns, reinterpret_cast<const long long*>(idx), h, ld_idx, d_wf, cin, kp, extent, dx, nchunk, kNoFix);
-    else
-        hipLaunchKernelGGL(k_kpconv_bwd_dx<false>, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, as_stream(stream), q_pts, nq,
-                           s_pts, ns, reinterpret_cast<const long long*>(idx), h, ld_idx, d_wf, cin, kp, extent, dx, nchunk, kNoFix);
-    PCRCG_CHECK_LAUNCH();
-    return PCRCG_OK;
+            hipLaunchKernelGGL(k_kpconv_bwd_dx<DET>, grid, dim3(256), 0, st, q_pts, nq, s_pts, ns, ix, h, ld_idx, d_wf, cin, kp, extent,
+                               dx, nchunk, fx);
+    });
 }
 
 extern "C" int pcrcg_gather_max_backward(const float* x, int ns, int c, const int64_t* idx, int nq, int h, int ld_idx,
@@ -708,18 +697,12 @@ extern "C" int pcrcg_gather_max_backward(const float* x, int ns, int c, const in
     const long items = (long)nq * nchunk;
     const dim3 grid((unsigned)((items + 3) / 4));
     const long long* ix = reinterpret_cast<const long long*>(idx);
-    if (debug_opts().deterministic) {
-        FixAcc fx;
-        PCRCG_PROPAGATE(det_begin(as_stream(stream), (size_t)ns * c, dy, nq, c, c, 20, &fx));
-        if (vec) hipLaunchKernelGGL(k_gather_max_bwd4<true>, grid, dim3(256), 0, as_stream(stream), x, ns, c, ix, nq, h, ld_idx, y, dy, dx, nchunk, fx);
-        else hipLaunchKernelGGL(k_gather_max_bwd<true>, grid, dim3(256), 0, as_stream(stream), x, ns, c, ix, nq, h, ld_idx, y, dy, dx, nchunk, fx);
-        PCRCG_CHECK_LAUNCH();
-        return det_end(as_stream(stream), fx, dx, (size_t)ns * c);
-    }
-    if (vec) hipLaunchKernelGGL(k_gather_max_bwd4<false>, grid, dim3(256), 0, as_stream(stream), x, ns, c, ix, nq, h, ld_idx, y, dy, dx, nchunk, kNoFix);
-    else hipLaunchKernelGGL(k_gather_max_bwd<false>, grid, dim3(256), 0, as_stream(stream), x, ns, c, ix, nq, h, ld_idx, y, dy, dx, nchunk, kNoFix);
-    PCRCG_CHECK_LAUNCH();
-    return PCRCG_OK;
+    hipStream_t st = as_stream(stream);
+    return scatter_launch(st, (size_t)ns * c, {dy, nq, c, c}, 20, {}, dx, [&](auto det, const FixAcc& fx) {
+        constexpr bool DET = decltype(det)::value;
+        if (vec) hipLaunchKernelGGL(k_gather_max_bwd4<DET>, grid, dim3(256), 0, st, x, ns, c, ix, nq, h, ld_idx, y, dy, dx, nchunk, fx);
+        else hipLaunchKernelGGL(k_gather_max_bwd<DET>, grid, dim3(256), 0, st, x, ns, c, ix, nq, h, ld_idx, y, dy, dx, nchunk, fx);
+    });
 }
 
 extern "C" int pcrcg_gather_first_backward(const float* dy, int ld_dy, int c, const int64_t* idx, int nq, int ld_idx,
@@ -727,18 +710,11 @@ extern "C" int pcrcg_gather_first_backward(const float* dy, int ld_dy, int c, co
     PCRCG_CHECK_ARG(c >= 1 && nq >= 0 && ld_idx >= 1 && ld_dy >= c && ns >= 0);
     if (nq == 0) return PCRCG_OK;
     PCRCG_CHECK_ARG(dy && idx && dx);
-    if (debug_opts().deterministic) {
-        FixAcc fx;
-        PCRCG_PROPAGATE(det_begin(as_stream(stream), (size_t)ns * c, dy, nq, c, ld_dy, 20, &fx));
-        hipLaunchKernelGGL(k_gather_first_bwd<true>, dim3((nq + 3) / 4), dim3(256), 0, as_stream(stream), dy, ld_dy, c,
+    hipStream_t st = as_stream(stream);
+    return scatter_launch(st, (size_t)ns * c, {dy, nq, c, ld_dy}, 20, {}, dx, [&](auto det, const FixAcc& fx) {
+        hipLaunchKernelGGL(k_gather_first_bwd<decltype(det)::value>, dim3((nq + 3) / 4), dim3(256), 0, st, dy, ld_dy, c,
                            reinterpret_cast<const long long*>(idx), nq, ld_idx, ns, dx, fx);
-        PCRCG_CHECK_LAUNCH();
-        return det_end(as_stream(stream), fx, dx, (size_t)ns * c);
-    }
-    hipLaunchKernelGGL(k_gather_first_bwd<false>, dim3((nq + 3) / 4), dim3(256), 0, as_stream(stream), dy, ld_dy, c,
-                       reinterpret_cast<const long long*>(idx), nq, ld_idx, ns, dx, kNoFix);
-    PCRCG_CHECK_LAUNCH();
-    return PCRCG_OK;
+    });
 }
 
 extern "C" size_t pcrcg_instnorm_backward_ws_bytes(int c) {
@@ -778,8 +754,7 @@ extern "C" int pcrcg_instnorm_backward(const float* x, int n, int c, int ldx, co
 }
 
 namespace pcrcg {
-// InstanceNorm + LeakyReLU backward in TWO launches for tensors of few row chunks: `sums` is a ZEROED [2][c] fp64 buffer
-// (the train tape keeps it in its gradient region, which one memset clears) that the statistics kernel's workgroups add to
+// InstanceNorm + LeakyReLU backward in two launches (trainops.h)
 bool instnorm_backward_sums_ok(const float* x, int n, int c, int ldx, const float* dy, int ld_dy, const float* dx, int ld_dx) {
     return !debug_opts().deterministic && n >= 1 && n <= 32 * 32 && c % 4 == 0 && ldx % 4 == 0 && ld_dy % 4 == 0 && ld_dx % 4 == 0 &&
            ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(dx)) & 15) == 0;
@@ -829,25 +804,19 @@ extern "C" int pcrcg_edgeconv_backward(const float* ctr, const float* nbr, const
     if (det) gx = 1;      // one workgroup per channel block: every sum receives exactly one add
     hipLaunchKernelGGL(k_edge_bwd_sums, dim3(gx, (c + 63) / 64), dim3(256), 0, st, ctr, nbr, idx, n, k, c, stats, dy, slope,
                        sums);
+    int fan = 36;
     if (det) {
         // |de| <= rstd (|dn| + |S1/E| + |n| |S2/E|) <= max(rstd) max|dy| (2 + sqrt(E)) (|n| <= sqrt(E), mean|n| <= 1), at most
         // E = n k edges per neighbour row: E (2 + sqrt(E)) < 2^36 for E < 2^23 (more edges widen the fan).  The scale follows
         // max|dy| x max(rstd), the scale of the result: from max|dy| alone the resolution relative to dnbr was 2^-26 / rstd
         // (1e-3 at a feature std of 1e4).
         const double edges = (double)n * (double)k;
-        int fan = 36;
         while (edges * (2.0 + sqrt(edges)) >= ldexp(1.0, fan)) ++fan;
-        FixAcc fx;
-        PCRCG_PROPAGATE(det_begin(st, (size_t)n * c, dy, n, c, c, fan, &fx, stats + 1, c, 2));
-        hipLaunchKernelGGL(k_edge_bwd_apply<true>, dim3((n + 3) / 4, (c + 63) / 64), dim3(256), 0, st, ctr, nbr, idx, n, k, c, stats,
-                           dy, slope, sums, dctr, dnbr, fx);
-        PCRCG_CHECK_LAUNCH();
-        return det_end(st, fx, dnbr, (size_t)n * c);
     }
-    hipLaunchKernelGGL(k_edge_bwd_apply<false>, dim3((n + 3) / 4, (c + 63) / 64), dim3(256), 0, st, ctr, nbr, idx, n, k, c, stats,
-                       dy, slope, sums, dctr, dnbr, kNoFix);
-    PCRCG_CHECK_LAUNCH();
-    return PCRCG_OK;
+    return scatter_launch(st, (size_t)n * c, {dy, n, c, c}, fan, {stats + 1, c, 1, 2}, dnbr, [&](auto det, const FixAcc& fx) {
+        hipLaunchKernelGGL(k_edge_bwd_apply<decltype(det)::value>, dim3((n + 3) / 4, (c + 63) / 64), dim3(256), 0, st, ctr, nbr, idx, n,
+                           k, c, stats, dy, slope, sums, dctr, dnbr, fx);
+    });
 }
 
 // ---- whole-op entry points (the exports SURVEY.md 8b recommends for a C caller) ---------------------

@@ -12,7 +12,7 @@ void set_error(const char*, ...) {}
 const DebugOpts& debug_opts() { static DebugOpts d; return d; }
 KpProfScope::KpProfScope(hipStream_t s, int, int, int, int, int) : st(s), a(nullptr), b(nullptr), on(false) {}
 KpProfScope::~KpProfScope() {}
-StreamScratch::StreamScratch() {}
+StreamScratch::StreamScratch(bool) {}
 void* StreamScratch::get(hipStream_t, size_t, size_t) { return nullptr; }
 void StreamScratch::release() {}
 }  // namespace pcrcg

@@ -70,37 +70,34 @@ def _c1_train_inputs(cfg, dev):
     return collate_fn_descriptor([item], cfg, synthetic.LIMITS["C1"], device=dev)
 
 
-def test_two_c1_train_steps_are_bit_identical(cuda):
-    """Forward with tape + MetricLoss + backward + SGD on the C1 pair, full-width model, twice from the same start: under
-    deterministic=1 every loss value, every parameter gradient of the first step and every parameter after two steps agree
-    bit for bit (split-K-free products, stored-partial statistics, fixed-point scatter sums, ordered loss reductions), and
-    the gradients stay within the usual distance of the default path's."""
+def _c1_two_steps(cuda, spec):
+    """Two train steps on the C1 pair from a fixed start under pcrcg_debug_set(spec) -> the loss values of both steps, the
+    first step's parameter gradients and the parameters after the second."""
     from pcrcg_amd.config import Config
     from pcrcg_amd.loss import MetricLoss
     from pcrcg_amd.trainer import Trainer
     loss_cfg = Config(pos_margin=0.1, neg_margin=1.4, pos_radius=0.0375, safe_radius=0.1, matchability_radius=0.05, max_points=256)
     cfg = indoor_config()
+    torch.manual_seed(0)
+    np.random.seed(0)
+    net = KPFCNN(cfg).to(cuda)
+    trainer = Trainer(net, MetricLoss(loss_cfg), lr=0.005, momentum=0.98)
+    inputs = _c1_train_inputs(cfg, cuda)
+    try:
+        _debug(spec)
+        np.random.seed(3)
+        stats = trainer.inference_one_batch(inputs, "train")          # forward + loss + backward, gradients kept
+        grads = {k: p.grad.detach().clone() for k, p in net.named_parameters() if p.grad is not None}
+        trainer.optimizer_step()
+        np.random.seed(3)
+        stats2 = trainer.train_step(inputs)
+        torch.cuda.synchronize()
+    finally:
+        _debug(None)
+    return stats, stats2, grads, {k: v.detach().clone() for k, v in net.state_dict().items()}
 
-    def run(spec):
-        torch.manual_seed(0)
-        np.random.seed(0)
-        net = KPFCNN(cfg).to(cuda)
-        trainer = Trainer(net, MetricLoss(loss_cfg), lr=0.005, momentum=0.98)
-        inputs = _c1_train_inputs(cfg, cuda)
-        try:
-            _debug(spec)
-            np.random.seed(3)
-            stats = trainer.inference_one_batch(inputs, "train")          # forward + loss + backward, gradients kept
-            grads = {k: p.grad.detach().clone() for k, p in net.named_parameters() if p.grad is not None}
-            trainer.optimizer_step()
-            np.random.seed(3)
-            stats2 = trainer.train_step(inputs)
-            torch.cuda.synchronize()
-        finally:
-            _debug(None)
-        return stats, stats2, grads, {k: v.detach().clone() for k, v in net.state_dict().items()}
 
-    a, b, ref = run("deterministic=1"), run("deterministic=1"), run(None)
+def _assert_same_bits(a, b):
     for k in ("circle_loss", "overlap_loss", "saliency_loss", "total_loss"):
         assert a[0][k] == b[0][k] and a[1][k] == b[1][k], k
     assert a[2].keys() == b[2].keys() and len(a[2]) > 50
@@ -108,6 +105,23 @@ def test_two_c1_train_steps_are_bit_identical(cuda):
         assert torch.equal(a[2][k], b[2][k]), k
     for k in a[3]:
         assert torch.equal(a[3][k], b[3][k]), k
+
+
+def test_c1_train_steps_after_debug_release_are_bit_identical(cuda):
+    """pcrcg_debug_release() frees the mode's per-stream scratch; the next deterministic steps allocate it anew -- the scatter
+    kernels' fixed-point sums must come zeroed -- and give the bits the steps before the release gave."""
+    a = _c1_two_steps(cuda, "deterministic=1")
+    _lib.check(_lib.lib().pcrcg_debug_release(), "pcrcg_debug_release")
+    _assert_same_bits(a, _c1_two_steps(cuda, "deterministic=1"))
+
+
+def test_two_c1_train_steps_are_bit_identical(cuda):
+    """Forward with tape + MetricLoss + backward + SGD on the C1 pair, full-width model, twice from the same start: under
+    deterministic=1 every loss value, every parameter gradient of the first step and every parameter after two steps agree
+    bit for bit (split-K-free products, stored-partial statistics, fixed-point scatter sums, ordered loss reductions), and
+    the gradients stay within the usual distance of the default path's."""
+    a, b, ref = _c1_two_steps(cuda, "deterministic=1"), _c1_two_steps(cuda, "deterministic=1"), _c1_two_steps(cuda, None)
+    _assert_same_bits(a, b)
     # the same gradients as the default arithmetic up to summation order
     # The same gradients as the default arithmetic up to summation order.  The step's gradients are ill-conditioned in fp32
     # (tests/test_scale_gpu.py: the fp32 CPU oracle itself sits up to 7.7e-2 from a float64 run on single tensors), so the
