@@ -19,6 +19,11 @@ namespace pcrcg {
 namespace {
 
 constexpr int GMAX = 4;   // fragment pairs one call can carry (pcrcg_kpfcnn_forward_group)
+// c.G <= GMAX everywhere below (validate_group; the two stacking sites double it only while 2 * c.G <= GMAX), and every
+// multi-cloud kernel of common.h takes that many: all clouds of a call always fit ONE launch of them, no per-cloud loop for the
+// count's sake.  The per-cloud paths that remain are for what those kernels refuse (alignment, widths, arithmetic mode).
+static_assert(GMAX <= 4, "instnorm_apply_sums_multi, instnorm_colsums_multi, gather_max_multi, copy2d_multi, heads_multi, "
+                         "edgeconv_rows_multi and attention_mfma_multi (common.h) take up to four clouds");
 
 // Row-major fp32 matrix view -- one per fragment pair of the call (same width and leading dimension, own rows).  With
 // several pairs every operator below runs its per-pair kernels once per pair and its weight products ONCE for all pairs (GemmGroup):
@@ -97,6 +102,8 @@ struct Ctx {
     void check(int r) { if (r != PCRCG_OK && rc == PCRCG_OK) rc = r; }
     // several pairs in one launch: only with the split-bf16 arithmetic (PCRCG_GEMM_MODE=0 runs the products pair by pair)
     bool paired() const { return G >= 2 && gemm_split_terms_on(); }
+    // a piece of the forward over twice the clouds (stacked() below); what it allocates stays allocated
+    template <class F> Mat twice(F&& f) { G *= 2; const Mat r = f(); G /= 2; return r; }
 };
 
 inline int pad4(int v) { return (v + 3) & ~3; }
@@ -115,14 +122,30 @@ inline Mat rows(const Mat& m, const int* r0, const int* n) {
     }
     return r;
 }
+// The two clouds of every pair as 2 * G0 independent clouds, [a of every pair | b of every pair], and either half of such a matrix
+inline Mat stacked(const Mat& a, const Mat& b, int G0) {
+    Mat m = a;
+    for (int g = 0; g < G0; ++g) { m.p[G0 + g] = b.p[g]; m.rows[G0 + g] = b.rows[g]; }
+    return m;
+}
+inline Mat half(const Mat& m, int which, int G0) {
+    Mat r = m;
+    for (int g = 0; g < GMAX; ++g) {
+        r.p[g] = g < G0 ? m.p[which * G0 + g] : nullptr;
+        r.rows[g] = g < G0 ? m.rows[which * G0 + g] : 0;
+    }
+    return r;
+}
 
 // A GEMM output together with the InstanceNorm column partials its epilogue may have produced (per pair).
 struct Stat {
-    void* partials[GMAX] = {};                // [2][cols][chunks] fp64 partials, valid when chunks > 0; or, when `sums`,
-                                                 // zeroed [2][cols] fp64 accumulators that hold the column sums when chunks == -1
+    void* partials[GMAX] = {};                // [2][cols][chunks] fp64 partials; or, when `sums`, zeroed [2][cols] fp64 accumulators
     size_t bytes = 0;
-    int chunks[GMAX] = {};
+    int chunks[GMAX] = {};                    // what the producer left (GemmCall::h_chunks): SUMS, NOTHING, or > 0 chunks of partials
     bool sums = false;
+    static constexpr int SUMS = -1, NOTHING = 0;
+    bool has_sums(int g) const { return chunks[g] == SUMS; }        // the accumulators hold the column sums
+    bool nothing(int g) const { return chunks[g] == NOTHING; }
 };
 
 // The GEMM epilogue adds its output's column sums into accumulators from the zero arena with fp64 atomics -- one pair per
@@ -152,10 +175,9 @@ inline bool sums_apply_ok(const Mat& x, const Mat& y, const Mat* res) {
 
 // (mean, rstd) of pair g's x: from the producing GEMM's partials when it left some, else by a pass over x
 void col_stats(Ctx& c, const Mat& x, int g, const Stat* s, float* stats, void* ws, size_t wsb) {
-    if (s && s->chunks[g] == -1)      // column sums: the finishing kernel reads them as one chunk per column
-        c.check(pcrcg_instnorm_stats_from_partials(s->partials[g], 1, x.cols, (double)x.rows[g], 1e-5f, stats, c.st));
-    else if (s && s->chunks[g] > 0)
-        c.check(pcrcg_instnorm_stats_from_partials(s->partials[g], s->chunks[g], x.cols, (double)x.rows[g], 1e-5f, stats, c.st));
+    if (s && !s->nothing(g))          // (column sums: the finishing kernel reads them as one chunk per column)
+        c.check(pcrcg_instnorm_stats_from_partials(s->partials[g], s->has_sums(g) ? 1 : s->chunks[g], x.cols, (double)x.rows[g], 1e-5f,
+                                                   stats, c.st));
     else
         c.check(pcrcg_instnorm_stats(x.p[g], x.rows[g], x.cols, x.ld, 1e-5f, stats, ws, wsb, c.st));
 }
@@ -165,24 +187,53 @@ void fill_sums(Ctx& c, const Mat& x, Stat* xs) {
     if (!c.live() || !xs || !xs->sums) return;
     {   // the pairs whose product left nothing: one launch for all of them
         const float* xp[GMAX]; double* sp[GMAX]; int np[GMAX]; int idx[GMAX]; int cnt = 0;
-        for (int g = 0; g < c.G && cnt < 4; ++g)
-            if (xs->chunks[g] == 0 && x.rows[g] >= 1) { xp[cnt] = x.p[g]; sp[cnt] = static_cast<double*>(xs->partials[g]); np[cnt] = x.rows[g]; idx[cnt++] = g; }
+        for (int g = 0; g < c.G; ++g)
+            if (xs->nothing(g) && x.rows[g] >= 1) { xp[cnt] = x.p[g]; sp[cnt] = static_cast<double*>(xs->partials[g]); np[cnt] = x.rows[g]; idx[cnt++] = g; }
         if (cnt >= 2) {
             c.check(instnorm_colsums_multi(xp, sp, np, cnt, x.cols, x.ld, c.st));
-            for (int i = 0; i < cnt; ++i) xs->chunks[idx[i]] = -1;
+            for (int i = 0; i < cnt; ++i) xs->chunks[idx[i]] = Stat::SUMS;
         }
     }
     for (int g = 0; g < c.G; ++g)
-        if (xs->chunks[g] == 0) {
+        if (xs->nothing(g)) {
             c.check(pcrcg_instnorm_colsums(x.p[g], x.rows[g], x.cols, x.ld, xs->partials[g], c.st));
-            xs->chunks[g] = -1;
+            xs->chunks[g] = Stat::SUMS;
         }
 }
 inline bool all_sums(const Ctx& c, const Stat* s) {
     if (!s) return false;
     for (int g = 0; g < c.G; ++g)
-        if (s->chunks[g] != -1) return false;
+        if (!s->has_sums(g)) return false;
     return true;
+}
+
+// The sums form of the normalisation (instnorm_apply_sums_multi) for all clouds of the call: y = lrelu(IN(x) [+ IN(res) | + res])
+// with x's statistics in sums[g] (res_sums: res is normalised too).  `aligned`: every base is 16-byte aligned, which the
+// kernel's float4 accesses need.  Callers with other row counts or the pack form edit the jobs.
+struct NormJobs {
+    NormJob j[GMAX];
+    bool aligned = true;
+};
+NormJobs norm_jobs(const Ctx& c, const Mat& x, void* const* sums, const Mat& y, const Mat* res = nullptr, void* const* res_sums = nullptr) {
+    NormJobs nj;
+    for (int g = 0; g < c.G; ++g) {
+        const float* r = res ? res->p[g] : nullptr;
+        nj.j[g] = NormJob{x.p[g], static_cast<const double*>(sums[g]), r, res_sums ? static_cast<const double*>(res_sums[g]) : nullptr,
+                          y.p[g], nullptr, nullptr, x.rows[g], (double)(x.rows[g] > 0 ? x.rows[g] : 1)};
+        nj.aligned = nj.aligned && ((reinterpret_cast<uintptr_t>(x.p[g]) | reinterpret_cast<uintptr_t>(y.p[g]) | reinterpret_cast<uintptr_t>(r)) & 15) == 0;
+    }
+    return nj;
+}
+// all clouds in ONE launch (a launch per cloud cost the stream ~5 us of queue time each), else the single-tensor entry per cloud
+void apply_sums(Ctx& c, const NormJob* jobs, bool one_launch, int cols, int ldx, int ldr, float slope, int ldy) {
+    if (one_launch) {
+        c.check(instnorm_apply_sums_multi(jobs, c.G, cols, ldx, 1e-5f, ldr, slope, ldy, false, c.st));
+        return;
+    }
+    for (int g = 0; g < c.G; ++g) {
+        const NormJob& j = jobs[g];
+        c.check(pcrcg_instnorm_apply_sums(j.x, j.n, cols, ldx, j.sums, j.count, 1e-5f, j.res, ldr, j.res_sums, slope, j.y, ldy, c.st));
+    }
 }
 
 // y = lrelu(IN(x) [+ IN(res) | + res], slope)
@@ -191,24 +242,8 @@ void norm_act(Ctx& c, const Mat& x, float slope, const Mat& y, Stat* xs = nullpt
     fill_sums(c, x, xs);
     if (res && norm_res) fill_sums(c, *res, rs);
     if (c.live() && all_sums(c, xs) && (!res || !norm_res || all_sums(c, rs)) && sums_apply_ok(x, y, res)) {
-        // every pair of the call in ONE launch (round 5: a launch per pair cost the stream ~5 us of queue time each)
-        NormJob jobs[GMAX];
-        bool al = true;
-        for (int g = 0; g < c.G; ++g) {
-            jobs[g] = NormJob{x.p[g], static_cast<const double*>(xs->partials[g]), res ? res->p[g] : nullptr,
-                              (res && norm_res) ? static_cast<const double*>(rs->partials[g]) : nullptr, y.p[g], nullptr, nullptr,
-                              x.rows[g], (double)(x.rows[g] > 0 ? x.rows[g] : 1)};
-            al = al && ((reinterpret_cast<uintptr_t>(x.p[g]) | reinterpret_cast<uintptr_t>(y.p[g]) |
-                         reinterpret_cast<uintptr_t>(res ? res->p[g] : nullptr)) & 15) == 0;
-        }
-        if (al && c.G <= 4) {
-            c.check(instnorm_apply_sums_multi(jobs, c.G, x.cols, x.ld, 1e-5f, res ? res->ld : 0, slope, y.ld, false, c.st));
-            return;
-        }
-        for (int g = 0; g < c.G; ++g)
-            c.check(pcrcg_instnorm_apply_sums(x.p[g], x.rows[g], x.cols, x.ld, xs->partials[g], (double)x.rows[g], 1e-5f,
-                                              res ? res->p[g] : nullptr, res ? res->ld : 0,
-                                              (res && norm_res) ? rs->partials[g] : nullptr, slope, y.p[g], y.ld, c.st));
+        const NormJobs nj = norm_jobs(c, x, xs->partials, y, res, (res && norm_res) ? rs->partials : nullptr);
+        apply_sums(c, nj.j, nj.aligned, x.cols, x.ld, res ? res->ld : 0, slope, y.ld);
         return;
     }
     const size_t m = c.mark();
@@ -339,6 +374,15 @@ const float* kp_weight(const pcrcg_block& blk, const Mat& x) {
     return (blk.kp_w_pad && blk.cin_pad > 0 && kp_cin(blk, x) == blk.cin_pad) ? blk.kp_w_pad : blk.kp_w;
 }
 
+// length of a wf row (the contraction's K).  cin = 1 (the first layer of the geometry-only configurations) with a K-contiguous
+// weight copy: that copy has rows of 16 floats (the 16th zero, pcrcg_amd/runner.py) and the gather kernel writes wf in rows of
+// 16 -- whole k-steps, so the contraction is the grouped fp16 A B^T product with the statistics in its epilogue like every other
+// layer's (round 6; before: one k-major six-product launch per pair and a column-sum pass over its output)
+int kp_k(const pcrcg_block& blk, const Mat& x) {
+    const int cin = kp_cin(blk, x);
+    return (cin == 1 && blk.kp_wt) ? 16 : PCRCG_KPOINTS * cin;
+}
+
 void kpconv(Ctx& c, const Batches& B, const pcrcg_block& blk, const Mat& x, const Mat& y, Stat* st = nullptr,
             void* const* packed_ws = nullptr) {
     const int l = blk.layer;
@@ -374,13 +418,8 @@ void kpconv(Ctx& c, const Batches& B, const pcrcg_block& blk, const Mat& x, cons
         wsb[g] = pcrcg_kpconv_ws_bytes(ns[g]);
         ws[g] = (packed_ws && packed_ws[g]) ? packed_ws[g] : c.raw(wsb[g]);
     }
-    // cin = 1 (the first layer of the geometry-only configurations) with a K-contiguous weight copy: that copy has rows of 16
-    // floats (the 16th zero, pcrcg_amd/runner.py) and the gather kernel writes wf in rows of 16 -- whole k-steps, so the
-    // contraction is the grouped fp16 A B^T product with the statistics in its epilogue like every other layer's (round 6;
-    // before: one k-major six-product launch per pair and a column-sum pass over its output)
-    const bool c1_16 = cin == 1 && blk.kp_wt != nullptr;
     const float* const kp_wt = blk.kp_wt;     // (cin = 1: the copy is the 16-float form or nothing)
-    const int kk = c1_16 ? 16 : PCRCG_KPOINTS * cin;
+    const int kk = kp_k(blk, x);
     // bf16 feature storage (pcrcg_model.feature_bf16): the gathers read a bf16 copy of x and wf is bf16 in HBM -- half
     // the bytes of the two streams that bound the encoder; the contraction takes wf as the (single-term) bf16 operand
     // against the exact three-term split of the fp32 weights, fp32 accumulate and fp32 output.
@@ -410,18 +449,12 @@ void kpconv(Ctx& c, const Batches& B, const pcrcg_block& blk, const Mat& x, cons
     Mat wf = c.mat(nq, kk);
     if (c.live()) {
         for (int g = 0; g < c.G; ++g) {
-            const pcrcg_batch& b = *B.b[g];
-            if (c1_16)
-                c.check(kpconv_aggregate_rows(q[g], nq[g], b.points[l], ns[g], tab[g]->idx, tab[g]->cols, tab[g]->ld, xin.p[g], cin,
-                                              blk.kp, blk.extent, wf.p[g], inv_n[g], ws[g], wsb[g], c.st, /*pack=*/true,
-                                              /*stream_out=*/true, 16));
-            else if (packed_ws && packed_ws[g] && xin.p[g] == x.p[g])
-                c.check(kpconv_aggregate_rows(q[g], nq[g], b.points[l], ns[g], tab[g]->idx, tab[g]->cols, tab[g]->ld, xin.p[g], cin,
-                                              blk.kp, blk.extent, wf.p[g], inv_n[g], ws[g], wsb[g], c.st, /*pack=*/false,
-                                              /*stream_out=*/true));
-            else
-                c.check(pcrcg_kpconv_aggregate(q[g], nq[g], b.points[l], ns[g], tab[g]->idx, tab[g]->cols, tab[g]->ld, xin.p[g], cin,
-                                               blk.kp, blk.extent, wf.p[g], inv_n[g], ws[g], wsb[g], c.st));
+            // (pcrcg_kpconv_aggregate is this call with pack = true; the support records are there already when the
+            // normalisation that wrote x packed them, norm_act_pack)
+            const bool packed = kk != 16 && packed_ws && packed_ws[g] && xin.p[g] == x.p[g];
+            c.check(kpconv_aggregate_rows(q[g], nq[g], B.b[g]->points[l], ns[g], tab[g]->idx, tab[g]->cols, tab[g]->ld, xin.p[g], cin,
+                                          blk.kp, blk.extent, wf.p[g], inv_n[g], ws[g], wsb[g], c.st, /*pack=*/!packed,
+                                          /*stream_out=*/true, /*c1_ld=*/kk == 16 ? 16 : 0));
         }
         // contraction wf @ W: against the K-contiguous copy wt [cout, 15*cin] when the descriptor carries one
         // (C = A * B^T form: both operands k-contiguous, the form the split-bf16 GEMM is built for).
@@ -438,11 +471,6 @@ void kpconv(Ctx& c, const Batches& B, const pcrcg_block& blk, const Mat& x, cons
                                                 (st && !st->sums) ? &st->chunks[g] : nullptr, c.st));
     }
     c.release(m);
-}
-
-// length of a wf row (the contraction's K)
-int kp_k(const pcrcg_block& blk, const Mat& x) {
-    return (x.cols == 1 && blk.kp_wt) ? 16 : PCRCG_KPOINTS * kp_cin(blk, x);
 }
 
 void out_rows(const Ctx& c, const Batches& B, const pcrcg_block& blk, int* rows) {
@@ -475,17 +503,16 @@ bool norm_act_pack(Ctx& c, const Batches& B, int layer, const Mat& t, float slop
     const size_t wsb = pcrcg_instnorm_ws_bytes(t.cols);
     void* ws = c.raw(wsb);
     fill_sums(c, t, ts);              // a split-K product left nothing: one pass into the accumulators
-    if (c.live() && all_sums(c, ts) && c.G <= 4) {          // every pair of the call in one launch
-        NormJob jobs[GMAX];
-        bool ok = true;
+    if (c.live() && all_sums(c, ts)) {          // every pair of the call in one launch
+        NormJobs nj = norm_jobs(c, t, ts->partials, u);
+        bool ok = nj.aligned;
         for (int g = 0; g < c.G; ++g) {
-            float4* pk = kpconv_pk_ptr(kp_ws[g], kp_ws_bytes[g], t.rows[g]);
-            ok = ok && pk != nullptr && ((reinterpret_cast<uintptr_t>(t.p[g]) | reinterpret_cast<uintptr_t>(u.p[g])) & 15) == 0;
-            jobs[g] = NormJob{t.p[g], static_cast<const double*>(ts->partials[g]), nullptr, nullptr, u.p[g], B.b[g]->points[layer], pk,
-                              t.rows[g], (double)(t.rows[g] > 0 ? t.rows[g] : 1)};
+            nj.j[g].s_pts = B.b[g]->points[layer];
+            nj.j[g].pk = kpconv_pk_ptr(kp_ws[g], kp_ws_bytes[g], t.rows[g]);
+            ok = ok && nj.j[g].pk != nullptr;
         }
         if (ok) {
-            c.check(instnorm_apply_sums_multi(jobs, c.G, t.cols, t.ld, 1e-5f, 0, slope, u.ld, true, c.st));
+            c.check(instnorm_apply_sums_multi(nj.j, c.G, t.cols, t.ld, 1e-5f, 0, slope, u.ld, true, c.st));
             c.release(m);
             return true;
         }
@@ -495,7 +522,7 @@ bool norm_act_pack(Ctx& c, const Batches& B, int layer, const Mat& t, float slop
             const float* s_pts = B.b[g]->points[layer];
             float4* pk = kpconv_pk_ptr(kp_ws[g], kp_ws_bytes[g], t.rows[g]);
             if (!pk) c.check(PCRCG_EWORKSPACE);
-            else if (ts && ts->chunks[g] == -1)
+            else if (ts && ts->has_sums(g))
                 c.check(instnorm_apply_pack(t.p[g], t.rows[g], t.cols, t.ld, nullptr, static_cast<const double*>(ts->partials[g]),
                                             (double)t.rows[g], 1e-5f, slope, u.p[g], u.ld, s_pts, pk, c.st));
             else {
@@ -546,18 +573,14 @@ Mat resnet_block(Ctx& c, const Batches& B, const pcrcg_block& blk, const Mat& fe
     Mat sc = feats;
     if (blk.strided) {   // max_pool shortcut (:672-673)
         sc = c.mat(nq, feats.cols);
-        if (c.live() && c.G <= 4) {          // every pair's pool in one launch
+        if (c.live()) {          // every pair's pool in one launch
             GatherJob jobs[GMAX];
             for (int g = 0; g < c.G; ++g) {
                 const pcrcg_table& t = B.b[g]->pools[blk.layer];
                 jobs[g] = GatherJob{feats.p[g], t.idx, sc.p[g], feats.rows[g], nq[g], t.cols, t.ld};
             }
             c.check(gather_max_multi(jobs, c.G, feats.cols, c.st));
-        } else if (c.live())
-            for (int g = 0; g < c.G; ++g) {
-                const pcrcg_table& t = B.b[g]->pools[blk.layer];
-                c.check(pcrcg_gather_max(feats.p[g], feats.rows[g], feats.cols, t.idx, nq[g], t.cols, t.ld, sc.p[g], c.st));
-            }
+        }
     }
     if (blk.shortcut) {
         Mat s2 = c.gemm_out(nq, blk.out_dim, sc.cols);
@@ -596,20 +619,13 @@ void edge_norm_all(Ctx& c, const Mat& cn, int cw, int* const* idx, const int* n,
     }
     if (multi && edgeconv_rows_ok(cl, c.G, cn.ld, cn.ld, e.ld, cw)) {
         c.check(edgeconv_rows_multi(cl, c.G, cn.ld, cn.ld, e.ld, cw, true, nullptr, c.st));
-        NormJob jobs[GMAX];
-        bool al = c.G <= 4;
+        NormJobs nj = norm_jobs(c, e, sums, out);       // (e has the clouds' n rows; the statistics are over n k edges)
+        bool one = nj.aligned;
         for (int g = 0; g < c.G; ++g) {
-            jobs[g] = NormJob{e.p[g], static_cast<const double*>(sums[g]), nullptr, nullptr, out.p[g], nullptr, nullptr, n[g],
-                              (double)n[g] * (double)k[g]};
-            al = al && ((reinterpret_cast<uintptr_t>(e.p[g]) | reinterpret_cast<uintptr_t>(out.p[g])) & 15) == 0 && n[g] > 0 && k[g] > 0;
+            nj.j[g].count = (double)n[g] * (double)k[g];
+            one = one && n[g] > 0 && k[g] > 0;
         }
-        if (al) {
-            c.check(instnorm_apply_sums_multi(jobs, c.G, cw, e.ld, 1e-5f, 0, 0.2f, out.ld, false, c.st));
-            return;
-        }
-        for (int g = 0; g < c.G; ++g)
-            c.check(pcrcg_instnorm_apply_sums(e.p[g], n[g], cw, e.ld, sums[g], (double)n[g] * (double)k[g], 1e-5f, nullptr, 0, nullptr,
-                                              0.2f, out.p[g], out.ld, c.st));
+        apply_sums(c, nj.j, one, cw, e.ld, 0, 0.2f, out.ld);
         return;
     }
     for (int g = 0; g < c.G; ++g)
@@ -649,9 +665,7 @@ Mat self_attention(Ctx& c, const pcrcg_model& mdl, const pcrcg_gnn_layer& gl, co
     if (c.live()) {
         if (!knn_given)
             for (int g = 0; g < c.G; ++g) c.check(pcrcg_knn(coords[g], f.rows[g], kq[g], idx[g], c.st));
-        if (c.G <= 4) c.check(copy2d_multi(f.p, cat.p, f.rows, c.G, f.ld, cat.ld, ch, c.st));                // x0, every cloud
-        else
-            for (int g = 0; g < c.G; ++g) c.check(pcrcg_copy2d(f.p[g], f.ld, cat.p[g], cat.ld, f.rows[g], ch, c.st));
+        c.check(copy2d_multi(f.p, cat.p, f.rows, c.G, f.ld, cat.ld, ch, c.st));                // x0, every cloud
         // x1 = max_k lrelu(IN2d(conv1(cat(f_i, f_j - f_i))))  (:121-125)
         linear(c, f, gl.edge1, ch, nullptr, cn1);
         edge_norm_all(c, cn1, ch, idx, f.rows, kq, e1, cat1, sums1, ok1, stats, ws, wsb);
@@ -686,14 +700,8 @@ Mat cross_attention(Ctx& c, const pcrcg_model& mdl, const pcrcg_gnn_layer& gl, c
         kk = c.gemm_out(src.rows, ch, ch);
         v = c.gemm_out(src.rows, ch, ch);
     }
-    int sc_rows[GMAX] = {};
-    for (int g = 0; g < c.G; ++g) sc_rows[g] = x.rows[g];
-    int ms_max = 0;
-    for (int g = 0; g < c.G; ++g) ms_max = src.rows[g] > ms_max ? src.rows[g] : ms_max;
-    Mat sc = c.mat(sc_rows, ms_max);
-    int r2[GMAX];
-    for (int g = 0; g < GMAX; ++g) r2[g] = x.rows[g];
-    Mat cat = c.mat(r2, 2 * ch), h0 = c.gemm_out(r2, 2 * ch, 2 * ch), h1 = c.mat(r2, 2 * ch), delta = c.gemm_out(r2, ch, 2 * ch);
+    Mat sc = c.mat(x.rows, c.max_rows(src.rows));
+    Mat cat = c.mat(x.rows, 2 * ch), h0 = c.gemm_out(x.rows, 2 * ch, 2 * ch), h1 = c.mat(x.rows, 2 * ch), delta = c.gemm_out(x.rows, ch, 2 * ch);
     if (!q_given) linear(c, x, gl.wq, ch, gl.bq, q);
     if (!kv_fused) {
         linear(c, src, gl.wk, ch, gl.bk, kk);
@@ -728,11 +736,9 @@ Mat cross_attention(Ctx& c, const pcrcg_model& mdl, const pcrcg_gnn_layer& gl, c
                 }
             }
         }
-    if (c.live() && c.G <= 4) c.check(copy2d_multi(x.p, cat.p, x.rows, c.G, x.ld, cat.ld, ch, c.st));
-    else if (c.live())
-        for (int g = 0; g < c.G; ++g) c.check(pcrcg_copy2d(x.p[g], x.ld, cat.p[g], cat.ld, x.rows[g], ch, c.st));
+    if (c.live()) c.check(copy2d_multi(x.p, cat.p, x.rows, c.G, x.ld, cat.ld, ch, c.st));
     linear(c, msg, gl.wm, ch, gl.bm, cols(cat, ch, ch));       // merge, written next to x: cat([x, message])
-    Stat h0s = stat_buffer(c, r2, 2 * ch);
+    Stat h0s = stat_buffer(c, x.rows, 2 * ch);
     linear(c, cat, gl.w0, 2 * ch, gl.b0, h0, &h0s);
     if (!linear_norm(c, h0, &h0s, 0.0f, gl.w3, 2 * ch, gl.b3, delta)) {      // InstanceNorm1d + ReLU, inside w3's A loads
         norm_act(c, h0, 0.0f, h1, &h0s);
@@ -791,54 +797,38 @@ void forward(Ctx& c, const pcrcg_model& mdl, const Batches& B, const pcrcg_outpu
                 c.check(pcrcg_knn(c1[g], nt[g], k1, knn1[g], c.st));
             }
         }
+    // Both clouds of every pair through one pass of 2 G clouds where a layer treats them alike, stacked() [source clouds |
+    // target clouds].  The multi-cloud kernels take four clouds, so this applies to calls of one or two pairs; with more
+    // pairs per call the two sides run as two passes.
+    const int G0 = c.G;
+    const bool stack = 2 * G0 <= GMAX && gemm_split_terms_on();
+    const float* c01[GMAX] = {};
+    int* knn01[GMAX] = {};
+    for (int g = 0; g < G0 && stack; ++g) { c01[g] = c0[g]; c01[G0 + g] = c1[g]; knn01[g] = knn0[g]; knn01[G0 + g] = knn1[g]; }
     for (int i = 0; i < mdl.n_gnn; ++i) {
         const pcrcg_gnn_layer& gl = mdl.gnn[i];
-        if (gl.cross && 2 * c.G <= GMAX && gemm_split_terms_on()) {
+        if (gl.cross) {
             // the second direction's queries come from d1, which the first direction does not change: both query
             // projections in one launch (2 G products sharing wq)
-            const int G0 = c.G, ch = d0.cols;
-            const size_t mk = c.mark();
-            Mat x2 = d0;
-            for (int g = 0; g < G0; ++g) { x2.p[G0 + g] = d1.p[g]; x2.rows[G0 + g] = d1.rows[g]; }
-            c.G = 2 * G0;
-            Mat q2 = c.gemm_out(x2.rows, ch, ch);
-            linear(c, x2, gl.wq, ch, gl.bq, q2);
-            c.G = G0;
-            Mat q0 = q2, q1 = q2;
-            for (int g = 0; g < GMAX; ++g) {
-                q0.p[g] = g < G0 ? q2.p[g] : nullptr; q0.rows[g] = g < G0 ? q2.rows[g] : 0;
-                q1.p[g] = g < G0 ? q2.p[G0 + g] : nullptr; q1.rows[g] = g < G0 ? q2.rows[G0 + g] : 0;
+            Mat q0, q1;
+            if (stack) {
+                const int ch = d0.cols;
+                const Mat x2 = stacked(d0, d1, G0);
+                const Mat q2 = c.twice([&] { Mat q = c.gemm_out(x2.rows, ch, ch); linear(c, x2, gl.wq, ch, gl.bq, q); return q; });
+                q0 = half(q2, 0, G0);
+                q1 = half(q2, 1, G0);
             }
             // (the results are allocated above the projections: the arena is a stack, so they stay until the forward ends)
-            d0 = cross_attention(c, mdl, gl, d0, d1, &q0);
-            d1 = cross_attention(c, mdl, gl, d1, d0, &q1);   // sees the updated d0 (:214)
-            (void)mk;
-        } else if (gl.cross) {
-            d0 = cross_attention(c, mdl, gl, d0, d1);
-            d1 = cross_attention(c, mdl, gl, d1, d0);   // sees the updated d0 (:214)
-        } else if (2 * c.G <= GMAX && gemm_split_terms_on()) {
+            d0 = cross_attention(c, mdl, gl, d0, d1, stack ? &q0 : nullptr);
+            d1 = cross_attention(c, mdl, gl, d1, d0, stack ? &q1 : nullptr);   // sees the updated d0 (:214)
+        } else if (stack) {
             // The layer is applied to the source cloud and to the target cloud of every pair with the SAME weights and no
-            // exchange between them (ref:models/gcn.py:207-211): 2 G independent clouds through ONE pass -- every weight
-            // product of the layer once for all of them (round 5: three launches per layer instead of six; the
-            // per-cloud kernels are unchanged).  The multi-cloud kernels take four clouds, so this applies to calls of one
-            // or two pairs; with four pairs per call the two sides run as two passes of four clouds.
-            const int G0 = c.G;
-            Mat f2;
-            const float* cc[GMAX];
-            int* kk[GMAX];
-            f2.cols = d0.cols; f2.ld = d0.ld;
-            for (int g = 0; g < G0; ++g) {
-                f2.p[g] = d0.p[g]; f2.rows[g] = d0.rows[g]; cc[g] = c0[g]; kk[g] = knn0[g];
-                f2.p[G0 + g] = d1.p[g]; f2.rows[G0 + g] = d1.rows[g]; cc[G0 + g] = c1[g]; kk[G0 + g] = knn1[g];
-            }
-            c.G = 2 * G0;
-            const Mat y2 = self_attention(c, mdl, gl, cc, f2, knn_once ? kk : nullptr);
-            c.G = G0;
-            d0 = y2; d1 = y2;
-            for (int g = 0; g < GMAX; ++g) {
-                d0.p[g] = g < G0 ? y2.p[g] : nullptr; d0.rows[g] = g < G0 ? y2.rows[g] : 0;
-                d1.p[g] = g < G0 ? y2.p[G0 + g] : nullptr; d1.rows[g] = g < G0 ? y2.rows[G0 + g] : 0;
-            }
+            // exchange between them (ref:models/gcn.py:207-211): every weight product of the layer once for all 2 G clouds
+            // (round 5: three launches per layer instead of six; the per-cloud kernels are unchanged).
+            const Mat f2 = stacked(d0, d1, G0);
+            const Mat y2 = c.twice([&] { return self_attention(c, mdl, gl, c01, f2, knn_once ? knn01 : nullptr); });
+            d0 = half(y2, 0, G0);
+            d1 = half(y2, 1, G0);
         } else {
             d0 = self_attention(c, mdl, gl, c0, d0, knn_once ? knn0 : nullptr);
             d1 = self_attention(c, mdl, gl, c1, d1, knn_once ? knn1 : nullptr);
@@ -850,10 +840,7 @@ void forward(Ctx& c, const pcrcg_model& mdl, const Batches& B, const pcrcg_outpu
     {
         const size_t m = c.mark();
         Mat gcat = c.mat(nc, gd), fn = c.mat(nc, gd);
-        int st_rows[GMAX], ts_rows[GMAX];
-        int nt_max = 0, ns_max = 0;
-        for (int g = 0; g < GMAX; ++g) { st_rows[g] = ns[g]; ts_rows[g] = nt[g]; nt_max = nt[g] > nt_max ? nt[g] : nt_max; ns_max = ns[g] > ns_max ? ns[g] : ns_max; }
-        Mat pst = c.mat(st_rows, nt_max), pts = c.mat(ts_rows, ns_max);
+        Mat pst = c.mat(ns, c.max_rows(nt)), pts = c.mat(nt, c.max_rows(ns));
         if (c.live())
             for (int g = 0; g < c.G; ++g) {
                 c.check(pcrcg_copy2d(d0.p[g], d0.ld, gcat.p[g], gcat.ld, ns[g], gd, c.st));
@@ -968,16 +955,9 @@ void forward(Ctx& c, const pcrcg_model& mdl, const Batches& B, const pcrcg_outpu
     // heads (:571-582)
     if (c.live()) {
         const int fd = mdl.final_dim;
-        if (c.G <= 4) {           // the three heads of every pair in one launch
-            float *ff[GMAX], *so[GMAX], *ss[GMAX];
-            for (int g = 0; g < c.G; ++g) { ff[g] = out[g].feats_f; so[g] = out[g].scores_overlap; ss[g] = out[g].scores_saliency; }
-            c.check(heads_multi(x.p, x.rows, c.G, x.ld, fd, ff, so, ss, c.st));
-        } else
-        for (int g = 0; g < c.G; ++g) {
-            c.check(pcrcg_l2norm_rows(x.p[g], x.ld, out[g].feats_f, fd, x.rows[g], fd, c.st));
-            c.check(pcrcg_sigmoid_scores(x.p[g] + fd, x.ld, out[g].scores_overlap, x.rows[g], c.st));
-            c.check(pcrcg_sigmoid_scores(x.p[g] + fd + 1, x.ld, out[g].scores_saliency, x.rows[g], c.st));
-        }
+        float *ff[GMAX], *so[GMAX], *ss[GMAX];           // the three heads of every pair in one launch
+        for (int g = 0; g < c.G; ++g) { ff[g] = out[g].feats_f; so[g] = out[g].scores_overlap; ss[g] = out[g].scores_saliency; }
+        c.check(heads_multi(x.p, x.rows, c.G, x.ld, fd, ff, so, ss, c.st));
     }
 }
 

@@ -82,17 +82,6 @@ class Outputs(ctypes.Structure):
     _fields_ = [("feats_f", _fp), ("scores_overlap", _fp), ("scores_saliency", _fp)]
 
 
-_bound = False
-
-
-def _bind():
-    global _bound
-    L = _lib.lib()
-    if not _bound:
-        _bound = True   # signatures are declared in _lib.SIGNATURES (struct pointers as void*)
-    return L
-
-
 def _dense(t):
     t = t.detach()
     if t.dtype != torch.float32 or not t.is_cuda:
@@ -344,8 +333,9 @@ class Runner:
     def launch_group(self, batches, n, dev, start=0):
         """Enqueue ONE forward call for n (1 to 4) consecutive pcrcg_batch structs of the ctypes array `batches`, from
         element `start` (as NativePyramid.build(group=2) returns them) on the current stream -> list of n output dicts.
-        Weight products run once for all pairs (pcrcg_kpfcnn_forward_group)."""
-        L = _bind()
+        Weight products run once for all pairs (pcrcg_kpfcnn_forward_group).  The caller keeps whatever the structs
+        point into alive until the stream has passed."""
+        L = _lib.lib()
         desc = self.descriptor()
         outs, o = [], (Outputs * n)()
         first = ctypes.byref(batches[start])
@@ -369,37 +359,13 @@ class Runner:
                 ws = torch.empty(int(nbytes * 1.25), dtype=torch.uint8, device=dev)
                 self.ws[key] = ws
             if key not in self._seen and self._built is not None:
-                cur.wait_event(self._built)
+                cur.wait_event(self._built)        # the descriptor's re-packed weights are complete before the first read
                 self._seen.add(key)
         _lib.check(L.pcrcg_kpfcnn_forward_group(ctypes.byref(desc), first, o, n, ws.data_ptr(), ws.numel(), stream),
                    "pcrcg_kpfcnn_forward_group")
         return outs
 
     def launch(self, b, dev):
-        """Enqueue the forward for a pcrcg_batch (from batch_struct, or filled by pcrcg_pyramid_build) on the
-        current stream; the caller keeps whatever `b` points into alive until the stream has passed."""
-        L = _bind()
-        desc = self.descriptor()
-        n0 = b.n_points[0]
-        out = {"feats_f": torch.empty((n0, desc.final_dim), dtype=torch.float32, device=dev),
-               "scores_overlap": torch.empty(n0, dtype=torch.float32, device=dev),
-               "scores_saliency": torch.empty(n0, dtype=torch.float32, device=dev)}
-        o = Outputs(out["feats_f"].data_ptr(), out["scores_overlap"].data_ptr(), out["scores_saliency"].data_ptr())
-        nbytes = L.pcrcg_kpfcnn_ws_bytes(ctypes.byref(desc), ctypes.byref(b))
-        if nbytes == 0:
-            raise RuntimeError("pcrcg_kpfcnn_ws_bytes rejected the descriptors: "
-                               + (L.pcrcg_last_error() or b"").decode())
-        cur = torch.cuda.current_stream()
-        stream = cur.cuda_stream
-        key = (dev.index if dev.index is not None else torch.cuda.current_device(), stream)
-        with self._lock:
-            ws = self.ws.get(key)
-            if ws is None or ws.numel() < nbytes:
-                ws = torch.empty(int(nbytes * 1.25), dtype=torch.uint8, device=dev)
-                self.ws[key] = ws
-            if key not in self._seen and self._built is not None:
-                cur.wait_event(self._built)        # the descriptor's re-packed weights are complete before the first read
-                self._seen.add(key)
-        _lib.check(L.pcrcg_kpfcnn_forward(ctypes.byref(desc), ctypes.byref(b), ctypes.byref(o), ws.data_ptr(),
-                                          ws.numel(), stream), "pcrcg_kpfcnn_forward")
-        return out
+        """launch_group for ONE pcrcg_batch (from batch_struct, or filled by pcrcg_pyramid_build) -> its output dict
+        (pcrcg_kpfcnn_forward is pcrcg_kpfcnn_forward_group with n = 1)."""
+        return self.launch_group((b,), 1, dev)[0]

@@ -273,26 +273,65 @@ def test_tables_with_ld_above_cols(cuda, mini):
 
 
 # ---- case 8: forward groups of ragged pairs ----------------------------------------------------------------------
-@pytest.mark.parametrize("form", ["kp_wt", "kp_wt+mlp_skip"])
-@pytest.mark.parametrize("n", [2, 3])
-def test_group_forms(cuda, mini, form, n):
-    """pcrcg_kpfcnn_forward_group over n pairs of different sizes (mini, C1, T8k recipes, one grouped pyramid build) with
-    the edited descriptor: each pair's outputs equal its own single-pair forward with the default descriptor."""
-    net, cfg, _, _, _ = mini
-    runner = net.runner()
-    pairs = [synthetic.pair(r, 0) for r in ("mini", "C1", "T8k")[:n]]
-    pts = [torch.from_numpy(np.concatenate([s, t])).to(cuda) for s, t in pairs]
-    lens = [torch.tensor([len(s), len(t)], dtype=torch.int32, device=cuda) for s, t in pairs]
+# (recipe, seed, rows kept of the source and of the target cloud).  Every recipe fixes its row count, so the second mini
+# pair is cut to other counts -- unequal ones: its clouds differ from the first pair's and from each other in rows.
+GROUP_PAIRS = (("mini", 0, None), ("C1", 0, None), ("T8k", 0, None), ("mini", 1, (1300, 1100)))
+
+
+def _group(cfg, dev, recipes):
+    """One grouped pyramid build over the pairs `recipes` (entries of GROUP_PAIRS) -> (pcrcg_batch array, its arena)."""
+    pairs = [synthetic.pair(r, seed) for r, seed, _ in recipes]
+    pairs = [(s[:keep[0]], t[:keep[1]]) if keep else (s, t) for (s, t), (_, _, keep) in zip(pairs, recipes)]
+    n = len(pairs)
+    pts = [torch.from_numpy(np.concatenate([s, t])).to(dev) for s, t in pairs]
+    lens = [torch.tensor([len(s), len(t)], dtype=torch.int32, device=dev) for s, t in pairs]
     nat = NativePyramid(cfg, synthetic.LIMITS["C1"], tie_order="auto")
     b, arena, lens_h, slot = nat.build(pts, lens, fresh_arena=True, group=2)
     torch.cuda.synchronize()
     assert int(nat.status[slot]) == 0
     assert len({b[g].n_points[0] for g in range(n)}) == n            # ragged
+    return b, arena
+
+
+@pytest.mark.parametrize("form", ["kp_wt", "kp_wt+mlp_skip"])
+@pytest.mark.parametrize("n", [2, 3, 4])
+def test_group_forms(cuda, mini, form, n):
+    """pcrcg_kpfcnn_forward_group over n pairs of different sizes (mini, C1, T8k recipes and a second, cut mini; one grouped
+    pyramid build) with the edited descriptor: each pair's outputs equal its own single-pair forward with the default
+    descriptor.  n = 2 stacks the two clouds of every pair (four clouds per pass of the GNN); n = 3 and n = 4 run the two
+    sides as two passes, n = 4 with every multi-cloud kernel at its four clouds."""
+    net, cfg, _, _, _ = mini
+    runner = net.runner()
+    b, arena = _group(cfg, cuda, GROUP_PAIRS[:n])
     got = forward(runner, _edited(runner, FORMS[form]), [b[g] for g in range(n)], cuda)
     for g in range(n):
         ref = forward(runner, _edited(runner, []), [b[g]], cuda)[0]
         for k in KEYS:
             assert rel(got[g][k], ref[k]) <= SAME, (g, k, rel(got[g][k], ref[k]))
+    del arena
+
+
+def test_group_with_fp32_products(cuda, mini):
+    """A group of two pairs (mini, C1) with pcrcg_gemm_set_mode(0): the products run pair by pair (the two clouds of a
+    pair are not stacked, the normalisations take their statistics from partials) while the launches that do not depend on
+    the arithmetic -- copies, max-pool shortcuts, heads -- stay grouped.  Each pair's outputs equal its own single-pair
+    forward in the same mode."""
+    net, cfg, _, _, _ = mini
+    runner = net.runner()
+    b, arena = _group(cfg, cuda, GROUP_PAIRS[:2])
+    d = _edited(runner, [])
+    L = _lib.lib()
+    old = L.pcrcg_gemm_get_mode()
+    try:
+        L.pcrcg_gemm_set_mode(0)
+        got = forward(runner, d, [b[0], b[1]], cuda)
+        refs = [forward(runner, d, [b[g]], cuda)[0] for g in range(2)]
+    finally:
+        torch.cuda.synchronize()
+        L.pcrcg_gemm_set_mode(old)
+    for g in range(2):
+        for k in KEYS:
+            assert rel(got[g][k], refs[g][k]) <= SAME, (g, k, rel(got[g][k], refs[g][k]))
     del arena
 
 
