@@ -57,7 +57,8 @@ const char* pcrcg_last_error(void);
  *   pcrcg_image_frame, pcrcg_superglue_valid_maps), added after them, and the inlier statistics
  *   (pcrcg_inlier_stats_batch_ws_bytes, pcrcg_inlier_stats_batch), added after those, and the 2-D backbone
  *   (pcrcg_res50unet_arena_bytes, pcrcg_res50unet_pack, pcrcg_res50unet_ws_bytes, pcrcg_res50unet_forward), added after those,
- *   and the ModelNet evaluation's Chamfer distance (pcrcg_chamfer_batch_ws_bytes, pcrcg_chamfer_batch), added after those. */
+ *   and the ModelNet evaluation's Chamfer distance (pcrcg_chamfer_batch_ws_bytes, pcrcg_chamfer_batch), added after those,
+ *   and the interest-point sampler (pcrcg_weighted_sample_ws_bytes, pcrcg_weighted_sample_batch), added after those. */
 #define PCRCG_ABI_VERSION 4
 int pcrcg_abi_version(void);
 
@@ -810,6 +811,33 @@ int pcrcg_ransac_batch(const float* src, const int* src_off, const float* tgt, c
                        const int* corr, const int* k, int B, int ransac_n, double threshold, double edge_similarity,
                        int distance_check, int max_iteration, int max_validation, const uint64_t* seeds,
                        double* out_transform, double* out_stats, void* ws, size_t ws_bytes, void* stream);
+
+/* Interest-point sampler: weighted sampling without replacement of S ragged segments in ONE launch, the step between the
+ * network's overlap x saliency scores and pcrcg_feature_match_batch (the reference draws it on the host with
+ * np.random.choice(..., replace=False, p = scores / sum), ref:lib/tester.py:152-164).  The distribution is that draw's
+ * (successive sampling proportional to the scores); the stream is this library's own, specified here, in DESIGN.md
+ * section 10 and in tests/sample_ref.py.
+ *   Layout: scores [n_total] f32, the segments concatenated; seg_off [S + 1] i32 DEVICE row offsets (seg_off[0] = 0,
+ *   non-decreasing); seeds [S] u64 DEVICE, each < 2^24; out_off [S + 1] i32 DEVICE = the prefix sums of
+ *   min(N_s, n_keep), which the caller computes (it knows the lengths); out_idx [out_off[S]] i32.
+ *   For segment s with N rows, scores w_i and seed sd:
+ *     h_i   = splitmix64(splitmix64((sd << 40) + i) ^ 0x53414D504C455231)      (splitmix64 as above; the constant keeps
+ *             the stream apart from the one pcrcg_ransac draws from under the same seed)
+ *     u_i   = ((double)(h_i >> 11) + 0.5) * 2^-53                               (IEEE double, round to nearest even)
+ *     key_i = -log(u_i) / (double)w_i  for a finite w_i > 0, +inf otherwise
+ *   N <= n_keep: every row is kept.  Otherwise the n_keep rows with the smallest keys are kept, equal keys (also the +inf
+ *   keys of a segment with fewer than n_keep positive scores) in ascending row order.  out_idx[out_off[s] ..] receives the
+ *   kept rows, local to the segment, in ascending order.  A segment's result depends on its own scores, n_keep and seed
+ *   only -- not on S, on its position, or on the schedule (no floating-point atomics) -- and is the same bits every run.
+ *   The offsets and seeds are not read by the host: an empty segment, or one whose offsets do not lie within the rows the
+ *   workspace was sized for, writes nothing, and a segment whose seed is >= 2^24 gets -1 in all of its outputs.
+ * Workspace: pcrcg_weighted_sample_ws_bytes(S, n_total) = 8 n_total bytes plus alignment padding (the keys); 0 for S < 1 or
+ * a negative total.  One workgroup per segment, rows walked in strides of it: any segment length.  The entry allocates
+ * nothing and synchronises nothing; null pointers, S < 1 and n_keep < 1 are rejected with PCRCG_EBADARG before anything
+ * launches. */
+size_t pcrcg_weighted_sample_ws_bytes(int S, int n_total);
+int pcrcg_weighted_sample_batch(const float* scores, const int* seg_off, int S, int n_keep, const uint64_t* seeds, int* out_idx,
+                                const int* out_off, void* ws, size_t ws_bytes, void* stream);
 
 /* Inlier statistics of many pairs: the inlier ratio and its mutual variant (ref:lib/benchmark_utils.py:226-267,
  * get_inlier_ratio) of B ragged pairs in one set of launches, the inputs of feature-match recall.

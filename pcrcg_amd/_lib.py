@@ -140,6 +140,10 @@ SIGNATURES = {
     "pcrcg_inlier_stats_batch": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p,
                                          c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                                          c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    # interest-point sampler (registration.sample_batch)
+    "pcrcg_weighted_sample_ws_bytes": (c_size_t, [c_int, c_int]),
+    "pcrcg_weighted_sample_batch": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                            c_void_p]),
     # ModelNet evaluation (pcrcg_amd/modelnet.py)
     "pcrcg_chamfer_batch_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "pcrcg_chamfer_batch": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int,

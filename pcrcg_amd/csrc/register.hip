@@ -30,21 +30,13 @@
 #include "cellgrid.h"
 #include "common.h"
 #include "pcrcg_train.h"
+#include "splitmix.h"
 
 namespace pcrcg {
 namespace {
 
 constexpr int kMaxSample = 8;         // ransac_n <= 8: the draws of hypothesis h are 8 h .. 8 h + 7
 constexpr int kEvalThreads = 512;     // evaluation workgroup: one validated hypothesis
-
-// splitmix64 (Steele, Lea & Flood 2014; the generator of java.util.SplittableRandom): the state x advanced by the golden
-// gamma 0x9E3779B97F4A7C15, then the variant-13 finaliser.  include/pcrcg.h documents the same constants.
-__host__ __device__ inline u64 splitmix64(u64 x) {
-    u64 z = x + 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
 
 // (score, column) as one orderable word: a larger score wins, an equal score keeps the smaller column
 __device__ inline u64 pack_max(float v, int j) {

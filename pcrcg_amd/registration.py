@@ -14,6 +14,9 @@
   * `inlier_ratio_batch`     -- the same ratios for many pairs and thresholds in one set of launches
                                 (`InlierRatioResult`), the inputs of feature-match recall (benchmark.py).
   * `get_angle_deviation`    -- numpy, as ref:lib/benchmark_utils.py:175-185.
+  * `sample_batch`           -- the interest points of many clouds, drawn on the device in one launch
+                                (pcrcg_weighted_sample_batch): weighted sampling without replacement on the scores,
+                                reproducible from integer seeds; reads nothing back.
 
 The algorithm (csrc/register.hip, include/pcrcg.h "Registration back end") is deterministic: a
 seed fixes every draw, and two runs give the same bits.  `register` reads the device ONCE, after the selection
@@ -351,6 +354,71 @@ def ransac_pose_estimation_batch(src_pcds, tgt_pcds, src_feats, tgt_feats, mutua
     return register_batch(src_pcds, tgt_pcds, src_feats, tgt_feats, distance_threshold, ransac_n,
                           max_iteration=max_iteration, max_validation=max_validation, seeds=seeds,
                           pairs_per_call=pairs_per_call).matrices
+
+
+_MAX_SAMPLE_SEED = 1 << 24   # segment seeds of pcrcg_weighted_sample_batch (include/pcrcg.h)
+
+
+def _sample_flat(scores, n_points, seeds):
+    """sample_batch's work: -> (idx [sum k_s] int32 device, the kept rows of every cloud, local to it, concatenated;
+    ns, ks: host lists of cloud lengths and kept counts; seg_off, out_off: their [S + 1] int32 device prefix sums).
+    Every check is made on the host before anything is uploaded."""
+    S = len(scores)
+    if S == 0:
+        raise ValueError("sample_batch: no clouds")
+    n_points = int(n_points)
+    if n_points < 1:
+        raise ValueError(f"sample_batch: n_points = {n_points}, need at least 1")
+    seeds = [int(seeds)] * S if np.ndim(seeds) == 0 else [int(x) for x in seeds]
+    if len(seeds) != S:
+        raise ValueError(f"sample_batch: {len(seeds)} seeds for {S} clouds")
+    if any(not 0 <= x < _MAX_SAMPLE_SEED for x in seeds):
+        raise ValueError("sample_batch: every seed must lie in [0, 2^24)")
+    ts = [x if isinstance(x, torch.Tensor) else torch.from_numpy(np.asarray(x)) for x in scores]
+    ns = [int(t.numel()) for t in ts]
+    for b, t in enumerate(ts):
+        if ns[b] == 0:
+            raise ValueError(f"sample_batch: cloud {b} is empty")
+        if t.dim() > 2 or (t.dim() == 2 and t.shape[1] != 1):
+            raise ValueError(f"sample_batch: cloud {b}: scores must be [N] or [N, 1], got {tuple(t.shape)}")
+    if sum(ns) > 0x7FFFFFFF:
+        raise ValueError("sample_batch: more than 2^31 - 1 rows in one call")
+    ks = [min(n, n_points) for n in ns]
+    dev = _device(*ts)
+    if all(not t.is_cuda for t in ts):
+        w = torch.cat([t.detach().reshape(-1).to(torch.float32) for t in ts]).to(dev)
+    else:
+        w = torch.cat([t.detach().reshape(-1).to(device=dev, dtype=torch.float32) for t in ts])
+    # ONE upload: the seeds [S] u64, then both offset arrays [S + 1] i32 packed into the following int64 words
+    meta = np.empty(2 * S + 1, dtype=np.int64)
+    meta[:S] = seeds
+    offs = meta[S:].view(np.int32)
+    offs[:S + 1] = np.cumsum([0] + ns)
+    offs[S + 1:] = np.cumsum([0] + ks)
+    meta_d = torch.from_numpy(meta).to(dev)
+    offs_d = meta_d[S:].view(torch.int32)
+    seg_off, out_off = offs_d[:S + 1], offs_d[S + 1:]
+    L = _lib.lib()
+    wsb = L.pcrcg_weighted_sample_ws_bytes(S, sum(ns))
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    idx = torch.empty(sum(ks), dtype=torch.int32, device=dev)
+    _lib.check(L.pcrcg_weighted_sample_batch(w.data_ptr(), seg_off.data_ptr(), S, n_points, meta_d.data_ptr(), idx.data_ptr(),
+                                             out_off.data_ptr(), ws.data_ptr(), wsb, _stream()), "pcrcg_weighted_sample_batch")
+    return idx, ns, ks, seg_off, out_off
+
+
+def sample_batch(scores, n_points, seeds):
+    """Weighted sampling without replacement of n_points rows from each of S clouds, on the device
+    (pcrcg_weighted_sample_batch; DESIGN.md section 10 has the specification) -> list of S int64 device tensors, cloud
+    s's kept rows in ascending order (all of them when it has no more than n_points).
+
+    scores: list of per-cloud [N_s] (or [N_s, 1]) score tensors -- overlap x saliency -- on the device or the host; a row
+    whose score is not a finite positive number is kept only when fewer than n_points rows are.  seeds: an int (every
+    cloud) or S ints in [0, 2^24); a cloud's result depends on its scores, n_points and seed alone.  One upload of offsets
+    and seeds (host-side scores are joined on the host and uploaded once as well), one launch, nothing read back; every
+    check runs on the host first."""
+    idx, _, ks, _, _ = _sample_flat(scores, n_points, seeds)
+    return list(idx.to(torch.int64).split(ks))
 
 
 def get_inlier_ratio(src_pcd, tgt_pcd, src_feat, tgt_feat, rot, trans, inlier_distance_threshold=0.1):

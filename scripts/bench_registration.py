@@ -6,7 +6,13 @@ Settings (50 000 iterations, 1 000 validations, 32-wide descriptors, 50 % outlie
   s30k     30 000 / 30 000 points (a pair without the sampling step), ransac_n = 3, threshold 0.05
 Per setting: pairs/s of `register` (matching + RANSAC + its one read-back, median of --reps) and the median ms of the
 stages from events: nn (pcrcg_feature_match), hypotheses (pcrcg_ransac with max_validation = 1: draws, checks, fits,
-compaction, one evaluation, selection) and evaluation (pcrcg_ransac at 1 000 validations minus that)."""
+compaction, one evaluation, selection) and evaluation (pcrcg_ransac at 1 000 validations minus that).
+
+  sampling (--settings sampling)  the stage before registration: 64 pairs of 2 x 20 000 points -> 5 000 interest points
+           per cloud on overlap x saliency.  device: tester.probabilistic_sample_batch (registration.sample_batch + gather)
+           on inputs that are on the device, between events, after a warm-up, median of --reps; host:
+           tester._sample_records on the same records as CPU tensors (what the evaluation scripts hand it), wall clock,
+           median of --reps (at most 5)."""
 import argparse
 import json
 import os
@@ -56,6 +62,40 @@ def bench(name, s, reps, max_iteration, max_validation):
             "fitness": round(res.fitness, 4), "rot_err_deg": round(rot, 4), "trans_err": round(trans, 5)}
 
 
+def bench_sampling(reps, pairs=64, n=20000, keep=5000, c=32):
+    import time
+    from pcrcg_amd import tester
+    dev = torch.device("cuda:0")
+    rng = np.random.RandomState(0)
+    records = [{"pcd": torch.from_numpy(rng.rand(2 * n, 3).astype(np.float32)),
+                "feats": torch.from_numpy(rng.randn(2 * n, c).astype(np.float32)),
+                "overlaps": torch.from_numpy(rng.rand(2 * n).astype(np.float32)),
+                "saliency": torch.from_numpy(rng.rand(2 * n).astype(np.float32)), "len_src": n} for _ in range(pairs)]
+    pcds, feats, scores = [], [], []
+    for r in records:
+        sc = (r["overlaps"] * r["saliency"]).to(dev)
+        p, f = r["pcd"].to(dev), r["feats"].to(dev)
+        pcds += [p[:n], p[n:]]
+        feats += [f[:n], f[n:]]
+        scores += [sc[:n], sc[n:]]
+    seeds = list(range(2 * pairs))
+    run = lambda: tester.probabilistic_sample_batch(pcds, feats, scores, keep, seeds)
+    run()                                                                            # warm-up
+    torch.cuda.synchronize()
+    device_ms = timed(run, reps)
+    select_ms = timed(lambda: REG.sample_batch(scores, keep, seeds), reps)
+    host = []
+    np.random.seed(0)
+    for _ in range(min(reps, 5)):
+        t0 = time.perf_counter()
+        tester._sample_records(records, keep)
+        host.append(1e3 * (time.perf_counter() - t0))
+    host_ms = float(np.median(host))
+    return {"pairs": pairs, "points": n, "keep": keep, "device_ms": round(device_ms, 3),
+            "device_select_ms": round(select_ms, 3), "device_ms_per_pair": round(device_ms / pairs, 4),
+            "host_ms": round(host_ms, 2), "host_ms_per_pair": round(host_ms / pairs, 3)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
@@ -66,6 +106,9 @@ def main():
     out = {"metric": "registration", "max_iteration": a.max_iteration, "max_validation": a.max_validation,
            "device": torch.cuda.get_device_name(0)}
     for name in a.settings.split(","):
+        if name == "sampling":
+            out[name] = bench_sampling(a.reps)
+            continue
         out[name] = bench(name, SETTINGS[name], a.reps, a.max_iteration, a.max_validation)
     print(json.dumps(out))
 

@@ -13,7 +13,10 @@ recall (FMR) lines of benchmark.feature_match_recall, without and with the mutua
 and added to the summary.
 
   python scripts/evaluate_registration.py --source_path snapshot/.../test/pth --gt_folder configs/benchmarks/3DMatch \\
-      --exp_dir snapshot/.../est_traj [--n_points 250 500 1000 2500 5000] [--inlier_ratio]
+      --exp_dir snapshot/.../est_traj [--n_points 250 500 1000 2500 5000] [--inlier_ratio] [--sampler device]
+
+--sampler device draws the interest points of all records on the GPU in one launch (registration.sample_batch: the same
+distribution from its own seeded stream, record b with sample seed --seed + b) instead of on the host generator.
 """
 import argparse
 import json
@@ -43,6 +46,8 @@ def main():
     ap.add_argument("--distance_threshold", type=float, default=0.05)
     ap.add_argument("--ransac_n", type=int, default=3)
     ap.add_argument("--seed", type=int, default=0, help="np.random seed before each sampling pass")
+    ap.add_argument("--sampler", choices=("host", "device"), default="host",
+                    help="host: np.random.choice as the reference; device: one GPU launch, sample seeds --seed + record index")
     ap.add_argument("--inlier_ratio", action="store_true", help="also report the inlier ratio and feature-match recall")
     ap.add_argument("--inlier_distance", type=float, default=0.1, help="inlier distance threshold of IR / FMR (m)")
     ap.add_argument("--fmr_threshold", type=float, default=0.05, help="inlier ratio above which a pair counts for FMR")
@@ -55,14 +60,16 @@ def main():
     if sum(len(k) for k in keys) != len(records):
         raise SystemExit(f"{len(records)} records for {sum(len(k) for k in keys)} gt pairs in {a.gt_folder}")
     summary = {}
+    sampling = dict(sampler=a.sampler, sample_seeds=[(a.seed + b) % (1 << 23) for b in range(len(records))])
     for n_points in a.n_points:
         np.random.seed(a.seed)
         if a.inlier_ratio:
             poses, inliers = tester.evaluate_records(records, n_points=n_points, distance_threshold=a.distance_threshold,
-                                                     ransac_n=a.ransac_n, inlier_thresholds=(a.inlier_distance,))
+                                                     ransac_n=a.ransac_n, inlier_thresholds=(a.inlier_distance,),
+                                                     **sampling)
         else:
             poses = tester.register_records(records, n_points=n_points, distance_threshold=a.distance_threshold,
-                                            ransac_n=a.ransac_n)
+                                            ransac_n=a.ransac_n, **sampling)
         out_dir = os.path.join(a.exp_dir, str(n_points))
         o = 0
         for scene, k in zip(scenes, keys):
