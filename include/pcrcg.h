@@ -457,7 +457,10 @@ int pcrcg_superglue_valid_maps(const float* keypoints0, int n0, const float* key
  * GNN head helpers (ref:models/gcn.py)
  * ---------------------------------------------------------------------------------------------- */
 /* get_graph_feature's kNN (ref:models/gcn.py:15-34,48-51): dist = -2ab + a^2 + b^2 clamped at 1e-12,
- * the k+1 smallest by (dist, index), first dropped.  coords [n,3] f32 -> idx [n,k] i32. */
+ * each step rounded as the reference's CPU run rounds it; the k+1 smallest, first dropped.  Among exactly equal
+ * distances the order -- and which of them survive the cut -- is that of torch.topk's CPU kernel for k <= 10
+ * (its std::partial_sort / std::nth_element + std::sort, replayed), and plain (dist, index) order for k > 10.
+ * coords [n,3] f32 -> idx [n,k] i32. */
 int pcrcg_knn(const float* coords, int n, int k, int* idx, void* stream);
 /* DGCNN edge conv after splitting the 1x1 conv over cat(f_i, f_j - f_i) into a centre term and a
  * neighbour term (ref:models/gcn.py:61-62,123-129):  e[i,j,c] = ctr[i,c] + nbr[idx[i,j],c];

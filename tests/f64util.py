@@ -1,11 +1,33 @@
-"""Helpers of the float64 kernel tests (test_backward_f64_gpu.py, test_loss_f64_gpu.py, test_train_ops_f64_gpu.py): the two
-arithmetic modes of the library and the per-tensor bar."""
+"""Helpers of the float64 kernel tests (test_backward_f64_gpu.py, test_loss_f64_gpu.py, test_train_ops_f64_gpu.py,
+test_forward_f64_gpu.py, test_gnn_forward_f64_gpu.py): the two arithmetic modes of the library, the per-tensor bar and the
+bar of InstanceNorm statistics."""
 import contextlib
 
 import torch
 
 MODES = ("default", "deterministic")
 TOL = 1e-4                        # max|a - b| <= TOL * max|ref| per tensor, as tests/test_autograd_gpu.py
+
+
+EPS = 1e-5                        # InstanceNorm's eps
+
+
+def check_stats(mean, rstd, x, what, mask=None):
+    """(mean, rstd) [c] from a kernel against float64 on x [n, c] (what the kernel received or stored): rstd to 1e-5 relative,
+    |mean - mu| <= 2^-23 |mu| + 1e-6 sigma."""
+    xd = x.double()
+    mu = xd.mean(0)
+    var = xd.var(0, unbiased=False)
+    sig = var.sqrt()
+    want_r = 1.0 / (var + EPS).sqrt()
+    mean, rstd = mean.double(), rstd.double()
+    if mask is not None:
+        mu, sig, want_r, mean, rstd = mu[mask], sig[mask], want_r[mask], mean[mask], rstd[mask]
+    err_r = float(((rstd - want_r).abs() / want_r).max())
+    err_m = float(((mean - mu).abs() - (2.0 ** -23 * mu.abs() + 1e-6 * sig)).max())
+    assert err_r <= 1e-5, (what, "rstd", err_r)
+    assert err_m <= 0.0, (what, "mean", err_m)
+    return err_r
 
 
 def rel(a, b):

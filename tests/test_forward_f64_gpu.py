@@ -20,11 +20,11 @@ import torch.nn.functional as F
 
 from oracle import model_ref as MR
 from pcrcg_amd import _lib, ops
-from tests.f64util import MODES, arithmetic, rel, run
+from tests.f64util import EPS, MODES, arithmetic, rel, run
+from tests.f64util import check_stats as _check_stats
 
 pytestmark = pytest.mark.gpu
 FWD = 1e-5
-EPS = 1e-5
 RATIOS = (0.0, 1.0, 30.0, 100.0, 1000.0)       # |mean| / std of column j: RATIOS[j % 5], sign alternating every five columns
 
 
@@ -35,23 +35,6 @@ def _ratio(n):
 def _rows_buffer(n, c, ld, dev, fill=float("nan")):
     """[n, c] view of a row-major [n, ld] buffer filled with `fill` (the columns beyond c must stay untouched)."""
     return torch.full((n, ld), fill, dtype=torch.float32, device=dev)[:, :c]
-
-
-def _check_stats(mean, rstd, x, what, mask=None):
-    """(mean, rstd) [c] from a kernel against float64 on x [n, c] (what the kernel received or stored)."""
-    xd = x.double()
-    mu = xd.mean(0)
-    var = xd.var(0, unbiased=False)
-    sig = var.sqrt()
-    want_r = 1.0 / (var + EPS).sqrt()
-    mean, rstd = mean.double(), rstd.double()
-    if mask is not None:
-        mu, sig, want_r, mean, rstd = mu[mask], sig[mask], want_r[mask], mean[mask], rstd[mask]
-    err_r = float(((rstd - want_r).abs() / want_r).max())
-    err_m = float(((mean - mu).abs() - (2.0 ** -23 * mu.abs() + 1e-6 * sig)).max())
-    assert err_r <= 1e-5, (what, "rstd", err_r)
-    assert err_m <= 0.0, (what, "mean", err_m)
-    return err_r
 
 
 # ---- A. column statistics from the product's epilogue ---------------------------------------------------------------------
