@@ -40,11 +40,6 @@ int exclusive_scan_i32(const int* in, int* out, int n, int* total, void* ws, hip
 
 constexpr int kWave = 64;
 
-// grid_subsample.hip: pcrcg_grid_subsample_batch with the number of points given as a host-side BOUND (the cloud
-// lengths on the device say how many there are) and room for out_cap output rows (more: *overflow = 1, output cut)
-int grid_subsample_bound(const float* pts, int n_bound, const int* len, int nb, float dl, int max_p, float* out_pts,
-                         int* out_len, int* out_m, int out_cap, int* overflow, void* ws, size_t ws_bytes, hipStream_t stream);
-
 // pointops.hip: InstanceNorm + LeakyReLU that also leaves the KPConv support records of its output (kpconv.hip: pk)
 bool instnorm_pack_ok(int c, int ldx, int ldy);
 int instnorm_apply_pack(const float* x, int n, int c, int ldx, const float* stats, const double* sums, double count, float eps,
@@ -75,24 +70,6 @@ private:
     std::mutex mu_;
     std::map<hipStream_t, Buf> bufs_;
 };
-
-// tieorder.hip: pcrcg_kdforest_build over clouds that are LEVELS of per_level clouds each, level l's rows starting at row
-// level_base[l] of sup (per_level = 0: one contiguous stack, the public entry point)
-int kdforest_build_levels(const float* sup, int ns, const int* slen, int nb, int per_level, const int* level_base, void* forest,
-                          size_t forest_bytes, hipStream_t stream);
-
-// radius.hip: pcrcg_radius_query_groups by pass (0 both kernels, 1 the first, 2 the redo of rows with > radius_fast_cap()
-// hits that the first one marked)
-int radius_fast_cap();
-int radius_query_pass(const float* q, int nq, const int* qlen, int ns, const int* slen, int nb, int group, float radius,
-                      const void* grid, int cols, int64_t* out_idx, int* out_count, int* out_max_count, int* status,
-                      int* out_tie_rows, int* out_tie_count, hipStream_t st, int pass);
-
-// radius.hip: the cell-cooperative search over a query grid (pass 0: + the per-query second pass, 1: the cell kernel only)
-int radius_cells_pass(const void* qgrid, const float* q, int nq, const int* qlen, const void* sgrid, int ns, const int* slen,
-                      int nb, int group, float radius, int cols, int64_t* out_idx, int* out_count, int* out_max_count,
-                      int* status, int* out_tie_rows, int* out_tie_count, hipStream_t st, int pass);
-constexpr int kRadiusRedoStatus = 4;   // status bit: rows were handed to the per-query second pass (cleared by that pass)
 
 // kpconv.hip: row-positive flags + packed (x, y, z, flag) support records into a pcrcg_kpconv_ws_bytes(ns) workspace
 // (x_bf16 != NULL: also the bf16 round-to-nearest-even copy of x, [ns, cin])

@@ -18,7 +18,7 @@
 //
 // This file is compiled with -ffp-contract=off: the reference is built without FMA.
 #include "block_scan.h"
-#include "common.h"
+#include "frontend.h"
 
 namespace pcrcg {
 namespace {

@@ -1,28 +1,32 @@
-// pyramid.hip -- host-side pyramid builder: the whole front end of one fragment pair (3 grid subsamplings, 4 cell
-// grids, 10 radius searches, the tie-order restore step) enqueued by ONE C-ABI call from plain C arguments.  The
-// counterpart of collate_fn_descriptor's pyramid loop (ref:datasets/dataloader.py:230-361) and of
+// pyramid.hip -- host-side pyramid builder: the whole front end of one fragment pair or of several stacked into one chain
+// (3 grid subsamplings, 4 cell grids, 10 radius searches, the tie-order restore step) enqueued by ONE C-ABI call from
+// plain C arguments.  The counterpart of collate_fn_descriptor's pyramid loop (ref:datasets/dataloader.py:230-361) and of
 // batch_grid_subsampling_kpconv / batch_neighbors_kpconv (:14-69); same sequence as pcrcg_amd/pyramid.py's
 // pyramid_steps (the Python mirror, kept for calibration and for tie_order="reference"), which this replaces on the
 // pipeline's hot path: ~85 launches cost one FFI crossing and ~0.3 ms of host time instead of ~1.7 ms of Python.
 //
-// No device code of its own: it sequences pcrcg_grid_subsample_batch, pcrcg_cellgrid_build, pcrcg_radius_query_ex,
-// pcrcg_kdforest_build and pcrcg_radius_reorder_jobs over a caller-provided arena.  The row count of a subsampled
-// level sizes the next level's tables, so the call WAITS for the stream once per pooled level (12 bytes come back
-// through the caller's pinned scratch) and once for the ten tables' column counts; callers that want the GPU busy
-// meanwhile run several pairs on several streams from several host threads (pcrcg_amd/pairstream.py) -- the call
-// holds no lock and no global state.
+// No device code of its own but the probe kernels of pcrcg_stream_pipe_classes: it sequences grid_subsample_bound,
+// pcrcg_cellgrid_build, radius_search, kdforest_build_levels (frontend.h) and pcrcg_radius_reorder_jobs over a
+// caller-provided arena, in two steps around ONE host round trip.  pyramid_enqueue carves the arena and enqueues the chain:
+// levels are sized from a row BOUND (pcrcg_pyramid_cfg::shrink), so nothing is read back between them, and every search is
+// the cell-cooperative kernel alone (RadiusPass::first).  Then the tables' metadata and every level's cloud lengths come
+// back through the caller's pinned scratch (MetaView); the call waits for an event of its own.  pyramid_finish launches the
+// per-query redo kernel for the tables that ask for it (normally none; then the metadata is fetched once more), fills the
+// pcrcg_batch structs and assembles the restore step, which it runs or hands to the caller (pcrcg_pyramid_restore).
+// Builders on several host threads may share a stream: a call holds the stream's enqueue lock (g_enqueue, the only global
+// state here) while it enqueues and lets go of it before it waits (pcrcg_amd/pairstream.py).
 //
 // Arena layout: persistent results first (points of all levels contiguous -- which is also the KD-forest's input,
 // so nothing is concatenated later --, lengths [levels][nb], features, tables, per-table counts / tie rows, cell
-// grids), transient subsampling scratch with stack discipline.  Everything the returned pcrcg_batch points to lives
-// in the arena (except level 0's points when they are used in place).
+// grids), then the subsamplings' scratch.  The input clouds are always copied into it (level 0's points too), so
+// everything the returned pcrcg_batch points to lives in the arena.
 #include <time.h>
 
 #include <cmath>
 #include <cstdlib>
 #include <vector>
 
-#include "common.h"
+#include "frontend.h"
 
 namespace pcrcg {
 namespace {
@@ -83,24 +87,33 @@ struct Arena {
     bool ok() const { return dry || off <= cap; }
 };
 
+// One table of the pyramid: its search (the first pass and the redo pass launch the SAME descriptor; s.cols is the limit
+// and the table's leading dimension, s.count / s.tie_rows feed the restore step) and where it goes in the batch.
 struct TableRec {
-    int kind;              // 0 conv (neighbors), 1 pool, 2 upsample
-    int level;             // level of the table in the batch
-    int q_level;           // level whose points are the queries
-    int64_t* idx;
-    int* counts;           // [nq] untruncated list lengths (tie restore cross-check), or null
-    int* ties;             // [nq] rows holding a tie, or null
-    int* meta;             // device [P + 2]: max_count per group, status, tie_rows
-    const float* q;
-    const int* qlen;
-    int nq, limit, sup_level;
-    float radius;
-    const void* grid;      // cell grid of the supports, their count and cloud lengths (for the redo pass)
-    const void* qgrid;     // a cell grid over the QUERIES (any cell size), or null: the cell-cooperative search walks it
-    int ns;
-    const int* slen;
+    RadiusSearch s;
+    int kind;                          // 0 conv (neighbors), 1 pool, 2 upsample
+    int level, q_level, sup_level;     // level of the table in the batch; levels whose points are the queries / the supports
 };
 
+// The metadata words of one build, in the order pyramid_enqueue lays them out on the device and ONE fetch brings them to
+// the host: for each of the 3 L table slots [max_count of each of the P output batches, status, tie_rows], then the
+// L subsampled row counts, then the "a level outgrew its bound" word -- and, from their own place on the device, the
+// [L][nb] cloud lengths behind them.  Over the device block only addresses are taken, over the host copy values are read.
+struct MetaView {
+    int* w; int P, L;
+    struct Table {
+        int* w; int P;
+        int& max_count(int p) const { return w[p]; }
+        int& status() const { return w[P]; }
+        int& tie_rows() const { return w[P + 1]; }
+        int widest() const { int m = 0; for (int p = 0; p < P; ++p) m = w[p] > m ? w[p] : m; return m; }
+    };
+    Table table(int i) const { return Table{w + (P + 2) * i, P}; }
+    int* row_counts() const { return w + (P + 2) * 3 * L; }
+    int& overflow() const { return row_counts()[L]; }
+    int words() const { return (P + 2) * 3 * L + L + 1; }      // (without the lengths)
+    const int* lengths() const { return w + words(); }
+};
 }  // namespace
 }  // namespace pcrcg
 
@@ -142,9 +155,8 @@ static void level_caps(int n0, const pcrcg_pyramid_cfg* cfg, int* cap) {
     }
 }
 
-// Builders on several host threads may share ONE stream (the pair engine's pipelined front end): a call holds the stream's
-// enqueue lock while it enqueues its chain and lets go of it before it waits for its round trip, so the chains stay whole
-// (one after the other in the stream, never interleaved) while one call's wait overlaps the next call's enqueue.
+// The enqueue lock of a stream: held while a call enqueues its chain, released before it waits for its round trip, so the
+// chains of several host threads stay whole in the stream while one call's wait overlaps the next call's enqueue.
 struct EnqueueLocks {
     std::mutex mu;
     hipStream_t key[16];
@@ -161,30 +173,44 @@ struct EnqueueLocks {
 };
 static EnqueueLocks g_enqueue;
 
-// ints the call uses of the caller's h_scratch: a reserved word (h_scratch[0], not written), (P + 2) metadata words for each
-// of the 3 L tables, the L subsampled row counts, the overflow word and the L nb cloud lengths (P = output batches).  The
-// argument checks of pyramid_build_checked (L <= 4 from 3 L <= PCRCG_MAX_REORDER_JOBS, P + 2 <= 16, L nb <= 64) bound it
+// ints the call uses of the caller's h_scratch: a reserved word (h_scratch[0], not written), MetaView's words and the L nb
+// cloud lengths (P = output batches).  The argument checks of pyramid_build_checked (L <= 4 from 3 L <= PCRCG_MAX_REORDER_JOBS, P + 2 <= 16, L nb <= 64) bound it
 // by 254 (L = 4, nb = 14, group = 1): within the 256 ints include/pcrcg.h asks for.
 constexpr int kHostScratchInts = 256;
 static int host_scratch_ints(int nb, const pcrcg_pyramid_cfg* cfg) {
     const int L = cfg->n_levels, P = cfg->group > 0 ? nb / cfg->group : 1;
-    return 1 + (P + 2) * 3 * L + L + 1 + L * nb;
+    return 1 + MetaView{nullptr, P, L}.words() + L * nb;
 }
 
-static int pyramid_run(const Parts& in, int n0, int nb, const pcrcg_pyramid_cfg* cfg, Arena& A,
-                       int* h_scratch, pcrcg_batch* out, int* h_lengths, int* h_status, pcrcg_pyramid_restore* deferred,
-                       hipStream_t st, std::unique_lock<std::mutex>* enqueue = nullptr) {
+
+// What pyramid_enqueue leaves for pyramid_finish: where things are in the arena, and what is in the streams.
+struct Build {
+    int nb, group;                                     // clouds, clouds per output batch (0: all in one)
+    bool want_ties, one_forest;
+    int cap[PCRCG_MAX_LEVELS];                         // row bound of every level (level_caps)
+    float* level_pts[PCRCG_MAX_LEVELS];
+    int* lens_all;                                     // [L][nb] cloud lengths
+    float* feats;
+    MetaView meta;                                     // the device block
+    int* tie_status;                                   // the restore step's status word, behind it
+    std::vector<TableRec> tables;
+    void* forest[2] = {nullptr, nullptr};              // [0] level 0 (one_forest: all levels), [1] levels 1 .. L-1
+    int forest_ns[2] = {0, 0}, forest_nb[2] = {0, 0};
+    EventBox events;
+    hipEvent_t forests_done = nullptr;                 // recorded behind the forests where they have a stream of their own
+};
+
+// Step 1: carve the arena and enqueue the whole chain.  A.dry: carve only (pcrcg_pyramid_ws_bytes; `in` is not read).
+static int pyramid_enqueue(const Parts& in, int n0, int nb, const pcrcg_pyramid_cfg* cfg, Arena& A, hipStream_t st, Build& B) {
     const int L = cfg->n_levels;
-    const bool dry = A.dry;
-    const bool want_ties = cfg->tie_order != 0;
-    const int group = cfg->group > 0 ? cfg->group : 0;
-    const int P = group > 0 ? nb / group : 1;          // output batches
-    const int MS = P + 2;                              // ints of table metadata
-    int cap[PCRCG_MAX_LEVELS];
+    const bool dry = A.dry, want_ties = B.want_ties = cfg->tie_order != 0;
+    const int group = B.group = cfg->group > 0 ? cfg->group : 0;
+    B.nb = nb;
+    int* const cap = B.cap;
+    float** const level_pts = B.level_pts;
     level_caps(n0, cfg, cap);
     // ---- persistent block 1: points of all levels (level l at its own bound-sized place), lengths, features, metadata ----
     // (one block, every level a whole number of ROWS behind the first: the upper levels' forest indexes them as one array)
-    float* level_pts[PCRCG_MAX_LEVELS];
     {
         size_t rows = 0;
         for (int l = 0; l < L; ++l) rows += (size_t)cap[l] + 1;
@@ -192,21 +218,18 @@ static int pyramid_run(const Parts& in, int n0, int nb, const pcrcg_pyramid_cfg*
         rows = 0;
         for (int l = 0; l < L; ++l) { level_pts[l] = pts_all + 3 * rows; rows += (size_t)cap[l] + 1; }
     }
-    int* lens_all = A.take<int>((size_t)L * nb);
-    float* feats = A.take<float>((size_t)n0);
-    const int max_tables = 3 * L;
-    // [MS per table] + subsampled row counts [L] + "a level outgrew its bound" [1] + the restore step's status word [1]
-    const size_t meta_ints = (size_t)MS * max_tables + L + 2;
-    int* metas = A.take<int>(meta_ints);
-    int* m_dev = metas + MS * max_tables;
-    int* overflow = m_dev + L;
-    int* tie_status = overflow + 1;
+    int* const lens_all = B.lens_all = A.take<int>((size_t)L * nb);
+    float* const feats = B.feats = A.take<float>((size_t)n0);
+    MetaView& meta = B.meta = MetaView{nullptr, group > 0 ? nb / group : 1, L};
+    const size_t meta_ints = (size_t)meta.words() + 1;                // + the restore step's status word
+    meta.w = A.take<int>(meta_ints);
+    B.tie_status = &meta.overflow() + 1;
     if (!A.ok()) return PCRCG_EWORKSPACE;
 
-    std::vector<TableRec> tables;
-    tables.reserve(max_tables);
+    std::vector<TableRec>& tables = B.tables;
+    tables.reserve(3 * L);
     if (!dry) {
-        PCRCG_CHECK_HIP(hipMemsetAsync(metas, 0, sizeof(int) * meta_ints, st));
+        PCRCG_CHECK_HIP(hipMemsetAsync(meta.w, 0, sizeof(int) * meta_ints, st));
         size_t row = 0, cloud = 0;
         for (int i = 0; i < in.count; ++i) {
             if (in.n[i] > 0)
@@ -234,56 +257,52 @@ static int pyramid_run(const Parts& in, int n0, int nb, const pcrcg_pyramid_cfg*
     // wait to be told that there are some.
     hipStream_t sub_st = cfg->side_stream ? as_stream(cfg->side_stream) : st;
     hipStream_t f_st = cfg->side_stream2 ? as_stream(cfg->side_stream2) : sub_st;
-    EventBox events;
     // b waits for everything enqueued on a so far
     auto order = [&](hipStream_t a, hipStream_t b) -> int {
         if (a == b || dry) return PCRCG_OK;
         hipEvent_t ev;
-        PCRCG_PROPAGATE(events.make(&ev));
+        PCRCG_PROPAGATE(B.events.make(&ev));
         PCRCG_CHECK_HIP(hipEventRecord(ev, a));
         PCRCG_CHECK_HIP(hipStreamWaitEvent(b, ev, 0));
         return PCRCG_OK;
     };
     // In line (no stream of their own) ONE forest over all levels, built when the last level exists: the levels' trees then
     // grow side by side in one persistent launch (1.07 ms per four-pair chain in the engine against 2 x 0.6 for two launches).
-    const bool one_forest = !want_ties || f_st == st || L < 2;
-    void* forest[2] = {nullptr, nullptr};              // [0] level 0 (one_forest: all levels), [1] levels 1 .. L-1
-    size_t forest_b[2] = {0, 0};
-    int forest_ns[2] = {0, 0}, forest_nb[2] = {0, 0};
+    const bool one_forest = B.one_forest = !want_ties || f_st == st || L < 2;
     int level_base[PCRCG_MAX_LEVELS] = {};               // row of level l relative to the first level of its forest
     auto build_forest = [&](int which) -> int {        // 0: level 0, 1: levels 1 .. L-1, 2: all levels (-> forest[0])
         if (!want_ties || (which == 1 && L < 2)) return PCRCG_OK;
         const int first = which == 1 ? 1 : 0, last = which == 0 ? 0 : L - 1, slot = which == 1 ? 1 : 0;
         for (int l = first; l <= last; ++l) level_base[l - first] = (int)((level_pts[l] - level_pts[first]) / 3);
-        forest_ns[slot] = level_base[last - first] + cap[last];
-        forest_nb[slot] = (last - first + 1) * nb;
-        forest_b[slot] = pcrcg_kdforest_ws_bytes(forest_ns[slot], forest_nb[slot]);
-        forest[slot] = A.raw(forest_b[slot]);
+        B.forest_ns[slot] = level_base[last - first] + cap[last];
+        B.forest_nb[slot] = (last - first + 1) * nb;
+        const size_t bytes = pcrcg_kdforest_ws_bytes(B.forest_ns[slot], B.forest_nb[slot]);
+        B.forest[slot] = A.raw(bytes);
         if (!A.ok()) return PCRCG_EWORKSPACE;
         if (dry) return PCRCG_OK;
         PCRCG_PROPAGATE(order(which == 0 ? st : sub_st, f_st));       // the input copies / the last subsampling
-        return kdforest_build_levels(level_pts[first], forest_ns[slot], lens_all + (size_t)first * nb, forest_nb[slot],
-                                     last > first ? nb : 0, level_base, forest[slot], forest_b[slot], f_st);
+        return kdforest_build_levels(level_pts[first], B.forest_ns[slot], lens_all + (size_t)first * nb, B.forest_nb[slot],
+                                     last > first ? nb : 0, level_base, B.forest[slot], bytes, f_st);
     };
 
     // nq / ns are the BOUNDS of the query / support level (grids and tables are carved for them)
     auto add_table = [&](int kind, int level, int q_level, const void* grid, const void* qgrid, float radius, const float* q,
                          const int* qlen, int nq, int ns, const int* slen, int limit, int sup_level) -> int {
+        const MetaView::Table m = meta.table((int)tables.size());
         TableRec t;
-        t.kind = kind; t.level = level; t.q_level = q_level;
-        t.idx = A.take<int64_t>((size_t)nq * limit);
-        t.counts = want_ties ? A.take<int>((size_t)nq) : nullptr;
-        t.ties = want_ties ? A.take<int>((size_t)nq) : nullptr;
-        t.meta = metas + MS * tables.size();
-        t.q = q; t.qlen = qlen; t.nq = nq; t.limit = limit; t.sup_level = sup_level; t.radius = radius;
-        t.grid = grid; t.ns = ns; t.slen = slen; t.qgrid = qgrid;
+        t.kind = kind; t.level = level; t.q_level = q_level; t.sup_level = sup_level;
+        RadiusSearch& s = t.s;
+        s.q = q; s.nq = nq; s.qlen = qlen; s.qgrid = qgrid; s.sgrid = grid; s.ns = ns; s.slen = slen;
+        s.nb = nb; s.group = group; s.radius = radius; s.cols = limit;
+        s.idx = A.take<int64_t>((size_t)nq * limit);
+        s.count = want_ties ? A.take<int>((size_t)nq) : nullptr;     // untruncated list lengths (tie restore cross-check)
+        s.tie_rows = want_ties ? A.take<int>((size_t)nq) : nullptr;  // rows holding a tie
+        s.max_count = &m.max_count(0); s.status = &m.status(); s.tie_count = want_ties ? &m.tie_rows() : nullptr;
         if (!A.ok()) return PCRCG_EWORKSPACE;
         // first pass only (the cell-cooperative search): rows with more than 128 hits (kCellListCap) and rows of a cell whose
         // neighbourhood does not fit LDS are marked and announced in the metadata; whether any table has one is known
-        // with the metadata round trip below, and only then (normally never) the redo pass runs
-        if (!dry)
-            PCRCG_PROPAGATE(radius_cells_pass(t.qgrid, q, nq, qlen, grid, ns, slen, nb, group, radius, limit, t.idx, t.counts,
-                                              t.meta, t.meta + P, t.ties, want_ties ? t.meta + P + 1 : nullptr, st, 1));
+        // with the metadata round trip, and only then (normally never) pyramid_finish launches the redo pass
+        if (!dry) PCRCG_PROPAGATE(radius_search(s, RadiusPass::first, st));
         tables.push_back(t);
         return PCRCG_OK;
     };
@@ -304,8 +323,7 @@ static int pyramid_run(const Parts& in, int n0, int nb, const pcrcg_pyramid_cfg*
     void* carried = nullptr;
     float carried_r = 0.f;
     PCRCG_PROPAGATE(order(st, sub_st));                  // the input is in place: the subsamplings may start
-    if (!one_forest) PCRCG_PROPAGATE(build_forest(0));
-    else if (L == 1) PCRCG_PROPAGATE(build_forest(0));
+    if (!one_forest || L == 1) PCRCG_PROPAGATE(build_forest(0));
     for (int l = 0; l < L; ++l) {
         const int limit = cfg->limit[l];
         const float r_conv = cfg->r_conv[l], r_pool = cfg->r_pool[l];
@@ -321,8 +339,8 @@ static int pyramid_run(const Parts& in, int n0, int nb, const pcrcg_pyramid_cfg*
         }
         // the level's subsampling first: on its own stream it runs beside the grid and the conv search below
         if (pooled && !dry)
-            PCRCG_PROPAGATE(grid_subsample_bound(pts, n, lens, nb, cfg->dl[l], 0, level_pts[l + 1], lens + nb, m_dev + l, cap[l + 1],
-                                                 overflow, sub_ws, sub_wsb, sub_st));
+            PCRCG_PROPAGATE(grid_subsample_bound(pts, n, lens, nb, cfg->dl[l], 0, level_pts[l + 1], lens + nb, meta.row_counts() + l,
+                                                 cap[l + 1], &meta.overflow(), sub_ws, sub_wsb, sub_st));
         if (pooled && l + 2 == L) PCRCG_PROPAGATE(build_forest(one_forest ? 2 : 1));      // the last subsampled level exists
         if (cfg->has_conv[l]) {
             if (carried && carried_r == r_conv) { grid = carried; grid_r = carried_r; }
@@ -349,26 +367,26 @@ static int pyramid_run(const Parts& in, int n0, int nb, const pcrcg_pyramid_cfg*
             carried_r = 2 * r_pool;
         }
     }
-    if (dry) return PCRCG_OK;
-    hipEvent_t forests_done = nullptr;
-    if (want_ties && f_st != st) {
-        PCRCG_PROPAGATE(events.make(&forests_done));
-        PCRCG_CHECK_HIP(hipEventRecord(forests_done, f_st));
+    if (!dry && want_ties && f_st != st) {
+        PCRCG_PROPAGATE(B.events.make(&B.forests_done));
+        PCRCG_CHECK_HIP(hipEventRecord(B.forests_done, f_st));
     }
+    return PCRCG_OK;
+}
 
-    // ---- the ONE round trip of the call: column counts, capacity status, rows holding ties, row counts, cloud lengths ----
-    const int nt = (int)tables.size();
-    const int meta_words = MS * max_tables + L + 1;       // (+ the reserved word and the L nb lengths: host_scratch_ints)
-    PCRCG_PROPAGATE(fetch(h_scratch, metas, meta_words, lens_all, L * nb, st, enqueue));
+// Step 2, after the ONE round trip of the call has brought MetaView's words and the cloud lengths to h_scratch + 1.
+static int pyramid_finish(const Build& B, const pcrcg_pyramid_cfg* cfg, int* h_scratch, pcrcg_batch* out, int* h_lengths,
+                          int* h_status, pcrcg_pyramid_restore* deferred, hipStream_t st) {
+    const int L = B.meta.L, P = B.meta.P, nb = B.nb, group = B.group, nt = (int)B.tables.size();
     // whatever follows on `st` (the reorder step, the caller's readers, a second attempt in the same arena) comes after the forests
-    if (forests_done) PCRCG_CHECK_HIP(hipStreamWaitEvent(st, forests_done, 0));
-    const int* hm = h_scratch + 1;
-    if (hm[MS * max_tables + L] != 0) {
+    if (B.forests_done) PCRCG_CHECK_HIP(hipStreamWaitEvent(st, B.forests_done, 0));
+    const MetaView hm{h_scratch + 1, P, L};
+    if (hm.overflow() != 0) {
         set_error("pcrcg_pyramid_build: a level keeps more rows than pcrcg_pyramid_cfg::shrink = %.3f allows -- call again with a "
                   "larger bound (1.0 always fits)", cfg->shrink);
         return PCRCG_EWORKSPACE;
     }
-    for (int i = 0; i < L * nb; ++i) h_lengths[i] = hm[meta_words + i];
+    for (int i = 0; i < L * nb; ++i) h_lengths[i] = hm.lengths()[i];
     int level_n[PCRCG_MAX_LEVELS];
     for (int l = 0; l < L; ++l) {
         level_n[l] = 0;
@@ -377,17 +395,12 @@ static int pyramid_run(const Parts& in, int n0, int nb, const pcrcg_pyramid_cfg*
     {   // tables with a row of more hits than the first pass stages (128 in the cell search, 256 in the per-query kernel): redo pass now, then the metadata once more (it appends tie rows)
         int redone = 0;
         for (int i = 0; i < nt; ++i) {
-            int widest = 0;
-            for (int p = 0; p < P; ++p) widest = hm[MS * i + p] > widest ? hm[MS * i + p] : widest;
-            const bool handed_over = (hm[MS * i + P] & kRadiusRedoStatus) != 0;     // (the redo pass clears the bit)
-            if (widest <= radius_fast_cap() && !handed_over) continue;
-            const TableRec& t = tables[i];
-            PCRCG_PROPAGATE(radius_query_pass(t.q, t.nq, t.qlen, t.ns, t.slen, nb, group, t.radius, t.grid, t.limit, t.idx,
-                                              t.counts, t.meta, t.meta + P, t.ties, want_ties ? t.meta + P + 1 : nullptr, st,
-                                              2));
+            const bool handed_over = (hm.table(i).status() & kRadiusRedoStatus) != 0;     // (the redo pass clears the bit)
+            if (hm.table(i).widest() <= radius_fast_cap() && !handed_over) continue;
+            PCRCG_PROPAGATE(radius_search(B.tables[i].s, RadiusPass::redo, st));
             ++redone;
         }
-        if (redone) PCRCG_PROPAGATE(fetch(h_scratch, metas, meta_words, lens_all, L * nb, st));
+        if (redone) PCRCG_PROPAGATE(fetch(h_scratch, B.meta.w, hm.words(), B.lens_all, L * nb, st));
     }
     // rows of group p at level l: [row0, row0 + rows)
     auto group_rows = [&](int l, int p, int* row0, int* rows) {
@@ -402,14 +415,14 @@ static int pyramid_run(const Parts& in, int n0, int nb, const pcrcg_pyramid_cfg*
         o.n_levels = L;
         int row0, rows;
         group_rows(0, p, &row0, &rows);
-        o.features = feats + row0;
+        o.features = B.feats + row0;
         o.feat_dim = 1;
         o.len_src_c = h_lengths[(size_t)(L - 1) * nb + (group > 0 ? p * group : 0)];
         for (int l = 0; l < L; ++l) {
             group_rows(l, p, &row0, &rows);
-            o.points[l] = level_pts[l] + 3 * (size_t)row0;
+            o.points[l] = B.level_pts[l] + 3 * (size_t)row0;
             o.n_points[l] = rows;
-            o.stack_lengths[l] = lens_all + (size_t)l * nb + (group > 0 ? p * group : 0);
+            o.stack_lengths[l] = B.lens_all + (size_t)l * nb + (group > 0 ? p * group : 0);
             o.neighbors[l] = pcrcg_table{nullptr, rows, 0, 1};
             o.pools[l] = pcrcg_table{nullptr, 0, 0, 1};
             o.upsamples[l] = pcrcg_table{nullptr, 0, 0, 1};
@@ -419,38 +432,38 @@ static int pyramid_run(const Parts& in, int n0, int nb, const pcrcg_pyramid_cfg*
     pcrcg_pyramid_restore& R = deferred ? *deferred : local;
     R.njobs = 0;
     for (int i = 0; i < nt; ++i) {
-        TableRec& t = tables[i];
-        const int status = hm[MS * i + P], tie_rows = hm[MS * i + P + 1];
-        if (status != 0) {
+        const TableRec& t = B.tables[i];
+        const RadiusSearch& s = t.s;
+        const MetaView::Table m = hm.table(i);
+        if (m.status() != 0) {
             set_error("pcrcg_pyramid_build: radius search capacity exceeded (table %d)", i);
             return PCRCG_ECAPACITY;
         }
-        int widest = 0;
         for (int p = 0; p < P; ++p) {
-            const int max_count = hm[MS * i + p];
-            widest = max_count > widest ? max_count : widest;
             // neighbors[:, :limit] keeps FEWER columns when the longest list is shorter (ref:datasets/dataloader.py:65-67)
-            const int cols = max_count < t.limit ? (max_count > 0 ? max_count : 0) : t.limit;
+            const int max_count = m.max_count(p);
+            const int cols = max_count < s.cols ? (max_count > 0 ? max_count : 0) : s.cols;
             int row0, rows;
             group_rows(t.q_level, p, &row0, &rows);
-            pcrcg_table tab{t.idx + (size_t)row0 * t.limit, rows, cols, t.limit};
+            pcrcg_table tab{s.idx + (size_t)row0 * s.cols, rows, cols, s.cols};
             if (t.kind == 0) out[p].neighbors[t.level] = tab;
             else if (t.kind == 1) out[p].pools[t.level] = tab;
             else out[p].upsamples[t.level] = tab;
         }
-        if (want_ties && widest > 0 && tie_rows > 0 && R.njobs < PCRCG_MAX_REORDER_JOBS) {
+        const int widest = m.widest(), tie_rows = m.tie_rows();
+        if (B.want_ties && widest > 0 && tie_rows > 0 && R.njobs < PCRCG_MAX_REORDER_JOBS) {
             pcrcg_reorder_job& j = R.jobs[R.njobs++];
-            const int fi = (one_forest || t.sup_level == 0) ? 0 : 1;
-            j.q = t.q; j.qlen = t.qlen; j.rows = t.ties; j.count = t.counts; j.idx = t.idx;
-            j.nq = level_n[t.q_level]; j.nbq = nb; j.cloud0 = one_forest ? t.sup_level * nb : (fi == 0 ? 0 : (t.sup_level - 1) * nb);
+            const int fi = (B.one_forest || t.sup_level == 0) ? 0 : 1;
+            j.q = s.q; j.qlen = s.qlen; j.rows = s.tie_rows; j.count = s.count; j.idx = s.idx;
+            j.nq = level_n[t.q_level]; j.nbq = nb; j.cloud0 = B.one_forest ? t.sup_level * nb : (fi == 0 ? 0 : (t.sup_level - 1) * nb);
             j.nrows = tie_rows;
             j.max_count = widest < 8192 ? widest : 8192;   // (tieorder.hip stages at most 8192 hits per row)
-            j.cols = t.limit; j.radius = t.radius; j.group = group;
-            j.sup = level_pts[fi]; j.forest = forest[fi]; j.forest_ns = forest_ns[fi]; j.forest_nb = forest_nb[fi];
+            j.cols = s.cols; j.radius = s.radius; j.group = group;
+            j.sup = B.level_pts[fi]; j.forest = B.forest[fi]; j.forest_ns = B.forest_ns[fi]; j.forest_nb = B.forest_nb[fi];
         }
     }
     // ---- the reference's order inside groups of exactly equal distance (tieorder.hip) ----------------------
-    R.tie_status = tie_status;
+    R.tie_status = B.tie_status;
     if (!deferred) return pcrcg_pyramid_restore_run(&R, h_status, st);
     return PCRCG_OK;
 }
@@ -460,8 +473,8 @@ extern "C" {
 size_t pcrcg_pyramid_ws_bytes(int n0, int nb, const pcrcg_pyramid_cfg* cfg) {
     if (!cfg || n0 < 0 || nb < 1 || cfg->n_levels < 1 || cfg->n_levels > PCRCG_MAX_LEVELS) return 0;
     Arena A(nullptr, 0, true);
-    const Parts none{nullptr, nullptr, nullptr, nullptr, 0};
-    if (pyramid_run(none, n0, nb, cfg, A, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr) != PCRCG_OK) return 0;
+    Build B;
+    if (pyramid_enqueue(Parts{}, n0, nb, cfg, A, nullptr, B) != PCRCG_OK) return 0;
     return A.peak + 4096;
 }
 
@@ -563,7 +576,11 @@ static int pyramid_build_checked(const Parts& in, int n0, int nb, const pcrcg_py
     Arena A(ws, ws_bytes, false);
     hipStream_t st = as_stream(stream);
     std::unique_lock<std::mutex> enqueue(*g_enqueue.of(st));
-    const int rc = pyramid_run(in, n0, nb, cfg, A, h_scratch, out, h_lengths, h_status, deferred, st, &enqueue);
+    Build B;
+    int rc = pyramid_enqueue(in, n0, nb, cfg, A, st, B);
+    // the ONE round trip of the call; the enqueue lock is released once the transfer is in the stream, before the wait
+    if (rc == PCRCG_OK) rc = fetch(h_scratch, B.meta.w, B.meta.words(), B.lens_all, cfg->n_levels * nb, st, &enqueue);
+    if (rc == PCRCG_OK) rc = pyramid_finish(B, cfg, h_scratch, out, h_lengths, h_status, deferred, st);
     if (rc == PCRCG_EWORKSPACE)
         if (A.off > ws_bytes) set_error("pcrcg_pyramid_build: arena too small (%zu needed so far, %zu given): size it with pcrcg_pyramid_ws_bytes for this cfg", A.off, ws_bytes);
     return rc;
@@ -593,3 +610,4 @@ int pcrcg_pyramid_build_parts(const float* const* pts_parts, const int* n_parts,
     return pyramid_build_checked(in, (int)n0, (int)nb, cfg, ws, ws_bytes, h_scratch, out, h_lengths, h_status, deferred, stream);
 }
 }
+

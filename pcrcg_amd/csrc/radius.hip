@@ -30,7 +30,7 @@
 #include "block_scan.h"
 #include <cstdlib>
 
-#include "common.h"
+#include "frontend.h"
 #include "cellgrid.h"
 
 namespace pcrcg {
@@ -929,127 +929,125 @@ int pcrcg_correspondences_emit(const int* stage, int cols, const int* counts, co
     return PCRCG_OK;
 }
 
-int pcrcg_radius_query(const float* q, int nq, const int* qlen, int ns, const int* slen, int nb,
-                       float radius, const void* grid, int cols, int64_t* out_idx, int* out_count,
-                       int* out_max_count, int* status, void* stream) {
-    return pcrcg_radius_query_ex(q, nq, qlen, ns, slen, nb, radius, grid, cols, out_idx, out_count, out_max_count,
-                                 status, nullptr, nullptr, stream);
-}
-
-int pcrcg_radius_query_ex(const float* q, int nq, const int* qlen, int ns, const int* slen, int nb,
-                          float radius, const void* grid, int cols, int64_t* out_idx, int* out_count,
-                          int* out_max_count, int* status, int* out_tie_rows, int* out_tie_count, void* stream) {
-    return pcrcg_radius_query_groups(q, nq, qlen, ns, slen, nb, 0, radius, grid, cols, out_idx, out_count, out_max_count,
-                                     status, out_tie_rows, out_tie_count, stream);
-}
-
-int pcrcg_radius_query_groups(const float* q, int nq, const int* qlen, int ns, const int* slen, int nb, int group,
-                              float radius, const void* grid, int cols, int64_t* out_idx, int* out_count,
-                              int* out_max_count, int* status, int* out_tie_rows, int* out_tie_count, void* stream) {
-    return pcrcg::radius_query_pass(q, nq, qlen, ns, slen, nb, group, radius, grid, cols, out_idx, out_count, out_max_count,
-                                    status, out_tie_rows, out_tie_count, as_stream(stream), 0);
-}
 }
 
 namespace pcrcg {
 int radius_fast_cap() { return kListCapFast; }
 
-// pass 0: both kernels (the public entry point).  pass 1: the first kernel only -- rows whose list does not fit its
-// 256-entry staging are marked, and out_max_count receives their true length, so a caller that reads out_max_count
-// anyway (the pyramid builder) launches pass 2 only for tables that need it: normally none.  pass 2: the redo kernel.
-int radius_query_pass(const float* q, int nq, const int* qlen, int ns, const int* slen, int nb, int group, float radius,
-                      const void* grid, int cols, int64_t* out_idx, int* out_count, int* out_max_count, int* status,
-                      int* out_tie_rows, int* out_tie_count, hipStream_t st, int pass) {
-    PCRCG_CHECK_ARG(nq >= 0 && ns >= 0 && nb >= 1 && cols >= 1 && group >= 0);
-    PCRCG_CHECK_ARG((out_tie_rows == nullptr) == (out_tie_count == nullptr));
-    PCRCG_CHECK_ARG(qlen && slen && grid && out_idx && out_max_count);
-    PCRCG_CHECK_ARG(nq == 0 || q);
-    (void)slen;
-    if (nq == 0) return PCRCG_OK;
+// the per-query kernels of a search whose arguments radius_search has checked: the first pass unless pass == redo, the
+// redo pass unless pass == first
+static int per_query_kernels(const RadiusSearch& s, RadiusPass pass, hipStream_t st) {
     bool ok;
-    GridView g = grid_view(const_cast<void*>(grid), grid_bytes(ns, nb), ns, nb, &ok);
-    const float r2 = radius * radius;  // neighbors.cpp:226
-    int blocks = (nq + kQueryWaves - 1) / kQueryWaves;
+    GridView g = grid_view(const_cast<void*>(s.sgrid), grid_bytes(s.ns, s.nb), s.ns, s.nb, &ok);
+    const float r2 = s.radius * s.radius;  // neighbors.cpp:226
+    int blocks = (s.nq + kQueryWaves - 1) / kQueryWaves;
     const int max_blocks_env = debug_opts().radius_blocks;
     // 2 workgroups (8 wavefronts) per CU, wavefronts loop over the queries: inside the pipeline a smaller grid takes less
     // from the model streams (1024 workgroups: 455 pairs/s, 512: 464, 384: 453, 256: 398), and on voxelised data every
     // workgroup appends its tie rows with one atomic on one word (4096 workgroups: 264 us per 60k-row table)
     const int max_blocks = max_blocks_env > 0 ? max_blocks_env : 256 * 2;
     if (blocks > max_blocks) blocks = max_blocks;
-    if (pass != 2) {
-        KpProfScope ev(st, nq, cols, ns, 0, 4);
+    if (pass != RadiusPass::redo) {
+        KpProfScope ev(st, s.nq, s.cols, s.ns, 0, 4);
         hipExtLaunchKernelGGL((k_radius_query<kListCapFast, false, kQueryWaves>), dim3(blocks), dim3(kQueryWaves * 64), 0, st, ev.a,
-                              ev.b, 0, q, nq, qlen, nb, r2, g, cols, reinterpret_cast<long long*>(out_idx), out_count,
-                              out_max_count, status, out_tie_rows, out_tie_count, group);
+                              ev.b, 0, s.q, s.nq, s.qlen, s.nb, r2, g, s.cols, reinterpret_cast<long long*>(s.idx), s.count,
+                              s.max_count, s.status, s.tie_rows, s.tie_count, s.group);
     }
-    // second pass: one wavefront per workgroup, 16 KB of LDS -- it finds a free slot at once on a busy GPU and
+    // redo pass: one wavefront per workgroup, 16 KB of LDS -- it finds a free slot at once on a busy GPU and
     // normally has nothing to do
     const int redo_blocks = blocks < 64 ? blocks : 64;
-    if (pass != 1)
-        hipLaunchKernelGGL((k_radius_query<kListCapFull, true, 1>), dim3(redo_blocks), dim3(64), 0, st, q, nq, qlen, nb, r2, g,
-                           cols, reinterpret_cast<long long*>(out_idx), out_count, out_max_count, status, out_tie_rows,
-                           out_tie_count, group);
+    if (pass != RadiusPass::first)
+        hipLaunchKernelGGL((k_radius_query<kListCapFull, true, 1>), dim3(redo_blocks), dim3(64), 0, st, s.q, s.nq, s.qlen, s.nb, r2,
+                           g, s.cols, reinterpret_cast<long long*>(s.idx), s.count, s.max_count, s.status, s.tie_rows,
+                           s.tie_count, s.group);
     PCRCG_CHECK_LAUNCH();
     return PCRCG_OK;
 }
-}  // namespace pcrcg
 
-namespace pcrcg {
-// The cell-cooperative search (k_radius_cells) over a query grid; pass 0: followed by the per-query second pass for the
-// rows it hands over (the public entry point), pass 1: the cell kernel only (the pyramid builder reads status / out_max
-// anyway and launches radius_query_pass(.., 2) for the tables that need it: normally none).
-int radius_cells_pass(const void* qgrid, const float* q, int nq, const int* qlen, const void* sgrid, int ns, const int* slen,
-                      int nb, int group, float radius, int cols, int64_t* out_idx, int* out_count, int* out_max_count,
-                      int* status, int* out_tie_rows, int* out_tie_count, hipStream_t st, int pass) {
-    PCRCG_CHECK_ARG(nq >= 0 && ns >= 0 && nb >= 1 && cols >= 1 && group >= 0 && radius > 0.0f);
-    PCRCG_CHECK_ARG((out_tie_rows == nullptr) == (out_tie_count == nullptr));
-    PCRCG_CHECK_ARG(qgrid && sgrid && out_idx && out_max_count);
-    PCRCG_CHECK_ARG(pass == 1 || (q && qlen && slen));
-    if (nq == 0) return PCRCG_OK;
-    bool ok;
-    GridView gq = grid_view(const_cast<void*>(qgrid), grid_bytes(nq, nb), nq, nb, &ok);
-    GridView gs = grid_view(const_cast<void*>(sgrid), grid_bytes(ns, nb), ns, nb, &ok);
-    const float r2 = radius * radius;  // neighbors.cpp:226
-    const double reach = (double)radius * (1.0 + 1e-6);
-    const int max_blocks_env = debug_opts().radius_blocks;
-    // Alone on the GPU the search is fastest with the CUs full (86 VGPRs: five workgroups per CU; 1536 workgroups -> 56 us
-    // for the 60 000-row table, 1280 -> 59).  Inside the pair engine (pass 1: the pyramid builder) the front-end stream
-    // shares the CUs with three model streams and the grid size hardly matters: 256 / 512 / 768 / 1024 / 1536 workgroups
-    // -> 457 / 463 / 461 / 460 / 463 pairs/s (same box); 512 as in rounds 1-3.
-    const int max_blocks = max_blocks_env > 0 ? max_blocks_env : (pass == 1 ? 512 : 1536);
-    int blocks = (nq + 7) / 8;                     // never more workgroups than there can be cells worth having one
-    if (blocks > max_blocks) blocks = max_blocks;
-    CellArgs ca;
-    ca.qhdr = gq.hdr; ca.qtick = gq.qtick; ca.qspts = gq.spts; ca.ckey = gq.ckey; ca.cinfo = gq.cinfo;
-    ca.shdr = gs.hdr; ca.soff = gs.soff; ca.tab = gs.tab; ca.spts = gs.spts;
-    ca.out_idx = reinterpret_cast<long long*>(out_idx); ca.out_count = out_count; ca.out_max = out_max_count;
-    ca.status = status; ca.tie_rows = out_tie_rows; ca.tie_count = out_tie_count;
-    ca.reach = reach; ca.r2 = r2; ca.nb = nb; ca.cols = cols; ca.group = group;
-    // The ticket block lives in the QUERY grid and cleans itself (the last workgroup of a shard to leave zeroes it), which
-    // is enough for the pyramid builder: it owns its grids, rebuilds them per call and walks them on one stream.  A caller
-    // of the public entry point may have aborted an earlier walk or may hand over a grid some other walk left mid-way, so
-    // here the block is reset on the launch stream first (4 KB; walks of ONE query grid must still not overlap in time:
-    // include/pcrcg.h, and pcrcg_amd/ops.py orders them by event).
-    if (pass != 1) PCRCG_CHECK_HIP(hipMemsetAsync(gq.qtick, 0, 16 * kTickStride * sizeof(int), st));
-    {
-        KpProfScope ev(st, nq, cols, ns, 1, 4);        // bench.py's radius roofline: the kernel's own start / stop events
-        hipExtLaunchKernelGGL((k_radius_cells<kCellCand, kCellListCap, kQueryWaves>), dim3(blocks), dim3(kQueryWaves * 64), 0, st,
-                              ev.a, ev.b, 0, ca);
+int radius_search(const RadiusSearch& s, RadiusPass pass, hipStream_t st) {
+    const bool cells = s.qgrid != nullptr && pass != RadiusPass::redo;       // the cell-cooperative kernel runs
+    const bool per_query = !(cells && pass == RadiusPass::first);            // a per-query kernel runs
+    PCRCG_CHECK_ARG(s.nq >= 0 && s.ns >= 0 && s.nb >= 1 && s.cols >= 1 && s.group >= 0);
+    PCRCG_CHECK_ARG((s.tie_rows == nullptr) == (s.tie_count == nullptr));
+    PCRCG_CHECK_ARG(s.sgrid && s.idx && s.max_count);
+    // only the cell kernel needs a positive radius (its reach is the radius itself); the per-query kernels compare squares
+    PCRCG_CHECK_ARG(!cells || s.radius > 0.0f);
+    // the cell kernel takes queries and cloud lengths from the two grids: only a per-query kernel reads q, qlen and slen
+    PCRCG_CHECK_ARG(!per_query || (s.qlen && s.slen && (s.nq == 0 || s.q)));
+    // behind the cell kernel (pcrcg_radius_query_cells) q is asked for even when there are no queries, as it always was
+    PCRCG_CHECK_ARG(!(cells && per_query) || s.q);
+    if (s.nq == 0) return PCRCG_OK;
+    if (cells) {
+        bool ok;
+        GridView gq = grid_view(const_cast<void*>(s.qgrid), grid_bytes(s.nq, s.nb), s.nq, s.nb, &ok);
+        GridView gs = grid_view(const_cast<void*>(s.sgrid), grid_bytes(s.ns, s.nb), s.ns, s.nb, &ok);
+        const int max_blocks_env = debug_opts().radius_blocks;
+        // Alone on the GPU the search is fastest with the CUs full (86 VGPRs: five workgroups per CU; 1536 workgroups -> 56 us
+        // for the 60 000-row table, 1280 -> 59).  Inside the pair engine (RadiusPass::first: the pyramid builder) the front-end
+        // stream shares the CUs with three model streams and the grid size hardly matters: 256 / 512 / 768 / 1024 / 1536
+        // workgroups -> 457 / 463 / 461 / 460 / 463 pairs/s (same box); 512 as in rounds 1-3.
+        const int max_blocks = max_blocks_env > 0 ? max_blocks_env : (pass == RadiusPass::first ? 512 : 1536);
+        int blocks = (s.nq + 7) / 8;                   // never more workgroups than there can be cells worth having one
+        if (blocks > max_blocks) blocks = max_blocks;
+        CellArgs ca;
+        ca.qhdr = gq.hdr; ca.qtick = gq.qtick; ca.qspts = gq.spts; ca.ckey = gq.ckey; ca.cinfo = gq.cinfo;
+        ca.shdr = gs.hdr; ca.soff = gs.soff; ca.tab = gs.tab; ca.spts = gs.spts;
+        ca.out_idx = reinterpret_cast<long long*>(s.idx); ca.out_count = s.count; ca.out_max = s.max_count;
+        ca.status = s.status; ca.tie_rows = s.tie_rows; ca.tie_count = s.tie_count;
+        ca.reach = (double)s.radius * (1.0 + 1e-6); ca.r2 = s.radius * s.radius;  // neighbors.cpp:226
+        ca.nb = s.nb; ca.cols = s.cols; ca.group = s.group;
+        // The ticket block lives in the QUERY grid and cleans itself (the last workgroup of a shard to leave zeroes it), which
+        // is enough for the pyramid builder: it owns its grids, rebuilds them per call and walks them on one stream.  A caller
+        // of the public entry point may have aborted an earlier walk or may hand over a grid some other walk left mid-way, so
+        // here the block is reset on the launch stream first (4 KB; walks of ONE query grid must still not overlap in time:
+        // include/pcrcg.h, and pcrcg_amd/ops.py orders them by event).
+        if (pass == RadiusPass::both) PCRCG_CHECK_HIP(hipMemsetAsync(gq.qtick, 0, 16 * kTickStride * sizeof(int), st));
+        {
+            KpProfScope ev(st, s.nq, s.cols, s.ns, 1, 4);  // bench.py's radius roofline: the kernel's own start / stop events
+            hipExtLaunchKernelGGL((k_radius_cells<kCellCand, kCellListCap, kQueryWaves>), dim3(blocks), dim3(kQueryWaves * 64), 0,
+                                  st, ev.a, ev.b, 0, ca);
+        }
+        PCRCG_CHECK_LAUNCH();
+        if (pass == RadiusPass::first) return PCRCG_OK;
+        return per_query_kernels(s, RadiusPass::redo, st);
     }
-    PCRCG_CHECK_LAUNCH();
-    if (pass == 1) return PCRCG_OK;
-    return radius_query_pass(q, nq, qlen, ns, slen, nb, group, radius, sgrid, cols, out_idx, out_count, out_max_count, status,
-                             out_tie_rows, out_tie_count, st, 2);
+    return per_query_kernels(s, pass, st);
 }
 }  // namespace pcrcg
 
 extern "C" {
 
+int pcrcg_radius_query(const float* q, int nq, const int* qlen, int ns, const int* slen, int nb,
+                       float radius, const void* grid, int cols, int64_t* out_idx, int* out_count,
+                       int* out_max_count, int* status, void* stream) {
+    const RadiusSearch s{q, nq, qlen, nullptr, grid, ns, slen, nb, 0, radius, cols, out_idx, out_count, out_max_count, status,
+                         nullptr, nullptr};
+    return radius_search(s, RadiusPass::both, as_stream(stream));
+}
+
+int pcrcg_radius_query_ex(const float* q, int nq, const int* qlen, int ns, const int* slen, int nb,
+                          float radius, const void* grid, int cols, int64_t* out_idx, int* out_count,
+                          int* out_max_count, int* status, int* out_tie_rows, int* out_tie_count, void* stream) {
+    const RadiusSearch s{q, nq, qlen, nullptr, grid, ns, slen, nb, 0, radius, cols, out_idx, out_count, out_max_count, status,
+                         out_tie_rows, out_tie_count};
+    return radius_search(s, RadiusPass::both, as_stream(stream));
+}
+
+int pcrcg_radius_query_groups(const float* q, int nq, const int* qlen, int ns, const int* slen, int nb, int group,
+                              float radius, const void* grid, int cols, int64_t* out_idx, int* out_count,
+                              int* out_max_count, int* status, int* out_tie_rows, int* out_tie_count, void* stream) {
+    const RadiusSearch s{q, nq, qlen, nullptr, grid, ns, slen, nb, group, radius, cols, out_idx, out_count, out_max_count, status,
+                         out_tie_rows, out_tie_count};
+    return radius_search(s, RadiusPass::both, as_stream(stream));
+}
+
 int pcrcg_radius_query_cells(const void* qgrid, const float* q, int nq, const int* qlen, const void* sgrid, int ns,
                              const int* slen, int nb, int group, float radius, int cols, int64_t* out_idx, int* out_count,
                              int* out_max_count, int* status, int* out_tie_rows, int* out_tie_count, void* stream) {
-    return pcrcg::radius_cells_pass(qgrid, q, nq, qlen, sgrid, ns, slen, nb, group, radius, cols, out_idx, out_count,
-                                    out_max_count, status, out_tie_rows, out_tie_count, as_stream(stream), 0);
+    PCRCG_CHECK_ARG(qgrid != nullptr);     // (in a RadiusSearch no query grid selects the per-query kernel: here it is an error)
+    const RadiusSearch s{q, nq, qlen, qgrid, sgrid, ns, slen, nb, group, radius, cols, out_idx, out_count, out_max_count, status,
+                         out_tie_rows, out_tie_count};
+    return radius_search(s, RadiusPass::both, as_stream(stream));
 }
 
 size_t pcrcg_radius_neighbors_ws_bytes(int ns, int nb) { return pcrcg_cellgrid_ws_bytes(ns, nb); }
@@ -1061,7 +1059,8 @@ int pcrcg_radius_neighbors_batch(const float* q, int nq, const float* sup, int n
     PCRCG_CHECK_ARG(out_max_count != nullptr);
     hipLaunchKernelGGL(k_zero2, dim3(1), dim3(1), 0, as_stream(stream), out_max_count, status);
     PCRCG_PROPAGATE(pcrcg_cellgrid_build(sup, ns, slen, nb, radius, ws, ws_bytes, stream));
-    return pcrcg_radius_query(q, nq, qlen, ns, slen, nb, radius, ws, cols, out_idx, out_count, out_max_count,
-                              status, stream);
+    const RadiusSearch s{q, nq, qlen, nullptr, ws, ns, slen, nb, 0, radius, cols, out_idx, out_count, out_max_count, status,
+                         nullptr, nullptr};
+    return radius_search(s, RadiusPass::both, as_stream(stream));
 }
 }

@@ -42,7 +42,7 @@
 #include <cstdlib>
 
 #include "block_scan.h"
-#include "common.h"
+#include "frontend.h"
 
 namespace pcrcg {
 namespace {

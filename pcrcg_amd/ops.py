@@ -179,17 +179,12 @@ class CellGrid:
             ev = torch.cuda.Event()
             ev.record(cur)
             query_grid._walk = (cur.cuda_stream, ev)
-            out = (idx, meta)
-            if want_counts or want_ties:
-                out += (counts,)
-            if want_ties:
-                out += (ties,)
-            return out
-        _lib.check(L.pcrcg_radius_query_ex(queries.data_ptr(), nq, q_lengths.data_ptr(), self.ns,
-                                           self.lengths.data_ptr(), self.nb, self.radius, self.grid.data_ptr(),
-                                           int(cols), idx.data_ptr(), _ptr(counts), meta[0:1].data_ptr(),
-                                           meta[1:2].data_ptr(), _ptr(ties), meta[2:3].data_ptr() if want_ties else None,
-                                           _stream()), "pcrcg_radius_query_ex")
+        else:
+            _lib.check(L.pcrcg_radius_query_ex(queries.data_ptr(), nq, q_lengths.data_ptr(), self.ns,
+                                               self.lengths.data_ptr(), self.nb, self.radius, self.grid.data_ptr(),
+                                               int(cols), idx.data_ptr(), _ptr(counts), meta[0:1].data_ptr(),
+                                               meta[1:2].data_ptr(), _ptr(ties), meta[2:3].data_ptr() if want_ties else None,
+                                               _stream()), "pcrcg_radius_query_ex")
         out = (idx, meta)
         if want_counts or want_ties:
             out += (counts,)

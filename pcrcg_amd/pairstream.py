@@ -341,28 +341,27 @@ class PairStreams:
                     claimed = True
                     pyr = self._pyr[f][a]
                     t1 = time.perf_counter()
-                    built = None
                     if k == 1:
                         # one pair: its tie-order restore step goes to the pair's model stream
-                        b, arena, lens_h, slot, deferred = pyr.build(items[0][1], items[0][2], defer_restore=True)
-                        batches = [b]
+                        group, defer, event = 0, True, True
                     elif self._overlap and len(sizes) == 1:
                         # overlapped builds (two front threads, one stream): when build() returns, its round trip has seen
                         # the chain through -- the tables are complete, nothing of this build is left in the front-end
                         # stream, and what IS in that stream by now is the other thread's next chain: no event from it.
                         # The restore step goes to the model stream of the build's one forward job.
-                        batches, arena, lens_h, slot, deferred = pyr.build([it[1] for it in items], [it[2] for it in items],
-                                                                           group=2, defer_restore=True)
-                        built = False
+                        group, defer, event = 2, True, False
                     else:
                         # several pairs stacked into ONE kernel chain (the chain is latency-bound: k pairs cost little
                         # more than one); the restore step covers all of them and runs here
-                        # (the pairs are handed over as PARTS: the builder copies them into its arena itself, no torch.cat)
-                        batches, arena, lens_h, slot = pyr.build([it[1] for it in items], [it[2] for it in items], group=2)
-                        deferred = None
+                        group, defer, event = 2, False, True
+                    # (the pairs are handed over as PARTS: the builder copies them into its arena itself, no torch.cat)
+                    res = pyr.build([it[1] for it in items], [it[2] for it in items], defer_restore=defer, group=group)
+                    batches, arena, lens_h, slot, deferred = (res + (None,))[:5]
+                    if group == 0:
+                        batches = [batches]
                     self._stat(arena_wait_s=t1 - t0, build_s=time.perf_counter() - t1, pairs=k, builds=1)
-                    if built is None:
-                        built = torch.cuda.Event()
+                    built = torch.cuda.Event() if event else False
+                    if event:
                         built.record(front)
                 start = 0
                 for j, n in enumerate(sizes):

@@ -6,13 +6,15 @@ The reference runs this on the CPU inside DataLoader workers and ships ten index
 here the stacked cloud is uploaded once and every table is produced in HBM.  Per level the supports
 are binned once and the conv / pool / upsample searches reuse that grid (all three use the level's
 radius, :273,:298,:301)."""
+import ctypes
 import os
 
 import numpy as np
 import torch
 
-from . import ops
+from . import _lib, ops
 from .config import as_config
+from .runner import Batch, PyramidCfg, PyramidRestore
 
 _I32 = torch.int32
 
@@ -54,8 +56,7 @@ def check_tie_status(code):
             code, TIE_STATUS_TEXT.get(code, "?")))
 
 
-def build_pyramid(points, lengths, config, neighborhood_limits, want_counts=False, tie_order=None,
-                  defer_tie_check=False, mirror=False, side_streams=None):
+def build_pyramid(points, lengths, config, neighborhood_limits, want_counts=False, tie_order=None, side_streams=None):
     """points [N0,3] f32 and lengths [B] i32 on the device -> the reference's batch dict
     (ref:datasets/dataloader.py:363-380) restricted to the keys KPFCNN.forward reads, all on the
     device: points, neighbors, pools, upsamples (int64, shadow = support count), stack_lengths,
@@ -69,13 +70,9 @@ def build_pyramid(points, lengths, config, neighborhood_limits, want_counts=Fals
       "reference"  the same through the KD-forest for every row (a cross-check of "auto");
       "index"      ascending index -- a defined order, NOT the reference's; no forest.
     None = the environment variable PCRCG_TIE_ORDER if set, else "auto".
-    mirror: build through the op-by-op Python mirror (pyramid_steps) instead of the C++ builder (same tables entry for
-    entry; want_counts / defer_tie_check / tie_order="reference" always take the mirror).
-    defer_tie_check: the restore step reports "cannot happen on sane clouds" conditions (a KD-tree with more than
-    128 pending branches on one query's path, ...) through a device status word.  By default it is read back here
-    (one more host sync); with defer_tie_check=True it is returned as out["tie_status"] ([1] i32 device tensor or
-    None) and the CALLER must pass its value to check_tie_status() once the stream has finished (a pipelining caller
-    does).
+    want_counts and tie_order="reference" take the op-by-op Python mirror (pyramid_steps: same tables entry for entry),
+    everything else the C++ builder.  Either way the restore step's status word -- "cannot happen on sane clouds"
+    conditions (a KD-tree with more than 128 pending branches on one query's path, ...) -- is read back and checked here.
 
     side_streams: (subsampling stream, KD-forest stream) -- two torch streams on hardware dispatchers OTHER than the current
     stream's and otherwise idle (pcrcg_amd.ops.streams_on_other_dispatchers() finds such): the C++ builder then runs the
@@ -88,9 +85,9 @@ def build_pyramid(points, lengths, config, neighborhood_limits, want_counts=Fals
     if not points.is_cuda:
         raise RuntimeError("pcrcg_amd.build_pyramid: points must be on a HIP device (no CPU path)")
     mode = tie_order if tie_order is not None else os.environ.get("PCRCG_TIE_ORDER", "auto")
-    if not want_counts and not defer_tie_check and mode in ("auto", "index") and not mirror:
+    if not want_counts and mode in ("auto", "index"):
         return build_pyramid_native(points, lengths, config, neighborhood_limits, mode, side_streams)
-    steps = pyramid_steps(points, lengths, config, neighborhood_limits, want_counts, tie_order, defer_tie_check)
+    steps = pyramid_steps(points, lengths, config, neighborhood_limits, want_counts, tie_order)
     try:
         while True:
             next(steps).synchronize()
@@ -98,15 +95,10 @@ def build_pyramid(points, lengths, config, neighborhood_limits, want_counts=Fals
         return done.value
 
 
-def pyramid_steps(points, lengths, config, neighborhood_limits, want_counts=False, tie_order=None,
-                  defer_tie_check=False, defer_restore=False):
-    """Generator form of build_pyramid: enqueues kernels on the current stream, yields a torch.cuda.Event whenever
-    it needs a value from the device (resume it -- under the same current stream -- once the event has passed),
-    and returns the batch dict through StopIteration.value.
-    defer_restore: do not launch the tie-order restore step (KD-forest + reorder) here; return it as
-    out["restore"] = (callable -> status tensor or None, [tensors it touches]) for the consumer to run on ITS stream
-    before it reads the tables (a pipelining caller runs it on the pair's model stream, which has slack, instead of the
-    front-end stream, which is the pipeline's bottleneck)."""
+def pyramid_steps(points, lengths, config, neighborhood_limits, want_counts=False, tie_order=None):
+    """Generator form of build_pyramid (the Python mirror): enqueues kernels on the current stream, yields a
+    torch.cuda.Event whenever it needs a value from the device (resume it -- under the same current stream -- once the
+    event has passed), and returns the batch dict through StopIteration.value."""
     config = as_config(config)
     if tie_order is None:
         tie_order = os.environ.get("PCRCG_TIE_ORDER", "auto")
@@ -186,24 +178,13 @@ def pyramid_steps(points, lengths, config, neighborhood_limits, want_counts=Fals
         tab["max_count"] = max_count
         if max_count > 0 and (tie_order == "reference" or (tie_order == "auto" and tie_rows > 0)):
             redo.append((tab, tie_rows))
-    out["tie_status"] = None
     if redo:
         for tab, _ in redo:
             tab["idx"] = out[tab["key"]][tab["layer"]]        # full-width, contiguous (trimmed views are made below)
-        all_rows = tie_order == "reference"
-        if defer_restore:
-            touched = list(in_points) + list(in_lens)
-            for tab, _ in redo:
-                touched += [t for t in (tab["idx"], tab["q"], tab["qlen"], tab["ties"], tab["counts"]) if t is not None]
-            out["restore"] = (lambda: _restore_reference_order(redo, in_points, in_lens, all_rows), touched)
-        else:
-            status = _restore_reference_order(redo, in_points, in_lens, all_rows)
-            if defer_tie_check:
-                out["tie_status"] = status
-            else:
-                status_h, ev = ops.host_copy(status)
-                yield ev
-                check_tie_status(int(status_h[0]))
+        status = _restore_reference_order(redo, in_points, in_lens, tie_order == "reference")
+        status_h, ev = ops.host_copy(status)
+        yield ev
+        check_tie_status(int(status_h[0]))
     for tab in tables:
         t = out[tab["key"]][tab["layer"]]
         if tab["max_count"] < t.shape[1]:
@@ -229,9 +210,9 @@ def _restore_reference_order(redo, level_points, level_lens, all_rows):
 
 
 class NativePyramid:
-    """Front end of one pair through pcrcg_pyramid_build (csrc/pyramid.hip): ONE call into the library enqueues the
-    whole pyramid (levels sized from the bound `shrink`; the call waits for its one host round trip itself, with the GIL
-    released).  One instance owns
+    """Front end of one pair, or of several stacked, through pcrcg_pyramid_build_parts (csrc/pyramid.hip): ONE call into the
+    library enqueues the whole pyramid (levels sized from the bound `shrink`; the call waits for its one host round trip
+    itself, with the GIL released).  One instance owns
     an arena, pinned scratch and a ring of status words; it serves one host thread / one stream at a time
     (pcrcg_amd/pairstream.py gives every worker its own).  tie_order "auto" or "index"; "reference" (every row
     through the KD-forest, a cross-check) and want_counts stay with the Python mirror pyramid_steps."""
@@ -239,15 +220,11 @@ class NativePyramid:
     STATUS_RING = 64
 
     def __init__(self, config, neighborhood_limits, tie_order=None, up_nearest=False):
-        import ctypes
-        from . import _lib
-        from .runner import Batch, PyramidCfg
         config = as_config(config)
         if tie_order is None:
             tie_order = os.environ.get("PCRCG_TIE_ORDER", "auto")
         if tie_order not in ("auto", "index"):
             raise ValueError("pcrcg_amd.NativePyramid: tie_order must be 'auto' or 'index'")
-        self._ct, self._lib, self._Batch = ctypes, _lib, Batch
         plan = _layer_plan(config)
         c = PyramidCfg()
         c.n_levels = len(plan)
@@ -262,7 +239,7 @@ class NativePyramid:
         self.scratch = torch.empty(512, dtype=_I32, pin_memory=True)
         self.status = torch.zeros(self.STATUS_RING, dtype=_I32, pin_memory=True)
         self.arena, self.shrink, self.calls = None, 0.5, 0
-        self.side = None        # set_side_stream(): a second stream for the KD-forests of the restore step
+        self.side = None        # set_side_streams(): the (subsampling, KD-forest) streams, kept alive here
 
     def set_side_streams(self, sub=None, forest=None):
         """Further torch streams of the caller's for the parts of the chain that need nothing from the searches
@@ -274,14 +251,14 @@ class NativePyramid:
 
     def restore(self, deferred, slot):
         """Enqueue a deferred tie-order restore step (build(..., defer_restore=True)) on the CURRENT stream."""
-        self._lib.check(self._lib.lib().pcrcg_pyramid_restore_run(self._ct.byref(deferred), self.status.data_ptr() + 4 * slot,
-                                                                  torch.cuda.current_stream().cuda_stream),
-                        "pcrcg_pyramid_restore_run")
+        _lib.check(_lib.lib().pcrcg_pyramid_restore_run(ctypes.byref(deferred), self.status.data_ptr() + 4 * slot,
+                                                        torch.cuda.current_stream().cuda_stream),
+                   "pcrcg_pyramid_restore_run")
 
     def build(self, points, lengths, fresh_arena=False, defer_restore=False, group=0):
         """points [N0,3] f32, lengths [B] i32 on the device -- or LISTS of such tensors, one entry per part (the pairs of a
-        grouped build): the builder copies the parts behind each other into its arena (pcrcg_pyramid_build_parts), no
-        torch.cat kernel runs; enqueues on the CURRENT stream.
+        grouped build): the builder copies the parts behind each other into its arena (pcrcg_pyramid_build_parts; one
+        tensor is a list of one), no torch.cat kernel runs; enqueues on the CURRENT stream.
         -> (pcrcg_batch mirror, arena tensor it points into, per-level cloud lengths (python lists),
             slot of this call's status word in self.status -- valid once the stream has drained).
         defer_restore: the tie-order restore step is not enqueued; a fifth value, its descriptor, is returned for
@@ -289,21 +266,25 @@ class NativePyramid:
         group: 0 = the clouds form one batch.  2 = the clouds are len(lengths) / 2 independent PAIRS stacked into one
         call (the front end's kernel chain is latency-bound: two pairs cost little more than one); the first value then
         is a ctypes array of that many pcrcg_batch mirrors, each with its own tables."""
-        ct, L = self._ct, self._lib.lib()
-        parts = isinstance(points, (list, tuple))
-        pts_l = [p.to(torch.float32).contiguous() for p in (points if parts else [points])]
-        lens_l = [l.to(_I32).contiguous() for l in (lengths if parts else [lengths])]
+        ct, L = ctypes, _lib.lib()
+        if not isinstance(points, (list, tuple)):
+            points, lengths = [points], [lengths]
+        pts_l = [p.to(torch.float32).contiguous() for p in points]
+        lens_l = [l.to(_I32).contiguous() for l in lengths]
         if not all(p.is_cuda for p in pts_l):
             raise RuntimeError("pcrcg_amd.build_pyramid: points must be on a HIP device (no CPU path)")
-        pts, lens = pts_l[0], lens_l[0]
-        n0, nb = sum(int(p.shape[0]) for p in pts_l), sum(int(l.shape[0]) for l in lens_l)
+        k, device = len(pts_l), pts_l[0].device
+        pp = (ct.c_void_p * k)(*[p.data_ptr() for p in pts_l])
+        lp = (ct.c_void_p * k)(*[l.data_ptr() for l in lens_l])
+        pn = (ct.c_int * k)(*[int(p.shape[0]) for p in pts_l])
+        ln = (ct.c_int * k)(*[int(l.shape[0]) for l in lens_l])
+        n0, nb = sum(pn), sum(ln)
         stream = torch.cuda.current_stream().cuda_stream
         if group and nb % group:
             raise RuntimeError("pcrcg_amd.NativePyramid: the number of clouds is not a multiple of `group`")
         self.cfg.group = int(group)
         nbatch = nb // group if group else 1
         h_len = (ct.c_int * (self.levels * nb))()
-        from .runner import PyramidRestore
         deferred = PyramidRestore() if defer_restore else None
         slot = self.calls % self.STATUS_RING
         self.calls += 1
@@ -313,30 +294,18 @@ class NativePyramid:
             if need == 0:
                 raise RuntimeError("pcrcg_pyramid_ws_bytes rejected the configuration")
             arena = self.arena
-            if fresh_arena or arena is None or arena.numel() < need or arena.device != pts.device:
-                arena = torch.empty(int(need), dtype=torch.uint8, device=pts.device)
+            if fresh_arena or arena is None or arena.numel() < need or arena.device != device:
+                arena = torch.empty(int(need), dtype=torch.uint8, device=device)
                 if not fresh_arena:
                     self.arena = arena
-            b = (self._Batch * nbatch)() if group else self._Batch()
-            if parts:
-                k = len(pts_l)
-                pp = (ct.c_void_p * k)(*[p.data_ptr() for p in pts_l])
-                lp = (ct.c_void_p * k)(*[l.data_ptr() for l in lens_l])
-                pn = (ct.c_int * k)(*[int(p.shape[0]) for p in pts_l])
-                ln = (ct.c_int * k)(*[int(l.shape[0]) for l in lens_l])
-                rc = L.pcrcg_pyramid_build_parts(pp, pn, lp, ln, k, ct.byref(self.cfg), arena.data_ptr(), arena.numel(),
-                                                 self.scratch.data_ptr(), ct.byref(b), h_len,
-                                                 self.status.data_ptr() + 4 * slot,
-                                                 ct.byref(deferred) if defer_restore else None, stream)
-            else:
-                rc = L.pcrcg_pyramid_build(pts.data_ptr(), n0, lens.data_ptr(), nb, ct.byref(self.cfg), arena.data_ptr(),
-                                           arena.numel(), self.scratch.data_ptr(), ct.byref(b), h_len,
-                                           self.status.data_ptr() + 4 * slot,
-                                           ct.byref(deferred) if defer_restore else None, stream)
+            b = (Batch * nbatch)() if group else Batch()
+            rc = L.pcrcg_pyramid_build_parts(pp, pn, lp, ln, k, ct.byref(self.cfg), arena.data_ptr(), arena.numel(),
+                                             self.scratch.data_ptr(), ct.byref(b), h_len, self.status.data_ptr() + 4 * slot,
+                                             ct.byref(deferred) if defer_restore else None, stream)
             if rc == -2 and self.shrink < 1.0:      # PCRCG_EWORKSPACE: this cloud keeps more rows per level than assumed
                 self.shrink = 1.0
                 continue
-            self._lib.check(rc, "pcrcg_pyramid_build")
+            _lib.check(rc, "pcrcg_pyramid_build_parts")
             break
         lens_h = [[int(h_len[l * nb + i]) for i in range(nb)] for l in range(self.levels)]
         if defer_restore:
@@ -383,9 +352,7 @@ def build_pyramid_native(points, lengths, config, neighborhood_limits, tie_order
     b, arena, lens_h, slot = nat.build(points, lengths, fresh_arena=True)
     torch.cuda.current_stream().synchronize()
     check_tie_status(int(nat.status[slot]))
-    out = nat.as_dict(b, arena, lens_h)
-    out["tie_status"] = None
-    return out
+    return nat.as_dict(b, arena, lens_h)
 
 
 def _point2node(nodes, points):

@@ -450,3 +450,96 @@ def test_build_pyramid_over_streams_of_other_dispatchers(cuda):
             assert torch.equal(got["points"][l].view(torch.int32), want["points"][l].view(torch.int32))
             for key in ("neighbors", "pools", "upsamples"):
                 assert torch.equal(got[key][l], want[key][l]), (recipe, key, l)
+
+
+def _same_pyramid(got, want, levels, tag):
+    assert got["stack_lengths_host"] == want["stack_lengths_host"], tag
+    for l in range(levels):
+        assert torch.equal(got["points"][l], want["points"][l]), (tag, l)
+        assert torch.equal(got["stack_lengths"][l], want["stack_lengths"][l]), (tag, l)
+        for key in ("neighbors", "pools", "upsamples"):
+            assert got[key][l].shape == want[key][l].shape, (tag, key, l, got[key][l].shape, want[key][l].shape)
+            assert torch.equal(got[key][l], want[key][l]), (tag, key, l)
+
+
+def _ball_pair(dev, seed=5, n=300, radius=0.02):
+    """Two clouds of n points inside a ball of `radius`, every second point snapped to a 0.005 lattice (ties, duplicates)."""
+    rng = np.random.RandomState(seed)
+    clouds = []
+    for _ in range(2):
+        d = rng.randn(n, 3)
+        d /= np.linalg.norm(d, axis=1, keepdims=True)
+        p = (d * radius * rng.rand(n, 1) ** (1.0 / 3.0)).astype(np.float32)
+        p[::2] = np.round(p[::2] / np.float32(0.005)) * np.float32(0.005)
+        clouds.append(p)
+    return torch.from_numpy(np.concatenate(clouds)).to(dev), torch.tensor([n, n], dtype=torch.int32, device=dev)
+
+
+def test_redo_pass_is_decided_and_trimmed_per_group(cuda):
+    """A grouped build whose groups differ in what the redo pass and the column trim see.  Pair A: two balls of 300 points,
+    narrower than the level-0 radius (0.0625), so every level-0 row has all 300 points of its cloud -- above what either
+    first pass stages (128, 256): the table goes through the redo pass -- and half the points sit on a lattice (tie rows).
+    Pair B: synthetic "mini".  On the CPU (oracle.frontend.oracle_batch_query at the level-0 radius) the longest level-0
+    list is 300 for pair A and 32 for pair B; the limit 320 is above both, so the two level-0 tables keep different column
+    counts from ONE metadata block (max_count per group, widest over the groups).  Each pair must come out as built alone."""
+    cfg, limits = indoor_config(), [320, 26, 30, 32]
+    pairs = [_ball_pair(cuda), _pair("mini", 0, cuda)]
+    nat = NativePyramid(cfg, limits, "auto")
+    b, arena, lens_h, slot = nat.build([p for p, _ in pairs], [l for _, l in pairs], group=2)
+    torch.cuda.synchronize()
+    assert int(nat.status[slot]) == 0 and len(b) == 2
+    got = [nat.as_dict(b[i], arena, lens_h, part=(2 * i, 2)) for i in range(2)]
+    for i, (pts, lens) in enumerate(pairs):
+        alone = NativePyramid(cfg, limits, "auto")
+        ab, a_arena, a_lens, a_slot = alone.build(pts, lens)          # group = 0
+        torch.cuda.synchronize()
+        assert int(alone.status[a_slot]) == 0
+        _same_pyramid(got[i], alone.as_dict(ab, a_arena, a_lens), cfg.num_layers, i)
+    assert got[0]["neighbors"][0].shape[1] == 300 and got[0]["neighbors"][0].shape[1] != got[1]["neighbors"][0].shape[1]
+
+
+@pytest.mark.parametrize("tie_order", ["auto", "index"])
+def test_both_c_entries_build_the_same_pyramid(cuda, tie_order):
+    """pcrcg_pyramid_build (one part, called here through ctypes) against NativePyramid.build, which always goes through
+    pcrcg_pyramid_build_parts: same tables, same lengths, status word 0."""
+    import ctypes
+    from pcrcg_amd import _lib
+    from pcrcg_amd.runner import Batch
+    cfg, limits = indoor_config(), [20, 26, 30, 32]
+    pts, lens = _pair("mini", 0, cuda)
+    nat = NativePyramid(cfg, limits, tie_order)
+    b, arena, lens_h, slot = nat.build(pts, lens, fresh_arena=True)
+    torch.cuda.synchronize()
+    assert int(nat.status[slot]) == 0
+    want = nat.as_dict(b, arena, lens_h)
+    lib = _lib.lib()
+    n0, nb = int(pts.shape[0]), int(lens.shape[0])
+    need = lib.pcrcg_pyramid_ws_bytes(n0, nb, ctypes.byref(nat.cfg))        # (nat.cfg: group 0 and the shrink that fitted)
+    assert need > 0
+    arena2 = torch.empty(int(need), dtype=torch.uint8, device=cuda)
+    scratch = torch.empty(256, dtype=torch.int32).pin_memory()
+    status = torch.full((1,), -1, dtype=torch.int32).pin_memory()
+    b2, h_len = Batch(), (ctypes.c_int * (nat.levels * nb))()
+    _lib.check(lib.pcrcg_pyramid_build(pts.data_ptr(), n0, lens.data_ptr(), nb, ctypes.byref(nat.cfg), arena2.data_ptr(),
+                                       arena2.numel(), scratch.data_ptr(), ctypes.byref(b2), h_len, status.data_ptr(), None,
+                                       torch.cuda.current_stream().cuda_stream), "pcrcg_pyramid_build")
+    torch.cuda.synchronize()
+    assert int(status[0]) == 0
+    lens_h2 = [[int(h_len[l * nb + i]) for i in range(nb)] for l in range(nat.levels)]
+    assert lens_h2 == lens_h
+    _same_pyramid(nat.as_dict(b2, arena2, lens_h2), want, cfg.num_layers, tie_order)
+
+
+def test_deferred_restore_equals_the_restore_in_line(cuda):
+    """build(defer_restore=True) + restore() on the same stream against a plain build(): T8k (tie-rich: lattice points)."""
+    cfg, limits = indoor_config(), synthetic.LIMITS["C1"]
+    pts, lens = _pair("T8k", 0, cuda)
+    nat = NativePyramid(cfg, limits, "auto")
+    b, arena, lens_h, slot = nat.build(pts, lens, fresh_arena=True)
+    later = NativePyramid(cfg, limits, "auto")
+    b2, arena2, lens_h2, slot2, deferred = later.build(pts, lens, fresh_arena=True, defer_restore=True)
+    assert deferred.njobs > 0                                      # there is a restore step to defer
+    later.restore(deferred, slot2)
+    torch.cuda.synchronize()
+    assert int(nat.status[slot]) == 0 and int(later.status[slot2]) == 0
+    _same_pyramid(later.as_dict(b2, arena2, lens_h2), nat.as_dict(b, arena, lens_h), cfg.num_layers, "T8k")
