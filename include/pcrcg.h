@@ -754,6 +754,9 @@ int pcrcg_stream_pipe_classes(void* const* streams, int n, int* cls, void* scrat
  *   out_transform [16] f64 (row-major 4 x 4) = its float64 fit, not refined; identity when no hypothesis passes or none
  *   has an inlier.  out_stats [6] f64 = (fitness = count / n, inlier_rmse = sqrt(sum / count), k, iterations = max_iteration,
  *   validations, chosen h or -1); fitness and rmse are 0 for the identity.
+ *   pcrcg_ransac does not read the grid's overflow flag: a target point with a coordinate beyond 2^20 cells of the
+ *   threshold is never found by the evaluation (no source point counts as its inlier), a moved source point beyond that
+ *   range is no inlier either, every other point is counted as usual, and nothing is reported.
  * trace (NULL, or any member NULL: not written) receives the stages for tests:
  *   samples [max_iteration, ransac_n] i32 rows drawn, pass [max_iteration] i32, xf32 / xf64 [max_iteration, 12] the fit as
  *   R (row-major) then t (zero where a check before the fit failed), valid_ids [max_validation] i32, counts

@@ -33,6 +33,78 @@ def kabsch(ps, pt):
     return R, ct - R @ cs, S
 
 
+def kabsch_reflects(ps, pt):
+    """True when kabsch's reflection fix engages (det(V U^T) < 0) for this sample."""
+    H = (ps - ps.mean(0)).T @ (pt - pt.mean(0))
+    U, _, Vt = np.linalg.svd(H)
+    return bool(np.linalg.det(Vt.T @ U.T) < 0)
+
+
+def jacobi_fit(ps, pt, dtype=np.longdouble):
+    """The fit of csrc/register.hip's hypothesis() restated operation by operation in `dtype` (np.longdouble: the 80-bit
+    yardstick of kabsch's own error; np.float64: the kernel's arithmetic): centroids, H, one-sided Jacobi on the columns of
+    H (at most 30 sweeps, a pair is skipped when |<h_p, h_q>| <= 1e-17 |h_p| |h_q|), R = v1 u1^T + v2 u2^T +
+    (v1 x v2)(u1 x u2)^T, t = ct - R cs -> (R, t, singular values descending, sigma_2 > 1e-12 sigma_1)."""
+    ps, pt = np.asarray(ps).astype(dtype), np.asarray(pt).astype(dtype)
+    n = len(ps)
+    cs, ct = np.zeros(3, dtype), np.zeros(3, dtype)
+    for s in range(n):
+        cs, ct = cs + ps[s], ct + pt[s]
+    cs, ct = cs / dtype(n), ct / dtype(n)
+    H = np.zeros((3, 3), dtype)
+    for s in range(n):
+        H = H + np.outer(ps[s] - cs, pt[s] - ct)
+    V = np.eye(3, dtype=dtype)
+    for _ in range(30):
+        rotated = False
+        for p, q in ((0, 1), (0, 2), (1, 2)):
+            al = (H[0, p] * H[0, p] + H[1, p] * H[1, p]) + H[2, p] * H[2, p]
+            be = (H[0, q] * H[0, q] + H[1, q] * H[1, q]) + H[2, q] * H[2, q]
+            ga = (H[0, p] * H[0, q] + H[1, p] * H[1, q]) + H[2, p] * H[2, q]
+            if ga == 0 or abs(ga) <= dtype(1e-17) * np.sqrt(al * be):
+                continue
+            rotated = True
+            zeta = (be - al) / (dtype(2) * ga)
+            tt = (dtype(1) if zeta >= 0 else dtype(-1)) / (abs(zeta) + np.sqrt(dtype(1) + zeta * zeta))
+            cc = dtype(1) / np.sqrt(dtype(1) + tt * tt)
+            sn = cc * tt
+            for M in (H, V):
+                mp, mq = M[:, p].copy(), M[:, q].copy()
+                M[:, p] = cc * mp - sn * mq
+                M[:, q] = sn * mp + cc * mq
+        if not rotated:
+            break
+    sg = np.sqrt((H[0] * H[0] + H[1] * H[1]) + H[2] * H[2])
+    i1 = 0
+    for c in (1, 2):
+        if sg[c] > sg[i1]:
+            i1 = c
+    i2 = 1 if i1 == 0 else 0
+    for c in range(3):
+        if c != i1 and sg[c] > sg[i2]:
+            i2 = c
+    S = np.array([sg[i1], sg[i2], sg[3 - i1 - i2]])
+    if not sg[i2] > dtype(1e-12) * sg[i1]:
+        return None, None, S, False
+    u1, u2, v1, v2 = H[:, i1] / sg[i1], H[:, i2] / sg[i2], V[:, i1], V[:, i2]
+    R = (np.outer(v1, u1) + np.outer(v2, u2)) + np.outer(np.cross(v1, v2), np.cross(u1, u2))
+    t = ct - ((R[:, 0] * cs[0] + R[:, 1] * cs[1]) + R[:, 2] * cs[2])
+    return R, t, S, True
+
+
+def kabsch_condition(S, reflects):
+    """Condition number of the Kabsch rotation: sigma_1 / (sigma_2 + d sigma_3), d = -1 with the reflection fix."""
+    S = [float(x) for x in S]
+    gap = S[1] - S[2] if reflects else S[1] + S[2]
+    return S[0] / gap if gap > 0 else np.inf
+
+
+def fit_residual(R, t, ps, pt):
+    """float64 sum of |R p_s + t - p_t|^2 over the sample."""
+    d = ps.astype(np.float64) @ np.asarray(R, np.float64).T + np.asarray(t, np.float64) - pt.astype(np.float64)
+    return float((d * d).sum())
+
+
 def hypothesis(src, tgt, corr, K, h, ransac_n, thr, sim, dist_check, seed):
     """-> (rows, passed, R, t, margin): margin = the smallest relative distance of a float64 test from its threshold
     (inf when the outcome does not depend on rounding)."""
@@ -84,6 +156,21 @@ def evaluate(src, tgt, xf32, thr):
     return int(hit.sum()), float(best[hit].astype(np.float64).sum())
 
 
+def grid_home_slot(p, thr, tsize):
+    """Home slot of the cell of point p in a target hash table of tsize slots, and the cell's key (csrc/cellgrid.h:
+    cells of (float)thr * (1 + 1e-5), coordinates biased by 2^20 and packed 21 bits each, mix32, multiply-high)."""
+    inv = 1.0 / (float(np.float32(thr)) * (1.0 + 1e-5))
+    c = [int(np.floor(float(np.float32(v)) * inv)) + (1 << 20) for v in p]
+    key = c[0] | (c[1] << 21) | (c[2] << 42)
+    x = key
+    x ^= x >> 33
+    x = (x * 0xFF51AFD7ED558CCD) & M64
+    x ^= x >> 33
+    x = (x * 0xC4CEB9FE1A85EC53) & M64
+    x ^= x >> 33
+    return ((x & 0xFFFFFFFF) * tsize) >> 32, key
+
+
 def better(a, b):
     """(count, sum, h) ordering of the selection: highest count, then lowest sum, then lowest h."""
     return a[0] > b[0] or (a[0] == b[0] and (a[1] < b[1] or (a[1] == b[1] and a[2] < b[2])))
@@ -113,6 +200,15 @@ def nn_l2(a, b):
             top = -np.partition(-s, 1, axis=1)[:, :2]
             gap[r:r + 1000] = (top[:, 0] - top[:, 1]) / scale[r:r + 1000]
     return idx, gap
+
+
+def nn_l2_distinct(a, b):
+    """nn_l2 with exact duplicate rows of b counted as ONE target: the index is the lowest of the winning row's copies
+    (equal rows score the same bits in any arithmetic, so the lowest-index rule decides) and the gap is the one to the
+    best DIFFERENT row.  The same as nn_l2 where b has no duplicate rows."""
+    ub, first = np.unique(b, axis=0, return_index=True)
+    idx, gap = nn_l2(a, ub)
+    return first[idx], gap
 
 
 def mutual_selection(score):
