@@ -426,7 +426,7 @@ int pcrcg_inject_image_features(const float* fmap, int c, int h, int w, const fl
  *   valid match i in order map[int(kx - window) : int(kx + window), int(ky - window) : int(ky + window)] = confidence[i]
  *   with (kx, ky) = keypoints0[i] (source) and keypoints1[matches[i]] (target); int() of the exact value, the bounds under
  *   numpy's slice rules (negative counts from the end, then clamps at 0; past the end clamps; start >= stop paints
- *   nothing).  A match with matches[i] >= n1 or a non-finite keypoint paints nothing.
+ *   nothing).  A match with matches[i] >= n1 or a non-finite keypoint (either of its two) paints nothing, on either map.
  *
  * Bad arguments (null pointers, sizes <= 0, h * w >= 2^31, ldx < c + 1, more than 3 frames of a side, a depth / fmap
  * size mismatch) are rejected with PCRCG_EBADARG before anything launches.

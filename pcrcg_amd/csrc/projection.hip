@@ -155,7 +155,10 @@ __global__ void __launch_bounds__(256) k_valid_maps(const float* __restrict__ kp
     for (int i = n0 - 1; i >= 0; --i) {
         const long long m = matches[i];
         if (m < 0 || m >= n1) continue;
-        const float* k = side ? kp1 + 2 * m : kp0 + 2 * (long)i;
+        const float* a = kp0 + 2 * (long)i;
+        const float* b = kp1 + 2 * m;
+        if (!(isfinite(a[0]) && isfinite(a[1]) && isfinite(b[0]) && isfinite(b[1]))) continue;   // the MATCH paints nothing
+        const float* k = side ? b : a;
         if (box_covers(k[0], k[1], wnd, mx, my, map_w, map_h)) {
             v = conf[i];
             break;

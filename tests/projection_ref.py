@@ -103,3 +103,41 @@ def load_fixture(golden_dir):
         valid.append({k: torch.from_numpy(np.ascontiguousarray(a)) for k, a in v.items()})
         j += 1
     return dict(projection=cases, valid_maps=valid, window=int(z["window"]))
+
+
+def load_edges(golden_dir):
+    """tests/golden/projection_edges.npz (scripts/make_golden_projection_edges.py): the reference's own output at the
+    projection's decision boundaries, as numpy arrays: [{name, points, depth ([H, W] or [1, H, W]), world2camera,
+    intrinsics (3x3 or 4x4), thresh, inds2d, inds3d}]."""
+    import os
+    z = np.load(os.path.join(golden_dir, "projection_edges.npz"))
+    cases = []
+    for j in range(int(z["n_cases"])):
+        pts = z[f"{j}/points"]
+        keep = np.unpackbits(z[f"{j}/keep"], count=len(pts)).astype(bool)
+        cases.append(dict(name=str(z[f"{j}/name"]), points=pts, depth=z[f"{j}/depth"], world2camera=z[f"{j}/world2camera"],
+                          intrinsics=z[f"{j}/intrinsics"], thresh=float(z[f"{j}/thresh"]),
+                          inds2d=z[f"{j}/inds2d"].astype(np.int64).reshape(-1, 2), inds3d=np.nonzero(keep)[0].astype(np.int64)))
+    return cases
+
+
+def inject_frames_ref(points, len_src, frames, c, ldx):
+    """include/pcrcg.h's rule for pcrcg_inject_frames, from project() alone: x [n, ldx] f32 = ones in columns 0..c and
+    zeros after; then per frame in write order, on the rows of its cloud that project() keeps,
+    x[rows, :c] = fmap[:, py, px].T * valid[px, py].  points [n, 3] (len_src source rows first); frames: dicts of numpy
+    arrays fmap [c, h, w], depth [h, w], world2camera, intrinsics, target, optionally valid [w, h] and thresh.
+    -> (x, winner [n] = the index of the frame each row took, -1: none)."""
+    points = np.asarray(points, F32)
+    n = len(points)
+    x = np.zeros((n, ldx), F32)
+    x[:, :c + 1] = 1
+    winner = np.full(n, -1, np.int64)
+    for j, fr in enumerate(frames):
+        lo, hi = (len_src, n) if fr.get("target") else (0, len_src)
+        i2, i3 = project(points[lo:hi], fr["depth"], fr["world2camera"], fr["intrinsics"], fr.get("thresh", 0.1))
+        feats = np.asarray(fr["fmap"], F32)[:, i2[:, 1], i2[:, 0]].T
+        if fr.get("valid") is not None:
+            feats = feats * np.asarray(fr["valid"], F32)[i2[:, 0], i2[:, 1]][:, None]
+        x[lo + i3, :c] = feats
+        winner[lo + i3] = j
+    return x, winner

@@ -30,6 +30,21 @@ def test_restatement_reproduces_the_reference(gold):
         assert 0 < len(i3) < c["points"].shape[0], c["name"]          # the depth test rejects a share of every case
 
 
+def test_restatement_reproduces_the_reference_at_the_edges():
+    """tests/golden/projection_edges.npz: the reference's own decisions on inputs with exact arithmetic -- quotients at -1,
+    in (-1, 0), at w / h and one ulp below, z = 0, z < 0, non-finite coordinates, |z - d| at thresh, thresh = 0, NaN / inf
+    / 0 depths, a 37 x 53 and a 1 x 1 frame."""
+    cases = PR.load_edges(GOLDEN)
+    assert len(cases) == 23 and sum(len(c["points"]) for c in cases) == 3270
+    for c in cases:
+        i2, i3 = PR.project(c["points"], c["depth"], c["world2camera"], c["intrinsics"], c["thresh"])
+        assert np.array_equal(i2, c["inds2d"]), c["name"]
+        assert np.array_equal(i3, c["inds3d"]), c["name"]
+    kept = {c["name"]: len(c["inds3d"]) for c in cases}
+    assert 0 < kept["borders_f1_z1.0"] < 138 and 0 < kept["frame_37x53"] < 2079 and kept["frame_1x1"] == 25
+    assert kept["thresh0.0_d1"] == kept["thresh0.0_d0"] == kept["behind_z-0.125"] == 0 and kept["behind_perm"] == 12
+
+
 def test_fixture_tells_the_rounding_apart(gold):
     """Unfused products (round after every multiply and add) change the result on the composed poses: the fixture pins the
     fused chain, not just "some float32 arithmetic"."""
