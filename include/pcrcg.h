@@ -818,6 +818,56 @@ int pcrcg_ransac_batch(const float* src, const int* src_off, const float* tgt, c
                        int distance_check, int max_iteration, int max_validation, const uint64_t* seeds,
                        double* out_transform, double* out_stats, void* ws, size_t ws_bytes, void* stream);
 
+/* ICP refinement: batched point-to-point ICP, the local pass after RANSAC's global one (csrc/icp.hip; added under ABI
+ * version 4, which it does not change).  It restates open3d 0.10's RegistrationICP with
+ * TransformationEstimationPointToPoint(false) -- what ref:datasets/kitti.py:105-121 refines its ground truth with -- as a
+ * deterministic algorithm; no bit parity with open3d is claimed.  DESIGN.md section 10 defines it, tests/icp_ref.py
+ * restates it in numpy.
+ *   Layout as pcrcg_ransac_batch's: src [n_total, 3] f32, the B pairs concatenated; src_off / tgt_off [B + 1] i32 DEVICE row
+ *   offsets; grid = pcrcg_cellgrid_build over the m_total concatenated targets with nb = B, slen = the pair lengths and
+ *   radius = (float)max_correspondence_distance (the grid holds the target points: they are not passed again).  n_max
+ *   (host) >= every pair's source length sizes the launch grid.  init [B, 16] f64 DEVICE, row-major T_0 per pair, or NULL:
+ *   the identity.  The distance d, max_iteration and the two convergence bounds are shared by all pairs of a call.
+ *   Evaluate(T): R|t rounded to fp32; every source point moved as RANSAC's evaluation moves it, ((r0 x + r1 y) + r2 z) + t0
+ *     unfused; its nearest target among the 27 cells around it, d2 = ((dx dx + dy dy) + dz dz) in fp32, the LOWEST target
+ *     index among equal d2; a correspondence iff d2 < (float)(d * d).  count = correspondences, sum = float64 sum of their
+ *     d2; fitness = count / n_b, rmse = sqrt(sum / count) (0 when count = 0).
+ *   Update: over the correspondences, with p the moved source point (the float64 value of the fp32 result) and q its
+ *     target: S_p = sum p, S_q = sum q, S_pq = sum p q^T in float64; cs = S_p / count, ct = S_q / count,
+ *     H = S_pq - S_p ct^T (an entry no larger than 1e-12 (|S_pq| + |S_p ct|) is rounding residue and counts as 0, so rows
+ *     that all found ONE target give H = 0); delta = the Kabsch fit of pcrcg_ransac from H, cs, ct (the same device function: reflection fixed,
+ *     degenerate iff sigma_2 <= 1e-12 sigma_1); T <- delta T in float64.  Every sum is reduced in a fixed order (inside a
+ *     wavefront by a shuffle tree, the eight wavefronts of a 512-row workgroup in order, the workgroups in order); there are
+ *     no floating-point atomics, so a pair's bits depend on its points and T_0 alone, not on B, its position or the run.
+ *   Loop: Evaluate(T_0); for k = 1 .. max_iteration: update, Evaluate(T_k), stop if |fitness_k - fitness_k-1| <
+ *     relative_fitness and |rmse_k - rmse_k-1| < relative_rmse (absolute differences, as open3d's).  Before an update the
+ *     pair stops, keeping T, if count < 3 or the fit is degenerate.
+ *   out_transform [B, 16] f64 = the last T; out_stats [B, 4] f64 = (fitness, rmse, count, updates applied) of its
+ *   evaluation.  A pair with n_b = 0 or m_b = 0 returns T_0, fitness 0, 0 iterations; a pair whose T_0 is not finite, or
+ *   whose n_b exceeds n_max, gets NaN in all 20 outputs (and no other pair is affected).
+ *   trace (NULL, or any member NULL: not written), for tests: transforms [B, max_iteration + 1, 16] f64 = T_k, counts
+ *   [B, max_iteration + 1] i32 and sums [B, max_iteration + 1] f64 of Evaluate(T_k), corr [max_iteration + 1, n_total] i32 =
+ *   the pair-local target index of every source row in Evaluate(T_k), or -1; entries past a pair's last evaluation are not
+ *   written.
+ *   All 2 (max_iteration + 1) + 1 launches are enqueued at once; a DEVICE `done` word per pair makes the workgroups of a
+ *   finished pair return at once, and the host reads nothing.  The entry allocates nothing and synchronises nothing.
+ *   Workspace: pcrcg_icp_batch_ws_bytes(B, n_total, m_total, max_iteration) = 152 B + 132 (n_total / 512 + B + 1) bytes plus
+ *   alignment padding (today a function of B and n_total alone); 0 for B outside 1..65535, a negative size or
+ *   max_iteration outside 1..65536.  Bad arguments (null pointers, those ranges, n_max > n_total, d <= 0, a negative or
+ *   NaN bound) are rejected with PCRCG_EBADARG and a short workspace with PCRCG_EWORKSPACE before anything launches. */
+typedef struct pcrcg_icp_trace {
+    double* transforms;
+    int* counts;
+    double* sums;
+    int* corr;
+} pcrcg_icp_trace;
+
+size_t pcrcg_icp_batch_ws_bytes(int B, int n_total, int m_total, int max_iteration);
+int pcrcg_icp_batch(const float* src, const int* src_off, int n_total, int n_max, const int* tgt_off, int m_total,
+                    const void* grid, const double* init, int B, double max_correspondence_distance, int max_iteration,
+                    double relative_fitness, double relative_rmse, double* out_transform, double* out_stats,
+                    const pcrcg_icp_trace* trace, void* ws, size_t ws_bytes, void* stream);
+
 /* Interest-point sampler: weighted sampling without replacement of S ragged segments in ONE launch, the step between the
  * network's overlap x saliency scores and pcrcg_feature_match_batch (the reference draws it on the host with
  * np.random.choice(..., replace=False, p = scores / sum), ref:lib/tester.py:152-164).  The distribution is that draw's

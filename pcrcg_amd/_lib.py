@@ -140,6 +140,11 @@ SIGNATURES = {
     "pcrcg_inlier_stats_batch": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p,
                                          c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                                          c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    # ICP refinement (registration.refine_batch)
+    "pcrcg_icp_batch_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "pcrcg_icp_batch": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, ctypes.c_double,
+                                c_int, ctypes.c_double, ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                c_void_p]),
     # interest-point sampler (registration.sample_batch)
     "pcrcg_weighted_sample_ws_bytes": (c_size_t, [c_int, c_int]),
     "pcrcg_weighted_sample_batch": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,

@@ -1,0 +1,314 @@
+// icp.hip -- batched point-to-point ICP on gfx950: the local refinement after RANSAC (register.hip).
+// ABI: include/pcrcg.h, section "ICP refinement"; DESIGN.md section 10 defines the algorithm and tests/icp_ref.py restates
+// it in numpy.
+//
+// open3d 0.10's RegistrationICP with TransformationEstimationPointToPoint(false), restated for B ragged pairs:
+//
+//   evaluate : grid (row blocks, pair), one thread per source point.  T (float64, per pair, on the device) is rounded to
+//              fp32, the point moved with the unfused fp32 arithmetic of RANSAC's evaluation and its nearest target looked
+//              up in the pair's cell grid (27 cells), minimising over (d2, target index); a correspondence iff
+//              d2 < (float)(d^2).  In the same pass every workgroup reduces, in a fixed order (wavefront shuffles, then its
+//              eight wavefronts one after the other), the count and 16 float64 sums of its correspondences: d2, the moved
+//              point p, its target q, and p q^T.
+//   update   : one wavefront per pair adds the workgroups' partial sums in workgroup order, takes fitness and rmse,
+//              applies the convergence test, fits delta (kabsch.h, the device function of RANSAC's hypotheses) and sets
+//              T <- delta T in float64 -- or finishes the pair: writes its outputs and sets its `done` word.
+//
+// All max_iteration + 1 evaluations are enqueued ahead; the host reads nothing in between.  The workgroups of a pair whose
+// `done` word is set leave at once.  No floating-point atomics: a pair's bits depend on its own points and T_0 alone.
+//
+// Compiled with -ffp-contract=off (every operation rounds where the source says).
+#include "cellgrid.h"
+#include "common.h"
+#include "kabsch.h"
+
+namespace pcrcg {
+namespace {
+
+constexpr int kIcpThreads = 512;                  // evaluation workgroup: 512 consecutive source rows of one pair
+constexpr int kIcpWaves = kIcpThreads / kWave;
+constexpr int kIcpTerms = 16;                     // sum d2 | sum p [3] | sum q [3] | sum p q^T [9]
+constexpr int kIcpMaxIteration = 1 << 16;
+constexpr int kIcpMaxBatch = 65535;               // pairs ride on a grid dimension
+
+struct IcpPair {          // the loop's state of one pair
+    double T[16];         // T_k, row-major
+    double fitness, rmse; // of Evaluate(T_k-1)
+    int done;
+    int pad;
+};
+
+struct IcpArgs {
+    const float* src;
+    const int* src_off;
+    const int* tgt_off;
+    const double* init;   // [B, 16] or null (identity)
+    IcpPair* state;       // [B]
+    int* p_cnt;           // [slots]      the workgroups' partial counts ...
+    double* p_sum;        // [slots, 16]  ... and sums; pair p's workgroups start at slot src_off[p] / 512 + p
+    double* out_t;        // [B, 16]
+    double* out_stats;    // [B, 4]
+    double* tr_t;         // [B, max_iteration + 1, 16] or null
+    int* tr_counts;       // [B, max_iteration + 1] or null
+    double* tr_sums;      // [B, max_iteration + 1] or null
+    int* tr_corr;         // [max_iteration + 1, n_total] or null
+    int n_total, n_max, max_iteration;
+    float thr2;
+    double rel_fitness, rel_rmse;
+};
+
+__device__ inline long first_slot(const IcpArgs& a, int p) { return (long)(a.src_off[p] / kIcpThreads) + p; }
+
+__global__ void __launch_bounds__(256) k_icp_init(IcpArgs a, int B) {
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= B) return;
+    IcpPair* st = a.state + p;
+    for (int e = 0; e < 16; ++e) st->T[e] = a.init ? a.init[16 * (long)p + e] : (e % 5 == 0 ? 1.0 : 0.0);
+    st->fitness = 0.0;
+    st->rmse = 0.0;
+    st->done = 0;
+    st->pad = 0;
+}
+
+// Evaluate(T_it) of every live pair; grid (row blocks, pair)
+__global__ void __launch_bounds__(kIcpThreads) k_icp_evaluate(IcpArgs a, GridView g, int it) {
+    __shared__ double s_sum[kIcpWaves][kIcpTerms];
+    __shared__ int s_cnt[kIcpWaves];
+    const int p = blockIdx.y;
+    const IcpPair* st = a.state + p;
+    if (st->done) return;
+    const int i0 = a.src_off[p], n = a.src_off[p + 1] - i0;
+    if ((long)blockIdx.x * kIcpThreads >= n) return;
+    const int j0 = a.tgt_off[p], m = a.tgt_off[p + 1] - j0;
+    float T[12];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) T[3 * r + c] = (float)st->T[4 * r + c];
+        T[9 + r] = (float)st->T[4 * r + 3];
+    }
+    const int i = blockIdx.x * kIcpThreads + threadIdx.x;
+    float px = 0.f, py = 0.f, pz = 0.f, qx = 0.f, qy = 0.f, qz = 0.f;
+    float best = a.thr2;
+    int bj = -1;
+    if (i < n && m > 0) {
+        const float* s = a.src + 3 * (long)(i0 + i);
+        const float x = s[0], y = s[1], z = s[2];
+        px = ((T[0] * x + T[1] * y) + T[2] * z) + T[9];
+        py = ((T[3] * x + T[4] * y) + T[5] * z) + T[10];
+        pz = ((T[6] * x + T[7] * y) + T[8] * z) + T[11];
+        int cx, cy, cz;
+        if (cell_coords(px, py, pz, g.hdr->inv_cell, &cx, &cy, &cz)) {      // false for a NaN or far-away point: no match
+            const Slot* tab = g.tab + 2 * (long)j0;
+            const unsigned tsize = 2u * (unsigned)m;
+            for (int c = 0; c < 27; ++c) {
+                const u64 key = cell_key(cx + c % 3 - 1, cy + (c / 3) % 3 - 1, cz + c / 9 - 1);
+                unsigned sl_i = __umulhi(mix32(key), tsize);
+                int cnt_c = 0, start = 0;
+                for (unsigned probe = 0; probe < tsize; ++probe) {
+                    const Slot sl = load_slot(&tab[sl_i]);
+                    if (sl.key == key) { cnt_c = sl.cnt; start = sl.start; break; }
+                    if (sl.key == kEmptyKey) break;
+                    sl_i = sl_i + 1 == tsize ? 0 : sl_i + 1;
+                }
+                for (int e = 0; e < cnt_c; ++e) {
+                    const float4 q = g.spts[start + e];
+                    const float dx = q.x - px, dy = q.y - py, dz = q.z - pz;
+                    const float d2 = (dx * dx + dy * dy) + dz * dz;
+                    const int j = __float_as_int(q.w);
+                    // (d2, index): the order of the points inside a cell is not defined, the lowest index of a tie is
+                    if (d2 < best || (d2 == best && j < bj)) { best = d2; bj = j; qx = q.x; qy = q.y; qz = q.z; }
+                }
+            }
+        }
+    }
+    const bool hit = bj >= 0;                 // best < thr2: bj is only ever set by a d2 below the start value or equal to a set one
+    if (a.tr_corr && i < n) a.tr_corr[(long)it * a.n_total + i0 + i] = hit ? bj - j0 : -1;
+    double v[kIcpTerms];
+    {
+        const double P[3] = {(double)px, (double)py, (double)pz}, Q[3] = {(double)qx, (double)qy, (double)qz};
+        v[0] = hit ? (double)best : 0.0;
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+            v[1 + r] = hit ? P[r] : 0.0;
+            v[4 + r] = hit ? Q[r] : 0.0;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) v[7 + 3 * r + c] = hit ? P[r] * Q[c] : 0.0;
+        }
+    }
+    // fixed order: the wavefront's tree, then (below) the eight wavefronts one after the other
+#pragma unroll
+    for (int e = 0; e < kIcpTerms; ++e)
+#pragma unroll
+        for (int sh = kWave / 2; sh >= 1; sh >>= 1) v[e] = v[e] + __shfl_down(v[e], sh, kWave);
+    const int cnt = (int)__popcll(__ballot(hit));
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+    if (lane == 0) {
+#pragma unroll
+        for (int e = 0; e < kIcpTerms; ++e) s_sum[wave][e] = v[e];
+        s_cnt[wave] = cnt;
+    }
+    __syncthreads();
+    const long slot = first_slot(a, p) + blockIdx.x;
+    if (threadIdx.x < kIcpTerms) {
+        double s = s_sum[0][threadIdx.x];
+        for (int w = 1; w < kIcpWaves; ++w) s = s + s_sum[w][threadIdx.x];
+        a.p_sum[kIcpTerms * slot + threadIdx.x] = s;
+    } else if (threadIdx.x == kIcpTerms) {
+        int c = 0;
+        for (int w = 0; w < kIcpWaves; ++w) c += s_cnt[w];
+        a.p_cnt[slot] = c;
+    }
+}
+
+// the pair's outputs and its `done` word: every later launch leaves this pair alone
+__device__ inline void icp_finish(const IcpArgs& a, int p, IcpPair* st, const double* T, double fitness, double rmse, double count,
+                                  double iterations) {
+    for (int e = 0; e < 16; ++e) a.out_t[16 * (long)p + e] = T[e];
+    double* s = a.out_stats + 4 * (long)p;
+    s[0] = fitness; s[1] = rmse; s[2] = count; s[3] = iterations;
+    st->done = 1;
+}
+
+// After Evaluate(T_it): one wavefront per pair
+__global__ void __launch_bounds__(kWave) k_icp_update(IcpArgs a, int it) {
+    __shared__ double s_tot[kIcpTerms];
+    __shared__ int s_count;
+    const int p = blockIdx.x;
+    IcpPair* st = a.state + p;
+    if (st->done) return;
+    const int n = a.src_off[p + 1] - a.src_off[p];
+    const int nblk = n <= a.n_max ? (n + kIcpThreads - 1) / kIcpThreads : 0;
+    const long slot0 = first_slot(a, p);
+    if (threadIdx.x < kIcpTerms) {
+        double s = 0.0;
+        for (int b = 0; b < nblk; ++b) s = s + a.p_sum[kIcpTerms * (slot0 + b) + threadIdx.x];
+        s_tot[threadIdx.x] = s;
+    } else if (threadIdx.x == kIcpTerms) {
+        int c = 0;
+        for (int b = 0; b < nblk; ++b) c += a.p_cnt[slot0 + b];
+        s_count = c;
+    }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    double T[16];
+    for (int e = 0; e < 16; ++e) T[e] = st->T[e];
+    if (it == 0) {
+        bool finite = n <= a.n_max;           // a pair longer than the launch grid covers: no result rather than a partial one
+        for (int e = 0; e < 16; ++e) finite = finite && fabs(T[e]) <= 1.79769313486231570815e308;
+        if (!finite) {
+            const double nan = __builtin_nan("");
+            for (int e = 0; e < 16; ++e) T[e] = nan;
+            icp_finish(a, p, st, T, nan, nan, nan, nan);
+            return;
+        }
+    }
+    const int count = s_count;
+    const double sum = s_tot[0];
+    const double fitness = n > 0 ? (double)count / (double)n : 0.0;
+    const double rmse = count > 0 ? sqrt(sum / (double)count) : 0.0;
+    const long tslot = (long)p * (a.max_iteration + 1) + it;
+    if (a.tr_t)
+        for (int e = 0; e < 16; ++e) a.tr_t[16 * tslot + e] = T[e];
+    if (a.tr_counts) a.tr_counts[tslot] = count;
+    if (a.tr_sums) a.tr_sums[tslot] = sum;
+    const bool converged = it > 0 && fabs(fitness - st->fitness) < a.rel_fitness && fabs(rmse - st->rmse) < a.rel_rmse;
+    st->fitness = fitness;
+    st->rmse = rmse;
+    if (converged || it >= a.max_iteration || count < 3) {
+        icp_finish(a, p, st, T, fitness, rmse, count, it);
+        return;
+    }
+    // Kabsch from the raw sums: centroids cs = sum p / count, ct = sum q / count, H = sum p q^T - (sum p) ct^T.  A difference
+    // that is within 1e-12 of the two magnitudes it was taken from is their rounding residue and counts as 0: every row
+    // matched to ONE target leaves H = 0 (degenerate by sigma_1 = 0), not a noise matrix with singular values of its own.
+    double cs[3], ct[3], H[3][3], R[9], t[3];
+    for (int r = 0; r < 3; ++r) { cs[r] = s_tot[1 + r] / (double)count; ct[r] = s_tot[4 + r] / (double)count; }
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) {
+            const double spq = s_tot[7 + 3 * r + c], sc = s_tot[1 + r] * ct[c];
+            const double h = spq - sc;
+            H[r][c] = fabs(h) <= 1e-12 * (fabs(spq) + fabs(sc)) ? 0.0 : h;
+        }
+    if (!kabsch_from_covariance(H, cs, ct, R, t)) {
+        icp_finish(a, p, st, T, fitness, rmse, count, it);
+        return;
+    }
+    // T <- delta T (the bottom row stays)
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 4; ++c) {
+            const double v = (R[3 * r] * T[c] + R[3 * r + 1] * T[4 + c]) + R[3 * r + 2] * T[8 + c];
+            st->T[4 * r + c] = c == 3 ? v + t[r] : v;
+        }
+}
+
+struct IcpWs {
+    IcpPair* state;
+    int* p_cnt;
+    double* p_sum;
+};
+
+size_t icp_slots(int B, int n_total) { return (size_t)n_total / kIcpThreads + (size_t)B + 1; }
+
+IcpWs carve_icp(Carver& cv, int B, int n_total) {
+    IcpWs w;
+    w.state = cv.take<IcpPair>((size_t)B);
+    w.p_cnt = cv.take<int>(icp_slots(B, n_total));
+    w.p_sum = cv.take<double>(icp_slots(B, n_total) * kIcpTerms);
+    return w;
+}
+
+}  // namespace
+}  // namespace pcrcg
+
+using namespace pcrcg;
+
+extern "C" {
+
+size_t pcrcg_icp_batch_ws_bytes(int B, int n_total, int m_total, int max_iteration) {
+    if (B < 1 || B > kIcpMaxBatch || n_total < 0 || m_total < 0 || max_iteration < 1 || max_iteration > kIcpMaxIteration) return 0;
+    Carver cv(nullptr, 0);
+    carve_icp(cv, B, n_total);
+    return cv.off;
+}
+
+int pcrcg_icp_batch(const float* src, const int* src_off, int n_total, int n_max, const int* tgt_off, int m_total,
+                    const void* grid, const double* init, int B, double max_correspondence_distance, int max_iteration,
+                    double relative_fitness, double relative_rmse, double* out_transform, double* out_stats,
+                    const pcrcg_icp_trace* trace, void* ws, size_t ws_bytes, void* stream) {
+    PCRCG_CHECK_ARG(src_off && tgt_off && grid && out_transform && out_stats && ws);
+    PCRCG_CHECK_ARG(B >= 1 && B <= kIcpMaxBatch);
+    PCRCG_CHECK_ARG(n_total >= 0 && m_total >= 0 && n_max >= 0 && n_max <= n_total);
+    PCRCG_CHECK_ARG(n_total == 0 || src);
+    PCRCG_CHECK_ARG(max_correspondence_distance > 0.0 && max_correspondence_distance < 1e18);
+    PCRCG_CHECK_ARG(max_iteration >= 1 && max_iteration <= kIcpMaxIteration);
+    PCRCG_CHECK_ARG(relative_fitness >= 0.0 && relative_rmse >= 0.0);      // (false for a NaN)
+    Carver cv(ws, ws_bytes);
+    IcpWs w = carve_icp(cv, B, n_total);
+    PCRCG_CHECK_WS(cv);
+    bool ok;
+    GridView g = grid_view(const_cast<void*>(grid), grid_bytes(m_total, B), m_total, B, &ok);
+    hipStream_t st = as_stream(stream);
+    IcpArgs a;
+    a.src = src; a.src_off = src_off; a.tgt_off = tgt_off; a.init = init;
+    a.state = w.state; a.p_cnt = w.p_cnt; a.p_sum = w.p_sum;
+    a.out_t = out_transform; a.out_stats = out_stats;
+    a.tr_t = trace ? trace->transforms : nullptr;
+    a.tr_counts = trace ? trace->counts : nullptr;
+    a.tr_sums = trace ? trace->sums : nullptr;
+    a.tr_corr = trace ? trace->corr : nullptr;
+    a.n_total = n_total; a.n_max = n_max; a.max_iteration = max_iteration;
+    a.thr2 = (float)(max_correspondence_distance * max_correspondence_distance);
+    a.rel_fitness = relative_fitness; a.rel_rmse = relative_rmse;
+    hipLaunchKernelGGL(k_icp_init, dim3((B + 255) / 256), dim3(256), 0, st, a, B);
+    PCRCG_CHECK_LAUNCH();
+    const dim3 eval_grid(n_max > 0 ? (n_max + kIcpThreads - 1) / kIcpThreads : 1, B);
+    for (int it = 0; it <= max_iteration; ++it) {
+        hipLaunchKernelGGL(k_icp_evaluate, eval_grid, dim3(kIcpThreads), 0, st, a, g, it);
+        hipLaunchKernelGGL(k_icp_update, dim3(B), dim3(kWave), 0, st, a, it);
+    }
+    PCRCG_CHECK_LAUNCH();
+    return PCRCG_OK;
+}
+
+}  // extern "C"

@@ -9,6 +9,9 @@
                                 `register(..., mutual=False, seed=seeds[b])`'s, bit for bit.
   * `ransac_pose_estimation_batch` -- the same as numpy [B,4,4] (the reference's mutual=False branch, pair by pair).
   * `feature_match_batch`    -- the nearest-neighbour lists of many pairs in one launch set.
+  * `refine_batch`           -- point-to-point ICP of many pairs in one set of launches (`BatchRefinementResult`), the
+                                local pass after RANSAC's global one; `refine` is the same for one pair.
+  * `refine_ground_truth`    -- ref:datasets/kitti.py:111-120: a KITTI ground-truth pose refined by ICP on the raw scans.
   * `mutual_correspondences` -- the mutual pairs of the inner-product score ([K,2] int64 device tensor).
   * `get_inlier_ratio`       -- device version of ref:lib/benchmark_utils.py:226-267 (same `w` / `wo` dict).
   * `inlier_ratio_batch`     -- the same ratios for many pairs and thresholds in one set of launches
@@ -354,6 +357,173 @@ def ransac_pose_estimation_batch(src_pcds, tgt_pcds, src_feats, tgt_feats, mutua
     return register_batch(src_pcds, tgt_pcds, src_feats, tgt_feats, distance_threshold, ransac_n,
                           max_iteration=max_iteration, max_validation=max_validation, seeds=seeds,
                           pairs_per_call=pairs_per_call).matrices
+
+
+_N_ICP_STATS = 4   # fitness, inlier_rmse, correspondences, updates applied
+_MAX_ICP_ITERATION = 1 << 16   # include/pcrcg.h
+
+
+class _IcpTrace(ctypes.Structure):
+    """Mirror of pcrcg_icp_trace (include/pcrcg.h)."""
+    _fields_ = [(f, ctypes.c_void_p) for f in ("transforms", "counts", "sums", "corr")]
+
+
+class BatchRefinementResult:
+    """Results of `refine_batch` for B pairs.  transformations: float64 [B,4,4] device tensor; matrices: the same as numpy
+    (from the one read); fitness, inlier_rmse: float64 numpy [B]; counts (correspondences of the last evaluation),
+    iterations (updates applied): int64 numpy [B] (-1 where the pair's start was not finite: its other outputs are NaN).
+    trace: None, or a dict of device tensors -- transforms [B, max_iteration + 1, 4, 4] (T_k), counts and sums
+    [B, max_iteration + 1] of Evaluate(T_k), corr: per pair [max_iteration + 1, n_b] int32, the target of every source row
+    or -1 (entries past a pair's last evaluation keep their fill: NaN / -1 / -2)."""
+
+    def __init__(self, buf, host, B, trace=None):
+        self.transformations = buf[:16 * B].view(B, 4, 4)
+        self.matrices = host[:16 * B].reshape(B, 4, 4).copy()
+        st = host[16 * B:].reshape(B, _N_ICP_STATS)
+        self.fitness = st[:, 0].copy()
+        self.inlier_rmse = st[:, 1].copy()
+        self.counts = np.where(np.isfinite(st[:, 2]), st[:, 2], -1).astype(np.int64)
+        self.iterations = np.where(np.isfinite(st[:, 3]), st[:, 3], -1).astype(np.int64)
+        self.trace = trace
+
+    def __len__(self):
+        return len(self.matrices)
+
+    def __repr__(self):
+        return (f"BatchRefinementResult(pairs={len(self)}, mean fitness={float(np.mean(self.fitness)):.6g}, "
+                f"mean iterations={float(np.mean(self.iterations)):.3g})")
+
+
+class RefinementResult:
+    """One pair of a BatchRefinementResult: transformation (float64 [4,4] device tensor), matrix (numpy), fitness,
+    inlier_rmse, count, iterations, trace."""
+
+    def __init__(self, batch):
+        self.transformation = batch.transformations[0]
+        self.matrix = batch.matrices[0]
+        self.fitness = float(batch.fitness[0])
+        self.inlier_rmse = float(batch.inlier_rmse[0])
+        self.count = int(batch.counts[0])
+        self.iterations = int(batch.iterations[0])
+        self.trace = batch.trace
+
+    def __repr__(self):
+        return (f"RefinementResult(fitness={self.fitness:.6g}, inlier_rmse={self.inlier_rmse:.6g}, count={self.count}, "
+                f"iterations={self.iterations})")
+
+
+def _cloud_rows(x, who, name, b):
+    shape = tuple(x.shape) if hasattr(x, "shape") else np.shape(x)
+    if len(shape) != 2 or shape[1] != 3:
+        raise ValueError(f"{who}: pair {b}: {name} must be an [N, 3] array, got shape {shape}")
+    return shape[0]
+
+
+def refine_batch(src_pcds, tgt_pcds, init, max_correspondence_distance, *, max_iteration=30, relative_fitness=1e-6,
+                 relative_rmse=1e-6, pairs_per_call=None, trace=False):
+    """Point-to-point ICP for B pairs at once (pcrcg_icp_batch; include/pcrcg.h "ICP refinement") ->
+    BatchRefinementResult.  open3d 0.10's registration_icp with TransformationEstimationPointToPoint() and
+    ICPConvergenceCriteria(relative_fitness, relative_rmse, max_iteration), deterministic: pair b's result depends on its
+    clouds and start alone, bit for bit.
+
+    Inputs: two lists of per-pair [N_b,3] / [M_b,3] points (numpy, CPU or HIP tensors; empty clouds are allowed: the pair
+    keeps its start).  init: the starts -- None (the identity), a [B,4,4] array or tensor, or a BatchRegistrationResult
+    (its device transforms are used: nothing is read back).  The distance, the iteration cap and the two bounds are
+    shared by all pairs.  pairs_per_call bounds the pairs per launch set (default: all).  Every size is checked on the
+    host before anything is uploaded or launched; all chunks write into one device buffer, read ONCE at the end."""
+    B = len(src_pcds)
+    if len(tgt_pcds) != B:
+        raise ValueError(f"refine_batch: list lengths differ ({B}, {len(tgt_pcds)})")
+    if B == 0:
+        raise ValueError("refine_batch: no pairs")
+    if isinstance(init, BatchRegistrationResult):
+        init = init.transformations
+    if init is not None:
+        ishape = tuple(init.shape) if hasattr(init, "shape") else np.shape(init)
+        if ishape != (B, 4, 4):
+            raise ValueError(f"refine_batch: init must be [{B}, 4, 4] (one start per pair), got shape {ishape}")
+    d = float(max_correspondence_distance)
+    if not 0.0 < d < 1e18:
+        raise ValueError("refine_batch: max_correspondence_distance must be positive")
+    mi = int(max_iteration)
+    if not 1 <= mi <= _MAX_ICP_ITERATION:
+        raise ValueError(f"refine_batch: max_iteration = {mi}, need 1..{_MAX_ICP_ITERATION}")
+    rf, rr = float(relative_fitness), float(relative_rmse)
+    if not (rf >= 0.0 and rr >= 0.0):
+        raise ValueError("refine_batch: relative_fitness and relative_rmse must be >= 0")
+    ns = [_cloud_rows(x, "refine_batch", "the source", b) for b, x in enumerate(src_pcds)]
+    ms = [_cloud_rows(x, "refine_batch", "the target", b) for b, x in enumerate(tgt_pcds)]
+    P = max(1, min(B if pairs_per_call is None else int(pairs_per_call), B, _MAX_BATCH))
+    chunks = [(b0, min(B, b0 + P)) for b0 in range(0, B, P)]
+    if any(max(sum(ns[b0:b1]), sum(ms[b0:b1])) > 0x7FFFFFFF for b0, b1 in chunks):
+        raise ValueError("refine_batch: more than 2^31 - 1 rows per call; lower pairs_per_call")
+    dev = _device(*src_pcds, *tgt_pcds, *([init] if init is not None else []))
+    L = _lib.lib()
+    wsb = max(L.pcrcg_icp_batch_ws_bytes(b1 - b0, sum(ns[b0:b1]), sum(ms[b0:b1]), mi) for b0, b1 in chunks)
+    if wsb == 0:
+        raise ValueError("refine_batch: sizes out of range for the batch workspace")
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    out = torch.empty(B * (16 + _N_ICP_STATS), dtype=torch.float64, device=dev)
+    init_d = None
+    if init is not None:
+        init_d = (init if isinstance(init, torch.Tensor) else torch.from_numpy(np.asarray(init, dtype=np.float64)))
+        init_d = init_d.to(device=dev, dtype=torch.float64).contiguous()
+    tr = None
+    if trace:
+        tr = {"transforms": torch.full((B, mi + 1, 4, 4), float("nan"), dtype=torch.float64, device=dev),
+              "counts": torch.full((B, mi + 1), -1, dtype=torch.int32, device=dev),
+              "sums": torch.full((B, mi + 1), float("nan"), dtype=torch.float64, device=dev), "corr": []}
+    for b0, b1 in chunks:
+        nb = b1 - b0
+        n_tot, m_tot = sum(ns[b0:b1]), sum(ms[b0:b1])
+        src = _cat(src_pcds[b0:b1], dev, "src_pcds", 3)
+        tgt = _cat(tgt_pcds[b0:b1], dev, "tgt_pcds", 3)
+        offs = torch.tensor(np.concatenate([np.cumsum([0] + ns[b0:b1]), np.cumsum([0] + ms[b0:b1]), ms[b0:b1]]),
+                            dtype=torch.int32, device=dev)
+        src_off, tgt_off, lengths = offs[:nb + 1], offs[nb + 1:2 * nb + 2], offs[2 * nb + 2:]
+        gbytes = L.pcrcg_cellgrid_ws_bytes(m_tot, nb)
+        grid = torch.empty(gbytes, dtype=torch.uint8, device=dev)
+        _lib.check(L.pcrcg_cellgrid_build(tgt.data_ptr() if m_tot else None, m_tot, lengths.data_ptr(), nb, d, grid.data_ptr(),
+                                          gbytes, _stream()), "pcrcg_cellgrid_build")
+        tr_ptr = None
+        if trace:
+            corr = torch.full((mi + 1, n_tot), -2, dtype=torch.int32, device=dev)
+            tr["corr"] += list(corr.split(ns[b0:b1], dim=1))
+            tr_ptr = ctypes.byref(_IcpTrace(tr["transforms"][b0:].data_ptr(), tr["counts"][b0:].data_ptr(),
+                                            tr["sums"][b0:].data_ptr(), corr.data_ptr()))
+        _lib.check(L.pcrcg_icp_batch(src.data_ptr() if n_tot else None, src_off.data_ptr(), n_tot, max(ns[b0:b1]),
+                                     tgt_off.data_ptr(), m_tot, grid.data_ptr(),
+                                     init_d[b0:].data_ptr() if init_d is not None else None, nb, d, mi, rf, rr,
+                                     out[16 * b0:].data_ptr(), out[16 * B + _N_ICP_STATS * b0:].data_ptr(), tr_ptr,
+                                     ws.data_ptr(), wsb, _stream()), "pcrcg_icp_batch")
+    return BatchRefinementResult(out, _read(out), B, tr)
+
+
+def refine(src_pcd, tgt_pcd, init, max_correspondence_distance, *, max_iteration=30, relative_fitness=1e-6,
+           relative_rmse=1e-6, trace=False):
+    """Point-to-point ICP of one pair -> RefinementResult: refine_batch with a batch of one (init: None or a [4,4]
+    start)."""
+    if init is not None:
+        ishape = tuple(init.shape) if hasattr(init, "shape") else np.shape(init)
+        if ishape != (4, 4):
+            raise ValueError(f"refine: init must be a [4, 4] transform, got shape {ishape}")
+        init = init[None] if isinstance(init, (torch.Tensor, np.ndarray)) else np.asarray(init, dtype=np.float64)[None]
+    return RefinementResult(refine_batch([src_pcd], [tgt_pcd], init, max_correspondence_distance,
+                                         max_iteration=max_iteration, relative_fitness=relative_fitness,
+                                         relative_rmse=relative_rmse, trace=trace))
+
+
+def refine_ground_truth(xyz0, xyz1, M):
+    """ref:datasets/kitti.py:111-120 -> float64 numpy [4,4]: the KITTI ground-truth pose M refined on the raw scans.  xyz0 is
+    moved by M as the reference's apply_transform moves it (xyz0 @ R.T + T), ICP runs from the identity with a
+    correspondence distance of 0.2 and 200 iterations, and M @ T is returned (the reference's convention)."""
+    M = np.asarray(M, dtype=np.float64)
+    if M.shape != (4, 4):
+        raise ValueError(f"refine_ground_truth: M must be a [4, 4] transform, got shape {M.shape}")
+    xyz0 = np.asarray(xyz0.cpu() if isinstance(xyz0, torch.Tensor) else xyz0)
+    moved = xyz0 @ M[:3, :3].T + M[:3, 3]
+    T = refine(moved.astype(np.float32), xyz1, None, 0.2, max_iteration=200).matrix
+    return M @ T
 
 
 _MAX_SAMPLE_SEED = 1 << 24   # segment seeds of pcrcg_weighted_sample_batch (include/pcrcg.h)

@@ -16,7 +16,7 @@ import tempfile
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-EXACT = {"grid_subsample.hip", "radius.hip", "tieorder.hip", "register.hip", "projection.hip", "chamfer.hip"}   # Makefile: EXACT_SRC
+EXACT = {"grid_subsample.hip", "radius.hip", "tieorder.hip", "register.hip", "icp.hip", "projection.hip", "chamfer.hip"}   # Makefile: EXACT_SRC
 
 
 def assembly(root, src, out):

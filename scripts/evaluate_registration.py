@@ -13,10 +13,12 @@ recall (FMR) lines of benchmark.feature_match_recall, without and with the mutua
 and added to the summary.
 
   python scripts/evaluate_registration.py --source_path snapshot/.../test/pth --gt_folder configs/benchmarks/3DMatch \\
-      --exp_dir snapshot/.../est_traj [--n_points 250 500 1000 2500 5000] [--inlier_ratio] [--sampler device]
+      --exp_dir snapshot/.../est_traj [--n_points 250 500 1000 2500 5000] [--inlier_ratio] [--sampler device] [--icp DIST]
 
 --sampler device draws the interest points of all records on the GPU in one launch (registration.sample_batch: the same
 distribution from its own seeded stream, record b with sample seed --seed + b) instead of on the host generator.
+--icp DIST refines every RANSAC pose by point-to-point ICP on the record's full clouds with correspondence distance DIST
+(registration.refine_batch); without it the poses are RANSAC's, as before.
 """
 import argparse
 import json
@@ -51,6 +53,8 @@ def main():
     ap.add_argument("--inlier_ratio", action="store_true", help="also report the inlier ratio and feature-match recall")
     ap.add_argument("--inlier_distance", type=float, default=0.1, help="inlier distance threshold of IR / FMR (m)")
     ap.add_argument("--fmr_threshold", type=float, default=0.05, help="inlier ratio above which a pair counts for FMR")
+    ap.add_argument("--icp", type=float, default=None, metavar="DIST",
+                    help="refine every pose by ICP on the full clouds with this correspondence distance (default: off)")
     a = ap.parse_args()
 
     files = sorted((f for f in os.listdir(a.source_path) if f.endswith(".pth")), key=natural_key)
@@ -61,6 +65,8 @@ def main():
         raise SystemExit(f"{len(records)} records for {sum(len(k) for k in keys)} gt pairs in {a.gt_folder}")
     summary = {}
     sampling = dict(sampler=a.sampler, sample_seeds=[(a.seed + b) % (1 << 23) for b in range(len(records))])
+    if a.icp is not None:
+        sampling["refine"] = a.icp
     for n_points in a.n_points:
         np.random.seed(a.seed)
         if a.inlier_ratio:
