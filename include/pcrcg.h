@@ -58,7 +58,9 @@ const char* pcrcg_last_error(void);
  *   (pcrcg_inlier_stats_batch_ws_bytes, pcrcg_inlier_stats_batch), added after those, and the 2-D backbone
  *   (pcrcg_res50unet_arena_bytes, pcrcg_res50unet_pack, pcrcg_res50unet_ws_bytes, pcrcg_res50unet_forward), added after those,
  *   and the ModelNet evaluation's Chamfer distance (pcrcg_chamfer_batch_ws_bytes, pcrcg_chamfer_batch), added after those,
- *   and the interest-point sampler (pcrcg_weighted_sample_ws_bytes, pcrcg_weighted_sample_batch), added after those. */
+ *   and the interest-point sampler (pcrcg_weighted_sample_ws_bytes, pcrcg_weighted_sample_batch), added after those,
+ *   and the voxel down-sampling of raw scans (pcrcg_voxel_down_sample_ws_bytes, pcrcg_voxel_down_sample_batch), added after
+ *   that. */
 #define PCRCG_ABI_VERSION 4
 int pcrcg_abi_version(void);
 
@@ -867,6 +869,40 @@ int pcrcg_icp_batch(const float* src, const int* src_off, int n_total, int n_max
                     const void* grid, const double* init, int B, double max_correspondence_distance, int max_iteration,
                     double relative_fitness, double relative_rmse, double* out_transform, double* out_stats,
                     const pcrcg_icp_trace* trace, void* ws, size_t ws_bytes, void* stream);
+
+/* Voxel down-sampling: open3d's PointCloud::VoxelDownSample for B ragged clouds in one set of launches (csrc/voxel.hip;
+ * added under ABI version 4, which it does not change) -- what ref:datasets/kitti.py:134-140 does to both raw scans of a
+ * pair before anything else sees them, and how raw 3DMatch fragments become the 2.5 cm clouds of ref:datasets/indoor.py.
+ * It is NOT pcrcg_grid_subsample_batch: that grid starts at floor(min / dl) * dl and works in fp32; this one starts at
+ * min - voxel_size / 2 and works in float64.  DESIGN.md section 14 defines it, tests/voxel_ref.py restates it in numpy.
+ *   Layout: pts [n_total, 3] f32, the B clouds concatenated; off [B + 1] i32 DEVICE row offsets, never read by the host.
+ *   out_pts [n_total, 3] f64 (capacity: the input rows); cloud b's rows follow cloud b-1's with no gap.  out_len [B] i32.
+ *   out_first, out_count [n_total] i32, each optional (NULL: not written): per output row, the cloud-local index of the first
+ *   input point of its voxel, and how many points the row averaged.
+ *   Definition, per cloud; every step in IEEE float64 from the exactly widened fp32 coordinates, unfused:
+ *     vmin = (min over the cloud) - 0.5 * voxel_size, per axis;  idx = (int)floor((p - vmin) / voxel_size), per axis;
+ *     points with equal idx form a voxel; its row is (the sum of its points, added one by one in ascending input index,
+ *     starting from 0.0) / (double)count.
+ *   Row order: open3d emits rows in the iteration order of its hash map, an artefact of its hash and of the standard
+ *     library it was built with.  That order is NOT reproduced, and -- as for pcrcg_icp_batch -- no bit parity with open3d
+ *     is claimed.  Rows come in ascending index of each voxel's first input point.  The reference's consumers
+ *     (get_correspondences, the collate function) take the down-sampled clouds as they come, so any fixed order is
+ *     consistent downstream.
+ *   Determinism: a cloud's output bits depend on its own points and voxel_size alone -- not on B, its position in the batch
+ *     or the run.  There are no floating-point atomics: one thread adds a voxel's points in order (a cloud that falls into
+ *     one voxel is slow but correct).
+ *   Rejected clouds get out_len[b] = -1 and no rows, and affect no other cloud: a cloud with a non-finite coordinate, and a
+ *     cloud whose index on any axis would reach 2^21, the limit of the key packing (open3d's "voxel_size is too small").
+ *   An empty cloud gets out_len[b] = 0.  Offsets that do not describe a range inside n_total (off[b] < 0, off[b] >
+ *     off[b + 1], off[b + 1] > n_total), or that step back over an earlier accepted range, read as an empty cloud.
+ *   Rows of out_pts / out_first / out_count past the last one written keep what they held.
+ *   The entry allocates nothing, synchronises nothing and enqueues everything (at most 12 launches) at once on `stream`.
+ *   Null pts / off / out_pts / out_len / ws, B outside 1..65535, n_total < 0 or above 2^30, and a voxel_size that is not
+ *   finite or not positive are rejected with PCRCG_EBADARG before any launch; a short workspace with PCRCG_EWORKSPACE.
+ *   Workspace: pcrcg_voxel_down_sample_ws_bytes(B, n_total), about 68 bytes per row; 0 for the same bad sizes. */
+size_t pcrcg_voxel_down_sample_ws_bytes(int B, int n_total);
+int pcrcg_voxel_down_sample_batch(const float* pts, const int* off, int n_total, int B, double voxel_size, double* out_pts,
+                                  int* out_len, int* out_first, int* out_count, void* ws, size_t ws_bytes, void* stream);
 
 /* Interest-point sampler: weighted sampling without replacement of S ragged segments in ONE launch, the step between the
  * network's overlap x saliency scores and pcrcg_feature_match_batch (the reference draws it on the host with

@@ -145,6 +145,10 @@ SIGNATURES = {
     "pcrcg_icp_batch": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, ctypes.c_double,
                                 c_int, ctypes.c_double, ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
                                 c_void_p]),
+    # voxel down-sampling of raw scans (pcrcg_amd/kitti.py)
+    "pcrcg_voxel_down_sample_ws_bytes": (c_size_t, [c_int, c_int]),
+    "pcrcg_voxel_down_sample_batch": (c_int, [c_void_p, c_void_p, c_int, c_int, ctypes.c_double, c_void_p, c_void_p, c_void_p,
+                                              c_void_p, c_void_p, c_size_t, c_void_p]),
     # interest-point sampler (registration.sample_batch)
     "pcrcg_weighted_sample_ws_bytes": (c_size_t, [c_int, c_int]),
     "pcrcg_weighted_sample_batch": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,

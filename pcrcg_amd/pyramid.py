@@ -383,13 +383,15 @@ def collate_fn_descriptor(list_data, config, neighborhood_limits, device=None, s
     assert len(list_data) == 1
     device = torch.device(device if device is not None else "cuda")
     item = list_data[0]
-    src = torch.as_tensor(np.asarray(item["src_pcd"]), dtype=torch.float32).to(device)
-    tgt = torch.as_tensor(np.asarray(item["tgt_pcd"]), dtype=torch.float32).to(device)
+    def f32(x):    # a tensor is taken as it is, wherever it lives (kitti.prepare_pairs hands over device tensors)
+        t = x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x))
+        return t.to(device=device, dtype=torch.float32)
+
+    src, tgt = f32(item["src_pcd"]), f32(item["tgt_pcd"])
     points = torch.cat([src, tgt], 0)
     lengths = torch.tensor([src.shape[0], tgt.shape[0]], dtype=_I32, device=device)
     out = build_pyramid(points, lengths, config, neighborhood_limits, side_streams=side_streams)
-    feats = np.concatenate([np.asarray(item["src_feats"]), np.asarray(item["tgt_feats"])], 0)
-    out["features"] = torch.as_tensor(feats, dtype=torch.float32).to(device)
+    out["features"] = torch.cat([f32(item["src_feats"]), f32(item["tgt_feats"])], 0)
     out["rot"] = torch.as_tensor(np.asarray(item["rot"])).to(device)
     out["trans"] = torch.as_tensor(np.asarray(item["trans"])).to(device)
     corr = item["correspondences"]
