@@ -1021,6 +1021,21 @@ int pcrcg_res50unet_forward(const float* arena, void* const* h_state, int n_tens
                             int n_images, int h, int w, int joint_stats, int training, float* out, void* ws, size_t ws_bytes,
                             void* stream);
 
+/* Decoded RGB-D frames to the loader's tensors (ref:datasets/indoor.py:63-78: transforms.Resize(size, Image.NEAREST) +
+ * transforms.ToTensor, and the depth frames' `/ 1000.0`), F colour and G depth frames in ONE launch (csrc/frames.hip).
+ *   color [F, H, W, 3] uint8 (a decoded PNG's rows)  -> color_out [F, 3, oh, ow] f32 = (float)v / 255.0f;
+ *   depth [G, Hd, Wd] uint16 (a 16-bit PNG's rows)   -> depth_out [G, ohd, owd] f32 = (float)(int16_t)v / 1000.0f.
+ *   The int16 reading is the reference's: ToTensor takes PIL mode I;16 through np.int16, so the sensor's "no reading" value
+ *   65535 becomes -0.001 and every raw value of 32768 or more comes out negative.  Both divisions are IEEE fp32 divisions.
+ *   Nearest rule (PIL's Image.NEAREST, not torch's interpolate): output index i of an axis n_in -> n_out reads input index
+ *   min(floor((i + 0.5) * n_in / n_out), n_in - 1), evaluated in float64.
+ *   The colour frames of a call share one input and one output size, and so do the depth frames; either count may be 0 (its
+ *   pointers and sizes are then ignored).  Plain stores, no atomics, no workspace; nothing is allocated or synchronised.
+ *   Bad arguments (F + G outside 1..65535, a null pointer or a side outside 1..32768 of a kind whose count is not 0) are
+ *   rejected with PCRCG_EBADARG before anything launches. */
+int pcrcg_prepare_frames(const uint8_t* color, int F, int H, int W, int oh, int ow, float* color_out, const uint16_t* depth,
+                         int G, int Hd, int Wd, int ohd, int owd, float* depth_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -35,6 +35,21 @@ int pcrcg_correspondences_rows(const float* src, int n, const double* trans, dou
                                const void* grid, int cols, int* stage, int* counts, int* max_count, void* stream);
 int pcrcg_correspondences_emit(const int* stage, int cols, const int* counts, const int64_t* offsets, int n, int64_t* out,
                                void* stream);
+/* The same for B pairs (1..65535) in one call, the contract of the two entries above per pair.  src [n_total, 3]: the
+ * sources of all pairs concatenated, src_off [B + 1] i32 DEVICE row offsets; the targets likewise (m_total rows), in a
+ * `grid` = pcrcg_cellgrid_build over them with nb = B and the B target lengths, so that every pair has its own hash table
+ * and a source row only ever meets targets of its own pair.  trans: DEVICE array of B row-major float64 4x4 transforms.
+ * One radius and one keep for all pairs.  A row finds its pair by a binary search in src_off.
+ *   _rows : stage [n_total, cols] / counts [n_total] / max_count as above; staged target indices are local to the pair.
+ *   _emit : out [sum(counts), 2] int64 = (source index, target index), both local to the pair, pairs in order and
+ *           source-major inside each; offsets [n_total] = exclusive scan of counts (int64).  Pair b's rows of `out` are
+ *           those between offsets[src_off[b]] and offsets[src_off[b + 1]].
+ * The offsets live on the device and are not read by the host; they must be ascending and end at n_total. */
+int pcrcg_correspondences_batch_rows(const float* src, const int* src_off, int n_total, int B, const double* trans,
+                                     double radius, int keep, int m_total, const void* grid, int cols, int* stage, int* counts,
+                                     int* max_count, void* stream);
+int pcrcg_correspondences_batch_emit(const int* stage, int cols, const int* counts, const int64_t* offsets, const int* src_off,
+                                     int n_total, int B, int64_t* out, void* stream);
 
 /* MetricLoss's dense parts with their gradients (ref:lib/loss.py:71-135; csrc/lossops.hip).
  * pcrcg_circle_loss: n <= 512 matched descriptor pairs a, b [n, c] (c <= 64) and their coordinate distances

@@ -164,6 +164,9 @@ SIGNATURES = {
     "pcrcg_res50unet_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
     "pcrcg_res50unet_forward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int,
                                         c_void_p, c_void_p, c_size_t, c_void_p]),
+    # decoded RGB-D frames to the loader's tensors (pcrcg_amd/indoor.py)
+    "pcrcg_prepare_frames": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                                     c_int, c_void_p, c_void_p]),
     # include/pcrcg_train.h -- the "next" rows
     "pcrcg_gemm_f32_ex": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int,
                                   c_void_p, c_void_p, c_void_p]),
@@ -196,6 +199,10 @@ SIGNATURES = {
     "pcrcg_correspondences_rows": (c_int, [c_void_p, c_int, c_void_p, ctypes.c_double, c_int, c_int, c_void_p, c_int, c_void_p,
                                            c_void_p, c_void_p, c_void_p]),
     "pcrcg_correspondences_emit": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    "pcrcg_correspondences_batch_rows": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, ctypes.c_double, c_int, c_int,
+                                                 c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pcrcg_correspondences_batch_emit": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p,
+                                                 c_void_p]),
     "pcrcg_kpfcnn_train_ws_bytes": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "pcrcg_kpfcnn_train_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_void_p,
                                            c_void_p, c_void_p]),

@@ -780,39 +780,36 @@ __global__ void k_zero2(int* a, int* b) {
 constexpr int kCorrCap = 1024;       // staged hits per source point (48 KB of LDS per workgroup)
 struct CorrXf { double r[9], t[3]; };
 
-__global__ void __launch_bounds__(256) k_correspond_rows(const float* __restrict__ src, int n, CorrXf xf, double radius,
-                                                          GridView g, int keep, int cols, int* __restrict__ stage,
-                                                          int* __restrict__ counts, int* __restrict__ max_count) {
-    __shared__ double s_d[4][kCorrCap];
-    __shared__ int s_i[4][kCorrCap];
-    __shared__ int s_excl[4][32];
-    __shared__ int s_start[4][32];
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int i = blockIdx.x * 4 + wave;
-    if (i >= n) return;
-    const double sx = src[3 * (long)i], sy = src[3 * (long)i + 1], sz = src[3 * (long)i + 2];
-    const double px = xf.r[0] * sx + xf.r[1] * sy + xf.r[2] * sz + xf.t[0];
-    const double py = xf.r[3] * sx + xf.r[4] * sy + xf.r[5] * sz + xf.t[1];
-    const double pz = xf.r[6] * sx + xf.r[7] * sy + xf.r[8] * sz + xf.t[2];
+struct CorrLds {                     // one workgroup's staging: four wavefronts, one source point each
+    double d[4][kCorrCap];
+    int i[4][kCorrCap];
+    int excl[4][32];
+    int start[4][32];
+};
+
+// One wavefront, one source point (already moved, float64) against ONE cloud's hash table: `tab` / `tsize` are that
+// cloud's slots (tsize = 0: the cloud is empty), `first` the index of its first support (staged indices are local to it).
+__device__ __forceinline__ void correspond_row(CorrLds& s, int wave, int lane, long i, double px, double py, double pz,
+                                               double radius, const GridView& g, const Slot* __restrict__ tab, unsigned tsize,
+                                               int first, int keep, int cols, int* __restrict__ stage,
+                                               int* __restrict__ counts, int* __restrict__ max_count) {
     int cx, cy, cz;
     const bool inrange = cell_coords((float)px, (float)py, (float)pz, g.hdr->inv_cell, &cx, &cy, &cz);
-    const int ns = g.hdr->ns;
     int ccount = 0, cstart = 0;
-    if (lane < 27 && inrange && ns > 0) {
+    if (lane < 27 && inrange && tsize > 0) {
         const int dx = lane % 3 - 1, dy = (lane / 3) % 3 - 1, dz = lane / 9 - 1;
         const u64 key = cell_key(cx + dx, cy + dy, cz + dz);
-        const unsigned tsize = 2u * (unsigned)ns;
-        unsigned s = __umulhi(mix32(key), tsize);
+        unsigned sl_i = __umulhi(mix32(key), tsize);
         for (unsigned probe = 0; probe < tsize; ++probe) {
-            const Slot sl = load_slot(&g.tab[s]);
+            const Slot sl = load_slot(&tab[sl_i]);
             if (sl.key == key) { ccount = sl.cnt; cstart = sl.start; break; }
             if (sl.key == kEmptyKey) break;
-            s = s + 1 == tsize ? 0 : s + 1;
+            sl_i = sl_i + 1 == tsize ? 0 : sl_i + 1;
         }
     }
     const int incl = wave_incl_scan_i32(ccount, lane);
     const int total = __shfl(incl, 26, 64);
-    if (lane < 32) { s_excl[wave][lane] = lane < 27 ? incl - ccount : 0x7FFFFFFF; s_start[wave][lane] = cstart; }
+    if (lane < 32) { s.excl[wave][lane] = lane < 27 ? incl - ccount : 0x7FFFFFFF; s.start[wave][lane] = cstart; }
     __builtin_amdgcn_wave_barrier();
     int nhit = 0;
     for (int base = 0; base < total; base += 64) {
@@ -821,14 +818,14 @@ __global__ void __launch_bounds__(256) k_correspond_rows(const float* __restrict
         int lo = 0;
 #pragma unroll
         for (int step = 16; step >= 1; step >>= 1)
-            if (s_excl[wave][lo + step] <= tc) lo += step;
-        const float4 p = g.spts[s_start[wave][lo] + (tc - s_excl[wave][lo])];
+            if (s.excl[wave][lo + step] <= tc) lo += step;
+        const float4 p = g.spts[s.start[wave][lo] + (tc - s.excl[wave][lo])];
         const double ex = (double)p.x - px, ey = (double)p.y - py, ez = (double)p.z - pz;
         const double d = sqrt(ex * ex + ey * ey + ez * ez);
         const bool hit = t < total && d < radius;
         const u64 mask = __ballot(hit);
         const int pos = nhit + __popcll(mask & ((1ull << lane) - 1ull));
-        if (hit && pos < kCorrCap) { s_d[wave][pos] = d; s_i[wave][pos] = __float_as_int(p.w); }
+        if (hit && pos < kCorrCap) { s.d[wave][pos] = d; s.i[wave][pos] = __float_as_int(p.w) - first; }
         nhit += __popcll(mask);
     }
     __builtin_amdgcn_wave_barrier();
@@ -841,15 +838,53 @@ __global__ void __launch_bounds__(256) k_correspond_rows(const float* __restrict
     // rank by (float64 distance, target index); ranks below the cut go to the staging row (only if it is wide enough:
     // the caller re-runs with cols >= max_count otherwise)
     for (int e = lane; e < nl; e += 64) {
-        const double md = s_d[wave][e];
-        const int mi = s_i[wave][e];
+        const double md = s.d[wave][e];
+        const int mi = s.i[wave][e];
         int rank = 0;
         for (int j = 0; j < nl; ++j) {
-            const double od = s_d[wave][j];
-            rank += (od < md || (od == md && s_i[wave][j] < mi)) ? 1 : 0;
+            const double od = s.d[wave][j];
+            rank += (od < md || (od == md && s.i[wave][j] < mi)) ? 1 : 0;
         }
-        if (rank < kept && rank < cols) stage[(long)i * cols + rank] = mi;
+        if (rank < kept && rank < cols) stage[i * cols + rank] = mi;
     }
+}
+
+__global__ void __launch_bounds__(256) k_correspond_rows(const float* __restrict__ src, int n, CorrXf xf, double radius,
+                                                          GridView g, int keep, int cols, int* __restrict__ stage,
+                                                          int* __restrict__ counts, int* __restrict__ max_count) {
+    __shared__ CorrLds s;
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int i = blockIdx.x * 4 + wave;
+    if (i >= n) return;
+    const double sx = src[3 * (long)i], sy = src[3 * (long)i + 1], sz = src[3 * (long)i + 2];
+    const double px = xf.r[0] * sx + xf.r[1] * sy + xf.r[2] * sz + xf.t[0];
+    const double py = xf.r[3] * sx + xf.r[4] * sy + xf.r[5] * sz + xf.t[1];
+    const double pz = xf.r[6] * sx + xf.r[7] * sy + xf.r[8] * sz + xf.t[2];
+    const int ns = g.hdr->ns;
+    correspond_row(s, wave, lane, i, px, py, pz, radius, g, g.tab, ns > 0 ? 2u * (unsigned)ns : 0u, 0, keep, cols, stage, counts,
+                   max_count);
+}
+
+// B pairs in one launch: row i belongs to the pair whose range of src_off holds it, is moved by that pair's transform
+// (xf [B, 16] float64 row-major 4x4, DEVICE) and searches that pair's table of a grid built over all targets with nb = B
+// (cloud b's slots: cellgrid.h), so it can only ever meet targets of its own pair.  Staged indices are local to the pair.
+__global__ void __launch_bounds__(256) k_correspond_rows_batch(const float* __restrict__ src, const int* __restrict__ src_off,
+                                                                int n, int nb, const double* __restrict__ xf, double radius,
+                                                                GridView g, int keep, int cols, int* __restrict__ stage,
+                                                                int* __restrict__ counts, int* __restrict__ max_count) {
+    __shared__ CorrLds s;
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int i = blockIdx.x * 4 + wave;
+    if (i >= n) return;
+    const int b = __builtin_amdgcn_readfirstlane(cloud_of(src_off, nb, i));
+    const double* m = xf + 16 * (long)b;
+    const double sx = src[3 * (long)i], sy = src[3 * (long)i + 1], sz = src[3 * (long)i + 2];
+    const double px = m[0] * sx + m[1] * sy + m[2] * sz + m[3];
+    const double py = m[4] * sx + m[5] * sy + m[6] * sz + m[7];
+    const double pz = m[8] * sx + m[9] * sy + m[10] * sz + m[11];
+    const int first = g.soff[b], nsb = g.soff[b + 1] - first;
+    correspond_row(s, wave, lane, i, px, py, pz, radius, g, g.tab + 2l * first, nsb > 0 ? 2u * (unsigned)nsb : 0u, first, keep,
+                   cols, stage, counts, max_count);
 }
 
 __global__ void __launch_bounds__(256) k_correspond_emit(const int* __restrict__ stage, int cols, const int* __restrict__ counts,
@@ -862,6 +897,23 @@ __global__ void __launch_bounds__(256) k_correspond_emit(const int* __restrict__
     const long long o = offsets[i];
     for (int e = lane; e < c; e += 64) {
         out[2 * (o + e)] = i;
+        out[2 * (o + e) + 1] = stage[(long)i * cols + e];
+    }
+}
+// the same for the rows of B pairs: both indices local to the row's pair (the staged targets already are)
+__global__ void __launch_bounds__(256) k_correspond_emit_batch(const int* __restrict__ stage, int cols,
+                                                                const int* __restrict__ counts,
+                                                                const long long* __restrict__ offsets,
+                                                                const int* __restrict__ src_off, int n, int nb,
+                                                                long long* __restrict__ out) {
+    const int lane = threadIdx.x & 63;
+    const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= n) return;
+    const int c = counts[i];
+    const long long o = offsets[i];
+    const int local = i - src_off[cloud_of(src_off, nb, i)];
+    for (int e = lane; e < c; e += 64) {
+        out[2 * (o + e)] = local;
         out[2 * (o + e) + 1] = stage[(long)i * cols + e];
     }
 }
@@ -925,6 +977,32 @@ int pcrcg_correspondences_emit(const int* stage, int cols, const int* counts, co
     PCRCG_CHECK_ARG(stage && counts && offsets && out);
     hipLaunchKernelGGL(k_correspond_emit, dim3((n + 3) / 4), dim3(256), 0, as_stream(stream), stage, cols, counts,
                        reinterpret_cast<const long long*>(offsets), n, reinterpret_cast<long long*>(out));
+    PCRCG_CHECK_LAUNCH();
+    return PCRCG_OK;
+}
+
+int pcrcg_correspondences_batch_rows(const float* src, const int* src_off, int n_total, int B, const double* trans,
+                                     double radius, int keep, int m_total, const void* grid, int cols, int* stage, int* counts,
+                                     int* max_count, void* stream) {
+    PCRCG_CHECK_ARG(B >= 1 && B <= 65535 && n_total >= 0 && m_total >= 0 && cols >= 1 && keep >= 0 && radius > 0.0);
+    PCRCG_CHECK_ARG(src_off && trans && grid && counts && max_count);
+    if (n_total == 0) return PCRCG_OK;
+    PCRCG_CHECK_ARG(src && stage);
+    bool ok;
+    GridView g = grid_view(const_cast<void*>(grid), grid_bytes(m_total, B), m_total, B, &ok);
+    hipLaunchKernelGGL(k_correspond_rows_batch, dim3((n_total + 3) / 4), dim3(256), 0, as_stream(stream), src, src_off, n_total,
+                       B, trans, radius, g, keep, cols, stage, counts, max_count);
+    PCRCG_CHECK_LAUNCH();
+    return PCRCG_OK;
+}
+
+int pcrcg_correspondences_batch_emit(const int* stage, int cols, const int* counts, const int64_t* offsets, const int* src_off,
+                                     int n_total, int B, int64_t* out, void* stream) {
+    PCRCG_CHECK_ARG(B >= 1 && B <= 65535 && n_total >= 0 && cols >= 1);
+    if (n_total == 0) return PCRCG_OK;
+    PCRCG_CHECK_ARG(stage && counts && offsets && src_off && out);
+    hipLaunchKernelGGL(k_correspond_emit_batch, dim3((n_total + 3) / 4), dim3(256), 0, as_stream(stream), stage, cols, counts,
+                       reinterpret_cast<const long long*>(offsets), src_off, n_total, B, reinterpret_cast<long long*>(out));
     PCRCG_CHECK_LAUNCH();
     return PCRCG_OK;
 }
