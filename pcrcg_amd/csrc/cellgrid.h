@@ -80,14 +80,20 @@ __device__ __forceinline__ unsigned mix32(u64 x) {
     return (unsigned)x;
 }
 
-__device__ __forceinline__ bool cell_coords(float x, float y, float z, double inv_cell, int* cx, int* cy, int* cz) {
-    const double fx = floor((double)x * inv_cell), fy = floor((double)y * inv_cell), fz = floor((double)z * inv_cell);
+// The cell of a float64 point: a point that was never an fp32 value (a source point moved in float64) must not be rounded to
+// one first -- from about 100 m out half an fp32 ulp exceeds what a cell is wider than the radius by (4e-6 m at 0.0375 with the
+// 1e-4 of correspondences.py), and the rounded point's 27 cells then miss targets the point's own 27 hold.
+__device__ __forceinline__ bool cell_coords(double x, double y, double z, double inv_cell, int* cx, int* cy, int* cz) {
+    const double fx = floor(x * inv_cell), fy = floor(y * inv_cell), fz = floor(z * inv_cell);
     const double lim = (double)(kCoordBias - 2);
     const bool ok = fx > -lim && fx < lim && fy > -lim && fy < lim && fz > -lim && fz < lim;
     *cx = ok ? (int)fx + kCoordBias : 0;
     *cy = ok ? (int)fy + kCoordBias : 0;
     *cz = ok ? (int)fz + kCoordBias : 0;
     return ok;
+}
+__device__ __forceinline__ bool cell_coords(float x, float y, float z, double inv_cell, int* cx, int* cy, int* cz) {
+    return cell_coords((double)x, (double)y, (double)z, inv_cell, cx, cy, cz);
 }
 __device__ __forceinline__ u64 cell_key(int cx, int cy, int cz) {
     return (u64)(unsigned)cx | ((u64)(unsigned)cy << 21) | ((u64)(unsigned)cz << 42);

@@ -794,7 +794,7 @@ __device__ __forceinline__ void correspond_row(CorrLds& s, int wave, int lane, l
                                                int first, int keep, int cols, int* __restrict__ stage,
                                                int* __restrict__ counts, int* __restrict__ max_count) {
     int cx, cy, cz;
-    const bool inrange = cell_coords((float)px, (float)py, (float)pz, g.hdr->inv_cell, &cx, &cy, &cz);
+    const bool inrange = cell_coords(px, py, pz, g.hdr->inv_cell, &cx, &cy, &cz);     // the float64 point's own cell: not (float)p's
     int ccount = 0, cstart = 0;
     if (lane < 27 && inrange && tsize > 0) {
         const int dx = lane % 3 - 1, dy = (lane / 3) % 3 - 1, dz = lane / 9 - 1;

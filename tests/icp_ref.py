@@ -5,6 +5,18 @@ import numpy as np
 from . import ransac_ref as RR
 
 EPS32 = 2.0 ** -24          # unit roundoff of fp32
+COORD_BIAS = 1 << 20        # csrc/cellgrid.h kCoordBias: cell_coords accepts |floor(x / cell)| < COORD_BIAS - 2
+
+
+def grid_cell(d):
+    """The cell of the target grid refine_batch builds for the distance d (pcrcg_cellgrid_build takes a float radius)."""
+    return float(np.float32(d)) * (1.0 + 1e-5)
+
+
+def grid_rejects(p, d):
+    """cell_coords on moved points p [n,3] -> [n] bool: True where the point has no cell (far away or not finite)."""
+    f = np.floor(np.asarray(p, np.float64) * (1.0 / grid_cell(d)))
+    return ~((f > -(COORD_BIAS - 2)) & (f < COORD_BIAS - 2)).all(1)
 
 
 def xf32(T):
@@ -65,6 +77,39 @@ def update(src, tgt, T, corr):
     delta = np.eye(4)
     delta[:3, :3], delta[:3, 3] = R, t
     return delta, S
+
+
+def raw_sum_update(src, tgt, T, corr):
+    """k_icp_update's formula in float64 numpy (not its summation order): the sums of p, q and p q^T over the correspondences,
+    cs = sum p / n, ct = sum q / n, H = sum p q^T - (sum p) ct^T with a difference within 1e-12 of its two magnitudes set to
+    0, then the fit from H (np.linalg.svd) and t = ct - R cs -> delta [4,4] float64."""
+    hit = corr >= 0
+    n = float(hit.sum())
+    p = move(src, T)[hit].astype(np.float64)
+    q = tgt[corr[hit]].astype(np.float64)
+    sp, sq = p.sum(0), q.sum(0)
+    spq = (p[:, :, None] * q[:, None, :]).sum(0)
+    cs, ct = sp / n, sq / n
+    sc = np.outer(sp, ct)
+    h = spq - sc
+    H = np.where(np.abs(h) <= 1e-12 * (np.abs(spq) + np.abs(sc)), 0.0, h)
+    U, S, Vt = np.linalg.svd(H)
+    sign = np.sign(np.linalg.det(Vt.T @ U.T)) or 1.0
+    R = Vt.T @ np.diag([1.0, 1.0, sign]) @ U.T
+    delta = np.eye(4)
+    delta[:3, :3], delta[:3, 3] = R, ct - R @ cs
+    return delta
+
+
+def centred_update_longdouble(src, tgt, T, corr):
+    """The same step as a centred fit in np.longdouble (ransac_ref.jacobi_fit: centroids first, H from the centred points)
+    -> delta [4,4] np.longdouble."""
+    hit = corr >= 0
+    R, t, _, ok = RR.jacobi_fit(move(src, T)[hit], tgt[corr[hit]], np.longdouble)
+    assert ok
+    delta = np.eye(4, dtype=np.longdouble)
+    delta[:3, :3], delta[:3, 3] = R, t
+    return delta
 
 
 def converged(fit, rmse, fit_prev, rmse_prev, relative_fitness=1e-6, relative_rmse=1e-6):
