@@ -60,7 +60,8 @@ const char* pcrcg_last_error(void);
  *   and the ModelNet evaluation's Chamfer distance (pcrcg_chamfer_batch_ws_bytes, pcrcg_chamfer_batch), added after those,
  *   and the interest-point sampler (pcrcg_weighted_sample_ws_bytes, pcrcg_weighted_sample_batch), added after those,
  *   and the voxel down-sampling of raw scans (pcrcg_voxel_down_sample_ws_bytes, pcrcg_voxel_down_sample_batch), added after
- *   that. */
+ *   that, and the decoded-frame conversion (pcrcg_prepare_frames), and the ModelNet pair preparation (pcrcg_modelnet_crop,
+ *   pcrcg_modelnet_assemble), added after those. */
 #define PCRCG_ABI_VERSION 4
 int pcrcg_abi_version(void);
 
@@ -1035,6 +1036,52 @@ int pcrcg_res50unet_forward(const float* arena, void* const* h_state, int n_tens
  *   rejected with PCRCG_EBADARG before anything launches. */
 int pcrcg_prepare_frames(const uint8_t* color, int F, int H, int W, int oh, int ow, float* color_out, const uint16_t* depth,
                          int G, int Hd, int Wd, int ohd, int owd, float* depth_out, void* stream);
+
+/* ModelNet pair preparation: the data-parallel part of ref:datasets/transforms.py (RandomCrop, RandomTransformSE3_euler,
+ * Resampler, RandomJitter, ShufflePoints) for many clouds in one launch each, after the host has drawn the random numbers
+ * in the reference's order (csrc/modelnet.hip, pcrcg_amd/modelnet_prep.py).
+ *
+ * pcrcg_modelnet_crop -- RandomCrop.crop for C clouds.  pts [n_total, ld] f32, ld = 3 or 6 (xyz first); cloud c is rows
+ *   off[c] .. off[c+1] (off [C+1] i32, on the device).  Per cloud: mode[c] (0 keep every row, 1 dist > 0, 2 percentile),
+ *   dir [C, 3] f64 (the plane's normal), lo[c] and gamma[c] (the percentile's lower order statistic and its weight; read in
+ *   mode 2 only).  kept [n_total] i32 receives, at rows off[c] .. off[c] + count[c], the kept rows' indices local to the
+ *   cloud in ascending order (rows past the count are not written); count [C] i32 the number kept.
+ *   Arithmetic contract (the file is compiled with -ffp-contract=off):
+ *     centroid   the three columns added in f32 in row order, then divided by (float)n -- numpy's np.mean(axis=0) of a
+ *                float32 array, bit for bit (a tree sum would round differently);
+ *     dist       (f64(cx) * d0 + f64(cy) * d1) + f64(cz) * d2 with c = p - centroid in f32, nothing fused;
+ *     threshold  mode 1: 0.  mode 2: numpy's 'linear' percentile of dist -- with a, b the lo-th and (lo+1)-th smallest
+ *                distances (0-based), a + (b - a) * gamma, or b - (b - a) * (1 - gamma) when gamma >= 0.5; a itself when
+ *                lo + 1 == n.  lo is clamped to 0 .. n - 1;
+ *     mask       a row is kept iff dist > threshold, the literal comparison: rows that tie with the threshold are dropped,
+ *                as numpy drops them (no rank cut);
+ *     order      the compaction is stable.
+ *   One workgroup per cloud with the distances resident in LDS; the order statistics come from a bitonic sort of a copy.  A
+ *   workgroup holds PCRCG_MODELNET_CROP_MAX_ROWS rows (two float64 arrays of that length are 128 KiB of gfx950's 160 KiB);
+ *   max_rows is the caller's statement of the longest cloud and sizes the LDS of the launch: max_rows above the capacity
+ *   is rejected with PCRCG_EBADARG before anything is launched, and a cloud longer than max_rows gets count -1.
+ *   count -1 also marks a cloud with a non-finite x, y or z, and a mode outside 0..2.  dir and gamma are the caller's: a
+ *   non-finite one makes the distances or the threshold NaN, every comparison false and the count 0 (nothing else happens).  An offsets pair that does not describe a
+ *   range inside the stack (negative, descending, past n_total) reads as an empty cloud: count 0.  No argument can cause
+ *   an out-of-bounds access.  No workspace, no atomics, nothing allocated or synchronised.
+ *
+ * pcrcg_modelnet_assemble -- one output row per thread: out[i] = f32(f64(T . raw[kept[pick[i]]]) + noise[i]).
+ *   raw [n_total, ld], in_off [C+1]: the input stack as above; kept / kept_count: pcrcg_modelnet_crop's outputs, or both
+ *   NULL (every row kept).  The m_total output rows form K output clouds: rows out_off[k] .. out_off[k+1] (out_off [K+1])
+ *   read input cloud out_cloud[k]; out_flags[k] bit 0: the cloud is moved by tf[k] ([K, 12] f32, a row-major [3, 4]), bit
+ *   1: its rows receive noise ([m_total, 3] f64, in output order).  tf or noise may be NULL: the flag then does nothing.
+ *   pick [m_total] i32 indexes the input cloud's kept list.  Arithmetic: xyz = ((x r0 + y r1) + z r2) + t in unfused f32;
+ *   then f32(f64(v) + noise) per coordinate; normals (ld = 6) = (u r0 + v r1) + w r2, no translation, no noise; an
+ *   untouched value is copied.  out [m_total, ld] f32.  A pick outside the kept list, a kept index outside its cloud, or a
+ *   bad cloud index or offsets pair writes a row of NaN; a row that belongs to no output cloud is left alone.  No
+ *   out-of-bounds access is possible through the device arrays. */
+#define PCRCG_MODELNET_CROP_MAX_ROWS 8192
+int pcrcg_modelnet_crop(const float* pts, int ld, int n_total, const int* off, int C, int max_rows, const int* mode,
+                        const double* dir, const int* lo, const double* gamma, int* kept, int* count, void* stream);
+int pcrcg_modelnet_assemble(const float* raw, int ld, int n_total, const int* in_off, int C, const int* kept,
+                            const int* kept_count, const int* out_off, const int* out_cloud, const int* out_flags,
+                            const float* tf, int K, const int* pick, const double* noise, int m_total, float* out,
+                            void* stream);
 
 #ifdef __cplusplus
 }

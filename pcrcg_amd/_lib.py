@@ -167,6 +167,11 @@ SIGNATURES = {
     # decoded RGB-D frames to the loader's tensors (pcrcg_amd/indoor.py)
     "pcrcg_prepare_frames": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                                      c_int, c_void_p, c_void_p]),
+    # ModelNet pair preparation (pcrcg_amd/modelnet_prep.py)
+    "pcrcg_modelnet_crop": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                    c_void_p, c_void_p, c_void_p]),
+    "pcrcg_modelnet_assemble": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                        c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     # include/pcrcg_train.h -- the "next" rows
     "pcrcg_gemm_f32_ex": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int,
                                   c_void_p, c_void_p, c_void_p]),

@@ -55,9 +55,11 @@ def kitti_config(**over):
 
 def modelnet_config(**over):
     """ModelNet40 configuration (ref:configs/test/modelnet.yaml:12-35): three levels, the `modelnet` block list with two
-    consecutive unary blocks in the decoder (ref:configs/models.py:42-57)."""
+    consecutive unary blocks in the decoder (ref:configs/models.py:42-57); and the dataset block's keys that
+    modelnet_prep.prepare_pairs reads (:70-74: partial, num_points, noise_type, rot_mag, trans_mag)."""
     cfg = Config(_COMMON, dataset="modelnet", num_layers=3, first_feats_dim=512, final_feats_dim=96, first_subsampling_dl=0.06,
-                 conv_radius=2.75, gnn_feats_dim=256, overlap_radius=0.04)
+                 conv_radius=2.75, gnn_feats_dim=256, overlap_radius=0.04,
+                 partial=[0.7, 0.7], num_points=1024, noise_type="crop", rot_mag=45.0, trans_mag=0.5)
     cfg.update(over)
     cfg["architecture"] = list(architectures[cfg["dataset"]])
     return cfg

@@ -236,3 +236,23 @@ def modelnet_pairs(B, seed, n=1024, keep=0.7, n_raw=2048):
         out.append({"points_src": src.astype(np.float32), "points_ref": views[1].astype(np.float32),
                     "points_raw": raw.astype(np.float32), "transform_gt": pose[:3].astype(np.float32)})
     return out
+
+
+def modelnet_clouds(S, seed, n_raw=2048):
+    """S ModelNet-shaped raw clouds with normals, what ref:datasets/modelnet.py _read_h5_files returns as `data`
+    ([S, n_raw, 6] float32: xyz and unit normals): the wavy torus of modelnet_pairs with its analytic normals (the
+    normalised cross product of the surface's two partial derivatives).  Input of modelnet_prep.prepare_pairs."""
+    out = np.empty((S, n_raw, 6), dtype=np.float32)
+    for b in range(S):
+        rng = np.random.RandomState([seed, b])
+        u, v = rng.rand(n_raw) * 2 * np.pi, rng.rand(n_raw) * 2 * np.pi
+        r_major, r_minor, d_minor = 0.6, 0.25 + 0.08 * np.sin(3 * u), 0.24 * np.cos(3 * u)
+        w = r_major + r_minor * np.cos(v)
+        p = np.stack([w * np.cos(u), w * np.sin(u), r_minor * np.sin(v)], 1)
+        du = np.stack([d_minor * np.cos(v) * np.cos(u) - w * np.sin(u), d_minor * np.cos(v) * np.sin(u) + w * np.cos(u),
+                       d_minor * np.sin(v)], 1)
+        dv = np.stack([-r_minor * np.sin(v) * np.cos(u), -r_minor * np.sin(v) * np.sin(u), r_minor * np.cos(v)], 1)
+        nrm = np.cross(du, dv)
+        nrm /= np.linalg.norm(nrm, axis=1, keepdims=True)
+        out[b] = np.concatenate([p, nrm], 1)
+    return out
