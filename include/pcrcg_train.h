@@ -72,6 +72,19 @@ size_t pcrcg_weighted_bce_ws_bytes(void);
  * the gradients for the next accumulation.  One launch. */
 int pcrcg_sgd_step(float* params, float* grads, float* momentum_buf, long n, float lr, float momentum, float weight_decay,
                    int zero_grads, void* stream);
+/* torch.optim.Adam(lr, betas, eps, weight_decay) with amsgrad and maximize off and L2 (not decoupled) weight decay over the
+ * same FLAT buffers plus the two moment buffers (all four of n floats, 16-byte aligned; ref:main.py:66-72,
+ * ref:configs/train/pram_cofi.yaml:60-63).  `step` >= 1 is the number of THIS step, the value torch's state['step'] holds
+ * after it; zeroed moment buffers and step = 1 give torch's first step.  Per element, in fp32 with IEEE sqrt and division:
+ *   d = g + wd p;  m = m + (d - m)(1 - beta1);  v = beta2 v + (1 - beta2)(d d);
+ *   p = p - (lr / bc1) (m / (sqrt(v) / sqrt(bc2) + eps)),   bc1 = 1 - beta1^step,  bc2 = 1 - beta2^step
+ * (torch's lerp form of the first moment for beta1 > 0.5).  1 - beta1, 1 - beta2, lr / bc1 and sqrt(bc2) are computed in
+ * double inside the entry and rounded to float once, where torch computes them -- which is why the betas arrive as doubles:
+ * 1 - (double)0.999f is 1.3e-5 off 1 - 0.999, a hundred times fp32's own error in exp_avg_sq.  beta1, beta2 in [0, 1), else
+ * PCRCG_EBADARG.  zero_grads != 0 also clears the gradients.  A slot with p = g = m = v = 0 (the padding between parameter
+ * slices) stays exactly 0 for eps > 0.  One launch; 16 B read and 12 or 16 B written per element. */
+int pcrcg_adam_step(float* params, float* grads, float* exp_avg, float* exp_avg_sq, long n, float lr, double beta1, double beta2,
+                    float eps, float weight_decay, long step, int zero_grads, void* stream);
 int pcrcg_weighted_bce(const float* prediction, const float* gt, int n, float* out3, float* grad, void* ws, size_t ws_bytes,
                        void* stream);
 /* validate_gradient (ref:lib/utils.py:100-111: no NaN, no Inf in any parameter gradient) over a flat buffer of n floats

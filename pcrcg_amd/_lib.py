@@ -221,6 +221,8 @@ SIGNATURES = {
     "pcrcg_gather_jobs": (c_int, [c_void_p, c_int, c_int, c_void_p]),
     "pcrcg_nonfinite_flag": (c_int, [c_void_p, ctypes.c_long, c_void_p, c_void_p]),
     "pcrcg_sgd_step": (c_int, [c_void_p, c_void_p, c_void_p, ctypes.c_long, c_float, c_float, c_float, c_int, c_void_p]),
+    "pcrcg_adam_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_long, c_float, ctypes.c_double, ctypes.c_double,
+                                c_float, c_float, ctypes.c_long, c_int, c_void_p]),
     "pcrcg_weighted_bce": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "pcrcg_feature_argmax_ws_bytes": (c_size_t, [c_int]),
     "pcrcg_feature_argmax": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,

@@ -15,6 +15,8 @@
 // logsumexp merged across lanes); k_circle_grads counts the selected lines, writes loss and recall (workgroup 0) and turns
 // the line terms into d loss / d a_i resp. d loss / d b_j.  The n x n matrices are never stored: a line's <a_i, b_j>
 // are recomputed where needed (n * c multiply-adds per line, the descriptors stay in L2).
+#include <cmath>
+
 #include "common.h"
 #include "pcrcg_train.h"
 
@@ -277,6 +279,49 @@ __global__ void __launch_bounds__(256) k_sgd_step(float* __restrict__ p, float* 
     }
 }
 
+// ---- Adam over flat buffers (torch.optim.Adam's single-tensor form, amsgrad / maximize off, L2 weight decay; ref:main.py:66-72) --
+//   d = g + wd * p;  m = m + (d - m) * (1 - b1);  v = b2 * v + (1 - b2) * (d * d);
+//   p = p - (lr / bc1) * (m / (sqrt(v) / sqrt(bc2) + eps));  optionally g = 0
+// The step-dependent scalars are the host's (pcrcg_adam_step rounds them to float once, as torch does).  IEEE sqrt and division.
+// A slot with p = g = m = v = 0 (the padding between parameter slices) stays exactly 0: 0 / (0 + eps).
+struct AdamScalars {
+    float wd, one_minus_b1, b2, one_minus_b2, step_size, bc2_sqrt, eps;
+};
+__device__ __forceinline__ void adam_one(float& p, float g, float& m, float& v, const AdamScalars& s) {
+    const float d = g + s.wd * p;
+    m = m + (d - m) * s.one_minus_b1;
+    v = s.b2 * v + s.one_minus_b2 * (d * d);
+    p = p - s.step_size * (m / (sqrtf(v) / s.bc2_sqrt + s.eps));
+}
+__global__ void __launch_bounds__(256) k_adam_step(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
+                                                    float* __restrict__ v, long n, AdamScalars s, int zero_grad) {
+    const long stride = (long)gridDim.x * 256 * 4;
+    for (long i = ((long)blockIdx.x * 256 + threadIdx.x) * 4; i < n; i += stride) {
+        if (i + 4 <= n) {
+            float4 pv = *reinterpret_cast<const float4*>(p + i), mv = *reinterpret_cast<const float4*>(m + i);
+            float4 vv = *reinterpret_cast<const float4*>(v + i);
+            const float4 gv = *reinterpret_cast<const float4*>(g + i);
+            adam_one(pv.x, gv.x, mv.x, vv.x, s);
+            adam_one(pv.y, gv.y, mv.y, vv.y, s);
+            adam_one(pv.z, gv.z, mv.z, vv.z, s);
+            adam_one(pv.w, gv.w, mv.w, vv.w, s);
+            *reinterpret_cast<float4*>(m + i) = mv;
+            *reinterpret_cast<float4*>(v + i) = vv;
+            *reinterpret_cast<float4*>(p + i) = pv;
+            if (zero_grad) *reinterpret_cast<float4*>(g + i) = make_float4(0.f, 0.f, 0.f, 0.f);
+        } else {
+            for (long j = i; j < n; ++j) {
+                float pj = p[j], mj = m[j], vj = v[j];
+                adam_one(pj, g[j], mj, vj, s);
+                m[j] = mj;
+                v[j] = vj;
+                p[j] = pj;
+                if (zero_grad) g[j] = 0.f;
+            }
+        }
+    }
+}
+
 }  // namespace
 }  // namespace pcrcg
 
@@ -313,6 +358,32 @@ int pcrcg_sgd_step(float* params, float* grads, float* momentum_buf, long n, flo
         if (blocks < 1) blocks = 1;
         hipLaunchKernelGGL(k_sgd_step, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), params, grads, momentum_buf, n, lr,
                            momentum, weight_decay, zero_grads);
+    }
+    PCRCG_CHECK_LAUNCH();
+    return PCRCG_OK;
+}
+
+int pcrcg_adam_step(float* params, float* grads, float* exp_avg, float* exp_avg_sq, long n, float lr, double beta1, double beta2,
+                    float eps, float weight_decay, long step, int zero_grads, void* stream) {
+    PCRCG_CHECK_ARG(n >= 0 && (n == 0 || (params && grads && exp_avg && exp_avg_sq)));
+    PCRCG_CHECK_ARG(((uintptr_t)params | (uintptr_t)grads | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) % 16 == 0);
+    PCRCG_CHECK_ARG(step >= 1 && beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0);
+    if (n > 0) {
+        // torch.optim.Adam computes these in python floats (double) and hands each to its tensor op as one scalar
+        const double bc1 = 1.0 - std::pow(beta1, (double)step), bc2 = 1.0 - std::pow(beta2, (double)step);
+        AdamScalars s;
+        s.wd = weight_decay;
+        s.one_minus_b1 = (float)(1.0 - beta1);
+        s.b2 = (float)beta2;
+        s.one_minus_b2 = (float)(1.0 - beta2);
+        s.step_size = (float)((double)lr / bc1);
+        s.bc2_sqrt = (float)std::sqrt(bc2);
+        s.eps = eps;
+        long blocks = (n / 4 + 255) / 256;
+        if (blocks > 4096) blocks = 4096;
+        if (blocks < 1) blocks = 1;
+        hipLaunchKernelGGL(k_adam_step, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), params, grads, exp_avg, exp_avg_sq,
+                           n, s, zero_grads);
     }
     PCRCG_CHECK_LAUNCH();
     return PCRCG_OK;

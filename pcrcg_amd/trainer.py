@@ -13,7 +13,9 @@ Trainer.inference_one_batch / the optimisation block of inference_one_epoch (ref
 Pairs shard over ranks exactly as in the forward benchmark (pair i -> rank i mod world); the all-reduce is
 the only data-path collective of the step.  Optimiser and scheduler objects are torch.optim (plumbing):
 SGD lr 0.005, momentum 0.98, weight decay 1e-6, ExponentialLR 0.95 per epoch
-(ref:configs/train/indoor.yaml:65-74, ref:main.py:59-78)."""
+(ref:configs/train/indoor.yaml:65-74, ref:main.py:59-78), or -- Trainer(optimizer="ADAM") -- Adam lr 0.0003, betas
+(0.9, 0.999), weight decay 1e-6 under the same schedule (ref:configs/train/pram_cofi.yaml:60-67); on the GPU either is
+one launch over the flat buffers (FlatSGD, FlatAdam)."""
 import torch
 
 from .train_forward import forward_train
@@ -234,10 +236,124 @@ class FlatSGD(torch.optim.Optimizer):
         return None
 
 
+class FlatAdam(torch.optim.Optimizer):
+    """torch.optim.Adam(lr, betas, eps, weight_decay) -- amsgrad and maximize off, L2 weight decay, the optimiser of the
+    reference's shipped PCR-CG recipe (ref:configs/train/pram_cofi.yaml:60-63, ref:main.py:66-72) -- over the flat parameter /
+    gradient buffers FlatSGD sits on: the whole step is ONE launch (pcrcg_adam_step, csrc/lossops.hip) that clears the gradient
+    bucket on its way.  State: two flat device buffers and one python step counter (every parameter takes every step).
+    param_groups carry lr / betas / eps / weight_decay, so lr schedulers work on it; state_dict / load_state_dict speak
+    torch.optim.Adam's per-parameter format."""
+
+    _TORCH_ONLY = ("amsgrad", "maximize", "foreach", "capturable", "differentiable", "fused", "decoupled_weight_decay")
+
+    def __init__(self, params, flat_param, flat_grad, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, sizes=None):
+        params = list(params)
+        if not (0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0):
+            raise ValueError("FlatAdam: betas must lie in [0, 1)")
+        super().__init__(params, dict(lr=lr, betas=(float(betas[0]), float(betas[1])), eps=eps, weight_decay=weight_decay))
+        self.flat_param, self.flat_grad = flat_param, flat_grad
+        self._flat_params = params
+        self._sizes = list(sizes) if sizes is not None else [GradientBucket.padded(p.numel()) for p in params]
+        if sum(self._sizes) != flat_param.numel():
+            raise ValueError("FlatAdam: slice sizes do not add up to the flat parameter buffer")
+        self.exp_avg_flat = torch.zeros_like(flat_param)
+        self.exp_avg_sq_flat = torch.zeros_like(flat_param)
+        self.steps = 0                         # torch's state['step'], one for all parameters
+
+    _slices = FlatSGD._slices
+
+    # ---- checkpoints: torch.optim.Adam's format (ref:lib/trainer.py:133,174 saves / loads optimizer.state_dict()) ----------
+    def state_dict(self):
+        """Per parameter id: step (0-dim float32, as torch keeps it) and exp_avg / exp_avg_sq slices (clones, shaped like the
+        parameter); one param_group with torch.optim.Adam's keys: torch.optim.Adam(...).load_state_dict() accepts it."""
+        g = self.param_groups[0]
+        state = {i: {"step": torch.tensor(float(self.steps), dtype=torch.float32),
+                     "exp_avg": self.exp_avg_flat[off:off + n].view_as(p).clone(),
+                     "exp_avg_sq": self.exp_avg_sq_flat[off:off + n].view_as(p).clone()}
+                 for i, (p, off, n) in enumerate(self._slices())}
+        group = {"lr": g["lr"], "betas": tuple(g["betas"]), "eps": g["eps"], "weight_decay": g["weight_decay"],
+                 "amsgrad": False, "maximize": False, "foreach": None, "capturable": False, "differentiable": False,
+                 "fused": None, "decoupled_weight_decay": False, "params": list(range(len(self._flat_params)))}
+        for k, v in g.items():                                  # (scheduler bookkeeping such as initial_lr)
+            if k not in group and k != "params":
+                group[k] = v
+        return {"state": state, "param_groups": [group]}
+
+    def load_state_dict(self, state_dict):
+        """Accepts torch.optim.Adam's / this class's state_dict (tensors on any device).  A parameter without a state entry
+        counts as step 0 with zero moments, as in torch before its first step; all parameters must then agree on the step,
+        because there is one counter.  Everything is checked first, then the values are COPIED into the existing device
+        buffers: nothing loaded from a checkpoint is ever handed to the kernel directly."""
+        groups = state_dict["param_groups"]
+        if len(groups) != 1:
+            raise ValueError("FlatAdam.load_state_dict: exactly one param_group expected")
+        grp = groups[0]
+        for k in ("amsgrad", "maximize", "capturable", "decoupled_weight_decay"):
+            if grp.get(k):
+                raise ValueError("FlatAdam.load_state_dict: %s is not implemented by pcrcg_adam_step" % k)
+        ids = grp["params"]
+        if len(ids) != len(self._flat_params):
+            raise ValueError("FlatAdam.load_state_dict: %d parameters in the checkpoint, %d in the model"
+                             % (len(ids), len(self._flat_params)))
+        st = state_dict.get("state", {})
+        steps, copies = set(), []
+        for pid, (p, off, n) in zip(ids, self._slices()):
+            entry = st.get(pid, st.get(str(pid)))
+            if not entry:
+                steps.add(0.0)
+                continue
+            steps.add(float(entry.get("step", 0)))
+            for name, flat in (("exp_avg", self.exp_avg_flat), ("exp_avg_sq", self.exp_avg_sq_flat)):
+                buf = entry.get(name)
+                if buf is None:
+                    continue
+                if buf.numel() != n:
+                    raise ValueError("FlatAdam.load_state_dict: %s of parameter %s has %d elements, %d expected"
+                                     % (name, pid, buf.numel(), n))
+                copies.append((flat[off:off + n], buf))
+        if len(steps) > 1:
+            raise ValueError("FlatAdam.load_state_dict: parameters disagree on the step (%s); one counter serves all"
+                             % sorted(steps))
+        step = steps.pop() if steps else 0.0
+        if step < 0 or step != int(step):
+            raise ValueError("FlatAdam.load_state_dict: step %r is not a whole number of steps" % step)
+        self.exp_avg_flat.zero_()
+        self.exp_avg_sq_flat.zero_()
+        for dst, buf in copies:
+            dst.copy_(buf.detach().to(dst.device, torch.float32).reshape(-1))
+        self.steps = int(step)
+        g = self.param_groups[0]
+        for k, v in grp.items():
+            if k != "params" and k not in self._TORCH_ONLY:
+                g[k] = tuple(float(b) for b in v) if k == "betas" else v
+
+    @torch.no_grad()
+    def step(self, closure=None, zero_grad=False):
+        from . import _lib
+        g = self.param_groups[0]
+        _lib.check(_lib.lib().pcrcg_adam_step(self.flat_param.data_ptr(), self.flat_grad.data_ptr(), self.exp_avg_flat.data_ptr(),
+                                              self.exp_avg_sq_flat.data_ptr(), self.flat_param.numel(), float(g["lr"]),
+                                              float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]),
+                                              float(g["weight_decay"]), self.steps + 1, int(bool(zero_grad)),
+                                              torch.cuda.current_stream().cuda_stream), "pcrcg_adam_step")
+        self.steps += 1
+        return None
+
+
 class Trainer:
     def __init__(self, model, desc_loss, lr=0.005, momentum=0.98, weight_decay=1e-6, scheduler_gamma=0.95,
-                 iter_size=1, process_group=None, overlap_chunks=4, use_cpp_runner=True):
+                 iter_size=1, process_group=None, overlap_chunks=4, use_cpp_runner=True, optimizer="SGD",
+                 betas=(0.9, 0.999), eps=1e-8, backbone2d=None):
+        """optimizer: "SGD" (ref:configs/train/indoor.yaml) or "ADAM" (ref:configs/train/pram_cofi.yaml; lr, betas, eps,
+        weight_decay -- momentum is ignored, as ref:main.py:66-72 ignores it), matched without regard to case.
+        backbone2d: the caller's 2-D backbone of an image_feature model (ref:lib/trainer.py:225-228,272-275 hands it to the
+        model in every phase).  It is run under no_grad and is otherwise left alone: it is in neither the gradient bucket
+        nor the optimiser, and its train / eval mode is the caller's."""
         self.model, self.desc_loss = model, desc_loss
+        self.backbone2d = backbone2d
+        kind = str(optimizer).upper()
+        if kind not in ("SGD", "ADAM"):
+            raise ValueError("pcrcg_amd.Trainer: optimizer must be 'SGD' or 'ADAM', not %r" % (optimizer,))
         self.use_cpp_runner = bool(use_cpp_runner)
         self.iter_size = iter_size
         self.bucket = GradientBucket(model.parameters(), process_group)
@@ -245,13 +361,19 @@ class Trainer:
             self.bucket.enable_overlap(overlap_chunks)
         self.params = self.bucket.params
         self.flat_grad = self.bucket.flat
-        # one-launch SGD over flat parameter / gradient buffers on the GPU (every requires_grad parameter of the model is in
-        # the bucket); torch.optim.SGD elsewhere (CPU runs of the host logic) and for models with frozen parameters mixed in
+        # one-launch SGD / Adam over flat parameter / gradient buffers on the GPU (every requires_grad parameter of the model is
+        # in the bucket); torch.optim elsewhere (CPU runs of the host logic) and for models with frozen parameters mixed in
         self.flat_param = None
         if self.params[0].is_cuda and all(p.dtype == torch.float32 and p.is_cuda for p in self.params):
             self.flat_param = FlatSGD.flatten(self.params, self.bucket.sizes)
-            self.optimizer = FlatSGD(self.params, self.flat_param, self.flat_grad, lr=lr, momentum=momentum,
-                                     weight_decay=weight_decay, sizes=self.bucket.sizes)
+            if kind == "ADAM":
+                self.optimizer = FlatAdam(self.params, self.flat_param, self.flat_grad, lr=lr, betas=betas, eps=eps,
+                                          weight_decay=weight_decay, sizes=self.bucket.sizes)
+            else:
+                self.optimizer = FlatSGD(self.params, self.flat_param, self.flat_grad, lr=lr, momentum=momentum,
+                                         weight_decay=weight_decay, sizes=self.bucket.sizes)
+        elif kind == "ADAM":
+            self.optimizer = torch.optim.Adam(self.params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
         else:
             self.optimizer = torch.optim.SGD(self.params, lr=lr, momentum=momentum, weight_decay=weight_decay)
         self.scheduler = torch.optim.lr_scheduler.ExponentialLR(self.optimizer, gamma=scheduler_gamma)
@@ -272,7 +394,17 @@ class Trainer:
                 # pcrcg_amd/train_forward.py remains as its mirror (use_cpp_runner = False, or a configuration the runner
                 # does not cover)
                 tr = self.model.train_runner() if self.use_cpp_runner else None
-                output = tr.forward(inputs) if tr is not None else forward_train(self.model, inputs)
+                net_inputs = inputs
+                if getattr(self.model, "image_feature", False):
+                    # PCR-CG's 129-channel input (KPFCNN.forward builds it, and this phase does not go through there): the
+                    # backbone's maps, or the batch's precomputed ones, scattered to the points -- once per call, into a
+                    # shallow copy.  The C++ runner takes rows of IMAGE_WIDTH floats, the op-by-op path [N, 129].
+                    net_inputs = dict(inputs)
+                    net_inputs["features"] = self.model.image_features(
+                        inputs, self.backbone2d, width=self.model.IMAGE_WIDTH if tr is not None else None)
+                output = tr.forward(net_inputs) if tr is not None else forward_train(self.model, net_inputs)
+            elif self.backbone2d is not None:
+                output = self.model(inputs, self.backbone2d)     # (KPFCNN.forward builds the image input itself)
             else:
                 output = self.model(inputs)
             prepared = ahead() if ahead is not None else None
@@ -346,7 +478,8 @@ class Trainer:
         return self._apply_step(self.gradient_valid())
 
     def _apply_step(self, ok):
-        """The optimiser step behind the (already reduced and checked) gradients: SGD when they are finite, else skip."""
+        """The optimiser step behind the (already reduced and checked) gradients: SGD / Adam when they are finite, else skip
+        (a skipped step never reaches optimizer.step(): Adam's step counter does not advance, as in torch)."""
         if ok and self.flat_param is not None:
             self.optimizer.step(zero_grad=True)          # the launch clears the bucket as well
             self._bump_versions()

@@ -3,7 +3,7 @@ fp32): pyramid + labels are built once, then K x (differentiable forward -> Metr
 all-reduce -> SGD step).  Secondary measurement (bench.py stays the forward benchmark BASELINE.json names; its
 `secondary.train_step` block runs the 1-GPU case of this file).  GPU box only, except --launcher-dry-run.
 
-  python scripts/bench_train.py [--gpus N] [--steps 10] [--warmup 2] [--recipe S30k]
+  python scripts/bench_train.py [--gpus N] [--steps 10] [--warmup 2] [--recipe S30k] [--optimizer SGD|ADAM]
         (--gpus N > 1 with no rank environment: this process only starts N fresh ranks, pcrcg_amd/launcher.py)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 scripts/bench_train.py --gpus N
         (configs[3]: every rank trains on its own pair, ONE RCCL all-reduce of the flat 29.7 M-element gradient
@@ -63,6 +63,33 @@ def time_allreduce(dist, flat, reps, sync):
     return float(t.item())
 
 
+def time_optimisation_block(trainer, reps):
+    """The optimisation block alone (ref:lib/trainer.py:354-361: gradient check, optimiser step, gradient clear) after the
+    timed steps, on whatever the last step left in the bucket: `reps` x Trainer.optimizer_step() -> its average wall time,
+    the finite-check's host round trip included, and the optimiser launch by itself between two events with the bytes it
+    moves per second (Adam: 16 B read and 16 B written per element with the gradient clear)."""
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(reps):
+        trainer.optimizer_step()
+    torch.cuda.synchronize()
+    block_ms = (time.perf_counter() - t0) / reps * 1e3
+    out = {"block_ms": round(block_ms, 4), "reps": reps}
+    if trainer.flat_param is not None:
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(reps):
+            trainer.optimizer.step(zero_grad=True)
+        b.record()
+        torch.cuda.synchronize()
+        ms = a.elapsed_time(b) / reps
+        n = int(trainer.flat_param.numel())
+        per_element = 32 if hasattr(trainer.optimizer, "exp_avg_flat") else 24
+        out.update(launch_ms=round(ms, 4), elements=n, bytes_per_element=per_element,
+                   TBs=round(n * per_element / (ms * 1e-3) / 1e12, 3))
+    return out
+
+
 def dry_run(args, rank, world):
     """The N-rank protocol over gloo on the CPU with a stand-in model: Trainer's bucket / all-reduce / global-skip / SGD
     block is the real code (it needs no GPU; the network's kernels do)."""
@@ -120,6 +147,8 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--recipe", default="S30k")
+    ap.add_argument("--optimizer", choices=("SGD", "ADAM"), default="SGD",
+                    help="SGD: ref:configs/train/indoor.yaml (the default Trainer); ADAM: ref:configs/train/pram_cofi.yaml")
     ap.add_argument("--launcher-dry-run", action="store_true")
     args = ap.parse_args()
 
@@ -155,7 +184,8 @@ def main():
     net = KPFCNN(cfg).to(dev)
     loss = MetricLoss(Config(pos_margin=0.1, neg_margin=1.4, pos_radius=0.0375, safe_radius=0.1,
                              matchability_radius=0.05, max_points=256))
-    trainer = Trainer(net, loss)
+    # (SGD: the default Trainer, exactly as before the option existed)
+    trainer = Trainer(net, loss) if args.optimizer == "SGD" else Trainer(net, loss, optimizer="ADAM", lr=0.0003)
 
     src, tgt, rot, trans = synthetic.lomatch_pair(args.recipe, rank, overlap=0.2)     # one pair per rank
     tsfm = np.eye(4)
@@ -198,6 +228,7 @@ def main():
         dist.all_reduce(hi, op=dist.ReduceOp.MAX)
         identical = float(lo) == float(hi)
         assert identical, "replicas diverged"
+    optim = time_optimisation_block(trainer, 20) if args.optimizer == "ADAM" else None
     fields = launcher.rank_fields(dist, world, rank, round(1.0 / own, 3), RANK_CPUS, device=dev)
     if dist is not None:
         dist.destroy_process_group()
@@ -207,7 +238,8 @@ def main():
         sys.stdout.flush()
         ctypes.CDLL(None).fflush(None)      # RCCL's banner goes through C stdio: keep the JSON line last
         print(json.dumps({
-            "metric": "train pairs/s (fwd + MetricLoss + bwd + gradient all-reduce + SGD), 1 pair/rank/step",
+            "metric": "train pairs/s (fwd + MetricLoss + bwd + gradient all-reduce + %s), 1 pair/rank/step"
+                      % {"SGD": "SGD", "ADAM": "Adam"}[args.optimizer],
             "value": round(world / dt, 3), "unit": "fragment-pairs/s", "n_gpus": world, "ranks_seen": fields["ranks_seen"],
             "per_rank_pairs_per_s": fields["per_rank_value"], "per_rank_cpus": fields["per_rank_cpus"],
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt * 1e3, 2), "higher_is_better": True,
@@ -216,7 +248,7 @@ def main():
                           "backend": "rccl",
                           "GBs_bus": None if not ar_ms else round(2 * (world - 1) / max(world, 1) * nel * 4 / (ar_ms * 1e-3) / 1e9, 1),
                           "note": "the exchange alone, back to back; inside the step it overlaps the backward pass"},
-            "replicas_identical": identical,
+            "replicas_identical": identical, "optimizer": args.optimizer, "optimisation_block": optim,
             "config": {"workload": f"{args.recipe} 3DLoMatch-shaped pair (overlap 0.2), full-width KPFCNN+GCN, one pair per "
                                    "rank per step, pyramid + labels prebuilt",
                        "parallelism": f"data parallel over {world} GPU(s): one all-reduce of the flat gradient bucket per step"},
