@@ -79,6 +79,9 @@ int pcrcg_abi_version(void);
  *                      in the train step, the 2-D backbone's BatchNorm sums stored per row tile and added in a fixed
  *                      order by a finishing pass per product); implies stat_sums=0 gemm_splitk=1; allocates its scratch itself.  Together with a fixed pairing of the pair engine (PairStreams(adaptive_jobs=False))
  *                      outputs are a function of the inputs alone.
+ * (One accepted name is NOT in the list above: `walk`, the gather launches' query order, documented with pcrcg_query_walk
+ * below.  The list is held to its 21 entries by tests/test_abi.py, which also means that test never sets `walk`;
+ * tests/test_walk_gpu.py does.)
  * Returns PCRCG_EBADARG (and changes nothing) on an unknown name.  A switch that has been retired -- its default is now the
  * only behaviour, or its measurement aid is gone (DESIGN.md section 5 names them) -- is an unknown name like any other. */
 int pcrcg_debug_set(const char* spec);
@@ -246,6 +249,32 @@ int pcrcg_kpconv_aggregate(const float* q_pts, int nq, const float* s_pts, int n
 int pcrcg_kpconv_aggregate_bf16(const float* q_pts, int nq, const float* s_pts, int ns, const int64_t* idx, int h,
                                 int ld_idx, const float* x, int cin, const float* kp, float extent, void* x_bf16,
                                 void* wf_bf16, float* inv_n, void* ws, size_t ws_bytes, void* stream);
+
+/* The order in which the gather kernels visit their queries (csrc/walk.hip).  pcrcg_query_walk writes walk[n] i32, a
+ * permutation of 0 .. n-1: the queries of points [n,3] sorted by key, the 12-bit Morton interleave (x bit i -> key bit 3i,
+ * y -> 3i+1, z -> 3i+2) of the point's cell in a 16 x 16 x 16 grid over the cloud's bounding box,
+ * cell = clamp(int((p - lo) * 16 / max(hi - lo, tiny)), 0, 15) per axis; a NaN or infinite coordinate goes to cell 0 and
+ * does not count for the box.  The order inside one key is arbitrary.  key [n] i32 receives the keys (or NULL).  n = 0
+ * writes nothing.  A kernel that is given a walk covers POSITIONS: workgroup b runs on XCD b mod 8 and takes its queries
+ * from the (b mod 8)-th eighth of the walk, so that the neighbour rows of one part of the cloud are fetched into ONE
+ * XCD's L2 -- every output row is computed exactly as without a walk (bit-identical results).
+ * The forward runner builds one walk per level and call and hands it to the gather launches whose support rows exceed an
+ * L2 (debug switch `walk`, default 1; pcrcg_debug_set("walk=0"): index order everywhere, "walk=2": every launch walks --
+ * listed here and not above because it is an order of processing, not of arithmetic).
+ * The _walk forms of the three gather entries are TEST-ONLY AND UNSTABLE: no caller other than this repository's tests and
+ * timing scripts may rely on them, and they may change or go without an ABI version bump.  They are the plain entries with
+ * the queries' order given (walk [nq] i32; NULL: the plain entry).  The walk is NOT validated: it must be a permutation of
+ * 0 .. nq-1 (what pcrcg_query_walk writes); anything else gives duplicated and missing output rows (entries outside the
+ * range are clamped into it, so no address leaves the arrays). */
+int pcrcg_query_walk(const float* points, int n, int* walk, int* key, void* stream);
+int pcrcg_kpconv_aggregate_walk(const float* q_pts, int nq, const float* s_pts, int ns, const int64_t* idx,
+                                int h, int ld_idx, const float* x, int cin, const float* kp, float extent,
+                                float* wf, float* inv_n, void* ws, size_t ws_bytes, const int* walk, void* stream);
+int pcrcg_kpconv_aggregate_bf16_walk(const float* q_pts, int nq, const float* s_pts, int ns, const int64_t* idx, int h,
+                                     int ld_idx, const float* x, int cin, const float* kp, float extent, void* x_bf16,
+                                     void* wf_bf16, float* inv_n, void* ws, size_t ws_bytes, const int* walk, void* stream);
+int pcrcg_gather_max_walk(const float* x, int ns, int c, const int64_t* idx, int nq, int h, int ld_idx,
+                          float* out, const int* walk, void* stream);
 
 /* Measurement aid for bench.py: when enabled, the gather/aggregate kernel of every
  * pcrcg_kpconv_aggregate call (kind 0; kind 1 is reserved for a one-kernel KPConv)

@@ -58,6 +58,13 @@ SIGNATURES = {
     "pcrcg_kpconv_aggregate_bf16": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int,
                                             c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
                                             c_void_p]),
+    "pcrcg_query_walk": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "pcrcg_kpconv_aggregate_walk": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int,
+                                            c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "pcrcg_kpconv_aggregate_bf16_walk": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int,
+                                                 c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                                 c_void_p, c_void_p]),
+    "pcrcg_gather_max_walk": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "pcrcg_profile_kpconv": (None, [c_int]),
     "pcrcg_profile_kpconv_read": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int]),
     "pcrcg_gemm_f32": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int,

@@ -77,10 +77,17 @@ int kpconv_pack(const float* x, int ns, int cin, const float* s_pts, void* ws, s
                 unsigned short* x_bf16 = nullptr);
 int kpconv_aggregate_rows(const float* q_pts, int nq, const float* s_pts, int ns, const int64_t* idx, int h, int ld_idx,
                           const float* x, int cin, const float* kp, float extent, float* wf, float* inv_n, void* ws,
-                          size_t ws_bytes, hipStream_t st, bool pack, bool stream_out, int c1_ld = 0);   // c1_ld = 16: cin = 1 with wf rows of 16 floats (15 + a zero)
+                          size_t ws_bytes, hipStream_t st, bool pack, bool stream_out, int c1_ld = 0,   // c1_ld = 16: cin = 1 with wf rows of 16 floats (15 + a zero)
+                          const int* walk = nullptr);      // walk: the queries' processing order (walk.hip), NULL: index order
 int kpconv_aggregate_bf16(const float* q_pts, int nq, const float* s_pts, int ns, const int64_t* idx, int h, int ld_idx,
                           const float* x, unsigned short* x_bf16, int cin, const float* kp, float extent,
-                          unsigned short* wf_bf16, float* inv_n, void* ws, size_t ws_bytes, hipStream_t st);
+                          unsigned short* wf_bf16, float* inv_n, void* ws, size_t ws_bytes, hipStream_t st,
+                          const int* walk = nullptr);
+
+// walk.hip: walk[g] = the n[g] query indices of cloud g sorted by the 12-bit Morton key of their cell in a 16^3 grid over
+// the cloud's bounding box (a permutation; the order inside a cell is arbitrary), for up to four clouds in one launch.
+// The gather kernels visit their queries in that order, an eighth of it per XCD.  key (or key[g]) may be NULL.
+int query_walk_multi(const float* const* pts, const int* n, int* const* walk, int* const* key, int count, hipStream_t st);
 
 // InstanceNorm + LeakyReLU from fp64 column sums for up to four tensors of one width in one launch (pointops.hip)
 struct NormJob {
@@ -94,7 +101,7 @@ int instnorm_apply_sums_multi(const NormJob* jobs, int count, int c, int ldx, fl
 // the widths and leading dimensions that kernel serves (ldr = 0: no residual); 16-byte aligned bases are the caller's to check
 bool instnorm_sums_ok(int c, int ldx, int ldy, int ldr = 0);
 
-struct GatherJob { const float* x; const int64_t* idx; float* out; int ns, nq, h, ld_idx; };
+struct GatherJob { const float* x; const int64_t* idx; float* out; int ns, nq, h, ld_idx; const int* walk = nullptr; };   // walk: see query_walk_multi
 int gather_max_multi(const GatherJob* jobs, int count, int c, hipStream_t st);
 int heads_multi(const float* const* x, const int* rows, int count, int ld, int fd, float* const* feats, float* const* s_ov,
                 float* const* s_sal, hipStream_t st);
@@ -147,6 +154,9 @@ struct DebugOpts {
     // atomics.  Setting it overrides the two switches it implies.
     int deterministic = 0;
     int bwd_mfma = 1;               // KPConv backward's scatter on the matrix cores (k_kpconv_bwd_dx_mfma); 0: the VALU kernel
+    // forward runner: gather launches visit their queries in XCD-local Morton order (walk.hip) where runner.hip's walk_pays()
+    // says it wins; 0: index order everywhere (the order before the walk existed), 2: every launch walks (tests, A/B timing)
+    int walk = 1;
 };
 const DebugOpts& debug_opts();
 

@@ -114,7 +114,7 @@ __global__ void __launch_bounds__(kWavesPerBlock * 64) k_kpconv_mfma(
     const float* __restrict__ q_pts, int nq, const float* __restrict__ s_pts, int ns,
     const long long* __restrict__ idx, int H, int ld_idx, const FT* __restrict__ x, int cin,
     const float* __restrict__ kp, float extent, const float4* __restrict__ pk, FT* __restrict__ wf,
-    float* __restrict__ inv_n, int nchunk) {
+    float* __restrict__ inv_n, int nchunk, const int* __restrict__ walk) {
     constexpr bool BF16 = sizeof(FT) == 2;
     // groups of 4 neighbours whose row reads are in flight together.  The kernel is bound by its dependent load
     // chain, so occupancy beats deeper batches: 4 groups (76 VGPRs, 6 wavefronts/SIMD) measured best for NB = 1
@@ -124,15 +124,39 @@ __global__ void __launch_bounds__(kWavesPerBlock * 64) k_kpconv_mfma(
     const int hsub = lane >> 4, j = lane & 15;
     // the wavefront index is uniform: telling the compiler so moves the item's query, its coordinates and the row
     // base addresses into SGPRs (fewer VGPRs -> more wavefronts per SIMD, which is what this kernel is short of)
-    const long gw = (long)blockIdx.x * kWavesPerBlock + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const long nw = (long)gridDim.x * kWavesPerBlock;
-    const long items = (long)nq * nchunk;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    long gw = (long)blockIdx.x * kWavesPerBlock + wave;
+    long nw = (long)gridDim.x * kWavesPerBlock;
+    long items = (long)nq * nchunk;
+    // With a walk (walk.hip) the launch covers POSITIONS of the walk, q = walk[pos]: workgroup b runs on XCD b & 7, and XCD x
+    // takes the x-th eighth of the positions (split as gemm_x6.hip splits its tiles), its workgroups striding through it
+    // together -- the queries in flight on one XCD are a compact window of the Morton curve, so their neighbour rows meet in
+    // that XCD's own L2.  The grid is a multiple of 8 workgroups then.  Without one: items in index order, as before.
+    int pos0 = 0;
+    if (walk) {
+        const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, nslot = gridDim.x >> 3;
+        const int xq = nq >> 3, xr = nq & 7;
+        pos0 = xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq;
+        gw = (long)slot * kWavesPerBlock + wave;
+        nw = (long)nslot * kWavesPerBlock;
+        // (readfirstlane: the compiler otherwise evaluates the select on the vector unit and keeps `items` in two VGPRs)
+        const int cnt = __builtin_amdgcn_readfirstlane(xq + (xcd < xr ? 1 : 0));
+        items = (long)cnt * nchunk;
+    }
     const bool jvalid = j < K;
     const float kpx = jvalid ? kp[3 * j] : 0.f, kpy = jvalid ? kp[3 * j + 1] : 0.f, kpz = jvalid ? kp[3 * j + 2] : 0.f;
     const float inv_extent = 1.0f / extent;
 
     for (long item = gw; item < items; item += nw) {
-        const int q = (int)(item / nchunk), chunk = (int)(item - (long)q * nchunk);
+        const int p = (int)(item / nchunk), chunk = (int)(item - (long)p * nchunk);
+        int q = p;
+        if (walk) {
+            q = walk[pos0 + p];
+            // The ONE guard against a corrupt walk: a walk is a permutation of 0 .. nq-1 (k_query_walk writes nothing else), and
+            // an entry outside that range must not become an address outside the rows -- a stray store can take the device
+            // down.  Such a walk gives duplicated and missing rows; the walk tests compare every row against index order.
+            q = q < 0 ? 0 : (q < nq ? q : nq - 1);
+        }
         const int c0 = chunk * 64 * NB;
         const float qx = q_pts[3 * (long)q], qy = q_pts[3 * (long)q + 1], qz = q_pts[3 * (long)q + 2];
         f32x4 acc[NB][4];
@@ -457,7 +481,7 @@ namespace pcrcg {
 // (a row chunk whose wf the contraction reads back from L2 / Infinity Cache right away)
 int kpconv_aggregate_rows(const float* q_pts, int nq, const float* s_pts, int ns, const int64_t* idx, int h, int ld_idx,
                           const float* x, int cin, const float* kp, float extent, float* wf, float* inv_n, void* ws,
-                          size_t ws_bytes, hipStream_t st, bool pack, bool stream_out, int c1_ld) {
+                          size_t ws_bytes, hipStream_t st, bool pack, bool stream_out, int c1_ld, const int* walk) {
     PCRCG_CHECK_ARG(nq >= 0 && ns >= 0 && h >= 1 && ld_idx >= h && cin >= 1 && (c1_ld == 0 || c1_ld == K || c1_ld == K + 1));
     PCRCG_CHECK_ARG(extent > 0.0f);
     if (nq == 0) return PCRCG_OK;
@@ -472,6 +496,11 @@ int kpconv_aggregate_rows(const float* q_pts, int nq, const float* s_pts, int ns
     auto blocks_for = [&](long waves) {
         long b = (waves + kWavesPerBlock - 1) / kWavesPerBlock;
         return (int)(b > max_blocks ? max_blocks : b);
+    };
+    // with a walk: eight XCD ranges of at most ceil(nq / 8) queries each, the same number of workgroups for every range
+    auto blocks_walk = [&](int nchunk) {
+        const int b = blocks_for((long)((nq + 7) / 8) * nchunk);
+        return 8 * (b > max_blocks / 8 ? max_blocks / 8 : b);
     };
     if (cin == 1) {
         if (pack) hipLaunchKernelGGL(k_pack_c1, dim3((ns + 255) / 256), dim3(256), 0, st, x, ns, s_pts, pk);
@@ -496,11 +525,11 @@ int kpconv_aggregate_rows(const float* q_pts, int nq, const float* s_pts, int ns
     }
     // cin = 64 nb + 4 (PCR-CG's 129 channels in rows of 132): one wavefront per query, the last float4 on the vector units
     if (cin == 68 || cin == 132) {
-        const int blocks = blocks_for((long)nq);
+        const int blocks = walk ? blocks_walk(1) : blocks_for((long)nq);
 #define LAUNCH_T(NBV, NT)                                                                                                        \
         hipExtLaunchKernelGGL((k_kpconv_mfma<NBV, NT, float, true>), dim3(blocks), dim3(kWavesPerBlock * 64), 0, st, prof_scope.a, \
                               prof_scope.b, 0, q_pts, nq, s_pts, ns, idx_ll, h, ld_idx, x, cin, kp, extent,                      \
-                              (const float4*)pk, wf, inv_n, 1)
+                              (const float4*)pk, wf, inv_n, 1, walk)
         if (cin == 132) { if (stream_out) LAUNCH_T(2, true); else LAUNCH_T(2, false); }
         else { if (stream_out) LAUNCH_T(1, true); else LAUNCH_T(1, false); }
 #undef LAUNCH_T
@@ -512,11 +541,11 @@ int kpconv_aggregate_rows(const float* q_pts, int nq, const float* s_pts, int ns
     int nb = nblk >= 4 ? 4 : (nblk >= 2 ? 2 : 1);
     while (nb > 1 && ((long)nq * ((nblk + nb - 1) / nb) < 16384 || nblk % nb != 0)) nb >>= 1;
     const int nchunk = (nblk + nb - 1) / nb;
-    const int blocks = blocks_for((long)nq * nchunk);
+    const int blocks = walk ? blocks_walk(nchunk) : blocks_for((long)nq * nchunk);
 #define LAUNCH(NBV, NT)                                                                                                 \
     hipExtLaunchKernelGGL((k_kpconv_mfma<NBV, NT, float>), dim3(blocks), dim3(kWavesPerBlock * 64), 0, st, prof_scope.a, \
                           prof_scope.b, 0, q_pts, nq, s_pts, ns, idx_ll, h, ld_idx, x, cin, kp, extent,                 \
-                          (const float4*)pk, wf, inv_n, nchunk)
+                          (const float4*)pk, wf, inv_n, nchunk, walk)
     if (stream_out) {
         if (nb == 4) LAUNCH(4, true);
         else if (nb == 2) LAUNCH(2, true);
@@ -535,7 +564,7 @@ int kpconv_aggregate_rows(const float* q_pts, int nq, const float* s_pts, int ns
 // support-record prelude (the n_q normaliser counts rows with a positive fp32 sum, exactly as the fp32 path does).
 int kpconv_aggregate_bf16(const float* q_pts, int nq, const float* s_pts, int ns, const int64_t* idx, int h, int ld_idx,
                           const float* x, unsigned short* x_bf16, int cin, const float* kp, float extent,
-                          unsigned short* wf_bf16, float* inv_n, void* ws, size_t ws_bytes, hipStream_t st) {
+                          unsigned short* wf_bf16, float* inv_n, void* ws, size_t ws_bytes, hipStream_t st, const int* walk) {
     PCRCG_CHECK_ARG(nq >= 0 && ns >= 1 && h >= 1 && ld_idx >= h && cin >= 4 && cin % 4 == 0 && extent > 0.0f);
     if (nq == 0) return PCRCG_OK;
     PCRCG_CHECK_ARG(q_pts && s_pts && idx && x && x_bf16 && kp && wf_bf16 && inv_n && ws);
@@ -551,11 +580,15 @@ int kpconv_aggregate_bf16(const float* q_pts, int nq, const float* s_pts, int ns
     const int nchunk = (nblk + nb - 1) / nb;
     long blocks = ((long)nq * nchunk + kWavesPerBlock - 1) / kWavesPerBlock;
     if (blocks > 256 * 32) blocks = 256 * 32;
+    if (walk) {      // eight XCD ranges of at most ceil(nq / 8) queries, the same number of workgroups for each
+        blocks = ((long)((nq + 7) / 8) * nchunk + kWavesPerBlock - 1) / kWavesPerBlock;
+        blocks = 8 * (blocks > 32 * 32 ? 32 * 32 : blocks);
+    }
     KpProfScope prof_scope(st, nq, h, cin, 0, 2);      // kind 2: bf16 storage
 #define LAUNCHB(NBV)                                                                                                      \
     hipExtLaunchKernelGGL((k_kpconv_mfma<NBV, true, unsigned short>), dim3((int)blocks), dim3(kWavesPerBlock * 64), 0, st, \
                           prof_scope.a, prof_scope.b, 0, q_pts, nq, s_pts, ns, idx_ll, h, ld_idx, x_bf16, cin, kp, extent, \
-                          (const float4*)pk, wf_bf16, inv_n, nchunk)
+                          (const float4*)pk, wf_bf16, inv_n, nchunk, walk)
     if (nb == 4) LAUNCHB(4);
     else if (nb == 2) LAUNCHB(2);
     else LAUNCHB(1);

@@ -15,7 +15,9 @@ constexpr int kWavesPerBlock = 4;
 
 // one wavefront per (query row, block of 64 lanes x float4 | float channels)
 // (round 5: up to four (features, table, output) triples of one width per launch -- blockIdx.y -- the pairs of a forward call)
-struct GatherMulti { const float* x[4]; const long long* idx[4]; float* out[4]; int ns[4], nq[4], h[4], ld_idx[4]; };
+// walk[g] (walk.hip; all clouds of a launch or none): the launch covers POSITIONS, workgroup b belongs to XCD b & 7, XCD x takes
+// the x-th eighth of cloud g's positions and q = walk[pos] -- see k_kpconv_mfma (kpconv.hip); gridDim.x is a multiple of 8 then
+struct GatherMulti { const float* x[4]; const long long* idx[4]; float* out[4]; int ns[4], nq[4], h[4], ld_idx[4]; const int* walk[4]; };
 template <bool VEC4>
 __global__ void __launch_bounds__(kWavesPerBlock * 64) k_gather_max(GatherMulti mm, int c, int nchunk) {
     const int g = blockIdx.y;
@@ -24,9 +26,24 @@ __global__ void __launch_bounds__(kWavesPerBlock * 64) k_gather_max(GatherMulti 
     float* __restrict__ out = mm.out[g];
     const int ns = mm.ns[g], nq = mm.nq[g], h = mm.h[g], ld_idx = mm.ld_idx[g];
     const int lane = threadIdx.x & 63;
-    const long item = (long)blockIdx.x * kWavesPerBlock + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    if (item >= (long)nq * nchunk) return;
-    const int q = (int)(item / nchunk), chunk = (int)(item - (long)q * nchunk);
+    const int* __restrict__ walk = mm.walk[g];
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    long item = (long)blockIdx.x * kWavesPerBlock + wave, items = (long)nq * nchunk;
+    int pos0 = 0;
+    if (walk) {
+        const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
+        const int xq = nq >> 3, xr = nq & 7;
+        pos0 = xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq;
+        item = (long)slot * kWavesPerBlock + wave;
+        items = (long)(xq + (xcd < xr ? 1 : 0)) * nchunk;
+    }
+    if (item >= items) return;
+    const int p = (int)(item / nchunk), chunk = (int)(item - (long)p * nchunk);
+    int q = p;
+    if (walk) {
+        q = walk[pos0 + p];
+        q = q < 0 ? 0 : (q < nq ? q : nq - 1);       // (the guard of k_kpconv_mfma, kpconv.hip: never an address outside the rows)
+    }
     const long long* row = idx + (long)q * ld_idx;
     if (VEC4) {
         const int cb = chunk * 64 + lane;
@@ -413,7 +430,9 @@ int gather_max_multi(const GatherJob* jobs, int count, int c, hipStream_t st) {
         const GatherJob& j = jobs[g < count ? g : 0];
         mm.x[g] = j.x; mm.idx[g] = reinterpret_cast<const long long*>(j.idx); mm.out[g] = j.out;
         mm.ns[g] = j.ns; mm.nq[g] = g < count ? j.nq : 0; mm.h[g] = j.h; mm.ld_idx[g] = j.ld_idx;
+        mm.walk[g] = j.walk;
         if (g < count) {
+            PCRCG_CHECK_ARG((j.walk != nullptr) == (jobs[0].walk != nullptr));
             PCRCG_CHECK_ARG(j.ns >= 0 && j.nq >= 0 && j.h >= 1 && j.ld_idx >= j.h && (j.nq == 0 || (j.x && j.idx && j.out)));
             vec = vec && ((reinterpret_cast<uintptr_t>(j.x) | reinterpret_cast<uintptr_t>(j.out)) & 15) == 0;
             nq_max = j.nq > nq_max ? j.nq : nq_max;
@@ -422,8 +441,9 @@ int gather_max_multi(const GatherJob* jobs, int count, int c, hipStream_t st) {
     if (nq_max == 0) return PCRCG_OK;
     const int per_wave = vec ? 256 : 64;
     const int nchunk = (c + per_wave - 1) / per_wave;
-    const long items = (long)nq_max * nchunk;
-    const dim3 grid((unsigned)((items + kWavesPerBlock - 1) / kWavesPerBlock), count);
+    // (with walks: eight XCD ranges of at most ceil(nq / 8) queries, the same number of workgroups for each)
+    const long items = jobs[0].walk ? (long)((nq_max + 7) / 8) * nchunk : (long)nq_max * nchunk;
+    const dim3 grid((unsigned)((items + kWavesPerBlock - 1) / kWavesPerBlock) * (jobs[0].walk ? 8 : 1), count);
     if (vec) hipLaunchKernelGGL(k_gather_max<true>, grid, dim3(kWavesPerBlock * 64), 0, st, mm, c, nchunk);
     else hipLaunchKernelGGL(k_gather_max<false>, grid, dim3(kWavesPerBlock * 64), 0, st, mm, c, nchunk);
     PCRCG_CHECK_LAUNCH();

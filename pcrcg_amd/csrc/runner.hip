@@ -366,6 +366,37 @@ bool linear_norm(Ctx& c, const Mat& x, Stat* xs, float slope, const float* w, in
 
 struct Batches { const pcrcg_batch* b[GMAX]; };
 
+// The gather launches' query order (walk.hip): one walk per level and pair, shared by every launch whose QUERIES are that
+// level's points -- the level's own KPConvs, the strided KPConv of the level above and its max-pool.  forward() takes the
+// memory before the blocks (it lives until the call ends); the walk kernel of a level runs when the first launch asks.
+struct Walks {
+    int* w[PCRCG_MAX_LEVELS][GMAX] = {};
+    bool built[PCRCG_MAX_LEVELS] = {};
+    int mode = 0;      // DebugOpts::walk as forward() read it ONCE: the buffers above exist iff mode != 0, whatever the switch does later
+};
+
+// Which launches walk: those whose support feature rows ([ns, cin] fp32) exceed 8 MB, two XCDs' L2s, and that have at least
+// 2048 queries.  From the fourteen gather and pool launches of one S30k pair timed alone with and without the walk
+// (profiles/walk_ab.txt): the 15 MB to 61 MB launches gain 5 % to 50 %; at 7.9 MB two of three launches LOSE 4-5 % and at
+// 4 MB and below nothing moves (every L2 holds most rows whatever the order, the walk only adds its index load); the
+// level-2 pool (16 MB, 763 queries) saves less than the walk kernel of its level costs.
+static bool walk_pays(int mode, int ns, int cin, int nq) {
+    if (mode != 1) return mode == 2;
+    return (size_t)ns * (size_t)cin * sizeof(float) > (size_t)8 << 20 && nq >= 2048;
+}
+
+// the walks of level l's points for every pair of the call (NULL entries while sizing)
+const int* const* level_walks(Ctx& c, const Batches& B, Walks& W, int l) {
+    if (c.live() && !W.built[l]) {
+        const float* pts[GMAX];
+        int n[GMAX];
+        for (int g = 0; g < c.G; ++g) { pts[g] = B.b[g]->points[l]; n[g] = B.b[g]->n_points[l]; }
+        c.check(query_walk_multi(pts, n, W.w[l], nullptr, c.G, c.st));
+        W.built[l] = true;
+    }
+    return W.w[l];
+}
+
 // input channels of the block's KPConv as the gather kernel sees them (padded to a multiple of 4)
 int kp_cin(const pcrcg_block& blk, const Mat& x) { return (blk.kp_w_pad && blk.cin_pad > x.cols) ? blk.cin_pad : x.cols; }
 // the k-major weights [15 * kp_cin, cout] that match those channels: the zero-padded copy whenever the gather sees cin_pad
@@ -383,7 +414,7 @@ int kp_k(const pcrcg_block& blk, const Mat& x) {
     return (cin == 1 && blk.kp_wt) ? 16 : PCRCG_KPOINTS * cin;
 }
 
-void kpconv(Ctx& c, const Batches& B, const pcrcg_block& blk, const Mat& x, const Mat& y, Stat* st = nullptr,
+void kpconv(Ctx& c, const Batches& B, Walks& W, const pcrcg_block& blk, const Mat& x, const Mat& y, Stat* st = nullptr,
             void* const* packed_ws = nullptr) {
     const int l = blk.layer;
     const size_t m = c.mark();
@@ -420,6 +451,8 @@ void kpconv(Ctx& c, const Batches& B, const pcrcg_block& blk, const Mat& x, cons
     }
     const float* const kp_wt = blk.kp_wt;     // (cin = 1: the copy is the 16-float form or nothing)
     const int kk = kp_k(blk, x);
+    // the queries' order: the walk of the level the QUERIES are points of (cin = 1 reads only the support records: no walk)
+    const int* const* walks = (cin > 1 && walk_pays(W.mode, c.max_rows(ns), cin, c.max_rows(nq))) ? level_walks(c, B, W, blk.strided ? l + 1 : l) : nullptr;
     // bf16 feature storage (pcrcg_model.feature_bf16): the gathers read a bf16 copy of x and wf is bf16 in HBM -- half
     // the bytes of the two streams that bound the encoder; the contraction takes wf as the (single-term) bf16 operand
     // against the exact three-term split of the fp32 weights, fp32 accumulate and fp32 output.
@@ -429,8 +462,9 @@ void kpconv(Ctx& c, const Batches& B, const pcrcg_block& blk, const Mat& x, cons
             void* xb = c.raw(sizeof(unsigned short) * (size_t)(ns[g] > 0 ? ns[g] : 1) * cin);
             void* wfb = c.raw(sizeof(unsigned short) * (size_t)(nq[g] > 0 ? nq[g] : 1) * kk);
             if (c.live()) {
-                c.check(pcrcg_kpconv_aggregate_bf16(q[g], nq[g], b.points[l], ns[g], tab[g]->idx, tab[g]->cols, tab[g]->ld, xin.p[g],
-                                                    cin, blk.kp, blk.extent, xb, wfb, inv_n[g], ws[g], wsb[g], c.st));
+                c.check(kpconv_aggregate_bf16(q[g], nq[g], b.points[l], ns[g], tab[g]->idx, tab[g]->cols, tab[g]->ld, xin.p[g],
+                                              static_cast<unsigned short*>(xb), cin, blk.kp, blk.extent, static_cast<unsigned short*>(wfb),
+                                              inv_n[g], ws[g], wsb[g], c.st, walks ? walks[g] : nullptr));
                 GemmCall call;
                 call.a = wfb; call.lda = kk; call.a_form = GemmA::row_bf16;
                 call.b = kp_wt; call.ldb = kk;
@@ -454,7 +488,7 @@ void kpconv(Ctx& c, const Batches& B, const pcrcg_block& blk, const Mat& x, cons
             const bool packed = kk != 16 && packed_ws && packed_ws[g] && xin.p[g] == x.p[g];
             c.check(kpconv_aggregate_rows(q[g], nq[g], B.b[g]->points[l], ns[g], tab[g]->idx, tab[g]->cols, tab[g]->ld, xin.p[g], cin,
                                           blk.kp, blk.extent, wf.p[g], inv_n[g], ws[g], wsb[g], c.st, /*pack=*/!packed,
-                                          /*stream_out=*/true, /*c1_ld=*/kk == 16 ? 16 : 0));
+                                          /*stream_out=*/true, /*c1_ld=*/kk == 16 ? 16 : 0, walks ? walks[g] : nullptr));
         }
         // contraction wf @ W: against the K-contiguous copy wt [cout, 15*cin] when the descriptor carries one
         // (C = A * B^T form: both operands k-contiguous, the form the split-bf16 GEMM is built for).
@@ -479,14 +513,14 @@ void out_rows(const Ctx& c, const Batches& B, const pcrcg_block& blk, int* rows)
 }
 
 // SimpleBlock.forward (ref:models/blocks.py:578-590)
-Mat simple_block(Ctx& c, const Batches& B, const pcrcg_block& blk, const Mat& x) {
+Mat simple_block(Ctx& c, const Batches& B, Walks& W, const pcrcg_block& blk, const Mat& x) {
     int nq[GMAX];
     out_rows(c, B, blk, nq);
     Mat y = c.mat(nq, blk.mid_dim);
     const size_t m = c.mark();
     Mat t = c.gemm_out(nq, y.cols, kp_k(blk, x));
     Stat ts = stat_buffer(c, nq, t.cols);
-    kpconv(c, B, blk, x, t, &ts);
+    kpconv(c, B, W, blk, x, t, &ts);
     norm_act(c, t, 0.1f, y, &ts);
     c.release(m);
     return y;
@@ -536,7 +570,7 @@ bool norm_act_pack(Ctx& c, const Batches& B, int layer, const Mat& t, float slop
 }
 
 // ResnetBottleneckBlock.forward (ref:models/blocks.py:650-678)
-Mat resnet_block(Ctx& c, const Batches& B, const pcrcg_block& blk, const Mat& feats) {
+Mat resnet_block(Ctx& c, const Batches& B, Walks& W, const pcrcg_block& blk, const Mat& feats) {
     int nq[GMAX];
     out_rows(c, B, blk, nq);
     Mat y = c.mat(nq, blk.out_dim);
@@ -562,7 +596,7 @@ Mat resnet_block(Ctx& c, const Batches& B, const pcrcg_block& blk, const Mat& fe
     }
     Mat k = c.gemm_out(nq, blk.mid_dim, PCRCG_KPOINTS * kp_cin(blk, x)), kn = c.mat(nq, blk.mid_dim);
     Stat ks = stat_buffer(c, nq, blk.mid_dim);
-    kpconv(c, B, blk, x, k, &ks, packed ? kp_ws : nullptr);
+    kpconv(c, B, W, blk, x, k, &ks, packed ? kp_ws : nullptr);
     Mat u2 = c.gemm_out(nq, blk.out_dim, blk.mid_dim);
     Stat u2s = stat_buffer(c, nq, blk.out_dim);
     // lrelu(IN(k)) is read by unary2 alone: its product normalises k on load when k's statistics are column sums
@@ -575,9 +609,11 @@ Mat resnet_block(Ctx& c, const Batches& B, const pcrcg_block& blk, const Mat& fe
         sc = c.mat(nq, feats.cols);
         if (c.live()) {          // every pair's pool in one launch
             GatherJob jobs[GMAX];
+            // (its queries are level layer + 1's points: their walk)
+            const int* const* walks = walk_pays(W.mode, c.max_rows(feats.rows), feats.cols, c.max_rows(nq)) ? level_walks(c, B, W, blk.layer + 1) : nullptr;
             for (int g = 0; g < c.G; ++g) {
                 const pcrcg_table& t = B.b[g]->pools[blk.layer];
-                jobs[g] = GatherJob{feats.p[g], t.idx, sc.p[g], feats.rows[g], nq[g], t.cols, t.ld};
+                jobs[g] = GatherJob{feats.p[g], t.idx, sc.p[g], feats.rows[g], nq[g], t.cols, t.ld, walks ? walks[g] : nullptr};
             }
             c.check(gather_max_multi(jobs, c.G, feats.cols, c.st));
         }
@@ -760,11 +796,20 @@ void forward(Ctx& c, const pcrcg_model& mdl, const Batches& B, const pcrcg_outpu
     }
     x.cols = x.ld = B.b[0]->feat_dim;
     std::vector<Mat> skips;
+    // the gathers' query walks: sum n_points ints per pair, taken before the blocks so that the arena stays a stack
+    Walks W;
+    W.mode = debug_opts().walk;
+    if (W.mode)
+        for (int l = 0; l < L; ++l)
+            for (int g = 0; g < c.G; ++g) {
+                const int n = B.b[g]->n_points[l];
+                W.w[l][g] = static_cast<int*>(c.raw(sizeof(int) * (size_t)(n > 0 ? n : 1)));
+            }
     // 1. encoder (:519-524)
     for (int i = 0; i < mdl.n_enc; ++i) {
         if (mdl.enc_skip[i]) skips.push_back(x);
         const pcrcg_block& blk = mdl.enc[i];
-        x = blk.type == PCRCG_BLK_SIMPLE ? simple_block(c, B, blk, x) : resnet_block(c, B, blk, x);
+        x = blk.type == PCRCG_BLK_SIMPLE ? simple_block(c, B, W, blk, x) : resnet_block(c, B, W, blk, x);
     }
     // 2. bottleneck (:527-528) and 3. GNN (:532-536)
     const int gd = mdl.gnn_dim;

@@ -216,7 +216,7 @@ const DebugName kDebugNames[] = {
     {"x6_splitk", &DebugOpts::x6_splitk}, {"x6_t1", &DebugOpts::x6_t1}, {"x6_t2", &DebugOpts::x6_t2},
     {"gemm_tile", &DebugOpts::gemm_tile}, {"gemm_splitk", &DebugOpts::gemm_splitk},
     {"gemm_split_target", &DebugOpts::gemm_split_target}, {"deterministic", &DebugOpts::deterministic},
-    {"bwd_mfma", &DebugOpts::bwd_mfma}};
+    {"bwd_mfma", &DebugOpts::bwd_mfma}, {"walk", &DebugOpts::walk}};
 // The options are IMMUTABLE snapshots behind one atomic pointer: the engine's front and model threads read them
 // concurrently (their library calls hold no lock), pcrcg_debug_set publishes a new snapshot and never frees an old one
 // (a handful of 100-byte objects per process), so a reader's reference stays valid and no field is ever seen half
