@@ -107,6 +107,29 @@ int pcrcg_grid_subsample_batch(const float* pts, int n, const int* len, int nb, 
                                float* out_pts, int* out_len, int* out_m, void* ws, size_t ws_bytes,
                                void* stream);
 
+/* The same with the reference's optional `features=` and `classes=` (zip:cpp_subsampling/wrapper.cpp:62-330, format
+ * "OO|$OOfsii"; grid_subsampling.cpp:59-70,88-102, grid_subsampling.h:33-73), added after ABI version 4 without changing
+ * it: the points, lengths and launches of pcrcg_grid_subsample_batch are what they were.
+ *   feats        [n, fdim] f32, row stride ld_feat >= fdim elements; NULL with fdim = 0: no features
+ *   classes      [n, ldim] i32, dense;                                NULL with ldim = 0: no classes
+ *   out_feats    [n, fdim] f32 dense (capacity n rows): per kept row the cell's features added in input order in fp32,
+ *                starting from +0.0f, then divided by float(count) -- one correctly rounded fp32 division
+ *   out_classes  [n, ldim] i32 dense (capacity n rows): per kept row and label column the most frequent label of the
+ *                cell; among equally frequent labels the one std::max_element meets first when it walks the reference's
+ *                std::unordered_map<int,int> histogram (libstdc++ list order, identity hash: not the smallest label)
+ * Rows are in the barycentres' order and max_p cuts all three at the same rows; every result is bit-identical to the
+ * reference's.  Two inputs on which the reference itself is undefined are defined here: a cloud of length 0 yields no
+ * rows (the reference divides by zero), and every cloud's classes are its own rows of `classes` (the reference slices
+ * them with an end that is out of range for ldim > 1 in every cloud after the first, grid_subsampling.cpp:155-156).
+ * Returns PCRCG_EBADARG before any launch for fdim < 0, ldim < 0, ld_feat < fdim, or a null array whose width is > 0.
+ * ws: pcrcg_grid_subsample_ex_ws_bytes(n, nb, fdim, ldim) bytes (>= the points-only size; the features need one int per
+ * point beyond it -- they are summed straight into out_feats -- and the classes six ints per point and label column). */
+size_t pcrcg_grid_subsample_ex_ws_bytes(int n, int nb, int fdim, int ldim);
+int pcrcg_grid_subsample_batch_ex(const float* pts, int n, const int* len, int nb, float dl, int max_p,
+                                  const float* feats, int fdim, int ld_feat, const int* classes, int ldim,
+                                  float* out_pts, int* out_len, int* out_m, float* out_feats, int* out_classes,
+                                  void* ws, size_t ws_bytes, void* stream);
+
 /* Iteration order of a libstdc++ std::unordered_map<size_t,T> (identity hash) after inserting the
  * m DISTINCT keys in order; order[j] = insertion rank of the j-th visited element.  This is the
  * ordering step of the subsampling above, exported for unit tests

@@ -31,6 +31,10 @@ SIGNATURES = {
     "pcrcg_grid_subsample_ws_bytes": (c_size_t, [c_int, c_int]),
     "pcrcg_grid_subsample_batch": (c_int, [c_void_p, c_int, c_void_p, c_int, c_float, c_int, c_void_p, c_void_p,
                                            c_void_p, c_void_p, c_size_t, c_void_p]),
+    "pcrcg_grid_subsample_ex_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "pcrcg_grid_subsample_batch_ex": (c_int, [c_void_p, c_int, c_void_p, c_int, c_float, c_int, c_void_p, c_int, c_int,
+                                              c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                              c_size_t, c_void_p]),
     "pcrcg_umap_order_ws_bytes": (c_size_t, [c_int]),
     "pcrcg_umap_order": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "pcrcg_cellgrid_ws_bytes": (c_size_t, [c_int, c_int]),

@@ -15,6 +15,10 @@
 //     multiply by float(1.0/count) (:87)
 //   5 per cloud, one workgroup: reproduce libstdc++'s unordered_map iteration order with a
 //     data-parallel restatement of its insert/rehash rules (see umap_order_block) and emit rows.
+//   6 (pcrcg_grid_subsample_batch_ex only) step 5 also writes the cell of every emitted row; per kept row the cell's
+//     features are added in input order and divided by the count (k_cell_features), and per kept row and label column
+//     the cell's most frequent label is chosen as the reference's unordered_map<int,int> histogram chooses it
+//     (k_cell_labels).  Rows that max_p cuts are never summed.
 //
 // This file is compiled with -ffp-contract=off: the reference is built without FMA.
 #include "block_scan.h"
@@ -378,7 +382,8 @@ __global__ void __launch_bounds__(kUmapThreads) k_order_emit(int nb, const int* 
                                                               int* __restrict__ ebase, int* __restrict__ bbase,
                                                               long estride, long bstride, int max_p,
                                                               float* __restrict__ out_pts, int* __restrict__ out_len,
-                                                              int* __restrict__ out_m, int out_cap, int* __restrict__ overflow) {
+                                                              int* __restrict__ out_m, int out_cap, int* __restrict__ overflow,
+                                                              int* __restrict__ out_cell) {
     __shared__ int smem[kUmapThreads / 64];
     __shared__ int s_lds[11 * kUmapLds];
     const int b = blockIdx.x;
@@ -405,6 +410,7 @@ __global__ void __launch_bounds__(kUmapThreads) k_order_emit(int nb, const int* 
         out_pts[3 * (long)(out_off + j)] = cbary[3 * c];
         out_pts[3 * (long)(out_off + j) + 1] = cbary[3 * c + 1];
         out_pts[3 * (long)(out_off + j) + 2] = cbary[3 * c + 2];
+        if (out_cell) out_cell[out_off + j] = (int)c;       // (the features / classes passes read it; else null)
     }
     if (threadIdx.x == 0) {
         out_len[b] = keep;
@@ -420,6 +426,205 @@ __global__ void __launch_bounds__(kUmapThreads) k_umap_only(const u64* __restric
     UmapWs w = umap_carve(ebase, bbase, estride, bstride, 0, 0);
     umap_order_block(key, m, w, smem, s_lds);
     for (int j = threadIdx.x; j < m; j += kUmapThreads) order[j] = w.ord_a[j];
+}
+
+// ------------------------------------------------------------------------------------------------
+// Features and classes of the kept rows (pcrcg_grid_subsample_batch_ex).  Both kernels run after k_order_emit and read
+// the cell of every output row from out_cell; a cell's cidx segment is already in ascending (= input) order.
+// ------------------------------------------------------------------------------------------------
+
+// SampledData::features: vector<float>(fdim) = +0.0f, `plus<float>` per point in input order (grid_subsampling.h:46,59),
+// then f / (float)count (grid_subsampling.cpp:90-94) -- a true division, unlike the points' multiply.
+// 2^lanes_log2 lanes share an output row, each owning V adjacent columns (V = 4: one 16-byte read per lane where the
+// width and the stride allow), so a point's row is one coalesced read; where a row needs fewer than 64 lanes a wavefront
+// holds several rows, where it needs more the lanes walk it in column blocks.  Every column is summed by one lane, point
+// after point: the order of the additions is the reference's.
+template <int V>
+__global__ void __launch_bounds__(256) k_cell_features(const float* __restrict__ feats, int fdim, long ld,
+                                                        const int* __restrict__ out_m, const int* __restrict__ out_cell,
+                                                        const int* __restrict__ cstart, const int* __restrict__ ccnt,
+                                                        const int* __restrict__ cidx, float* __restrict__ out,
+                                                        int lanes_log2) {
+    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long row = t >> lanes_log2;
+    const int sub = (int)(t & ((1l << lanes_log2) - 1));
+    if (row >= *out_m) return;
+    const int c = out_cell[row];
+    const int* __restrict__ seg = cidx + cstart[c];
+    const int cnt = ccnt[c];
+    const float fcnt = (float)cnt;
+    for (int col = sub * V; col < fdim; col += V << lanes_log2) {
+        float acc[V];
+#pragma unroll
+        for (int v = 0; v < V; ++v) acc[v] = 0.0f;
+#pragma unroll 4
+        for (int a = 0; a < cnt; ++a) {
+            const float* __restrict__ r = feats + (long)seg[a] * ld + col;
+            if (V == 4) {
+                const float4 x = *reinterpret_cast<const float4*>(r);
+                acc[0] += x.x; acc[1] += x.y; acc[2] += x.z; acc[3] += x.w;
+            } else {
+                acc[0] += r[0];
+            }
+        }
+        float* __restrict__ o = out + row * fdim + col;
+        if (V == 4) {
+            *reinterpret_cast<float4*>(o) = make_float4(div_rn(acc[0], fcnt), div_rn(acc[1], fcnt), div_rn(acc[2], fcnt),
+                                                        div_rn(acc[3], fcnt));
+        } else {
+            o[0] = div_rn(acc[0], fcnt);
+        }
+    }
+}
+
+// std::hash<int> is the identity on the int converted to size_t: a negative label becomes a huge key
+__device__ __forceinline__ u64 label_key(int v) { return (u64)(long long)v; }
+
+// Scratch of the label vote, [n * ldim] ints each; the pair (cell, column) owns the `count` entries from
+// cstart * ldim + column * count on.
+struct VoteWs {
+    int *lab, *num;           // distinct labels in first-seen order and how often each was seen
+    int *bkt, *fst;           // per time stamp of a growth stage: bucket, first time stamp that hit that bucket
+    int *ord_a, *ord_b;       // list order ping-pong
+};
+
+constexpr int kVoteSmall = 13;   // cells of up to 13 points never leave the 13-bucket stage: one thread, registers only
+
+// One cell, one label column, any size, by one wavefront (a workgroup of its own: __syncthreads orders the scratch).
+// labels[i][*it] += 1 in input order (grid_subsampling.h:48-52) and max_element with a.second < b.second
+// (grid_subsampling.cpp:100-101): the first maximal count in the iteration order of an unordered_map<int,int>.  The order
+// is built stage by stage as umap_order_block builds it -- time stamp t = position in the previous stage's list, then
+// first-seen rank; the list is sorted by (first time stamp of the bucket, t), both descending -- with comparisons in
+// place of its counting sort (a histogram rarely has more than a few distinct labels); the last stage only has to find
+// the foremost element among those of maximal count.
+__device__ int vote_wave(const int* __restrict__ cls, int ldim, int col, const int* __restrict__ seg, int cnt, VoteWs w) {
+    const int lane = threadIdx.x;
+    int d = 0;
+    for (int base = 0; base < cnt; base += 64) {
+        const int mine = base + lane < cnt ? cls[(long)seg[base + lane] * ldim + col] : 0;
+        const int chunk = min(64, cnt - base);
+        for (int k = 0; k < chunk; ++k) {
+            const int v = __shfl(mine, k, 64);
+            int found = -1;
+            for (int j0 = 0; j0 < d; j0 += 64) {
+                const int j = j0 + lane;
+                const u64 hit = __ballot(j < d && w.lab[j] == v);
+                if (hit) { found = j0 + __ffsll((long long)hit) - 1; break; }
+            }
+            if (found >= 0) {
+                if (lane == 0) w.num[found] += 1;
+            } else {
+                if (lane == 0) { w.lab[d] = v; w.num[d] = 1; }
+                ++d;
+                __syncthreads();
+            }
+        }
+    }
+    __syncthreads();
+    int top = 0;
+    for (int j = lane; j < d; j += 64) top = max(top, w.num[j]);
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1) top = max(top, __shfl_xor(top, s, 64));
+    int cur = 0;
+    int* ord = w.ord_a;
+    for (int s = 1; s < kNGrow; ++s) {
+        const u64 B = kGrow[s];
+        const int cur2 = (u64)d < B ? d : (int)B;
+        const bool last = cur2 == d;
+        for (int t = lane; t < cur2; t += 64) w.bkt[t] = (int)(label_key(w.lab[t < cur ? ord[t] : t]) % B);
+        __syncthreads();
+        long long best = -1;
+        for (int t = lane; t < cur2; t += 64) {
+            const int b = w.bkt[t];
+            int f = t;
+            for (int u = 0; u < t; ++u)
+                if (w.bkt[u] == b) { f = u; break; }
+            if (!last) w.fst[t] = f;
+            else if (w.num[t < cur ? ord[t] : t] == top) best = max(best, ((long long)f << 32) | (long long)t);
+        }
+        if (last) {
+#pragma unroll
+            for (int x = 32; x >= 1; x >>= 1) {
+                const int hi = __shfl_xor((int)(best >> 32), x, 64), lo = __shfl_xor((int)best, x, 64);
+                best = max(best, ((long long)hi << 32) | (long long)(unsigned)lo);
+            }
+            const int t = (int)(best & 0xFFFFFFFFll);
+            return w.lab[t < cur ? ord[t] : t];
+        }
+        __syncthreads();
+        int* nord = ord == w.ord_a ? w.ord_b : w.ord_a;
+        for (int t = lane; t < cur2; t += 64) {
+            const int f = w.fst[t];
+            int pos = 0;
+            for (int u = 0; u < cur2; ++u) {
+                const int g = w.fst[u];
+                pos += (g > f || (g == f && u > t)) ? 1 : 0;
+            }
+            nord[pos] = t < cur ? ord[t] : t;
+        }
+        __syncthreads();
+        ord = nord;
+        cur = cur2;
+    }
+    return 0;   // more distinct labels than the probed growth table holds: cannot happen below 49 969 847 points
+}
+
+// One lane per (kept row, label column); workgroups of one wavefront.  A cell of up to kVoteSmall points is voted by its
+// lane alone: all its labels fall into the 13-bucket stage, where the foremost of two elements is the one whose bucket
+// was hit first by the LATER label, and inside a bucket the later label -- positions in the cell serve as time stamps.
+// Larger cells are then taken one after the other by the whole wavefront (vote_wave).
+__global__ void __launch_bounds__(64) k_cell_labels(const int* __restrict__ cls, int ldim, const int* __restrict__ out_m,
+                                                     const int* __restrict__ out_cell, const int* __restrict__ cstart,
+                                                     const int* __restrict__ ccnt, const int* __restrict__ cidx,
+                                                     int* __restrict__ out_cls, VoteWs w) {
+    const int lane = threadIdx.x;
+    const long item = (long)blockIdx.x * 64 + lane;
+    const long total = (long)*out_m * ldim;
+    int c = 0, col = 0;
+    bool big = false;
+    if (item < total) {
+        const long row = item / ldim;
+        col = (int)(item - row * ldim);
+        c = out_cell[row];
+        const int cnt = ccnt[c];
+        if (cnt > kVoteSmall) {
+            big = true;
+        } else {
+            const int* __restrict__ seg = cidx + cstart[c];
+            int v[kVoteSmall], bk[kVoteSmall];
+#pragma unroll
+            for (int a = 0; a < kVoteSmall; ++a) {
+                v[a] = a < cnt ? cls[(long)seg[a] * ldim + col] : 0;
+                bk[a] = (int)(label_key(v[a]) % 13ull);
+            }
+            int best_v = v[0], best_n = 0, best_f = 0;
+#pragma unroll
+            for (int a = 0; a < kVoteSmall; ++a) {
+                int n = 0, f = a;
+                bool seen = false;
+#pragma unroll
+                for (int u = kVoteSmall - 1; u >= 0; --u) {
+                    if (u < cnt && v[u] == v[a]) { ++n; if (u < a) seen = true; }
+                    if (u < a && bk[u] == bk[a]) f = u;
+                }
+                // later elements win ties of (count, bucket's first stamp): scanning a upwards with >= does that
+                if (a < cnt && !seen && (n > best_n || (n == best_n && f >= best_f))) { best_v = v[a]; best_n = n; best_f = f; }
+            }
+            out_cls[item] = best_v;
+        }
+    }
+    u64 todo = __ballot(big);
+    while (todo) {
+        const int src = __ffsll((long long)todo) - 1;
+        todo &= todo - 1;
+        const int bc = __shfl(c, src, 64), bcol = __shfl(col, src, 64);
+        const int cnt = ccnt[bc];
+        const long off = (long)cstart[bc] * ldim + (long)bcol * cnt;
+        VoteWs x = {w.lab + off, w.num + off, w.bkt + off, w.fst + off, w.ord_a + off, w.ord_b + off};
+        const int win = vote_wave(cls, ldim, bcol, cidx + cstart[bc], cnt, x);
+        if (lane == 0) out_cls[(long)blockIdx.x * 64 + src] = win;
+        __syncthreads();
+    }
 }
 
 inline size_t umap_bucket_cap(int n, int nb) { return (size_t)3 * (size_t)n + (size_t)16 * (size_t)nb + 64; }
@@ -478,13 +683,30 @@ int pcrcg_grid_subsample_batch(const float* pts, int n, const int* len, int nb, 
     return pcrcg::grid_subsample_bound(pts, n, len, nb, dl, max_p, out_pts, out_len, out_m, n, nullptr, ws, ws_bytes,
                                        as_stream(stream));
 }
+
+size_t pcrcg_grid_subsample_ex_ws_bytes(int n, int nb, int fdim, int ldim) {
+    if (n < 0) n = 0;
+    if (ldim < 0) ldim = 0;
+    const size_t N = (size_t)n + 1;
+    size_t b = pcrcg_grid_subsample_ws_bytes(n, nb);
+    if (fdim > 0 || ldim > 0) b += carve_bytes(N, sizeof(int));            // cell of every output row
+    if (ldim > 0) b += 6 * carve_bytes(N * (size_t)ldim, sizeof(int));     // VoteWs
+    return b;
+}
 }
 
-// n = a BOUND on the number of points (the clouds' lengths, on the device, say how many there are); out_cap rows fit
-// behind out_pts (fewer than the result: *overflow = 1, the output is cut there).
-int pcrcg::grid_subsample_bound(const float* pts, int n, const int* len, int nb, float dl, int max_p, float* out_pts,
-                                int* out_len, int* out_m, int out_cap, int* overflow, void* ws, size_t ws_bytes,
-                                hipStream_t stream) {
+namespace pcrcg {
+namespace {
+
+// what pcrcg_grid_subsample_batch_ex adds to the points: all null / 0 for the points-only entries
+struct CellExtras {
+    const float* feats; int fdim; long ld_feat; float* out_feats;
+    const int* classes; int ldim; int* out_classes;
+};
+
+int grid_subsample_run(const float* pts, int n, const int* len, int nb, float dl, int max_p, float* out_pts, int* out_len,
+                       int* out_m, int out_cap, int* overflow, const CellExtras& ex, void* ws, size_t ws_bytes,
+                       hipStream_t stream) {
     PCRCG_CHECK_ARG(n >= 0 && nb >= 1 && out_cap >= 0);
     PCRCG_CHECK_ARG(pts && len && out_pts && out_len && out_m && ws);
     PCRCG_CHECK_ARG(dl > 0.0f);
@@ -513,6 +735,14 @@ int pcrcg::grid_subsample_bound(const float* pts, int n, const int* len, int nb,
     int* ebase = cv.take<int>(7 * es);
     int* bbase = cv.take<int>(4 * bs);
     void* scan_ws = cv.take<char>(scan_ws_bytes(n + 1));
+    // (the points-only layout ends here; what follows exists for features / classes alone)
+    int* out_cell = ex.fdim > 0 || ex.ldim > 0 ? cv.take<int>(N) : nullptr;
+    VoteWs vote = {};
+    if (ex.ldim > 0) {
+        const size_t vs = carve_bytes(N * (size_t)ex.ldim, sizeof(int)) / sizeof(int);
+        int* v = cv.take<int>(6 * vs);
+        vote = {v, v + vs, v + 2 * vs, v + 3 * vs, v + 4 * vs, v + 5 * vs};
+    }
     PCRCG_CHECK_WS(cv);
 
     const int blocks = n > 0 ? (n + 255) / 256 : 1;
@@ -534,7 +764,54 @@ int pcrcg::grid_subsample_bound(const float* pts, int n, const int* len, int nb,
         hipLaunchKernelGGL(k_barycentres, dim3(blocks), dim3(256), 0, st, pts, mtot, cstart, ccnt, cidx, cbary);
     }
     hipLaunchKernelGGL(k_order_emit, dim3(nb), dim3(kUmapThreads), 0, st, nb, coff, rank, mtot, ckey, cbary, ebase,
-                       bbase, (long)es, (long)bs, max_p, out_pts, out_len, out_m, out_cap, overflow);
+                       bbase, (long)es, (long)bs, max_p, out_pts, out_len, out_m, out_cap, overflow, out_cell);
+    // the rows are known to the device alone (*out_m): the grids below cover the bound and the rest returns at once
+    const long rows_bound = n < out_cap ? n : out_cap;
+    if (ex.fdim > 0 && rows_bound > 0) {
+        const bool wide = ex.fdim % 4 == 0 && ex.ld_feat % 4 == 0 && ((uintptr_t)ex.feats & 15) == 0 &&
+                          ((uintptr_t)ex.out_feats & 15) == 0;
+        const int per_lane = wide ? 4 : 1;
+        int lanes_log2 = 0;
+        while (lanes_log2 < 6 && (per_lane << lanes_log2) < ex.fdim) ++lanes_log2;
+        const long fblocks = ((rows_bound << lanes_log2) + 255) / 256;
+        if (wide)
+            hipLaunchKernelGGL(k_cell_features<4>, dim3((unsigned)fblocks), dim3(256), 0, st, ex.feats, ex.fdim, ex.ld_feat,
+                               out_m, out_cell, cstart, ccnt, cidx, ex.out_feats, lanes_log2);
+        else
+            hipLaunchKernelGGL(k_cell_features<1>, dim3((unsigned)fblocks), dim3(256), 0, st, ex.feats, ex.fdim, ex.ld_feat,
+                               out_m, out_cell, cstart, ccnt, cidx, ex.out_feats, lanes_log2);
+    }
+    if (ex.ldim > 0 && rows_bound > 0) {
+        const long lblocks = (rows_bound * ex.ldim + 63) / 64;
+        hipLaunchKernelGGL(k_cell_labels, dim3((unsigned)lblocks), dim3(64), 0, st, ex.classes, ex.ldim, out_m, out_cell, cstart,
+                           ccnt, cidx, ex.out_classes, vote);
+    }
     PCRCG_CHECK_LAUNCH();
     return PCRCG_OK;
+}
+
+}  // namespace
+}  // namespace pcrcg
+
+// n = a BOUND on the number of points (the clouds' lengths, on the device, say how many there are); out_cap rows fit
+// behind out_pts (fewer than the result: *overflow = 1, the output is cut there).
+int pcrcg::grid_subsample_bound(const float* pts, int n, const int* len, int nb, float dl, int max_p, float* out_pts,
+                                int* out_len, int* out_m, int out_cap, int* overflow, void* ws, size_t ws_bytes,
+                                hipStream_t stream) {
+    return grid_subsample_run(pts, n, len, nb, dl, max_p, out_pts, out_len, out_m, out_cap, overflow, CellExtras{}, ws,
+                              ws_bytes, stream);
+}
+
+extern "C" int pcrcg_grid_subsample_batch_ex(const float* pts, int n, const int* len, int nb, float dl, int max_p,
+                                             const float* feats, int fdim, int ld_feat, const int* classes, int ldim,
+                                             float* out_pts, int* out_len, int* out_m, float* out_feats, int* out_classes,
+                                             void* ws, size_t ws_bytes, void* stream) {
+    PCRCG_CHECK_ARG(fdim >= 0 && ldim >= 0);
+    PCRCG_CHECK_ARG(fdim == 0 || (feats && out_feats && ld_feat >= fdim));
+    PCRCG_CHECK_ARG(ldim == 0 || (classes && out_classes));
+    PCRCG_CHECK_ARG(n >= 0 && (unsigned long long)n * (unsigned long long)(ldim > fdim ? ldim : fdim) < (1ull << 40));
+    const CellExtras ex = {fdim ? feats : nullptr, fdim, (long)ld_feat, fdim ? out_feats : nullptr,
+                           ldim ? classes : nullptr, ldim, ldim ? out_classes : nullptr};
+    return grid_subsample_run(pts, n, len, nb, dl, max_p, out_pts, out_len, out_m, n, nullptr, ex, ws, ws_bytes,
+                              as_stream(stream));
 }

@@ -107,6 +107,48 @@ def grid_subsample(points, lengths, dl, max_p=0):
     return out[:int(out_m.item())], out_len
 
 
+def grid_subsample_ex(points, lengths, dl, max_p=0, features=None, classes=None):
+    """batch_grid_subsampling with the reference's optional features and classes, on device.  points [N,3] f32,
+    lengths [B] i32, features [N,fdim] f32 (any row stride) or None, classes [N] or [N,ldim] i32 or None ->
+    (sub_points [M,3] f32, sub_lengths [B] i32, sub_features [M,fdim] f32 or None, sub_classes [M,ldim] i32 or None):
+    per cell the fp32 mean of the feature rows (summed in input order, one fp32 division) and per label column the most
+    frequent label, ties as the reference's unordered_map decides them; rows in the barycentres' order, cut by max_p at
+    the same rows.  Every cloud's classes are its own rows.  One host sync (to learn M)."""
+    L = _lib.lib()
+    points = _dev(points, _F32, "points").contiguous()
+    lengths = _dev(lengths, _I32, "lengths").contiguous()
+    n, nb = points.shape[0], lengths.shape[0]
+    dev = points.device
+    fdim = ldim = ld_feat = 0
+    out_f = out_c = None
+    if features is not None:
+        features, ld_feat = _rows(features, _F32, "features")
+        if features.shape[0] != n:
+            raise RuntimeError("pcrcg_amd: `features` must have one row per point")
+        fdim = features.shape[1]
+        out_f = torch.empty((max(n, 1), fdim), dtype=_F32, device=dev)
+    if classes is not None:
+        classes = _dev(classes, _I32, "classes")
+        if classes.dim() not in (1, 2) or classes.shape[0] != n:
+            raise RuntimeError("pcrcg_amd: `classes` must be [N] or [N, d] with one row per point")
+        classes = classes.reshape(n, -1).contiguous()
+        ldim = classes.shape[1]
+        out_c = torch.empty((max(n, 1), ldim), dtype=_I32, device=dev)
+    out = torch.empty((max(n, 1), 3), dtype=_F32, device=dev)
+    out_len = torch.empty(nb, dtype=_I32, device=dev)
+    out_m = torch.zeros(1, dtype=_I32, device=dev)
+    nbytes = L.pcrcg_grid_subsample_ex_ws_bytes(n, nb, fdim, ldim)
+    ws = _ws.get("subsample", nbytes, dev)
+    _lib.check(L.pcrcg_grid_subsample_batch_ex(points.data_ptr(), n, lengths.data_ptr(), nb, float(dl), int(max_p),
+                                               _ptr(features) if fdim else None, fdim, ld_feat,
+                                               _ptr(classes) if ldim else None, ldim, out.data_ptr(), out_len.data_ptr(),
+                                               out_m.data_ptr(), _ptr(out_f) if fdim else None,
+                                               _ptr(out_c) if ldim else None, ws.data_ptr(), nbytes, _stream()),
+               "pcrcg_grid_subsample_batch_ex")
+    m = int(out_m.item())
+    return out[:m], out_len, None if out_f is None else out_f[:m], None if out_c is None else out_c[:m]
+
+
 def host_copy(t):
     """Asynchronous device -> pinned-host copy of a small int tensor on the current stream:
     -> (pinned tensor, event recorded after the copy); read the tensor after event.synchronize()."""
