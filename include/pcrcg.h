@@ -273,6 +273,24 @@ int pcrcg_kpconv_aggregate_bf16(const float* q_pts, int nq, const float* s_pts, 
                                 int ld_idx, const float* x, int cin, const float* kp, float extent, void* x_bf16,
                                 void* wf_bf16, float* inv_n, void* ws, size_t ws_bytes, void* stream);
 
+/* The GENERAL KPConv gather (csrc/kpconv_ex.hip): deformable and modulated kernels, every influence function and both
+ * aggregation modes of ref:models/blocks.py:229-374.  The arguments of pcrcg_kpconv_aggregate (same workspace, same wf
+ * and inv_n) plus:
+ *   offset_features [nq, ld_off] f32 or NULL (rigid kernel): the offset convolution's output with offset_bias added;
+ *     columns 0 .. 44 are the offsets, kp_q[k] = offset_features[q, 3k..3k+2] * extent + kp[k] (fp32, not fused), columns
+ *     45 .. 59 the modulation logits when `modulated` (ld_off >= 45, or 60 when modulated);
+ *   influence: 0 constant (1), 1 linear (max(0, 1 - sqrt(d2)/extent)), 2 gaussian (exp(-d2 / (2 (0.3 extent)^2 + 1e-9)));
+ *   closest: 0 sum, 1 only the nearest kernel point of a neighbour keeps its weight (first index on ties);
+ *   modulated: wf[q,k,:] is multiplied by 2 sigmoid(offset_features[q, 45 + k]);
+ *   min_d2 [nq, 15] f32 or NULL: min over ALL h columns (shadow columns included) of d2[q,h,k].
+ * d2[q,h,k] = |s[idx[q,h]] - q - kp_q[k]|^2.  With offset_features, neighbour h is KEPT iff d2[q,h,k] < extent * extent
+ * for some k; a neighbour that is not kept contributes nothing to wf, is not counted in n_q and its feature row is not
+ * read.  Without, every neighbour is kept.  Inference only: there is no backward for this entry. */
+int pcrcg_kpconv_aggregate_ex(const float* q_pts, int nq, const float* s_pts, int ns, const int64_t* idx, int h,
+                              int ld_idx, const float* x, int cin, const float* kp, float extent,
+                              const float* offset_features, int ld_off, int influence, int closest, int modulated,
+                              float* wf, float* inv_n, float* min_d2, void* ws, size_t ws_bytes, void* stream);
+
 /* The order in which the gather kernels visit their queries (csrc/walk.hip).  pcrcg_query_walk writes walk[n] i32, a
  * permutation of 0 .. n-1: the queries of points [n,3] sorted by key, the 12-bit Morton interleave (x bit i -> key bit 3i,
  * y -> 3i+1, z -> 3i+2) of the point's cell in a 16 x 16 x 16 grid over the cloud's bounding box,

@@ -62,6 +62,9 @@ SIGNATURES = {
     "pcrcg_kpconv_aggregate_bf16": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int,
                                             c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
                                             c_void_p]),
+    "pcrcg_kpconv_aggregate_ex": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int,
+                                          c_void_p, c_float, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                          c_void_p, c_void_p, c_size_t, c_void_p]),
     "pcrcg_query_walk": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "pcrcg_kpconv_aggregate_walk": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int,
                                             c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),

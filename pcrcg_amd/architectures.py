@@ -11,7 +11,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops
-from .blocks import NearestUpsampleBlock, block_decider
+from .blocks import NearestUpsampleBlock, block_decider, non_rigid_block
 from .config import as_config
 from .gcn import GCN
 
@@ -92,6 +92,11 @@ class KPFCNN(nn.Module):
         self._runner = None
         # the C++ runner enqueues the forward (one FFI call); set use_runner = False for the op-by-op mirror forward_ops
         self.use_runner = bool(config.use_batch_norm)
+        # a deformable, 'gaussian' / 'constant' influence or 'closest' aggregation KPConv anywhere: the general gather
+        # kernel (ops.kpconv_ex), which the C++ runners do not sequence and which has no backward -- forward_ops, inference
+        self.non_rigid = non_rigid_block(self)
+        if self.non_rigid is not None:
+            self.use_runner = False
 
     def regular_score(self, score):
         """ref:models/architectures.py:176-179."""
@@ -175,6 +180,9 @@ class KPFCNN(nn.Module):
 
     def forward(self, batch, backbone2d=None):
         training = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+        if training and self.non_rigid is not None:
+            raise NotImplementedError("pcrcg_amd.KPFCNN: a model with %s is inference only; wrap the call in "
+                                      "torch.no_grad()" % self.non_rigid)
         if self.image_feature:
             # the C++ runners (inference and train step) take the 129 channels in rows of 132 floats -- the first KPConv's
             # gather kernel reads whole float4s -- against weights padded with zero rows; the op-by-op paths take [N, 129]

@@ -70,15 +70,18 @@ def global_average(x, batch_lengths):
 
 
 class KPConv(nn.Module):
-    """ref:models/blocks.py:135-379 (rigid kernel, 'linear' influence, 'sum' aggregation)."""
+    """ref:models/blocks.py:135-379.  The rigid / linear / sum configuration of the shipped architectures runs in
+    ops.kpconv; every other one (deformable, modulated, 'constant' / 'gaussian' influence, 'closest' aggregation) in
+    ops.kpconv_ex, which is inference only."""
 
     def __init__(self, kernel_size, p_dim, in_channels, out_channels, KP_extent, radius,
                  fixed_kernel_points="center", KP_influence="linear", aggregation_mode="sum", deformable=False,
                  modulated=False):
         super().__init__()
-        if deformable or KP_influence != "linear" or aggregation_mode != "sum":
-            raise NotImplementedError("pcrcg_amd.KPConv: only the rigid / linear / sum configuration of the "
-                                      "shipped architectures is implemented")
+        if KP_influence not in ("constant", "linear", "gaussian"):
+            raise ValueError("Unknown influence function type (config.KP_influence)")
+        if aggregation_mode not in ("sum", "closest"):
+            raise ValueError("Unknown convolution mode. Should be 'closest' or 'sum'")
         self.K = kernel_size
         self.p_dim = p_dim
         self.in_channels = in_channels
@@ -90,17 +93,55 @@ class KPConv(nn.Module):
         self.aggregation_mode = aggregation_mode
         self.deformable = deformable
         self.modulated = modulated
+        # running values of the last forward (the reference's regularisation loss reads them, :169-172)
+        self.min_d2 = None
+        self.deformed_KP = None
+        self.offset_features = None
         self.weights = Parameter(torch.zeros((self.K, in_channels, out_channels), dtype=torch.float32),
                                  requires_grad=True)
+        # :179-198 -- created before this module's own weights are drawn, as in the reference (same random stream)
+        if deformable:
+            self.offset_dim = (self.p_dim + 1) * self.K if modulated else self.p_dim * self.K
+            self.offset_conv = KPConv(self.K, self.p_dim, self.in_channels, self.offset_dim, KP_extent, radius,
+                                      fixed_kernel_points=fixed_kernel_points, KP_influence=KP_influence,
+                                      aggregation_mode=aggregation_mode)
+            self.offset_bias = Parameter(torch.zeros(self.offset_dim, dtype=torch.float32), requires_grad=True)
+        else:
+            self.offset_dim = None
+            self.offset_conv = None
+            self.offset_bias = None
         kaiming_uniform_(self.weights, a=math.sqrt(5))
         self.kernel_points = Parameter(
             torch.tensor(load_kernels(self.radius, self.K, dimension=self.p_dim, fixed=self.fixed_kernel_points),
                          dtype=torch.float32), requires_grad=False)
 
+    @property
+    def rigid(self):
+        """The configuration of the shipped architectures: the one the C++ runners and the backward kernels cover."""
+        return not self.deformable and self.KP_influence == "linear" and self.aggregation_mode == "sum"
+
     def forward(self, q_pts, s_pts, neighb_inds, x):
-        _no_autograd(x, self.weights)
-        return ops.kpconv(q_pts, s_pts, neighb_inds, x, self.kernel_points.data, self.weights.data,
-                          self.KP_extent)
+        if self.rigid:
+            _no_autograd(x, self.weights)
+            return ops.kpconv(q_pts, s_pts, neighb_inds, x, self.kernel_points.data, self.weights.data,
+                              self.KP_extent)
+        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
+            raise NotImplementedError("pcrcg_amd.KPConv: deformable kernels, 'constant' / 'gaussian' influence and "
+                                      "'closest' aggregation are inference only; wrap the call in torch.no_grad()")
+        offset_features = None
+        if self.deformable:
+            # :238 -- the offset convolution with offset_bias added (a rigid kernel of this module's influence mode)
+            offset_features = self.offset_conv(q_pts, s_pts, neighb_inds, x) + self.offset_bias.data
+            self.offset_features = offset_features
+            offsets = offset_features[:, :self.p_dim * self.K].reshape(-1, self.K, self.p_dim) * self.KP_extent
+            self.deformed_KP = offsets + self.kernel_points.data                                  # :258,279
+        out = ops.kpconv_ex(q_pts, s_pts, neighb_inds, x, self.kernel_points.data, self.weights.data, self.KP_extent,
+                            offset_features=offset_features, influence=self.KP_influence,
+                            aggregation=self.aggregation_mode, modulated=self.deformable and self.modulated,
+                            want_min_d2=self.deformable)
+        if self.deformable:
+            out, self.min_d2 = out
+        return out
 
     def __repr__(self):
         return "KPConv(radius: {:.2f}, extent: {:.2f}, in_feat: {:d}, out_feat: {:d})".format(
@@ -292,15 +333,35 @@ class MaxPoolBlock(nn.Module):
         return max_pool(x, batch["pools"][self.layer_ind + 1])
 
 
+def non_rigid_block(model):
+    """Name of the first block of `model` whose KPConv is outside the rigid / linear / sum configuration, or None."""
+    for group in ("encoder_blocks", "decoder_blocks"):
+        for i, block in enumerate(getattr(model, group, [])):
+            conv = getattr(block, "KPConv", None)
+            if conv is not None and not conv.rigid:
+                what = "deformable" if conv.deformable else "KP_influence='%s', aggregation_mode='%s'" % (
+                    conv.KP_influence, conv.aggregation_mode)
+                return "%s[%d] '%s' (%s)" % (group, i, block.block_name, what)
+    return None
+
+
+def refuse_non_rigid(model, who):
+    name = non_rigid_block(model)
+    if name is not None:
+        raise RuntimeError("pcrcg_amd.%s covers rigid KPConv kernels with 'linear' influence and 'sum' aggregation only; "
+                           "this model has %s: run it through KPFCNN.forward (forward_ops) under torch.no_grad()"
+                           % (who, name))
+
+
 def block_decider(block_name, radius, in_dim, out_dim, layer_ind, config):
     """ref:models/blocks.py:387-430."""
     if block_name == "unary":
         return UnaryBlock(in_dim, out_dim, config.use_batch_norm, config.batch_norm_momentum)
     if block_name == "last_unary":
         return LastUnaryBlock(in_dim, config.final_feats_dim + 2, config.use_batch_norm, config.batch_norm_momentum)
-    if block_name in ("simple", "simple_strided"):
+    if block_name in ("simple", "simple_strided", "simple_deformable", "simple_deformable_strided"):
         return SimpleBlock(block_name, in_dim, out_dim, radius, layer_ind, config)
-    if block_name in ("resnetb", "resnetb_strided"):
+    if block_name in ("resnetb", "resnetb_strided", "resnetb_deformable", "resnetb_deformable_strided"):
         return ResnetBottleneckBlock(block_name, in_dim, out_dim, radius, layer_ind, config)
     if block_name in ("max_pool", "max_pool_wide"):
         return MaxPoolBlock(layer_ind)
@@ -308,6 +369,6 @@ def block_decider(block_name, radius, in_dim, out_dim, layer_ind, config):
         return GlobalAverageBlock()
     if block_name == "nearest_upsample":
         return NearestUpsampleBlock(layer_ind)
-    if any(t in block_name for t in ("deformable", "invariant", "equivariant")):
+    if any(t in block_name for t in ("invariant", "equivariant")):
         raise NotImplementedError("pcrcg_amd: block '%s' is not used by the shipped architectures" % block_name)
     raise ValueError("Unknown block name in the architecture definition : " + block_name)

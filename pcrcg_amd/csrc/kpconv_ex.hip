@@ -1,0 +1,327 @@
+// kpconv_ex.hip -- the general KPConv gather: deformable and modulated kernels, every influence function and both
+// aggregation modes of ref:models/blocks.py:229-374 (stage 1 of KPConv.forward; stage 2 is the same wf @ W contraction
+// as for the rigid kernel).  kpconv.hip keeps the rigid / linear / sum configuration of the shipped architectures; this
+// file serves everything else and is built with contraction off (the deformed kernel points are offset * extent + kp,
+// a product and a sum, as the reference rounds them).
+//
+//   kp_q[k]   = offset_features[q, 3k..3k+2] * extent + kp[k]                     (rigid: kp[k])          (:258,279)
+//   d2[q,h,k] = |s[idx[q,h]] - q - kp_q[k]|^2          (shadow idx == ns: the point (1e6, 1e6, 1e6))      (:269-289)
+//   kept(q,h) = deformable ? any_k d2 < extent^2 : true                                                  (:292-316)
+//   w[q,h,k]  = constant 1 | linear max(0, 1 - sqrt(d2) / extent) | gaussian exp(-d2 / (2 (0.3 extent)^2 + 1e-9));
+//               closest: only k* = argmin_k d2 (first index on ties) keeps its weight                     (:321-342)
+//   wf[q,k,:] = sum_{h kept} w * x[idx[q,h],:]   (* 2 sigmoid(offset_features[q, 3K+k]) when modulated)   (:354-358)
+//   n_q       = max(1, #{h kept : sum_c x[idx[q,h],c] > 0})                                              (:369-372)
+//   min_d2[q,k] = min over ALL h < H of d2, shadow columns included                                       (:295)
+//
+// k_kpconv_ex_mfma follows the plan of k_kpconv_mfma (kpconv.hip): one wavefront per (query, channel chunk), lane
+// (hsub = lane >> 4, j = lane & 15) evaluates neighbour h0 + hsub against kernel point j and supplies that weight as
+// the A element of v_mfma_f32_16x16x4_f32; the 16 lanes of a neighbour read one 256-byte segment of its feature row.
+// What is new: the kernel points are the item's own (lane j holds kp_q[j]); the kept bit of a neighbour is the OR over
+// its 16 lanes (one ballot per step); closest mode is a 16-lane (d2, k) argmin by four butterfly shuffles; min_d2 is a
+// running per-lane minimum, joined over the four neighbour groups at the end.  A neighbour that is not kept reads no
+// feature row of its own (its address is clamped to row 0, as a shadow's is, and the value discarded).
+// k_kpconv_ex_scalar (cin == 1, channel counts that are no multiple of 4, unaligned rows) is a plain restatement:
+// one wavefront per query, lanes = channels, neighbours in turn.
+#include <hip/hip_ext.h>
+
+#include "common.h"
+
+namespace pcrcg {
+namespace {
+
+constexpr int K = PCRCG_KPOINTS;
+constexpr int kWavesPerBlock = 4;
+constexpr float kShadow = 1e6f;
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+struct ExMode {
+    int influence;      // 0 constant, 1 linear, 2 gaussian
+    int closest, modulated;
+    float extent, ext2, gauss_den;
+};
+
+__device__ __forceinline__ float influence_of(float d2, const ExMode& m) {
+    if (m.influence == 0) return 1.0f;
+    if (m.influence == 1) return fmaxf(1.0f - sqrtf(d2) / m.extent, 0.0f);
+    return expf(-d2 / m.gauss_den);
+}
+
+template <int NB>
+__global__ void __launch_bounds__(kWavesPerBlock * 64) k_kpconv_ex_mfma(
+    const float* __restrict__ q_pts, int nq, int ns, const long long* __restrict__ idx, int H, int ld_idx,
+    const float* __restrict__ x, int cin, const float* __restrict__ kp, const float* __restrict__ off, int ld_off,
+    ExMode mode, const float4* __restrict__ pk, float* __restrict__ wf, float* __restrict__ inv_n,
+    float* __restrict__ min_d2, int nchunk) {
+    constexpr int STEPS = NB >= 4 ? 2 : 4;
+    const int lane = threadIdx.x & 63;
+    const int hsub = lane >> 4, j = lane & 15;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const long gw = (long)blockIdx.x * kWavesPerBlock + wave;
+    const long nw = (long)gridDim.x * kWavesPerBlock;
+    const long items = (long)nq * nchunk;
+    const bool jvalid = j < K;
+    const float kx0 = jvalid ? kp[3 * j] : 0.f, ky0 = jvalid ? kp[3 * j + 1] : 0.f, kz0 = jvalid ? kp[3 * j + 2] : 0.f;
+    const bool deform = off != nullptr;
+
+    for (long item = gw; item < items; item += nw) {
+        const int q = (int)(item / nchunk), chunk = (int)(item - (long)q * nchunk);
+        const int c0 = chunk * 64 * NB;
+        const float qx = q_pts[3 * (long)q], qy = q_pts[3 * (long)q + 1], qz = q_pts[3 * (long)q + 2];
+        float kpx = kx0, kpy = ky0, kpz = kz0;
+        if (deform && jvalid) {
+            const float* o = off + (long)q * ld_off + 3 * j;
+            kpx = o[0] * mode.extent + kx0;
+            kpy = o[1] * mode.extent + ky0;
+            kpz = o[2] * mode.extent + kz0;
+        }
+        const bool want_min = min_d2 != nullptr && chunk == 0;
+        f32x4 acc[NB][4];
+#pragma unroll
+        for (int b = 0; b < NB; ++b)
+#pragma unroll
+            for (int n = 0; n < 4; ++n) acc[b][n] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        int npos = 0;
+        float dmin = INFINITY;
+        bool any_shadow = false;
+        for (int hc = 0; hc < H; hc += 64) {
+            // lanes = neighbours: index, centred coordinates and row-positive flag, once per 64 neighbours
+            const int h = hc + lane;
+            const long long iv = idx[(long)q * ld_idx + (h < H ? h : H - 1)];
+            const int i = (h < H && iv >= 0 && iv < ns) ? (int)iv : -1;
+            const float4 sp = pk[i >= 0 ? i : 0];
+            const float px = sp.x - qx, py = sp.y - qy, pz = sp.z - qz;
+            const bool pos = i >= 0 && sp.w != 0.f;
+            any_shadow = any_shadow || __ballot(h < H && i < 0) != 0ull;
+            const unsigned long long real_lanes = __ballot(i >= 0);
+            const int hn = real_lanes ? 64 - (int)__clzll(real_lanes) : 0;      // behind the last real neighbour: shadows only
+            for (int h0 = 0; h0 < hn; h0 += 4 * STEPS) {
+                float w[STEPS];
+                float4 v[STEPS][NB];
+#pragma unroll
+                for (int s = 0; s < STEPS; ++s) {
+                    const int src = (h0 + 4 * s + hsub) & 63;
+                    const int ii = __shfl(i, src, 64);
+                    const float nx = __shfl(px, src, 64), ny = __shfl(py, src, 64), nz = __shfl(pz, src, 64);
+                    const int pp = __shfl((int)pos, src, 64);
+                    const bool real = ii >= 0 && h0 + 4 * s + hsub < hn;
+                    const float dx = nx - kpx, dy = ny - kpy, dz = nz - kpz;
+                    const float d2 = (real && jvalid) ? dx * dx + dy * dy + dz * dz : INFINITY;
+                    dmin = fminf(dmin, d2);
+                    // kept: any of the neighbour's 16 lanes in range (rigid: every real neighbour)
+                    bool kept = real;
+                    if (deform) {
+                        const unsigned long long inr = __ballot(d2 < mode.ext2);
+                        kept = ((inr >> (16 * hsub)) & 0xffffull) != 0ull;
+                    }
+                    float wv = influence_of(d2 == INFINITY ? 0.f : d2, mode);
+                    if (mode.closest) {
+                        float bd = d2;
+                        int bk = j;
+#pragma unroll
+                        for (int m = 1; m < 16; m <<= 1) {
+                            const float od = __shfl_xor(bd, m, 64);
+                            const int ok = __shfl_xor(bk, m, 64);
+                            const bool take = od < bd || (od == bd && ok < bk);
+                            bd = take ? od : bd;
+                            bk = take ? ok : bk;
+                        }
+                        if (bk != j) wv = 0.f;
+                    }
+                    w[s] = (kept && jvalid) ? wv : 0.f;
+                    if (chunk == 0 && j == 0 && kept && pp) ++npos;
+                    const float* xrow = x + (long)(kept ? ii : 0) * cin;
+#pragma unroll
+                    for (int b = 0; b < NB; ++b) {
+                        const int c = c0 + 64 * b + 4 * j;
+                        const float4 t = *reinterpret_cast<const float4*>(xrow + (c < cin ? c : cin - 4));
+                        const bool ok = kept && c < cin;
+                        v[s][b] = make_float4(ok ? t.x : 0.f, ok ? t.y : 0.f, ok ? t.z : 0.f, ok ? t.w : 0.f);
+                    }
+                }
+#pragma unroll
+                for (int s = 0; s < STEPS; ++s)
+#pragma unroll
+                    for (int b = 0; b < NB; ++b) {
+                        acc[b][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[s], v[s][b].x, acc[b][0], 0, 0, 0);
+                        acc[b][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[s], v[s][b].y, acc[b][1], 0, 0, 0);
+                        acc[b][2] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[s], v[s][b].z, acc[b][2], 0, 0, 0);
+                        acc[b][3] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[s], v[s][b].w, acc[b][3], 0, 0, 0);
+                    }
+            }
+        }
+        // D layout: register r of lane (hsub, j) = kernel point 4*hsub + r, channel group j
+        float mod[4] = {1.f, 1.f, 1.f, 1.f};
+        if (mode.modulated) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int k = 4 * hsub + r;
+                if (k < K) mod[r] = 2.0f * (1.0f / (1.0f + expf(-off[(long)q * ld_off + 3 * K + k])));
+            }
+        }
+        float* o = wf + (long)q * K * cin + c0;
+#pragma unroll
+        for (int b = 0; b < NB; ++b) {
+            const int c = 64 * b + 4 * j;
+            if (c0 + c >= cin) continue;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int k = 4 * hsub + r;
+                if (k < K) {
+                    typedef float v4f __attribute__((ext_vector_type(4)));
+                    const v4f val = {acc[b][0][r] * mod[r], acc[b][1][r] * mod[r], acc[b][2][r] * mod[r], acc[b][3][r] * mod[r]};
+                    __builtin_nontemporal_store(val, reinterpret_cast<v4f*>(o + (long)k * cin + c));
+                }
+            }
+        }
+        if (chunk == 0) {
+            npos += __shfl_xor(npos, 16, 64);
+            npos += __shfl_xor(npos, 32, 64);
+            if (lane == 0) inv_n[q] = 1.0f / (float)(npos > 1 ? npos : 1);
+        }
+        if (want_min) {
+            dmin = fminf(dmin, __shfl_xor(dmin, 16, 64));
+            dmin = fminf(dmin, __shfl_xor(dmin, 32, 64));
+            if (any_shadow) {       // every shadow column is the same point
+                const float dx = (kShadow - qx) - kpx, dy = (kShadow - qy) - kpy, dz = (kShadow - qz) - kpz;
+                dmin = fminf(dmin, dx * dx + dy * dy + dz * dz);
+            }
+            if (hsub == 0 && jvalid) min_d2[(long)q * K + j] = dmin;
+        }
+    }
+}
+
+// Plain restatement for cin == 1, channel counts that are no multiple of 4 and unaligned rows: one wavefront per query,
+// lanes = channels, neighbours in turn; every lane evaluates the neighbour's 15 distances itself.
+__global__ void __launch_bounds__(kWavesPerBlock * 64) k_kpconv_ex_scalar(
+    const float* __restrict__ q_pts, int nq, const float* __restrict__ s_pts, int ns, const long long* __restrict__ idx, int H,
+    int ld_idx, const float* __restrict__ x, int cin, const float* __restrict__ kp, const float* __restrict__ off, int ld_off,
+    ExMode mode, const unsigned char* __restrict__ pos, float* __restrict__ wf, float* __restrict__ inv_n,
+    float* __restrict__ min_d2) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int gw = blockIdx.x * kWavesPerBlock + wave, nw = gridDim.x * kWavesPerBlock;
+    for (int q = gw; q < nq; q += nw) {
+        const float qx = q_pts[3 * (long)q], qy = q_pts[3 * (long)q + 1], qz = q_pts[3 * (long)q + 2];
+        float kpx[K], kpy[K], kpz[K], mod[K], dmin[K];
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            kpx[k] = kp[3 * k]; kpy[k] = kp[3 * k + 1]; kpz[k] = kp[3 * k + 2];
+            if (off) {
+                const float* o = off + (long)q * ld_off + 3 * k;
+                kpx[k] = o[0] * mode.extent + kpx[k];
+                kpy[k] = o[1] * mode.extent + kpy[k];
+                kpz[k] = o[2] * mode.extent + kpz[k];
+            }
+            mod[k] = mode.modulated ? 2.0f * (1.0f / (1.0f + expf(-off[(long)q * ld_off + 3 * K + k]))) : 1.0f;
+            dmin[k] = INFINITY;
+        }
+        int npos = 0;
+        for (int cbase = 0; cbase < cin; cbase += 64) {
+            const int c = cbase + lane;
+            float acc[K];
+#pragma unroll
+            for (int k = 0; k < K; ++k) acc[k] = 0.0f;
+            for (int h = 0; h < H; ++h) {
+                const long long iv = idx[(long)q * ld_idx + h];
+                const bool real = iv >= 0 && iv < ns;
+                const long i = real ? (long)iv : 0;
+                const float nx = (real ? s_pts[3 * i] : kShadow) - qx, ny = (real ? s_pts[3 * i + 1] : kShadow) - qy,
+                            nz = (real ? s_pts[3 * i + 2] : kShadow) - qz;
+                float d2[K];
+                bool inr = false;
+                int kmin = 0;
+#pragma unroll
+                for (int k = 0; k < K; ++k) {
+                    const float dx = nx - kpx[k], dy = ny - kpy[k], dz = nz - kpz[k];
+                    d2[k] = dx * dx + dy * dy + dz * dz;
+                    inr = inr || d2[k] < mode.ext2;
+                    if (cbase == 0) dmin[k] = fminf(dmin[k], d2[k]);
+                }
+#pragma unroll
+                for (int k = 1; k < K; ++k)
+                    if (d2[k] < d2[kmin]) kmin = k;
+                const bool kept = real && (off ? inr : true);
+                if (!kept) continue;
+                if (cbase == 0 && pos[i] != 0) ++npos;
+                const float xv = c < cin ? x[i * cin + c] : 0.0f;
+#pragma unroll
+                for (int k = 0; k < K; ++k) {
+                    float wv = influence_of(d2[k], mode);
+                    if (mode.closest && k != kmin) wv = 0.f;
+                    acc[k] += wv * xv;
+                }
+            }
+            if (c < cin)
+#pragma unroll
+                for (int k = 0; k < K; ++k) wf[(long)q * K * cin + (long)k * cin + c] = acc[k] * mod[k];
+        }
+        if (lane == 0) {
+            inv_n[q] = 1.0f / (float)(npos > 1 ? npos : 1);
+            if (min_d2)
+#pragma unroll
+                for (int k = 0; k < K; ++k) min_d2[(long)q * K + k] = dmin[k];
+        }
+    }
+}
+
+}  // namespace
+}  // namespace pcrcg
+
+using namespace pcrcg;
+
+extern "C" int pcrcg_kpconv_aggregate_ex(const float* q_pts, int nq, const float* s_pts, int ns, const int64_t* idx, int h,
+                                         int ld_idx, const float* x, int cin, const float* kp, float extent,
+                                         const float* offset_features, int ld_off, int influence, int closest, int modulated,
+                                         float* wf, float* inv_n, float* min_d2, void* ws, size_t ws_bytes, void* stream) {
+    PCRCG_CHECK_ARG(nq >= 0 && ns >= 1 && h >= 1 && ld_idx >= h && cin >= 1);
+    PCRCG_CHECK_ARG(extent > 0.0f);
+    PCRCG_CHECK_ARG(influence >= 0 && influence <= 2);
+    PCRCG_CHECK_ARG((closest == 0 || closest == 1) && (modulated == 0 || modulated == 1));
+    PCRCG_CHECK_ARG(q_pts && s_pts && idx && x && kp && wf && inv_n && ws);
+    PCRCG_CHECK_ARG(offset_features || !modulated);
+    PCRCG_CHECK_ARG(!offset_features || ld_off >= (modulated ? 4 : 3) * K);
+    if (nq == 0) return PCRCG_OK;
+    hipStream_t st = as_stream(stream);
+    Carver cv(ws, ws_bytes);
+    unsigned char* pos = cv.take<unsigned char>((size_t)ns + 1);
+    float4* pk = cv.take<float4>((size_t)ns + 1);
+    PCRCG_CHECK_WS(cv);
+    PCRCG_PROPAGATE(kpconv_pack(x, ns, cin, s_pts, ws, ws_bytes, st));
+    ExMode mode;
+    mode.influence = influence;
+    mode.closest = closest;
+    mode.modulated = modulated;
+    mode.extent = extent;
+    mode.ext2 = extent * extent;
+    const double sigma = 0.3 * (double)extent;
+    mode.gauss_den = (float)(2.0 * sigma * sigma + 1e-9);
+    const long long* idx_ll = reinterpret_cast<const long long*>(idx);
+    const int max_blocks = 256 * 32;
+    auto blocks_for = [&](long waves) {
+        const long b = (waves + kWavesPerBlock - 1) / kWavesPerBlock;
+        return (int)(b > max_blocks ? max_blocks : b);
+    };
+    const bool aligned = (cin % 4 == 0) && ((reinterpret_cast<uintptr_t>(x) & 15) == 0) &&
+                         ((reinterpret_cast<uintptr_t>(wf) & 15) == 0);
+    if (!aligned) {
+        hipLaunchKernelGGL(k_kpconv_ex_scalar, dim3(blocks_for(nq)), dim3(kWavesPerBlock * 64), 0, st, q_pts, nq, s_pts, ns,
+                           idx_ll, h, ld_idx, x, cin, kp, offset_features, ld_off, mode, (const unsigned char*)pos, wf, inv_n,
+                           min_d2);
+        PCRCG_CHECK_LAUNCH();
+        return PCRCG_OK;
+    }
+    // channel blocks of 64 per wavefront, chosen as kpconv.hip chooses them
+    const int nblk = (cin + 63) / 64;
+    int nb = nblk >= 4 ? 4 : (nblk >= 2 ? 2 : 1);
+    while (nb > 1 && ((long)nq * ((nblk + nb - 1) / nb) < 16384 || nblk % nb != 0)) nb >>= 1;
+    const int nchunk = (nblk + nb - 1) / nb;
+    const int blocks = blocks_for((long)nq * nchunk);
+#define LAUNCH(NBV)                                                                                                         \
+    hipLaunchKernelGGL((k_kpconv_ex_mfma<NBV>), dim3(blocks), dim3(kWavesPerBlock * 64), 0, st, q_pts, nq, ns, idx_ll, h,    \
+                       ld_idx, x, cin, kp, offset_features, ld_off, mode, (const float4*)pk, wf, inv_n, min_d2, nchunk)
+    if (nb == 4) LAUNCH(4);
+    else if (nb == 2) LAUNCH(2);
+    else LAUNCH(1);
+#undef LAUNCH
+    PCRCG_CHECK_LAUNCH();
+    return PCRCG_OK;
+}

@@ -460,6 +460,56 @@ def kpconv(q_pts, s_pts, idx, x, kernel_points, weights, extent):
     return gemm(wf, w2, row_scale=inv_n)
 
 
+_INFLUENCE = {"constant": 0, "linear": 1, "gaussian": 2}
+
+
+def kpconv_ex(q_pts, s_pts, idx, x, kernel_points, weights, extent, offset_features=None, influence="linear",
+              aggregation="sum", modulated=False, want_min_d2=False):
+    """KPConv.forward in every configuration of ref:models/blocks.py:229-374 (pcrcg_kpconv_aggregate_ex + the contraction
+    of `kpconv`).  offset_features [nq, 3K (+K when modulated)]: the offset convolution's output with its bias added, or
+    None for a rigid kernel.  -> out, or (out, min_d2 [nq, K]) with want_min_d2.  Inference only."""
+    L = _lib.lib()
+    if influence not in _INFLUENCE:
+        raise ValueError("Unknown influence function type (config.KP_influence)")
+    if aggregation not in ("sum", "closest"):
+        raise ValueError("Unknown convolution mode. Should be 'closest' or 'sum'")
+    q_pts = _dev(q_pts, _F32, "q_pts").contiguous()
+    s_pts = _dev(s_pts, _F32, "s_pts").contiguous()
+    idx, ld_idx = _rows(idx, _I64, "neighb_inds")
+    x = _dev(x, _F32, "x").contiguous()
+    kp = _dev(kernel_points, _F32, "kernel_points").contiguous()
+    nq, h = idx.shape
+    ns, cin = x.shape
+    kdim = kp.shape[0]
+    if kdim != 15:
+        raise RuntimeError("pcrcg_amd.kpconv_ex: only 15 kernel points are supported")
+    off, ld_off = None, 0
+    if offset_features is not None:
+        off, ld_off = _rows(offset_features, _F32, "offset_features")
+        if off.shape[0] != nq or off.shape[1] < (4 if modulated else 3) * kdim:
+            raise RuntimeError("pcrcg_amd.kpconv_ex: offset_features must be [nq, 3K] ([nq, 4K] when modulated)")
+    elif modulated:
+        raise RuntimeError("pcrcg_amd.kpconv_ex: modulated needs offset_features")
+    if cin % 4 != 0 and cin > 4:
+        pad = (-cin) % 4        # as in kpconv: zero channels change neither the sums nor the normaliser
+        x = torch.nn.functional.pad(x, (0, pad))
+        weights = torch.nn.functional.pad(weights, (0, 0, 0, pad))
+        cin += pad
+    wf = torch.empty((nq, kdim * cin), dtype=_F32, device=x.device)
+    inv_n = torch.empty(nq, dtype=_F32, device=x.device)
+    min_d2 = torch.empty((nq, kdim), dtype=_F32, device=x.device) if want_min_d2 else None
+    nbytes = L.pcrcg_kpconv_ws_bytes(ns)
+    ws = _ws.get("kpconv", nbytes, x.device)
+    w2 = _dev(weights, _F32, "weights").reshape(kdim * cin, -1)
+    _lib.check(L.pcrcg_kpconv_aggregate_ex(q_pts.data_ptr(), nq, s_pts.data_ptr(), ns, idx.data_ptr(), h, ld_idx,
+                                           x.data_ptr(), cin, kp.data_ptr(), float(extent), _ptr(off), ld_off,
+                                           _INFLUENCE[influence], int(aggregation == "closest"), int(bool(modulated)),
+                                           wf.data_ptr(), inv_n.data_ptr(), _ptr(min_d2), ws.data_ptr(), nbytes,
+                                           _stream()), "pcrcg_kpconv_aggregate_ex")
+    out = gemm(wf, w2, row_scale=inv_n)
+    return (out, min_d2) if want_min_d2 else out
+
+
 def inject_image_features(n_points, len_src, images, channels=128, width=None):
     """PCR-CG's image-feature injection (ref:models/architectures.py:195-514): -> x [n_points, channels + 1] f32 = ones
     with the 2-D features of the projected points written in.  `images`: list, IN THE REFERENCE'S WRITE ORDER (the last

@@ -16,7 +16,7 @@ import torch
 
 from . import _lib
 from .blocks import (LastUnaryBlock, NearestUpsampleBlock, ResnetBottleneckBlock, SimpleBlock, UnaryBlock,
-                     aligned_weight)
+                     aligned_weight, refuse_non_rigid)
 from .gcn import AttentionalPropagation, SelfAttention
 
 MAX_LEVELS, MAX_BLOCKS, MAX_GNN = 8, 32, 8
@@ -93,6 +93,7 @@ class Runner:
     """Descriptor cache for one KPFCNN module."""
 
     def __init__(self, model):
+        refuse_non_rigid(model, "runner.Runner")
         self.model = model
         self.sig = None
         self.desc = None

@@ -15,7 +15,8 @@ import ctypes
 import torch
 
 from . import _lib
-from .blocks import LastUnaryBlock, NearestUpsampleBlock, ResnetBottleneckBlock, SimpleBlock, UnaryBlock
+from .blocks import (LastUnaryBlock, NearestUpsampleBlock, ResnetBottleneckBlock, SimpleBlock, UnaryBlock,
+                     refuse_non_rigid)
 from .gcn import AttentionalPropagation, SelfAttention
 from .runner import (BLK_LAST_UNARY, BLK_RESNETB, BLK_SIMPLE, BLK_UNARY, BLK_UPSAMPLE, MAX_BLOCKS, MAX_GNN, Model, Runner)
 
@@ -61,6 +62,7 @@ def _grad(p):
 
 class TrainRunner:
     def __init__(self, model):
+        refuse_non_rigid(model, "train_runner.TrainRunner")
         self.model = model
         self.ws = None                            # cached workspace (values | gradients | scratch of one step)
         self._lent = None                         # ... while a tape that lives in it is outstanding
