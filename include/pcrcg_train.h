@@ -138,6 +138,27 @@ int pcrcg_gemm_f32_grad(const float* a, int lda, int trans_a, const float* b, in
 int pcrcg_kpconv_backward_dx(const float* q_pts, int nq, const float* s_pts, int ns, const int64_t* idx, int h,
                              int ld_idx, const float* d_wf, int cin, const float* kp, float extent, float* dx,
                              void* stream);
+/* Backward of the general gather pcrcg_kpconv_aggregate_ex (include/pcrcg.h: deformable / modulated kernels, every influence
+ * function, both aggregation modes; autograd of ref:models/blocks.py:229-374).  Geometry, x, offset_features and the mode
+ * arguments as for the forward entry.  d_wf [nq, 15*cin] = dL/d wf of the wf the forward STORED (after modulation), i.e.
+ * (dy * 1/n_q) @ W^T from pcrcg_gemm_f32_grad.  With nb = the centred neighbour, kp_q[k] = off[q,3k:3k+3] * extent + kp[k],
+ * diff = nb - kp_q, d2 = |diff|^2, w[q,h,k] the forward's influence weight (closest one-hot and kept bit applied),
+ * m[q,k] = 2 sigmoid(off[q,3K+k]) when modulated, else 1, and g[q,h,k] = sum_c d_wf[q,k,c] x[idx[q,h],c] over kept neighbours:
+ *   dx [ns, cin]   (ACCUMULATED into, zero it first; may be NULL):  dx[idx[q,h],c] += sum_k w m d_wf[q,k,c]
+ *   d_off [nq, 3K or 4K], leading dimension ld_doff (OVERWRITTEN; may be NULL, must be NULL without offset_features):
+ *     d_off[q,3k+a] = extent * sum_h m g dw/dkp_a,   dw/dkp_a = linear:   diff_a / (sqrt(d2) extent) where w > 0, else 0
+ *                                                               gaussian: 2 w diff_a / (2 (0.3 extent)^2 + 1e-9)
+ *                                                               constant: 0
+ *     d_off[q,3K+k] = (sum_h w g) * m (1 - m/2)      (modulated only; w before modulation)
+ * The kept mask and the closest one-hot are constants, as in torch; shadow and not-kept neighbours contribute nothing; n_q and
+ * min_d2 carry no gradient.  ONE DEPARTURE from torch: at d2 == 0 in linear mode torch's autograd yields NaN (0 * inf through
+ * sqrt); this entry returns the zero subgradient there.  d_off is written without atomics by the workgroup that owns the
+ * query (bit-reproducible run to run); dx is scattered with fp32 atomics, or fixed point under deterministic=1.
+ * cin a multiple of 4 with 16-byte aligned x and d_wf runs on the matrix cores; anything else takes a plain kernel. */
+int pcrcg_kpconv_backward_ex(const float* q_pts, int nq, const float* s_pts, int ns, const int64_t* idx, int h, int ld_idx,
+                             const float* x, int cin, const float* kp, float extent, const float* offset_features, int ld_off,
+                             int influence, int closest, int modulated, const float* d_wf, float* dx, float* d_off,
+                             int ld_doff, void* stream);
 /* Whole-op KPConv for a C caller (KPConv.forward and its autograd, ref:models/blocks.py:229-374):
  *   forward : out [nq,cout] = ((aggregate of x) @ weights [15*cin, cout]) / n_q; `ws` (pcrcg_kpconv_forward_ws_bytes)
  *             keeps the aggregated features and 1/n_q and must be handed unchanged to the backward call;

@@ -193,6 +193,9 @@ SIGNATURES = {
                                   c_void_p, c_void_p, c_int, c_void_p]),
     "pcrcg_kpconv_backward_dx": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int,
                                          c_void_p, c_float, c_void_p, c_void_p]),
+    "pcrcg_kpconv_backward_ex": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int,
+                                         c_void_p, c_float, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                         c_void_p, c_int, c_void_p]),
     "pcrcg_kpconv_forward_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
     "pcrcg_kpconv_forward": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p,
                                      c_float, c_void_p, c_int, c_void_p, c_int, c_void_p, c_size_t, c_void_p]),

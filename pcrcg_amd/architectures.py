@@ -181,8 +181,9 @@ class KPFCNN(nn.Module):
     def forward(self, batch, backbone2d=None):
         training = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
         if training and self.non_rigid is not None:
-            raise NotImplementedError("pcrcg_amd.KPFCNN: a model with %s is inference only; wrap the call in "
-                                      "torch.no_grad()" % self.non_rigid)
+            raise NotImplementedError("pcrcg_amd.KPFCNN: the module forward of a model with %s is inference only; wrap the "
+                                      "call in torch.no_grad(), or train it through Trainer.train_step / "
+                                      "train_forward.forward_train" % self.non_rigid)
         if self.image_feature:
             # the C++ runners (inference and train step) take the 129 channels in rows of 132 floats -- the first KPConv's
             # gather kernel reads whole float4s -- against weights padded with zero rows; the op-by-op paths take [N, 129]

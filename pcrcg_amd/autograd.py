@@ -4,13 +4,20 @@ records the graph; the gradient formulas are the ones of SURVEY.md appendix C:
 
   matmul        y = (a @ b) * row_scale + bias    da = (dy * rs) @ b^T,  db = a^T @ (dy * rs),  dbias = sum_m dy
   kpconv        y = (wf @ W) / n_q                dW = wf^T @ (dy/n),  d wf = (dy/n) @ W^T,  dx = scatter(w^T d wf)
+  kpconv_ex     y = (m (w^T x) @ W) / n_q         dW, d wf as kpconv;  dx = scatter(w m d wf);  with g = d wf . x[idx] and
+                kp_q = off * extent + kp,         d off[3k+a] = extent m sum_h g dw/dkp_a  (linear: diff_a / (d extent) where
+                m = 2 sigmoid(off[3K+k]) or 1     w > 0, 0 at d = 0;  gaussian: 2 w diff_a / (2 (0.3 extent)^2 + 1e-9);
+                                                  constant: 0),  d off[3K+k] = (sum_h w g) m (1 - m/2)
   instnorm      y = lrelu((x - mean) * rstd)      dx = rstd * (g - mean(g) - xhat * mean(g * xhat))
   max_pool      y = max_h x[idx]                  dx[arg max] += dy
   closest_pool  y = x[idx[:, 0]]                  dx[idx[:, 0]] += dy
   softmax_rows  p = softmax(s * scale)            ds = scale * p * (dp - sum p * dp)
   edge_conv     y = lrelu(IN2d(max_j(ctr_i + nbr_idx[i,j])), 0.2)   (DGCNN edge conv of ref:models/gcn.py:37-64,121-129)
 
-Geometry (points, neighbour tables, kernel points) never receives a gradient (rigid KPConv)."""
+Points, neighbour tables and the stored kernel points never receive a gradient.  The deformed kernel points do, through
+`offset_features` of kpconv_ex (every KPConv configuration of ref:models/blocks.py:229-374: deformable, modulated,
+constant / linear / gaussian influence, sum / closest aggregation); the kept mask, the closest one-hot and n_q are
+constants there, as in torch."""
 import torch
 
 from . import _lib, ops
@@ -100,6 +107,92 @@ class _KPConv(torch.autograd.Function):
 def kpconv(x, weights, q_pts, s_pts, idx, kernel_points, extent):
     """KPConv.forward (ref:models/blocks.py:229-374), differentiable in x and weights [15, cin, cout]."""
     return _KPConv.apply(x, weights, q_pts, s_pts, idx, kernel_points, extent)
+
+
+class _KPConvEx(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weights, offset_features, q_pts, s_pts, idx, kp, extent, influence, aggregation, modulated):
+        L = _lib.lib()
+        x = _c(x)
+        q_pts, s_pts, kp = _c(q_pts), _c(s_pts), _c(kp)
+        idx2, ld_idx = ops._rows(idx, torch.int64, "neighb_inds")
+        nq, h = idx2.shape
+        ns, cin0 = x.shape
+        kdim = kp.shape[0]
+        if kdim != 15:
+            raise RuntimeError("pcrcg_amd.autograd.kpconv_ex: only 15 kernel points are supported")
+        cols = (4 if modulated else 3) * kdim
+        off, ld_off = None, 0
+        if offset_features is not None:
+            off, ld_off = ops._rows(offset_features, _F32, "offset_features")
+            if off.shape[0] != nq or off.shape[1] < cols:
+                raise RuntimeError("pcrcg_amd.autograd.kpconv_ex: offset_features must be [nq, 3K] ([nq, 4K] when modulated)")
+        elif modulated:
+            raise RuntimeError("pcrcg_amd.autograd.kpconv_ex: modulated needs offset_features")
+        pad = (-cin0) % 4 if cin0 > 4 else 0     # as ops.kpconv_ex: zero channels change neither the sums nor n_q
+        w3 = weights
+        if pad:
+            x = torch.nn.functional.pad(x, (0, pad))
+            w3 = torch.nn.functional.pad(weights, (0, 0, 0, pad))
+        cin = cin0 + pad
+        wf = torch.empty((nq, kdim * cin), dtype=_F32, device=x.device)
+        inv_n = torch.empty(nq, dtype=_F32, device=x.device)
+        min_d2 = torch.empty((nq, kdim), dtype=_F32, device=x.device)
+        nbytes = L.pcrcg_kpconv_ws_bytes(ns)
+        ws = ops._ws.get("kpconv", nbytes, x.device)
+        mode = (ops._INFLUENCE[influence], int(aggregation == "closest"), int(bool(modulated)))
+        _lib.check(L.pcrcg_kpconv_aggregate_ex(q_pts.data_ptr(), nq, s_pts.data_ptr(), ns, idx2.data_ptr(), h, ld_idx,
+                                               x.data_ptr(), cin, kp.data_ptr(), float(extent), ops._ptr(off), ld_off,
+                                               *mode, wf.data_ptr(), inv_n.data_ptr(), min_d2.data_ptr(), ws.data_ptr(),
+                                               nbytes, ops._stream()), "pcrcg_kpconv_aggregate_ex")
+        w2 = _c(w3).reshape(kdim * cin, -1)
+        ctx.save_for_backward(wf, inv_n, w2, q_pts, s_pts, idx2, kp, x, off)
+        ctx.meta = (float(extent), ns, cin0, cin, ld_idx, ld_off, cols, mode, tuple(weights.shape),
+                    None if offset_features is None else tuple(offset_features.shape))
+        out = ops.gemm(wf, w2, row_scale=inv_n)
+        ctx.mark_non_differentiable(min_d2)
+        return out, min_d2
+
+    @staticmethod
+    def backward(ctx, dy, _d_min):
+        L = _lib.lib()
+        wf, inv_n, w2, q_pts, s_pts, idx2, kp, x, off = ctx.saved_tensors
+        extent, ns, cin0, cin, ld_idx, ld_off, cols, mode, wshape, oshape = ctx.meta
+        dy = _c(dy)
+        kdim = kp.shape[0]
+        dx = dw = d_off = None
+        if ctx.needs_input_grad[1]:
+            dw = ops.gemm(wf.t(), dy * inv_n[:, None], grad_operand=2).reshape(kdim, cin, -1)[:, :cin0].reshape(wshape)
+        want_dx = ctx.needs_input_grad[0]
+        want_off = off is not None and ctx.needs_input_grad[2]
+        if want_dx or want_off:
+            d_wf = ops.gemm(dy, w2.t(), row_scale=inv_n, grad_operand=1)               # [nq, 15*cin]
+            nq, h = idx2.shape
+            if want_dx:
+                dx = torch.zeros((ns, cin), dtype=_F32, device=dy.device)
+            if want_off:
+                d_off = torch.zeros(oshape, dtype=_F32, device=dy.device)              # columns beyond 3K / 4K: unused
+            _lib.check(L.pcrcg_kpconv_backward_ex(q_pts.data_ptr(), nq, s_pts.data_ptr(), ns, idx2.data_ptr(), h, ld_idx,
+                                                  x.data_ptr(), cin, kp.data_ptr(), extent, ops._ptr(off), ld_off, *mode,
+                                                  d_wf.data_ptr(), ops._ptr(dx), ops._ptr(d_off),
+                                                  oshape[1] if want_off else 0, ops._stream()),
+                       "pcrcg_kpconv_backward_ex")
+            if want_dx and cin != cin0:
+                dx = dx[:, :cin0]
+        return dx, dw, d_off, None, None, None, None, None, None, None, None
+
+
+def kpconv_ex(x, weights, q_pts, s_pts, idx, kernel_points, extent, offset_features=None, influence="linear",
+              aggregation="sum", modulated=False):
+    """KPConv.forward in every configuration of ref:models/blocks.py:229-374, differentiable in x, weights [15, cin, cout]
+    and offset_features [nq, 3K (+K when modulated)] (the offset convolution's output with its bias added; None: a rigid
+    kernel).  -> (out [nq, cout], min_d2 [nq, 15]); min_d2 carries no gradient."""
+    if influence not in ops._INFLUENCE:
+        raise ValueError("Unknown influence function type (config.KP_influence)")
+    if aggregation not in ("sum", "closest"):
+        raise ValueError("Unknown convolution mode. Should be 'closest' or 'sum'")
+    return _KPConvEx.apply(x, weights, offset_features, q_pts, s_pts, idx, kernel_points, extent, influence, aggregation,
+                           bool(modulated))
 
 
 class _InstNorm(torch.autograd.Function):

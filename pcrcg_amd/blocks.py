@@ -72,7 +72,7 @@ def global_average(x, batch_lengths):
 class KPConv(nn.Module):
     """ref:models/blocks.py:135-379.  The rigid / linear / sum configuration of the shipped architectures runs in
     ops.kpconv; every other one (deformable, modulated, 'constant' / 'gaussian' influence, 'closest' aggregation) in
-    ops.kpconv_ex, which is inference only."""
+    ops.kpconv_ex.  This forward is inference only; train_forward._kpconv (autograd.kpconv_ex) is its differentiable form."""
 
     def __init__(self, kernel_size, p_dim, in_channels, out_channels, KP_extent, radius,
                  fixed_kernel_points="center", KP_influence="linear", aggregation_mode="sum", deformable=False,
@@ -126,8 +126,9 @@ class KPConv(nn.Module):
             return ops.kpconv(q_pts, s_pts, neighb_inds, x, self.kernel_points.data, self.weights.data,
                               self.KP_extent)
         if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
-            raise NotImplementedError("pcrcg_amd.KPConv: deformable kernels, 'constant' / 'gaussian' influence and "
-                                      "'closest' aggregation are inference only; wrap the call in torch.no_grad()")
+            raise NotImplementedError("pcrcg_amd.KPConv: the module forward of deformable kernels, 'constant' / 'gaussian' "
+                                      "influence and 'closest' aggregation is inference only; wrap the call in "
+                                      "torch.no_grad(), or train through train_forward.forward_train / autograd.kpconv_ex")
         offset_features = None
         if self.deformable:
             # :238 -- the offset convolution with offset_bias added (a rigid kernel of this module's influence mode)

@@ -467,7 +467,8 @@ def kpconv_ex(q_pts, s_pts, idx, x, kernel_points, weights, extent, offset_featu
               aggregation="sum", modulated=False, want_min_d2=False):
     """KPConv.forward in every configuration of ref:models/blocks.py:229-374 (pcrcg_kpconv_aggregate_ex + the contraction
     of `kpconv`).  offset_features [nq, 3K (+K when modulated)]: the offset convolution's output with its bias added, or
-    None for a rigid kernel.  -> out, or (out, min_d2 [nq, K]) with want_min_d2.  Inference only."""
+    None for a rigid kernel.  -> out, or (out, min_d2 [nq, K]) with want_min_d2.  Not recorded by autograd:
+    autograd.kpconv_ex is the differentiable form."""
     L = _lib.lib()
     if influence not in _INFLUENCE:
         raise ValueError("Unknown influence function type (config.KP_influence)")
@@ -508,6 +509,47 @@ def kpconv_ex(q_pts, s_pts, idx, x, kernel_points, weights, extent, offset_featu
                                            _stream()), "pcrcg_kpconv_aggregate_ex")
     out = gemm(wf, w2, row_scale=inv_n)
     return (out, min_d2) if want_min_d2 else out
+
+
+def kpconv_backward_ex(q_pts, s_pts, idx, x, kernel_points, extent, d_wf, offset_features=None, influence="linear",
+                       aggregation="sum", modulated=False, want_dx=True, want_d_off=True):
+    """pcrcg_kpconv_backward_ex (include/pcrcg_train.h): the backward of the gather of `kpconv_ex`.  d_wf [nq, 15 * cin] is
+    the gradient of the wf the forward stored; x [ns, cin] with cin == 1, cin <= 4 or a multiple of 4 (the caller pads, as
+    `kpconv_ex` does).  -> (dx [ns, cin] or None, d_off [nq, 3K or 4K] or None)."""
+    L = _lib.lib()
+    if influence not in _INFLUENCE:
+        raise ValueError("Unknown influence function type (config.KP_influence)")
+    if aggregation not in ("sum", "closest"):
+        raise ValueError("Unknown convolution mode. Should be 'closest' or 'sum'")
+    q_pts = _dev(q_pts, _F32, "q_pts").contiguous()
+    s_pts = _dev(s_pts, _F32, "s_pts").contiguous()
+    idx, ld_idx = _rows(idx, _I64, "neighb_inds")
+    x = _dev(x, _F32, "x").contiguous()
+    kp = _dev(kernel_points, _F32, "kernel_points").contiguous()
+    d_wf = _dev(d_wf, _F32, "d_wf").contiguous()
+    nq, h = idx.shape
+    ns, cin = x.shape
+    kdim = kp.shape[0]
+    if kdim != 15:
+        raise RuntimeError("pcrcg_amd.kpconv_backward_ex: only 15 kernel points are supported")
+    if tuple(d_wf.shape) != (nq, kdim * cin):
+        raise RuntimeError("pcrcg_amd.kpconv_backward_ex: d_wf must be [nq, 15 * cin]")
+    off, ld_off = None, 0
+    cols = (4 if modulated else 3) * kdim
+    if offset_features is not None:
+        off, ld_off = _rows(offset_features, _F32, "offset_features")
+        if off.shape[0] != nq or off.shape[1] < cols:
+            raise RuntimeError("pcrcg_amd.kpconv_backward_ex: offset_features must be [nq, 3K] ([nq, 4K] when modulated)")
+    elif modulated:
+        raise RuntimeError("pcrcg_amd.kpconv_backward_ex: modulated needs offset_features")
+    dx = torch.zeros((ns, cin), dtype=_F32, device=x.device) if want_dx else None
+    d_off = torch.empty((nq, cols), dtype=_F32, device=x.device) if (want_d_off and off is not None) else None
+    _lib.check(L.pcrcg_kpconv_backward_ex(q_pts.data_ptr(), nq, s_pts.data_ptr(), ns, idx.data_ptr(), h, ld_idx,
+                                          x.data_ptr(), cin, kp.data_ptr(), float(extent), _ptr(off), ld_off,
+                                          _INFLUENCE[influence], int(aggregation == "closest"), int(bool(modulated)),
+                                          d_wf.data_ptr(), _ptr(dx), _ptr(d_off), cols, _stream()),
+               "pcrcg_kpconv_backward_ex")
+    return dx, d_off
 
 
 def inject_image_features(n_points, len_src, images, channels=128, width=None):

@@ -35,7 +35,23 @@ def _norm(bn_block, x, slope):
 
 
 def _kpconv(mod, q_pts, s_pts, inds, x):
-    return AG.kpconv(x, mod.weights, q_pts, s_pts, inds, mod.kernel_points.data, mod.KP_extent)
+    """KPConv.forward with gradients (ref:models/blocks.py:229-374).  The rigid / linear / sum configuration of the shipped
+    architectures stays on AG.kpconv; every other one runs its offset convolution first (itself a rigid kernel of the
+    module's influence and aggregation mode, :179-198), adds offset_bias (:238) and goes through AG.kpconv_ex."""
+    if mod.rigid:
+        return AG.kpconv(x, mod.weights, q_pts, s_pts, inds, mod.kernel_points.data, mod.KP_extent)
+    offset_features = None
+    if mod.deformable:
+        offset_features = _kpconv(mod.offset_conv, q_pts, s_pts, inds, x) + mod.offset_bias
+        mod.offset_features = offset_features.detach()
+        offsets = mod.offset_features[:, :mod.p_dim * mod.K].reshape(-1, mod.K, mod.p_dim) * mod.KP_extent
+        mod.deformed_KP = offsets + mod.kernel_points.data                                      # :258,279
+    out, min_d2 = AG.kpconv_ex(x, mod.weights, q_pts, s_pts, inds, mod.kernel_points.data, mod.KP_extent,
+                               offset_features=offset_features, influence=mod.KP_influence,
+                               aggregation=mod.aggregation_mode, modulated=mod.deformable and mod.modulated)
+    if mod.deformable:
+        mod.min_d2 = min_d2.detach()
+    return out
 
 
 def _block(block, x, batch):
