@@ -265,6 +265,17 @@ size_t pcrcg_kpconv_ws_bytes(int ns);
 int pcrcg_kpconv_aggregate(const float* q_pts, int nq, const float* s_pts, int ns, const int64_t* idx,
                            int h, int ld_idx, const float* x, int cin, const float* kp, float extent,
                            float* wf, float* inv_n, void* ws, size_t ws_bytes, void* stream);
+/* The whole first layer of the geometry-only configurations (cin = 1: x [ns] f32, one feature per support point) in ONE
+ * kernel -- what pcrcg_kpfcnn_forward runs for it when its statistics are column sums:
+ *   out[q, c] = inv_n[q] * sum_k wf[q, k] * wt[c, k]    for c < cout,  wf and inv_n as pcrcg_kpconv_aggregate defines them,
+ * wt [cout, 16] f32 the K-contiguous weights (pcrcg_block.kp_wt; column 15 is not used), accumulated in fp64 over k = 0 .. 14 in
+ * order and rounded to fp32 once.
+ * sums [2][cout] f64, ZEROED by the caller, receives the column sums and the column sums of squares of out (fp64 atomics,
+ * one pair per column and 64 queries).  Columns cout .. ld_out - 1 of out are not written.  cout % 4 == 0, cout >= 4 and wt
+ * 16-byte aligned, else PCRCG_EBADARG.  ws: pcrcg_kpconv_ws_bytes(ns). */
+int pcrcg_kpconv_c1_layer(const float* q_pts, int nq, const float* s_pts, int ns, const int64_t* idx, int h, int ld_idx,
+                          const float* x, const float* kp, float extent, const float* wt, int cout, float* out, int ld_out,
+                          float* inv_n, void* sums, void* ws, size_t ws_bytes, void* stream);
 /* Stage 1 of the bf16 feature-storage VARIANT (pcrcg_model.feature_bf16): x is fp32 at the boundary; x_bf16
  * ([ns, cin] u16 scratch) receives its round-to-nearest-even bf16 copy, which is what the neighbour gathers read, and
  * wf_bf16 ([nq, 15*cin] u16) the aggregate rounded the same way.  Geometry, influences, n_q and the accumulation are
@@ -424,6 +435,11 @@ int pcrcg_gather_max(const float* x, int ns, int c, const int64_t* idx, int nq, 
  * destination with leading dimension ld_out (so it can fill the left part of a concat buffer). */
 int pcrcg_gather_first(const float* x, int ns, int c, const int64_t* idx, int nq, int ld_idx, float* out,
                        int ld_out, void* stream);
+/* The same for `count` (1 .. 4) clouds of one width in ONE launch: x, ns, idx, nq, ld_idx and out are host arrays of
+ * `count` entries; the rows of every x[g] have leading dimension ld_x >= c (the single-cloud entry reads dense rows).
+ * Columns c .. ld_out - 1 of out are not written; a cloud with nq[g] = 0 is skipped. */
+int pcrcg_gather_first_multi(const float* const* x, const int* ns, const int64_t* const* idx, const int* nq, const int* ld_idx,
+                             float* const* out, int count, int c, int ld_x, int ld_out, void* stream);
 /* InstanceNorm over all rows + LeakyReLU (BatchNormBlock/UnaryBlock/ResnetBottleneckBlock,
  * ref:models/blocks.py:433-470, 493-500, 650-678):
  *   stats[2*c] receives per-channel (mean, 1/sqrt(var+eps)) of x [n,c] (biased variance);

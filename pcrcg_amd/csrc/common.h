@@ -79,6 +79,13 @@ int kpconv_aggregate_rows(const float* q_pts, int nq, const float* s_pts, int ns
                           const float* x, int cin, const float* kp, float extent, float* wf, float* inv_n, void* ws,
                           size_t ws_bytes, hipStream_t st, bool pack, bool stream_out, int c1_ld = 0,   // c1_ld = 16: cin = 1 with wf rows of 16 floats (15 + a zero)
                           const int* walk = nullptr);      // walk: the queries' processing order (walk.hip), NULL: index order
+// the first layer (cin = 1, features x [ns]) in ONE kernel: y [nq, cout] = (wf @ wt^T) / n_q against the K-contiguous weights
+// wt [cout, 16], inv_n as kpconv_aggregate_rows leaves it, and the column sums / sums of squares of y ADDED to the zeroed
+// sums [2][cout] f64.  _ok: the widths and outputs it serves (everything else keeps gather + product).
+bool kpconv_c1_fused_ok(int cout, const float* wt);
+int kpconv_c1_fused(const float* q_pts, int nq, const float* s_pts, int ns, const int64_t* idx, int h, int ld_idx, const float* x,
+                    const float* kp, float extent, const float* wt, int cout, float* y, int ld_y, float* inv_n, double* sums,
+                    void* ws, size_t ws_bytes, hipStream_t st, bool pack);
 int kpconv_aggregate_bf16(const float* q_pts, int nq, const float* s_pts, int ns, const int64_t* idx, int h, int ld_idx,
                           const float* x, unsigned short* x_bf16, int cin, const float* kp, float extent,
                           unsigned short* wf_bf16, float* inv_n, void* ws, size_t ws_bytes, hipStream_t st,
@@ -103,6 +110,10 @@ bool instnorm_sums_ok(int c, int ldx, int ldy, int ldr = 0);
 
 struct GatherJob { const float* x; const int64_t* idx; float* out; int ns, nq, h, ld_idx; const int* walk = nullptr; };   // walk: see query_walk_multi
 int gather_max_multi(const GatherJob* jobs, int count, int c, hipStream_t st);
+// closest_pool for up to four clouds of one width in ONE launch: out_g[q, :c] = x_g[idx_g[q * ld_idx], :c], a zero row for a
+// first index outside [0, ns_g); x rows have leading dimension ld_x, out rows ld_out (columns c .. ld_out - 1 are not written)
+struct FirstJob { const float* x; const int64_t* idx; float* out; int ns, nq, ld_idx; };
+int gather_first_multi(const FirstJob* jobs, int count, int c, int ld_x, int ld_out, hipStream_t st);
 int heads_multi(const float* const* x, const int* rows, int count, int ld, int fd, float* const* feats, float* const* s_ov,
                 float* const* s_sal, hipStream_t st);
 int copy2d_multi(const float* const* src, float* const* dst, const int* rows, int count, int ld_src, int ld_dst, int cols,

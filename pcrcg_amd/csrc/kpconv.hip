@@ -282,23 +282,19 @@ __global__ void __launch_bounds__(kWavesPerBlock * 64) k_kpconv_mfma(
 // loads, then all gathers, in flight together; the 15 partial sums are combined with two butterfly
 // shuffles.  Kernel points live in SGPRs, loads are branch-free (clamped addresses + select).
 constexpr int C1_PARTS = 4, C1_BATCH = 6;
-__global__ void __launch_bounds__(256) k_kpconv_c1(
-    const float* __restrict__ q_pts, int nq, const float* __restrict__ s_pts, int ns,
-    const long long* __restrict__ idx, int H, int ld_idx, const float4* __restrict__ pk, const float* __restrict__ kp,
-    float extent, float* __restrict__ wf, float* __restrict__ inv_n, int ld_wf) {
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    const int part = t & (C1_PARTS - 1);
-    const int qraw = t / C1_PARTS;
-    const int q = qraw < nq ? qraw : nq - 1;          // surplus lanes shadow the last query (shuffles stay uniform)
+// The gather of one query by its four lanes (part = the lane's share of the neighbours): on return every lane holds the query's
+// 15 influence sums and its count of neighbours with a positive feature.
+__device__ __forceinline__ void c1_gather(const float* __restrict__ q_pts, int q, int part, int ns, const long long* __restrict__ idx,
+                                          int H, int ld_idx, const float4* __restrict__ pk, const float* __restrict__ kp, float extent,
+                                          float (&acc)[K], int& npos) {
     float kpx[K], kpy[K], kpz[K];
 #pragma unroll
     for (int k = 0; k < K; ++k) { kpx[k] = kp[3 * k]; kpy[k] = kp[3 * k + 1]; kpz[k] = kp[3 * k + 2]; }
     const float inv_extent = 1.0f / extent;
     const float qx = q_pts[3 * (long)q], qy = q_pts[3 * (long)q + 1], qz = q_pts[3 * (long)q + 2];
-    float acc[K];
 #pragma unroll
     for (int k = 0; k < K; ++k) acc[k] = 0.f;
-    int npos = 0;
+    npos = 0;
     const long long* row = idx + (long)q * ld_idx;
     for (int h0 = 0; h0 < H; h0 += C1_PARTS * C1_BATCH) {
         long long iv[C1_BATCH];
@@ -337,12 +333,104 @@ __global__ void __launch_bounds__(256) k_kpconv_c1(
         for (int k = 0; k < K; ++k) acc[k] += __shfl_xor(acc[k], d, 64);
         npos += __shfl_xor(npos, d, 64);
     }
+}
+
+__global__ void __launch_bounds__(256) k_kpconv_c1(
+    const float* __restrict__ q_pts, int nq, const float* __restrict__ s_pts, int ns,
+    const long long* __restrict__ idx, int H, int ld_idx, const float4* __restrict__ pk, const float* __restrict__ kp,
+    float extent, float* __restrict__ wf, float* __restrict__ inv_n, int ld_wf) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    const int part = t & (C1_PARTS - 1);
+    const int qraw = t / C1_PARTS;
+    const int q = qraw < nq ? qraw : nq - 1;          // surplus lanes shadow the last query (shuffles stay uniform)
+    float acc[K];
+    int npos;
+    c1_gather(q_pts, q, part, ns, idx, H, ld_idx, pk, kp, extent, acc, npos);
     if (qraw >= nq) return;
 #pragma unroll
     for (int k = 0; k < K; ++k)
         if ((k & (C1_PARTS - 1)) == part) wf[(long)q * ld_wf + k] = acc[k];
     if (ld_wf > K && part == C1_PARTS - 1) wf[(long)q * ld_wf + K] = 0.f;      // rows of 16 floats: the contraction's k-steps are whole
     if (part == 0) inv_n[q] = 1.0f / (float)(npos > 1 ? npos : 1);
+}
+
+// Cin == 1, the whole layer in one kernel: the gather of k_kpconv_c1 (the same loads, the same sums, the same n_q), then
+//   y[q, c] = inv_n[q] * sum_k wf[q, k] * wt[c][k]        (fp64 FMAs, k = 0 .. 14 in order, ONE rounding to fp32)
+// for the workgroup's 64 queries, and the column sums of the stored y for the InstanceNorm that follows -- no [nq, 16] wf
+// matrix in memory and no K = 16 product through a kernel built for K in the hundreds.
+// The contraction accumulates in fp64: y is then the correctly rounded product of the fp32 sums, as good as the split-term
+// product it replaces (whose error on these shapes is the gather's own), where a chain of fifteen fp32 FMAs measured up to
+// 2.6 times that product's error against float64 (tests/test_c1_fused_gpu.py allows 2).
+// After the gather the roles turn: the 64 x 15 sums (and 1 / n_q) of the workgroup wait in LDS as doubles, a lane owns a
+// COLUMN -- its 15 weights in registers, four 16-byte loads of its row of wt -- and wavefront w the queries 16 w .. 16 w + 15:
+// a query costs a lane eight LDS reads that all lanes share and 15 FMAs, a wavefront's store is 256 contiguous bytes of one
+// output row, and the lane sums its column as it goes: fp32 sums of the deviations from its first value, finished in fp64
+// (the pivot form of the GEMM epilogue, gemm_x6.hip, whose lanes sum 16 rows as well).  The four wavefronts meet in LDS: ONE
+// pair of fp64 atomics per column and 64-query tile -- the count that epilogue issues.  Widths above 64 take the columns in
+// blocks of 64.  (First version: weights in LDS, lanes = queries, the output through an LDS tile: 42-49 KB of LDS kept a
+// fifth of a 60 000-query launch's workgroups waiting for a CU, and the weight reads, one per FMA, ran at the LDS rate.)
+constexpr int C1F_ROWS = 256 / C1_PARTS;          // queries per workgroup
+__global__ void __launch_bounds__(256) k_kpconv_c1_fused(
+    const float* __restrict__ q_pts, int nq, int ns, const long long* __restrict__ idx, int H, int ld_idx,
+    const float4* __restrict__ pk, const float* __restrict__ kp, float extent, const float* __restrict__ wt, int cout,
+    float* __restrict__ y, int ld_y, float* __restrict__ inv_n, double* __restrict__ sums) {
+    __shared__ __attribute__((aligned(16))) double s_wf[C1F_ROWS][16];      // [query][k], [query][15] = 1 / n_q
+    __shared__ double s_red[4][64][2];
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    const int part = t & (C1_PARTS - 1);
+    const int qraw = t / C1_PARTS;
+    const int q = qraw < nq ? qraw : nq - 1;          // surplus lanes shadow the last query (shuffles stay uniform)
+    float acc[K];
+    int npos;
+    c1_gather(q_pts, q, part, ns, idx, H, ld_idx, pk, kp, extent, acc, npos);
+    const float rn = 1.0f / (float)(npos > 1 ? npos : 1);
+    if (qraw < nq && part == 0) inv_n[q] = rn;
+    const int ql = threadIdx.x / C1_PARTS;
+#pragma unroll
+    for (int k = 0; k < K; ++k)
+        if ((k & (C1_PARTS - 1)) == part) s_wf[ql][k] = (double)acc[k];
+    if (part == C1_PARTS - 1) s_wf[ql][K] = (double)rn;
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int q0 = blockIdx.x * C1F_ROWS;
+    const int rows = nq - q0 < C1F_ROWS ? nq - q0 : C1F_ROWS;          // >= 1: the grid has no empty workgroup
+    const int r0 = 16 * w, r1 = r0 + 16 < rows ? r0 + 16 : rows;
+    for (int c0 = 0; c0 < cout; c0 += 64) {
+        const int c = c0 + lane;
+        double s = 0.0, s2 = 0.0;
+        if (c < cout && r0 < rows) {
+            double wd[16];
+#pragma unroll
+            for (int k4 = 0; k4 < 4; ++k4) {
+                const float4 v = *reinterpret_cast<const float4*>(wt + (long)c * 16 + 4 * k4);
+                wd[4 * k4] = (double)v.x; wd[4 * k4 + 1] = (double)v.y; wd[4 * k4 + 2] = (double)v.z; wd[4 * k4 + 3] = (double)v.w;
+            }
+            float piv = 0.f, cs = 0.f, cq = 0.f;
+            for (int r = r0; r < r1; ++r) {
+                double o = 0.0;
+#pragma unroll
+                for (int k = 0; k < K; ++k) o = fma(s_wf[r][k], wd[k], o);
+                const float v = (float)(o * s_wf[r][K]);
+                y[(long)(q0 + r) * ld_y + c] = v;
+                if (r == r0) piv = v;
+                const float d = v - piv;
+                cs += d;
+                cq += d * d;
+            }
+            const double p = (double)piv, s1 = (double)cs, n = (double)(r1 - r0);
+            s = s1 + n * p;
+            s2 = (double)cq + p * (2.0 * s1 + n * p);
+        }
+        s_red[w][lane][0] = s;
+        s_red[w][lane][1] = s2;
+        __syncthreads();
+        if (w == 0 && c < cout) {
+            unsafeAtomicAdd(&sums[c], (s_red[0][lane][0] + s_red[1][lane][0]) + (s_red[2][lane][0] + s_red[3][lane][0]));
+            unsafeAtomicAdd(&sums[cout + c], (s_red[0][lane][1] + s_red[1][lane][1]) + (s_red[2][lane][1] + s_red[3][lane][1]));
+        }
+        __syncthreads();                                   // s_red is free for the next 64 columns
+    }
 }
 
 // Scalar fallback for channel counts that are not a multiple of 4: weights staged in LDS, lanes =
@@ -560,6 +648,33 @@ int kpconv_aggregate_rows(const float* q_pts, int nq, const float* s_pts, int ns
     return PCRCG_OK;
 }
 
+// The first layer (cin = 1) in one kernel, k_kpconv_c1_fused: widths of whole float4s, and weight rows a lane can read as four
+bool kpconv_c1_fused_ok(int cout, const float* wt) { return cout >= 4 && cout % 4 == 0 && wt && (reinterpret_cast<uintptr_t>(wt) & 15) == 0; }
+
+// y [nq, cout] = KPConv of the one-column features x [ns] against wt [cout, 16] (K-contiguous, the 16th column unused), inv_n
+// [nq] as pcrcg_kpconv_aggregate leaves it, and sums [2][cout] f64 (zeroed by the caller) += the column sums and sums of
+// squares of y.  `pack`: build the support records in ws first.
+int kpconv_c1_fused(const float* q_pts, int nq, const float* s_pts, int ns, const int64_t* idx, int h, int ld_idx, const float* x,
+                    const float* kp, float extent, const float* wt, int cout, float* y, int ld_y, float* inv_n, double* sums,
+                    void* ws, size_t ws_bytes, hipStream_t st, bool pack) {
+    PCRCG_CHECK_ARG(nq >= 0 && ns >= 0 && h >= 1 && ld_idx >= h && extent > 0.0f);
+    PCRCG_CHECK_ARG(kpconv_c1_fused_ok(cout, wt) && ld_y >= cout);
+    if (nq == 0) return PCRCG_OK;
+    PCRCG_CHECK_ARG(q_pts && s_pts && idx && x && kp && wt && y && inv_n && sums && ws);
+    PCRCG_CHECK_ARG(ns >= 1);
+    Carver cv(ws, ws_bytes);
+    cv.take<unsigned char>((size_t)ns + 1);
+    float4* pk = cv.take<float4>((size_t)ns + 1);
+    PCRCG_CHECK_WS(cv);
+    if (pack) hipLaunchKernelGGL(k_pack_c1, dim3((ns + 255) / 256), dim3(256), 0, st, x, ns, s_pts, pk);
+    KpProfScope prof_scope(st, nq, h, 1, cout, 1);      // kind 1: the one-kernel KPConv
+    hipExtLaunchKernelGGL(k_kpconv_c1_fused, dim3((int)(((long)nq * C1_PARTS + 255) / 256)), dim3(256), 0, st,
+                          prof_scope.a, prof_scope.b, 0, q_pts, nq, ns, reinterpret_cast<const long long*>(idx), h, ld_idx,
+                          (const float4*)pk, kp, extent, wt, cout, y, ld_y, inv_n, sums);
+    PCRCG_CHECK_LAUNCH();
+    return PCRCG_OK;
+}
+
 // The bf16 feature-storage variant: x_bf16 [ns, cin] and wf_bf16 [nq, 15*cin] are bf16; `x` (fp32) is only read by the
 // support-record prelude (the n_q normaliser counts rows with a positive fp32 sum, exactly as the fp32 path does).
 int kpconv_aggregate_bf16(const float* q_pts, int nq, const float* s_pts, int ns, const int64_t* idx, int h, int ld_idx,
@@ -598,3 +713,10 @@ int kpconv_aggregate_bf16(const float* q_pts, int nq, const float* s_pts, int ns
 }
 
 }  // namespace pcrcg
+
+extern "C" int pcrcg_kpconv_c1_layer(const float* q_pts, int nq, const float* s_pts, int ns, const int64_t* idx, int h, int ld_idx,
+                                     const float* x, const float* kp, float extent, const float* wt, int cout, float* out,
+                                     int ld_out, float* inv_n, void* sums, void* ws, size_t ws_bytes, void* stream) {
+    return pcrcg::kpconv_c1_fused(q_pts, nq, s_pts, ns, idx, h, ld_idx, x, kp, extent, wt, cout, out, ld_out, inv_n,
+                                  static_cast<double*>(sums), ws, ws_bytes, pcrcg::as_stream(stream), true);
+}

@@ -86,6 +86,31 @@ __global__ void __launch_bounds__(256) k_gather_first(const float* __restrict__ 
     for (int cc = lane; cc < c; cc += 64) out[(long)q * ld_out + cc] = real ? x[i * c + cc] : 0.f;
 }
 
+// The same rule for up to four clouds of one width in ONE launch (blockIdx.y = cloud): out_g[q, :c] = x_g[idx_g[q, 0], :c], a
+// zero row for a first index outside [0, ns_g).  One thread per (row, group of four columns): whole groups move as one
+// 16-byte access when VEC (every base and leading dimension 16-byte aligned), the columns of a last partial group one by
+// one -- columns c .. ld_out - 1 of out are never written.
+struct FirstMulti { const float* x[4]; const long long* idx[4]; float* out[4]; int ns[4], nq[4], ld_idx[4]; };
+template <bool VEC>
+__global__ void __launch_bounds__(256) k_gather_first_multi(FirstMulti mm, int c, int ld_x, int ld_out) {
+    const int g = blockIdx.y;
+    const int segs = (c + 3) >> 2;
+    const long t = (long)blockIdx.x * 256 + threadIdx.x;
+    const long q = t / segs;
+    if (q >= mm.nq[g]) return;
+    const int c0 = (int)(t - q * segs) * 4;
+    const long long i = mm.idx[g][q * mm.ld_idx[g]];
+    const bool real = i >= 0 && i < mm.ns[g];
+    const float* __restrict__ src = mm.x[g] + (real ? i : 0) * ld_x + c0;
+    float* __restrict__ dst = mm.out[g] + q * ld_out + c0;
+    if (VEC && c0 + 4 <= c) {
+        *reinterpret_cast<float4*>(dst) = real ? *reinterpret_cast<const float4*>(src) : make_float4(0.f, 0.f, 0.f, 0.f);
+    } else {
+        const int n = c - c0 < 4 ? c - c0 : 4;
+        for (int k = 0; k < n; ++k) dst[k] = real ? src[k] : 0.f;
+    }
+}
+
 // ---- InstanceNorm statistics: deterministic two-stage column reduction in fp64 -----------------
 constexpr int kStatChunks = 128;   // row chunks (= partial sums per channel)
 
@@ -450,6 +475,31 @@ int gather_max_multi(const GatherJob* jobs, int count, int c, hipStream_t st) {
     return PCRCG_OK;
 }
 
+// out_g[q, :c] = x_g[idx_g[q, 0], :c] (zero for a first index outside [0, ns_g)) for up to four clouds of one width in ONE launch
+int gather_first_multi(const FirstJob* jobs, int count, int c, int ld_x, int ld_out, hipStream_t st) {
+    PCRCG_CHECK_ARG(jobs && count >= 1 && count <= 4 && c >= 1 && ld_x >= c && ld_out >= c);
+    FirstMulti mm;
+    bool vec = ld_x % 4 == 0 && ld_out % 4 == 0;
+    int nq_max = 0;
+    for (int g = 0; g < 4; ++g) {
+        const FirstJob& j = jobs[g < count ? g : 0];
+        mm.x[g] = j.x; mm.idx[g] = reinterpret_cast<const long long*>(j.idx); mm.out[g] = j.out;
+        mm.ns[g] = j.ns; mm.nq[g] = g < count ? j.nq : 0; mm.ld_idx[g] = j.ld_idx;
+        if (g < count) {
+            PCRCG_CHECK_ARG(j.ns >= 0 && j.nq >= 0 && j.ld_idx >= 1 && (j.nq == 0 || (j.idx && j.out && (j.x || j.ns == 0))));
+            if (j.nq > 0) vec = vec && ((reinterpret_cast<uintptr_t>(j.x) | reinterpret_cast<uintptr_t>(j.out)) & 15) == 0;
+            nq_max = j.nq > nq_max ? j.nq : nq_max;
+        }
+    }
+    if (nq_max == 0) return PCRCG_OK;
+    const long threads = (long)nq_max * ((c + 3) / 4);
+    const dim3 grid((unsigned)((threads + 255) / 256), count);
+    if (vec) hipLaunchKernelGGL(k_gather_first_multi<true>, grid, dim3(256), 0, st, mm, c, ld_x, ld_out);
+    else hipLaunchKernelGGL(k_gather_first_multi<false>, grid, dim3(256), 0, st, mm, c, ld_x, ld_out);
+    PCRCG_CHECK_LAUNCH();
+    return PCRCG_OK;
+}
+
 // column sums (sum, sum of squares) of up to four [n_g, c] tensors added into their zeroed [2][c] fp64 accumulators, one launch
 int instnorm_colsums_multi(const float* const* x, double* const* sums, const int* n, int count, int c, int ldx, hipStream_t st) {
     PCRCG_CHECK_ARG(count >= 1 && count <= 4 && c >= 1 && ldx >= c);
@@ -496,6 +546,14 @@ int pcrcg_gather_first(const float* x, int ns, int c, const int64_t* idx, int nq
                        reinterpret_cast<const long long*>(idx), nq, ld_idx, out, ld_out);
     PCRCG_CHECK_LAUNCH();
     return PCRCG_OK;
+}
+
+int pcrcg_gather_first_multi(const float* const* x, const int* ns, const int64_t* const* idx, const int* nq, const int* ld_idx,
+                             float* const* out, int count, int c, int ld_x, int ld_out, void* stream) {
+    PCRCG_CHECK_ARG(x && ns && idx && nq && ld_idx && out && count >= 1 && count <= 4);
+    FirstJob jobs[4];
+    for (int g = 0; g < count; ++g) jobs[g] = FirstJob{x[g], idx[g], out[g], ns[g], nq[g], ld_idx[g]};
+    return gather_first_multi(jobs, count, c, ld_x, ld_out, as_stream(stream));
 }
 
 size_t pcrcg_instnorm_ws_bytes(int c) { return colstats_ws_bytes(c); }

@@ -22,7 +22,7 @@ constexpr int GMAX = 4;   // fragment pairs one call can carry (pcrcg_kpfcnn_for
 // c.G <= GMAX everywhere below (validate_group; the two stacking sites double it only while 2 * c.G <= GMAX), and every
 // multi-cloud kernel of common.h takes that many: all clouds of a call always fit ONE launch of them, no per-cloud loop for the
 // count's sake.  The per-cloud paths that remain are for what those kernels refuse (alignment, widths, arithmetic mode).
-static_assert(GMAX <= 4, "instnorm_apply_sums_multi, instnorm_colsums_multi, gather_max_multi, copy2d_multi, heads_multi, "
+static_assert(GMAX <= 4, "instnorm_apply_sums_multi, instnorm_colsums_multi, gather_max_multi, gather_first_multi, copy2d_multi, heads_multi, "
                          "edgeconv_rows_multi and attention_mfma_multi (common.h) take up to four clouds");
 
 // Row-major fp32 matrix view -- one per fragment pair of the call (same width and leading dimension, own rows).  With
@@ -83,15 +83,15 @@ struct Ctx {
     }
     int max_rows(const int* rows) const { int m = rows[0]; for (int g = 1; g < G; ++g) m = rows[g] > m ? rows[g] : m; return m; }
     // the output of a [rows, k] x [cols, k]^T product (the plan of the pair with most rows decides for all)
-    Mat gemm_out(const int* rows, int cols, int k) {
+    Mat gemm_out(const int* rows, int cols, int k, int ld = 0) {
         long total = 0;
         for (int g = 0; g < G; ++g) total += rows[g];
-        if (!gemm_bt_accumulates(max_rows(rows), cols, k, total)) return mat(rows, cols);
+        if (!gemm_bt_accumulates(max_rows(rows), cols, k, total)) return mat(rows, cols, ld);
         Mat m;
-        m.cols = cols; m.ld = cols;
+        m.cols = cols; m.ld = ld ? ld : cols;
         for (int g = 0; g < G; ++g) {
             m.rows[g] = rows[g];
-            m.p[g] = static_cast<float*>(zraw((size_t)(rows[g] > 0 ? rows[g] : 1) * cols * sizeof(float)));
+            m.p[g] = static_cast<float*>(zraw((size_t)(rows[g] > 0 ? rows[g] : 1) * m.ld * sizeof(float)));
         }
         m.zeroed = true;
         return m;
@@ -269,11 +269,8 @@ void stats_into(GemmCall& call, Stat* st, int g) {
     call.h_chunks = &st->chunks[g];
     call.colstats_sums = st->sums;
 }
-// What a product may fold into its A loads, for all pairs.  tabs: per-pair gather table (first column; the source has
-// x.rows[g] rows, indices outside read zero_row); sums: per-pair column sums of the raw A (normalise-on-load), or NULL
+// What a product may fold into its A loads, for all pairs.  sums: per-pair column sums of the raw A (normalise-on-load), or NULL
 struct Fold {
-    const pcrcg_table* const* tabs = nullptr;
-    const float* zero_row = nullptr;
     Stat* sums = nullptr;
     float slope = 1.0f;
     bool accumulate = false;
@@ -284,12 +281,6 @@ GemmExtra extra_of(const Fold& f, const Mat& x, int g) {
         ex.a_sums = static_cast<const double*>(f.sums->partials[g]);
         ex.a_count = (double)x.rows[g];
         ex.a_slope = f.slope;
-    }
-    if (f.tabs) {
-        ex.a_idx = reinterpret_cast<const long long*>(f.tabs[g]->idx);
-        ex.a_idx_ld = f.tabs[g]->ld;
-        ex.a_ns = x.rows[g];
-        ex.a_zero = f.zero_row;
     }
     ex.accumulate = f.accumulate;
     return ex;
@@ -302,12 +293,11 @@ GemmGroup group_of(const Ctx& c, const Mat& x, const Mat& y, bool c_zeroed, Stat
         GemmPair& p = grp.p[g - 1];
         p.a = x.p[g];
         p.c = y.p[g];
-        p.m = (f && f->tabs) ? f->tabs[g]->rows : x.rows[g];
+        p.m = x.rows[g];
         p.row_scale = row_scale ? row_scale[g] : nullptr;
         p.colstats = st ? st->partials[g] : nullptr;
         p.h_chunks = st ? &st->chunks[g] : nullptr;
         p.c_zeroed = c_zeroed;
-        if (f && f->tabs) { p.a_idx = reinterpret_cast<const long long*>(f->tabs[g]->idx); p.a_ns = x.rows[g]; }
         if (f && f->sums) { p.a_sums = static_cast<const double*>(f->sums->partials[g]); p.a_count = (double)x.rows[g]; }
     }
     return grp;
@@ -320,15 +310,13 @@ GemmGroup group_of(const Ctx& c, const Mat& x, const Mat& y, bool c_zeroed, Stat
 void linear(Ctx& c, const Mat& x, const float* w, int ldw, const float* bias, const Mat& y, bool c_zeroed, Stat* st = nullptr,
             const float* const* row_scale = nullptr, const Fold* f = nullptr) {
     if (!c.live()) return;
-    bool same_ld = true;
-    for (int g = 1; g < c.G && f && f->tabs; ++g) same_ld = same_ld && f->tabs[g]->ld == f->tabs[0]->ld;
-    const bool grouped = c.paired() && same_ld;
+    const bool grouped = c.paired();
     for (int g = 0; g < (grouped ? 1 : c.G); ++g) {
         GemmCall call;
         call.a = x.p[g]; call.lda = x.ld;
         call.b = w; call.ldb = ldw;
         call.c = y.p[g]; call.ldc = y.ld;
-        call.m = (f && f->tabs) ? f->tabs[g]->rows : x.rows[g]; call.n = y.cols; call.k = x.cols;
+        call.m = x.rows[g]; call.n = y.cols; call.k = x.cols;
         call.row_scale = row_scale ? row_scale[g] : nullptr;
         call.bias = bias;
         call.st = c.st;
@@ -477,6 +465,20 @@ void kpconv(Ctx& c, const Batches& B, Walks& W, const pcrcg_block& blk, const Ma
                 c.check(gemm_run(call));
             }
         }
+        c.release(m);
+        return;
+    }
+    // cin = 1 with column-sum statistics: gather, contraction, row scale and the sums in one kernel per cloud -- no wf matrix
+    // and no K = 16 product.  (stat_sums=0, deterministic=1, PCRCG_GEMM_MODE=0, a descriptor without kp_wt and widths
+    // the kernel does not serve keep the two launches below.)
+    if (cin == 1 && st && st->sums && kpconv_c1_fused_ok(y.cols, kp_wt)) {
+        if (c.live())
+            for (int g = 0; g < c.G; ++g) {
+                c.check(kpconv_c1_fused(q[g], nq[g], B.b[g]->points[l], ns[g], tab[g]->idx, tab[g]->cols, tab[g]->ld, xin.p[g],
+                                        blk.kp, blk.extent, kp_wt, y.cols, y.p[g], y.ld, inv_n[g],
+                                        static_cast<double*>(st->partials[g]), ws[g], wsb[g], c.st, /*pack=*/true));
+                st->chunks[g] = Stat::SUMS;
+            }
         c.release(m);
         return;
     }
@@ -942,17 +944,24 @@ void forward(Ctx& c, const pcrcg_model& mdl, const Batches& B, const pcrcg_outpu
                 skips.back().ld % 4 == 0) {
                 const Mat& sk = skips.back();
                 const bool last = next->type == PCRCG_BLK_LAST_UNARY;
-                Mat tt = c.mat(trows, next->out_dim, pad4(next->out_dim));    // rows 16-byte aligned: it may be gathered next
-                float* zero_row = static_cast<float*>(c.zraw(sizeof(float) * (size_t)(x.cols + 8)));
+                Mat tt = c.mat(trows, next->out_dim, pad4(next->out_dim));    // rows 16-byte aligned: it may be read normalised next
                 if (lazy && !(gemm_split_terms_on() && lazy_stats_ready(c, x, &xs))) materialise();
-                // the producer's normalisation (when lazy) applied to the gathered rows; then the skip part on top
+                // nearest_upsample commutes with the linear map: the unary's first columns are applied to the COARSE rows
+                // (with the producer's normalisation on load when lazy) and the product's rows copied up through the table,
+                // the shadow index giving a zero row (no bias: what a zero input row maps to) -- a fine row repeated its
+                // coarse row's product before, 4-5 times the flops and a random row gather per fine row.  Then the skip
+                // part on top.
+                Mat z = c.gemm_out(x.rows, next->out_dim, x.cols, pad4(next->out_dim));
                 Fold up, add;
-                up.tabs = tabs;
-                up.zero_row = zero_row;
                 up.sums = lazy ? &xs : nullptr;
                 up.slope = 0.1f;
                 add.accumulate = true;
-                linear(c, x, next->mlp, next->mlp_ld, nullptr, tt, /*c_zeroed=*/false, nullptr, nullptr, &up);
+                linear(c, x, next->mlp, next->mlp_ld, nullptr, z, z.zeroed, nullptr, nullptr, &up);
+                if (c.live()) {          // every pair's rows in one launch
+                    FirstJob jobs[GMAX];
+                    for (int g = 0; g < c.G; ++g) jobs[g] = FirstJob{z.p[g], tabs[g]->idx, tt.p[g], z.rows[g], trows[g], tabs[g]->ld};
+                    c.check(gather_first_multi(jobs, c.G, z.cols, z.ld, tt.ld, c.st));
+                }
                 linear(c, sk, next->mlp_skip, next->mlp_skip_ld, nullptr, tt, /*c_zeroed=*/true, nullptr, nullptr, &add);
                 skips.pop_back();
                 lazy = false;

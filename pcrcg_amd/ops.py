@@ -460,6 +460,35 @@ def kpconv(q_pts, s_pts, idx, x, kernel_points, weights, extent):
     return gemm(wf, w2, row_scale=inv_n)
 
 
+def kpconv_c1_layer(q_pts, s_pts, idx, x, kernel_points, wt, extent, out=None):
+    """The first layer (one feature per point, x [ns] or [ns, 1]) in one kernel (pcrcg_kpconv_c1_layer): wt [cout, 16] is the
+    K-contiguous weight copy of the runner's descriptor.  `out`: a [nq, cout] column slice of a row-major buffer whose rows are
+    16-byte aligned, or None.  -> (out, inv_n [nq], sums [2, cout] float64: column sums and sums of squares of out)."""
+    L = _lib.lib()
+    q_pts = _dev(q_pts, _F32, "q_pts").contiguous()
+    s_pts = _dev(s_pts, _F32, "s_pts").contiguous()
+    idx, ld_idx = _rows(idx, _I64, "neighb_inds")
+    x = _dev(x, _F32, "x").contiguous()
+    kp = _dev(kernel_points, _F32, "kernel_points").contiguous()
+    wt = _dev(wt, _F32, "wt").contiguous()
+    nq, h = idx.shape
+    ns, cout = x.shape[0], wt.shape[0]
+    if kp.shape[0] != 15 or wt.shape[1] != 16 or x.numel() != ns:
+        raise RuntimeError("pcrcg_amd.kpconv_c1_layer: 15 kernel points, wt [cout, 16] and one feature per point")
+    if out is None:
+        out = torch.empty((nq, cout), dtype=_F32, device=x.device)
+    ld_out = out.stride(0) if nq > 1 else max(cout, out.stride(0))
+    inv_n = torch.empty(nq, dtype=_F32, device=x.device)
+    sums = torch.zeros((2, cout), dtype=torch.float64, device=x.device)
+    nbytes = L.pcrcg_kpconv_ws_bytes(ns)
+    ws = _ws.get("kpconv", nbytes, x.device)
+    _lib.check(L.pcrcg_kpconv_c1_layer(q_pts.data_ptr(), nq, s_pts.data_ptr(), ns, idx.data_ptr(), h, ld_idx, x.data_ptr(),
+                                       kp.data_ptr(), float(extent), wt.data_ptr(), cout, out.data_ptr(), ld_out,
+                                       inv_n.data_ptr(), sums.data_ptr(), ws.data_ptr(), nbytes, _stream()),
+               "pcrcg_kpconv_c1_layer")
+    return out, inv_n, sums
+
+
 _INFLUENCE = {"constant": 0, "linear": 1, "gaussian": 2}
 
 
@@ -735,6 +764,34 @@ def gather_first(x, idx, out=None):
     _lib.check(L.pcrcg_gather_first(x.data_ptr(), ns, c, idx.data_ptr(), nq, ld_idx, out.data_ptr(), ld_out,
                                     _stream()), "pcrcg_gather_first")
     return out
+
+
+def gather_first_multi(xs, idxs, outs):
+    """closest_pool for up to four clouds of one width in one launch: outs[g][:, :c] = xs[g][idxs[g][:, 0]] (a zero row for an
+    index outside the cloud).  xs[g] [ns_g, c] and outs[g] [nq_g, >= c] may be row-strided, with one leading dimension each
+    for all clouds; columns of outs[g] beyond c are left as they are."""
+    L = _lib.lib()
+    n = len(xs)
+    if not (1 <= n <= 4 and len(idxs) == n and len(outs) == n):
+        raise RuntimeError("pcrcg_amd.gather_first_multi: one to four clouds")
+    c = xs[0].shape[1]
+    xs, ld_x = zip(*[_rows(x, _F32, "x") for x in xs])
+    idxs, ld_idx = zip(*[_rows(i, _I64, "inds") for i in idxs])
+    for o in outs:
+        _dev(o, _F32, "out")
+        if o.dim() != 2 or (o.shape[1] > 1 and o.stride(1) != 1):
+            raise RuntimeError("pcrcg_amd.gather_first_multi: `out` must be 2-D with unit inner stride")
+    ld_out = [o.stride(0) if o.shape[0] > 1 else max(c, o.stride(0)) for o in outs]
+    many_x = [l for x, l in zip(xs, ld_x) if x.shape[0] > 1] or [max(ld_x)]
+    many_o = [l for o, l in zip(outs, ld_out) if o.shape[0] > 1] or [max(ld_out)]
+    if len(set(many_x)) != 1 or len(set(many_o)) != 1 or any(x.shape[1] != c for x in xs):
+        raise RuntimeError("pcrcg_amd.gather_first_multi: the clouds must share width and leading dimensions")
+    ptrs = lambda ts: (ctypes.c_void_p * n)(*[t.data_ptr() for t in ts])
+    ints = lambda vs: (ctypes.c_int * n)(*[int(v) for v in vs])
+    _lib.check(L.pcrcg_gather_first_multi(ptrs(xs), ints([x.shape[0] for x in xs]), ptrs(idxs), ints([i.shape[0] for i in idxs]),
+                                          ints(ld_idx), ptrs(outs), n, c, many_x[0], many_o[0], _stream()),
+               "pcrcg_gather_first_multi")
+    return outs
 
 
 def instnorm_stats(x, eps=1e-5):
