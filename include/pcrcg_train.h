@@ -131,7 +131,9 @@ int pcrcg_gemm_f32_grad(const float* a, int lda, int trans_a, const float* b, in
 /* ---- backward kernels (autograd of the hot path) -------------------------------
  * Gradients flow to features and parameters only: geometry (points, influence weights) and the neighbour-count
  * normaliser carry none (ref:models/blocks.py:264-372).  Scatter kernels ACCUMULATE into dx with hardware fp32
- * atomics; the caller provides dx zero-initialised ([ns, c] row-major, shadow row not included). */
+ * atomics; the caller provides dx zero-initialised ([ns, c] row-major, shadow row not included).  The rigid KPConv, max_pool
+ * and closest_pool scatters also exist as GATHERS over a transposed neighbour table, without atomics and with a fixed
+ * summation order: the `_t` entries after pcrcg_neighbors_transpose_* below. */
 
 /* KPConv: dx[idx[q,h], c] += sum_k w[q,h,k] * d_wf[q,k,c]; d_wf [nq, 15*cin] = (dy * 1/n_q) @ W^T comes from
  * pcrcg_gemm_f32 (row_scale = inv_n), the weight gradient dW = wf^T @ (dy * 1/n_q) from pcrcg_gemm_f32_ex. */
@@ -179,6 +181,55 @@ int pcrcg_gather_max_backward(const float* x, int ns, int c, const int64_t* idx,
 /* closest_pool (ref:models/blocks.py:71-83): dx[idx[q,0], :] += dy[q, :]. */
 int pcrcg_gather_first_backward(const float* dy, int ld_dy, int c, const int64_t* idx, int nq, int ld_idx, int ns,
                                 float* dx, void* stream);
+/* ---- transposed neighbour tables: the three scatters above as gathers (csrc/transpose.hip) ---------------------------
+ * A table idx [nq, h] (leading dimension ld_idx) lists per query the supports it reads; an entry v is an EDGE iff
+ * 0 <= v < ns, everything else is a shadow, as the gather kernels read it.  The transpose lists per support the edges that
+ * arrive there.  Built once per pyramid, in two calls with one 8-byte read-back between them (the width the caller must
+ * allocate):
+ *   _count : deg [ns] i32 (overwritten) = edges into each support row; stats[0] = the edge total, stats[1] = the largest
+ *            in-degree (stats: two i32, overwritten).
+ *   _fill  : tq [ns, cols] i64 (leading dimension ld_tq): row s holds the queries q of the edges (q, j) into s in ascending
+ *            (q, j) order -- real entries lead -- and the value nq, the shadow index of the transposed problem, in every
+ *            position >= deg[s].  th (NULL, or [ns, cols] i32 with leading dimension ld_th) holds the column j of each edge,
+ *            pads -1.  A query that lists a support twice gives two edges.  status (one i32, overwritten) = 0 when every row
+ *            fits, 1 when some deg[s] > cols: that row keeps its first `cols` edges in order.  Nothing is written outside
+ *            [ns, cols].  deg = what _count left for the SAME table.  ws: pcrcg_neighbors_transpose_ws_bytes(nq, h, ns),
+ *            sized from the bound nq * h (the edge total is not known on the host).
+ * The table does not depend on scheduling: two calls give the same bytes.  nq = 0: zero degrees, an all-pad table.
+ * PCRCG_EBADARG before any launch unless nq, ns >= 0, h >= 1, ld_idx >= h, (long)nq * h < 2^31, cols >= 1, leading
+ * dimensions >= cols, and non-null pointers wherever the sizes are positive. */
+int pcrcg_neighbors_transpose_count(const int64_t* idx, int nq, int h, int ld_idx, int ns, int* deg, int* stats, void* stream);
+size_t pcrcg_neighbors_transpose_ws_bytes(int nq, int h, int ns);
+int pcrcg_neighbors_transpose_fill(const int64_t* idx, int nq, int h, int ld_idx, int ns, const int* deg, int cols, int64_t* tq,
+                                   int ld_tq, int* th, int ld_th, int* status, void* ws, size_t ws_bytes, void* stream);
+/* The gradients over such a table.  All three OVERWRITE every element of dx [ns, .] (no zeroing by the caller), use no
+ * floating-point atomic and none of deterministic=1's scratch, and add in table order in fp32: their own kernels give the
+ * same bits run after run in either arithmetic mode (the product inside the KPConv form follows pcrcg_gemm_f32_grad).
+ * A support row of in-degree 0 gets zeros.  Rows of tq must hold their real entries first (what _fill writes).
+ *
+ * pcrcg_kpconv_backward_dx_t: the input gradient of the rigid KPConv (pcrcg_kpconv_backward_dx with its d_wf product) as a
+ *   KPConv on the transposed graph.  With g = dy * inv_n[:, None]  (dy [nq, cout], inv_n [nq] as the forward left it):
+ *     dx[s, c] = sum_k ( sum_{(q,j): idx[q,j] = s} max(0, 1 - |q_pts[q] - s_pts[s] + kp[k]| / extent) g[q, :] ) @ W[k]^T
+ *   i.e. pcrcg_kpconv_aggregate with queries and supports swapped, the table tq (transpose of the layer's table; ns >
+ *   nq for a strided layer), features g and kernel points -kp, then one product of wf' [ns, 15 * cout] against
+ *     wt [15 * cout, cin] row-major,  wt[k * cout + o, c] = W[k, c, o]        (weights [15, cin, cout] with the last two
+ *   axes swapped), through pcrcg_gemm_f32_grad with the gradient operand A.  dx [ns, cin], leading dimension ld_dx.
+ *   ws: pcrcg_kpconv_backward_dx_t_ws_bytes(nq, ns, cout) = [ g | -kp | wf' | 1/n of the aggregate (unused) | its scratch ],
+ *   each part rounded up to 256 bytes.
+ * pcrcg_gather_max_backward_t: max_pool.  tq / th [ns, cols] (one leading dimension ld_t) = the transpose of idx WITH
+ *   columns; x, y, dy, idx as for pcrcg_gather_max_backward.  Edge (q, j) gives dy[q, c] to row s = idx[q, j] iff x[s, c] ==
+ *   y[q, c] and no column before j of row q attains y[q, c] (a shadow counts as 0 and swallows the gradient when it comes
+ *   first; an earlier real column of the same value wins) -- the element the scatter form adds to.  dx [ns, c] dense.
+ * pcrcg_gather_first_backward_t: closest_pool.  tq = the transpose of column 0 ALONE (pcrcg_neighbors_transpose_* with
+ *   h = 1 and the table's ld_idx): dx[s, :] = sum_j dy[tq[s, j], :]. */
+size_t pcrcg_kpconv_backward_dx_t_ws_bytes(int nq, int ns, int cout);
+int pcrcg_kpconv_backward_dx_t(const float* q_pts, int nq, const float* s_pts, int ns, const int64_t* tq, int cols, int ld_tq,
+                               const float* dy, int ld_dy, const float* inv_n, int cout, const float* kp, float extent,
+                               const float* wt, int cin, float* dx, int ld_dx, void* ws, size_t ws_bytes, void* stream);
+int pcrcg_gather_max_backward_t(const float* x, int ns, int c, const int64_t* idx, int nq, int h, int ld_idx, const float* y,
+                                const float* dy, const int64_t* tq, const int* th, int cols, int ld_t, float* dx, void* stream);
+int pcrcg_gather_first_backward_t(const float* dy, int ld_dy, int c, const int64_t* tq, int cols, int ld_tq, int nq, int ns,
+                                  float* dx, int ld_dx, void* stream);
 /* InstanceNorm over the rows + LeakyReLU(slope) (ref:models/blocks.py:448-462): with xhat = (x-mean)*rstd
  * (stats = pcrcg_instnorm_stats layout) and g = dy * (xhat > 0 ? 1 : slope):
  *   dx = rstd * (g - mean(g) - xhat * mean(g * xhat)). */

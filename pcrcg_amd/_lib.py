@@ -210,6 +210,18 @@ SIGNATURES = {
     "pcrcg_gather_max_backward": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
                                           c_void_p, c_void_p]),
     "pcrcg_gather_first_backward": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "pcrcg_neighbors_transpose_count": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "pcrcg_neighbors_transpose_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "pcrcg_neighbors_transpose_fill": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p,
+                                               c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "pcrcg_kpconv_backward_dx_t_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "pcrcg_kpconv_backward_dx_t": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p,
+                                           c_int, c_void_p, c_float, c_void_p, c_int, c_void_p, c_int, c_void_p, c_size_t,
+                                           c_void_p]),
+    "pcrcg_gather_max_backward_t": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                            c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "pcrcg_gather_first_backward_t": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int,
+                                              c_void_p]),
     "pcrcg_instnorm_backward_ws_bytes": (c_size_t, [c_int]),
     "pcrcg_instnorm_backward": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_float, c_void_p,
                                         c_int, c_void_p, c_size_t, c_void_p]),

@@ -17,7 +17,11 @@ records the graph; the gradient formulas are the ones of SURVEY.md appendix C:
 Points, neighbour tables and the stored kernel points never receive a gradient.  The deformed kernel points do, through
 `offset_features` of kpconv_ex (every KPConv configuration of ref:models/blocks.py:229-374: deformable, modulated,
 constant / linear / gaussian influence, sum / closest aggregation); the kept mask, the closest one-hot and n_q are
-constants there, as in torch."""
+constants there, as in torch.
+
+kpconv, max_pool and closest_pool take `transposed=` (an ops.NeighborTranspose of their table): dx is then GATHERED over the
+edges that arrive at each support row (include/pcrcg_train.h, the `_t` entries) -- no atomics, a fixed
+order.  None keeps today's scatters; the forwards are the same either way."""
 import torch
 
 from . import _lib, ops
@@ -27,6 +31,20 @@ _F32 = torch.float32
 
 def _c(t):
     return t if t.is_contiguous() else t.contiguous()
+
+
+def _checked_transpose(t, nq, ns, what, columns=False):
+    """None, or the ops.NeighborTranspose handed to `what`, refused when it was built for a table of another shape."""
+    if t is None:
+        return None
+    if not isinstance(t, ops.NeighborTranspose):
+        raise TypeError(f"pcrcg_amd.autograd.{what}: `transposed` must be an ops.NeighborTranspose or None")
+    if t.nq != nq or t.ns != ns:
+        raise RuntimeError(f"pcrcg_amd.autograd.{what}: `transposed` was built for {t.nq} queries and {t.ns} supports, "
+                           f"the table has {nq} and {ns}")
+    if columns and t.th is None:
+        raise RuntimeError(f"pcrcg_amd.autograd.{what}: `transposed` needs its columns (transpose_neighbors(with_columns=True))")
+    return t
 
 
 class _Matmul(torch.autograd.Function):
@@ -64,7 +82,7 @@ def linear(x, weight, bias=None):
 
 class _KPConv(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, weights, q_pts, s_pts, idx, kp, extent):
+    def forward(ctx, x, weights, q_pts, s_pts, idx, kp, extent, transposed=None):
         L = _lib.lib()
         x = _c(x)
         q_pts, s_pts, kp = _c(q_pts), _c(s_pts), _c(kp)
@@ -72,6 +90,7 @@ class _KPConv(torch.autograd.Function):
         nq, h = idx2.shape
         ns, cin = x.shape
         kdim = kp.shape[0]
+        ctx.transposed = _checked_transpose(transposed, nq, ns, "kpconv")
         wf = torch.empty((nq, kdim * cin), dtype=_F32, device=x.device)
         inv_n = torch.empty(nq, dtype=_F32, device=x.device)
         nbytes = L.pcrcg_kpconv_ws_bytes(ns)
@@ -94,19 +113,34 @@ class _KPConv(torch.autograd.Function):
         dx = dw = None
         if ctx.needs_input_grad[1]:
             dw = ops.gemm(wf.t(), dy * inv_n[:, None], grad_operand=2).reshape(wshape)
-        if ctx.needs_input_grad[0]:
+        if ctx.needs_input_grad[0] and ctx.transposed is not None:
+            # the gather form: a KPConv of dy / n on the transposed graph, contracted with the weights' last two axes swapped
+            t = ctx.transposed
+            nq, cout = dy.shape
+            kdim = kp.shape[0]
+            wt = w2.reshape(kdim, cin, cout).permute(0, 2, 1).reshape(kdim * cout, cin).contiguous()
+            dx = torch.empty((ns, cin), dtype=_F32, device=dy.device)
+            nbytes = L.pcrcg_kpconv_backward_dx_t_ws_bytes(nq, ns, cout)
+            ws = ops._ws.get("kpconv_dx_t", nbytes, dy.device)
+            _lib.check(L.pcrcg_kpconv_backward_dx_t(q_pts.data_ptr(), nq, s_pts.data_ptr(), ns, t.tq.data_ptr(), t.tq.shape[1],
+                                                    t.tq.stride(0), dy.data_ptr(), cout, inv_n.data_ptr(), cout, kp.data_ptr(),
+                                                    extent, wt.data_ptr(), cin, dx.data_ptr(), cin, ws.data_ptr(), nbytes,
+                                                    ops._stream()), "pcrcg_kpconv_backward_dx_t")
+        elif ctx.needs_input_grad[0]:
             d_wf = ops.gemm(dy, w2.t(), row_scale=inv_n, grad_operand=1)               # [nq, 15*cin]
             dx = torch.zeros((ns, cin), dtype=_F32, device=dy.device)
             nq, h = idx2.shape
             _lib.check(L.pcrcg_kpconv_backward_dx(q_pts.data_ptr(), nq, s_pts.data_ptr(), ns, idx2.data_ptr(), h, ld_idx,
                                                   d_wf.data_ptr(), cin, kp.data_ptr(), extent, dx.data_ptr(),
                                                   ops._stream()), "pcrcg_kpconv_backward_dx")
-        return dx, dw, None, None, None, None, None
+        return dx, dw, None, None, None, None, None, None
 
 
-def kpconv(x, weights, q_pts, s_pts, idx, kernel_points, extent):
-    """KPConv.forward (ref:models/blocks.py:229-374), differentiable in x and weights [15, cin, cout]."""
-    return _KPConv.apply(x, weights, q_pts, s_pts, idx, kernel_points, extent)
+def kpconv(x, weights, q_pts, s_pts, idx, kernel_points, extent, transposed=None):
+    """KPConv.forward (ref:models/blocks.py:229-374), differentiable in x and weights [15, cin, cout].  transposed: the
+    ops.NeighborTranspose of `idx` (ops.transpose_neighbors(idx, ns)); the input gradient is then gathered over it
+    (pcrcg_kpconv_backward_dx_t: no atomics) instead of scattered.  The forward is the same either way."""
+    return _KPConv.apply(x, weights, q_pts, s_pts, idx, kernel_points, extent, transposed)
 
 
 class _KPConvEx(torch.autograd.Function):
@@ -226,10 +260,11 @@ def instnorm_lrelu(x, slope=1.0, eps=1e-5):
 
 class _MaxPool(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, idx):
+    def forward(ctx, x, idx, transposed=None):
         x = _c(x)
         y = ops.gather_max(x, idx)
         ctx.save_for_backward(x, idx, y)
+        ctx.transposed = _checked_transpose(transposed, idx.shape[0], x.shape[0], "max_pool", columns=True)
         return y
 
     @staticmethod
@@ -240,23 +275,33 @@ class _MaxPool(torch.autograd.Function):
         idx2, ld_idx = ops._rows(idx, torch.int64, "inds")
         ns, c = x.shape
         nq, h = idx2.shape
+        t = ctx.transposed
+        if t is not None:
+            dx = torch.empty_like(x)
+            _lib.check(L.pcrcg_gather_max_backward_t(x.data_ptr(), ns, c, idx2.data_ptr(), nq, h, ld_idx, y.data_ptr(),
+                                                     dy.data_ptr(), t.tq.data_ptr(), t.th.data_ptr(), t.tq.shape[1],
+                                                     t.tq.stride(0), dx.data_ptr(), ops._stream()),
+                       "pcrcg_gather_max_backward_t")
+            return dx, None, None
         dx = torch.zeros_like(x)
         _lib.check(L.pcrcg_gather_max_backward(x.data_ptr(), ns, c, idx2.data_ptr(), nq, h, ld_idx, y.data_ptr(),
                                                dy.data_ptr(), dx.data_ptr(), ops._stream()), "pcrcg_gather_max_backward")
-        return dx, None
+        return dx, None, None
 
 
-def max_pool(x, inds):
-    """ref:models/blocks.py:86-102."""
-    return _MaxPool.apply(x, inds)
+def max_pool(x, inds, transposed=None):
+    """ref:models/blocks.py:86-102.  transposed: ops.transpose_neighbors(inds, ns, with_columns=True) -- the backward then
+    gathers over it (pcrcg_gather_max_backward_t) instead of scattering."""
+    return _MaxPool.apply(x, inds, transposed)
 
 
 class _ClosestPool(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, idx):
+    def forward(ctx, x, idx, transposed=None):
         x = _c(x)
         ctx.save_for_backward(idx)
         ctx.shape = tuple(x.shape)
+        ctx.transposed = _checked_transpose(transposed, idx.shape[0], x.shape[0], "closest_pool")
         return ops.gather_first(x, idx)
 
     @staticmethod
@@ -266,15 +311,23 @@ class _ClosestPool(torch.autograd.Function):
         dy = _c(dy)
         idx2, ld_idx = ops._rows(idx, torch.int64, "inds")
         ns, c = ctx.shape
+        t = ctx.transposed
+        if t is not None:
+            dx = torch.empty(ctx.shape, dtype=_F32, device=dy.device)
+            _lib.check(L.pcrcg_gather_first_backward_t(dy.data_ptr(), c, c, t.tq.data_ptr(), t.tq.shape[1], t.tq.stride(0),
+                                                       idx2.shape[0], ns, dx.data_ptr(), c, ops._stream()),
+                       "pcrcg_gather_first_backward_t")
+            return dx, None, None
         dx = torch.zeros(ctx.shape, dtype=_F32, device=dy.device)
         _lib.check(L.pcrcg_gather_first_backward(dy.data_ptr(), c, c, idx2.data_ptr(), idx2.shape[0], ld_idx, ns,
                                                  dx.data_ptr(), ops._stream()), "pcrcg_gather_first_backward")
-        return dx, None
+        return dx, None, None
 
 
-def closest_pool(x, inds):
-    """ref:models/blocks.py:71-83."""
-    return _ClosestPool.apply(x, inds)
+def closest_pool(x, inds, transposed=None):
+    """ref:models/blocks.py:71-83.  transposed: the transpose of column 0 alone, ops.transpose_neighbors(inds[:, :1], ns) --
+    the backward then gathers over it (pcrcg_gather_first_backward_t) instead of scattering."""
+    return _ClosestPool.apply(x, inds, transposed)
 
 
 class _SoftmaxRows(torch.autograd.Function):

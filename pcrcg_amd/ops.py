@@ -766,6 +766,47 @@ def gather_first(x, idx, out=None):
     return out
 
 
+class NeighborTranspose:
+    """A neighbour table transposed (include/pcrcg_train.h, pcrcg_neighbors_transpose_*): tq [ns, max(d_max, 1)] int64 = per
+    support the queries that list it, in ascending (query, column) order, padded with nq; th (with_columns) the column of
+    each of those edges, padded with -1; deg [ns] int32 the in-degrees; n_edges their total and d_max their maximum (host
+    ints); nq, ns the shape of the problem the table came from."""
+    __slots__ = ("tq", "th", "deg", "n_edges", "d_max", "nq", "ns")
+
+    def __init__(self, tq, th, deg, n_edges, d_max, nq, ns):
+        self.tq, self.th, self.deg, self.n_edges, self.d_max, self.nq, self.ns = tq, th, deg, n_edges, d_max, nq, ns
+
+
+def transpose_neighbors(idx, ns, with_columns=False, max_cols=None):
+    """Transpose the table idx [nq, h] (int64; entries outside [0, ns) are shadows) for the gather-form backward passes of
+    pcrcg_amd.autograd.  One 8-byte read-back (edge total, largest in-degree) sits between the count and the fill: it sizes
+    the table.  max_cols: raise RuntimeError instead of building a table wider than that."""
+    L = _lib.lib()
+    idx, ld_idx = _rows(idx, _I64, "inds")
+    nq, h = idx.shape
+    ns = int(ns)
+    if h < 1:
+        raise RuntimeError("pcrcg_amd.transpose_neighbors: the table needs at least one column")
+    dev = idx.device
+    deg = torch.empty(max(ns, 1), dtype=_I32, device=dev)[:ns]
+    stats = torch.empty(2, dtype=_I32, device=dev)
+    _lib.check(L.pcrcg_neighbors_transpose_count(idx.data_ptr(), nq, h, ld_idx, ns, deg.data_ptr(), stats.data_ptr(), _stream()),
+               "pcrcg_neighbors_transpose_count")
+    n_edges, d_max = (int(v) for v in stats.cpu())
+    if max_cols is not None and d_max > max_cols:
+        raise RuntimeError(f"pcrcg_amd.transpose_neighbors: d_max = {d_max} exceeds max_cols = {max_cols}")
+    cols = max(d_max, 1)
+    tq = torch.empty((ns, cols), dtype=_I64, device=dev)
+    th = torch.empty((ns, cols), dtype=_I32, device=dev) if with_columns else None
+    status = torch.empty(1, dtype=_I32, device=dev)
+    nbytes = L.pcrcg_neighbors_transpose_ws_bytes(nq, h, ns)
+    ws = _ws.get("transpose", nbytes, dev)
+    _lib.check(L.pcrcg_neighbors_transpose_fill(idx.data_ptr(), nq, h, ld_idx, ns, deg.data_ptr(), cols, tq.data_ptr(), cols,
+                                                _ptr(th), cols, status.data_ptr(), ws.data_ptr(), nbytes, _stream()),
+               "pcrcg_neighbors_transpose_fill")
+    return NeighborTranspose(tq, th, deg, n_edges, d_max, nq, ns)
+
+
 def gather_first_multi(xs, idxs, outs):
     """closest_pool for up to four clouds of one width in one launch: outs[g][:, :c] = xs[g][idxs[g][:, 0]] (a zero row for an
     index outside the cloud).  xs[g] [ns_g, c] and outs[g] [nq_g, >= c] may be row-strided, with one leading dimension each

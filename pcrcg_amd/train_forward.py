@@ -34,15 +34,16 @@ def _norm(bn_block, x, slope):
     return y if slope == 1.0 else F.leaky_relu(y, slope)
 
 
-def _kpconv(mod, q_pts, s_pts, inds, x):
+def _kpconv(mod, q_pts, s_pts, inds, x, transposed=None):
     """KPConv.forward with gradients (ref:models/blocks.py:229-374).  The rigid / linear / sum configuration of the shipped
     architectures stays on AG.kpconv; every other one runs its offset convolution first (itself a rigid kernel of the
-    module's influence and aggregation mode, :179-198), adds offset_bias (:238) and goes through AG.kpconv_ex."""
+    module's influence and aggregation mode, :179-198), adds offset_bias (:238) and goes through AG.kpconv_ex.
+    transposed: the table's ops.NeighborTranspose for the rigid layers' input gradient; the others keep the scatter."""
     if mod.rigid:
-        return AG.kpconv(x, mod.weights, q_pts, s_pts, inds, mod.kernel_points.data, mod.KP_extent)
+        return AG.kpconv(x, mod.weights, q_pts, s_pts, inds, mod.kernel_points.data, mod.KP_extent, **_tr(transposed))
     offset_features = None
     if mod.deformable:
-        offset_features = _kpconv(mod.offset_conv, q_pts, s_pts, inds, x) + mod.offset_bias
+        offset_features = _kpconv(mod.offset_conv, q_pts, s_pts, inds, x, transposed) + mod.offset_bias
         mod.offset_features = offset_features.detach()
         offsets = mod.offset_features[:, :mod.p_dim * mod.K].reshape(-1, mod.K, mod.p_dim) * mod.KP_extent
         mod.deformed_KP = offsets + mod.kernel_points.data                                      # :258,279
@@ -54,16 +55,47 @@ def _kpconv(mod, q_pts, s_pts, inds, x):
     return out
 
 
+def transpose_tables(batch):
+    """The batch's neighbour tables transposed once (ops.transpose_neighbors), for forward_train(dx="transposed"):
+    {"neighbors": [...], "pools": [...], "upsamples": [...]}, one ops.NeighborTranspose per level (None where the batch has
+    no table) -- neighbors[l] as it is, pools[l] with its columns (the strided shortcut's max_pool needs them), and column 0
+    alone of upsamples[l] (all closest_pool reads)."""
+    n = [int(p.shape[0]) for p in batch["points"]]
+
+    def one(table, level, column0=False, **kw):
+        """the table's supports are the points of `level`; the empty placeholder of the last level has no transpose"""
+        if table.dim() != 2 or table.shape[0] == 0 or level >= len(n):
+            return None
+        return ops.transpose_neighbors(table[:, :1] if column0 else table, n[level], **kw)
+    return {
+        "neighbors": [one(t, l) for l, t in enumerate(batch["neighbors"])],
+        "pools": [one(t, l, with_columns=True) for l, t in enumerate(batch["pools"])],
+        "upsamples": [one(t, l + 1, column0=True) for l, t in enumerate(batch["upsamples"])],
+    }
+
+
+def _transposed(batch, kind, layer_ind):
+    tables = batch.get("_transposes")
+    return None if tables is None else tables[kind][layer_ind]
+
+
+def _tr(transposed):
+    """the `transposed=` keyword of an autograd op, only where there is a table: the scatter path's calls stay as they were"""
+    return {} if transposed is None else {"transposed": transposed}
+
+
 def _block(block, x, batch):
     if isinstance(block, SimpleBlock):                                   # ref:models/blocks.py:579-590
         q_pts, s_pts, inds = _geometry(block.block_name, block.layer_ind, batch)
-        return _norm(block.batch_norm, _kpconv(block.KPConv, q_pts, s_pts, inds, x), 0.1)
+        tr = _transposed(batch, "pools" if "strided" in block.block_name else "neighbors", block.layer_ind)
+        return _norm(block.batch_norm, _kpconv(block.KPConv, q_pts, s_pts, inds, x, tr), 0.1)
     if isinstance(block, ResnetBottleneckBlock):                         # :650-678
         q_pts, s_pts, inds = _geometry(block.block_name, block.layer_ind, batch)
+        tr = _transposed(batch, "pools" if "strided" in block.block_name else "neighbors", block.layer_ind)
         y = x if isinstance(block.unary1, nn.Identity) else _unary(block.unary1, x)
-        y = _norm(block.batch_norm_conv, _kpconv(block.KPConv, q_pts, s_pts, inds, y), 0.1)
+        y = _norm(block.batch_norm_conv, _kpconv(block.KPConv, q_pts, s_pts, inds, y, tr), 0.1)
         y = _unary(block.unary2, y)
-        shortcut = AG.max_pool(x, inds) if "strided" in block.block_name else x
+        shortcut = AG.max_pool(x, inds, **_tr(tr)) if "strided" in block.block_name else x
         if not isinstance(block.unary_shortcut, nn.Identity):
             shortcut = _unary(block.unary_shortcut, shortcut)
         return F.leaky_relu(y + shortcut, 0.1)
@@ -72,7 +104,8 @@ def _block(block, x, batch):
     if isinstance(block, LastUnaryBlock):                                # :527-529
         return AG.linear(x, block.mlp.weight)
     if isinstance(block, NearestUpsampleBlock):                          # :704-705
-        return AG.closest_pool(x, batch["upsamples"][block.layer_ind - 1])
+        table = block.layer_ind - 1
+        return AG.closest_pool(x, batch["upsamples"][table], **_tr(_transposed(batch, "upsamples", table)))
     raise NotImplementedError(f"pcrcg_amd.train_forward: block {type(block).__name__}")
 
 
@@ -134,8 +167,16 @@ def _gnn(gnn, coords0, coords1, desc0, desc1):
     return desc0, desc1
 
 
-def forward_train(net, batch):
-    """KPFCNN.forward with gradients (ref:models/architectures.py:181-191,516-610)."""
+def forward_train(net, batch, dx="scatter", transposes=None):
+    """KPFCNN.forward with gradients (ref:models/architectures.py:181-191,516-610).  dx: how the backward of the rigid
+    KPConvs, the strided shortcuts' max_pool and the upsamplings reaches the support rows -- "scatter" (fp32 atomics, fixed
+    point under deterministic=1) or "transposed" (gathers over the transposed tables, no atomics: `transposes` =
+    transpose_tables(batch), built here when None).  The forward values are the same either way."""
+    if dx not in ("scatter", "transposed"):
+        raise ValueError("pcrcg_amd.forward_train: dx must be 'scatter' or 'transposed', not %r" % (dx,))
+    if dx == "transposed":
+        batch = dict(batch)
+        batch["_transposes"] = transposes if transposes is not None else transpose_tables(batch)
     x = batch["features"].clone().detach()
     if "stack_lengths_host" in batch:
         len_src_c = int(batch["stack_lengths_host"][-1][0])

@@ -343,12 +343,19 @@ class FlatAdam(torch.optim.Optimizer):
 class Trainer:
     def __init__(self, model, desc_loss, lr=0.005, momentum=0.98, weight_decay=1e-6, scheduler_gamma=0.95,
                  iter_size=1, process_group=None, overlap_chunks=4, use_cpp_runner=True, optimizer="SGD",
-                 betas=(0.9, 0.999), eps=1e-8, backbone2d=None):
+                 betas=(0.9, 0.999), eps=1e-8, backbone2d=None, kpconv_dx="scatter"):
         """optimizer: "SGD" (ref:configs/train/indoor.yaml) or "ADAM" (ref:configs/train/pram_cofi.yaml; lr, betas, eps,
         weight_decay -- momentum is ignored, as ref:main.py:66-72 ignores it), matched without regard to case.
         backbone2d: the caller's 2-D backbone of an image_feature model (ref:lib/trainer.py:225-228,272-275 hands it to the
         model in every phase).  It is run under no_grad and is otherwise left alone: it is in neither the gradient bucket
-        nor the optimiser, and its train / eval mode is the caller's."""
+        nor the optimiser, and its train / eval mode is the caller's.
+        kpconv_dx: "scatter", or "transposed" -- the gather-form backward of train_forward.forward_train; the
+        C++ runner has no such path, so it needs use_cpp_runner=False."""
+        if kpconv_dx not in ("scatter", "transposed"):
+            raise ValueError("pcrcg_amd.Trainer: kpconv_dx must be 'scatter' or 'transposed', not %r" % (kpconv_dx,))
+        if kpconv_dx == "transposed" and use_cpp_runner:
+            raise ValueError("pcrcg_amd.Trainer: kpconv_dx='transposed' runs on the op-by-op path only: pass use_cpp_runner=False")
+        self.kpconv_dx = kpconv_dx
         self.model, self.desc_loss = model, desc_loss
         self.backbone2d = backbone2d
         kind = str(optimizer).upper()
@@ -402,7 +409,7 @@ class Trainer:
                     net_inputs = dict(inputs)
                     net_inputs["features"] = self.model.image_features(
                         inputs, self.backbone2d, width=self.model.IMAGE_WIDTH if tr is not None else None)
-                output = tr.forward(net_inputs) if tr is not None else forward_train(self.model, net_inputs)
+                output = tr.forward(net_inputs) if tr is not None else forward_train(self.model, net_inputs, dx=self.kpconv_dx)
             elif self.backbone2d is not None:
                 output = self.model(inputs, self.backbone2d)     # (KPFCNN.forward builds the image input itself)
             else:
