@@ -258,6 +258,31 @@ int pcrcg_edgeconv_backward(const float* ctr, const float* nbr, const int* idx, 
                             const float* dy, float slope, float* dctr, float* dnbr, void* ws, size_t ws_bytes,
                             void* stream);
 
+/* ---- the tail of PCR-CG's pose head and its gradient (csrc/heads.hip; ref:models/architectures.py:589-596) ------------
+ * h [n, ld_h] is the last folding activation, `width` columns of it are used (ld_h >= width, ld_h % 4 == 0); w_q [4, width],
+ * b_q [4], w_t [3, width], b_t [3] are linear1 / linear2 as nn.Linear stores them, dense.  Per row u_r = w_q h_r + b_q and
+ * v_r = w_t h_r + b_t;
+ *   out7[0..3] = quaternion_pred = mean_r(u_r / |u_r|)   (plain division, no epsilon: a row with |u_r| = 0 makes all four NaN,
+ *                                                          as torch's; out7[4..6] stay finite)
+ *   out7[4..6] = trans_pred      = mean_r(v_r)
+ * q_rows (NULL, or [n, 4] dense) receives the raw u_r, which the backward entry needs.  h is read once.  Row sums leave the
+ * workgroups (64 rows each) as float64 partials in `ws` and a finishing launch adds them in ascending workgroup order: no
+ * floating-point atomics, two calls give the same bits.
+ * _backward: g7 (device) = dL/d out7.  With u^ = u_r / |u_r| and s_r = (I - u^ u^T) g_q / (|u_r| n):
+ *   dh [n, ld_dh] (columns < width OVERWRITTEN, the others untouched) : dh_r = w_q^T s_r + w_t^T g_t / n
+ *   dw_q [4, width] = sum_r s_r h_r^T,  db_q [4] = sum_r s_r,  dw_t [3, width] = (g_t / n) (sum_r h_r)^T,  db_t [3] = g_t
+ * all overwritten, dense, from the same kind of fixed-order float64 partials.  h, q_rows and the weights as the forward had them.
+ * PCRCG_EBADARG before any launch unless 1 <= n <= 2^30, width == 1024 (the one width served), the leading dimensions as
+ * above, non-null pointers (q_rows of the forward excepted), h, dh, w_q, w_t, q_rows 16-byte aligned, ws 8-byte aligned and
+ * ws_bytes >= pcrcg_pose_head_ws_bytes(n, width), which serves either entry (0 for an n or a width that is not served).
+ * Two launches each; nothing is allocated or synchronised inside. */
+size_t pcrcg_pose_head_ws_bytes(int n, int width);
+int pcrcg_pose_head(const float* h, int ld_h, int n, int width, const float* w_q, const float* b_q, const float* w_t,
+                    const float* b_t, float* out7, float* q_rows, void* ws, size_t ws_bytes, void* stream);
+int pcrcg_pose_head_backward(const float* h, int ld_h, int n, int width, const float* w_q, const float* w_t,
+                             const float* q_rows, const float* g7, float* dh, int ld_dh, float* dw_q, float* db_q, float* dw_t,
+                             float* db_t, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- the train step's network part in two calls (csrc/train_runner.hip) ---------------------------------------
  * KPFCNN.forward with a tape, and its backward (ref:lib/trainer.py:216-265 runs ref:models/architectures.py:181-191,
  * 516-610 under torch.autograd).  `model` as for pcrcg_kpfcnn_forward, with these differences in what the fields hold:

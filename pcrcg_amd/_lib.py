@@ -241,6 +241,11 @@ SIGNATURES = {
                                                  c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "pcrcg_correspondences_batch_emit": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p,
                                                  c_void_p]),
+    "pcrcg_pose_head_ws_bytes": (c_size_t, [c_int, c_int]),
+    "pcrcg_pose_head": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                c_void_p, c_size_t, c_void_p]),
+    "pcrcg_pose_head_backward": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "pcrcg_kpfcnn_train_ws_bytes": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "pcrcg_kpfcnn_train_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_void_p,
                                            c_void_p, c_void_p]),

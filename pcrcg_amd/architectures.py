@@ -23,9 +23,13 @@ class KPFCNN(nn.Module):
     def __init__(self, config):
         super().__init__()
         config = as_config(config)
-        if config.get("node_overlap", False) or config.get("quaternion", False):
-            raise NotImplementedError("pcrcg_amd.KPFCNN: the node-overlap / quaternion heads are outside the "
-                                      "accelerated path (SURVEY.md 8f)")
+        # PCR-CG's two optional heads (ref:models/architectures.py:157-173,545-552,584-596): a node-overlap score on the
+        # coarse rows and a pose (quaternion + translation) regressed from the fine descriptors
+        self.node_overlap = bool(config.get("node_overlap", False))
+        self.quaternion = bool(config.get("quaternion", False))
+        if self.quaternion and config.final_feats_dim != 32:
+            raise ValueError("pcrcg_amd.KPFCNN: quaternion needs final_feats_dim = 32 (the reference's folding1 starts with "
+                             "Linear(32, 64)), not %d" % config.final_feats_dim)
         # PCR-CG's image-feature injection (ref:models/architectures.py:48-50,195-514): the 2-D backbone is the caller's
         # (forward(batch, backbone2d)); the gather of its per-pixel features into the [N, 129] point features is ours
         self.image_feature = bool(config.get("image_feature", False))
@@ -88,6 +92,14 @@ class KPFCNN(nn.Module):
                 layer -= 1
                 r *= 0.5
                 out_dim = out_dim // 2
+        # the heads, created after the decoder in the reference's order: same keys, shapes and seeded state (:157-173)
+        if self.node_overlap:
+            self.node_overlap_predict = nn.Conv1d(gnn_feats_dim, 1, kernel_size=1, bias=True)
+        if self.quaternion:
+            self.folding1 = nn.Sequential(nn.Linear(32, 64), nn.ReLU(), nn.Linear(64, 128), nn.ReLU(), nn.Linear(128, 256),
+                                          nn.ReLU(), nn.Linear(256, 512), nn.ReLU(), nn.Linear(512, 1024), nn.ReLU())
+            self.linear1 = nn.Linear(1024, 4)
+            self.linear2 = nn.Linear(1024, 3)
         self._eps_cache = None
         self._runner = None
         # the C++ runner enqueues the forward (one FFI call); set use_runner = False for the op-by-op mirror forward_ops
@@ -96,6 +108,9 @@ class KPFCNN(nn.Module):
         # kernel (ops.kpconv_ex), which the C++ runners do not sequence and which has no backward -- forward_ops, inference
         self.non_rigid = non_rigid_block(self)
         if self.non_rigid is not None:
+            self.use_runner = False
+        # the heads are not sequenced by the C++ runners either (blocks.refuse_heads): op by op, inference and training
+        if self.node_overlap or self.quaternion:
             self.use_runner = False
 
     def regular_score(self, score):
@@ -255,6 +270,10 @@ class KPFCNN(nn.Module):
         feats_c = self._conv1x1(self.proj_gnn, feats_c)                          # :538
         scores_c = self._conv1x1(self.proj_score, feats_c)                       # :539  [N, 1]
         feats_norm = F.normalize(feats_c, p=2, dim=1)                            # :541
+        res = {}
+        if self.node_overlap:                                                    # :546-552 (no regular_score, as :550)
+            node = self._conv1x1(self.node_overlap_predict, feats_c)
+            res["node_overlap_score_pred"] = torch.clamp(torch.sigmoid(node.view(-1)), min=0, max=1)
 
         # 4. cross-cloud saliency (:556-565)
         src_n, tgt_n = feats_norm[:len_src_c], feats_norm[len_src_c:]
@@ -281,4 +300,13 @@ class KPFCNN(nn.Module):
         scores_overlap = self.regular_score(scores_overlap)
         scores_saliency = self.regular_score(scores_saliency)
         feats_f = F.normalize(feats_f, p=2, dim=1)                                             # :582
-        return {"feats_f": feats_f, "scores_overlap": scores_overlap, "scores_saliency": scores_saliency}
+        if self.quaternion:                                                                    # :584-596
+            temp = feats_f
+            for layer in self.folding1:
+                if isinstance(layer, nn.Linear):
+                    temp = torch.relu_(ops.gemm(temp, layer.weight.data.t(), bias=layer.bias.data))
+            # linear1, linear2, the row normalisation and the two means in one pass over temp [N, 1024] (csrc/heads.hip)
+            res["quaternion_pred"], res["trans_pred"] = ops.pose_head(
+                temp, self.linear1.weight.data, self.linear1.bias.data, self.linear2.weight.data, self.linear2.bias.data)[:2]
+        res.update({"feats_f": feats_f, "scores_overlap": scores_overlap, "scores_saliency": scores_saliency})
+        return res

@@ -13,6 +13,9 @@ records the graph; the gradient formulas are the ones of SURVEY.md appendix C:
   closest_pool  y = x[idx[:, 0]]                  dx[idx[:, 0]] += dy
   softmax_rows  p = softmax(s * scale)            ds = scale * p * (dp - sum p * dp)
   edge_conv     y = lrelu(IN2d(max_j(ctr_i + nbr_idx[i,j])), 0.2)   (DGCNN edge conv of ref:models/gcn.py:37-64,121-129)
+  pose_head     q = mean_r(u_r / |u_r|), t = mean_r(v_r),  u = h w_q^T + b_q,  v = h w_t^T + b_t
+                                                  s_r = (I - u^ u^T) g_q / (|u_r| n),  dh_r = w_q^T s_r + w_t^T g_t / n,
+                                                  dw_q = sum_r s_r h_r^T,  db_q = sum_r s_r,  dw_t = (g_t / n) (sum_r h_r)^T,  db_t = g_t
 
 Points, neighbour tables and the stored kernel points never receive a gradient.  The deformed kernel points do, through
 `offset_features` of kpconv_ex (every KPConv configuration of ref:models/blocks.py:229-374: deformable, modulated,
@@ -384,3 +387,28 @@ class _EdgeConv(torch.autograd.Function):
 def edge_conv(ctr, nbr, idx, slope=0.2, eps=1e-5):
     """max_j LeakyReLU(InstanceNorm2d(ctr_i + nbr_idx[i,j])) with the statistics taken over all N*k edges."""
     return _EdgeConv.apply(ctr, nbr, idx, slope, eps)
+
+
+class _PoseHead(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, h, w_q, b_q, w_t, b_t):
+        quat, trans, q_rows = ops.pose_head(h, w_q, b_q, w_t, b_t, want_rows=True)
+        ctx.save_for_backward(h, w_q, w_t, q_rows)
+        return quat.clone(), trans.clone()          # (ops.pose_head returns two views of one tensor)
+
+    @staticmethod
+    def backward(ctx, d_quat, d_trans):
+        h, w_q, w_t, q_rows = ctx.saved_tensors
+        g = torch.zeros(7, dtype=_F32, device=h.device)
+        if d_quat is not None:
+            g[:4] = d_quat
+        if d_trans is not None:
+            g[4:] = d_trans
+        dh, dw_q, db_q, dw_t, db_t = ops.pose_head_backward(h, w_q, w_t, q_rows, g)
+        return dh, dw_q, db_q, dw_t, db_t
+
+
+def pose_head(h, w_q, b_q, w_t, b_t):
+    """linear1 / linear2 of PCR-CG's pose head with the row normalisation and the two means (ref:models/architectures.py:
+    589-596) on h [n, 1024]: -> (quaternion_pred [4], trans_pred [3]), differentiable in all five arguments."""
+    return _PoseHead.apply(h, w_q, b_q, w_t, b_t)

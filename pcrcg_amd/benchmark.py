@@ -87,6 +87,32 @@ def mat2quat(M):
     return q
 
 
+def quaternion_from_matrix(matrix, isprecise=False):
+    """ref:models/r_eval.py quaternion_from_matrix, the ground truth of PCR-CG's pose loss (ref:lib/trainer.py:250): the
+    unit quaternion (w, x, y, z), w >= 0, of a rotation given as [3,3] or homogeneous [4,4], taken in float64.  Default: the
+    eigenvector method of mat2quat above (the same K, the same sign rule) -- what the trainer uses.  isprecise: the closed
+    form for an exact homogeneous [4,4] matrix -- from the trace when it exceeds M[3,3], else from the largest diagonal
+    entry.  (That second case follows the published algorithm: the reference's copy of it indexes the matrix one off and
+    leaves q[0] unset, so there is nothing to reproduce; tests/golden/model_heads_mini.pt records the trace case only.)"""
+    M = np.asarray(matrix, dtype=np.float64)[:4, :4]
+    if not isprecise:
+        return mat2quat(M[:3, :3])
+    q = np.empty(4)
+    t = np.trace(M)
+    if t > M[3, 3]:
+        q[:] = t, M[2, 1] - M[1, 2], M[0, 2] - M[2, 0], M[1, 0] - M[0, 1]
+    else:
+        i = int(np.argmax(np.diag(M)[:3]))                  # (ties go to the first, as the reference's chain of '>' does)
+        j, k = (i + 1) % 3, (i + 2) % 3
+        t = M[i, i] - (M[j, j] + M[k, k]) + M[3, 3]
+        q[i + 1], q[j + 1], q[k + 1] = t, M[i, j] + M[j, i], M[k, i] + M[i, k]
+        q[0] = M[k, j] - M[j, k]
+    q *= 0.5 / np.sqrt(t * M[3, 3])
+    if q[0] < 0.0:
+        q = -q
+    return q
+
+
 def transformation_error(trans, info):
     """ref:lib/benchmark.py computeTransformationErr: er = (t, q_xyz) of trans [4,4], p = er^T info er / info[0,0] (an
     approximation of the RMSE of the correspondences, squared)."""

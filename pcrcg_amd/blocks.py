@@ -354,6 +354,22 @@ def refuse_non_rigid(model, who):
                            % (who, name))
 
 
+def model_heads(model):
+    """The optional heads of `model` (ref:models/architectures.py:157-173), by the name of their first module."""
+    return [name for flag, name in (("node_overlap", "node_overlap_predict"), ("quaternion", "folding1 / linear1 / linear2"))
+            if getattr(model, flag, False)]
+
+
+def refuse_heads(model, who):
+    """The C++ runners sequence the trunk alone: a model with the node-overlap or the pose head goes op by op."""
+    heads = model_heads(model)
+    if heads:
+        raise RuntimeError("pcrcg_amd.%s does not sequence the %s head%s (%s): run the model through KPFCNN.forward "
+                           "(forward_ops / train_forward.forward_train) or Trainer"
+                           % (who, " and ".join("node_overlap" if h.startswith("node") else "quaternion" for h in heads),
+                              "s" if len(heads) > 1 else "", "; ".join(heads)))
+
+
 def block_decider(block_name, radius, in_dim, out_dim, layer_ind, config):
     """ref:models/blocks.py:387-430."""
     if block_name == "unary":

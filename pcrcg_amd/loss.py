@@ -188,6 +188,20 @@ class MetricLoss(torch.nn.Module):
         p["coords_dist"] = torch.sqrt(square_distance(src_pcd[p["src_sel"]][None], tgt_pcd[p["tgt_sel"]][None]).squeeze(0))
         return p
 
+    def head_losses(self, inputs):
+        """The statistics of the two optional heads (ref:lib/loss.py:166-187), the first entries of forward()'s dict: the
+        node-overlap BCE (the reference binds the second and third result of its BCE to 'recall' and 'precision' in that
+        order) and the pose loss, two summed squared errors."""
+        stats = dict()
+        if self.node_overlap:
+            loss, a, b = self.get_weighted_bce_loss(inputs["node_overlap_score_pred"], inputs["node_overlap_gt"])
+            stats["node_overlap_loss"], stats["node_overlap_recall"], stats["node_overlap_precision"] = loss, a, b
+        if self.quaternion:
+            q = F.mse_loss(inputs["quaternion_pred"], inputs["quaternion_gt"], reduction="sum")
+            t = F.mse_loss(inputs["trans_pred"], inputs["trans_gt"], reduction="sum")
+            stats["pose_loss"] = q + t
+        return stats
+
     def forward(self, inputs, prepared=None):
         """ref:lib/loss.py:139-252.  inputs: rot [3,3], trans [3,1], src_feats [N,C], tgt_feats [M,C],
         src_pcd_raw [N,3], tgt_pcd_raw [M,3], correspondences [K,2] int64, scores_overlap / scores_saliency
@@ -197,15 +211,7 @@ class MetricLoss(torch.nn.Module):
         p = prepared if prepared is not None else self.prepare(inputs)
         src_idx, tgt_idx = p["src_idx"], p["tgt_idx"]
         n_src = inputs["src_pcd_raw"].size(0)
-        stats = dict()
-
-        if self.node_overlap:
-            loss, a, b = self.get_weighted_bce_loss(inputs["node_overlap_score_pred"], inputs["node_overlap_gt"])
-            stats["node_overlap_loss"], stats["node_overlap_recall"], stats["node_overlap_precision"] = loss, a, b
-        if self.quaternion:
-            q = F.mse_loss(inputs["quaternion_pred"], inputs["quaternion_gt"], reduction="sum")
-            t = F.mse_loss(inputs["trans_pred"], inputs["trans_gt"], reduction="sum")
-            stats["pose_loss"] = q + t
+        stats = self.head_losses(inputs)
 
         # overlap BCE (:193-203)
         class_loss, cls_precision, cls_recall = self.get_weighted_bce_loss(scores_overlap, p["overlap_labels"])

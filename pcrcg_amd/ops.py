@@ -1006,3 +1006,60 @@ def feature_argmax(a, b, want_best=False):
     _lib.check(L.pcrcg_feature_argmax(a.data_ptr(), lda, n, b.data_ptr(), ldb, m, c, arg.data_ptr(), _ptr(best),
                                       ws.data_ptr(), nbytes, _stream()), "pcrcg_feature_argmax")
     return (arg, best) if want_best else arg
+
+
+POSE_HEAD_WIDTH = 1024      # the one width csrc/heads.hip serves
+POSE_HEAD_ROWS = 64         # rows per workgroup of its forward kernel (kRowsPerWg)
+
+
+def _pose_head_args(h, w_q, w_t, what):
+    h, ld_h = _rows(h, _F32, "h")
+    n, width = h.shape
+    w_q, w_t = _dev(w_q, _F32, "w_q").contiguous(), _dev(w_t, _F32, "w_t").contiguous()
+    if tuple(w_q.shape) != (4, width) or tuple(w_t.shape) != (3, width):
+        raise RuntimeError(f"pcrcg_amd.{what}: w_q must be [4, {width}] and w_t [3, {width}]")
+    nbytes = _lib.lib().pcrcg_pose_head_ws_bytes(n, width)
+    if nbytes == 0:
+        _lib.check(-1, "pcrcg_pose_head_ws_bytes")
+    return h, ld_h, n, width, w_q, w_t, nbytes, _ws.get("pose_head", nbytes, h.device)
+
+
+def pose_head(h, w_q, b_q, w_t, b_t, want_rows=False):
+    """The pose head's tail (include/pcrcg_train.h pcrcg_pose_head) on h [n, 1024] (unit inner stride, any leading dimension
+    that is a multiple of 4): u = h w_q^T + b_q, v = h w_t^T + b_t -> (quaternion_pred [4] = mean_r(u_r / |u_r|),
+    trans_pred [3] = mean_r(v_r), q_rows): two views of one [7] tensor and, with want_rows, the raw u [n, 4] for
+    pose_head_backward (else None)."""
+    L = _lib.lib()
+    h, ld_h, n, width, w_q, w_t, nbytes, ws = _pose_head_args(h, w_q, w_t, "pose_head")
+    b_q, b_t = _dev(b_q, _F32, "b_q").contiguous(), _dev(b_t, _F32, "b_t").contiguous()
+    if b_q.numel() != 4 or b_t.numel() != 3:
+        raise RuntimeError("pcrcg_amd.pose_head: b_q must have 4 entries and b_t 3")
+    out = torch.empty(7, dtype=_F32, device=h.device)
+    q_rows = torch.empty((n, 4), dtype=_F32, device=h.device) if want_rows else None
+    _lib.check(L.pcrcg_pose_head(h.data_ptr(), ld_h, n, width, w_q.data_ptr(), b_q.data_ptr(), w_t.data_ptr(), b_t.data_ptr(),
+                                 out.data_ptr(), _ptr(q_rows), ws.data_ptr(), nbytes, _stream()), "pcrcg_pose_head")
+    return out[:4], out[4:], q_rows
+
+
+def pose_head_backward(h, w_q, w_t, q_rows, g, dh=None):
+    """Gradients of pose_head (pcrcg_pose_head_backward): g [7] = dL/d(quaternion_pred, trans_pred), q_rows as the forward
+    left them -> (dh, dw_q [4, 1024], db_q [4], dw_t [3, 1024], db_t [3]).  dh: optional [n, >= 1024] output with unit inner
+    stride (only its first 1024 columns are written); a dense one is allocated when None."""
+    L = _lib.lib()
+    h, ld_h, n, width, w_q, w_t, nbytes, ws = _pose_head_args(h, w_q, w_t, "pose_head_backward")
+    q_rows = _dev(q_rows, _F32, "q_rows").contiguous()
+    g = _dev(g, _F32, "g").contiguous()
+    if tuple(q_rows.shape) != (n, 4) or g.numel() != 7:
+        raise RuntimeError("pcrcg_amd.pose_head_backward: q_rows must be [n, 4] and g must have 7 entries")
+    if dh is None:
+        dh = torch.empty((n, width), dtype=_F32, device=h.device)
+    dh_, ld_dh = _rows(dh, _F32, "dh")
+    if dh_.data_ptr() != dh.data_ptr() or dh.shape[0] != n or dh.shape[1] < width:
+        raise RuntimeError("pcrcg_amd.pose_head_backward: `dh` must be [n, >= width] with unit inner stride")
+    dw_q = torch.empty((4, width), dtype=_F32, device=h.device)
+    dw_t = torch.empty((3, width), dtype=_F32, device=h.device)
+    db = torch.empty(7, dtype=_F32, device=h.device)
+    _lib.check(L.pcrcg_pose_head_backward(h.data_ptr(), ld_h, n, width, w_q.data_ptr(), w_t.data_ptr(), q_rows.data_ptr(),
+                                          g.data_ptr(), dh.data_ptr(), ld_dh, dw_q.data_ptr(), db.data_ptr(), dw_t.data_ptr(),
+                                          db[4:].data_ptr(), ws.data_ptr(), nbytes, _stream()), "pcrcg_pose_head_backward")
+    return dh, dw_q, db[:4], dw_t, db[4:]

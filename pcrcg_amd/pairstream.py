@@ -40,7 +40,7 @@ import time
 
 import torch
 
-from .blocks import refuse_non_rigid
+from .blocks import refuse_heads, refuse_non_rigid
 from .pyramid import NativePyramid, check_tie_status
 
 
@@ -90,6 +90,7 @@ class PairStreams:
         self.net, self.config, self.limits = net, config, neighborhood_limits
         self.device = torch.device(device if device is not None else "cuda")
         refuse_non_rigid(net, "PairStreams")
+        refuse_heads(net, "PairStreams")
         if not getattr(net, "use_runner", False):
             raise RuntimeError("pcrcg_amd.PairStreams needs the C++ runner path (use_batch_norm=True)")
         self.runner = net.runner()

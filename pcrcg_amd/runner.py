@@ -16,7 +16,7 @@ import torch
 
 from . import _lib
 from .blocks import (LastUnaryBlock, NearestUpsampleBlock, ResnetBottleneckBlock, SimpleBlock, UnaryBlock,
-                     aligned_weight, refuse_non_rigid)
+                     aligned_weight, refuse_heads, refuse_non_rigid)
 from .gcn import AttentionalPropagation, SelfAttention
 
 MAX_LEVELS, MAX_BLOCKS, MAX_GNN = 8, 32, 8
@@ -94,6 +94,7 @@ class Runner:
 
     def __init__(self, model):
         refuse_non_rigid(model, "runner.Runner")
+        refuse_heads(model, "runner.Runner")
         self.model = model
         self.sig = None
         self.desc = None

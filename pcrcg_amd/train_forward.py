@@ -196,6 +196,10 @@ def forward_train(net, batch, dx="scatter", transposes=None):
     feats_c = _conv1x1(net.proj_gnn, torch.cat([src_f, tgt_f], 0))
     scores_c = _conv1x1(net.proj_score, feats_c)                        # [N, 1]
     feats_norm = F.normalize(feats_c, p=2, dim=1)
+    res = {}
+    if getattr(net, "node_overlap", False):                             # :546-552: its gradient reaches the GNN through feats_c
+        node = _conv1x1(net.node_overlap_predict, feats_c)
+        res["node_overlap_score_pred"] = torch.clamp(torch.sigmoid(node.view(-1)), min=0, max=1)
 
     src_n, tgt_n = feats_norm[:len_src_c], feats_norm[len_src_c:]
     inner = AG.matmul(src_n.contiguous(), tgt_n.contiguous().t())
@@ -214,4 +218,12 @@ def forward_train(net, batch, dx="scatter", transposes=None):
     feats_f = F.normalize(x[:, :fd], p=2, dim=1)
     scores_overlap = net.regular_score(torch.clamp(torch.sigmoid(x[:, fd].view(-1)), min=0, max=1))
     scores_saliency = net.regular_score(torch.clamp(torch.sigmoid(x[:, fd + 1].view(-1)), min=0, max=1))
-    return {"feats_f": feats_f, "scores_overlap": scores_overlap, "scores_saliency": scores_saliency}
+    if getattr(net, "quaternion", False):                               # :584-596: the pose loss reaches the decoder through feats_f
+        temp = feats_f
+        for layer in net.folding1:
+            if isinstance(layer, nn.Linear):
+                temp = F.relu(AG.linear(temp, layer.weight, layer.bias))
+        res["quaternion_pred"], res["trans_pred"] = AG.pose_head(temp, net.linear1.weight, net.linear1.bias, net.linear2.weight,
+                                                                 net.linear2.bias)
+    res.update({"feats_f": feats_f, "scores_overlap": scores_overlap, "scores_saliency": scores_saliency})
+    return res

@@ -16,7 +16,7 @@ import torch
 
 from . import _lib
 from .blocks import (LastUnaryBlock, NearestUpsampleBlock, ResnetBottleneckBlock, SimpleBlock, UnaryBlock,
-                     refuse_non_rigid)
+                     refuse_heads, refuse_non_rigid)
 from .gcn import AttentionalPropagation, SelfAttention
 from .runner import (BLK_LAST_UNARY, BLK_RESNETB, BLK_SIMPLE, BLK_UNARY, BLK_UPSAMPLE, MAX_BLOCKS, MAX_GNN, Model, Runner)
 
@@ -63,6 +63,7 @@ def _grad(p):
 class TrainRunner:
     def __init__(self, model):
         refuse_non_rigid(model, "train_runner.TrainRunner")
+        refuse_heads(model, "train_runner.TrainRunner")
         self.model = model
         self.ws = None                            # cached workspace (values | gradients | scratch of one step)
         self._lent = None                         # ... while a tape that lives in it is outstanding

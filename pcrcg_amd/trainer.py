@@ -425,6 +425,16 @@ class Trainer:
                 "src_pcd_raw": inputs["src_pcd_raw"], "tgt_pcd_raw": inputs["tgt_pcd_raw"],
                 "correspondences": inputs["correspondences"],
             }
+            # the optional heads, in every phase (ref:lib/trainer.py:241-253,288-300); the flags are the model's
+            if getattr(self.model, "node_overlap", False):
+                loss_input["node_overlap_gt"] = inputs["node_overlap_gt"].float()
+                loss_input["node_overlap_score_pred"] = output["node_overlap_score_pred"]
+            if getattr(self.model, "quaternion", False):
+                from .benchmark import quaternion_from_matrix
+                rot64 = inputs["rot"].detach().cpu().numpy().astype("float64")   # (the reference hands numpy the fp32 matrix)
+                loss_input["quaternion_pred"] = output["quaternion_pred"]
+                loss_input["quaternion_gt"] = torch.from_numpy(quaternion_from_matrix(rot64)).float().to(feats.device)
+                loss_input["trans_pred"], loss_input["trans_gt"] = output["trans_pred"], inputs["trans"].squeeze()
             res = self.desc_loss(loss_input, prepared=prepared) if prepared is not None else self.desc_loss(loss_input)
             if train:
                 c_loss = sum(res[k] for k in res if k in LOSS_KEYS)
