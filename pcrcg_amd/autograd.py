@@ -86,26 +86,13 @@ def linear(x, weight, bias=None):
 class _KPConv(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weights, q_pts, s_pts, idx, kp, extent, transposed=None):
-        L = _lib.lib()
-        x = _c(x)
-        q_pts, s_pts, kp = _c(q_pts), _c(s_pts), _c(kp)
-        idx2, ld_idx = ops._rows(idx, torch.int64, "neighb_inds")
-        nq, h = idx2.shape
-        ns, cin = x.shape
-        kdim = kp.shape[0]
-        ctx.transposed = _checked_transpose(transposed, nq, ns, "kpconv")
-        wf = torch.empty((nq, kdim * cin), dtype=_F32, device=x.device)
-        inv_n = torch.empty(nq, dtype=_F32, device=x.device)
-        nbytes = L.pcrcg_kpconv_ws_bytes(ns)
-        ws = ops._ws.get("kpconv", nbytes, x.device)
-        _lib.check(L.pcrcg_kpconv_aggregate(q_pts.data_ptr(), nq, s_pts.data_ptr(), ns, idx2.data_ptr(), h, ld_idx,
-                                            x.data_ptr(), cin, kp.data_ptr(), float(extent), wf.data_ptr(),
-                                            inv_n.data_ptr(), ws.data_ptr(), nbytes, ops._stream()),
-                   "pcrcg_kpconv_aggregate")
-        w2 = weights.reshape(kdim * cin, -1)
-        ctx.save_for_backward(wf, inv_n, w2, q_pts, s_pts, idx2, kp)
-        ctx.meta = (float(extent), ns, cin, ld_idx, tuple(weights.shape))
-        return ops.gemm(wf, w2, row_scale=inv_n)
+        a = ops._kpconv_args("autograd.kpconv", q_pts, s_pts, idx, x, kp, dev=False, k15=False, pad=False)
+        ctx.transposed = _checked_transpose(transposed, a.nq, a.ns, "kpconv")
+        ops._kpconv_gather(a, extent)
+        w2 = weights.reshape(a.kdim * a.cin, -1)
+        ctx.save_for_backward(a.wf, a.inv_n, w2, a.q_pts, a.s_pts, a.idx, a.kp)
+        ctx.meta = (float(extent), a.ns, a.cin, a.ld_idx, tuple(weights.shape))
+        return ops.gemm(a.wf, w2, row_scale=a.inv_n)
 
     @staticmethod
     def backward(ctx, dy):
@@ -149,46 +136,18 @@ def kpconv(x, weights, q_pts, s_pts, idx, kernel_points, extent, transposed=None
 class _KPConvEx(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weights, offset_features, q_pts, s_pts, idx, kp, extent, influence, aggregation, modulated):
-        L = _lib.lib()
-        x = _c(x)
-        q_pts, s_pts, kp = _c(q_pts), _c(s_pts), _c(kp)
-        idx2, ld_idx = ops._rows(idx, torch.int64, "neighb_inds")
-        nq, h = idx2.shape
-        ns, cin0 = x.shape
-        kdim = kp.shape[0]
-        if kdim != 15:
-            raise RuntimeError("pcrcg_amd.autograd.kpconv_ex: only 15 kernel points are supported")
-        cols = (4 if modulated else 3) * kdim
-        off, ld_off = None, 0
-        if offset_features is not None:
-            off, ld_off = ops._rows(offset_features, _F32, "offset_features")
-            if off.shape[0] != nq or off.shape[1] < cols:
-                raise RuntimeError("pcrcg_amd.autograd.kpconv_ex: offset_features must be [nq, 3K] ([nq, 4K] when modulated)")
-        elif modulated:
-            raise RuntimeError("pcrcg_amd.autograd.kpconv_ex: modulated needs offset_features")
-        pad = (-cin0) % 4 if cin0 > 4 else 0     # as ops.kpconv_ex: zero channels change neither the sums nor n_q
-        w3 = weights
-        if pad:
-            x = torch.nn.functional.pad(x, (0, pad))
-            w3 = torch.nn.functional.pad(weights, (0, 0, 0, pad))
-        cin = cin0 + pad
-        wf = torch.empty((nq, kdim * cin), dtype=_F32, device=x.device)
-        inv_n = torch.empty(nq, dtype=_F32, device=x.device)
-        min_d2 = torch.empty((nq, kdim), dtype=_F32, device=x.device)
-        nbytes = L.pcrcg_kpconv_ws_bytes(ns)
-        ws = ops._ws.get("kpconv", nbytes, x.device)
+        cin0 = x.shape[1]
+        a = ops._kpconv_args("autograd.kpconv_ex", q_pts, s_pts, idx, x, kp, offset_features, modulated, dev=False,
+                             want_min_d2=True)
         mode = (ops._INFLUENCE[influence], int(aggregation == "closest"), int(bool(modulated)))
-        _lib.check(L.pcrcg_kpconv_aggregate_ex(q_pts.data_ptr(), nq, s_pts.data_ptr(), ns, idx2.data_ptr(), h, ld_idx,
-                                               x.data_ptr(), cin, kp.data_ptr(), float(extent), ops._ptr(off), ld_off,
-                                               *mode, wf.data_ptr(), inv_n.data_ptr(), min_d2.data_ptr(), ws.data_ptr(),
-                                               nbytes, ops._stream()), "pcrcg_kpconv_aggregate_ex")
-        w2 = _c(w3).reshape(kdim * cin, -1)
-        ctx.save_for_backward(wf, inv_n, w2, q_pts, s_pts, idx2, kp, x, off)
-        ctx.meta = (float(extent), ns, cin0, cin, ld_idx, ld_off, cols, mode, tuple(weights.shape),
+        ops._kpconv_gather(a, extent, ex=mode)
+        w2 = _c(ops._pad_cin(weights, a.pad)).reshape(a.kdim * a.cin, -1)
+        ctx.save_for_backward(a.wf, a.inv_n, w2, a.q_pts, a.s_pts, a.idx, a.kp, a.x, a.off)
+        ctx.meta = (float(extent), a.ns, cin0, a.cin, a.ld_idx, a.ld_off, a.cols, mode, tuple(weights.shape),
                     None if offset_features is None else tuple(offset_features.shape))
-        out = ops.gemm(wf, w2, row_scale=inv_n)
-        ctx.mark_non_differentiable(min_d2)
-        return out, min_d2
+        out = ops.gemm(a.wf, w2, row_scale=a.inv_n)
+        ctx.mark_non_differentiable(a.min_d2)
+        return out, a.min_d2
 
     @staticmethod
     def backward(ctx, dy, _d_min):

@@ -50,8 +50,6 @@ size_t colstats_ws_bytes(int c);
 int colstats_finalize(const double* partial, int nchunks, int c, double count, float eps, float* stats,
                       hipStream_t st);
 int colstats_chunks();
-// kpconv.hip: where the support records live inside a pcrcg_kpconv_ws_bytes(ns) workspace
-float4* kpconv_pk_ptr(void* ws, size_t ws_bytes, int ns);
 
 // The deterministic debug mode's scratch: one device buffer per stream, kept until pcrcg_debug_release() (scan.hip) frees
 // those of every instance.  An instance is a namespace-scope object of the file that uses it (gemm_x6.hip: the split-K
@@ -70,26 +68,6 @@ private:
     std::mutex mu_;
     std::map<hipStream_t, Buf> bufs_;
 };
-
-// kpconv.hip: row-positive flags + packed (x, y, z, flag) support records into a pcrcg_kpconv_ws_bytes(ns) workspace
-// (x_bf16 != NULL: also the bf16 round-to-nearest-even copy of x, [ns, cin])
-int kpconv_pack(const float* x, int ns, int cin, const float* s_pts, void* ws, size_t ws_bytes, hipStream_t st,
-                unsigned short* x_bf16 = nullptr);
-int kpconv_aggregate_rows(const float* q_pts, int nq, const float* s_pts, int ns, const int64_t* idx, int h, int ld_idx,
-                          const float* x, int cin, const float* kp, float extent, float* wf, float* inv_n, void* ws,
-                          size_t ws_bytes, hipStream_t st, bool pack, bool stream_out, int c1_ld = 0,   // c1_ld = 16: cin = 1 with wf rows of 16 floats (15 + a zero)
-                          const int* walk = nullptr);      // walk: the queries' processing order (walk.hip), NULL: index order
-// the first layer (cin = 1, features x [ns]) in ONE kernel: y [nq, cout] = (wf @ wt^T) / n_q against the K-contiguous weights
-// wt [cout, 16], inv_n as kpconv_aggregate_rows leaves it, and the column sums / sums of squares of y ADDED to the zeroed
-// sums [2][cout] f64.  _ok: the widths and outputs it serves (everything else keeps gather + product).
-bool kpconv_c1_fused_ok(int cout, const float* wt);
-int kpconv_c1_fused(const float* q_pts, int nq, const float* s_pts, int ns, const int64_t* idx, int h, int ld_idx, const float* x,
-                    const float* kp, float extent, const float* wt, int cout, float* y, int ld_y, float* inv_n, double* sums,
-                    void* ws, size_t ws_bytes, hipStream_t st, bool pack);
-int kpconv_aggregate_bf16(const float* q_pts, int nq, const float* s_pts, int ns, const int64_t* idx, int h, int ld_idx,
-                          const float* x, unsigned short* x_bf16, int cin, const float* kp, float extent,
-                          unsigned short* wf_bf16, float* inv_n, void* ws, size_t ws_bytes, hipStream_t st,
-                          const int* walk = nullptr);
 
 // walk.hip: walk[g] = the n[g] query indices of cloud g sorted by the 12-bit Morton key of their cell in a 16^3 grid over
 // the cloud's bounding box (a permutation; the order inside a cell is arbitrary), for up to four clouds in one launch.
@@ -171,7 +149,7 @@ struct DebugOpts {
 };
 const DebugOpts& debug_opts();
 
-// Optional start / stop events of a KPConv kernel (bench.py roofline); see pcrcg_profile_kpconv in
+// prof.hip.  Optional start / stop events of a KPConv kernel (bench.py roofline); see pcrcg_profile_kpconv in
 // include/pcrcg.h.  The events are handed to hipExtLaunchKernelGGL, so they stamp the kernel's own begin and
 // end (what rocprofv3 reports), not the time its dispatch waited behind other streams.  a/b are NULL when
 // profiling is off (a plain launch).  kind 0 = gather/aggregate kernel, 1 = fused kernel, 2 = bf16-storage gather kernel,

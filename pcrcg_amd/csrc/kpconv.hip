@@ -22,34 +22,17 @@
 //
 // Fallbacks: k_kpconv_c1 for Cin == 1 (first layer, features are a column of ones; four lanes per query), and the scalar
 // k_kpconv_generic for channel counts that are not a multiple of 4.
-#include <mutex>
-#include <vector>
-
+//
+// Host side (kpconv.h): one descriptor, KpconvCall, and one entry, kpconv_run, for the fp32 gather, its bf16-storage form
+// and the one-kernel first layer: it checks the call, carves the workspace (kpconv_ws), packs the support records if asked,
+// plans (kpconv_plan) and launches.  Every C entry of the gather is in this file, the _walk ones included, and only fills a
+// KpconvCall; so do the forward runner (runner.hip) and the transposed backward (transpose.hip).  wf is stored non-temporally
+// in every form: it is streamed once through HBM and read back by the contraction.
 #include <hip/hip_ext.h>
 
-#include "common.h"
+#include "kpconv.h"
 
 namespace pcrcg {
-
-// optional HIP-event timing of every KPConv launch (bench.py roofline)
-struct ProfRec { hipEvent_t a, b; int nq, h, cin, cout, kind; };
-static int g_prof_on = 0;         // bit 0: KPConv kernels (kinds 0-2), bit 1: the GEMM family (kind 3)
-static std::vector<ProfRec> g_prof;
-static std::mutex g_prof_mu;   // forwards may be enqueued from several host threads
-
-KpProfScope::KpProfScope(hipStream_t s, int nq_, int h_, int cin_, int cout_, int kind_)
-    : st(s), a(nullptr), b(nullptr), nq(nq_), h(h_), cin(cin_), cout(cout_), kind(kind_),
-      on((g_prof_on & (kind_ == 3 ? 2 : kind_ == 4 ? 4 : 1)) != 0) {
-    if (!on) return;
-    (void)hipEventCreate(&a);
-    (void)hipEventCreate(&b);
-}
-KpProfScope::~KpProfScope() {
-    if (!on) return;
-    std::lock_guard<std::mutex> lock(g_prof_mu);
-    g_prof.push_back({a, b, nq, h, cin, cout, kind});
-}
-
 namespace {
 
 constexpr int K = PCRCG_KPOINTS;
@@ -109,7 +92,7 @@ __device__ __forceinline__ float4 load4(const unsigned short* p) {
 // the shuffles and the 15 square roots for four channels: what the plain plan gave this width) but rides along on the vector
 // units: every lane multiplies its influence weight with its neighbour's last float4 (the 16 lanes of a neighbour read one
 // address), the four neighbour groups meet by two shuffles at the end.
-template <int NB, bool NT_STORE, typename FT, bool TAIL = false>  // 64-channel blocks handled per wavefront (one float4 per lane and block)
+template <int NB, typename FT, bool TAIL = false>  // 64-channel blocks handled per wavefront (one float4 per lane and block)
 __global__ void __launch_bounds__(kWavesPerBlock * 64) k_kpconv_mfma(
     const float* __restrict__ q_pts, int nq, const float* __restrict__ s_pts, int ns,
     const long long* __restrict__ idx, int H, int ld_idx, const FT* __restrict__ x, int cin,
@@ -254,8 +237,7 @@ __global__ void __launch_bounds__(kWavesPerBlock * 64) k_kpconv_mfma(
                     } else {
                         typedef float v4f __attribute__((ext_vector_type(4)));
                         const v4f val = {acc[b][0][r], acc[b][1][r], acc[b][2][r], acc[b][3][r]};
-                        if (NT_STORE) __builtin_nontemporal_store(val, reinterpret_cast<v4f*>(o + (long)k * cin + c));
-                        else *reinterpret_cast<v4f*>(o + (long)k * cin + c) = val;
+                        __builtin_nontemporal_store(val, reinterpret_cast<v4f*>(o + (long)k * cin + c));
                     }
                 }
             }
@@ -267,8 +249,7 @@ __global__ void __launch_bounds__(kWavesPerBlock * 64) k_kpconv_mfma(
                 typedef float v4f __attribute__((ext_vector_type(4)));
                 const v4f val = {ta0, ta1, ta2, ta3};
                 v4f* dst = reinterpret_cast<v4f*>(reinterpret_cast<float*>(wf) + (long)q * K * cin + (long)j * cin + 64 * NB);
-                if (NT_STORE) __builtin_nontemporal_store(val, dst);
-                else *dst = val;
+                __builtin_nontemporal_store(val, dst);
             }
         }
         if (chunk == 0 && lane == 0) inv_n[q] = 1.0f / (float)(npos > 1 ? npos : 1);
@@ -492,21 +473,78 @@ __global__ void __launch_bounds__(kWavesPerBlock * 64) k_kpconv_generic(
 
 }  // namespace
 
-float4* kpconv_pk_ptr(void* ws, size_t ws_bytes, int ns) {
+int kpconv_ws(void* ws, size_t ws_bytes, int ns, KpWs* out) {
     Carver cv(ws, ws_bytes);
-    cv.take<unsigned char>((size_t)ns + 1);
-    float4* pk = cv.take<float4>((size_t)ns + 1);
-    return cv.ok() ? pk : nullptr;
+    out->pos = cv.take<unsigned char>((size_t)ns + 1);
+    out->pk = cv.take<float4>((size_t)ns + 1);
+    PCRCG_CHECK_WS(cv);
+    return PCRCG_OK;
 }
 
-// pos / pk records of `x` (see k_row_positive) into the workspace layout of pcrcg_kpconv_ws_bytes
-int kpconv_pack(const float* x, int ns, int cin, const float* s_pts, void* ws, size_t ws_bytes, hipStream_t st,
-                unsigned short* x_bf16) {
-    Carver cv(ws, ws_bytes);
-    unsigned char* pos = cv.take<unsigned char>((size_t)ns + 1);
-    float4* pk = cv.take<float4>((size_t)ns + 1);
-    PCRCG_CHECK_WS(cv);
-    if (ns > 0) hipLaunchKernelGGL(k_row_positive, dim3((ns + 3) / 4), dim3(256), 0, st, x, ns, cin, s_pts, pos, pk, x_bf16);
+int kpconv_pack(const float* x, int ns, int cin, const float* s_pts, const KpWs& w, hipStream_t st, unsigned short* x_bf16) {
+    if (ns > 0) hipLaunchKernelGGL(k_row_positive, dim3((ns + 3) / 4), dim3(256), 0, st, x, ns, cin, s_pts, w.pos, w.pk, x_bf16);
+    PCRCG_CHECK_LAUNCH();
+    return PCRCG_OK;
+}
+
+// widths of whole float4s, and weight rows a lane can read as four
+bool kpconv_c1_fused_ok(int cout, const float* wt) { return cout >= 4 && cout % 4 == 0 && wt && (reinterpret_cast<uintptr_t>(wt) & 15) == 0; }
+
+int kpconv_run(const KpconvCall& c) {
+    const bool bf16 = c.form == KpForm::bf16, fused = c.form == KpForm::c1_fused;
+    const int nq = c.nq, ns = c.ns, h = c.h, cin = fused ? 1 : c.cin;
+    // everything that is refused for an empty call as well (the forms differ: tests/test_kpconv_args_cpu.py)
+    PCRCG_CHECK_ARG(nq >= 0 && ns >= 0 && h >= 1 && c.ld_idx >= h && cin >= 1 && c.extent > 0.0f);
+    if (bf16) PCRCG_CHECK_ARG(ns >= 1 && cin % 4 == 0);
+    else if (fused) PCRCG_CHECK_ARG(kpconv_c1_fused_ok(c.cout, c.wt) && c.ld_y >= c.cout);
+    else PCRCG_CHECK_ARG(c.c1_ld == 0 || c.c1_ld == K || c.c1_ld == K + 1);
+    if (nq == 0) return PCRCG_OK;
+    PCRCG_CHECK_ARG(c.q_pts && c.s_pts && c.idx && c.x && c.kp && c.inv_n && c.ws && ns >= 1);
+    if (bf16)
+        PCRCG_CHECK_ARG(c.x_bf16 && c.wf_bf16 && (reinterpret_cast<uintptr_t>(c.x_bf16) & 7) == 0 &&
+                        (reinterpret_cast<uintptr_t>(c.wf_bf16) & 7) == 0);
+    else if (fused) PCRCG_CHECK_ARG(c.y && c.sums);
+    else PCRCG_CHECK_ARG(c.wf);
+    KpWs w;
+    PCRCG_PROPAGATE(kpconv_ws(c.ws, c.ws_bytes, ns, &w));
+    const long long* idx_ll = reinterpret_cast<const long long*>(c.idx);
+    if (cin == 1) {
+        if (c.pack) hipLaunchKernelGGL(k_pack_c1, dim3((ns + 255) / 256), dim3(256), 0, c.st, c.x, ns, c.s_pts, w.pk);
+    } else if (c.pack) {
+        PCRCG_PROPAGATE(kpconv_pack(c.x, ns, cin, c.s_pts, w, c.st, bf16 ? c.x_bf16 : nullptr));
+    }
+    // start / stop events of the gather kernel itself; kind 1: the one-kernel layer, 2: bf16 storage
+    KpProfScope prof(c.st, nq, h, cin, fused ? c.cout : 0, fused ? 1 : bf16 ? 2 : 0);
+    const dim3 c1_grid((int)(((long)nq * C1_PARTS + 255) / 256));
+    if (fused) {
+        hipExtLaunchKernelGGL(k_kpconv_c1_fused, c1_grid, dim3(256), 0, c.st, prof.a, prof.b, 0, c.q_pts, nq, ns, idx_ll, h,
+                              c.ld_idx, (const float4*)w.pk, c.kp, c.extent, c.wt, c.cout, c.y, c.ld_y, c.inv_n, c.sums);
+    } else if (cin == 1) {
+        hipExtLaunchKernelGGL(k_kpconv_c1, c1_grid, dim3(256), 0, c.st, prof.a, prof.b, 0, c.q_pts, nq, c.s_pts, ns, idx_ll, h,
+                              c.ld_idx, (const float4*)w.pk, c.kp, c.extent, c.wf, c.inv_n, c.c1_ld > 0 ? c.c1_ld : K);
+    } else if (!bf16 && !kpconv_vec_ok(cin, c.x, c.wf)) {
+        hipLaunchKernelGGL(k_kpconv_generic, dim3(kpconv_blocks(nq)), dim3(kWavesPerBlock * 64), 0, c.st, c.q_pts, nq, c.s_pts,
+                           ns, idx_ll, h, c.ld_idx, c.x, cin, c.kp, c.extent, (const unsigned char*)w.pos, c.wf, c.inv_n);
+    } else {
+        const KpPlan p = kpconv_plan(nq, cin, c.walk != nullptr, !bf16);
+#define LAUNCH(NBV, FT, TAILV, X, WF)                                                                                          \
+        hipExtLaunchKernelGGL((k_kpconv_mfma<NBV, FT, TAILV>), dim3(p.blocks), dim3(kWavesPerBlock * 64), 0, c.st, prof.a,    \
+                              prof.b, 0, c.q_pts, nq, c.s_pts, ns, idx_ll, h, c.ld_idx, X, cin, c.kp, c.extent,               \
+                              (const float4*)w.pk, WF, c.inv_n, p.nchunk, c.walk)
+        if (bf16) {
+            if (p.nb == 4) LAUNCH(4, unsigned short, false, c.x_bf16, c.wf_bf16);
+            else if (p.nb == 2) LAUNCH(2, unsigned short, false, c.x_bf16, c.wf_bf16);
+            else LAUNCH(1, unsigned short, false, c.x_bf16, c.wf_bf16);
+        } else if (p.tail) {
+            if (p.nb == 2) LAUNCH(2, float, true, c.x, c.wf);
+            else LAUNCH(1, float, true, c.x, c.wf);
+        } else {
+            if (p.nb == 4) LAUNCH(4, float, false, c.x, c.wf);
+            else if (p.nb == 2) LAUNCH(2, float, false, c.x, c.wf);
+            else LAUNCH(1, float, false, c.x, c.wf);
+        }
+#undef LAUNCH
+    }
     PCRCG_CHECK_LAUNCH();
     return PCRCG_OK;
 }
@@ -515,208 +553,71 @@ int kpconv_pack(const float* x, int ns, int cin, const float* s_pts, void* ws, s
 
 using namespace pcrcg;
 
+// what every C entry of the gather passes on as it got it
+static KpconvCall entry_call(const float* q_pts, int nq, const float* s_pts, int ns, const int64_t* idx, int h, int ld_idx,
+                             const float* x, int cin, const float* kp, float extent, float* inv_n, void* ws, size_t ws_bytes,
+                             const int* walk, void* stream) {
+    KpconvCall c;
+    c.q_pts = q_pts; c.nq = nq; c.s_pts = s_pts; c.ns = ns;
+    c.idx = idx; c.h = h; c.ld_idx = ld_idx;
+    c.x = x; c.cin = cin; c.kp = kp; c.extent = extent;
+    c.inv_n = inv_n; c.ws = ws; c.ws_bytes = ws_bytes;
+    c.walk = walk; c.st = as_stream(stream);
+    return c;
+}
+
 extern "C" {
-
-void pcrcg_profile_kpconv(int enable) {
-    std::lock_guard<std::mutex> lock(g_prof_mu);
-    for (auto& r : g_prof) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
-    g_prof.clear();
-    g_prof_on = enable;
-}
-
-int pcrcg_profile_kpconv_read(float* ms, int* nq, int* h, int* cin, int* cout, int* kind, int cap) {
-    std::lock_guard<std::mutex> lock(g_prof_mu);
-    int n = 0;
-    for (auto& r : g_prof) {
-        if (n >= cap) break;
-        if (hipEventSynchronize(r.b) != hipSuccess) return -1;
-        float t = 0.f;
-        if (hipEventElapsedTime(&t, r.a, r.b) != hipSuccess) return -1;
-        ms[n] = t; nq[n] = r.nq; h[n] = r.h; cin[n] = r.cin; cout[n] = r.cout; kind[n] = r.kind;
-        ++n;
-    }
-    return n;
-}
 
 size_t pcrcg_kpconv_ws_bytes(int ns) {
     const size_t n = (size_t)(ns > 0 ? ns : 0) + 1;
     return carve_bytes(n, 1) + carve_bytes(n, sizeof(float4));     // row-positive flags + packed (x, y, z, flag) records
 }
 
-int pcrcg_kpconv_aggregate(const float* q_pts, int nq, const float* s_pts, int ns, const int64_t* idx,
-                           int h, int ld_idx, const float* x, int cin, const float* kp, float extent,
-                           float* wf, float* inv_n, void* ws, size_t ws_bytes, void* stream) {
-    return kpconv_aggregate_rows(q_pts, nq, s_pts, ns, idx, h, ld_idx, x, cin, kp, extent, wf, inv_n, ws, ws_bytes,
-                                 as_stream(stream), true, true, 0);
+// the _walk entries: the queries' order given -- what the forward runner launches, for tests and A/B timing
+int pcrcg_kpconv_aggregate_walk(const float* q_pts, int nq, const float* s_pts, int ns, const int64_t* idx, int h, int ld_idx,
+                                const float* x, int cin, const float* kp, float extent, float* wf, float* inv_n, void* ws,
+                                size_t ws_bytes, const int* walk, void* stream) {
+    KpconvCall c = entry_call(q_pts, nq, s_pts, ns, idx, h, ld_idx, x, cin, kp, extent, inv_n, ws, ws_bytes, walk, stream);
+    c.wf = wf;
+    return kpconv_run(c);
 }
 
-// The bf16 feature-storage variant of pcrcg_kpconv_aggregate: x stays fp32 at the boundary; `x_bf16` ([ns, cin] u16
+int pcrcg_kpconv_aggregate(const float* q_pts, int nq, const float* s_pts, int ns, const int64_t* idx, int h, int ld_idx,
+                           const float* x, int cin, const float* kp, float extent, float* wf, float* inv_n, void* ws,
+                           size_t ws_bytes, void* stream) {
+    return pcrcg_kpconv_aggregate_walk(q_pts, nq, s_pts, ns, idx, h, ld_idx, x, cin, kp, extent, wf, inv_n, ws, ws_bytes, nullptr,
+                                       stream);
+}
+
+// The bf16 feature-storage variant of pcrcg_kpconv_aggregate: x stays fp32 at the boundary (the support-record prelude reads
+// it: the n_q normaliser counts rows with a positive fp32 sum, exactly as the fp32 path does); `x_bf16` ([ns, cin] u16
 // scratch) receives its round-to-nearest-even copy, which is what the neighbour gathers read, and `wf_bf16`
 // ([nq, 15*cin] u16) the aggregated features rounded the same way.  Geometry, influences, the neighbour-count
 // normaliser and the accumulation are fp32 as in the fp32 path.
+int pcrcg_kpconv_aggregate_bf16_walk(const float* q_pts, int nq, const float* s_pts, int ns, const int64_t* idx, int h,
+                                     int ld_idx, const float* x, int cin, const float* kp, float extent, void* x_bf16,
+                                     void* wf_bf16, float* inv_n, void* ws, size_t ws_bytes, const int* walk, void* stream) {
+    KpconvCall c = entry_call(q_pts, nq, s_pts, ns, idx, h, ld_idx, x, cin, kp, extent, inv_n, ws, ws_bytes, walk, stream);
+    c.form = KpForm::bf16;
+    c.x_bf16 = static_cast<unsigned short*>(x_bf16);
+    c.wf_bf16 = static_cast<unsigned short*>(wf_bf16);
+    return kpconv_run(c);
+}
+
 int pcrcg_kpconv_aggregate_bf16(const float* q_pts, int nq, const float* s_pts, int ns, const int64_t* idx, int h,
                                 int ld_idx, const float* x, int cin, const float* kp, float extent, void* x_bf16,
                                 void* wf_bf16, float* inv_n, void* ws, size_t ws_bytes, void* stream) {
-    return kpconv_aggregate_bf16(q_pts, nq, s_pts, ns, idx, h, ld_idx, x, static_cast<unsigned short*>(x_bf16), cin, kp,
-                                 extent, static_cast<unsigned short*>(wf_bf16), inv_n, ws, ws_bytes, as_stream(stream));
-}
-}
-
-namespace pcrcg {
-
-// pcrcg_kpconv_aggregate for a slice of the queries; `pack` = (re)build the support records in `ws` first (once per
-// layer), `stream_out` = non-temporal wf stores (the whole layer's wf is streamed once through HBM) or plain stores
-// (a row chunk whose wf the contraction reads back from L2 / Infinity Cache right away)
-int kpconv_aggregate_rows(const float* q_pts, int nq, const float* s_pts, int ns, const int64_t* idx, int h, int ld_idx,
-                          const float* x, int cin, const float* kp, float extent, float* wf, float* inv_n, void* ws,
-                          size_t ws_bytes, hipStream_t st, bool pack, bool stream_out, int c1_ld, const int* walk) {
-    PCRCG_CHECK_ARG(nq >= 0 && ns >= 0 && h >= 1 && ld_idx >= h && cin >= 1 && (c1_ld == 0 || c1_ld == K || c1_ld == K + 1));
-    PCRCG_CHECK_ARG(extent > 0.0f);
-    if (nq == 0) return PCRCG_OK;
-    PCRCG_CHECK_ARG(q_pts && s_pts && idx && x && kp && wf && inv_n && ws);
-    PCRCG_CHECK_ARG(ns >= 1);
-    Carver cv(ws, ws_bytes);
-    unsigned char* pos = cv.take<unsigned char>((size_t)ns + 1);
-    float4* pk = cv.take<float4>((size_t)ns + 1);
-    PCRCG_CHECK_WS(cv);
-    const long long* idx_ll = reinterpret_cast<const long long*>(idx);
-    const int max_blocks = 256 * 32;
-    auto blocks_for = [&](long waves) {
-        long b = (waves + kWavesPerBlock - 1) / kWavesPerBlock;
-        return (int)(b > max_blocks ? max_blocks : b);
-    };
-    // with a walk: eight XCD ranges of at most ceil(nq / 8) queries each, the same number of workgroups for every range
-    auto blocks_walk = [&](int nchunk) {
-        const int b = blocks_for((long)((nq + 7) / 8) * nchunk);
-        return 8 * (b > max_blocks / 8 ? max_blocks / 8 : b);
-    };
-    if (cin == 1) {
-        if (pack) hipLaunchKernelGGL(k_pack_c1, dim3((ns + 255) / 256), dim3(256), 0, st, x, ns, s_pts, pk);
-        KpProfScope prof_scope(st, nq, h, cin, 0, 0);
-        hipExtLaunchKernelGGL(k_kpconv_c1, dim3((int)(((long)nq * C1_PARTS + 255) / 256)), dim3(256), 0, st, prof_scope.a,
-                              prof_scope.b, 0, q_pts, nq, s_pts, ns, idx_ll, h, ld_idx, (const float4*)pk, kp, extent, wf,
-                              inv_n, c1_ld > 0 ? c1_ld : K);
-        PCRCG_CHECK_LAUNCH();
-        return PCRCG_OK;
-    }
-    if (pack && ns > 0)
-        hipLaunchKernelGGL(k_row_positive, dim3((ns + 3) / 4), dim3(256), 0, st, x, ns, cin, s_pts, pos, pk,
-                           (unsigned short*)nullptr);
-    KpProfScope prof_scope(st, nq, h, cin, 0, 0);   // start / stop events of the gather/aggregate kernel itself
-    const bool aligned = (cin % 4 == 0) && ((reinterpret_cast<uintptr_t>(x) & 15) == 0) &&
-                         ((reinterpret_cast<uintptr_t>(wf) & 15) == 0);
-    if (!aligned) {
-        hipLaunchKernelGGL(k_kpconv_generic, dim3(blocks_for(nq)), dim3(kWavesPerBlock * 64), 0, st, q_pts, nq, s_pts,
-                           ns, idx_ll, h, ld_idx, x, cin, kp, extent, pos, wf, inv_n);
-        PCRCG_CHECK_LAUNCH();
-        return PCRCG_OK;
-    }
-    // cin = 64 nb + 4 (PCR-CG's 129 channels in rows of 132): one wavefront per query, the last float4 on the vector units
-    if (cin == 68 || cin == 132) {
-        const int blocks = walk ? blocks_walk(1) : blocks_for((long)nq);
-#define LAUNCH_T(NBV, NT)                                                                                                        \
-        hipExtLaunchKernelGGL((k_kpconv_mfma<NBV, NT, float, true>), dim3(blocks), dim3(kWavesPerBlock * 64), 0, st, prof_scope.a, \
-                              prof_scope.b, 0, q_pts, nq, s_pts, ns, idx_ll, h, ld_idx, x, cin, kp, extent,                      \
-                              (const float4*)pk, wf, inv_n, 1, walk)
-        if (cin == 132) { if (stream_out) LAUNCH_T(2, true); else LAUNCH_T(2, false); }
-        else { if (stream_out) LAUNCH_T(1, true); else LAUNCH_T(1, false); }
-#undef LAUNCH_T
-        PCRCG_CHECK_LAUNCH();
-        return PCRCG_OK;
-    }
-    // channel blocks of 64 per wavefront: as many as possible while keeping >= ~16k wavefronts in the grid
-    const int nblk = (cin + 63) / 64;
-    int nb = nblk >= 4 ? 4 : (nblk >= 2 ? 2 : 1);
-    while (nb > 1 && ((long)nq * ((nblk + nb - 1) / nb) < 16384 || nblk % nb != 0)) nb >>= 1;
-    const int nchunk = (nblk + nb - 1) / nb;
-    const int blocks = walk ? blocks_walk(nchunk) : blocks_for((long)nq * nchunk);
-#define LAUNCH(NBV, NT)                                                                                                 \
-    hipExtLaunchKernelGGL((k_kpconv_mfma<NBV, NT, float>), dim3(blocks), dim3(kWavesPerBlock * 64), 0, st, prof_scope.a, \
-                          prof_scope.b, 0, q_pts, nq, s_pts, ns, idx_ll, h, ld_idx, x, cin, kp, extent,                 \
-                          (const float4*)pk, wf, inv_n, nchunk, walk)
-    if (stream_out) {
-        if (nb == 4) LAUNCH(4, true);
-        else if (nb == 2) LAUNCH(2, true);
-        else LAUNCH(1, true);
-    } else {
-        if (nb == 4) LAUNCH(4, false);
-        else if (nb == 2) LAUNCH(2, false);
-        else LAUNCH(1, false);
-    }
-#undef LAUNCH
-    PCRCG_CHECK_LAUNCH();
-    return PCRCG_OK;
+    return pcrcg_kpconv_aggregate_bf16_walk(q_pts, nq, s_pts, ns, idx, h, ld_idx, x, cin, kp, extent, x_bf16, wf_bf16, inv_n, ws,
+                                            ws_bytes, nullptr, stream);
 }
 
-// The first layer (cin = 1) in one kernel, k_kpconv_c1_fused: widths of whole float4s, and weight rows a lane can read as four
-bool kpconv_c1_fused_ok(int cout, const float* wt) { return cout >= 4 && cout % 4 == 0 && wt && (reinterpret_cast<uintptr_t>(wt) & 15) == 0; }
-
-// y [nq, cout] = KPConv of the one-column features x [ns] against wt [cout, 16] (K-contiguous, the 16th column unused), inv_n
-// [nq] as pcrcg_kpconv_aggregate leaves it, and sums [2][cout] f64 (zeroed by the caller) += the column sums and sums of
-// squares of y.  `pack`: build the support records in ws first.
-int kpconv_c1_fused(const float* q_pts, int nq, const float* s_pts, int ns, const int64_t* idx, int h, int ld_idx, const float* x,
-                    const float* kp, float extent, const float* wt, int cout, float* y, int ld_y, float* inv_n, double* sums,
-                    void* ws, size_t ws_bytes, hipStream_t st, bool pack) {
-    PCRCG_CHECK_ARG(nq >= 0 && ns >= 0 && h >= 1 && ld_idx >= h && extent > 0.0f);
-    PCRCG_CHECK_ARG(kpconv_c1_fused_ok(cout, wt) && ld_y >= cout);
-    if (nq == 0) return PCRCG_OK;
-    PCRCG_CHECK_ARG(q_pts && s_pts && idx && x && kp && wt && y && inv_n && sums && ws);
-    PCRCG_CHECK_ARG(ns >= 1);
-    Carver cv(ws, ws_bytes);
-    cv.take<unsigned char>((size_t)ns + 1);
-    float4* pk = cv.take<float4>((size_t)ns + 1);
-    PCRCG_CHECK_WS(cv);
-    if (pack) hipLaunchKernelGGL(k_pack_c1, dim3((ns + 255) / 256), dim3(256), 0, st, x, ns, s_pts, pk);
-    KpProfScope prof_scope(st, nq, h, 1, cout, 1);      // kind 1: the one-kernel KPConv
-    hipExtLaunchKernelGGL(k_kpconv_c1_fused, dim3((int)(((long)nq * C1_PARTS + 255) / 256)), dim3(256), 0, st,
-                          prof_scope.a, prof_scope.b, 0, q_pts, nq, ns, reinterpret_cast<const long long*>(idx), h, ld_idx,
-                          (const float4*)pk, kp, extent, wt, cout, y, ld_y, inv_n, sums);
-    PCRCG_CHECK_LAUNCH();
-    return PCRCG_OK;
+int pcrcg_kpconv_c1_layer(const float* q_pts, int nq, const float* s_pts, int ns, const int64_t* idx, int h, int ld_idx,
+                          const float* x, const float* kp, float extent, const float* wt, int cout, float* out, int ld_out,
+                          float* inv_n, void* sums, void* ws, size_t ws_bytes, void* stream) {
+    KpconvCall c = entry_call(q_pts, nq, s_pts, ns, idx, h, ld_idx, x, 1, kp, extent, inv_n, ws, ws_bytes, nullptr, stream);
+    c.form = KpForm::c1_fused;
+    c.wt = wt; c.cout = cout; c.y = out; c.ld_y = ld_out;
+    c.sums = static_cast<double*>(sums);
+    return kpconv_run(c);
 }
-
-// The bf16 feature-storage variant: x_bf16 [ns, cin] and wf_bf16 [nq, 15*cin] are bf16; `x` (fp32) is only read by the
-// support-record prelude (the n_q normaliser counts rows with a positive fp32 sum, exactly as the fp32 path does).
-int kpconv_aggregate_bf16(const float* q_pts, int nq, const float* s_pts, int ns, const int64_t* idx, int h, int ld_idx,
-                          const float* x, unsigned short* x_bf16, int cin, const float* kp, float extent,
-                          unsigned short* wf_bf16, float* inv_n, void* ws, size_t ws_bytes, hipStream_t st, const int* walk) {
-    PCRCG_CHECK_ARG(nq >= 0 && ns >= 1 && h >= 1 && ld_idx >= h && cin >= 4 && cin % 4 == 0 && extent > 0.0f);
-    if (nq == 0) return PCRCG_OK;
-    PCRCG_CHECK_ARG(q_pts && s_pts && idx && x && x_bf16 && kp && wf_bf16 && inv_n && ws);
-    PCRCG_CHECK_ARG((reinterpret_cast<uintptr_t>(x_bf16) & 7) == 0 && (reinterpret_cast<uintptr_t>(wf_bf16) & 7) == 0);
-    PCRCG_PROPAGATE(kpconv_pack(x, ns, cin, s_pts, ws, ws_bytes, st, x_bf16));   // also writes the bf16 copy of x
-    Carver cv(ws, ws_bytes);
-    cv.take<unsigned char>((size_t)ns + 1);
-    float4* pk = cv.take<float4>((size_t)ns + 1);
-    const long long* idx_ll = reinterpret_cast<const long long*>(idx);
-    const int nblk = (cin + 63) / 64;
-    int nb = nblk >= 4 ? 4 : (nblk >= 2 ? 2 : 1);
-    while (nb > 1 && ((long)nq * ((nblk + nb - 1) / nb) < 16384 || nblk % nb != 0)) nb >>= 1;
-    const int nchunk = (nblk + nb - 1) / nb;
-    long blocks = ((long)nq * nchunk + kWavesPerBlock - 1) / kWavesPerBlock;
-    if (blocks > 256 * 32) blocks = 256 * 32;
-    if (walk) {      // eight XCD ranges of at most ceil(nq / 8) queries, the same number of workgroups for each
-        blocks = ((long)((nq + 7) / 8) * nchunk + kWavesPerBlock - 1) / kWavesPerBlock;
-        blocks = 8 * (blocks > 32 * 32 ? 32 * 32 : blocks);
-    }
-    KpProfScope prof_scope(st, nq, h, cin, 0, 2);      // kind 2: bf16 storage
-#define LAUNCHB(NBV)                                                                                                      \
-    hipExtLaunchKernelGGL((k_kpconv_mfma<NBV, true, unsigned short>), dim3((int)blocks), dim3(kWavesPerBlock * 64), 0, st, \
-                          prof_scope.a, prof_scope.b, 0, q_pts, nq, s_pts, ns, idx_ll, h, ld_idx, x_bf16, cin, kp, extent, \
-                          (const float4*)pk, wf_bf16, inv_n, nchunk, walk)
-    if (nb == 4) LAUNCHB(4);
-    else if (nb == 2) LAUNCHB(2);
-    else LAUNCHB(1);
-#undef LAUNCHB
-    PCRCG_CHECK_LAUNCH();
-    return PCRCG_OK;
-}
-
-}  // namespace pcrcg
-
-extern "C" int pcrcg_kpconv_c1_layer(const float* q_pts, int nq, const float* s_pts, int ns, const int64_t* idx, int h, int ld_idx,
-                                     const float* x, const float* kp, float extent, const float* wt, int cout, float* out,
-                                     int ld_out, float* inv_n, void* sums, void* ws, size_t ws_bytes, void* stream) {
-    return pcrcg::kpconv_c1_fused(q_pts, nq, s_pts, ns, idx, h, ld_idx, x, kp, extent, wt, cout, out, ld_out, inv_n,
-                                  static_cast<double*>(sums), ws, ws_bytes, pcrcg::as_stream(stream), true);
 }

@@ -23,10 +23,14 @@
 // k_kpconv_ex_scalar (cin == 1, channel counts that are no multiple of 4, unaligned rows) is a plain restatement:
 // one wavefront per query, lanes = channels, neighbours in turn.
 // The backward (pcrcg_kpconv_backward_ex: dx and the gradient of offset_features) follows the forward entry in this file,
-// so that both are built with the same flags and decide the kept bit and the argmin by the same expressions.
+// so that both are built with the same flags and decide the kept bit and the argmin by the same expressions: the deformed
+// kernel point, the modulation and the argmin's tie rule are device functions all four kernels call (deformed, modulation,
+// argmin_takes).  The host side shares kpconv.h with kpconv.hip -- the workspace layout (kpconv_ws), the pack, the channel
+// plan (kpconv_plan, never a tail, never a walk) and kpconv_vec_ok -- but keeps its own launches: it does not go through
+// kpconv_run.  Both entries take their common argument checks from ex_check.
 #include <hip/hip_ext.h>
 
-#include "common.h"
+#include "kpconv.h"
 #include "pcrcg_train.h"
 #include "scatter.h"
 
@@ -49,6 +53,16 @@ __device__ __forceinline__ float influence_of(float d2, const ExMode& m) {
     if (m.influence == 1) return fmaxf(1.0f - sqrtf(d2) / m.extent, 0.0f);
     return expf(-d2 / m.gauss_den);
 }
+
+// The expressions the four kernels must agree on, bit for bit.
+// one coordinate of a deformed kernel point: a product and a sum, as the reference rounds them (contraction is off)
+__device__ __forceinline__ float deformed(float o, float extent, float kp) { return o * extent + kp; }
+// m = 2 sigmoid(off[q, 3K + k])
+__device__ __forceinline__ float modulation(const float* off, long q, int ld_off, int k) {
+    return 2.0f * (1.0f / (1.0f + expf(-off[q * ld_off + 3 * K + k])));
+}
+// butterfly argmin over (d2, k): the smaller distance, the smaller index on ties
+__device__ __forceinline__ bool argmin_takes(float od, int ok, float bd, int bk) { return od < bd || (od == bd && ok < bk); }
 
 template <int NB>
 __global__ void __launch_bounds__(kWavesPerBlock * 64) k_kpconv_ex_mfma(
@@ -74,9 +88,9 @@ __global__ void __launch_bounds__(kWavesPerBlock * 64) k_kpconv_ex_mfma(
         float kpx = kx0, kpy = ky0, kpz = kz0;
         if (deform && jvalid) {
             const float* o = off + (long)q * ld_off + 3 * j;
-            kpx = o[0] * mode.extent + kx0;
-            kpy = o[1] * mode.extent + ky0;
-            kpz = o[2] * mode.extent + kz0;
+            kpx = deformed(o[0], mode.extent, kx0);
+            kpy = deformed(o[1], mode.extent, ky0);
+            kpz = deformed(o[2], mode.extent, kz0);
         }
         const bool want_min = min_d2 != nullptr && chunk == 0;
         f32x4 acc[NB][4];
@@ -125,7 +139,7 @@ __global__ void __launch_bounds__(kWavesPerBlock * 64) k_kpconv_ex_mfma(
                         for (int m = 1; m < 16; m <<= 1) {
                             const float od = __shfl_xor(bd, m, 64);
                             const int ok = __shfl_xor(bk, m, 64);
-                            const bool take = od < bd || (od == bd && ok < bk);
+                            const bool take = argmin_takes(od, ok, bd, bk);
                             bd = take ? od : bd;
                             bk = take ? ok : bk;
                         }
@@ -159,7 +173,7 @@ __global__ void __launch_bounds__(kWavesPerBlock * 64) k_kpconv_ex_mfma(
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int k = 4 * hsub + r;
-                if (k < K) mod[r] = 2.0f * (1.0f / (1.0f + expf(-off[(long)q * ld_off + 3 * K + k])));
+                if (k < K) mod[r] = modulation(off, q, ld_off, k);
             }
         }
         float* o = wf + (long)q * K * cin + c0;
@@ -211,11 +225,11 @@ __global__ void __launch_bounds__(kWavesPerBlock * 64) k_kpconv_ex_scalar(
             kpx[k] = kp[3 * k]; kpy[k] = kp[3 * k + 1]; kpz[k] = kp[3 * k + 2];
             if (off) {
                 const float* o = off + (long)q * ld_off + 3 * k;
-                kpx[k] = o[0] * mode.extent + kpx[k];
-                kpy[k] = o[1] * mode.extent + kpy[k];
-                kpz[k] = o[2] * mode.extent + kpz[k];
+                kpx[k] = deformed(o[0], mode.extent, kpx[k]);
+                kpy[k] = deformed(o[1], mode.extent, kpy[k]);
+                kpz[k] = deformed(o[2], mode.extent, kpz[k]);
             }
-            mod[k] = mode.modulated ? 2.0f * (1.0f / (1.0f + expf(-off[(long)q * ld_off + 3 * K + k]))) : 1.0f;
+            mod[k] = mode.modulated ? modulation(off, q, ld_off, k) : 1.0f;
             dmin[k] = INFINITY;
         }
         int npos = 0;
@@ -320,11 +334,11 @@ __global__ void __launch_bounds__(256) k_kpconv_ex_bwd_mfma(
         kpx[r] = kp[3 * kc]; kpy[r] = kp[3 * kc + 1]; kpz[r] = kp[3 * kc + 2];
         if (deform) {
             const float* o = off + (long)q * ld_off + 3 * kc;
-            kpx[r] = o[0] * mode.extent + kpx[r];
-            kpy[r] = o[1] * mode.extent + kpy[r];
-            kpz[r] = o[2] * mode.extent + kpz[r];
+            kpx[r] = deformed(o[0], mode.extent, kpx[r]);
+            kpy[r] = deformed(o[1], mode.extent, kpy[r]);
+            kpz[r] = deformed(o[2], mode.extent, kpz[r]);
         }
-        mod[r] = mode.modulated ? 2.0f * (1.0f / (1.0f + expf(-off[(long)q * ld_off + 3 * K + kc]))) : 1.0f;
+        mod[r] = mode.modulated ? modulation(off, q, ld_off, kc) : 1.0f;
     }
     for (int c = threadIdx.x; c < stride; c += blockDim.x) dws[15 * stride + c] = 0.f;
     float sx[4] = {0.f, 0.f, 0.f, 0.f}, sy[4] = {0.f, 0.f, 0.f, 0.f}, sz[4] = {0.f, 0.f, 0.f, 0.f}, sm[4] = {0.f, 0.f, 0.f, 0.f};
@@ -361,7 +375,7 @@ __global__ void __launch_bounds__(256) k_kpconv_ex_bwd_mfma(
             for (int m = 16; m < 64; m <<= 1) {
                 const float od = __shfl_xor(bd, m, 64);
                 const int ok = __shfl_xor(bk, m, 64);
-                const bool take = od < bd || (od == bd && ok < bk);
+                const bool take = argmin_takes(od, ok, bd, bk);
                 bd = take ? od : bd;
                 bk = take ? ok : bk;
             }
@@ -462,7 +476,7 @@ __global__ void __launch_bounds__(256) k_kpconv_ex_bwd_mfma(
             const float4 t = *reinterpret_cast<const float4*>(red + (wv * 16 + k) * 4);
             s.x += t.x; s.y += t.y; s.z += t.z; s.w += t.w;
         }
-        const float m = mode.modulated ? 2.0f * (1.0f / (1.0f + expf(-off[(long)q * ld_off + 3 * K + k]))) : 1.0f;
+        const float m = mode.modulated ? modulation(off, q, ld_off, k) : 1.0f;
         float* o = d_off + (long)q * ld_doff;
         const float em = mode.extent * m;
         o[3 * k] = em * s.x;
@@ -486,7 +500,7 @@ __global__ void __launch_bounds__(kWavesPerBlock * 64) k_kpconv_ex_bwd_scalar(
     const double fscale = DET ? fix_scale(fx) : 1.0;
     const float qx = q_pts[3 * q], qy = q_pts[3 * q + 1], qz = q_pts[3 * q + 2];
     for (int k = 0; k < K; ++k) {
-        const float m = mode.modulated ? 2.0f * (1.0f / (1.0f + expf(-off[q * ld_off + 3 * K + k]))) : 1.0f;
+        const float m = mode.modulated ? modulation(off, q, ld_off, k) : 1.0f;
         const float* dk = d_wf + (q * K + k) * cin;
         float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
         for (int hc = 0; hc < H; hc += 64) {
@@ -503,9 +517,9 @@ __global__ void __launch_bounds__(kWavesPerBlock * 64) k_kpconv_ex_bwd_scalar(
                 float kx = kp[3 * kk], ky = kp[3 * kk + 1], kz = kp[3 * kk + 2];
                 if (off) {
                     const float* o = off + q * ld_off + 3 * kk;
-                    kx = o[0] * mode.extent + kx;
-                    ky = o[1] * mode.extent + ky;
-                    kz = o[2] * mode.extent + kz;
+                    kx = deformed(o[0], mode.extent, kx);
+                    ky = deformed(o[1], mode.extent, ky);
+                    kz = deformed(o[2], mode.extent, kz);
                 }
                 const float ddx = nx - kx, ddy = ny - ky, ddz = nz - kz;
                 const float d = ddx * ddx + ddy * ddy + ddz * ddz;
@@ -569,51 +583,47 @@ static ExMode ex_mode(float extent, int influence, int closest, int modulated) {
     return mode;
 }
 
-extern "C" int pcrcg_kpconv_aggregate_ex(const float* q_pts, int nq, const float* s_pts, int ns, const int64_t* idx, int h,
-                                         int ld_idx, const float* x, int cin, const float* kp, float extent,
-                                         const float* offset_features, int ld_off, int influence, int closest, int modulated,
-                                         float* wf, float* inv_n, float* min_d2, void* ws, size_t ws_bytes, void* stream) {
+// the argument checks of both entries; the pointers are looked at before the empty-call exit (each entry adds its own)
+static int ex_check(const float* q_pts, int nq, const float* s_pts, int ns, const int64_t* idx, int h, int ld_idx, const float* x,
+                    int cin, const float* kp, float extent, const float* offset_features, int ld_off, int influence, int closest,
+                    int modulated) {
     PCRCG_CHECK_ARG(nq >= 0 && ns >= 1 && h >= 1 && ld_idx >= h && cin >= 1);
     PCRCG_CHECK_ARG(extent > 0.0f);
     PCRCG_CHECK_ARG(influence >= 0 && influence <= 2);
     PCRCG_CHECK_ARG((closest == 0 || closest == 1) && (modulated == 0 || modulated == 1));
-    PCRCG_CHECK_ARG(q_pts && s_pts && idx && x && kp && wf && inv_n && ws);
+    PCRCG_CHECK_ARG(q_pts && s_pts && idx && x && kp);
     PCRCG_CHECK_ARG(offset_features || !modulated);
     PCRCG_CHECK_ARG(!offset_features || ld_off >= (modulated ? 4 : 3) * K);
+    return PCRCG_OK;
+}
+
+extern "C" int pcrcg_kpconv_aggregate_ex(const float* q_pts, int nq, const float* s_pts, int ns, const int64_t* idx, int h,
+                                         int ld_idx, const float* x, int cin, const float* kp, float extent,
+                                         const float* offset_features, int ld_off, int influence, int closest, int modulated,
+                                         float* wf, float* inv_n, float* min_d2, void* ws, size_t ws_bytes, void* stream) {
+    PCRCG_PROPAGATE(ex_check(q_pts, nq, s_pts, ns, idx, h, ld_idx, x, cin, kp, extent, offset_features, ld_off, influence, closest,
+                             modulated));
+    PCRCG_CHECK_ARG(wf && inv_n && ws);
     if (nq == 0) return PCRCG_OK;
     hipStream_t st = as_stream(stream);
-    Carver cv(ws, ws_bytes);
-    unsigned char* pos = cv.take<unsigned char>((size_t)ns + 1);
-    float4* pk = cv.take<float4>((size_t)ns + 1);
-    PCRCG_CHECK_WS(cv);
-    PCRCG_PROPAGATE(kpconv_pack(x, ns, cin, s_pts, ws, ws_bytes, st));
+    KpWs w;
+    PCRCG_PROPAGATE(kpconv_ws(ws, ws_bytes, ns, &w));
+    PCRCG_PROPAGATE(kpconv_pack(x, ns, cin, s_pts, w, st));
     const ExMode mode = ex_mode(extent, influence, closest, modulated);
     const long long* idx_ll = reinterpret_cast<const long long*>(idx);
-    const int max_blocks = 256 * 32;
-    auto blocks_for = [&](long waves) {
-        const long b = (waves + kWavesPerBlock - 1) / kWavesPerBlock;
-        return (int)(b > max_blocks ? max_blocks : b);
-    };
-    const bool aligned = (cin % 4 == 0) && ((reinterpret_cast<uintptr_t>(x) & 15) == 0) &&
-                         ((reinterpret_cast<uintptr_t>(wf) & 15) == 0);
-    if (!aligned) {
-        hipLaunchKernelGGL(k_kpconv_ex_scalar, dim3(blocks_for(nq)), dim3(kWavesPerBlock * 64), 0, st, q_pts, nq, s_pts, ns,
-                           idx_ll, h, ld_idx, x, cin, kp, offset_features, ld_off, mode, (const unsigned char*)pos, wf, inv_n,
+    if (!kpconv_vec_ok(cin, x, wf)) {
+        hipLaunchKernelGGL(k_kpconv_ex_scalar, dim3(kpconv_blocks(nq)), dim3(kWavesPerBlock * 64), 0, st, q_pts, nq, s_pts, ns,
+                           idx_ll, h, ld_idx, x, cin, kp, offset_features, ld_off, mode, (const unsigned char*)w.pos, wf, inv_n,
                            min_d2);
         PCRCG_CHECK_LAUNCH();
         return PCRCG_OK;
     }
-    // channel blocks of 64 per wavefront, chosen as kpconv.hip chooses them
-    const int nblk = (cin + 63) / 64;
-    int nb = nblk >= 4 ? 4 : (nblk >= 2 ? 2 : 1);
-    while (nb > 1 && ((long)nq * ((nblk + nb - 1) / nb) < 16384 || nblk % nb != 0)) nb >>= 1;
-    const int nchunk = (nblk + nb - 1) / nb;
-    const int blocks = blocks_for((long)nq * nchunk);
+    const KpPlan p = kpconv_plan(nq, cin, false, false);
 #define LAUNCH(NBV)                                                                                                         \
-    hipLaunchKernelGGL((k_kpconv_ex_mfma<NBV>), dim3(blocks), dim3(kWavesPerBlock * 64), 0, st, q_pts, nq, ns, idx_ll, h,    \
-                       ld_idx, x, cin, kp, offset_features, ld_off, mode, (const float4*)pk, wf, inv_n, min_d2, nchunk)
-    if (nb == 4) LAUNCH(4);
-    else if (nb == 2) LAUNCH(2);
+    hipLaunchKernelGGL((k_kpconv_ex_mfma<NBV>), dim3(p.blocks), dim3(kWavesPerBlock * 64), 0, st, q_pts, nq, ns, idx_ll, h,  \
+                       ld_idx, x, cin, kp, offset_features, ld_off, mode, (const float4*)w.pk, wf, inv_n, min_d2, p.nchunk)
+    if (p.nb == 4) LAUNCH(4);
+    else if (p.nb == 2) LAUNCH(2);
     else LAUNCH(1);
 #undef LAUNCH
     PCRCG_CHECK_LAUNCH();
@@ -624,20 +634,15 @@ extern "C" int pcrcg_kpconv_backward_ex(const float* q_pts, int nq, const float*
                                         int ld_idx, const float* x, int cin, const float* kp, float extent,
                                         const float* offset_features, int ld_off, int influence, int closest, int modulated,
                                         const float* d_wf, float* dx, float* d_off, int ld_doff, void* stream) {
-    PCRCG_CHECK_ARG(nq >= 0 && ns >= 1 && h >= 1 && ld_idx >= h && cin >= 1);
-    PCRCG_CHECK_ARG(extent > 0.0f);
-    PCRCG_CHECK_ARG(influence >= 0 && influence <= 2);
-    PCRCG_CHECK_ARG((closest == 0 || closest == 1) && (modulated == 0 || modulated == 1));
-    PCRCG_CHECK_ARG(q_pts && s_pts && idx && x && kp && d_wf);
-    PCRCG_CHECK_ARG(offset_features || !modulated);
-    PCRCG_CHECK_ARG(!offset_features || ld_off >= (modulated ? 4 : 3) * K);
+    PCRCG_PROPAGATE(ex_check(q_pts, nq, s_pts, ns, idx, h, ld_idx, x, cin, kp, extent, offset_features, ld_off, influence, closest,
+                             modulated));
+    PCRCG_CHECK_ARG(d_wf);
     PCRCG_CHECK_ARG(!d_off || (offset_features && ld_doff >= (modulated ? 4 : 3) * K));
     if (nq == 0 || (!dx && !d_off)) return PCRCG_OK;
     hipStream_t st = as_stream(stream);
     const ExMode mode = ex_mode(extent, influence, closest, modulated);
     const long long* ix = reinterpret_cast<const long long*>(idx);
-    const bool aligned = (cin % 4 == 0) && ((reinterpret_cast<uintptr_t>(x) & 15) == 0) &&
-                         ((reinterpret_cast<uintptr_t>(d_wf) & 15) == 0);
+    const bool aligned = kpconv_vec_ok(cin, x, d_wf);
     const int cchunk = cin < kBwdChunk ? (cin + 3) / 4 * 4 : kBwdChunk;
     const int nwaves = (h + 15) / 16 < 4 ? (h + 15) / 16 : 4;
     const size_t lds_bytes = ((size_t)16 * (cchunk + kBwdPad) + 4 * 16 * 4) * sizeof(float);

@@ -14,6 +14,7 @@
 #include <cstdlib>
 
 #include "gemm.h"
+#include "kpconv.h"
 
 namespace pcrcg {
 namespace {
@@ -441,18 +442,28 @@ void kpconv(Ctx& c, const Batches& B, Walks& W, const pcrcg_block& blk, const Ma
     const int kk = kp_k(blk, x);
     // the queries' order: the walk of the level the QUERIES are points of (cin = 1 reads only the support records: no walk)
     const int* const* walks = (cin > 1 && walk_pays(W.mode, c.max_rows(ns), cin, c.max_rows(nq))) ? level_walks(c, B, W, blk.strided ? l + 1 : l) : nullptr;
+    auto gather_call = [&](int g) {
+        KpconvCall k;
+        k.q_pts = q[g]; k.nq = nq[g]; k.s_pts = B.b[g]->points[l]; k.ns = ns[g];
+        k.idx = tab[g]->idx; k.h = tab[g]->cols; k.ld_idx = tab[g]->ld;
+        k.x = xin.p[g]; k.cin = cin; k.kp = blk.kp; k.extent = blk.extent;
+        k.inv_n = inv_n[g]; k.ws = ws[g]; k.ws_bytes = wsb[g]; k.st = c.st;
+        k.walk = walks ? walks[g] : nullptr;
+        return k;
+    };
     // bf16 feature storage (pcrcg_model.feature_bf16): the gathers read a bf16 copy of x and wf is bf16 in HBM -- half
     // the bytes of the two streams that bound the encoder; the contraction takes wf as the (single-term) bf16 operand
     // against the exact three-term split of the fp32 weights, fp32 accumulate and fp32 output.
     if (c.bf16 && kp_wt && cin % 32 == 0) {
         for (int g = 0; g < c.G; ++g) {
-            const pcrcg_batch& b = *B.b[g];
             void* xb = c.raw(sizeof(unsigned short) * (size_t)(ns[g] > 0 ? ns[g] : 1) * cin);
             void* wfb = c.raw(sizeof(unsigned short) * (size_t)(nq[g] > 0 ? nq[g] : 1) * kk);
             if (c.live()) {
-                c.check(kpconv_aggregate_bf16(q[g], nq[g], b.points[l], ns[g], tab[g]->idx, tab[g]->cols, tab[g]->ld, xin.p[g],
-                                              static_cast<unsigned short*>(xb), cin, blk.kp, blk.extent, static_cast<unsigned short*>(wfb),
-                                              inv_n[g], ws[g], wsb[g], c.st, walks ? walks[g] : nullptr));
+                KpconvCall gather_bf16 = gather_call(g);
+                gather_bf16.form = KpForm::bf16;
+                gather_bf16.x_bf16 = static_cast<unsigned short*>(xb);
+                gather_bf16.wf_bf16 = static_cast<unsigned short*>(wfb);
+                c.check(kpconv_run(gather_bf16));
                 GemmCall call;
                 call.a = wfb; call.lda = kk; call.a_form = GemmA::row_bf16;
                 call.b = kp_wt; call.ldb = kk;
@@ -474,9 +485,11 @@ void kpconv(Ctx& c, const Batches& B, Walks& W, const pcrcg_block& blk, const Ma
     if (cin == 1 && st && st->sums && kpconv_c1_fused_ok(y.cols, kp_wt)) {
         if (c.live())
             for (int g = 0; g < c.G; ++g) {
-                c.check(kpconv_c1_fused(q[g], nq[g], B.b[g]->points[l], ns[g], tab[g]->idx, tab[g]->cols, tab[g]->ld, xin.p[g],
-                                        blk.kp, blk.extent, kp_wt, y.cols, y.p[g], y.ld, inv_n[g],
-                                        static_cast<double*>(st->partials[g]), ws[g], wsb[g], c.st, /*pack=*/true));
+                KpconvCall layer = gather_call(g);
+                layer.form = KpForm::c1_fused;
+                layer.wt = kp_wt; layer.cout = y.cols; layer.y = y.p[g]; layer.ld_y = y.ld;
+                layer.sums = static_cast<double*>(st->partials[g]);
+                c.check(kpconv_run(layer));
                 st->chunks[g] = Stat::SUMS;
             }
         c.release(m);
@@ -487,10 +500,11 @@ void kpconv(Ctx& c, const Batches& B, Walks& W, const pcrcg_block& blk, const Ma
         for (int g = 0; g < c.G; ++g) {
             // (pcrcg_kpconv_aggregate is this call with pack = true; the support records are there already when the
             // normalisation that wrote x packed them, norm_act_pack)
-            const bool packed = kk != 16 && packed_ws && packed_ws[g] && xin.p[g] == x.p[g];
-            c.check(kpconv_aggregate_rows(q[g], nq[g], B.b[g]->points[l], ns[g], tab[g]->idx, tab[g]->cols, tab[g]->ld, xin.p[g], cin,
-                                          blk.kp, blk.extent, wf.p[g], inv_n[g], ws[g], wsb[g], c.st, /*pack=*/!packed,
-                                          /*stream_out=*/true, /*c1_ld=*/kk == 16 ? 16 : 0, walks ? walks[g] : nullptr));
+            KpconvCall gather = gather_call(g);
+            gather.wf = wf.p[g];
+            gather.pack = !(kk != 16 && packed_ws && packed_ws[g] && xin.p[g] == x.p[g]);
+            gather.c1_ld = kk == 16 ? 16 : 0;
+            c.check(kpconv_run(gather));
         }
         // contraction wf @ W: against the K-contiguous copy wt [cout, 15*cin] when the descriptor carries one
         // (C = A * B^T form: both operands k-contiguous, the form the split-bf16 GEMM is built for).

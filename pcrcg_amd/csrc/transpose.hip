@@ -15,6 +15,7 @@
 // the table does not depend on scheduling; the placement is out of place (raw -> tq), so there is no hazard between readers
 // and writers.  deg / 64 segment loads and deg readlane-compares per edge.
 #include "pcrcg_train.h"
+#include "kpconv.h"
 #include "trainops.h"
 
 namespace pcrcg {
@@ -271,8 +272,12 @@ extern "C" int pcrcg_kpconv_backward_dx_t(const float* q_pts, int nq, const floa
     hipLaunchKernelGGL(k_negate, dim3(1), dim3(64), 0, st, kp, kpn, 3 * K);
     PCRCG_CHECK_LAUNCH();
     // the supports are the queries of the transposed problem, g its features, nq its shadow index
-    PCRCG_PROPAGATE(kpconv_aggregate_rows(s_pts, ns, q_pts, nq, tq, cols, ld_tq, g, cout, kpn, extent, wf, inv, agg, agg_bytes, st,
-                                          true, true));
+    KpconvCall gather;
+    gather.q_pts = s_pts; gather.nq = ns; gather.s_pts = q_pts; gather.ns = nq;
+    gather.idx = tq; gather.h = cols; gather.ld_idx = ld_tq;
+    gather.x = g; gather.cin = cout; gather.kp = kpn; gather.extent = extent;
+    gather.wf = wf; gather.inv_n = inv; gather.ws = agg; gather.ws_bytes = agg_bytes; gather.st = st;
+    PCRCG_PROPAGATE(kpconv_run(gather));
     return pcrcg_gemm_f32_grad(wf, K * cout, 0, wt, cin, 0, dx, ld_dx, ns, cin, K * cout, nullptr, nullptr, 1, stream);
 }
 

@@ -8,6 +8,9 @@
 // One workgroup of 1024 threads per cloud (latency work, once per level and forward call): bounding box, LDS histogram
 // over the 4096 keys, scan, scatter through LDS cursors.  The order INSIDE a bin depends on the atomics' arrival; only the
 // processing order of the gathers depends on it, never a result.
+//
+// This file builds walks (k_query_walk, query_walk_multi, pcrcg_query_walk) and holds the max-pool entry that takes one;
+// the KPConv gather's entries that take one are with the gather's other entries in kpconv.hip.
 #include <cfloat>
 
 #include "block_scan.h"
@@ -167,21 +170,8 @@ int pcrcg_query_walk(const float* points, int n, int* walk, int* key, void* stre
     return query_walk_multi(&points, &n, &walk, key ? &key : nullptr, 1, as_stream(stream));
 }
 
-// the gather entries with the queries' order given: what the forward runner launches, for tests and A/B timing
-int pcrcg_kpconv_aggregate_walk(const float* q_pts, int nq, const float* s_pts, int ns, const int64_t* idx, int h, int ld_idx,
-                                const float* x, int cin, const float* kp, float extent, float* wf, float* inv_n, void* ws,
-                                size_t ws_bytes, const int* walk, void* stream) {
-    return kpconv_aggregate_rows(q_pts, nq, s_pts, ns, idx, h, ld_idx, x, cin, kp, extent, wf, inv_n, ws, ws_bytes,
-                                 as_stream(stream), true, true, 0, walk);
-}
-
-int pcrcg_kpconv_aggregate_bf16_walk(const float* q_pts, int nq, const float* s_pts, int ns, const int64_t* idx, int h,
-                                     int ld_idx, const float* x, int cin, const float* kp, float extent, void* x_bf16,
-                                     void* wf_bf16, float* inv_n, void* ws, size_t ws_bytes, const int* walk, void* stream) {
-    return kpconv_aggregate_bf16(q_pts, nq, s_pts, ns, idx, h, ld_idx, x, static_cast<unsigned short*>(x_bf16), cin, kp,
-                                 extent, static_cast<unsigned short*>(wf_bf16), inv_n, ws, ws_bytes, as_stream(stream), walk);
-}
-
+// the max-pool gather with the queries' order given: what the forward runner launches, for tests and A/B timing (the KPConv
+// gather's _walk entries are in kpconv.hip)
 int pcrcg_gather_max_walk(const float* x, int ns, int c, const int64_t* idx, int nq, int h, int ld_idx, float* out,
                           const int* walk, void* stream) {
     PCRCG_CHECK_ARG(ns >= 0 && c >= 1 && nq >= 0 && h >= 1 && ld_idx >= h);

@@ -427,69 +427,113 @@ def gemm_fused(a, w, idx=None, out=None, accumulate=False, sums=None, slope=1.0,
     return out
 
 
+_INFLUENCE = {"constant": 0, "linear": 1, "gaussian": 2}
+
+
+class _KpArgs:
+    """What _kpconv_args leaves: the normalised tensors, the sizes and the buffers of one KPConv gather."""
+    off, ld_off, pad, wf, inv_n, min_d2, ws, nbytes = None, 0, 0, None, None, None, None, 0
+
+
+def _kpconv_args(who, q_pts, s_pts, idx, x, kernel_points, offset_features=None, modulated=False, d_wf=None, dev=True,
+                 idx_name="neighb_inds", k15=True, pad=True, c1=False, scratch=True, wf=True, want_min_d2=False):
+    """The prologue every KPConv wrapper shares, for the function `who` (its name in the error texts): the five tensors
+    contiguous (dev: and refused unless fp32 on a HIP device), 15 kernel points (k15), d_wf [nq, 15 * cin] when given,
+    offset_features [nq, >= 3K or 4K], channels zero-padded to a multiple of 4 above 4 (pad; the caller pads its weights by
+    a.pad), then inv_n and the workspace (scratch), wf and min_d2.  c1: x is one feature per point, [ns] or [ns, 1]."""
+    norm = (lambda t, name: _dev(t, _F32, name).contiguous()) if dev else (lambda t, name: t if t.is_contiguous() else t.contiguous())
+    a = _KpArgs()
+    a.q_pts, a.s_pts = norm(q_pts, "q_pts"), norm(s_pts, "s_pts")
+    a.idx, a.ld_idx = _rows(idx, _I64, idx_name)
+    a.x, a.kp = norm(x, "x"), norm(kernel_points, "kernel_points")
+    if d_wf is not None:
+        d_wf = norm(d_wf, "d_wf")
+    a.nq, a.h = a.idx.shape
+    a.ns, a.cin = (a.x.shape[0], 1) if c1 else a.x.shape
+    a.kdim = a.kp.shape[0]
+    if k15 and a.kdim != 15:
+        raise RuntimeError(f"pcrcg_amd.{who}: only 15 kernel points are supported")
+    if d_wf is not None and tuple(d_wf.shape) != (a.nq, a.kdim * a.cin):
+        raise RuntimeError(f"pcrcg_amd.{who}: d_wf must be [nq, 15 * cin]")
+    a.d_wf = d_wf
+    a.cols = (4 if modulated else 3) * a.kdim
+    if offset_features is not None:
+        a.off, a.ld_off = _rows(offset_features, _F32, "offset_features")
+        if a.off.shape[0] != a.nq or a.off.shape[1] < a.cols:
+            raise RuntimeError(f"pcrcg_amd.{who}: offset_features must be [nq, 3K] ([nq, 4K] when modulated)")
+    elif modulated:
+        raise RuntimeError(f"pcrcg_amd.{who}: modulated needs offset_features")
+    if pad and a.cin % 4 != 0 and a.cin > 4:
+        # e.g. PCR-CG's 129-channel first layer: zero-pad the channels so that the MFMA gather kernel applies
+        # (zeros change neither the sums nor the neighbour count of the normaliser)
+        a.pad = (-a.cin) % 4
+        a.x = torch.nn.functional.pad(a.x, (0, a.pad))
+        a.cin += a.pad
+    device = a.x.device
+    if scratch:
+        a.inv_n = torch.empty(a.nq, dtype=_F32, device=device)
+        a.nbytes = _lib.lib().pcrcg_kpconv_ws_bytes(a.ns)
+        a.ws = _ws.get("kpconv", a.nbytes, device)
+    if wf:
+        a.wf = torch.empty((a.nq, a.kdim * a.cin), dtype=_F32, device=device)
+    if want_min_d2:
+        a.min_d2 = torch.empty((a.nq, a.kdim), dtype=_F32, device=device)
+    return a
+
+
+def _pad_cin(weights, pad):
+    return torch.nn.functional.pad(weights, (0, 0, 0, pad)) if pad else weights
+
+
+def _kpconv_gather(a, extent, ex=None, bf16=None):
+    """The gather of prologue `a`: pcrcg_kpconv_aggregate into a.wf, with ex = (influence, closest, modulated) the general
+    pcrcg_kpconv_aggregate_ex, with bf16 = (x_bf16, wf_bf16) the bf16-storage entry into those."""
+    head = (a.q_pts.data_ptr(), a.nq, a.s_pts.data_ptr(), a.ns, a.idx.data_ptr(), a.h, a.ld_idx, a.x.data_ptr(), a.cin,
+            a.kp.data_ptr(), float(extent))
+    tail = (a.ws.data_ptr(), a.nbytes, _stream())
+    if ex is not None:
+        name, mid = "pcrcg_kpconv_aggregate_ex", (_ptr(a.off), a.ld_off, *ex, a.wf.data_ptr(), a.inv_n.data_ptr(), _ptr(a.min_d2))
+    elif bf16 is not None:
+        name, mid = "pcrcg_kpconv_aggregate_bf16", (bf16[0].data_ptr(), bf16[1].data_ptr(), a.inv_n.data_ptr())
+    else:
+        name, mid = "pcrcg_kpconv_aggregate", (a.wf.data_ptr(), a.inv_n.data_ptr())
+    _lib.check(getattr(_lib.lib(), name)(*head, *mid, *tail), name)
+
+
+def _check_mode(influence, aggregation):
+    if influence not in _INFLUENCE:
+        raise ValueError("Unknown influence function type (config.KP_influence)")
+    if aggregation not in ("sum", "closest"):
+        raise ValueError("Unknown convolution mode. Should be 'closest' or 'sum'")
+
+
 def kpconv(q_pts, s_pts, idx, x, kernel_points, weights, extent):
     """KPConv.forward (rigid / linear / sum): aggregate kernel + MFMA contraction with 1/n row scale.
     weights: [15, cin, cout] as stored in the reference state_dict."""
-    L = _lib.lib()
-    q_pts = _dev(q_pts, _F32, "q_pts").contiguous()
-    s_pts = _dev(s_pts, _F32, "s_pts").contiguous()
-    idx, ld_idx = _rows(idx, _I64, "neighb_inds")
-    x = _dev(x, _F32, "x").contiguous()
-    kp = _dev(kernel_points, _F32, "kernel_points").contiguous()
-    nq, h = idx.shape
-    ns, cin = x.shape
-    kdim = kp.shape[0]
-    if kdim != 15:
-        raise RuntimeError("pcrcg_amd.kpconv: only 15 kernel points are supported")
-    if cin % 4 != 0 and cin > 4:
-        # e.g. PCR-CG's 129-channel first layer: zero-pad the channels so that the MFMA gather kernel applies
-        # (zeros change neither the sums nor the neighbour count of the normaliser)
-        pad = (-cin) % 4
-        x = torch.nn.functional.pad(x, (0, pad))
-        weights = torch.nn.functional.pad(weights, (0, 0, 0, pad))
-        cin += pad
-    wf = torch.empty((nq, kdim * cin), dtype=_F32, device=x.device)
-    inv_n = torch.empty(nq, dtype=_F32, device=x.device)
-    nbytes = L.pcrcg_kpconv_ws_bytes(ns)
-    ws = _ws.get("kpconv", nbytes, x.device)
-    w2 = _dev(weights, _F32, "weights").reshape(kdim * cin, -1)
-    _lib.check(L.pcrcg_kpconv_aggregate(q_pts.data_ptr(), nq, s_pts.data_ptr(), ns, idx.data_ptr(), h, ld_idx,
-                                        x.data_ptr(), cin, kp.data_ptr(), float(extent), wf.data_ptr(),
-                                        inv_n.data_ptr(), ws.data_ptr(), nbytes, _stream()),
-               "pcrcg_kpconv_aggregate")
-    return gemm(wf, w2, row_scale=inv_n)
+    a = _kpconv_args("kpconv", q_pts, s_pts, idx, x, kernel_points)
+    w2 = _dev(_pad_cin(weights, a.pad), _F32, "weights").reshape(a.kdim * a.cin, -1)
+    _kpconv_gather(a, extent)
+    return gemm(a.wf, w2, row_scale=a.inv_n)
 
 
 def kpconv_c1_layer(q_pts, s_pts, idx, x, kernel_points, wt, extent, out=None):
     """The first layer (one feature per point, x [ns] or [ns, 1]) in one kernel (pcrcg_kpconv_c1_layer): wt [cout, 16] is the
     K-contiguous weight copy of the runner's descriptor.  `out`: a [nq, cout] column slice of a row-major buffer whose rows are
     16-byte aligned, or None.  -> (out, inv_n [nq], sums [2, cout] float64: column sums and sums of squares of out)."""
-    L = _lib.lib()
-    q_pts = _dev(q_pts, _F32, "q_pts").contiguous()
-    s_pts = _dev(s_pts, _F32, "s_pts").contiguous()
-    idx, ld_idx = _rows(idx, _I64, "neighb_inds")
-    x = _dev(x, _F32, "x").contiguous()
-    kp = _dev(kernel_points, _F32, "kernel_points").contiguous()
+    a = _kpconv_args("kpconv_c1_layer", q_pts, s_pts, idx, x, kernel_points, k15=False, pad=False, c1=True, wf=False)
     wt = _dev(wt, _F32, "wt").contiguous()
-    nq, h = idx.shape
-    ns, cout = x.shape[0], wt.shape[0]
-    if kp.shape[0] != 15 or wt.shape[1] != 16 or x.numel() != ns:
+    cout = wt.shape[0]
+    if a.kdim != 15 or wt.shape[1] != 16 or a.x.numel() != a.ns:
         raise RuntimeError("pcrcg_amd.kpconv_c1_layer: 15 kernel points, wt [cout, 16] and one feature per point")
     if out is None:
-        out = torch.empty((nq, cout), dtype=_F32, device=x.device)
-    ld_out = out.stride(0) if nq > 1 else max(cout, out.stride(0))
-    inv_n = torch.empty(nq, dtype=_F32, device=x.device)
-    sums = torch.zeros((2, cout), dtype=torch.float64, device=x.device)
-    nbytes = L.pcrcg_kpconv_ws_bytes(ns)
-    ws = _ws.get("kpconv", nbytes, x.device)
-    _lib.check(L.pcrcg_kpconv_c1_layer(q_pts.data_ptr(), nq, s_pts.data_ptr(), ns, idx.data_ptr(), h, ld_idx, x.data_ptr(),
-                                       kp.data_ptr(), float(extent), wt.data_ptr(), cout, out.data_ptr(), ld_out,
-                                       inv_n.data_ptr(), sums.data_ptr(), ws.data_ptr(), nbytes, _stream()),
-               "pcrcg_kpconv_c1_layer")
-    return out, inv_n, sums
-
-
-_INFLUENCE = {"constant": 0, "linear": 1, "gaussian": 2}
+        out = torch.empty((a.nq, cout), dtype=_F32, device=a.x.device)
+    ld_out = out.stride(0) if a.nq > 1 else max(cout, out.stride(0))
+    sums = torch.zeros((2, cout), dtype=torch.float64, device=a.x.device)
+    _lib.check(_lib.lib().pcrcg_kpconv_c1_layer(a.q_pts.data_ptr(), a.nq, a.s_pts.data_ptr(), a.ns, a.idx.data_ptr(), a.h,
+                                                a.ld_idx, a.x.data_ptr(), a.kp.data_ptr(), float(extent), wt.data_ptr(), cout,
+                                                out.data_ptr(), ld_out, a.inv_n.data_ptr(), sums.data_ptr(), a.ws.data_ptr(),
+                                                a.nbytes, _stream()), "pcrcg_kpconv_c1_layer")
+    return out, a.inv_n, sums
 
 
 def kpconv_ex(q_pts, s_pts, idx, x, kernel_points, weights, extent, offset_features=None, influence="linear",
@@ -498,46 +542,12 @@ def kpconv_ex(q_pts, s_pts, idx, x, kernel_points, weights, extent, offset_featu
     of `kpconv`).  offset_features [nq, 3K (+K when modulated)]: the offset convolution's output with its bias added, or
     None for a rigid kernel.  -> out, or (out, min_d2 [nq, K]) with want_min_d2.  Not recorded by autograd:
     autograd.kpconv_ex is the differentiable form."""
-    L = _lib.lib()
-    if influence not in _INFLUENCE:
-        raise ValueError("Unknown influence function type (config.KP_influence)")
-    if aggregation not in ("sum", "closest"):
-        raise ValueError("Unknown convolution mode. Should be 'closest' or 'sum'")
-    q_pts = _dev(q_pts, _F32, "q_pts").contiguous()
-    s_pts = _dev(s_pts, _F32, "s_pts").contiguous()
-    idx, ld_idx = _rows(idx, _I64, "neighb_inds")
-    x = _dev(x, _F32, "x").contiguous()
-    kp = _dev(kernel_points, _F32, "kernel_points").contiguous()
-    nq, h = idx.shape
-    ns, cin = x.shape
-    kdim = kp.shape[0]
-    if kdim != 15:
-        raise RuntimeError("pcrcg_amd.kpconv_ex: only 15 kernel points are supported")
-    off, ld_off = None, 0
-    if offset_features is not None:
-        off, ld_off = _rows(offset_features, _F32, "offset_features")
-        if off.shape[0] != nq or off.shape[1] < (4 if modulated else 3) * kdim:
-            raise RuntimeError("pcrcg_amd.kpconv_ex: offset_features must be [nq, 3K] ([nq, 4K] when modulated)")
-    elif modulated:
-        raise RuntimeError("pcrcg_amd.kpconv_ex: modulated needs offset_features")
-    if cin % 4 != 0 and cin > 4:
-        pad = (-cin) % 4        # as in kpconv: zero channels change neither the sums nor the normaliser
-        x = torch.nn.functional.pad(x, (0, pad))
-        weights = torch.nn.functional.pad(weights, (0, 0, 0, pad))
-        cin += pad
-    wf = torch.empty((nq, kdim * cin), dtype=_F32, device=x.device)
-    inv_n = torch.empty(nq, dtype=_F32, device=x.device)
-    min_d2 = torch.empty((nq, kdim), dtype=_F32, device=x.device) if want_min_d2 else None
-    nbytes = L.pcrcg_kpconv_ws_bytes(ns)
-    ws = _ws.get("kpconv", nbytes, x.device)
-    w2 = _dev(weights, _F32, "weights").reshape(kdim * cin, -1)
-    _lib.check(L.pcrcg_kpconv_aggregate_ex(q_pts.data_ptr(), nq, s_pts.data_ptr(), ns, idx.data_ptr(), h, ld_idx,
-                                           x.data_ptr(), cin, kp.data_ptr(), float(extent), _ptr(off), ld_off,
-                                           _INFLUENCE[influence], int(aggregation == "closest"), int(bool(modulated)),
-                                           wf.data_ptr(), inv_n.data_ptr(), _ptr(min_d2), ws.data_ptr(), nbytes,
-                                           _stream()), "pcrcg_kpconv_aggregate_ex")
-    out = gemm(wf, w2, row_scale=inv_n)
-    return (out, min_d2) if want_min_d2 else out
+    _check_mode(influence, aggregation)
+    a = _kpconv_args("kpconv_ex", q_pts, s_pts, idx, x, kernel_points, offset_features, modulated, want_min_d2=want_min_d2)
+    w2 = _dev(_pad_cin(weights, a.pad), _F32, "weights").reshape(a.kdim * a.cin, -1)
+    _kpconv_gather(a, extent, ex=(_INFLUENCE[influence], int(aggregation == "closest"), int(bool(modulated))))
+    out = gemm(a.wf, w2, row_scale=a.inv_n)
+    return (out, a.min_d2) if want_min_d2 else out
 
 
 def kpconv_backward_ex(q_pts, s_pts, idx, x, kernel_points, extent, d_wf, offset_features=None, influence="linear",
@@ -545,39 +555,16 @@ def kpconv_backward_ex(q_pts, s_pts, idx, x, kernel_points, extent, d_wf, offset
     """pcrcg_kpconv_backward_ex (include/pcrcg_train.h): the backward of the gather of `kpconv_ex`.  d_wf [nq, 15 * cin] is
     the gradient of the wf the forward stored; x [ns, cin] with cin == 1, cin <= 4 or a multiple of 4 (the caller pads, as
     `kpconv_ex` does).  -> (dx [ns, cin] or None, d_off [nq, 3K or 4K] or None)."""
-    L = _lib.lib()
-    if influence not in _INFLUENCE:
-        raise ValueError("Unknown influence function type (config.KP_influence)")
-    if aggregation not in ("sum", "closest"):
-        raise ValueError("Unknown convolution mode. Should be 'closest' or 'sum'")
-    q_pts = _dev(q_pts, _F32, "q_pts").contiguous()
-    s_pts = _dev(s_pts, _F32, "s_pts").contiguous()
-    idx, ld_idx = _rows(idx, _I64, "neighb_inds")
-    x = _dev(x, _F32, "x").contiguous()
-    kp = _dev(kernel_points, _F32, "kernel_points").contiguous()
-    d_wf = _dev(d_wf, _F32, "d_wf").contiguous()
-    nq, h = idx.shape
-    ns, cin = x.shape
-    kdim = kp.shape[0]
-    if kdim != 15:
-        raise RuntimeError("pcrcg_amd.kpconv_backward_ex: only 15 kernel points are supported")
-    if tuple(d_wf.shape) != (nq, kdim * cin):
-        raise RuntimeError("pcrcg_amd.kpconv_backward_ex: d_wf must be [nq, 15 * cin]")
-    off, ld_off = None, 0
-    cols = (4 if modulated else 3) * kdim
-    if offset_features is not None:
-        off, ld_off = _rows(offset_features, _F32, "offset_features")
-        if off.shape[0] != nq or off.shape[1] < cols:
-            raise RuntimeError("pcrcg_amd.kpconv_backward_ex: offset_features must be [nq, 3K] ([nq, 4K] when modulated)")
-    elif modulated:
-        raise RuntimeError("pcrcg_amd.kpconv_backward_ex: modulated needs offset_features")
-    dx = torch.zeros((ns, cin), dtype=_F32, device=x.device) if want_dx else None
-    d_off = torch.empty((nq, cols), dtype=_F32, device=x.device) if (want_d_off and off is not None) else None
-    _lib.check(L.pcrcg_kpconv_backward_ex(q_pts.data_ptr(), nq, s_pts.data_ptr(), ns, idx.data_ptr(), h, ld_idx,
-                                          x.data_ptr(), cin, kp.data_ptr(), float(extent), _ptr(off), ld_off,
-                                          _INFLUENCE[influence], int(aggregation == "closest"), int(bool(modulated)),
-                                          d_wf.data_ptr(), _ptr(dx), _ptr(d_off), cols, _stream()),
-               "pcrcg_kpconv_backward_ex")
+    _check_mode(influence, aggregation)
+    a = _kpconv_args("kpconv_backward_ex", q_pts, s_pts, idx, x, kernel_points, offset_features, modulated, d_wf=d_wf, pad=False,
+                     scratch=False, wf=False)
+    dx = torch.zeros((a.ns, a.cin), dtype=_F32, device=a.x.device) if want_dx else None
+    d_off = torch.empty((a.nq, a.cols), dtype=_F32, device=a.x.device) if (want_d_off and a.off is not None) else None
+    _lib.check(_lib.lib().pcrcg_kpconv_backward_ex(a.q_pts.data_ptr(), a.nq, a.s_pts.data_ptr(), a.ns, a.idx.data_ptr(), a.h,
+                                                   a.ld_idx, a.x.data_ptr(), a.cin, a.kp.data_ptr(), float(extent), _ptr(a.off),
+                                                   a.ld_off, _INFLUENCE[influence], int(aggregation == "closest"),
+                                                   int(bool(modulated)), a.d_wf.data_ptr(), _ptr(dx), _ptr(d_off), a.cols,
+                                                   _stream()), "pcrcg_kpconv_backward_ex")
     return dx, d_off
 
 
@@ -690,30 +677,20 @@ def kpconv_bf16(q_pts, s_pts, idx, x, kernel_points, weights, extent, intermedia
     """KPConv.forward of the bf16 feature-storage VARIANT (pcrcg_model.feature_bf16): the gathers read a bf16 copy of
     x, the aggregate is bf16 in memory, the contraction takes it as the bf16 operand against the exactly split fp32
     weights.  cin % 32 == 0.  intermediates=True also returns (x_bf16, wf_bf16, inv_n) as int16 / fp32 tensors."""
-    L = _lib.lib()
-    q_pts, s_pts = _dev(q_pts, _F32, "q_pts").contiguous(), _dev(s_pts, _F32, "s_pts").contiguous()
-    idx, ld_idx = _rows(idx, _I64, "idx")
-    x = _dev(x, _F32, "x").contiguous()
-    kernel_points = _dev(kernel_points, _F32, "kernel_points").contiguous()
-    nq, ns, h, cin, cout = q_pts.shape[0], s_pts.shape[0], idx.shape[1], x.shape[1], weights.shape[2]
-    if cin % 32:
+    a = _kpconv_args("kpconv_bf16", q_pts, s_pts, idx, x, kernel_points, idx_name="idx", k15=False, pad=False, wf=False)
+    cout = weights.shape[2]
+    if a.cin % 32:
         raise RuntimeError("pcrcg_amd.kpconv_bf16: cin must be a multiple of 32")
-    kk = 15 * cin
+    kk = 15 * a.cin
     wt = _dev(weights, _F32, "weights").reshape(-1, cout).t().contiguous()           # [cout, 15*cin], K-contiguous
-    xb = torch.empty((ns, cin), dtype=torch.int16, device=x.device)
-    wfb = torch.empty((nq, kk), dtype=torch.int16, device=x.device)
-    inv_n = torch.empty(nq, dtype=_F32, device=x.device)
-    out = torch.empty((nq, cout), dtype=_F32, device=x.device)
-    nbytes = L.pcrcg_kpconv_ws_bytes(ns)
-    ws = _ws.get("kpconv", nbytes, x.device)
-    _lib.check(L.pcrcg_kpconv_aggregate_bf16(q_pts.data_ptr(), nq, s_pts.data_ptr(), ns, idx.data_ptr(), h, ld_idx,
-                                             x.data_ptr(), cin, kernel_points.data_ptr(), float(extent), xb.data_ptr(),
-                                             wfb.data_ptr(), inv_n.data_ptr(), ws.data_ptr(), nbytes, _stream()),
-               "pcrcg_kpconv_aggregate_bf16")
-    _lib.check(L.pcrcg_gemm_bf16a_f32_colstats(wfb.data_ptr(), kk, wt.data_ptr(), kk, out.data_ptr(), cout, nq, cout, kk,
-                                               inv_n.data_ptr(), None, None, 0, None, _stream()),
+    xb = torch.empty((a.ns, a.cin), dtype=torch.int16, device=a.x.device)
+    wfb = torch.empty((a.nq, kk), dtype=torch.int16, device=a.x.device)
+    out = torch.empty((a.nq, cout), dtype=_F32, device=a.x.device)
+    _kpconv_gather(a, extent, bf16=(xb, wfb))
+    _lib.check(_lib.lib().pcrcg_gemm_bf16a_f32_colstats(wfb.data_ptr(), kk, wt.data_ptr(), kk, out.data_ptr(), cout, a.nq, cout,
+                                                        kk, a.inv_n.data_ptr(), None, None, 0, None, _stream()),
                "pcrcg_gemm_bf16a_f32_colstats")
-    return (out, xb, wfb, inv_n) if intermediates else out
+    return (out, xb, wfb, a.inv_n) if intermediates else out
 
 
 def gemm_bf16a(a_bf16, b, row_scale=None, bias=None):

@@ -21,8 +21,8 @@ LIB = os.path.join(REPO, "scripts", "micro", "libpcrcg_hip_knock.so")   # a wron
 FAMILIES = [("pcrcg_copy2d(", "K_COPY"), ("pcrcg_gather_max(", "K_GMAX"), ("pcrcg_instnorm_colsums(", "K_CSUM"),
             ("pcrcg_instnorm_stats_from_partials(", "K_CFIN"), ("pcrcg_instnorm_apply_sums(", "K_APPLY"),
             ("pcrcg_instnorm_apply(", "K_APPLY"), ("instnorm_apply_pack(t.p[g]", "K_PACK"), ("pcrcg_attention(q.p[g]", "K_ATT"),
-            ("pcrcg_edgeconv_reduce_sums(", "K_EDGE"), ("kpconv_aggregate_rows(q[g], nq[g]", "K_GATH"),
-            ("pcrcg_kpconv_aggregate(q[g], nq[g]", "K_GATH"), ("pcrcg_knn(coords[g]", "K_KNN")]
+            ("pcrcg_edgeconv_reduce_sums(", "K_EDGE"), ("kpconv_run(gather)", "K_GATH"),
+            ("pcrcg_knn(coords[g]", "K_KNN")]
 
 
 def build():
