@@ -957,6 +957,78 @@ int pcrcg_icp_batch(const float* src, const int* src_off, int n_total, int n_max
                     double relative_fitness, double relative_rmse, double* out_transform, double* out_stats,
                     const pcrcg_icp_trace* trace, void* ws, size_t ws_bytes, void* stream);
 
+/* Normal estimation: surface normals of B ragged clouds in ONE launch (csrc/normals.hip; added under ABI version 4, which
+ * it does not change) -- open3d's estimate_normals(KDTreeSearchParamHybrid(radius, max_nn)), what
+ * ref:datasets/visualize.py:154-155 calls, restated as a deterministic algorithm; no bit parity with open3d is claimed.
+ * DESIGN.md section 10 defines it, tests/normals_ref.py restates it in numpy.
+ *   Layout: pts [n_total, 3] f32, the B clouds concatenated; off [B + 1] i32 DEVICE row offsets, never read by the host;
+ *   grid = pcrcg_cellgrid_build over the same points with nb = B, slen = the cloud lengths and radius = (float)radius.
+ *   n_max (host) >= every cloud's length sizes the launch (rows of a longer cloud past n_max are not written).
+ *   viewpoints [B, 3] f64 DEVICE, or NULL: the origin (the sensor of a KITTI scan).
+ *   Outputs: normals [n_total, 3] f64; optional (NULL: not written), for tests: count [n_total] i32 and cov [n_total, 6] f64.
+ *   Definition, per point p_i of a cloud:
+ *     Neighbours: the cloud's own points with d2 < (float)radius * (float)radius, d2 = ((dx dx + dy dy) + dz dz) in fp32,
+ *       unfused; p_i itself is one of them.  They are taken in ascending (d2, cloud-local index) order and cut to the
+ *       first max_nn: the library's radius-query contract, and open3d's hybrid search.  count = the length after the cut.
+ *     Moments: d_k = (double)q_k - (double)p_i, k = count: m = sum d_k / k, C = sum d_k d_k^T / k - m m^T, in float64; the
+ *       sums are taken over the neighbours in their (d2, index) order by a 64-lane shuffle tree (lane j holds neighbour j,
+ *       zero beyond count), so they are a function of the row alone.  No floating-point atomics.
+ *       cov = (xx, xy, xz, yy, yz, zz) of C.
+ *     Normal: the unit eigenvector of C's smallest eigenvalue, by a float64 cyclic Jacobi on the symmetric 3 x 3 matrix
+ *       (csrc/smallsolve.h).  count < 3, or C identically zero or not finite, gives (0, 0, 1) -- as it stands: the sign
+ *       rule is not applied to this fallback.
+ *     Sign: flipped so that n . (v - p_i) >= 0 with v the cloud's viewpoint; if that product is exactly 0, so that the
+ *       first non-zero component is positive.
+ *   A point with a NaN coordinate, or beyond 2^20 cells of the radius, has no neighbours (count = 0).
+ *   The entry allocates nothing, synchronises nothing and reads nothing back.  Null pts / off / grid / normals / ws, B
+ *   outside 1..65535, radius <= 0 or NaN, max_nn outside 1..64 and n_max > n_total are rejected with PCRCG_EBADARG before
+ *   any launch; a short workspace with PCRCG_EWORKSPACE.  Workspace: pcrcg_estimate_normals_ws_bytes(B, n_total) (256 bytes
+ *   today: the neighbour lists live in LDS); 0 for B outside 1..65535 or a negative n_total. */
+size_t pcrcg_estimate_normals_ws_bytes(int B, int n_total);
+int pcrcg_estimate_normals_batch(const float* pts, const int* off, int n_total, int n_max, const void* grid, int B, double radius,
+                                 int max_nn, const double* viewpoints, double* normals, int* count, double* cov, void* ws,
+                                 size_t ws_bytes, void* stream);
+
+/* ICP refinement with a choice of estimator (csrc/icp.hip; added under ABI version 4, which it does not change).
+ * Everything pcrcg_icp_batch takes, plus
+ *   estimation: 0 = point-to-point -- every output is pcrcg_icp_batch's, bit for bit; 1 = point-to-plane, open3d's
+ *     TransformationEstimationPointToPlane;
+ *   tgt_normals [m_total, 3] f64 DEVICE, in the targets' row order (pcrcg_estimate_normals_batch's output); required
+ *     for estimation = 1, not read for 0.
+ * Point-to-plane differs from the definition above in the update alone.  Evaluate(T) is unchanged -- the same moved point,
+ * nearest target, tie rule, count, fitness and Euclidean rmse -- and convergence is tested on those, as open3d's loop does.
+ *   Update: over the correspondences, with p the moved source point (the float64 value of the fp32 result), q its target
+ *     and n the target's normal: r = ((p - q) . n), J = [p x n, n] (6 entries); A = sum J J^T (the 21 entries of the upper
+ *     triangle, row by row), b = -sum J r (6), in float64 and in the fixed order of the other sums (shuffle tree, the eight
+ *     wavefronts in order, the workgroups in order).  A x = b is solved by LDL^T with diagonal pivoting in float64
+ *     (csrc/smallsolve.h) in the one lane that runs the Kabsch fit of estimation 0.  The pair stops, keeping T, if
+ *     count < 6 or a pivot is <= 1e-12 times the largest (the relative rule of the Kabsch fit's sigma_2 <= 1e-12 sigma_1): a
+ *     planar set of correspondences is degenerate.  delta = Rz(x2) Ry(x1) Rx(x0) | (x3, x4, x5), open3d's
+ *     TransformVector6dToMatrix4d; T <- delta T in float64.
+ *   A and b are even in n (every term holds n twice), so the result does not depend on the normals' signs, bit for bit.
+ *   A normal that is not finite makes the pair's system not finite: the pair stops as a degenerate one.
+ *   Outputs, the NaN rules, empty pairs, the `done` word and the launch count are pcrcg_icp_batch's.
+ *   trace: pcrcg_icp_trace's members, plus sums27 [B, max_iteration + 1, 27] f64 = A's upper triangle then b of
+ *   Evaluate(T_k) (written for estimation = 1 only).
+ *   Workspace: pcrcg_icp_batch_ex_ws_bytes(B, n_total, m_total, max_iteration) = 152 B + 228 (n_total / 512 + B + 1) bytes
+ *   plus alignment padding, enough for either estimator; 0 as pcrcg_icp_batch_ws_bytes.  Bad arguments (pcrcg_icp_batch's,
+ *   an estimation other than 0 or 1, estimation = 1 without normals) give PCRCG_EBADARG, a short workspace
+ *   PCRCG_EWORKSPACE, before anything launches. */
+typedef struct pcrcg_icp_trace_ex {
+    double* transforms;
+    int* counts;
+    double* sums;
+    int* corr;
+    double* sums27;
+} pcrcg_icp_trace_ex;
+
+size_t pcrcg_icp_batch_ex_ws_bytes(int B, int n_total, int m_total, int max_iteration);
+int pcrcg_icp_batch_ex(const float* src, const int* src_off, int n_total, int n_max, const int* tgt_off, int m_total,
+                       const void* grid, const double* init, int B, double max_correspondence_distance, int max_iteration,
+                       double relative_fitness, double relative_rmse, int estimation, const double* tgt_normals,
+                       double* out_transform, double* out_stats, const pcrcg_icp_trace_ex* trace, void* ws, size_t ws_bytes,
+                       void* stream);
+
 /* Voxel down-sampling: open3d's PointCloud::VoxelDownSample for B ragged clouds in one set of launches (csrc/voxel.hip;
  * added under ABI version 4, which it does not change) -- what ref:datasets/kitti.py:134-140 does to both raw scans of a
  * pair before anything else sees them, and how raw 3DMatch fragments become the 2.5 cm clouds of ref:datasets/indoor.py.

@@ -163,6 +163,14 @@ SIGNATURES = {
     "pcrcg_icp_batch": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, ctypes.c_double,
                                 c_int, ctypes.c_double, ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
                                 c_void_p]),
+    # normals and the estimator choice of the ICP refinement (registration.estimate_normals_batch, refine_batch)
+    "pcrcg_estimate_normals_ws_bytes": (c_size_t, [c_int, c_int]),
+    "pcrcg_estimate_normals_batch": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, ctypes.c_double, c_int, c_void_p,
+                                             c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "pcrcg_icp_batch_ex_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "pcrcg_icp_batch_ex": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, ctypes.c_double,
+                                   c_int, ctypes.c_double, ctypes.c_double, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                   c_void_p, c_size_t, c_void_p]),
     # voxel down-sampling of raw scans (pcrcg_amd/kitti.py)
     "pcrcg_voxel_down_sample_ws_bytes": (c_size_t, [c_int, c_int]),
     "pcrcg_voxel_down_sample_batch": (c_int, [c_void_p, c_void_p, c_int, c_int, ctypes.c_double, c_void_p, c_void_p, c_void_p,

@@ -14,6 +14,11 @@
 //              applies the convergence test, fits delta (kabsch.h, the device function of RANSAC's hypotheses) and sets
 //              T <- delta T in float64 -- or finishes the pair: writes its outputs and sets its `done` word.
 //
+// pcrcg_icp_batch_ex adds TransformationEstimationPointToPlane as a second estimator (template argument EST = 1 of the two
+// kernels; EST = 0 is the code above, bit for bit): the evaluation is the same, its sums are d2, the upper triangle of
+// sum J J^T and -sum J r with r = (p - q) . n, J = [p x n, n] from the targets' normals (normals.hip), and the update solves
+// the 6 x 6 system by a pivoted LDL^T (smallsolve.h) and applies Rz Ry Rx | t of the solution.
+//
 // All max_iteration + 1 evaluations are enqueued ahead; the host reads nothing in between.  The workgroups of a pair whose
 // `done` word is set leave at once.  No floating-point atomics: a pair's bits depend on its own points and T_0 alone.
 //
@@ -21,6 +26,7 @@
 #include "cellgrid.h"
 #include "common.h"
 #include "kabsch.h"
+#include "smallsolve.h"
 
 namespace pcrcg {
 namespace {
@@ -28,6 +34,8 @@ namespace {
 constexpr int kIcpThreads = 512;                  // evaluation workgroup: 512 consecutive source rows of one pair
 constexpr int kIcpWaves = kIcpThreads / kWave;
 constexpr int kIcpTerms = 16;                     // sum d2 | sum p [3] | sum q [3] | sum p q^T [9]
+constexpr int kIcpPlaneTerms = 28;                // sum d2 | sum J J^T, upper triangle [21] | -sum J r [6]
+template <int EST> constexpr int icp_terms() { return EST == 0 ? kIcpTerms : kIcpPlaneTerms; }   // EST 0: point-to-point, 1: point-to-plane
 constexpr int kIcpMaxIteration = 1 << 16;
 constexpr int kIcpMaxBatch = 65535;               // pairs ride on a grid dimension
 
@@ -45,13 +53,15 @@ struct IcpArgs {
     const double* init;   // [B, 16] or null (identity)
     IcpPair* state;       // [B]
     int* p_cnt;           // [slots]      the workgroups' partial counts ...
-    double* p_sum;        // [slots, 16]  ... and sums; pair p's workgroups start at slot src_off[p] / 512 + p
+    double* p_sum;        // [slots, 16 or 28]  ... and sums; pair p's workgroups start at slot src_off[p] / 512 + p
     double* out_t;        // [B, 16]
     double* out_stats;    // [B, 4]
     double* tr_t;         // [B, max_iteration + 1, 16] or null
     int* tr_counts;       // [B, max_iteration + 1] or null
     double* tr_sums;      // [B, max_iteration + 1] or null
     int* tr_corr;         // [max_iteration + 1, n_total] or null
+    const double* tgt_nrm;// [m_total, 3] point-to-plane: the targets' normals
+    double* tr_sums27;    // [B, max_iteration + 1, 27] or null (point-to-plane)
     int n_total, n_max, max_iteration;
     float thr2;
     double rel_fitness, rel_rmse;
@@ -71,8 +81,10 @@ __global__ void __launch_bounds__(256) k_icp_init(IcpArgs a, int B) {
 }
 
 // Evaluate(T_it) of every live pair; grid (row blocks, pair)
+template <int EST>
 __global__ void __launch_bounds__(kIcpThreads) k_icp_evaluate(IcpArgs a, GridView g, int it) {
-    __shared__ double s_sum[kIcpWaves][kIcpTerms];
+    constexpr int kTerms = icp_terms<EST>();
+    __shared__ double s_sum[kIcpWaves][kTerms];
     __shared__ int s_cnt[kIcpWaves];
     const int p = blockIdx.y;
     const IcpPair* st = a.state + p;
@@ -124,10 +136,10 @@ __global__ void __launch_bounds__(kIcpThreads) k_icp_evaluate(IcpArgs a, GridVie
     }
     const bool hit = bj >= 0;                 // best < thr2: bj is only ever set by a d2 below the start value or equal to a set one
     if (a.tr_corr && i < n) a.tr_corr[(long)it * a.n_total + i0 + i] = hit ? bj - j0 : -1;
-    double v[kIcpTerms];
-    {
-        const double P[3] = {(double)px, (double)py, (double)pz}, Q[3] = {(double)qx, (double)qy, (double)qz};
-        v[0] = hit ? (double)best : 0.0;
+    double v[kTerms];
+    const double P[3] = {(double)px, (double)py, (double)pz}, Q[3] = {(double)qx, (double)qy, (double)qz};
+    v[0] = hit ? (double)best : 0.0;
+    if constexpr (EST == 0) {
 #pragma unroll
         for (int r = 0; r < 3; ++r) {
             v[1 + r] = hit ? P[r] : 0.0;
@@ -135,26 +147,39 @@ __global__ void __launch_bounds__(kIcpThreads) k_icp_evaluate(IcpArgs a, GridVie
 #pragma unroll
             for (int c = 0; c < 3; ++c) v[7 + 3 * r + c] = hit ? P[r] * Q[c] : 0.0;
         }
+    } else {
+        // residual r = (p - q) . n and its Jacobian J = [p x n, n] about the moved point; both even in n as J J^T and J r
+        double N[3] = {0.0, 0.0, 0.0};
+        if (hit) { const double* nr = a.tgt_nrm + 3 * (long)bj; N[0] = nr[0]; N[1] = nr[1]; N[2] = nr[2]; }
+        const double res = ((P[0] - Q[0]) * N[0] + (P[1] - Q[1]) * N[1]) + (P[2] - Q[2]) * N[2];
+        const double J[6] = {P[1] * N[2] - P[2] * N[1], P[2] * N[0] - P[0] * N[2], P[0] * N[1] - P[1] * N[0], N[0], N[1], N[2]};
+        int e = 1;
+#pragma unroll
+        for (int r = 0; r < 6; ++r)
+#pragma unroll
+            for (int c = r; c < 6; ++c) v[e++] = hit ? J[r] * J[c] : 0.0;
+#pragma unroll
+        for (int r = 0; r < 6; ++r) v[22 + r] = hit ? -(J[r] * res) : 0.0;
     }
     // fixed order: the wavefront's tree, then (below) the eight wavefronts one after the other
 #pragma unroll
-    for (int e = 0; e < kIcpTerms; ++e)
+    for (int e = 0; e < kTerms; ++e)
 #pragma unroll
         for (int sh = kWave / 2; sh >= 1; sh >>= 1) v[e] = v[e] + __shfl_down(v[e], sh, kWave);
     const int cnt = (int)__popcll(__ballot(hit));
     const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
     if (lane == 0) {
 #pragma unroll
-        for (int e = 0; e < kIcpTerms; ++e) s_sum[wave][e] = v[e];
+        for (int e = 0; e < kTerms; ++e) s_sum[wave][e] = v[e];
         s_cnt[wave] = cnt;
     }
     __syncthreads();
     const long slot = first_slot(a, p) + blockIdx.x;
-    if (threadIdx.x < kIcpTerms) {
+    if (threadIdx.x < kTerms) {
         double s = s_sum[0][threadIdx.x];
         for (int w = 1; w < kIcpWaves; ++w) s = s + s_sum[w][threadIdx.x];
-        a.p_sum[kIcpTerms * slot + threadIdx.x] = s;
-    } else if (threadIdx.x == kIcpTerms) {
+        a.p_sum[kTerms * slot + threadIdx.x] = s;
+    } else if (threadIdx.x == kTerms) {
         int c = 0;
         for (int w = 0; w < kIcpWaves; ++w) c += s_cnt[w];
         a.p_cnt[slot] = c;
@@ -171,8 +196,10 @@ __device__ inline void icp_finish(const IcpArgs& a, int p, IcpPair* st, const do
 }
 
 // After Evaluate(T_it): one wavefront per pair
+template <int EST>
 __global__ void __launch_bounds__(kWave) k_icp_update(IcpArgs a, int it) {
-    __shared__ double s_tot[kIcpTerms];
+    constexpr int kTerms = icp_terms<EST>();
+    __shared__ double s_tot[kTerms];
     __shared__ int s_count;
     const int p = blockIdx.x;
     IcpPair* st = a.state + p;
@@ -180,11 +207,11 @@ __global__ void __launch_bounds__(kWave) k_icp_update(IcpArgs a, int it) {
     const int n = a.src_off[p + 1] - a.src_off[p];
     const int nblk = n <= a.n_max ? (n + kIcpThreads - 1) / kIcpThreads : 0;
     const long slot0 = first_slot(a, p);
-    if (threadIdx.x < kIcpTerms) {
+    if (threadIdx.x < kTerms) {
         double s = 0.0;
-        for (int b = 0; b < nblk; ++b) s = s + a.p_sum[kIcpTerms * (slot0 + b) + threadIdx.x];
+        for (int b = 0; b < nblk; ++b) s = s + a.p_sum[kTerms * (slot0 + b) + threadIdx.x];
         s_tot[threadIdx.x] = s;
-    } else if (threadIdx.x == kIcpTerms) {
+    } else if (threadIdx.x == kTerms) {
         int c = 0;
         for (int b = 0; b < nblk; ++b) c += a.p_cnt[slot0 + b];
         s_count = c;
@@ -215,8 +242,30 @@ __global__ void __launch_bounds__(kWave) k_icp_update(IcpArgs a, int it) {
     const bool converged = it > 0 && fabs(fitness - st->fitness) < a.rel_fitness && fabs(rmse - st->rmse) < a.rel_rmse;
     st->fitness = fitness;
     st->rmse = rmse;
-    if (converged || it >= a.max_iteration || count < 3) {
+    if constexpr (EST == 1) {
+        if (a.tr_sums27)
+            for (int e = 0; e < 27; ++e) a.tr_sums27[27 * tslot + e] = s_tot[1 + e];
+    }
+    if (converged || it >= a.max_iteration || count < (EST == 0 ? 3 : 6)) {
         icp_finish(a, p, st, T, fitness, rmse, count, it);
+        return;
+    }
+    if constexpr (EST == 1) {
+        // Gauss-Newton step of sum r^2: (sum J J^T) x = -sum J r; delta = Rz(x2) Ry(x1) Rx(x0) | (x3, x4, x5)
+        double x[6];
+        if (!solve_ldlt6(s_tot + 1, s_tot + 22, x)) {
+            icp_finish(a, p, st, T, fitness, rmse, count, it);
+            return;
+        }
+        const double ca = cos(x[0]), sa = sin(x[0]), cb = cos(x[1]), sb = sin(x[1]), cg = cos(x[2]), sg = sin(x[2]);
+        const double R[9] = {cg * cb, cg * sb * sa - sg * ca, cg * sb * ca + sg * sa,
+                             sg * cb, sg * sb * sa + cg * ca, sg * sb * ca - cg * sa,
+                             -sb,     cb * sa,                cb * ca};
+        for (int r = 0; r < 3; ++r)
+            for (int c = 0; c < 4; ++c) {
+                const double v = (R[3 * r] * T[c] + R[3 * r + 1] * T[4 + c]) + R[3 * r + 2] * T[8 + c];
+                st->T[4 * r + c] = c == 3 ? v + x[3 + r] : v;
+            }
         return;
     }
     // Kabsch from the raw sums: centroids cs = sum p / count, ct = sum q / count, H = sum p q^T - (sum p) ct^T.  A difference
@@ -250,13 +299,71 @@ struct IcpWs {
 
 size_t icp_slots(int B, int n_total) { return (size_t)n_total / kIcpThreads + (size_t)B + 1; }
 
-IcpWs carve_icp(Carver& cv, int B, int n_total) {
+IcpWs carve_icp(Carver& cv, int B, int n_total, int terms = kIcpTerms) {
     IcpWs w;
     w.state = cv.take<IcpPair>((size_t)B);
     w.p_cnt = cv.take<int>(icp_slots(B, n_total));
-    w.p_sum = cv.take<double>(icp_slots(B, n_total) * kIcpTerms);
+    w.p_sum = cv.take<double>(icp_slots(B, n_total) * terms);
     return w;
 }
+
+// the launches of either estimator: init, then max_iteration + 1 evaluate / update pairs
+template <int EST>
+int icp_enqueue(const IcpArgs& a, const GridView& g, int B, hipStream_t st) {
+    hipLaunchKernelGGL(k_icp_init, dim3((B + 255) / 256), dim3(256), 0, st, a, B);
+    PCRCG_CHECK_LAUNCH();
+    const dim3 eval_grid(a.n_max > 0 ? (a.n_max + kIcpThreads - 1) / kIcpThreads : 1, B);
+    for (int it = 0; it <= a.max_iteration; ++it) {
+        hipLaunchKernelGGL(k_icp_evaluate<EST>, eval_grid, dim3(kIcpThreads), 0, st, a, g, it);
+        hipLaunchKernelGGL(k_icp_update<EST>, dim3(B), dim3(kWave), 0, st, a, it);
+    }
+    PCRCG_CHECK_LAUNCH();
+    return PCRCG_OK;
+}
+
+// Both entries: the argument rules (reported under the entry's own name `who`), the workspace, the launches
+#define ICP_CHECK_ARG(cond)                                          \
+    do {                                                             \
+        if (!(cond)) {                                               \
+            set_error("%s: bad argument: %s", who, #cond);           \
+            return PCRCG_EBADARG;                                    \
+        }                                                            \
+    } while (0)
+
+int icp_run(const char* who, const float* src, const int* src_off, int n_total, int n_max, const int* tgt_off, int m_total,
+            const void* grid, const double* init, int B, double max_correspondence_distance, int max_iteration,
+            double relative_fitness, double relative_rmse, int estimation, const double* tgt_normals, double* out_transform,
+            double* out_stats, const pcrcg_icp_trace_ex& trace, void* ws, size_t ws_bytes, void* stream) {
+    ICP_CHECK_ARG(src_off && tgt_off && grid && out_transform && out_stats && ws);
+    ICP_CHECK_ARG(B >= 1 && B <= kIcpMaxBatch);
+    ICP_CHECK_ARG(n_total >= 0 && m_total >= 0 && n_max >= 0 && n_max <= n_total);
+    ICP_CHECK_ARG(n_total == 0 || src);
+    ICP_CHECK_ARG(max_correspondence_distance > 0.0 && max_correspondence_distance < 1e18);
+    ICP_CHECK_ARG(max_iteration >= 1 && max_iteration <= kIcpMaxIteration);
+    ICP_CHECK_ARG(relative_fitness >= 0.0 && relative_rmse >= 0.0);      // (false for a NaN)
+    ICP_CHECK_ARG(estimation == 0 || estimation == 1);
+    ICP_CHECK_ARG(estimation == 0 || m_total == 0 || tgt_normals);
+    Carver cv(ws, ws_bytes);
+    IcpWs w = carve_icp(cv, B, n_total, estimation == 0 ? kIcpTerms : kIcpPlaneTerms);
+    if (!cv.ok()) {
+        set_error("%s: workspace too small (%zu needed, %zu given)", who, cv.off, cv.cap);
+        return PCRCG_EWORKSPACE;
+    }
+    bool ok;
+    GridView g = grid_view(const_cast<void*>(grid), grid_bytes(m_total, B), m_total, B, &ok);
+    IcpArgs a;
+    a.src = src; a.src_off = src_off; a.tgt_off = tgt_off; a.init = init;
+    a.state = w.state; a.p_cnt = w.p_cnt; a.p_sum = w.p_sum;
+    a.out_t = out_transform; a.out_stats = out_stats;
+    a.tr_t = trace.transforms; a.tr_counts = trace.counts; a.tr_sums = trace.sums; a.tr_corr = trace.corr;
+    a.tgt_nrm = tgt_normals;
+    a.tr_sums27 = estimation == 1 ? trace.sums27 : nullptr;
+    a.n_total = n_total; a.n_max = n_max; a.max_iteration = max_iteration;
+    a.thr2 = (float)(max_correspondence_distance * max_correspondence_distance);
+    a.rel_fitness = relative_fitness; a.rel_rmse = relative_rmse;
+    return estimation == 0 ? icp_enqueue<0>(a, g, B, as_stream(stream)) : icp_enqueue<1>(a, g, B, as_stream(stream));
+}
+#undef ICP_CHECK_ARG
 
 }  // namespace
 }  // namespace pcrcg
@@ -276,39 +383,28 @@ int pcrcg_icp_batch(const float* src, const int* src_off, int n_total, int n_max
                     const void* grid, const double* init, int B, double max_correspondence_distance, int max_iteration,
                     double relative_fitness, double relative_rmse, double* out_transform, double* out_stats,
                     const pcrcg_icp_trace* trace, void* ws, size_t ws_bytes, void* stream) {
-    PCRCG_CHECK_ARG(src_off && tgt_off && grid && out_transform && out_stats && ws);
-    PCRCG_CHECK_ARG(B >= 1 && B <= kIcpMaxBatch);
-    PCRCG_CHECK_ARG(n_total >= 0 && m_total >= 0 && n_max >= 0 && n_max <= n_total);
-    PCRCG_CHECK_ARG(n_total == 0 || src);
-    PCRCG_CHECK_ARG(max_correspondence_distance > 0.0 && max_correspondence_distance < 1e18);
-    PCRCG_CHECK_ARG(max_iteration >= 1 && max_iteration <= kIcpMaxIteration);
-    PCRCG_CHECK_ARG(relative_fitness >= 0.0 && relative_rmse >= 0.0);      // (false for a NaN)
-    Carver cv(ws, ws_bytes);
-    IcpWs w = carve_icp(cv, B, n_total);
-    PCRCG_CHECK_WS(cv);
-    bool ok;
-    GridView g = grid_view(const_cast<void*>(grid), grid_bytes(m_total, B), m_total, B, &ok);
-    hipStream_t st = as_stream(stream);
-    IcpArgs a;
-    a.src = src; a.src_off = src_off; a.tgt_off = tgt_off; a.init = init;
-    a.state = w.state; a.p_cnt = w.p_cnt; a.p_sum = w.p_sum;
-    a.out_t = out_transform; a.out_stats = out_stats;
-    a.tr_t = trace ? trace->transforms : nullptr;
-    a.tr_counts = trace ? trace->counts : nullptr;
-    a.tr_sums = trace ? trace->sums : nullptr;
-    a.tr_corr = trace ? trace->corr : nullptr;
-    a.n_total = n_total; a.n_max = n_max; a.max_iteration = max_iteration;
-    a.thr2 = (float)(max_correspondence_distance * max_correspondence_distance);
-    a.rel_fitness = relative_fitness; a.rel_rmse = relative_rmse;
-    hipLaunchKernelGGL(k_icp_init, dim3((B + 255) / 256), dim3(256), 0, st, a, B);
-    PCRCG_CHECK_LAUNCH();
-    const dim3 eval_grid(n_max > 0 ? (n_max + kIcpThreads - 1) / kIcpThreads : 1, B);
-    for (int it = 0; it <= max_iteration; ++it) {
-        hipLaunchKernelGGL(k_icp_evaluate, eval_grid, dim3(kIcpThreads), 0, st, a, g, it);
-        hipLaunchKernelGGL(k_icp_update, dim3(B), dim3(kWave), 0, st, a, it);
-    }
-    PCRCG_CHECK_LAUNCH();
-    return PCRCG_OK;
+    pcrcg_icp_trace_ex tr = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    if (trace) { tr.transforms = trace->transforms; tr.counts = trace->counts; tr.sums = trace->sums; tr.corr = trace->corr; }
+    return icp_run(__func__, src, src_off, n_total, n_max, tgt_off, m_total, grid, init, B, max_correspondence_distance,
+                   max_iteration, relative_fitness, relative_rmse, 0, nullptr, out_transform, out_stats, tr, ws, ws_bytes, stream);
+}
+
+size_t pcrcg_icp_batch_ex_ws_bytes(int B, int n_total, int m_total, int max_iteration) {
+    if (B < 1 || B > kIcpMaxBatch || n_total < 0 || m_total < 0 || max_iteration < 1 || max_iteration > kIcpMaxIteration) return 0;
+    Carver cv(nullptr, 0);
+    carve_icp(cv, B, n_total, kIcpPlaneTerms);
+    return cv.off;
+}
+
+int pcrcg_icp_batch_ex(const float* src, const int* src_off, int n_total, int n_max, const int* tgt_off, int m_total,
+                       const void* grid, const double* init, int B, double max_correspondence_distance, int max_iteration,
+                       double relative_fitness, double relative_rmse, int estimation, const double* tgt_normals,
+                       double* out_transform, double* out_stats, const pcrcg_icp_trace_ex* trace, void* ws, size_t ws_bytes,
+                       void* stream) {
+    const pcrcg_icp_trace_ex none = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    return icp_run(__func__, src, src_off, n_total, n_max, tgt_off, m_total, grid, init, B, max_correspondence_distance,
+                   max_iteration, relative_fitness, relative_rmse, estimation, tgt_normals, out_transform, out_stats,
+                   trace ? *trace : none, ws, ws_bytes, stream);
 }
 
 }  // extern "C"

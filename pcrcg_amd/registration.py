@@ -9,8 +9,11 @@
                                 `register(..., mutual=False, seed=seeds[b])`'s, bit for bit.
   * `ransac_pose_estimation_batch` -- the same as numpy [B,4,4] (the reference's mutual=False branch, pair by pair).
   * `feature_match_batch`    -- the nearest-neighbour lists of many pairs in one launch set.
-  * `refine_batch`           -- point-to-point ICP of many pairs in one set of launches (`BatchRefinementResult`), the
-                                local pass after RANSAC's global one; `refine` is the same for one pair.
+  * `refine_batch`           -- ICP of many pairs in one set of launches (`BatchRefinementResult`), the local pass after
+                                RANSAC's global one: point-to-point, or point-to-plane on the targets' normals;
+                                `refine` is the same for one pair.
+  * `estimate_normals_batch` -- the normals of many clouds in one launch (open3d's hybrid-search estimate_normals),
+                                float64 device tensors; `estimate_normals` is the same for one cloud.
   * `refine_ground_truth`    -- ref:datasets/kitti.py:111-120: a KITTI ground-truth pose refined by ICP on the raw scans.
   * `mutual_correspondences` -- the mutual pairs of the inner-product score ([K,2] int64 device tensor).
   * `get_inlier_ratio`       -- device version of ref:lib/benchmark_utils.py:226-267 (same `w` / `wo` dict).
@@ -368,13 +371,24 @@ class _IcpTrace(ctypes.Structure):
     _fields_ = [(f, ctypes.c_void_p) for f in ("transforms", "counts", "sums", "corr")]
 
 
+class _IcpTraceEx(ctypes.Structure):
+    """Mirror of pcrcg_icp_trace_ex (include/pcrcg.h)."""
+    _fields_ = [(f, ctypes.c_void_p) for f in ("transforms", "counts", "sums", "corr", "sums27")]
+
+
+_ESTIMATIONS = {"point_to_point": 0, "point_to_plane": 1}
+_MAX_NORMAL_NN = 64   # include/pcrcg.h: one neighbour per lane
+
+
 class BatchRefinementResult:
     """Results of `refine_batch` for B pairs.  transformations: float64 [B,4,4] device tensor; matrices: the same as numpy
     (from the one read); fitness, inlier_rmse: float64 numpy [B]; counts (correspondences of the last evaluation),
     iterations (updates applied): int64 numpy [B] (-1 where the pair's start was not finite: its other outputs are NaN).
     trace: None, or a dict of device tensors -- transforms [B, max_iteration + 1, 4, 4] (T_k), counts and sums
     [B, max_iteration + 1] of Evaluate(T_k), corr: per pair [max_iteration + 1, n_b] int32, the target of every source row
-    or -1 (entries past a pair's last evaluation keep their fill: NaN / -1 / -2)."""
+    or -1 (entries past a pair's last evaluation keep their fill: NaN / -1 / -2).  Point-to-plane adds sums27
+    [B, max_iteration + 1, 27] (the upper triangle of sum J J^T, then -sum J r) and normals: per pair the [M_b,3] float64
+    target normals the updates read."""
 
     def __init__(self, buf, host, B, trace=None):
         self.transformations = buf[:16 * B].view(B, 4, 4)
@@ -419,9 +433,94 @@ def _cloud_rows(x, who, name, b):
     return shape[0]
 
 
+def _check_normal_search(who, radius, max_nn):
+    r, k = float(radius), int(max_nn)
+    if not 0.0 < r < 1e18:
+        raise ValueError(f"{who}: the normal radius must be positive and finite, got {radius}")
+    if not 1 <= k <= _MAX_NORMAL_NN:
+        raise ValueError(f"{who}: max_nn = {k}, need 1..{_MAX_NORMAL_NN}")
+    return r, k
+
+
+def _normals_of(L, pts, off, lengths, n_tot, nb, n_max, radius, max_nn, viewpoints, trace):
+    """pcrcg_estimate_normals_batch over nb concatenated clouds already on the device, on the current stream ->
+    (normals [n_tot,3] float64, counts or None, covariances or None).  Nothing is read back."""
+    dev = pts.device
+    gbytes = L.pcrcg_cellgrid_ws_bytes(n_tot, nb)
+    grid = torch.empty(gbytes, dtype=torch.uint8, device=dev)
+    _lib.check(L.pcrcg_cellgrid_build(pts.data_ptr() if n_tot else None, n_tot, lengths.data_ptr(), nb, radius, grid.data_ptr(),
+                                      gbytes, _stream()), "pcrcg_cellgrid_build")
+    wsb = L.pcrcg_estimate_normals_ws_bytes(nb, n_tot)
+    ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device=dev)
+    nrm = torch.empty((n_tot, 3), dtype=torch.float64, device=dev)
+    cnt = torch.empty(n_tot, dtype=torch.int32, device=dev) if trace else None
+    cov = torch.empty((n_tot, 6), dtype=torch.float64, device=dev) if trace else None
+    _lib.check(L.pcrcg_estimate_normals_batch(pts.data_ptr() if n_tot else None, off.data_ptr(), n_tot, n_max, grid.data_ptr(), nb,
+                                              radius, max_nn, viewpoints.data_ptr() if viewpoints is not None else None,
+                                              nrm.data_ptr() if n_tot else None, cnt.data_ptr() if trace else None,
+                                              cov.data_ptr() if trace else None, ws.data_ptr(), wsb, _stream()),
+               "pcrcg_estimate_normals_batch")
+    return nrm, cnt, cov
+
+
+def estimate_normals_batch(pcds, radius, max_nn=30, *, viewpoints=None, pairs_per_call=None, trace=False):
+    """The normals of B clouds in one launch (pcrcg_estimate_normals_batch; include/pcrcg.h "Normal estimation", DESIGN.md
+    section 10) -> a list of float64 [N_b,3] device tensors; with trace=True -> (normals, counts, covariances), the last two
+    lists of int32 [N_b] and float64 [N_b,6] device tensors.  open3d's estimate_normals(KDTreeSearchParamHybrid(radius,
+    max_nn)), deterministic: cloud b's result depends on its points alone, bit for bit.
+
+    Inputs: a list of [N_b,3] points (numpy, CPU or HIP tensors; empty clouds are allowed).  viewpoints: None (the origin)
+    or [B,3]: every normal points to its cloud's side of it.  pairs_per_call bounds the clouds per launch (default: all).
+    Every size is checked on the host before anything is uploaded or launched; nothing is read back."""
+    B = len(pcds)
+    if B == 0:
+        raise ValueError("estimate_normals_batch: no clouds")
+    r, k = _check_normal_search("estimate_normals_batch", radius, max_nn)
+    if viewpoints is not None:
+        vshape = tuple(viewpoints.shape) if hasattr(viewpoints, "shape") else np.shape(viewpoints)
+        if vshape != (B, 3):
+            raise ValueError(f"estimate_normals_batch: viewpoints must be [{B}, 3] (one per cloud), got shape {vshape}")
+    ns = [_cloud_rows(x, "estimate_normals_batch", "the cloud", b) for b, x in enumerate(pcds)]
+    P = max(1, min(B if pairs_per_call is None else int(pairs_per_call), B, _MAX_BATCH))
+    chunks = [(b0, min(B, b0 + P)) for b0 in range(0, B, P)]
+    if any(sum(ns[b0:b1]) > 0x7FFFFFFF for b0, b1 in chunks):
+        raise ValueError("estimate_normals_batch: more than 2^31 - 1 rows per call; lower pairs_per_call")
+    dev = _device(*pcds, *([viewpoints] if viewpoints is not None else []))
+    L = _lib.lib()
+    view_d = None
+    if viewpoints is not None:
+        view_d = viewpoints if isinstance(viewpoints, torch.Tensor) else torch.from_numpy(np.asarray(viewpoints, dtype=np.float64))
+        view_d = view_d.to(device=dev, dtype=torch.float64).contiguous()
+    normals, counts, covs = [], [], []
+    for b0, b1 in chunks:
+        nb, n_tot = b1 - b0, sum(ns[b0:b1])
+        pts = _cat(pcds[b0:b1], dev, "pcds", 3)
+        offs = torch.tensor(np.concatenate([np.cumsum([0] + ns[b0:b1]), ns[b0:b1]]), dtype=torch.int32, device=dev)
+        nrm, cnt, cov = _normals_of(L, pts, offs[:nb + 1], offs[nb + 1:], n_tot, nb, max(ns[b0:b1]), r, k,
+                                    view_d[b0:b1] if view_d is not None else None, trace)
+        normals += list(nrm.split(ns[b0:b1]))
+        if trace:
+            counts += list(cnt.split(ns[b0:b1]))
+            covs += list(cov.split(ns[b0:b1]))
+    return (normals, counts, covs) if trace else normals
+
+
+def estimate_normals(pcd, radius, max_nn=30, *, viewpoint=None, trace=False):
+    """The normals of one cloud: estimate_normals_batch with a batch of one (viewpoint: None or 3 numbers) -> float64 [N,3]
+    device tensor; with trace=True -> (normals, counts, covariances)."""
+    if viewpoint is not None:
+        vshape = tuple(viewpoint.shape) if hasattr(viewpoint, "shape") else np.shape(viewpoint)
+        if vshape != (3,):
+            raise ValueError(f"estimate_normals: viewpoint must hold 3 numbers, got shape {vshape}")
+        viewpoint = viewpoint[None] if isinstance(viewpoint, (torch.Tensor, np.ndarray)) else np.asarray(viewpoint, np.float64)[None]
+    out = estimate_normals_batch([pcd], radius, max_nn, viewpoints=viewpoint, trace=trace)
+    return tuple(x[0] for x in out) if trace else out[0]
+
+
 def refine_batch(src_pcds, tgt_pcds, init, max_correspondence_distance, *, max_iteration=30, relative_fitness=1e-6,
-                 relative_rmse=1e-6, pairs_per_call=None, trace=False):
-    """Point-to-point ICP for B pairs at once (pcrcg_icp_batch; include/pcrcg.h "ICP refinement") ->
+                 relative_rmse=1e-6, pairs_per_call=None, trace=False, estimation="point_to_point", tgt_normals=None,
+                 normal_radius=None, normal_max_nn=30):
+    """ICP for B pairs at once (pcrcg_icp_batch / pcrcg_icp_batch_ex; include/pcrcg.h "ICP refinement") ->
     BatchRefinementResult.  open3d 0.10's registration_icp with TransformationEstimationPointToPoint() and
     ICPConvergenceCriteria(relative_fitness, relative_rmse, max_iteration), deterministic: pair b's result depends on its
     clouds and start alone, bit for bit.
@@ -430,12 +529,32 @@ def refine_batch(src_pcds, tgt_pcds, init, max_correspondence_distance, *, max_i
     keeps its start).  init: the starts -- None (the identity), a [B,4,4] array or tensor, or a BatchRegistrationResult
     (its device transforms are used: nothing is read back).  The distance, the iteration cap and the two bounds are
     shared by all pairs.  pairs_per_call bounds the pairs per launch set (default: all).  Every size is checked on the
-    host before anything is uploaded or launched; all chunks write into one device buffer, read ONCE at the end."""
+    host before anything is uploaded or launched; all chunks write into one device buffer, read ONCE at the end.
+
+    estimation: "point_to_point" (the default: everything above) or "point_to_plane", open3d's
+    TransformationEstimationPointToPlane -- the same evaluation and convergence test, the update a Gauss-Newton step on
+    the distances to the targets' tangent planes.  It reads the targets' normals: tgt_normals, a list of per-pair [M_b,3]
+    arrays (their signs do not matter), or, without it, normal_radius (required then) and normal_max_nn: the normals are
+    estimated in the same call on the same stream (estimate_normals_batch's, viewpoint at the origin)."""
     B = len(src_pcds)
     if len(tgt_pcds) != B:
         raise ValueError(f"refine_batch: list lengths differ ({B}, {len(tgt_pcds)})")
     if B == 0:
         raise ValueError("refine_batch: no pairs")
+    if estimation not in _ESTIMATIONS:
+        raise ValueError(f"refine_batch: estimation must be one of {sorted(_ESTIMATIONS)}, got {estimation!r}")
+    plane = _ESTIMATIONS[estimation] == 1
+    if not plane and (tgt_normals is not None or normal_radius is not None):
+        raise ValueError("refine_batch: tgt_normals / normal_radius belong to estimation='point_to_plane'")
+    if plane and tgt_normals is None:
+        if normal_radius is None:
+            raise ValueError("refine_batch: point_to_plane needs tgt_normals or a normal_radius to estimate them with")
+        nr, nk = _check_normal_search("refine_batch", normal_radius, normal_max_nn)
+    elif plane:
+        if normal_radius is not None:
+            raise ValueError("refine_batch: give tgt_normals or normal_radius, not both")
+        if len(tgt_normals) != B:
+            raise ValueError(f"refine_batch: {len(tgt_normals)} sets of target normals for {B} pairs")
     if isinstance(init, BatchRegistrationResult):
         init = init.transformations
     if init is not None:
@@ -453,13 +572,18 @@ def refine_batch(src_pcds, tgt_pcds, init, max_correspondence_distance, *, max_i
         raise ValueError("refine_batch: relative_fitness and relative_rmse must be >= 0")
     ns = [_cloud_rows(x, "refine_batch", "the source", b) for b, x in enumerate(src_pcds)]
     ms = [_cloud_rows(x, "refine_batch", "the target", b) for b, x in enumerate(tgt_pcds)]
+    if plane and tgt_normals is not None:
+        for b, x in enumerate(tgt_normals):
+            if _cloud_rows(x, "refine_batch", "the target normals", b) != ms[b]:
+                raise ValueError(f"refine_batch: pair {b}: the target normals must have one row per target point")
     P = max(1, min(B if pairs_per_call is None else int(pairs_per_call), B, _MAX_BATCH))
     chunks = [(b0, min(B, b0 + P)) for b0 in range(0, B, P)]
     if any(max(sum(ns[b0:b1]), sum(ms[b0:b1])) > 0x7FFFFFFF for b0, b1 in chunks):
         raise ValueError("refine_batch: more than 2^31 - 1 rows per call; lower pairs_per_call")
     dev = _device(*src_pcds, *tgt_pcds, *([init] if init is not None else []))
     L = _lib.lib()
-    wsb = max(L.pcrcg_icp_batch_ws_bytes(b1 - b0, sum(ns[b0:b1]), sum(ms[b0:b1]), mi) for b0, b1 in chunks)
+    ws_bytes = L.pcrcg_icp_batch_ex_ws_bytes if plane else L.pcrcg_icp_batch_ws_bytes
+    wsb = max(ws_bytes(b1 - b0, sum(ns[b0:b1]), sum(ms[b0:b1]), mi) for b0, b1 in chunks)
     if wsb == 0:
         raise ValueError("refine_batch: sizes out of range for the batch workspace")
     ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
@@ -473,6 +597,9 @@ def refine_batch(src_pcds, tgt_pcds, init, max_correspondence_distance, *, max_i
         tr = {"transforms": torch.full((B, mi + 1, 4, 4), float("nan"), dtype=torch.float64, device=dev),
               "counts": torch.full((B, mi + 1), -1, dtype=torch.int32, device=dev),
               "sums": torch.full((B, mi + 1), float("nan"), dtype=torch.float64, device=dev), "corr": []}
+        if plane:
+            tr["sums27"] = torch.full((B, mi + 1, 27), float("nan"), dtype=torch.float64, device=dev)
+            tr["normals"] = []
     for b0, b1 in chunks:
         nb = b1 - b0
         n_tot, m_tot = sum(ns[b0:b1]), sum(ms[b0:b1])
@@ -489,8 +616,26 @@ def refine_batch(src_pcds, tgt_pcds, init, max_correspondence_distance, *, max_i
         if trace:
             corr = torch.full((mi + 1, n_tot), -2, dtype=torch.int32, device=dev)
             tr["corr"] += list(corr.split(ns[b0:b1], dim=1))
-            tr_ptr = ctypes.byref(_IcpTrace(tr["transforms"][b0:].data_ptr(), tr["counts"][b0:].data_ptr(),
-                                            tr["sums"][b0:].data_ptr(), corr.data_ptr()))
+            members = [tr["transforms"][b0:].data_ptr(), tr["counts"][b0:].data_ptr(), tr["sums"][b0:].data_ptr(), corr.data_ptr()]
+            tr_ptr = ctypes.byref(_IcpTraceEx(*members, tr["sums27"][b0:].data_ptr()) if plane else _IcpTrace(*members))
+        if plane:
+            if tgt_normals is None:
+                nrm = _normals_of(L, tgt, tgt_off, lengths, m_tot, nb, max(ms[b0:b1]), nr, nk, None, False)[0]
+            else:
+                ts = [x if isinstance(x, torch.Tensor) else torch.from_numpy(np.asarray(x)) for x in tgt_normals[b0:b1]]
+                if all(not t.is_cuda for t in ts):
+                    nrm = torch.cat([t.to(torch.float64) for t in ts]).to(dev).contiguous()
+                else:
+                    nrm = torch.cat([t.to(device=dev, dtype=torch.float64) for t in ts]).contiguous()
+            if trace:
+                tr["normals"] += list(nrm.split(ms[b0:b1]))
+            _lib.check(L.pcrcg_icp_batch_ex(src.data_ptr() if n_tot else None, src_off.data_ptr(), n_tot, max(ns[b0:b1]),
+                                            tgt_off.data_ptr(), m_tot, grid.data_ptr(),
+                                            init_d[b0:].data_ptr() if init_d is not None else None, nb, d, mi, rf, rr, 1,
+                                            nrm.data_ptr() if m_tot else None, out[16 * b0:].data_ptr(),
+                                            out[16 * B + _N_ICP_STATS * b0:].data_ptr(), tr_ptr, ws.data_ptr(), wsb, _stream()),
+                       "pcrcg_icp_batch_ex")
+            continue
         _lib.check(L.pcrcg_icp_batch(src.data_ptr() if n_tot else None, src_off.data_ptr(), n_tot, max(ns[b0:b1]),
                                      tgt_off.data_ptr(), m_tot, grid.data_ptr(),
                                      init_d[b0:].data_ptr() if init_d is not None else None, nb, d, mi, rf, rr,
@@ -500,9 +645,10 @@ def refine_batch(src_pcds, tgt_pcds, init, max_correspondence_distance, *, max_i
 
 
 def refine(src_pcd, tgt_pcd, init, max_correspondence_distance, *, max_iteration=30, relative_fitness=1e-6,
-           relative_rmse=1e-6, trace=False):
-    """Point-to-point ICP of one pair -> RefinementResult: refine_batch with a batch of one (init: None or a [4,4]
-    start)."""
+           relative_rmse=1e-6, trace=False, estimation="point_to_point", tgt_normals=None, normal_radius=None,
+           normal_max_nn=30):
+    """ICP of one pair -> RefinementResult: refine_batch with a batch of one (init: None or a [4,4] start; tgt_normals: None
+    or the target's [M,3] normals)."""
     if init is not None:
         ishape = tuple(init.shape) if hasattr(init, "shape") else np.shape(init)
         if ishape != (4, 4):
@@ -510,7 +656,9 @@ def refine(src_pcd, tgt_pcd, init, max_correspondence_distance, *, max_iteration
         init = init[None] if isinstance(init, (torch.Tensor, np.ndarray)) else np.asarray(init, dtype=np.float64)[None]
     return RefinementResult(refine_batch([src_pcd], [tgt_pcd], init, max_correspondence_distance,
                                          max_iteration=max_iteration, relative_fitness=relative_fitness,
-                                         relative_rmse=relative_rmse, trace=trace))
+                                         relative_rmse=relative_rmse, trace=trace, estimation=estimation,
+                                         tgt_normals=None if tgt_normals is None else [tgt_normals],
+                                         normal_radius=normal_radius, normal_max_nn=normal_max_nn))
 
 
 def refine_ground_truth(xyz0, xyz1, M):

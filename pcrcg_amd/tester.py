@@ -159,17 +159,20 @@ def register_record(record, n_points=5000, distance_threshold=0.05, ransac_n=3, 
                                   distance_threshold=distance_threshold, ransac_n=ransac_n, seed=seed)
 
 
-def _refine_poses(records, res, refine):
+def _refine_poses(records, res, refine, icp_estimation="point_to_point", normal_radius=None):
     """register_batch's poses refined by ICP on the records' FULL clouds (registration.refine_batch, correspondence
-    distance `refine`), started from the device transforms of `res` -> list of float64 numpy [4,4]."""
+    distance `refine`), started from the device transforms of `res` -> list of float64 numpy [4,4].  icp_estimation,
+    normal_radius: refine_batch's estimation and normal_radius (point-to-plane estimates the targets' normals in the call)."""
     from .registration import refine_batch
     src = [r["pcd"][:r["len_src"]] for r in records]
     tgt = [r["pcd"][r["len_src"]:] for r in records]
-    return list(refine_batch(src, tgt, res, refine).matrices)
+    if icp_estimation == "point_to_point" and normal_radius is None:
+        return list(refine_batch(src, tgt, res, refine).matrices)
+    return list(refine_batch(src, tgt, res, refine, estimation=icp_estimation, normal_radius=normal_radius).matrices)
 
 
 def register_records(records, n_points=5000, distance_threshold=0.05, ransac_n=3, seeds=0, sampler="host", sample_seeds=0,
-                     refine=None):
+                     refine=None, icp_estimation="point_to_point", normal_radius=None):
     """-> list of float64 numpy [4,4]: `register_record` over `records`, with the RANSAC of all pairs batched.  The
     samples are drawn on the host generator in the reference loop's order (record by record, source then target), so
     under the same np.random state the result equals [register_record(r, ...) for r in records] exactly.  seeds: one int
@@ -179,12 +182,14 @@ def register_records(records, n_points=5000, distance_threshold=0.05, ransac_n=3
     record, in [0, 2^23); record b's source and target are drawn with segment seeds 2 sample_seeds[b] and
     2 sample_seeds[b] + 1.
     refine=<distance>: every pose is then refined by point-to-point ICP on the record's full clouds with that
-    correspondence distance (registration.refine_batch, its defaults); None (the default): RANSAC's pose as it is."""
+    correspondence distance (registration.refine_batch, its defaults); None (the default): RANSAC's pose as it is.
+    icp_estimation="point_to_plane" with normal_radius=<radius> refines by point-to-plane ICP instead, on target normals
+    estimated with that radius (both are read only when `refine` is set)."""
     from .registration import register_batch
     src_pcds, tgt_pcds, src_feats, tgt_feats = _sample_records(records, n_points, sampler, sample_seeds)
     res = register_batch(src_pcds, tgt_pcds, src_feats, tgt_feats, distance_threshold, ransac_n, seeds=seeds)
     if refine is not None:
-        return _refine_poses(records, res, refine)
+        return _refine_poses(records, res, refine, icp_estimation, normal_radius)
     return list(res.matrices)
 
 
@@ -216,19 +221,19 @@ def _sample_records(records, n_points, sampler="host", sample_seeds=0):
 
 
 def evaluate_records(records, n_points=5000, distance_threshold=0.05, ransac_n=3, seeds=0, inlier_thresholds=(0.1,),
-                     sampler="host", sample_seeds=0, refine=None):
+                     sampler="host", sample_seeds=0, refine=None, icp_estimation="point_to_point", normal_radius=None):
     """-> (poses, inliers): register_records' poses (list of float64 numpy [4,4]) and registration.inlier_ratio_batch on
     the SAME samples against each record's ground truth (record["rot"], record["trans"]) at `inlier_thresholds`.  The
     host generator is consumed exactly as register_records consumes it, so under the same np.random state the poses
-    equal register_records' bit for bit.  sampler / sample_seeds / refine: as register_records' (the inlier ratios are
-    those of the descriptors and do not depend on `refine`)."""
+    equal register_records' bit for bit.  sampler / sample_seeds / refine / icp_estimation / normal_radius: as
+    register_records' (the inlier ratios are those of the descriptors and do not depend on `refine`)."""
     from .registration import inlier_ratio_batch, register_batch
     src_pcds, tgt_pcds, src_feats, tgt_feats = _sample_records(records, n_points, sampler, sample_seeds)
     res = register_batch(src_pcds, tgt_pcds, src_feats, tgt_feats, distance_threshold, ransac_n, seeds=seeds)
     inliers = inlier_ratio_batch(src_pcds, tgt_pcds, src_feats, tgt_feats, [r["rot"] for r in records],
                                  [r["trans"] for r in records], inlier_thresholds)
     if refine is not None:
-        return _refine_poses(records, res, refine), inliers
+        return _refine_poses(records, res, refine, icp_estimation, normal_radius), inliers
     return list(res.matrices), inliers
 
 
