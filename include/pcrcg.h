@@ -989,6 +989,50 @@ int pcrcg_estimate_normals_batch(const float* pts, const int* off, int n_total, 
                                  int max_nn, const double* viewpoints, double* normals, int* count, double* cov, void* ws,
                                  size_t ws_bytes, void* stream);
 
+/* FPFH descriptors: the 33-bin Fast Point Feature Histograms of B ragged clouds in TWO launches (csrc/fpfh.hip; added under
+ * ABI version 4, which it does not change) -- open3d 0.10's ComputeFPFHFeature(KDTreeSearchParamHybrid(radius, max_nn)),
+ * restated as a deterministic algorithm; no bit parity with open3d is claimed.  DESIGN.md section 21 defines it,
+ * tests/fpfh_ref.py restates it in numpy.
+ *   Layout: pts, off, n_max and grid as pcrcg_estimate_normals_batch (the grid is built at THIS radius).
+ *   normals [n_total, 3] f64 DEVICE, required: pcrcg_estimate_normals_batch's output, or the caller's own.
+ *   Outputs: fpfh [n_total, 33] f32, one row per point (the [N, C] layout pcrcg_feature_match takes); optional (NULL: not
+ *   written), for tests: count [n_total] i32, hist [n_total, 33] u8 and fpfh64 [n_total, 33] f64.
+ *   Definition, per point p_i of a cloud, independent of every other cloud in the call:
+ *     Neighbours: exactly the list of "Normal estimation" above -- the cloud's own points with fp32 unfused
+ *       d2 < (float)radius * (float)radius, in ascending (d2, cloud-local index) order, cut to the first max_nn; k_i is its
+ *       length (count).  max_nn ranges over 1..128 here.  A point with a NaN coordinate or out of cell range has k_i = 0 and
+ *       is in nobody's list.
+ *     Entry 0 is skipped (open3d skips "the point itself"): it is the point itself unless a coincident point with a lower
+ *       index precedes it, and then the point pairs with itself at entry 1, with d = 0.
+ *     Pair feature of (p, n1) with an entry (q, n2), in float64 from the widened fp32 coordinates, every operation rounded
+ *       separately, dot products as ((x + y) + z), cross products as a b - c d per component:
+ *         dp = q - p; d = sqrt(dp . dp); if d == 0: f = (0, 0, 0).
+ *         a1 = (n1 . dp) / d, a2 = (n2 . dp) / d.  Swap iff |a1| < |a2|: n1 and n2 are exchanged, dp = -dp, f2 = -a2;
+ *         otherwise f2 = a1.  (open3d compares acos(|a1|) > acos(|a2|): the same test without acos's rounding.)
+ *         v = dp x n1; vn = sqrt(v . v); if vn == 0: f = (0, 0, 0).  v = v / vn; w = n1 x v; f1 = v . n2;
+ *         f0 = atan2(w . n2, n1 . n2).
+ *     Bins: h0 = floor(11 (f0 + M_PI) / (2 M_PI)), h1 = floor(11 (f1 + 1.0) 0.5), h2 = floor(11 (f2 + 1.0) 0.5), each
+ *       clamped to 0..10; the pair counts in bins h0, 11 + h1 and 22 + h2.  A pair whose f is not all finite (a non-finite
+ *       normal) counts in no bin, and still counts in k_i.
+ *     SPFH: integer counts c_i[33] (hist; a bin holds at most 127); SPFH_i[j] = (double)c_i[j] * (100.0 / (k_i - 1)), zero
+ *       for k_i <= 1.  (open3d adds 100 / (k_i - 1) c times: a difference in rounding only.)
+ *     FPFH: over the entries e = 1 .. k_i - 1 in order, with D = ((dx dx + dy dy) + dz dz) in float64 (not the fp32 ranking
+ *       key): if D == 0 the entry is skipped, otherwise F[j] = F[j] + SPFH_q[j] / D.  S_g = F[11 g] + ... + F[11 g + 10] in
+ *       ascending order; if S_g != 0, F[j] = F[j] * (100.0 / S_g).  fpfh64[j] = F[j] + SPFH_i[j]; fpfh = (float)fpfh64.
+ *       A row with k_i <= 1 is all zero.
+ *   A row's bits depend on its cloud's points and normals alone: not on B, the order of the clouds or scheduling.  The bins are
+ *   counted by integer adds, and nothing is added by floating-point atomics.
+ *   The entry allocates nothing, synchronises nothing and reads nothing back.  Null pts / off / grid / normals / fpfh / ws, B
+ *   outside 1..65535, radius <= 0 or NaN, max_nn outside 1..128 and n_max > n_total are rejected with PCRCG_EBADARG before
+ *   any launch; a short workspace with PCRCG_EWORKSPACE.  Workspace: pcrcg_fpfh_ws_bytes(B, n_total, max_nn) =
+ *   (n_total + 1) (40 + 4 max_nn) bytes plus alignment padding -- the lists' lengths, the byte histograms (36 bytes a row)
+ *   and the ordered neighbour lists the second launch reads; 0 for B outside 1..65535, a negative n_total or max_nn outside
+ *   1..128. */
+size_t pcrcg_fpfh_ws_bytes(int B, int n_total, int max_nn);
+int pcrcg_fpfh_batch(const float* pts, const int* off, int n_total, int n_max, const void* grid, int B, double radius, int max_nn,
+                     const double* normals, float* fpfh, int* count, unsigned char* hist, double* fpfh64, void* ws,
+                     size_t ws_bytes, void* stream);
+
 /* ICP refinement with a choice of estimator (csrc/icp.hip; added under ABI version 4, which it does not change).
  * Everything pcrcg_icp_batch takes, plus
  *   estimation: 0 = point-to-point -- every output is pcrcg_icp_batch's, bit for bit; 1 = point-to-plane, open3d's

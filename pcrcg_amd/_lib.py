@@ -167,6 +167,10 @@ SIGNATURES = {
     "pcrcg_estimate_normals_ws_bytes": (c_size_t, [c_int, c_int]),
     "pcrcg_estimate_normals_batch": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, ctypes.c_double, c_int, c_void_p,
                                              c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    # FPFH descriptors (registration.compute_fpfh_feature_batch)
+    "pcrcg_fpfh_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "pcrcg_fpfh_batch": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, ctypes.c_double, c_int, c_void_p, c_void_p,
+                                 c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "pcrcg_icp_batch_ex_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "pcrcg_icp_batch_ex": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, ctypes.c_double,
                                    c_int, ctypes.c_double, ctypes.c_double, c_int, c_void_p, c_void_p, c_void_p, c_void_p,

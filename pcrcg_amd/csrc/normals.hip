@@ -3,19 +3,15 @@
 // restates it in numpy.
 //
 // open3d's estimate_normals(KDTreeSearchParamHybrid(radius, max_nn)), restated: one wavefront per point.
-//   probe   : lanes 0..26 look the 27 cells around the point up in its cloud's hash table (one 16-byte load per probe).
-//   collect : the cells' supports are walked 64 at a time; a support with d2 < (float)r * (float)r (fp32, unfused) is
-//             appended to the wavefront's LDS list.  Before the list could pass 128 entries it is ranked by (d2, index) and cut
-//             to its first max_nn, so a cell neighbourhood of any size fits.
-//   rank    : the final list is ranked the same way: entry k is the k-th neighbour, whatever order the grid held them in.
+//   search  : hybrid_search.h (probe 27 cells, collect the supports with fp32 d2 < (float)r * (float)r, rank by (d2, index),
+//             cut to max_nn on the way), with a list of 128 entries: up to 64 kept + 64 of the current step.
 //   moments : lane k takes neighbour k's nine float64 terms (d, d d^T with d = q - p); a shuffle tree adds them.
 //   normal  : lane 0 forms the covariance, runs the 3 x 3 Jacobi (smallsolve.h), orients the vector and stores it.
 // No neighbour table goes to memory, and nothing is added by atomics: a row's bits depend on its cloud's points alone.
 //
 // Compiled with -ffp-contract=off (every operation rounds where the source says).
-#include "block_scan.h"
-#include "cellgrid.h"
 #include "common.h"
+#include "hybrid_search.h"
 #include "smallsolve.h"
 
 namespace pcrcg {
@@ -26,15 +22,7 @@ constexpr int kNrmCap = 128;                      // list entries per wavefront:
 constexpr int kNrmMaxNn = 64;                     // one neighbour per lane
 constexpr int kNrmMaxBatch = 65535;               // clouds ride on a grid dimension
 
-struct NrmList {                                  // one wavefront's candidates, twice: ranking writes the other copy
-    float4 q[2][kNrmCap];                         // (x, y, z, index)
-    float d2[2][kNrmCap];
-};
-struct NrmLds {
-    NrmList list[kNrmWaves];
-    int excl[kNrmWaves][32];
-    int start[kNrmWaves][32];
-};
+typedef HybridLds<kNrmWaves, kNrmCap> NrmLds;     // the search's lists (hybrid_search.h)
 
 struct NrmArgs {
     const float* pts;
@@ -47,23 +35,6 @@ struct NrmArgs {
     int max_nn;
 };
 
-// entries [0, fill) of copy `from` -> their first min(fill, keep) by (d2, index), in that order, in the other copy
-__device__ __forceinline__ int rank_and_cut(NrmList& l, int from, int fill, int keep, int lane) {
-    for (int e = lane; e < fill; e += kWave) {
-        const float md = l.d2[from][e];
-        const float4 mq = l.q[from][e];
-        const int mi = __float_as_int(mq.w);
-        int rank = 0;
-        for (int j = 0; j < fill; ++j) {
-            const float od = l.d2[from][j];
-            rank += (od < md || (od == md && __float_as_int(l.q[from][j].w) < mi)) ? 1 : 0;
-        }
-        if (rank < keep) { l.d2[from ^ 1][rank] = md; l.q[from ^ 1][rank] = mq; }
-    }
-    __builtin_amdgcn_wave_barrier();
-    return fill < keep ? fill : keep;
-}
-
 // grid (blocks of four rows, cloud)
 __global__ void __launch_bounds__(kNrmWaves* kWave) k_estimate_normals(NrmArgs a, GridView g) {
     __shared__ NrmLds s;
@@ -74,53 +45,9 @@ __global__ void __launch_bounds__(kNrmWaves* kWave) k_estimate_normals(NrmArgs a
     if (il >= n) return;
     const long i = (long)i0 + il;
     const float px = a.pts[3 * i], py = a.pts[3 * i + 1], pz = a.pts[3 * i + 2];
-    NrmList& l = s.list[wave];
-
-    int cx, cy, cz;
-    const bool inrange = cell_coords(px, py, pz, g.hdr->inv_cell, &cx, &cy, &cz);      // false for a NaN or far-away point
-    const int first = g.soff[b], nsb = g.soff[b + 1] - first;
-    const Slot* tab = g.tab + 2l * first;
-    const unsigned tsize = nsb > 0 ? 2u * (unsigned)nsb : 0u;
-    int ccount = 0, cstart = 0;
-    if (lane < 27 && inrange && tsize > 0) {
-        const u64 key = cell_key(cx + lane % 3 - 1, cy + (lane / 3) % 3 - 1, cz + lane / 9 - 1);
-        unsigned sl_i = __umulhi(mix32(key), tsize);
-        for (unsigned probe = 0; probe < tsize; ++probe) {
-            const Slot sl = load_slot(&tab[sl_i]);
-            if (sl.key == key) { ccount = sl.cnt; cstart = sl.start; break; }
-            if (sl.key == kEmptyKey) break;
-            sl_i = sl_i + 1 == tsize ? 0 : sl_i + 1;
-        }
-    }
-    const int incl = wave_incl_scan_i32(ccount, lane);
-    const int total = __shfl(incl, 26, kWave);
-    if (lane < 32) { s.excl[wave][lane] = lane < 27 ? incl - ccount : 0x7FFFFFFF; s.start[wave][lane] = cstart; }
-    __builtin_amdgcn_wave_barrier();
-
-    int cur = 0, fill = 0;
-    for (int base = 0; base < total; base += kWave) {
-        if (fill > kNrmCap - kWave) {             // the next 64 might not fit: keep the best max_nn of what is there
-            fill = rank_and_cut(l, cur, fill, a.max_nn, lane);
-            cur ^= 1;
-        }
-        const int t = base + lane;
-        const int tc = t < total ? t : total - 1;
-        int lo = 0;
-#pragma unroll
-        for (int step = 16; step >= 1; step >>= 1)
-            if (s.excl[wave][lo + step] <= tc) lo += step;
-        const float4 q = g.spts[s.start[wave][lo] + (tc - s.excl[wave][lo])];
-        const float dx = q.x - px, dy = q.y - py, dz = q.z - pz;
-        const float d2 = (dx * dx + dy * dy) + dz * dz;
-        const bool hit = t < total && d2 < a.r2;
-        const u64 mask = __ballot(hit);
-        const int pos = fill + __popcll(mask & ((1ull << lane) - 1ull));
-        if (hit) { l.d2[cur][pos] = d2; l.q[cur][pos] = q; }          // pos < fill + 64 <= kNrmCap
-        fill += __popcll(mask);
-        __builtin_amdgcn_wave_barrier();
-    }
-    const int k = rank_and_cut(l, cur, fill, a.max_nn, lane);          // k <= max_nn <= 64
-    cur ^= 1;
+    const HybridList<kNrmCap>& l = s.list[wave];
+    int cur;
+    const int k = hybrid_search(s, wave, lane, px, py, pz, g, b, a.r2, a.max_nn, &cur);          // k <= max_nn <= 64
 
     // lane e: neighbour e's terms about the query point
     double v[9];

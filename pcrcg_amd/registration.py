@@ -14,6 +14,9 @@
                                 `refine` is the same for one pair.
   * `estimate_normals_batch` -- the normals of many clouds in one launch (open3d's hybrid-search estimate_normals),
                                 float64 device tensors; `estimate_normals` is the same for one cloud.
+  * `compute_fpfh_feature_batch` -- the FPFH descriptors of many clouds in one set of launches (open3d's hybrid-search
+                                compute_fpfh_feature), float32 [N,33] device tensors that `register_batch` takes as
+                                they are; `compute_fpfh_feature` is the same for one cloud.
   * `refine_ground_truth`    -- ref:datasets/kitti.py:111-120: a KITTI ground-truth pose refined by ICP on the raw scans.
   * `mutual_correspondences` -- the mutual pairs of the inner-product score ([K,2] int64 device tensor).
   * `get_inlier_ratio`       -- device version of ref:lib/benchmark_utils.py:226-267 (same `w` / `wo` dict).
@@ -514,6 +517,109 @@ def estimate_normals(pcd, radius, max_nn=30, *, viewpoint=None, trace=False):
             raise ValueError(f"estimate_normals: viewpoint must hold 3 numbers, got shape {vshape}")
         viewpoint = viewpoint[None] if isinstance(viewpoint, (torch.Tensor, np.ndarray)) else np.asarray(viewpoint, np.float64)[None]
     out = estimate_normals_batch([pcd], radius, max_nn, viewpoints=viewpoint, trace=trace)
+    return tuple(x[0] for x in out) if trace else out[0]
+
+
+_MAX_FPFH_NN = 128    # include/pcrcg.h: two list entries per lane
+_FPFH_BINS = 33
+
+
+def compute_fpfh_feature_batch(pcds, radius, max_nn=100, *, normals=None, normal_radius=None, normal_max_nn=30, viewpoints=None,
+                               pairs_per_call=None, trace=False):
+    """The FPFH descriptors of B clouds in one set of launches (pcrcg_fpfh_batch; include/pcrcg.h "FPFH descriptors", DESIGN.md
+    section 21) -> a list of float32 [N_b,33] device tensors, rows are points: what feature_match and register_batch take.  With
+    trace=True -> (fpfh, counts, hists, fpfh64): lists of int32 [N_b], uint8 [N_b,33] and float64 [N_b,33] device tensors.
+    open3d's compute_fpfh_feature(KDTreeSearchParamHybrid(radius, max_nn)), deterministic: cloud b's result depends on its
+    points and normals alone, bit for bit.
+
+    Inputs: a list of [N_b,3] points (numpy, CPU or HIP tensors; empty clouds are allowed).  normals: a list of [N_b,3] arrays
+    (numpy, CPU or HIP), or None: they are then estimated on the same uploaded points (estimate_normals_batch's, with
+    normal_radius -- required then --, normal_max_nn and viewpoints).  pairs_per_call bounds the clouds per launch (default:
+    all).  Every size is checked on the host before anything is uploaded or launched; nothing is read back."""
+    who = "compute_fpfh_feature_batch"
+    B = len(pcds)
+    if B == 0:
+        raise ValueError(f"{who}: no clouds")
+    r, k = float(radius), int(max_nn)
+    if not 0.0 < r < 1e18:
+        raise ValueError(f"{who}: the radius must be positive and finite, got {radius}")
+    if not 1 <= k <= _MAX_FPFH_NN:
+        raise ValueError(f"{who}: max_nn = {k}, need 1..{_MAX_FPFH_NN}")
+    ns = [_cloud_rows(x, who, "the cloud", b) for b, x in enumerate(pcds)]
+    if normals is None:
+        if normal_radius is None:
+            raise ValueError(f"{who}: needs normals or a normal_radius to estimate them with")
+        nr, nk = _check_normal_search(who, normal_radius, normal_max_nn)
+        if viewpoints is not None:
+            vshape = tuple(viewpoints.shape) if hasattr(viewpoints, "shape") else np.shape(viewpoints)
+            if vshape != (B, 3):
+                raise ValueError(f"{who}: viewpoints must be [{B}, 3] (one per cloud), got shape {vshape}")
+    else:
+        if normal_radius is not None or viewpoints is not None:
+            raise ValueError(f"{who}: normal_radius and viewpoints belong to normals=None; give normals or those, not both")
+        if len(normals) != B:
+            raise ValueError(f"{who}: {len(normals)} sets of normals for {B} clouds")
+        for b, x in enumerate(normals):
+            if _cloud_rows(x, who, "the normals", b) != ns[b]:
+                raise ValueError(f"{who}: pair {b}: the normals must have one row per point")
+    P = max(1, min(B if pairs_per_call is None else int(pairs_per_call), B, _MAX_BATCH))
+    chunks = [(b0, min(B, b0 + P)) for b0 in range(0, B, P)]
+    if any(sum(ns[b0:b1]) > 0x7FFFFFFF for b0, b1 in chunks):
+        raise ValueError(f"{who}: more than 2^31 - 1 rows per call; lower pairs_per_call")
+    dev = _device(*pcds, *(normals if normals is not None else []), *([viewpoints] if viewpoints is not None else []))
+    L = _lib.lib()
+    view_d = None
+    if viewpoints is not None:
+        view_d = viewpoints if isinstance(viewpoints, torch.Tensor) else torch.from_numpy(np.asarray(viewpoints, dtype=np.float64))
+        view_d = view_d.to(device=dev, dtype=torch.float64).contiguous()
+    fpfh, counts, hists, f64s = [], [], [], []
+    for b0, b1 in chunks:
+        nb, n_tot, n_max = b1 - b0, sum(ns[b0:b1]), max(ns[b0:b1])
+        pts = _cat(pcds[b0:b1], dev, "pcds", 3)
+        offs = torch.tensor(np.concatenate([np.cumsum([0] + ns[b0:b1]), ns[b0:b1]]), dtype=torch.int32, device=dev)
+        off, lengths = offs[:nb + 1], offs[nb + 1:]
+        if normals is None:
+            nrm = _normals_of(L, pts, off, lengths, n_tot, nb, n_max, nr, nk, view_d[b0:b1] if view_d is not None else None,
+                              False)[0]
+        else:
+            ts = [x if isinstance(x, torch.Tensor) else torch.from_numpy(np.asarray(x)) for x in normals[b0:b1]]
+            if all(not t.is_cuda for t in ts):
+                nrm = torch.cat([t.to(torch.float64) for t in ts]).to(dev).contiguous()
+            else:
+                nrm = torch.cat([t.to(device=dev, dtype=torch.float64) for t in ts]).contiguous()
+        gbytes = L.pcrcg_cellgrid_ws_bytes(n_tot, nb)
+        grid = torch.empty(gbytes, dtype=torch.uint8, device=dev)
+        _lib.check(L.pcrcg_cellgrid_build(pts.data_ptr() if n_tot else None, n_tot, lengths.data_ptr(), nb, r, grid.data_ptr(),
+                                          gbytes, _stream()), "pcrcg_cellgrid_build")
+        wsb = L.pcrcg_fpfh_ws_bytes(nb, n_tot, k)
+        ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device=dev)
+        out = torch.empty((n_tot, _FPFH_BINS), dtype=torch.float32, device=dev)
+        cnt = torch.empty(n_tot, dtype=torch.int32, device=dev) if trace else None
+        hst = torch.empty((n_tot, _FPFH_BINS), dtype=torch.uint8, device=dev) if trace else None
+        f64 = torch.empty((n_tot, _FPFH_BINS), dtype=torch.float64, device=dev) if trace else None
+        _lib.check(L.pcrcg_fpfh_batch(pts.data_ptr() if n_tot else None, off.data_ptr(), n_tot, n_max, grid.data_ptr(), nb, r, k,
+                                      nrm.data_ptr() if n_tot else None, out.data_ptr() if n_tot else None,
+                                      cnt.data_ptr() if trace else None, hst.data_ptr() if trace else None,
+                                      f64.data_ptr() if trace else None, ws.data_ptr(), wsb, _stream()), "pcrcg_fpfh_batch")
+        fpfh += list(out.split(ns[b0:b1]))
+        if trace:
+            counts += list(cnt.split(ns[b0:b1]))
+            hists += list(hst.split(ns[b0:b1]))
+            f64s += list(f64.split(ns[b0:b1]))
+    return (fpfh, counts, hists, f64s) if trace else fpfh
+
+
+def compute_fpfh_feature(pcd, radius, max_nn=100, *, normals=None, normal_radius=None, normal_max_nn=30, viewpoint=None,
+                         trace=False):
+    """The FPFH descriptors of one cloud: compute_fpfh_feature_batch with a batch of one (normals: None or the cloud's [N,3]
+    normals; viewpoint: None or 3 numbers) -> float32 [N,33] device tensor; with trace=True -> (fpfh, counts, hists, fpfh64)."""
+    if viewpoint is not None:
+        vshape = tuple(viewpoint.shape) if hasattr(viewpoint, "shape") else np.shape(viewpoint)
+        if vshape != (3,):
+            raise ValueError(f"compute_fpfh_feature: viewpoint must hold 3 numbers, got shape {vshape}")
+        viewpoint = viewpoint[None] if isinstance(viewpoint, (torch.Tensor, np.ndarray)) else np.asarray(viewpoint, np.float64)[None]
+    out = compute_fpfh_feature_batch([pcd], radius, max_nn, normals=None if normals is None else [normals],
+                                     normal_radius=normal_radius, normal_max_nn=normal_max_nn, viewpoints=viewpoint, trace=trace)
     return tuple(x[0] for x in out) if trace else out[0]
 
 
