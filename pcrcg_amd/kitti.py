@@ -17,7 +17,7 @@ so every index in `correspondences` refers to the rows this module returns.
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, ragged
 from .config import as_config
 from .correspondences import get_correspondences
 
@@ -26,24 +26,14 @@ _MAX_ROWS = 1 << 30         # ... and n_total
 
 
 def _device(clouds):
-    for x in clouds:
-        if isinstance(x, torch.Tensor) and x.is_cuda:
-            return x.device
-    if not torch.cuda.is_available():
-        raise RuntimeError("pcrcg_amd.kitti: no HIP device is visible (there is no CPU implementation)")
-    return torch.device("cuda", torch.cuda.current_device())
+    return ragged.device(clouds, "kitti")
 
 
 def _rows(x, who, b):
-    shape = tuple(x.shape) if hasattr(x, "shape") else np.shape(x)
+    shape = ragged.shape_of(x)
     if len(shape) != 2 or shape[1] != 3:
         raise ValueError(f"{who}: cloud {b} must be an [N, 3] array, got shape {shape}")
     return shape[0]
-
-
-def _f32(x, dev):
-    t = x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x))
-    return t.to(device=dev, dtype=torch.float32).reshape(-1, 3)
 
 
 def voxel_down_sample_batch(clouds, voxel_size, *, with_index=False):
@@ -69,8 +59,9 @@ def voxel_down_sample_batch(clouds, voxel_size, *, with_index=False):
         raise ValueError(f"voxel_down_sample_batch: {n_total} rows in one call, at most {_MAX_ROWS}")
     dev = _device(clouds)
     L = _lib.lib()
-    pts = torch.cat([_f32(x, dev) for x in clouds], 0).contiguous() if n_total else torch.zeros((1, 3), dtype=torch.float32, device=dev)
-    off = torch.tensor(np.cumsum([0] + ns), dtype=torch.int32, device=dev)
+    pts = (ragged.upload(clouds, dev, torch.float32, 3, "clouds") if n_total
+           else torch.zeros((1, 3), dtype=torch.float32, device=dev))    # all clouds empty: a placeholder row, not read
+    off, = ragged.offsets(dev, ns)
     cap = max(n_total, 1)
     out = torch.empty((cap, 3), dtype=torch.float64, device=dev)
     out_len = torch.empty(B, dtype=torch.int32, device=dev)

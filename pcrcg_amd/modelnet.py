@@ -15,8 +15,7 @@ reference's `Rotation.from_dcm(...).as_euler('xyz')` is restated in `dcm2euler_x
 import numpy as np
 import torch
 
-from . import _lib
-from .registration import _MAX_BATCH, _device, _read, _rows, _stream
+from . import _lib, ragged
 
 # calls of pcrcg_chamfer_batch made by this module (tests count them: one per chamfer_batch / compute_metrics call)
 CALLS = [0]
@@ -53,15 +52,11 @@ def _cloud_list(x, name):
 
 
 def _stack_clouds(xs, dev, name):
-    ts = [x if isinstance(x, torch.Tensor) else torch.from_numpy(np.asarray(x)) for x in xs]
+    ts = ragged.tensors(xs)
     for b, t in enumerate(ts):
         if t.dim() != 2 or t.shape[1] < 3:
             raise ValueError(f"chamfer_batch: {name}[{b}] must be [n, 3], got {tuple(t.shape)}")
-    if all(not t.is_cuda for t in ts):
-        t = torch.cat([t[:, :3].to(torch.float32) for t in ts]).to(dev)
-    else:
-        t = torch.cat([t[:, :3].to(device=dev, dtype=torch.float32) for t in ts])
-    return t.contiguous()
+    return ragged.join(ts, dev, torch.float32, lambda t: t[:, :3])
 
 
 def _poses(x, B, dev, name):
@@ -92,16 +87,16 @@ def chamfer_batch(points_src, points_ref, points_raw, pred, gt, *, per_point=Fal
         raise ValueError("chamfer_batch: no pairs")
     if not len(ref) == len(raw) == B:
         raise ValueError(f"chamfer_batch: list lengths differ ({B}, {len(ref)}, {len(raw)})")
-    if B > _MAX_BATCH:
-        raise ValueError(f"chamfer_batch: {B} pairs, one call takes up to {_MAX_BATCH}")
-    ns, ms, rs = ([_rows(x) for x in xs] for xs in (src, ref, raw))
+    if B > ragged.MAX_BATCH:
+        raise ValueError(f"chamfer_batch: {B} pairs, one call takes up to {ragged.MAX_BATCH}")
+    ns, ms, rs = ([ragged.rows(x) for x in xs] for xs in (src, ref, raw))
     N, M, R = sum(ns), sum(ms), sum(rs)
-    if max(N, M, R) > 0x7FFFFFFF:
+    if max(N, M, R) > ragged.MAX_ROWS:
         raise ValueError("chamfer_batch: more than 2^31 - 1 rows in one call")
-    dev = _device(*src, *ref, *raw)
+    dev = ragged.device([*src, *ref, *raw], "registration")
     P, G = _poses(pred, B, dev, "pred"), _poses(gt, B, dev, "gt")
     s, r, w = _stack_clouds(src, dev, "points_src"), _stack_clouds(ref, dev, "points_ref"), _stack_clouds(raw, dev, "points_raw")
-    offs = torch.tensor(np.concatenate([np.cumsum([0] + xs) for xs in (ns, ms, rs)]), dtype=torch.int32, device=dev)
+    off_s, off_r, off_w = ragged.offsets(dev, ns, ms, rs)
     L = _lib.lib()
     wsb = L.pcrcg_chamfer_batch_ws_bytes(B, N, M, R)
     ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device=dev)
@@ -114,13 +109,13 @@ def chamfer_batch(points_src, points_ref, points_raw, pred, gt, *, per_point=Fal
         # an empty stack still needs a pointer the entry accepts; nothing is read through it
         return (t[o:].data_ptr() if t.numel() > o else out.data_ptr()) if on else None
 
-    _lib.check(L.pcrcg_chamfer_batch(ptr(s), offs.data_ptr(), N, ptr(r), offs[B + 1:].data_ptr(), M, ptr(w),
-                                     offs[2 * B + 2:].data_ptr(), R, B, P.data_ptr(), G.data_ptr(), out.data_ptr(),
+    _lib.check(L.pcrcg_chamfer_batch(ptr(s), off_s.data_ptr(), N, ptr(r), off_r.data_ptr(), M, ptr(w),
+                                     off_w.data_ptr(), R, B, P.data_ptr(), G.data_ptr(), out.data_ptr(),
                                      out[B:].data_ptr(), out[2 * B:].data_ptr(), ptr(out, o_ds, per_point),
                                      ptr(out, o_as, per_point), ptr(out, o_dr, per_point), ptr(out, o_ar, per_point),
-                                     ws.data_ptr(), wsb, _stream()), "pcrcg_chamfer_batch")
+                                     ws.data_ptr(), wsb, torch.cuda.current_stream().cuda_stream), "pcrcg_chamfer_batch")
     CALLS[0] += 1
-    h = _read(out)
+    h = ragged.read(out)
     f = h[:3 * B].view(np.float32).reshape(3, B).copy()
     extra = ()
     if per_point:

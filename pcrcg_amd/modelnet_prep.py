@@ -31,7 +31,7 @@ import math
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, ragged
 from .config import as_config
 from .correspondences import get_correspondences_batch
 
@@ -285,12 +285,7 @@ def compose(steps, d):
 
 
 def _device(clouds):
-    for x in clouds:
-        if isinstance(x, torch.Tensor) and x.is_cuda:
-            return x.device
-    if not torch.cuda.is_available():
-        raise RuntimeError("pcrcg_amd.modelnet_prep: no HIP device is visible (there is no CPU implementation)")
-    return torch.device("cuda", torch.cuda.current_device())
+    return ragged.device(clouds, "modelnet_prep")
 
 
 def _cloud_list(points, who):
@@ -300,7 +295,7 @@ def _cloud_list(points, who):
         raise ValueError(f"{who}: no clouds")
     ld = None
     for b, x in enumerate(clouds):
-        shape = tuple(x.shape) if hasattr(x, "shape") else np.shape(x)
+        shape = ragged.shape_of(x)
         if len(shape) != 2 or shape[1] not in (3, 6):
             raise ValueError(f"{who}: cloud {b} must be an [n, 3] or [n, 6] array, got shape {shape}")
         if ld is None:
@@ -316,10 +311,7 @@ def _cloud_list(points, who):
 
 def _upload(clouds, dev):
     """-> the clouds as one float32 device stack (host clouds travel in one upload)."""
-    ts = [x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x)) for x in clouds]
-    if all(not t.is_cuda for t in ts):
-        return torch.cat([t.to(torch.float32) for t in ts]).to(dev).contiguous()
-    return torch.cat([t.to(device=dev, dtype=torch.float32) for t in ts]).contiguous()
+    return ragged.upload(clouds, dev, torch.float32, name="clouds")
 
 
 def _crop(stack, ld, off, first, params, kept, count):

@@ -31,16 +31,18 @@ The algorithm (csrc/register.hip, include/pcrcg.h "Registration back end", DESIG
 seed fixes every draw, and two runs give the same bits.  `register` reads the device ONCE, after the selection
 (the transform and the statistics in one buffer); every call before it is enqueued on the current stream.  So do
 `register_batch` and `inlier_ratio_batch`, however many chunks of pairs they launch.
+
+Every batched entry here is its own argument rules, its library call and its result; what they share -- joining and uploading
+lists of arrays, offsets, chunk lists, cell grids, the counted read, the small checkers -- is in ragged.py.  The device is
+looked up through this module's `_device`, after the host checks, and handed to those helpers.
 """
 import ctypes
 
 import numpy as np
 import torch
 
-from . import _lib
-
-# device -> host reads made by this module (one per `register` call; tests/test_registration_gpu.py counts them)
-D2H_READS = 0
+from . import _lib, ragged
+from .ragged import MAX_BATCH as _MAX_BATCH, read as _read, rows as _rows, shape_of
 
 _N_STATS = 6   # fitness, inlier_rmse, K, iterations, validations, chosen hypothesis (-1: none)
 
@@ -50,12 +52,15 @@ def _stream():
 
 
 def _device(*xs):
-    for x in xs:
-        if isinstance(x, torch.Tensor) and x.is_cuda:
-            return x.device
-    if not torch.cuda.is_available():
-        raise RuntimeError("pcrcg_amd.registration: no HIP device is visible (there is no CPU implementation)")
-    return torch.device("cuda", torch.cuda.current_device())
+    """Every function here looks this name up when it is called, after its host checks (tests replace it)."""
+    return ragged.device(xs, "registration")
+
+
+def __getattr__(name):
+    # D2H_READS: device -> host reads made through _read (one per `register` call; the tests count them)
+    if name == "D2H_READS":
+        return ragged.READS[0]
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
 def _f32(x, dev, name, cols=None):
@@ -64,13 +69,6 @@ def _f32(x, dev, name, cols=None):
     if t.dim() != 2 or (cols is not None and t.shape[1] != cols):
         raise ValueError(f"{name} must be a [N, {cols or 'C'}] array, got shape {tuple(t.shape)}")
     return t.contiguous()
-
-
-def _read(t):
-    """The module's one way to the host (counted)."""
-    global D2H_READS
-    D2H_READS += 1
-    return t.cpu().numpy()
 
 
 class RegistrationResult:
@@ -156,11 +154,7 @@ def register(src_pcd, tgt_pcd, src_feat, tgt_feat, mutual=False, distance_thresh
     ws = _workspace(n, m, int(max_iteration), int(max_validation), dev)
     corr, k = feature_match(src_feat, tgt_feat, mutual, ws)
     L = _lib.lib()
-    gbytes = L.pcrcg_cellgrid_ws_bytes(m, 1)
-    grid = torch.empty(gbytes, dtype=torch.uint8, device=dev)
-    lengths = torch.tensor([m], dtype=torch.int32, device=dev)
-    _lib.check(L.pcrcg_cellgrid_build(tgt.data_ptr(), m, lengths.data_ptr(), 1, thr, grid.data_ptr(), gbytes, _stream()),
-               "pcrcg_cellgrid_build")
+    grid = ragged.cell_grid(tgt, m, torch.tensor([m], dtype=torch.int32, device=dev), 1, thr, _stream())
     out = torch.empty(16 + _N_STATS, dtype=torch.float64, device=dev)
     tr, tr_ptr = None, None
     if trace:
@@ -198,7 +192,6 @@ def ransac_pose_estimation(src_pcd, tgt_pcd, src_feat, tgt_feat, mutual=False, d
 # register_batch's default chunking: as many consecutive pairs per call as keep pcrcg_ransac_batch_ws_bytes within this
 # (576 pairs at 5 000 points and 50 000 / 1 000)
 BATCH_WS_BUDGET = 256 << 20
-_MAX_BATCH = 65535     # pairs per call (include/pcrcg.h)
 
 
 class BatchRegistrationResult:
@@ -224,21 +217,8 @@ class BatchRegistrationResult:
         return f"BatchRegistrationResult(pairs={len(self)}, mean fitness={float(np.mean(self.fitness)):.6g})"
 
 
-def _rows(x):
-    return x.shape[0] if hasattr(x, "shape") else len(x)
-
-
 def _cat(xs, dev, name, cols=None):
-    """Concatenate per-pair [N_b, cols] arrays into one float32 [sum N_b, cols] device tensor: host inputs are joined on
-    the host and uploaded once."""
-    ts = [x if isinstance(x, torch.Tensor) else torch.from_numpy(np.asarray(x)) for x in xs]
-    if all(not t.is_cuda for t in ts):
-        t = torch.cat([t.to(torch.float32) for t in ts]).to(dev)
-    else:
-        t = torch.cat([t.to(device=dev, dtype=torch.float32) for t in ts])
-    if t.dim() != 2 or (cols is not None and t.shape[1] != cols):
-        raise ValueError(f"{name} must be [N, {cols or 'C'}] arrays, got {tuple(t.shape)} concatenated")
-    return t.contiguous()
+    return ragged.upload(xs, dev, torch.float32, cols, name)
 
 
 def _match_batch(fa, src_off, n_max, fb, tgt_off, m_max, ws):
@@ -260,10 +240,10 @@ def feature_match_batch(src_feats, tgt_feats):
     dev = _device(*src_feats, *tgt_feats)
     fa = _cat(src_feats, dev, "src_feats")
     fb = _cat(tgt_feats, dev, "tgt_feats", fa.shape[1])
-    offs = torch.tensor(np.concatenate([np.cumsum([0] + ns), np.cumsum([0] + ms)]), dtype=torch.int32, device=dev)
+    src_off, tgt_off = ragged.offsets(dev, ns, ms)
     wsb = _lib.lib().pcrcg_ransac_batch_ws_bytes(len(ns), sum(ns), sum(ms), 1, 1)
     ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-    return _match_batch(fa, offs[:len(ns) + 1], max(ns), fb, offs[len(ns) + 1:], max(ms), (ws, wsb))
+    return _match_batch(fa, src_off, max(ns), fb, tgt_off, max(ms), (ws, wsb))
 
 
 def register_batch(src_pcds, tgt_pcds, src_feats, tgt_feats, distance_threshold=0.05, ransac_n=3, *, max_iteration=50000,
@@ -295,11 +275,7 @@ def register_batch(src_pcds, tgt_pcds, src_feats, tgt_feats, distance_threshold=
         raise ValueError("register_batch: distance_threshold must be positive")
     if not 0.0 <= float(edge_similarity) <= 1.0:
         raise ValueError("register_batch: edge_similarity must lie in [0, 1]")
-    seeds = [int(seeds)] * B if np.ndim(seeds) == 0 else [int(x) for x in seeds]
-    if len(seeds) != B:
-        raise ValueError(f"register_batch: {len(seeds)} seeds for {B} pairs")
-    if any(not 0 <= x < (1 << 24) for x in seeds):
-        raise ValueError("register_batch: every seed must lie in [0, 2^24)")
+    seeds = ragged.seed_list(seeds, B, "register_batch", "pairs")
     ns = [_rows(x) for x in src_pcds]
     ms = [_rows(x) for x in tgt_pcds]
     c = None
@@ -308,23 +284,14 @@ def register_batch(src_pcds, tgt_pcds, src_feats, tgt_feats, distance_threshold=
             raise ValueError(f"register_batch: pair {b} has {ns[b]} source points, fewer than ransac_n = {ransac_n}")
         if ms[b] == 0:
             raise ValueError(f"register_batch: pair {b} has an empty target cloud")
-        fs, ft = src_feats[b], tgt_feats[b]
-        if _rows(fs) != ns[b] or _rows(ft) != ms[b]:
-            raise ValueError(f"register_batch: pair {b}: the descriptors must have one row per point")
-        cb = (fs.shape[1], ft.shape[1])
-        if c is None:
-            c = cb[0]
-        if cb != (c, c):
-            raise ValueError(f"register_batch: pair {b}: descriptor width {cb}, the batch uses {c}")
+        c = ragged.descriptor_width("register_batch", b, src_feats[b], tgt_feats[b], ns[b], ms[b], c)
     mi, mv = int(max_iteration), int(max_validation)
     L = _lib.lib()
     if pairs_per_call is None:
-        per_pair = L.pcrcg_ransac_batch_ws_bytes(1, max(ns), max(ms), mi, mv)
-        pairs_per_call = max(1, BATCH_WS_BUDGET // max(per_pair, 1))
-    P = max(1, min(int(pairs_per_call), B, _MAX_BATCH, (0x7FFFFFFF // mi)))
+        pairs_per_call = ragged.per_call_within(BATCH_WS_BUDGET, L.pcrcg_ransac_batch_ws_bytes(1, max(ns), max(ms), mi, mv))
     dev = _device(*src_pcds, *tgt_pcds, *src_feats, *tgt_feats)
     thr = float(distance_threshold)
-    chunks = [(b0, min(B, b0 + P)) for b0 in range(0, B, P)]
+    chunks = ragged.chunks(B, pairs_per_call, min(_MAX_BATCH, 0x7FFFFFFF // mi), "register_batch")
     wsb = max(L.pcrcg_ransac_batch_ws_bytes(b1 - b0, sum(ns[b0:b1]), sum(ms[b0:b1]), mi, mv) for b0, b1 in chunks)
     if wsb == 0:
         raise ValueError("register_batch: sizes out of range for the batch workspace")
@@ -332,20 +299,14 @@ def register_batch(src_pcds, tgt_pcds, src_feats, tgt_feats, distance_threshold=
     out = torch.empty(B * (16 + _N_STATS), dtype=torch.float64, device=dev)
     seeds_d = torch.tensor(seeds, dtype=torch.int64, device=dev)
     for b0, b1 in chunks:
-        nb = b1 - b0
-        n_tot, m_tot = sum(ns[b0:b1]), sum(ms[b0:b1])
+        nb, m_tot = b1 - b0, sum(ms[b0:b1])
         src = _cat(src_pcds[b0:b1], dev, "src_pcds", 3)
         tgt = _cat(tgt_pcds[b0:b1], dev, "tgt_pcds", 3)
         fa = _cat(src_feats[b0:b1], dev, "src_feats", c)
         fb = _cat(tgt_feats[b0:b1], dev, "tgt_feats", c)
-        offs = torch.tensor(np.concatenate([np.cumsum([0] + ns[b0:b1]), np.cumsum([0] + ms[b0:b1]), ms[b0:b1]]),
-                            dtype=torch.int32, device=dev)
-        src_off, tgt_off, lengths = offs[:nb + 1], offs[nb + 1:2 * nb + 2], offs[2 * nb + 2:]
+        src_off, tgt_off, lengths = ragged.offsets(dev, ns[b0:b1], ms[b0:b1], lengths=[ms[b0:b1]])
         corr, k = _match_batch(fa, src_off, max(ns[b0:b1]), fb, tgt_off, max(ms[b0:b1]), (ws, wsb))
-        gbytes = L.pcrcg_cellgrid_ws_bytes(m_tot, nb)
-        grid = torch.empty(gbytes, dtype=torch.uint8, device=dev)
-        _lib.check(L.pcrcg_cellgrid_build(tgt.data_ptr(), m_tot, lengths.data_ptr(), nb, thr, grid.data_ptr(), gbytes,
-                                          _stream()), "pcrcg_cellgrid_build")
+        grid = ragged.cell_grid(tgt, m_tot, lengths, nb, thr, _stream())
         _lib.check(L.pcrcg_ransac_batch(src.data_ptr(), src_off.data_ptr(), tgt.data_ptr(), tgt_off.data_ptr(), m_tot,
                                         grid.data_ptr(), corr.data_ptr(), k.data_ptr(), nb, ransac_n, thr,
                                         float(edge_similarity), int(bool(distance_check)), mi, mv, seeds_d[b0:].data_ptr(),
@@ -430,7 +391,7 @@ class RefinementResult:
 
 
 def _cloud_rows(x, who, name, b):
-    shape = tuple(x.shape) if hasattr(x, "shape") else np.shape(x)
+    shape = shape_of(x)
     if len(shape) != 2 or shape[1] != 3:
         raise ValueError(f"{who}: pair {b}: {name} must be an [N, 3] array, got shape {shape}")
     return shape[0]
@@ -449,10 +410,7 @@ def _normals_of(L, pts, off, lengths, n_tot, nb, n_max, radius, max_nn, viewpoin
     """pcrcg_estimate_normals_batch over nb concatenated clouds already on the device, on the current stream ->
     (normals [n_tot,3] float64, counts or None, covariances or None).  Nothing is read back."""
     dev = pts.device
-    gbytes = L.pcrcg_cellgrid_ws_bytes(n_tot, nb)
-    grid = torch.empty(gbytes, dtype=torch.uint8, device=dev)
-    _lib.check(L.pcrcg_cellgrid_build(pts.data_ptr() if n_tot else None, n_tot, lengths.data_ptr(), nb, radius, grid.data_ptr(),
-                                      gbytes, _stream()), "pcrcg_cellgrid_build")
+    grid = ragged.cell_grid(pts, n_tot, lengths, nb, radius, _stream())
     wsb = L.pcrcg_estimate_normals_ws_bytes(nb, n_tot)
     ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device=dev)
     nrm = torch.empty((n_tot, 3), dtype=torch.float64, device=dev)
@@ -479,27 +437,18 @@ def estimate_normals_batch(pcds, radius, max_nn=30, *, viewpoints=None, pairs_pe
     if B == 0:
         raise ValueError("estimate_normals_batch: no clouds")
     r, k = _check_normal_search("estimate_normals_batch", radius, max_nn)
-    if viewpoints is not None:
-        vshape = tuple(viewpoints.shape) if hasattr(viewpoints, "shape") else np.shape(viewpoints)
-        if vshape != (B, 3):
-            raise ValueError(f"estimate_normals_batch: viewpoints must be [{B}, 3] (one per cloud), got shape {vshape}")
+    ragged.check_viewpoints(viewpoints, B, "estimate_normals_batch")
     ns = [_cloud_rows(x, "estimate_normals_batch", "the cloud", b) for b, x in enumerate(pcds)]
-    P = max(1, min(B if pairs_per_call is None else int(pairs_per_call), B, _MAX_BATCH))
-    chunks = [(b0, min(B, b0 + P)) for b0 in range(0, B, P)]
-    if any(sum(ns[b0:b1]) > 0x7FFFFFFF for b0, b1 in chunks):
-        raise ValueError("estimate_normals_batch: more than 2^31 - 1 rows per call; lower pairs_per_call")
+    chunks = ragged.chunks(B, pairs_per_call, _MAX_BATCH, "estimate_normals_batch", ns)
     dev = _device(*pcds, *([viewpoints] if viewpoints is not None else []))
     L = _lib.lib()
-    view_d = None
-    if viewpoints is not None:
-        view_d = viewpoints if isinstance(viewpoints, torch.Tensor) else torch.from_numpy(np.asarray(viewpoints, dtype=np.float64))
-        view_d = view_d.to(device=dev, dtype=torch.float64).contiguous()
+    view_d = ragged.upload_f64(viewpoints, dev) if viewpoints is not None else None
     normals, counts, covs = [], [], []
     for b0, b1 in chunks:
         nb, n_tot = b1 - b0, sum(ns[b0:b1])
         pts = _cat(pcds[b0:b1], dev, "pcds", 3)
-        offs = torch.tensor(np.concatenate([np.cumsum([0] + ns[b0:b1]), ns[b0:b1]]), dtype=torch.int32, device=dev)
-        nrm, cnt, cov = _normals_of(L, pts, offs[:nb + 1], offs[nb + 1:], n_tot, nb, max(ns[b0:b1]), r, k,
+        off, lengths = ragged.offsets(dev, ns[b0:b1], lengths=[ns[b0:b1]])
+        nrm, cnt, cov = _normals_of(L, pts, off, lengths, n_tot, nb, max(ns[b0:b1]), r, k,
                                     view_d[b0:b1] if view_d is not None else None, trace)
         normals += list(nrm.split(ns[b0:b1]))
         if trace:
@@ -511,11 +460,7 @@ def estimate_normals_batch(pcds, radius, max_nn=30, *, viewpoints=None, pairs_pe
 def estimate_normals(pcd, radius, max_nn=30, *, viewpoint=None, trace=False):
     """The normals of one cloud: estimate_normals_batch with a batch of one (viewpoint: None or 3 numbers) -> float64 [N,3]
     device tensor; with trace=True -> (normals, counts, covariances)."""
-    if viewpoint is not None:
-        vshape = tuple(viewpoint.shape) if hasattr(viewpoint, "shape") else np.shape(viewpoint)
-        if vshape != (3,):
-            raise ValueError(f"estimate_normals: viewpoint must hold 3 numbers, got shape {vshape}")
-        viewpoint = viewpoint[None] if isinstance(viewpoint, (torch.Tensor, np.ndarray)) else np.asarray(viewpoint, np.float64)[None]
+    viewpoint = ragged.lift(viewpoint, (3,), "estimate_normals: viewpoint must hold 3 numbers")
     out = estimate_normals_batch([pcd], radius, max_nn, viewpoints=viewpoint, trace=trace)
     return tuple(x[0] for x in out) if trace else out[0]
 
@@ -550,10 +495,7 @@ def compute_fpfh_feature_batch(pcds, radius, max_nn=100, *, normals=None, normal
         if normal_radius is None:
             raise ValueError(f"{who}: needs normals or a normal_radius to estimate them with")
         nr, nk = _check_normal_search(who, normal_radius, normal_max_nn)
-        if viewpoints is not None:
-            vshape = tuple(viewpoints.shape) if hasattr(viewpoints, "shape") else np.shape(viewpoints)
-            if vshape != (B, 3):
-                raise ValueError(f"{who}: viewpoints must be [{B}, 3] (one per cloud), got shape {vshape}")
+        ragged.check_viewpoints(viewpoints, B, who)
     else:
         if normal_radius is not None or viewpoints is not None:
             raise ValueError(f"{who}: normal_radius and viewpoints belong to normals=None; give normals or those, not both")
@@ -562,35 +504,21 @@ def compute_fpfh_feature_batch(pcds, radius, max_nn=100, *, normals=None, normal
         for b, x in enumerate(normals):
             if _cloud_rows(x, who, "the normals", b) != ns[b]:
                 raise ValueError(f"{who}: pair {b}: the normals must have one row per point")
-    P = max(1, min(B if pairs_per_call is None else int(pairs_per_call), B, _MAX_BATCH))
-    chunks = [(b0, min(B, b0 + P)) for b0 in range(0, B, P)]
-    if any(sum(ns[b0:b1]) > 0x7FFFFFFF for b0, b1 in chunks):
-        raise ValueError(f"{who}: more than 2^31 - 1 rows per call; lower pairs_per_call")
+    chunks = ragged.chunks(B, pairs_per_call, _MAX_BATCH, who, ns)
     dev = _device(*pcds, *(normals if normals is not None else []), *([viewpoints] if viewpoints is not None else []))
     L = _lib.lib()
-    view_d = None
-    if viewpoints is not None:
-        view_d = viewpoints if isinstance(viewpoints, torch.Tensor) else torch.from_numpy(np.asarray(viewpoints, dtype=np.float64))
-        view_d = view_d.to(device=dev, dtype=torch.float64).contiguous()
+    view_d = ragged.upload_f64(viewpoints, dev) if viewpoints is not None else None
     fpfh, counts, hists, f64s = [], [], [], []
     for b0, b1 in chunks:
         nb, n_tot, n_max = b1 - b0, sum(ns[b0:b1]), max(ns[b0:b1])
         pts = _cat(pcds[b0:b1], dev, "pcds", 3)
-        offs = torch.tensor(np.concatenate([np.cumsum([0] + ns[b0:b1]), ns[b0:b1]]), dtype=torch.int32, device=dev)
-        off, lengths = offs[:nb + 1], offs[nb + 1:]
+        off, lengths = ragged.offsets(dev, ns[b0:b1], lengths=[ns[b0:b1]])
         if normals is None:
             nrm = _normals_of(L, pts, off, lengths, n_tot, nb, n_max, nr, nk, view_d[b0:b1] if view_d is not None else None,
                               False)[0]
         else:
-            ts = [x if isinstance(x, torch.Tensor) else torch.from_numpy(np.asarray(x)) for x in normals[b0:b1]]
-            if all(not t.is_cuda for t in ts):
-                nrm = torch.cat([t.to(torch.float64) for t in ts]).to(dev).contiguous()
-            else:
-                nrm = torch.cat([t.to(device=dev, dtype=torch.float64) for t in ts]).contiguous()
-        gbytes = L.pcrcg_cellgrid_ws_bytes(n_tot, nb)
-        grid = torch.empty(gbytes, dtype=torch.uint8, device=dev)
-        _lib.check(L.pcrcg_cellgrid_build(pts.data_ptr() if n_tot else None, n_tot, lengths.data_ptr(), nb, r, grid.data_ptr(),
-                                          gbytes, _stream()), "pcrcg_cellgrid_build")
+            nrm = ragged.upload(normals[b0:b1], dev, torch.float64, 3, "normals")
+        grid = ragged.cell_grid(pts, n_tot, lengths, nb, r, _stream())
         wsb = L.pcrcg_fpfh_ws_bytes(nb, n_tot, k)
         ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device=dev)
         out = torch.empty((n_tot, _FPFH_BINS), dtype=torch.float32, device=dev)
@@ -613,11 +541,7 @@ def compute_fpfh_feature(pcd, radius, max_nn=100, *, normals=None, normal_radius
                          trace=False):
     """The FPFH descriptors of one cloud: compute_fpfh_feature_batch with a batch of one (normals: None or the cloud's [N,3]
     normals; viewpoint: None or 3 numbers) -> float32 [N,33] device tensor; with trace=True -> (fpfh, counts, hists, fpfh64)."""
-    if viewpoint is not None:
-        vshape = tuple(viewpoint.shape) if hasattr(viewpoint, "shape") else np.shape(viewpoint)
-        if vshape != (3,):
-            raise ValueError(f"compute_fpfh_feature: viewpoint must hold 3 numbers, got shape {vshape}")
-        viewpoint = viewpoint[None] if isinstance(viewpoint, (torch.Tensor, np.ndarray)) else np.asarray(viewpoint, np.float64)[None]
+    viewpoint = ragged.lift(viewpoint, (3,), "compute_fpfh_feature: viewpoint must hold 3 numbers")
     out = compute_fpfh_feature_batch([pcd], radius, max_nn, normals=None if normals is None else [normals],
                                      normal_radius=normal_radius, normal_max_nn=normal_max_nn, viewpoints=viewpoint, trace=trace)
     return tuple(x[0] for x in out) if trace else out[0]
@@ -663,10 +587,8 @@ def refine_batch(src_pcds, tgt_pcds, init, max_correspondence_distance, *, max_i
             raise ValueError(f"refine_batch: {len(tgt_normals)} sets of target normals for {B} pairs")
     if isinstance(init, BatchRegistrationResult):
         init = init.transformations
-    if init is not None:
-        ishape = tuple(init.shape) if hasattr(init, "shape") else np.shape(init)
-        if ishape != (B, 4, 4):
-            raise ValueError(f"refine_batch: init must be [{B}, 4, 4] (one start per pair), got shape {ishape}")
+    if init is not None and shape_of(init) != (B, 4, 4):
+        raise ValueError(f"refine_batch: init must be [{B}, 4, 4] (one start per pair), got shape {shape_of(init)}")
     d = float(max_correspondence_distance)
     if not 0.0 < d < 1e18:
         raise ValueError("refine_batch: max_correspondence_distance must be positive")
@@ -682,10 +604,7 @@ def refine_batch(src_pcds, tgt_pcds, init, max_correspondence_distance, *, max_i
         for b, x in enumerate(tgt_normals):
             if _cloud_rows(x, "refine_batch", "the target normals", b) != ms[b]:
                 raise ValueError(f"refine_batch: pair {b}: the target normals must have one row per target point")
-    P = max(1, min(B if pairs_per_call is None else int(pairs_per_call), B, _MAX_BATCH))
-    chunks = [(b0, min(B, b0 + P)) for b0 in range(0, B, P)]
-    if any(max(sum(ns[b0:b1]), sum(ms[b0:b1])) > 0x7FFFFFFF for b0, b1 in chunks):
-        raise ValueError("refine_batch: more than 2^31 - 1 rows per call; lower pairs_per_call")
+    chunks = ragged.chunks(B, pairs_per_call, _MAX_BATCH, "refine_batch", ns, ms)
     dev = _device(*src_pcds, *tgt_pcds, *([init] if init is not None else []))
     L = _lib.lib()
     ws_bytes = L.pcrcg_icp_batch_ex_ws_bytes if plane else L.pcrcg_icp_batch_ws_bytes
@@ -694,10 +613,7 @@ def refine_batch(src_pcds, tgt_pcds, init, max_correspondence_distance, *, max_i
         raise ValueError("refine_batch: sizes out of range for the batch workspace")
     ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
     out = torch.empty(B * (16 + _N_ICP_STATS), dtype=torch.float64, device=dev)
-    init_d = None
-    if init is not None:
-        init_d = (init if isinstance(init, torch.Tensor) else torch.from_numpy(np.asarray(init, dtype=np.float64)))
-        init_d = init_d.to(device=dev, dtype=torch.float64).contiguous()
+    init_d = ragged.upload_f64(init, dev) if init is not None else None
     tr = None
     if trace:
         tr = {"transforms": torch.full((B, mi + 1, 4, 4), float("nan"), dtype=torch.float64, device=dev),
@@ -706,47 +622,34 @@ def refine_batch(src_pcds, tgt_pcds, init, max_correspondence_distance, *, max_i
         if plane:
             tr["sums27"] = torch.full((B, mi + 1, 27), float("nan"), dtype=torch.float64, device=dev)
             tr["normals"] = []
+    entry = "pcrcg_icp_batch_ex" if plane else "pcrcg_icp_batch"
     for b0, b1 in chunks:
         nb = b1 - b0
         n_tot, m_tot = sum(ns[b0:b1]), sum(ms[b0:b1])
         src = _cat(src_pcds[b0:b1], dev, "src_pcds", 3)
         tgt = _cat(tgt_pcds[b0:b1], dev, "tgt_pcds", 3)
-        offs = torch.tensor(np.concatenate([np.cumsum([0] + ns[b0:b1]), np.cumsum([0] + ms[b0:b1]), ms[b0:b1]]),
-                            dtype=torch.int32, device=dev)
-        src_off, tgt_off, lengths = offs[:nb + 1], offs[nb + 1:2 * nb + 2], offs[2 * nb + 2:]
-        gbytes = L.pcrcg_cellgrid_ws_bytes(m_tot, nb)
-        grid = torch.empty(gbytes, dtype=torch.uint8, device=dev)
-        _lib.check(L.pcrcg_cellgrid_build(tgt.data_ptr() if m_tot else None, m_tot, lengths.data_ptr(), nb, d, grid.data_ptr(),
-                                          gbytes, _stream()), "pcrcg_cellgrid_build")
+        src_off, tgt_off, lengths = ragged.offsets(dev, ns[b0:b1], ms[b0:b1], lengths=[ms[b0:b1]])
+        grid = ragged.cell_grid(tgt, m_tot, lengths, nb, d, _stream())
         tr_ptr = None
         if trace:
             corr = torch.full((mi + 1, n_tot), -2, dtype=torch.int32, device=dev)
             tr["corr"] += list(corr.split(ns[b0:b1], dim=1))
             members = [tr["transforms"][b0:].data_ptr(), tr["counts"][b0:].data_ptr(), tr["sums"][b0:].data_ptr(), corr.data_ptr()]
             tr_ptr = ctypes.byref(_IcpTraceEx(*members, tr["sums27"][b0:].data_ptr()) if plane else _IcpTrace(*members))
+        plane_args = ()     # pcrcg_icp_batch_ex's two more: the estimation and the targets' normals
         if plane:
             if tgt_normals is None:
                 nrm = _normals_of(L, tgt, tgt_off, lengths, m_tot, nb, max(ms[b0:b1]), nr, nk, None, False)[0]
             else:
-                ts = [x if isinstance(x, torch.Tensor) else torch.from_numpy(np.asarray(x)) for x in tgt_normals[b0:b1]]
-                if all(not t.is_cuda for t in ts):
-                    nrm = torch.cat([t.to(torch.float64) for t in ts]).to(dev).contiguous()
-                else:
-                    nrm = torch.cat([t.to(device=dev, dtype=torch.float64) for t in ts]).contiguous()
+                nrm = ragged.upload(tgt_normals[b0:b1], dev, torch.float64, 3, "tgt_normals")
             if trace:
                 tr["normals"] += list(nrm.split(ms[b0:b1]))
-            _lib.check(L.pcrcg_icp_batch_ex(src.data_ptr() if n_tot else None, src_off.data_ptr(), n_tot, max(ns[b0:b1]),
-                                            tgt_off.data_ptr(), m_tot, grid.data_ptr(),
-                                            init_d[b0:].data_ptr() if init_d is not None else None, nb, d, mi, rf, rr, 1,
-                                            nrm.data_ptr() if m_tot else None, out[16 * b0:].data_ptr(),
-                                            out[16 * B + _N_ICP_STATS * b0:].data_ptr(), tr_ptr, ws.data_ptr(), wsb, _stream()),
-                       "pcrcg_icp_batch_ex")
-            continue
-        _lib.check(L.pcrcg_icp_batch(src.data_ptr() if n_tot else None, src_off.data_ptr(), n_tot, max(ns[b0:b1]),
+            plane_args = (1, nrm.data_ptr() if m_tot else None)
+        _lib.check(getattr(L, entry)(src.data_ptr() if n_tot else None, src_off.data_ptr(), n_tot, max(ns[b0:b1]),
                                      tgt_off.data_ptr(), m_tot, grid.data_ptr(),
-                                     init_d[b0:].data_ptr() if init_d is not None else None, nb, d, mi, rf, rr,
+                                     init_d[b0:].data_ptr() if init_d is not None else None, nb, d, mi, rf, rr, *plane_args,
                                      out[16 * b0:].data_ptr(), out[16 * B + _N_ICP_STATS * b0:].data_ptr(), tr_ptr,
-                                     ws.data_ptr(), wsb, _stream()), "pcrcg_icp_batch")
+                                     ws.data_ptr(), wsb, _stream()), entry)
     return BatchRefinementResult(out, _read(out), B, tr)
 
 
@@ -755,11 +658,7 @@ def refine(src_pcd, tgt_pcd, init, max_correspondence_distance, *, max_iteration
            normal_max_nn=30):
     """ICP of one pair -> RefinementResult: refine_batch with a batch of one (init: None or a [4,4] start; tgt_normals: None
     or the target's [M,3] normals)."""
-    if init is not None:
-        ishape = tuple(init.shape) if hasattr(init, "shape") else np.shape(init)
-        if ishape != (4, 4):
-            raise ValueError(f"refine: init must be a [4, 4] transform, got shape {ishape}")
-        init = init[None] if isinstance(init, (torch.Tensor, np.ndarray)) else np.asarray(init, dtype=np.float64)[None]
+    init = ragged.lift(init, (4, 4), "refine: init must be a [4, 4] transform")
     return RefinementResult(refine_batch([src_pcd], [tgt_pcd], init, max_correspondence_distance,
                                          max_iteration=max_iteration, relative_fitness=relative_fitness,
                                          relative_rmse=relative_rmse, trace=trace, estimation=estimation,
@@ -780,10 +679,7 @@ def refine_ground_truth(xyz0, xyz1, M):
     return M @ T
 
 
-_MAX_SAMPLE_SEED = 1 << 24   # segment seeds of pcrcg_weighted_sample_batch (include/pcrcg.h)
-
-
-def _sample_flat(scores, n_points, seeds):
+def sample_flat(scores, n_points, seeds):
     """sample_batch's work: -> (idx [sum k_s] int32 device, the kept rows of every cloud, local to it, concatenated;
     ns, ks: host lists of cloud lengths and kept counts; seg_off, out_off: their [S + 1] int32 device prefix sums).
     Every check is made on the host before anything is uploaded."""
@@ -793,12 +689,8 @@ def _sample_flat(scores, n_points, seeds):
     n_points = int(n_points)
     if n_points < 1:
         raise ValueError(f"sample_batch: n_points = {n_points}, need at least 1")
-    seeds = [int(seeds)] * S if np.ndim(seeds) == 0 else [int(x) for x in seeds]
-    if len(seeds) != S:
-        raise ValueError(f"sample_batch: {len(seeds)} seeds for {S} clouds")
-    if any(not 0 <= x < _MAX_SAMPLE_SEED for x in seeds):
-        raise ValueError("sample_batch: every seed must lie in [0, 2^24)")
-    ts = [x if isinstance(x, torch.Tensor) else torch.from_numpy(np.asarray(x)) for x in scores]
+    seeds = ragged.seed_list(seeds, S, "sample_batch", "clouds")    # the segment seeds of include/pcrcg.h: 24 bits
+    ts = ragged.tensors(scores)
     ns = [int(t.numel()) for t in ts]
     for b, t in enumerate(ts):
         if ns[b] == 0:
@@ -809,10 +701,7 @@ def _sample_flat(scores, n_points, seeds):
         raise ValueError("sample_batch: more than 2^31 - 1 rows in one call")
     ks = [min(n, n_points) for n in ns]
     dev = _device(*ts)
-    if all(not t.is_cuda for t in ts):
-        w = torch.cat([t.detach().reshape(-1).to(torch.float32) for t in ts]).to(dev)
-    else:
-        w = torch.cat([t.detach().reshape(-1).to(device=dev, dtype=torch.float32) for t in ts])
+    w = ragged.join(ts, dev, torch.float32, lambda t: t.detach().reshape(-1))
     # ONE upload: the seeds [S] u64, then both offset arrays [S + 1] i32 packed into the following int64 words
     meta = np.empty(2 * S + 1, dtype=np.int64)
     meta[:S] = seeds
@@ -831,6 +720,9 @@ def _sample_flat(scores, n_points, seeds):
     return idx, ns, ks, seg_off, out_off
 
 
+_sample_flat = sample_flat
+
+
 def sample_batch(scores, n_points, seeds):
     """Weighted sampling without replacement of n_points rows from each of S clouds, on the device
     (pcrcg_weighted_sample_batch; DESIGN.md section 10 has the specification) -> list of S int64 device tensors, cloud
@@ -841,7 +733,7 @@ def sample_batch(scores, n_points, seeds):
     cloud) or S ints in [0, 2^24); a cloud's result depends on its scores, n_points and seed alone.  One upload of offsets
     and seeds (host-side scores are joined on the host and uploaded once as well), one launch, nothing read back; every
     check runs on the host first."""
-    idx, _, ks, _, _ = _sample_flat(scores, n_points, seeds)
+    idx, _, ks, _, _ = sample_flat(scores, n_points, seeds)
     return list(idx.to(torch.int64).split(ks))
 
 
@@ -961,24 +853,13 @@ def inlier_ratio_batch(src_pcds, tgt_pcds, src_feats, tgt_feats, rots, trans, th
     for b in range(B):
         if ns[b] == 0 or ms[b] == 0:
             raise ValueError(f"inlier_ratio_batch: pair {b} has an empty cloud ({ns[b]}, {ms[b]} points)")
-        fs, ft = src_feats[b], tgt_feats[b]
-        if _rows(fs) != ns[b] or _rows(ft) != ms[b]:
-            raise ValueError(f"inlier_ratio_batch: pair {b}: the descriptors must have one row per point")
-        cb = (fs.shape[1], ft.shape[1])
-        if c is None:
-            c = cb[0]
-        if cb != (c, c):
-            raise ValueError(f"inlier_ratio_batch: pair {b}: descriptor width {cb}, the batch uses {c}")
+        c = ragged.descriptor_width("inlier_ratio_batch", b, src_feats[b], tgt_feats[b], ns[b], ms[b], c)
     if _numel(rots) != 9 * B or _numel(trans) != 3 * B:
         raise ValueError("inlier_ratio_batch: need a [3,3] rotation and a [3] translation per pair")
     L = _lib.lib()
     if pairs_per_call is None:
-        per_pair = L.pcrcg_inlier_stats_batch_ws_bytes(1, max(ns), max(ms))
-        pairs_per_call = max(1, BATCH_WS_BUDGET // max(per_pair, 1))
-    P = max(1, min(int(pairs_per_call), B, _MAX_BATCH))
-    chunks = [(b0, min(B, b0 + P)) for b0 in range(0, B, P)]
-    if any(max(sum(ns[b0:b1]), sum(ms[b0:b1])) > 0x7FFFFFFF for b0, b1 in chunks):
-        raise ValueError("inlier_ratio_batch: more than 2^31 - 1 rows per call; lower pairs_per_call")
+        pairs_per_call = ragged.per_call_within(BATCH_WS_BUDGET, L.pcrcg_inlier_stats_batch_ws_bytes(1, max(ns), max(ms)))
+    chunks = ragged.chunks(B, pairs_per_call, _MAX_BATCH, "inlier_ratio_batch", ns, ms)
     dev = _device(*src_pcds, *tgt_pcds, *src_feats, *tgt_feats)
     wsb = max(L.pcrcg_inlier_stats_batch_ws_bytes(b1 - b0, sum(ns[b0:b1]), sum(ms[b0:b1])) for b0, b1 in chunks)
     ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
@@ -1004,10 +885,9 @@ def inlier_ratio_batch(src_pcds, tgt_pcds, src_feats, tgt_feats, rots, trans, th
         tgt = _cat(tgt_pcds[b0:b1], dev, "tgt_pcds", 3)
         fa = _cat(src_feats[b0:b1], dev, "src_feats", c)
         fb = _cat(tgt_feats[b0:b1], dev, "tgt_feats", c)
-        offs = torch.tensor(np.concatenate([np.cumsum([0] + ns[b0:b1]), np.cumsum([0] + ms[b0:b1])]), dtype=torch.int32,
-                            device=dev)
-        _lib.check(L.pcrcg_inlier_stats_batch(src.data_ptr(), fa.data_ptr(), c, offs.data_ptr(), n_tot, max(ns[b0:b1]),
-                                              tgt.data_ptr(), fb.data_ptr(), c, offs[nb + 1:].data_ptr(), m_tot,
+        src_off, tgt_off = ragged.offsets(dev, ns[b0:b1], ms[b0:b1])
+        _lib.check(L.pcrcg_inlier_stats_batch(src.data_ptr(), fa.data_ptr(), c, src_off.data_ptr(), n_tot, max(ns[b0:b1]),
+                                              tgt.data_ptr(), fb.data_ptr(), c, tgt_off.data_ptr(), m_tot,
                                               max(ms[b0:b1]), c, nb, rt[b0:].data_ptr(), thr_h, T,
                                               out[2 * T * b0:].data_ptr(), out[o_k + b0:].data_ptr(),
                                               ptr(o_d + r0, distances), ptr(o_m + r0, distances), ptr(o_as + r0, matches),

@@ -23,6 +23,7 @@ registration back end.
 import numpy as np
 import torch
 
+from . import ragged
 
 def test_record(inputs, outputs):
     """ref:lib/tester.py:92-101."""
@@ -77,13 +78,13 @@ def probabilistic_sample_batch(pcds, feats, scores, n_points, seeds):
     S = len(scores)
     if not (len(pcds) == len(feats) == S):
         raise ValueError(f"probabilistic_sample_batch: list lengths differ ({len(pcds)}, {len(feats)}, {S})")
-    idx, ns, ks, seg_off, out_off = REG._sample_flat(scores, n_points, seeds)
+    idx, ns, ks, seg_off, out_off = REG.sample_flat(scores, n_points, seeds)
     for b in range(S):
-        if REG._rows(pcds[b]) != ns[b] or REG._rows(feats[b]) != ns[b]:
+        if ragged.rows(pcds[b]) != ns[b] or ragged.rows(feats[b]) != ns[b]:
             raise ValueError(f"probabilistic_sample_batch: cloud {b}: points, descriptors and scores differ in length")
     dev = idx.device
-    pts = REG._cat(pcds, dev, "pcds", 3)
-    fts = REG._cat(feats, dev, "feats")
+    pts = ragged.upload(pcds, dev, torch.float32, 3, "pcds")
+    fts = ragged.upload(feats, dev, torch.float32, None, "feats")
     # local rows -> rows of the concatenation: + the cloud's first row, repeated over its kept rows (sizes known: no sync)
     first = torch.repeat_interleave(seg_off[:-1].to(torch.int64), (out_off[1:] - out_off[:-1]).to(torch.int64),
                                     output_size=sum(ks))
@@ -93,11 +94,7 @@ def probabilistic_sample_batch(pcds, feats, scores, n_points, seeds):
 
 def _pair_sample_seeds(sample_seeds, B, who):
     """Per-pair sampler seeds in [0, 2^23) -> the 2 B segment seeds (source 2 p, target 2 p + 1)."""
-    seeds = [int(sample_seeds)] * B if np.ndim(sample_seeds) == 0 else [int(x) for x in sample_seeds]
-    if len(seeds) != B:
-        raise ValueError(f"{who}: {len(seeds)} sample_seeds for {B} pairs")
-    if any(not 0 <= x < (1 << 23) for x in seeds):
-        raise ValueError(f"{who}: every sample seed must lie in [0, 2^23)")
+    seeds = ragged.seed_list(sample_seeds, B, who, "pairs", 23, "sample_seeds", "sample seed")
     return [2 * p + side for p in seeds for side in (0, 1)]
 
 

@@ -1,0 +1,346 @@
+"""Record, or check, tests/golden/registration_errors.json: what every public ragged-batch entry of the registration back end
+and its siblings raises for bad arguments, before it asks for a device -- the exception type and the exact message -- and,
+for one valid call per entry, that the device lookup is where the call stops.
+
+    python scripts/record_registration_contract.py --record FILE   # run in a checkout of the commit whose contract is kept
+    python scripts/record_registration_contract.py --check FILE    # the checkout at hand against the recorded file
+
+It runs on the CPU: registration._device is replaced by a function that raises DeviceReached, and torch.cuda.is_available
+answers False, so the siblings' own device lookups raise their "no HIP device" error.  A row is {entry, args, kwargs,
+raises, message}; the arguments are JSON literals, with {"zeros": [n, c], "dtype": ...} for an array, {"shape": [...]} for
+an object that has only a shape (the row-limit checks read nothing else) and {"times": k, "of": x} for a list of k x.
+tests/test_registration_contract_cpu.py replays the file.
+
+Not in the table: crop_batch's limits of 2^20 clouds and 2^30 rows per call (no input that reaches them is built in
+milliseconds), and the raises that follow the device lookup.
+"""
+import argparse
+import importlib
+import json
+import os
+import sys
+
+import numpy as np
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+class DeviceReached(Exception):
+    pass
+
+
+class Shaped:
+    """An argument of which only the shape is looked at."""
+
+    def __init__(self, shape):
+        self.shape = tuple(shape)
+
+    def __len__(self):
+        return self.shape[0]
+
+
+def decode(x):
+    if isinstance(x, list):
+        return [decode(v) for v in x]
+    if isinstance(x, dict):
+        if "zeros" in x:
+            return np.zeros(x["zeros"], dtype=x.get("dtype", "float32"))
+        if "shape" in x:
+            return Shaped(x["shape"])
+        if "times" in x:
+            return [decode(x["of"])] * x["times"]
+        return {k: decode(v) for k, v in x.items()}
+    return x
+
+
+def Z(n, c=3, dtype="float32"):
+    return {"zeros": [n, c], "dtype": dtype}
+
+
+def S(*shape):
+    return {"shape": list(shape)}
+
+
+NAN, INF = float("nan"), float("inf")
+P, Q, F, G, N64 = Z(5), Z(4), Z(5, 32), Z(4, 32), Z(5, 3, "float64")
+EYE = [[1.0, 0.0, 0.0, 0.0], [0.0, 1.0, 0.0, 0.0], [0.0, 0.0, 1.0, 0.0], [0.0, 0.0, 0.0, 1.0]]
+ROT = [[1.0, 0.0, 0.0], [0.0, 1.0, 0.0], [0.0, 0.0, 1.0]]
+BIG = 1 << 30
+
+
+def _rows():
+    rows = []
+
+    def add(entry, *args, **kwargs):
+        rows.append({"entry": entry, "args": list(args), "kwargs": kwargs})
+
+    e = "registration.feature_match_batch"
+    add(e, [F], [G, G])
+    add(e, [], [])
+    add(e, [Z(0, 32)], [G])
+    add(e, [F], [Z(0, 32)])
+    add(e, [F, F], [G, G])                                               # valid
+
+    e = "registration.register_batch"
+    add(e, [P], [Q], [F], [G], mutual=True)
+    add(e, [P], [Q, Q], [F], [G], mutual=True)                           # two wrong: mutual first
+    add(e, [P], [Q, Q], [F], [G])
+    add(e, [], [Q], [], [])                                              # two wrong: lengths before "no pairs"
+    add(e, [], [], [], [])
+    add(e, [P], [Q], [F], [G], ransac_n=2)
+    add(e, [P], [Q], [F], [G], ransac_n=9)
+    add(e, [P], [Q], [F], [G], ransac_n=9, max_iteration=0)              # two wrong: ransac_n first
+    add(e, [P], [Q], [F], [G], max_iteration=0)
+    add(e, [P], [Q], [F], [G], max_validation=0)
+    add(e, [P], [Q], [F], [G], max_iteration=4, max_validation=5)
+    add(e, [P], [Q], [F], [G], 0.0)
+    add(e, [P], [Q], [F], [G], NAN)
+    add(e, [P], [Q], [F], [G], 0.0, edge_similarity=2.0)                 # two wrong: threshold first
+    add(e, [P], [Q], [F], [G], edge_similarity=1.5)
+    add(e, [P], [Q], [F], [G], edge_similarity=-0.1)
+    add(e, [P], [Q], [F], [G], seeds=[1, 2])
+    add(e, [P], [Q], [F], [G], seeds=[-1])
+    add(e, [P], [Q], [F], [G], seeds=1 << 24)
+    add(e, [Z(2)], [Q], [Z(2, 32)], [G], seeds=[1 << 24])                # two wrong: seeds before the short cloud
+    add(e, [P, Z(2)], [Q, Q], [F, Z(2, 32)], [G, G])
+    add(e, [P], [Z(0)], [F], [Z(0, 32)])
+    add(e, [Z(2)], [Z(0)], [Z(2, 32)], [Z(0, 32)])                       # two wrong: the source before the target
+    add(e, [P], [Q], [G], [G])
+    add(e, [P], [Q], [F], [F])
+    add(e, [P], [Q], [F], [Z(4, 33)])
+    add(e, [P, P], [Q, Q], [F, Z(5, 33)], [G, Z(4, 33)])
+    add(e, [P, P], [Q, Q], [F, F], [G, G], seeds=[3, 4], pairs_per_call=1, max_iteration=64, max_validation=8)   # valid
+
+    e = "registration.estimate_normals_batch"
+    add(e, [], 0.1)
+    for bad in (0.0, -1.0, NAN, INF):
+        add(e, [P], bad)
+    for bad in (0, 65):
+        add(e, [P], 0.1, bad)
+    add(e, [P], 0.0, 0)                                                  # two wrong: radius before max_nn
+    add(e, [P], 0.0, viewpoints=Z(2, 3))                                 # two wrong: radius before viewpoints
+    add(e, [P], 0.1, viewpoints=Z(2, 3))
+    add(e, [P], 0.1, viewpoints=[0.0, 0.0, 0.0])
+    add(e, [Z(5, 2)], 0.1, viewpoints=Z(2, 3))                           # two wrong: viewpoints before the cloud
+    add(e, [P, Z(5, 2)], 0.1)
+    add(e, [P, {"zeros": [5]}], 0.1)
+    add(e, [P, [[0.0, 0.0]]], 0.1)
+    add(e, [S(BIG, 3), S(BIG, 3)], 0.1)
+    add(e, [S(BIG, 3), S(BIG, 3)], 0.1, pairs_per_call=1)                # valid sizes: one cloud per call
+    add(e, [P, Z(0)], 0.1, viewpoints=Z(2, 3, "float64"), trace=True)    # valid
+
+    e = "registration.estimate_normals"
+    add(e, P, 0.1, viewpoint={"zeros": [4]})
+    add(e, P, 0.1, viewpoint=[0.0, 0.0])
+    add(e, P, 0.0, viewpoint=[0.0, 0.0])                                 # two wrong: viewpoint before radius
+    add(e, P, 0.0)
+    add(e, P, 0.1, viewpoint=[0.0, 0.0, 1.0])                            # valid
+    add(e, P, 0.1, viewpoint={"zeros": [3], "dtype": "float64"})         # valid
+
+    e = "registration.compute_fpfh_feature_batch"
+    add(e, [], 0.1, normals=[])
+    for bad in (0.0, NAN, INF):
+        add(e, [P], bad, normals=[N64])
+    for bad in (0, 129):
+        add(e, [P], 0.1, bad, normals=[N64])
+    add(e, [Z(5, 2)], 0.0, normals=[N64])                                # two wrong: radius before the cloud
+    add(e, [P, Z(5, 2)], 0.1, normals=[N64, N64])
+    add(e, [Z(5, 2)], 0.1)                                               # two wrong: the cloud before "needs normals"
+    add(e, [P], 0.1)
+    add(e, [P], 0.1, normal_radius=0.0)
+    add(e, [P], 0.1, normal_radius=0.1, normal_max_nn=65)
+    add(e, [P], 0.1, normal_radius=0.0, viewpoints=Z(2, 3))              # two wrong: normal radius before viewpoints
+    add(e, [P], 0.1, normal_radius=0.1, viewpoints=Z(2, 3))
+    add(e, [P], 0.1, normals=[N64], normal_radius=0.1)
+    add(e, [P], 0.1, normals=[N64], viewpoints=Z(1, 3))
+    add(e, [P, P], 0.1, normals=[N64])
+    add(e, [P], 0.1, normals=[Z(4, 3, "float64")])
+    add(e, [P], 0.1, normals=[Z(5, 2, "float64")])
+    add(e, [S(BIG, 3), S(BIG, 3)], 0.1, normal_radius=0.1)
+    add(e, [P, Z(0)], 0.1, normals=[N64, Z(0, 3, "float64")], pairs_per_call=1)                  # valid
+    add(e, [P, Z(0)], 0.1, normal_radius=0.2, viewpoints=Z(2, 3, "float64"), trace=True)         # valid
+
+    e = "registration.compute_fpfh_feature"
+    add(e, P, 0.1, normal_radius=0.1, viewpoint={"zeros": [4]})
+    add(e, P, 0.1, 129, normals=N64)
+    add(e, P, 0.1, 129, normal_radius=0.1, viewpoint=[1.0])              # two wrong: viewpoint before max_nn
+    add(e, P, 0.1, normals=N64)                                          # valid
+    add(e, P, 0.1, normal_radius=0.2, viewpoint=[0.0, 0.0, 1.0])         # valid
+
+    e = "registration.refine_batch"
+    add(e, [P], [Q, Q], None, 0.1)
+    add(e, [], [Q], None, 0.1)                                           # two wrong: lengths before "no pairs"
+    add(e, [], [], None, 0.1)
+    add(e, [P], [Q], None, 0.1, estimation="plane")
+    add(e, [P], [Q], [EYE, EYE], 0.1, estimation="plane")                # two wrong: estimation before init
+    add(e, [P], [Q], None, 0.1, tgt_normals=[Z(4, 3, "float64")])
+    add(e, [P], [Q], None, 0.1, normal_radius=0.1)
+    add(e, [P], [Q], None, 0.1, estimation="point_to_plane")
+    add(e, [P], [Q], None, 0.1, estimation="point_to_plane", normal_radius=0.0)
+    add(e, [P], [Q], None, 0.1, estimation="point_to_plane", normal_radius=0.1, normal_max_nn=0)
+    add(e, [P], [Q], None, 0.1, estimation="point_to_plane", normal_radius=0.1, tgt_normals=[Z(4, 3, "float64")])
+    add(e, [P], [Q], None, 0.1, estimation="point_to_plane", tgt_normals=[])
+    add(e, [P], [Q], [EYE, EYE], 0.1)
+    add(e, [P], [Q], EYE, 0.1)
+    add(e, [P], [Q], {"zeros": [1, 4, 3], "dtype": "float64"}, 0.0)     # two wrong: init before the distance
+    for bad in (0.0, NAN, INF):
+        add(e, [P], [Q], None, bad)
+    for bad in (0, (1 << 16) + 1):
+        add(e, [P], [Q], None, 0.1, max_iteration=bad)
+    add(e, [P], [Q], None, 0.0, max_iteration=0)                         # two wrong: the distance before max_iteration
+    add(e, [P], [Q], None, 0.1, relative_fitness=-1.0)
+    add(e, [P], [Q], None, 0.1, relative_rmse=NAN)
+    add(e, [Z(5, 2)], [Q], None, 0.1, relative_rmse=-1.0)                # two wrong: the bounds before the clouds
+    add(e, [Z(5, 2)], [Q], None, 0.1)
+    add(e, [P], [Z(4, 4)], None, 0.1)
+    add(e, [Z(5, 2)], [Z(4, 4)], None, 0.1)                              # two wrong: the source before the target
+    add(e, [P], [Q], None, 0.1, estimation="point_to_plane", tgt_normals=[Z(4, 2, "float64")])
+    add(e, [P], [Q], None, 0.1, estimation="point_to_plane", tgt_normals=[Z(5, 3, "float64")])
+    add(e, [S(BIG, 3), S(BIG, 3)], [Q, Q], None, 0.1)
+    add(e, [P, P], [S(BIG, 3), S(BIG, 3)], None, 0.1)
+    add(e, [P, Z(0)], [Q, Q], None, 0.1, max_iteration=3, trace=True, pairs_per_call=1)                         # valid
+    add(e, [P], [Q], [EYE], 0.1, estimation="point_to_plane", tgt_normals=[Z(4, 3, "float64")])                 # valid
+    add(e, [P], [Z(0)], None, 0.1, estimation="point_to_plane", normal_radius=0.2)                              # valid
+
+    e = "registration.refine"
+    add(e, P, Q, {"zeros": [3, 4], "dtype": "float64"}, 0.1)
+    add(e, P, Q, [EYE], 0.0)                                             # two wrong: init before the distance
+    add(e, P, Q, None, 0.0)
+    add(e, P, Q, EYE, 0.1)                                               # valid
+    add(e, P, Q, {"zeros": [4, 4], "dtype": "float64"}, 0.1, estimation="point_to_plane", normal_radius=0.2)    # valid
+
+    e = "registration.inlier_ratio_batch"
+    add(e, [P], [Q], [F], [G], [ROT], [])
+    add(e, [], [], [], [], [], [ROT])                                    # two wrong: lengths before "no pairs"
+    add(e, [], [], [], [], [], [])
+    add(e, [P], [Q], [F], [G], [ROT], [[0.0, 0.0, 0.0]], [])
+    add(e, [P], [Q], [F], [G], [ROT], [[0.0, 0.0, 0.0]], [0.1] * 33)
+    add(e, [P], [Q], [F], [G], [ROT], [[0.0, 0.0, 0.0]], [0.1, NAN])
+    add(e, [Z(0)], [Q], [Z(0, 32)], [G], [ROT], [[0.0, 0.0, 0.0]], [NAN])     # two wrong: thresholds before the clouds
+    add(e, [Z(0)], [Q], [Z(0, 32)], [G], [ROT], [[0.0, 0.0, 0.0]])
+    add(e, [P], [Z(0)], [F], [Z(0, 32)], [ROT], [[0.0, 0.0, 0.0]])
+    add(e, [P], [Q], [G], [G], [ROT], [[0.0, 0.0, 0.0]])
+    add(e, [P], [Q], [F], [Z(4, 33)], [ROT], [[0.0, 0.0, 0.0]])
+    add(e, [P, P], [Q, Q], [F, Z(5, 33)], [G, Z(4, 33)], [ROT, ROT], [[0.0, 0.0, 0.0]] * 2)
+    add(e, [P], [Q], [F], [G], [ROT], [[0.0, 0.0]])
+    add(e, [P], [Q], [F], [G], [[1.0, 0.0, 0.0]], [[0.0, 0.0, 0.0]])
+    add(e, [P], [Q], [F], [Z(4, 33)], [ROT], [[0.0, 0.0]])               # two wrong: the width before the poses
+    add(e, [S(BIG, 3), S(BIG, 3)], [Q, Q], [S(BIG, 32), S(BIG, 32)], [G, G], [ROT, ROT], [[0.0, 0.0, 0.0]] * 2,
+        pairs_per_call=2)
+    add(e, [P, P], [Q, Q], [F, F], [G, G], [ROT, ROT], [[0.0, 0.0, 0.0]] * 2, [0.05, 0.1, 0.2], pairs_per_call=1,
+        distances=True, matches=True)                                    # valid
+    add(e, [P], [Q], [F], [G], {"zeros": [1, 3, 3]}, {"zeros": [1, 3]})  # valid (default pairs_per_call)
+
+    e = "registration.sample_batch"
+    W = {"zeros": [6]}
+    add(e, [], 4, 0)
+    add(e, [W], 0, 0)
+    add(e, [], 0, 0)                                                     # two wrong: "no clouds" before n_points
+    add(e, [W, W], 4, [1])
+    add(e, [W], 4, [1 << 24])
+    add(e, [W], 4, -1)
+    add(e, [{"zeros": [0]}], 4, [1 << 24])                               # two wrong: seeds before the empty cloud
+    add(e, [W, {"zeros": [0]}], 4, 0)
+    add(e, [Z(6, 2)], 4, 0)
+    add(e, [{"zeros": [6, 1, 1]}], 4, 0)
+    add(e, [W, Z(6, 1)], 4, [1, 2])                                      # valid
+
+    e = "tester.probabilistic_sample_batch"
+    add(e, [P], [F, F], [W], 4, 0)
+    add(e, [P], [F, F], [W], 0, 0)                                       # two wrong: lengths before n_points
+    add(e, [P], [F], [W], 0, 0)
+    add(e, [P], [F], [W], 4, [1, 2])
+    add(e, [Z(6)], [Z(6, 32)], [W], 4, 7)                                # valid
+
+    e = "modelnet.chamfer_batch"
+    POSE = [EYE]
+    add(e, [], [], [], [], [])
+    add(e, [P], [Q, Q], [P], POSE, POSE)
+    add(e, [], [Q], [], [], [])                                          # two wrong: "no pairs" before the lengths
+    add(e, Z(5), [Q], [P], POSE, POSE)
+    add(e, [P], {"zeros": [4]}, [P], POSE, POSE)
+    add(e, {"times": 65536, "of": P}, {"times": 65536, "of": Q}, {"times": 65536, "of": P}, POSE, POSE)
+    add(e, [S(BIG, 3), S(BIG, 3)], [Q, Q], [P, P], POSE, POSE)
+    add(e, [P, P], [Q, Q], [S(BIG, 3), S(BIG, 3)], POSE, POSE)
+    add(e, [P, Z(0)], [Q, Q], {"zeros": [2, 7, 3]}, [EYE, EYE], [EYE, EYE], per_point=True)    # valid
+
+    e = "kitti.voxel_down_sample_batch"
+    add(e, [], 0.3)
+    add(e, {"times": 65536, "of": P}, 0.3)
+    for bad in (0.0, -1.0, NAN, INF):
+        add(e, [P], bad)
+    add(e, [Z(5, 2)], 0.0)                                               # two wrong: voxel_size before the cloud
+    add(e, [P, Z(5, 2)], 0.3)
+    add(e, [P, {"zeros": [5]}], 0.3)
+    add(e, [S(BIG, 3), S(1, 3)], 0.3)
+    add(e, [P, Z(0)], 0.3, with_index=True)                              # valid
+    add(e, [Z(0)], 0.3)                                                  # valid: every cloud empty
+
+    e = "modelnet_prep.crop_batch"
+    D1 = {"zeros": [1, 3], "dtype": "float64"}
+    add(e, [], D1, 0.7)
+    add(e, [Z(5, 4)], D1, 0.7)
+    add(e, [P, Z(5, 6)], D1, 0.7)
+    add(e, [P, Z(0)], D1, 0.7)
+    add(e, [Z(8193)], D1, 0.7)
+    add(e, [Z(8193, 4)], D1, 0.7)                                        # two wrong: the columns before the rows
+    add(e, [P], {"zeros": [2, 3], "dtype": "float64"}, 0.7)
+    add(e, [P], D1, [0.7, 0.5])
+    add(e, [P], {"zeros": [2, 3], "dtype": "float64"}, [0.7, 0.5])       # two wrong: directions before p_keep
+    add(e, [P], D1, 1.5)
+    add(e, [P, Z(7)], {"zeros": [2, 3], "dtype": "float64"}, [0.7, None])                      # valid
+    return rows
+
+
+def observe(rows):
+    """-> rows with what the checkout at hand raises ("raises", "message")."""
+    import torch
+    mods = {m: importlib.import_module("pcrcg_amd." + m) for m in ("registration", "tester", "modelnet", "kitti", "modelnet_prep")}
+
+    def no_device(*a, **k):
+        raise DeviceReached("the device lookup")
+
+    saved = mods["registration"]._device, torch.cuda.is_available
+    mods["registration"]._device, torch.cuda.is_available = no_device, (lambda: False)
+    try:
+        out = []
+        for row in rows:
+            mod, name = row["entry"].split(".")
+            try:
+                getattr(mods[mod], name)(*decode(row["args"]), **decode(row["kwargs"]))
+                got = {"raises": None, "message": None}
+            except Exception as e:      # noqa: BLE001 -- whatever it raises is the record
+                got = {"raises": type(e).__name__, "message": str(e)}
+            out.append({**{k: row[k] for k in ("entry", "args", "kwargs")}, **got})
+        return out
+    finally:
+        mods["registration"]._device, torch.cuda.is_available = saved
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--record", metavar="FILE")
+    ap.add_argument("--check", metavar="FILE")
+    args = ap.parse_args()
+    sys.path.insert(0, REPO)
+    if args.record:
+        got = observe(_rows())
+        with open(args.record, "w") as f:
+            f.write("[\n" + ",\n".join(json.dumps(r) for r in got) + "\n]\n")
+        kinds = {}
+        for r in got:
+            kinds[r["raises"]] = kinds.get(r["raises"], 0) + 1
+        print(f"{len(got)} rows -> {args.record}: {kinds}")
+    if args.check:
+        with open(args.check) as f:
+            want = json.load(f)
+        bad = [(w, g) for w, g in zip(want, observe(want)) if (w["raises"], w["message"]) != (g["raises"], g["message"])]
+        for w, g in bad:
+            print(f"{w['entry']} {json.dumps(w['args'])[:80]} {w['kwargs']}:\n  recorded {w['raises']}: {w['message']}\n"
+                  f"  now      {g['raises']}: {g['message']}")
+        print(f"{len(want) - len(bad)} of {len(want)} rows agree")
+        sys.exit(1 if bad else 0)
+
+
+if __name__ == "__main__":
+    main()

@@ -1,0 +1,44 @@
+"""Which library calls the ragged-batch entries make: every case of tests/registration_cases.py, run once per form of input
+(numpy, device tensors, mixed), against tests/golden/registration_calls.json -- the sequence of library entries with every
+non-pointer argument, whether each pointer was null, and how often the device was read.  The file was recorded on the GPU
+by scripts/registration_digests.py --record-calls at the commit before the marshalling moved to pcrcg_amd/ragged.py; the three
+forms gave one record there, so it is kept once.  No numerical result is checked here: the suites of the entries do that."""
+import json
+import os
+
+import pytest
+
+from . import registration_cases as RC
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def golden(golden_dir):
+    with open(os.path.join(golden_dir, "registration_calls.json")) as f:
+        return json.load(f)
+
+
+@pytest.mark.parametrize("form", RC.FORMS)
+def test_calls_arguments_and_reads_are_the_recorded_ones(cuda, golden, form):
+    got = json.loads(json.dumps(RC.record_calls(form, cuda)))       # tuples -> lists, as the file holds them
+    assert list(got) == list(golden)
+    for name in golden:
+        assert got[name]["counters"] == golden[name]["counters"], name
+        assert [c[0] for c in got[name]["calls"]] == [c[0] for c in golden[name]["calls"]], name
+        for mine, want in zip(got[name]["calls"], golden[name]["calls"]):
+            assert mine == want, name
+
+
+def test_the_cases_reach_every_branch_of_the_marshalling(golden):
+    """What the inputs are chosen for: chunks of 2, 2 and 1; a null cloud pointer in the empty chunk; both ICP entries."""
+    def calls(case, entry):
+        return [c for c in golden[case]["calls"] if c[0] == entry]
+    assert [c[9] for c in calls("register_batch/c32", "pcrcg_ransac_batch")] == [2, 2, 1]
+    empty = ["null" if sum(n for n, _ in RC.EMPTY[b0:b0 + RC.PER_CALL]) == 0 else "ptr" for b0 in range(0, RC.B, RC.PER_CALL)]
+    assert empty == ["null", "ptr", "null"]
+    assert [c[1] for c in calls("estimate_normals_batch/empty_chunk", "pcrcg_cellgrid_build")] == empty
+    assert [c[1] for c in calls("refine_batch/point/empty_chunk", "pcrcg_icp_batch")] == empty
+    assert len(calls("refine_batch/plane_normals", "pcrcg_icp_batch_ex")) == 3 and not calls("refine_batch/plane_normals", "pcrcg_icp_batch")
+    assert len(calls("refine_batch/point", "pcrcg_icp_batch")) == 3 and not calls("refine_batch/point", "pcrcg_icp_batch_ex")
+    assert all(golden[k]["counters"]["d2h_reads"] == 1 for k in golden if k.startswith(("register_batch", "refine_batch", "inlier")))
