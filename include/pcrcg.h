@@ -876,7 +876,8 @@ int pcrcg_ransac(const float* src, int n, const float* tgt, int m, const void* g
 /* Several pairs per call: B independent pairs in one set of launches.  Pair b's result is exactly (bit for bit: transform,
  * statistics) that of pcrcg_feature_match with mutual = 0 followed by pcrcg_ransac on that pair alone with seed = seeds[b];
  * no pair affects another, and nothing depends on the order of the pairs or on B (no floating-point atomics).
- * Mutual correspondences are not offered here (every reference tester uses mutual = False).
+ * Mutual correspondences are not offered by these two entries (every reference tester uses mutual = False); the batched
+ * mutual L2 list is pcrcg_mutual_match_batch ("Fast global registration" below).
  *   Layout: the pairs are ragged and concatenated.  src [n_total, 3], tgt [m_total, 3] f32; src_off / tgt_off [B + 1] i32
  *   DEVICE arrays of row offsets (src_off[0] = 0, non-decreasing, src_off[B] = n_total; likewise tgt_off); descriptors
  *   [n_total, c] / [m_total, c] with row strides ld_src / ld_tgt.  corr [n_total, 2] i32: pair b's rows start at
@@ -1072,6 +1073,91 @@ int pcrcg_icp_batch_ex(const float* src, const int* src_off, int n_total, int n_
                        double relative_fitness, double relative_rmse, int estimation, const double* tgt_normals,
                        double* out_transform, double* out_stats, const pcrcg_icp_trace_ex* trace, void* ws, size_t ws_bytes,
                        void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Fast global registration
+ * The other half of the classical global-registration recipe that FPFH feeds: Zhou, Park, Koltun, "Fast Global
+ * Registration" (ECCV 2016), open3d's registration_fast_based_on_feature_matching, for B ragged pairs in one launch
+ * (csrc/fgr.hip; added under ABI version 4, which it does not change).  open3d draws its tuples with rand(), so this is a
+ * deterministic algorithm of the same structure; no bit parity with open3d is claimed.  This comment is the definition,
+ * DESIGN.md section 22 explains it and tests/fgr_ref.py restates it in numpy float64.
+ *
+ * pcrcg_mutual_match_batch: the mutual L2 correspondences of B pairs.  Layout, argument checks and conventions are
+ * pcrcg_feature_match_batch's.
+ *   nn_s(i) = pcrcg_feature_match_batch's row i: the arg-max over j of <a_i, b_j> - |b_j|^2 / 2 in fp32, lowest index on ties;
+ *   nn_t(j) = the same rule with the roles exchanged: the arg-max over i of <b_j, a_i> - |a_i|^2 / 2, lowest index on ties.
+ *   Pair b's list holds the (i, nn_s(i)) with nn_t(nn_s(i)) == i in ascending i, written from row src_off[b] of
+ *   corr [n_total, 2] i32 with indices local to the pair; k[b] is its length; rows k[b] .. n_b - 1 of the pair are written as
+ *   (-1, -1).  A pair with n_b = 0 or m_b = 0 gets k[b] = 0.  (FPFH rows are not normalised, so the inner-product arg-max of
+ *   pcrcg_feature_match's mutual = 1 is not their L2 neighbour; this is.)
+ *   Workspace: pcrcg_mutual_match_batch_ws_bytes(B, n_total, m_total) = 12 (n_total + m_total) bytes plus alignment padding;
+ *   0 for B outside 1..65535 or a negative size.  Nothing is allocated, synchronised or read back.
+ *
+ * pcrcg_fgr_batch: src [n_total, 3] / tgt [m_total, 3] f32 and src_off / tgt_off [B + 1] i32 DEVICE row offsets as
+ * pcrcg_ransac_batch's; corr [n_total, 2] i32 and k [B] i32 as pcrcg_mutual_match_batch or pcrcg_feature_match_batch write
+ * them, or the caller's own (pair b's rows start at src_off[b], indices local to the pair; like pcrcg_ransac_batch the entry
+ * trusts them).  seeds [B] u64 DEVICE, each < 2^24.  Every parameter is shared by the pairs of a call.
+ * Per pair b, independent of every other pair, with P = min(max(k[b], 0), n_b) (0 when a side of the pair is empty) and
+ * delta = maximum_correspondence_distance:
+ *   Tuple stage.  tuple_scale == 0: skipped; E = the first min(P, 3 maximum_tuple_count) rows of the list, in order (the
+ *     statistics report 0 tuples and 0 trials).  Otherwise trial t = 0 .. 100 P - 1 (64-bit) draws the three rows
+ *     ((r >> 32) * P) >> 32, r = splitmix64((seed << 40) + 4 t + s), s < 3 (splitmix64 as in "Registration back end").  With
+ *     p_0..p_2 the drawn source points and q_0..q_2 the drawn target points widened to float64, and for the edges (0,1), (1,2),
+ *     (2,0): li = sqrt((dx dx + dy dy) + dz dz) over the p, lj likewise over the q.  The trial passes iff
+ *     li * tuple_scale < lj and lj * tuple_scale < li for all three edges (a repeated row gives li = 0 and fails by itself).
+ *     The first maximum_tuple_count passing trials in ascending t are accepted; E = their rows, three per trial, in trial
+ *     order, duplicates kept.  trials_used = (last accepted t) + 1 when the cap is reached, else 100 P.
+ *   Frame.  |E| < 10: the identity, updates = 0, mu = 0, share = 0.  Otherwise cs = (sum_e p_e) / |E|, ct = (sum_e q_e) / |E|
+ *     in float64; p~ = p - cs, q~ = q - ct; D2 = max_e max(|p~_e|^2, |q~_e|^2), |v|^2 = (x x + y y) + z z; mu = D2.  D2 zero or
+ *     not finite: the identity, updates = 0, mu = D2, share = 0.
+ *   Iterations it = 0 .. iteration_number - 1, T = [R|t] float64 from the identity.  Moved point
+ *     p = ((R0 x + R1 y) + R2 z) + t0 of p~ (and likewise the other components), r = p - q~, weight
+ *     l = (mu / (|r|^2 + mu))^2.  J_x = (0, p_z, -p_y, 1, 0, 0), J_y = (-p_z, 0, p_x, 0, 1, 0), J_z = (p_y, -p_x, 0, 0, 0, 1);
+ *     A = sum l (J_x J_x^T + J_y J_y^T + J_z J_z^T) (the 21 entries of the upper triangle, row by row) and
+ *     g = -sum l (J_x r_x + J_y r_y + J_z r_z) (6), in float64 and in a fixed order: per thread over its entries
+ *     e = thread, thread + 512, ..., a shuffle tree inside each wavefront, the eight wavefronts in order.  No floating-point
+ *     atomics.  x = the LDL^T solve of A x = g (csrc/smallsolve.h, pcrcg_icp_batch_ex's): on failure the loop ends and T is
+ *     kept; otherwise delta = Rz(x2) Ry(x1) Rx(x0) | (x3, x4, x5) as pcrcg_icp_batch_ex's update, T <- delta T, updates += 1,
+ *     and then, if decrease_mu and it % 4 == 0 and mu > delta^2, mu <- mu / division_factor.
+ *   Output.  R_out = R, t_out = (t - R cs) + ct with R cs as ((r0 x + r1 y) + r2 z).  out_transform [B, 16] f64 row-major;
+ *     out_stats [B, 6] f64 = (P, tuples accepted, trials_used, updates, final mu, the share of E's entries with |r|^2 < delta^2
+ *     at the final T).  A pair whose seed is >= 2^24 gets NaN in all 22 outputs, as in pcrcg_ransac_batch.
+ *   Departures from open3d 0.10: the source is moved, so the result maps source onto target and no final inverse is taken;
+ *     everything is in the clouds' own units and mu runs from D2 towards delta^2 as in the paper (open3d's normalised-unit
+ *     distance and its distance-versus-squared-distance comparison are not reproduced); centroids and D are taken over E, not
+ *     over the clouds; the edge test multiplies by the scale on both sides, as RANSAC's edge-length checker; rand() is
+ *     replaced by the counter-based draws above.
+ *   trace (NULL, or any member NULL: not written), for tests: trials [B, maximum_tuple_count] i64 the accepted trial ids,
+ *     entries [B, 3 maximum_tuple_count, 2] i32 = E, frame [B, 7] f64 = cs, ct, D2 (written when |E| >= 10), and per iteration
+ *     that ran transforms [B, iteration_number, 16] f64 = T before the step, mu [B, iteration_number] f64 = mu before the
+ *     step, sums27 [B, iteration_number, 27] f64 = A's upper triangle then g.  What is not reached keeps what it held.
+ *   One launch, one workgroup of 512 threads per pair: every loop is bounded by what the host passes (100 P <= 100 n_b
+ *   trials, iteration_number steps) and no workgroup waits for another.  Workspace:
+ *   pcrcg_fgr_batch_ws_bytes(B, n_total, maximum_tuple_count, iteration_number) = 96 B maximum_tuple_count bytes plus
+ *   alignment padding (today a function of B and maximum_tuple_count alone); 0 for arguments out of range.  Rejected with
+ *   PCRCG_EBADARG before anything launches: null pointers (trace may be NULL), B outside 1..65535, delta <= 0 or not finite,
+ *   division_factor <= 1, decrease_mu other than 0 or 1, iteration_number outside 1..65536, tuple_scale outside [0, 1],
+ *   maximum_tuple_count outside 1..4096; a short workspace gives PCRCG_EWORKSPACE.  The entry allocates nothing and
+ *   synchronises nothing.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct pcrcg_fgr_trace {
+    int64_t* trials;
+    int* entries;
+    double* frame;
+    double* transforms;
+    double* mu;
+    double* sums27;
+} pcrcg_fgr_trace;
+
+size_t pcrcg_mutual_match_batch_ws_bytes(int B, int n_total, int m_total);
+int pcrcg_mutual_match_batch(const float* src_feat, int ld_src, const int* src_off, int n_total, int n_max,
+                             const float* tgt_feat, int ld_tgt, const int* tgt_off, int m_total, int m_max, int c, int B,
+                             int* corr, int* k, void* ws, size_t ws_bytes, void* stream);
+size_t pcrcg_fgr_batch_ws_bytes(int B, int n_total, int maximum_tuple_count, int iteration_number);
+int pcrcg_fgr_batch(const float* src, const int* src_off, const float* tgt, const int* tgt_off, const int* corr, const int* k, int B,
+                    double maximum_correspondence_distance, double division_factor, int decrease_mu, int iteration_number,
+                    double tuple_scale, int maximum_tuple_count, const uint64_t* seeds, double* out_transform, double* out_stats,
+                    const pcrcg_fgr_trace* trace, void* ws, size_t ws_bytes, void* stream);
 
 /* Voxel down-sampling: open3d's PointCloud::VoxelDownSample for B ragged clouds in one set of launches (csrc/voxel.hip;
  * added under ABI version 4, which it does not change) -- what ref:datasets/kitti.py:134-140 does to both raw scans of a

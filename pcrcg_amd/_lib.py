@@ -175,6 +175,14 @@ SIGNATURES = {
     "pcrcg_icp_batch_ex": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, ctypes.c_double,
                                    c_int, ctypes.c_double, ctypes.c_double, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                    c_void_p, c_size_t, c_void_p]),
+    # fast global registration (registration.mutual_match_batch, fast_global_registration_batch)
+    "pcrcg_mutual_match_batch_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "pcrcg_mutual_match_batch": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int,
+                                         c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "pcrcg_fgr_batch_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "pcrcg_fgr_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, ctypes.c_double,
+                                ctypes.c_double, c_int, c_int, ctypes.c_double, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                c_void_p, c_size_t, c_void_p]),
     # voxel down-sampling of raw scans (pcrcg_amd/kitti.py)
     "pcrcg_voxel_down_sample_ws_bytes": (c_size_t, [c_int, c_int]),
     "pcrcg_voxel_down_sample_batch": (c_int, [c_void_p, c_void_p, c_int, c_int, ctypes.c_double, c_void_p, c_void_p, c_void_p,

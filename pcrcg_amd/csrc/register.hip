@@ -216,6 +216,43 @@ __global__ void __launch_bounds__(256) k_mutual_emit(const int* __restrict__ fla
     corr[2 * o + 1] = (int)arg_s[i];
 }
 
+// the mutual L2 list of ragged pairs (pcrcg_mutual_match_batch): one workgroup per pair walks its source rows 256 at a time,
+// ps / pt the packed arg-max words of the rows (source -> target) and of the columns (target -> source).  Row i is kept iff
+// its column's arg-max is i; a block scan ranks a round's kept rows, so the list is in ascending i.  Rows k .. n - 1 of the
+// pair get (-1, -1).  (A kept row is written at or before its own place, the tail after the walk: corr is never read.)
+__global__ void __launch_bounds__(256) k_mutual_emit_batch(const u64* __restrict__ ps, const int* __restrict__ s_off,
+                                                           const u64* __restrict__ pt, const int* __restrict__ t_off,
+                                                           int* __restrict__ corr, int* __restrict__ k) {
+    __shared__ int s_scan[4];
+    const int p = blockIdx.x;
+    const int i0 = s_off[p], n = s_off[p + 1] - i0;
+    const int j0 = t_off[p], m = t_off[p + 1] - j0;
+    int kept = 0;
+    if (m > 0) {
+        for (int base = 0; base < n; base += 256) {
+            const int i = base + (int)threadIdx.x;
+            int j = -1;
+            bool keep = false;
+            if (i < n) {
+                j = (int)(0xFFFFFFFFu - (unsigned)(ps[i0 + i] & 0xFFFFFFFFull));
+                keep = j >= 0 && j < m && (int)(0xFFFFFFFFu - (unsigned)(pt[j0 + j] & 0xFFFFFFFFull)) == i;
+            }
+            int total;
+            const int rank = block_excl_scan_i32<256>(keep ? 1 : 0, &total, s_scan);
+            if (keep) {
+                corr[2 * (long)(i0 + kept + rank)] = i;
+                corr[2 * (long)(i0 + kept + rank) + 1] = j;
+            }
+            kept += total;
+        }
+    }
+    for (int i = kept + (int)threadIdx.x; i < n; i += 256) {
+        corr[2 * (long)(i0 + i)] = -1;
+        corr[2 * (long)(i0 + i) + 1] = -1;
+    }
+    if (threadIdx.x == 0) k[p] = kept;
+}
+
 // ---- hypotheses ----------------------------------------------------------------------------------------------------
 struct HypArgs {
     const float* src;
@@ -798,6 +835,53 @@ InlierWs carve_inlier(Carver& cv, int n_total, int m_total) {
 
 constexpr int kMaxBatch = 65535;      // pairs ride on a grid dimension
 
+// The L2 arg-max of every row of a over its pair's rows of b, for B ragged pairs (pcrcg_feature_match_batch; both directions of
+// pcrcg_mutual_match_batch): packed [rows of a] must be zeroed, hb = k_half_norms of b.  The single-pair launch shapes with the
+// pair count folded into the workgroup target; the arg-max does not depend on how the columns are split, so every pair gets
+// the single-pair result.
+void launch_l2nn_batch(const float* a, int lda, const int* a_off, int n_max, const float* b, int ldb, const int* b_off, int m_max,
+                       int c, int B, const float* hb, u64* packed, hipStream_t st) {
+    const bool aligned = lda % 4 == 0 && ldb % 4 == 0 && ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15) == 0;
+    if ((c == 32 || c == 64) && aligned) {
+        const int gxm = (n_max + 127) / 128;
+        long splits = (1024 + (long)gxm * B - 1) / ((long)gxm * B);
+        const int max_splits = (m_max + 255) / 256;
+        if (splits > max_splits) splits = max_splits;
+        if (splits < 1) splits = 1;
+        const int cols_per = ((m_max + (int)splits - 1) / (int)splits + 31) / 32 * 32;
+        const dim3 grid(gxm, (m_max + cols_per - 1) / cols_per, B);
+        if (c == 32)
+            hipLaunchKernelGGL(k_l2nn_mfma_batch<32>, grid, dim3(256), 0, st, a, lda, a_off, b, ldb, b_off, hb, cols_per, packed);
+        else
+            hipLaunchKernelGGL(k_l2nn_mfma_batch<64>, grid, dim3(256), 0, st, a, lda, a_off, b, ldb, b_off, hb, cols_per, packed);
+    } else {
+        const int gx = (n_max + 255) / 256;
+        long splits = (2048 + (long)gx * B - 1) / ((long)gx * B);
+        const int max_splits = (m_max + 127) / 128;
+        if (splits > max_splits) splits = max_splits;
+        if (splits < 1) splits = 1;
+        const int cols_per = (m_max + (int)splits - 1) / (int)splits;
+        hipLaunchKernelGGL(k_l2nn_any_batch, dim3(gx, (m_max + cols_per - 1) / cols_per, B), dim3(256), 0, st, a, lda, a_off, b,
+                           ldb, b_off, c, hb, cols_per, packed);
+    }
+}
+
+struct MutualWs {
+    u64* ps;       // [n_total] the rows' arg-max words
+    u64* pt;       // [m_total] the columns'
+    float* hs;     // [n_total] |a_i|^2 / 2
+    float* ht;     // [m_total] |b_j|^2 / 2
+};
+
+MutualWs carve_mutual(Carver& cv, int n_total, int m_total) {
+    MutualWs w;
+    w.ps = cv.take<u64>((size_t)(n_total > 0 ? n_total : 1));
+    w.pt = cv.take<u64>((size_t)(m_total > 0 ? m_total : 1));
+    w.hs = cv.take<float>((size_t)(n_total > 0 ? n_total : 1));
+    w.ht = cv.take<float>((size_t)(m_total > 0 ? m_total : 1));
+    return w;
+}
+
 }  // namespace
 }  // namespace pcrcg
 
@@ -931,35 +1015,38 @@ int pcrcg_feature_match_batch(const float* src_feat, int ld_src, const int* src_
     hipStream_t st = as_stream(stream);
     PCRCG_CHECK_HIP(hipMemsetAsync(w.packed, 0, (size_t)n_total * 8, st));
     hipLaunchKernelGGL(k_half_norms, dim3((m_total + 255) / 256), dim3(256), 0, st, tgt_feat, ld_tgt, m_total, c, w.hb);
-    const bool aligned = ld_src % 4 == 0 && ld_tgt % 4 == 0 &&
-                         ((reinterpret_cast<uintptr_t>(src_feat) | reinterpret_cast<uintptr_t>(tgt_feat)) & 15) == 0;
-    // the single-pair launch shapes with the pair count folded into the workgroup target; the arg-max does not depend on
-    // how the columns are split, so every pair gets the single-pair result
-    if ((c == 32 || c == 64) && aligned) {
-        const int gxm = (n_max + 127) / 128;
-        long splits = (1024 + (long)gxm * B - 1) / ((long)gxm * B);
-        const int max_splits = (m_max + 255) / 256;
-        if (splits > max_splits) splits = max_splits;
-        if (splits < 1) splits = 1;
-        const int cols_per = ((m_max + (int)splits - 1) / (int)splits + 31) / 32 * 32;
-        const dim3 grid(gxm, (m_max + cols_per - 1) / cols_per, B);
-        if (c == 32)
-            hipLaunchKernelGGL(k_l2nn_mfma_batch<32>, grid, dim3(256), 0, st, src_feat, ld_src, src_off, tgt_feat, ld_tgt, tgt_off,
-                               w.hb, cols_per, w.packed);
-        else
-            hipLaunchKernelGGL(k_l2nn_mfma_batch<64>, grid, dim3(256), 0, st, src_feat, ld_src, src_off, tgt_feat, ld_tgt, tgt_off,
-                               w.hb, cols_per, w.packed);
-    } else {
-        const int gx = (n_max + 255) / 256;
-        long splits = (2048 + (long)gx * B - 1) / ((long)gx * B);
-        const int max_splits = (m_max + 127) / 128;
-        if (splits > max_splits) splits = max_splits;
-        if (splits < 1) splits = 1;
-        const int cols_per = (m_max + (int)splits - 1) / (int)splits;
-        hipLaunchKernelGGL(k_l2nn_any_batch, dim3(gx, (m_max + cols_per - 1) / cols_per, B), dim3(256), 0, st, src_feat, ld_src,
-                           src_off, tgt_feat, ld_tgt, tgt_off, c, w.hb, cols_per, w.packed);
-    }
+    launch_l2nn_batch(src_feat, ld_src, src_off, n_max, tgt_feat, ld_tgt, tgt_off, m_max, c, B, w.hb, w.packed, st);
     hipLaunchKernelGGL(k_nn_emit_batch, dim3((n_max + 255) / 256, B), dim3(256), 0, st, w.packed, src_off, corr, k);
+    PCRCG_CHECK_LAUNCH();
+    return PCRCG_OK;
+}
+
+size_t pcrcg_mutual_match_batch_ws_bytes(int B, int n_total, int m_total) {
+    if (B < 1 || B > kMaxBatch || n_total < 0 || m_total < 0) return 0;
+    Carver cv(nullptr, 0);
+    carve_mutual(cv, n_total, m_total);
+    return cv.off;
+}
+
+int pcrcg_mutual_match_batch(const float* src_feat, int ld_src, const int* src_off, int n_total, int n_max,
+                             const float* tgt_feat, int ld_tgt, const int* tgt_off, int m_total, int m_max, int c, int B,
+                             int* corr, int* k, void* ws, size_t ws_bytes, void* stream) {
+    PCRCG_CHECK_ARG(src_feat && src_off && tgt_feat && tgt_off && corr && k && ws);
+    PCRCG_CHECK_ARG(B >= 1 && B <= kMaxBatch);
+    PCRCG_CHECK_ARG(n_max >= 1 && m_max >= 1 && n_total >= n_max && m_total >= m_max);
+    PCRCG_CHECK_ARG(c >= 1 && ld_src >= c && ld_tgt >= c);
+    Carver cv(ws, ws_bytes);
+    MutualWs w = carve_mutual(cv, n_total, m_total);
+    PCRCG_CHECK_WS(cv);
+    hipStream_t st = as_stream(stream);
+    PCRCG_CHECK_HIP(hipMemsetAsync(w.ps, 0, (size_t)n_total * 8, st));
+    PCRCG_CHECK_HIP(hipMemsetAsync(w.pt, 0, (size_t)m_total * 8, st));
+    hipLaunchKernelGGL(k_half_norms, dim3((m_total + 255) / 256), dim3(256), 0, st, tgt_feat, ld_tgt, m_total, c, w.ht);
+    hipLaunchKernelGGL(k_half_norms, dim3((n_total + 255) / 256), dim3(256), 0, st, src_feat, ld_src, n_total, c, w.hs);
+    // nn_s: pcrcg_feature_match_batch's launch; nn_t: the same with the roles exchanged
+    launch_l2nn_batch(src_feat, ld_src, src_off, n_max, tgt_feat, ld_tgt, tgt_off, m_max, c, B, w.ht, w.ps, st);
+    launch_l2nn_batch(tgt_feat, ld_tgt, tgt_off, m_max, src_feat, ld_src, src_off, n_max, c, B, w.hs, w.pt, st);
+    hipLaunchKernelGGL(k_mutual_emit_batch, dim3(B), dim3(256), 0, st, w.ps, src_off, w.pt, tgt_off, corr, k);
     PCRCG_CHECK_LAUNCH();
     return PCRCG_OK;
 }

@@ -9,6 +9,12 @@
                                 `register(..., mutual=False, seed=seeds[b])`'s, bit for bit.
   * `ransac_pose_estimation_batch` -- the same as numpy [B,4,4] (the reference's mutual=False branch, pair by pair).
   * `feature_match_batch`    -- the nearest-neighbour lists of many pairs in one launch set.
+  * `mutual_match_batch`     -- the mutual L2 nearest-neighbour lists of many pairs in one launch set.
+  * `fast_global_registration_batch` -- fast global registration (Zhou, Park, Koltun 2016; open3d's
+                                registration_fast_based_on_feature_matching) of many pairs in one launch, on the mutual L2
+                                matches of their descriptors or on the caller's correspondences
+                                (`FastGlobalRegistrationResult`, which `refine_batch` takes as its start);
+                                `fast_global_registration` is the same for one pair.
   * `refine_batch`           -- ICP of many pairs in one set of launches (`BatchRefinementResult`), the local pass after
                                 RANSAC's global one: point-to-point, or point-to-plane on the targets' normals;
                                 `refine` is the same for one pair.
@@ -255,7 +261,8 @@ def register_batch(src_pcds, tgt_pcds, src_feats, tgt_feats, distance_threshold=
 
     Inputs: four lists of per-pair [N_b,3] / [M_b,3] points and [N_b,C] / [M_b,C] descriptors (numpy, CPU or HIP tensors;
     one C for the whole batch).  seeds: an int (every pair) or a sequence of B ints in [0, 2^24).  Only the L2
-    nearest-neighbour correspondences are offered (mutual=True raises).  pairs_per_call bounds the pairs per launch set
+    nearest-neighbour correspondences are offered (mutual=True raises; the batched mutual L2 list is
+    mutual_match_batch, and fast_global_registration_batch registers on it).  pairs_per_call bounds the pairs per launch set
     and so the workspace; by default it is the largest count whose pcrcg_ransac_batch_ws_bytes, sized with the largest
     pair, stays within BATCH_WS_BUDGET.  Every size is checked on the host before anything is uploaded or launched; all
     chunks write into one device buffer, read ONCE at the end."""
@@ -324,6 +331,268 @@ def ransac_pose_estimation_batch(src_pcds, tgt_pcds, src_feats, tgt_feats, mutua
     return register_batch(src_pcds, tgt_pcds, src_feats, tgt_feats, distance_threshold, ransac_n,
                           max_iteration=max_iteration, max_validation=max_validation, seeds=seeds,
                           pairs_per_call=pairs_per_call).matrices
+
+
+_MAX_FGR_TUPLES = 4096         # include/pcrcg.h
+_MAX_FGR_ITERATION = 1 << 16
+
+
+class _FgrTrace(ctypes.Structure):
+    """Mirror of pcrcg_fgr_trace (include/pcrcg.h)."""
+    _fields_ = [(f, ctypes.c_void_p) for f in ("trials", "entries", "frame", "transforms", "mu", "sums27")]
+
+
+def _mutual_batch(fa, src_off, ns, fb, tgt_off, ms):
+    """pcrcg_mutual_match_batch over concatenated descriptors already on the device -> (corr, k).  A call whose sources or
+    targets are all empty has no list: every row (-1, -1), every k 0."""
+    n_tot, m_tot, c, nb = fa.shape[0], fb.shape[0], fa.shape[1], len(ns)
+    corr = torch.empty((n_tot, 2), dtype=torch.int32, device=fa.device)
+    k = torch.empty(nb, dtype=torch.int32, device=fa.device)
+    if n_tot == 0 or m_tot == 0:
+        return corr.fill_(-1), k.zero_()
+    L = _lib.lib()
+    wsb = L.pcrcg_mutual_match_batch_ws_bytes(nb, n_tot, m_tot)
+    ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device=fa.device)
+    _lib.check(L.pcrcg_mutual_match_batch(fa.data_ptr(), c, src_off.data_ptr(), n_tot, max(ns), fb.data_ptr(), c,
+                                          tgt_off.data_ptr(), m_tot, max(ms), c, nb, corr.data_ptr(), k.data_ptr(),
+                                          ws.data_ptr(), wsb, _stream()), "pcrcg_mutual_match_batch")
+    return corr, k
+
+
+def _descriptor_lists(who, src_feats, tgt_feats):
+    """Two equally long lists of [N_b, C] / [M_b, C] descriptor sets of one width C >= 1 -> (ns, ms, C); sets may be empty."""
+    if len(src_feats) != len(tgt_feats) or len(src_feats) == 0:
+        raise ValueError(f"{who}: need two equally long, non-empty lists of descriptor sets")
+    ns, ms, c = [], [], None
+    for b, (fs, ft) in enumerate(zip(src_feats, tgt_feats)):
+        ss, st = shape_of(fs), shape_of(ft)
+        if len(ss) != 2 or len(st) != 2:
+            raise ValueError(f"{who}: pair {b}: descriptors must be [N, C] arrays, got shapes {ss} and {st}")
+        c = ss[1] if c is None else c
+        if ss[1] != c or st[1] != c or c < 1:
+            raise ValueError(f"{who}: pair {b}: descriptor widths {(ss[1], st[1])}, the batch uses {c}")
+        ns.append(ss[0])
+        ms.append(st[0])
+    return ns, ms, c
+
+
+def mutual_match_batch(src_feats, tgt_feats):
+    """-> (corr [sum N_b, 2] int32 device, k [B] int32 device): the mutual L2 correspondences of B pairs in one launch set
+    (pcrcg_mutual_match_batch; include/pcrcg.h "Fast global registration").  Pair b's list starts at row sum(N_0 .. N_b-1): the
+    (i, j) with j the L2-nearest target descriptor of source i and i the L2-nearest source descriptor of target j (lowest
+    index on ties), ascending i, indices local to the pair; k[b] is its length and the pair's other rows are (-1, -1).  A pair
+    with an empty side has k = 0.  Nothing is read back."""
+    ns, ms, c = _descriptor_lists("mutual_match_batch", src_feats, tgt_feats)
+    if len(ns) > _MAX_BATCH or sum(ns) > ragged.MAX_ROWS or sum(ms) > ragged.MAX_ROWS:
+        raise ValueError("mutual_match_batch: more than 65535 pairs or 2^31 - 1 rows in one call")
+    dev = _device(*src_feats, *tgt_feats)
+    fa = _cat(src_feats, dev, "src_feats", c)
+    fb = _cat(tgt_feats, dev, "tgt_feats", c)
+    src_off, tgt_off = ragged.offsets(dev, ns, ms)
+    return _mutual_batch(fa, src_off, ns, fb, tgt_off, ms)
+
+
+class FastGlobalRegistrationResult(BatchRegistrationResult):
+    """Results of `fast_global_registration_batch` for B pairs (a BatchRegistrationResult as far as `refine_batch(init=...)` is
+    concerned: its device transforms are used, nothing is read back).  transformations: float64 [B,4,4] device tensor;
+    matrices: the same as numpy (from the one read); the six statistics as numpy [B]: n_correspondences (the list length P),
+    tuples (accepted), trials (trials_used), updates (Gauss-Newton steps applied): int64, -1 where the pair's seed was out of
+    range (its other outputs are NaN); mu (its final value) and inlier_share (the share of the entries within the distance at
+    the final pose): float64.  trace: None, or a dict of device tensors -- trials [B, maximum_tuple_count] int64 (-1: none),
+    entries [B, 3 maximum_tuple_count, 2] int32 (-1: none), frame [B,7] (cs, ct, D2), transforms [B, iteration_number, 4, 4],
+    mu [B, iteration_number], sums27 [B, iteration_number, 27] (NaN where an iteration did not run), corr / k: per call chunk
+    the correspondence lists the pairs ran on."""
+
+    def __init__(self, buf, host, B, trace=None):
+        self.transformations = buf[:16 * B].view(B, 4, 4)
+        self.matrices = host[:16 * B].reshape(B, 4, 4).copy()
+        st = host[16 * B:].reshape(B, _N_STATS)
+        count = lambda x: np.where(np.isfinite(x), x, -1).astype(np.int64)
+        self.n_correspondences = count(st[:, 0])
+        self.tuples = count(st[:, 1])
+        self.trials = count(st[:, 2])
+        self.updates = count(st[:, 3])
+        self.mu = st[:, 4].copy()
+        self.inlier_share = st[:, 5].copy()
+        self.trace = trace
+
+    def __repr__(self):
+        return (f"FastGlobalRegistrationResult(pairs={len(self)}, mean inlier_share={float(np.mean(self.inlier_share)):.6g}, "
+                f"mean updates={float(np.mean(self.updates)):.3g})")
+
+
+class FastGlobalRegistrationPair:
+    """One pair of a FastGlobalRegistrationResult: transformation (float64 [4,4] device tensor), matrix (numpy),
+    n_correspondences, tuples, trials, updates, mu, inlier_share, trace."""
+
+    def __init__(self, batch):
+        self.transformation = batch.transformations[0]
+        self.matrix = batch.matrices[0]
+        self.n_correspondences = int(batch.n_correspondences[0])
+        self.tuples = int(batch.tuples[0])
+        self.trials = int(batch.trials[0])
+        self.updates = int(batch.updates[0])
+        self.mu = float(batch.mu[0])
+        self.inlier_share = float(batch.inlier_share[0])
+        self.trace = batch.trace
+
+    def __repr__(self):
+        return (f"FastGlobalRegistrationPair(n_correspondences={self.n_correspondences}, tuples={self.tuples}, "
+                f"updates={self.updates}, inlier_share={self.inlier_share:.6g})")
+
+
+def _correspondence_chunk(correspondences, ns, ms, b0, b1, dev):
+    """The caller's per-pair [K_b, 2] lists of pairs b0 .. b1 - 1 -> (corr [sum N_b, 2] int32 with each pair's list at its
+    source offset and (-1, -1) elsewhere, k [nb] int32), on the device: host lists travel in ONE upload."""
+    n_tot = sum(ns[b0:b1])
+    ks = [_rows(c) for c in correspondences[b0:b1]]
+    if all(not (isinstance(c, torch.Tensor) and c.is_cuda) for c in correspondences[b0:b1]):
+        host = np.full((n_tot, 2), -1, dtype=np.int32)
+        at = 0
+        for b in range(b0, b1):
+            c = correspondences[b]
+            host[at:at + ks[b - b0]] = np.asarray(c.numpy() if isinstance(c, torch.Tensor) else c).reshape(-1, 2)
+            at += ns[b]
+        corr = torch.from_numpy(host).to(dev)
+    else:
+        corr = torch.full((n_tot, 2), -1, dtype=torch.int32, device=dev)
+        at = 0
+        for b in range(b0, b1):
+            c = correspondences[b]
+            if ks[b - b0]:
+                c = c if isinstance(c, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(c))
+                corr[at:at + ks[b - b0]] = c.to(device=dev, dtype=torch.int32)
+            at += ns[b]
+    return corr, torch.tensor(ks, dtype=torch.int32, device=dev)
+
+
+
+def fast_global_registration_batch(src_pcds, tgt_pcds, src_feats=None, tgt_feats=None, *, maximum_correspondence_distance,
+                                   correspondences=None, division_factor=1.4, decrease_mu=True, iteration_number=64,
+                                   tuple_scale=0.95, maximum_tuple_count=1000, seeds=0, pairs_per_call=None, trace=False):
+    """Fast global registration (Zhou, Park, Koltun 2016; open3d's registration_fast_based_on_feature_matching) for B pairs
+    in one launch per call (pcrcg_fgr_batch; include/pcrcg.h "Fast global registration" is the definition, DESIGN.md section
+    22) -> FastGlobalRegistrationResult.  Deterministic: pair b's result depends on its clouds, its correspondences, the
+    parameters and seeds[b] alone, bit for bit.
+
+    Inputs: two lists of per-pair [N_b,3] / [M_b,3] points (numpy, CPU or HIP tensors; empty clouds are allowed: the pair gets
+    the identity), and EITHER src_feats / tgt_feats, lists of [N_b,C] / [M_b,C] descriptors -- the pairs are matched by
+    `mutual_match_batch`'s mutual L2 rule in the same call -- OR correspondences=, a list of per-pair [K_b,2] integer arrays of
+    (source row, target row), K_b <= N_b (host arrays are checked against the cloud sizes; device tensors are trusted, as the
+    library entry trusts its list).  The source is moved: the result maps source onto target.  maximum_correspondence_distance
+    (in the clouds' units) is where the graduated robust weight stops; tuple_scale = 0 skips the tuple test and takes the
+    first 3 maximum_tuple_count correspondences.  seeds: an int (every pair) or B ints in [0, 2^24).  pairs_per_call bounds
+    the pairs per launch set and so the workspace (default: what keeps it within BATCH_WS_BUDGET).  Every check runs on the
+    host before anything is uploaded or launched; all chunks write into one device buffer, read ONCE at the end."""
+    who = "fast_global_registration_batch"
+    B = len(src_pcds)
+    if len(tgt_pcds) != B:
+        raise ValueError(f"{who}: list lengths differ ({B}, {len(tgt_pcds)})")
+    if B == 0:
+        raise ValueError(f"{who}: no pairs")
+    by_feats = src_feats is not None or tgt_feats is not None
+    if by_feats == (correspondences is not None):
+        raise ValueError(f"{who}: give src_feats and tgt_feats, or correspondences=, not both and not neither")
+    if by_feats and (src_feats is None or tgt_feats is None):
+        raise ValueError(f"{who}: src_feats and tgt_feats come together")
+    d = float(maximum_correspondence_distance)
+    if not 0.0 < d < float("inf"):
+        raise ValueError(f"{who}: maximum_correspondence_distance must be positive and finite")
+    div = float(division_factor)
+    if not 1.0 < div < float("inf"):
+        raise ValueError(f"{who}: division_factor must be above 1")
+    it = int(iteration_number)
+    if not 1 <= it <= _MAX_FGR_ITERATION:
+        raise ValueError(f"{who}: iteration_number = {it}, need 1..{_MAX_FGR_ITERATION}")
+    ts = float(tuple_scale)
+    if not 0.0 <= ts <= 1.0:
+        raise ValueError(f"{who}: tuple_scale must lie in [0, 1]")
+    mtc = int(maximum_tuple_count)
+    if not 1 <= mtc <= _MAX_FGR_TUPLES:
+        raise ValueError(f"{who}: maximum_tuple_count = {mtc}, need 1..{_MAX_FGR_TUPLES}")
+    seeds = ragged.seed_list(seeds, B, who, "pairs")
+    ns = [_cloud_rows(x, who, "the source", b) for b, x in enumerate(src_pcds)]
+    ms = [_cloud_rows(x, who, "the target", b) for b, x in enumerate(tgt_pcds)]
+    c = None
+    if by_feats:
+        if len(src_feats) != B or len(tgt_feats) != B:
+            raise ValueError(f"{who}: {len(src_feats)} / {len(tgt_feats)} descriptor sets for {B} pairs")
+        fns, fms, c = _descriptor_lists(who, src_feats, tgt_feats)
+        if fns != ns or fms != ms:
+            raise ValueError(f"{who}: the descriptors must have one row per point")
+    else:
+        if len(correspondences) != B:
+            raise ValueError(f"{who}: {len(correspondences)} correspondence lists for {B} pairs")
+        for b, cb in enumerate(correspondences):
+            shape = shape_of(cb)
+            if len(shape) != 2 or shape[1] != 2:
+                raise ValueError(f"{who}: pair {b}: correspondences must be a [K, 2] array, got shape {shape}")
+            if shape[0] > ns[b]:
+                raise ValueError(f"{who}: pair {b}: {shape[0]} correspondences for {ns[b]} source points (at most one per row)")
+            if shape[0] and not (isinstance(cb, torch.Tensor) and cb.is_cuda):
+                h = np.asarray(cb.numpy() if isinstance(cb, torch.Tensor) else cb)
+                if h.dtype.kind not in "iu":
+                    raise ValueError(f"{who}: pair {b}: correspondences must be integers, got {h.dtype}")
+                if h.min() < 0 or h[:, 0].max() >= ns[b] or h[:, 1].max() >= ms[b]:
+                    raise ValueError(f"{who}: pair {b}: a correspondence lies outside the pair's clouds")
+    L = _lib.lib()
+    if pairs_per_call is None:
+        pairs_per_call = ragged.per_call_within(BATCH_WS_BUDGET, L.pcrcg_fgr_batch_ws_bytes(1, max(ns), mtc, it))
+    chunks = ragged.chunks(B, pairs_per_call, _MAX_BATCH, who, ns, ms)
+    dev = _device(*src_pcds, *tgt_pcds, *(list(src_feats) + list(tgt_feats) if by_feats else correspondences))
+    wsb = max(L.pcrcg_fgr_batch_ws_bytes(b1 - b0, sum(ns[b0:b1]), mtc, it) for b0, b1 in chunks)
+    if wsb == 0:
+        raise ValueError(f"{who}: sizes out of range for the batch workspace")
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    out = torch.empty(B * (16 + _N_STATS), dtype=torch.float64, device=dev)
+    seeds_d = torch.tensor(seeds, dtype=torch.int64, device=dev)
+    tr = None
+    if trace:
+        nan = float("nan")
+        tr = {"trials": torch.full((B, mtc), -1, dtype=torch.int64, device=dev),
+              "entries": torch.full((B, 3 * mtc, 2), -1, dtype=torch.int32, device=dev),
+              "frame": torch.full((B, 7), nan, dtype=torch.float64, device=dev),
+              "transforms": torch.full((B, it, 4, 4), nan, dtype=torch.float64, device=dev),
+              "mu": torch.full((B, it), nan, dtype=torch.float64, device=dev),
+              "sums27": torch.full((B, it, 27), nan, dtype=torch.float64, device=dev), "corr": [], "k": []}
+    for b0, b1 in chunks:
+        nb = b1 - b0
+        src = _cat(src_pcds[b0:b1], dev, "src_pcds", 3)
+        tgt = _cat(tgt_pcds[b0:b1], dev, "tgt_pcds", 3)
+        src_off, tgt_off = ragged.offsets(dev, ns[b0:b1], ms[b0:b1])
+        if by_feats:
+            fa = _cat(src_feats[b0:b1], dev, "src_feats", c)
+            fb = _cat(tgt_feats[b0:b1], dev, "tgt_feats", c)
+            corr, k = _mutual_batch(fa, src_off, ns[b0:b1], fb, tgt_off, ms[b0:b1])
+        else:
+            corr, k = _correspondence_chunk(correspondences, ns, ms, b0, b1, dev)
+        tr_ptr = None
+        if trace:
+            tr["corr"].append(corr)
+            tr["k"].append(k)
+            tr_ptr = ctypes.byref(_FgrTrace(*[tr[f][b0:].data_ptr() for f in ("trials", "entries", "frame", "transforms", "mu",
+                                                                            "sums27")]))
+        # (an empty stack has no storage: any valid address stands in for rows that no pair can index)
+        _lib.check(L.pcrcg_fgr_batch((src if src.numel() else out).data_ptr(), src_off.data_ptr(),
+                                     (tgt if tgt.numel() else out).data_ptr(), tgt_off.data_ptr(),
+                                     (corr if corr.numel() else out).data_ptr(), k.data_ptr(), nb, d, div, int(bool(decrease_mu)),
+                                     it, ts, mtc, seeds_d[b0:].data_ptr(), out[16 * b0:].data_ptr(),
+                                     out[16 * B + _N_STATS * b0:].data_ptr(), tr_ptr, ws.data_ptr(), wsb, _stream()),
+                   "pcrcg_fgr_batch")
+    return FastGlobalRegistrationResult(out, _read(out), B, tr)
+
+
+def fast_global_registration(src_pcd, tgt_pcd, src_feat=None, tgt_feat=None, *, maximum_correspondence_distance,
+                             correspondences=None, division_factor=1.4, decrease_mu=True, iteration_number=64, tuple_scale=0.95,
+                             maximum_tuple_count=1000, seed=0, trace=False):
+    """Fast global registration of one pair -> FastGlobalRegistrationPair: fast_global_registration_batch with a batch of one
+    (src_feat / tgt_feat: the pair's descriptors, or correspondences: its [K,2] list)."""
+    return FastGlobalRegistrationPair(fast_global_registration_batch(
+        [src_pcd], [tgt_pcd], None if src_feat is None else [src_feat], None if tgt_feat is None else [tgt_feat],
+        maximum_correspondence_distance=maximum_correspondence_distance,
+        correspondences=None if correspondences is None else [correspondences], division_factor=division_factor,
+        decrease_mu=decrease_mu, iteration_number=iteration_number, tuple_scale=tuple_scale,
+        maximum_tuple_count=maximum_tuple_count, seeds=int(seed), trace=trace))
 
 
 _N_ICP_STATS = 4   # fitness, inlier_rmse, correspondences, updates applied
