@@ -72,6 +72,76 @@ def test_fewer_than_six_correspondences_stop_the_pair(corner):
     assert PR.update(src, tgt, nrm, T_gt, few)[0] is None
 
 
+def test_the_cases_are_what_they_claim():
+    """The conditions tests/test_icp_plane_edges_gpu.py and tests/test_smallsolve_cpu.py rely on, checked on the restatement."""
+    # the ladder: the rungs 0, 10, 100 m update at every step with every pivot ratio 10 x above the rule, 1000 m is refused
+    # 10 x below it (300 m, 4 x above, is left out)
+    for s in PR.LADDER:
+        src, tgt, T_gt, nrm, run = PR.ladder_case(s)
+        assert run[4] >= 2 and run[1] == 1.0 and len(run[5]) == run[4] + 1
+        lowest = min(PR.pivot_ratios(A).min() for A, _ in PR.ladder_systems(s))
+        cond = np.linalg.cond(PR.ladder_systems(s)[0][0])
+        worst = PR.worst_displacement(src, run[0], T_gt)
+        print(f"s = {s}: cond(A) at T_0 {cond:.2e}, lowest pivot ratio {lowest:.2e}, updates {run[4]}, worst point {worst:.2e}")
+        assert lowest >= 1e-11 and run[4] < PR.LADDER_MI
+        for (A, b), (Tk, _, _) in zip(PR.ladder_systems(s), run[5]):
+            assert PR.solve_ldlt(A, b) is not None and len(PR.pivot_ratios(A)) == 6
+    src, tgt, T_gt, nrm, run = PR.ladder_case(PR.FAR)
+    A, b = PR.ladder_systems(PR.FAR)[0]
+    ratios = PR.pivot_ratios(A)
+    failing = ratios[ratios <= PR.PIVOT_RATIO]
+    print(f"s = {PR.FAR}: cond(A) at T_0 {np.linalg.cond(A):.2e}, pivot ratios {ratios}")
+    assert len(failing) >= 1 and failing[0] <= 1e-13 and (ratios[:4] > 1e-11).all()
+    assert run[4] == 0 and run[1] == 1.0 and np.array_equal(run[0], np.eye(4)) and PR.solve_ldlt(A, b) is None
+    assert PR.step_from_sums(np.concatenate([A[np.triu_indices(6)], b]), np.eye(4)) is None
+    for s in PR.LADDER + (PR.FAR,):
+        src, tgt, T_gt = PR.offset_pair(s)
+        assert src.min() >= s - 0.1 and IR.evaluate(src, tgt, T_gt, 0.01)[2] == len(src)
+    # the near-plane pair: the lowest pivot ratio is small, and three to five decades above the rule
+    assert PR.near_plane_pair.__defaults__[2] == 2e-3
+    for tilt, (low, high) in PR.NEAR_PLANE_TILTS.items():
+        src, tgt, nrm, start = PR.near_plane_pair(tilt=tilt)
+        out = PR.icp(src, tgt, nrm, start, D, max_iteration=10)
+        assert out[4] >= 1 and out[1] == 1.0
+        for Tk, _, _ in out[5]:
+            A, _ = PR.system(PR.sums27(src, tgt, nrm, Tk, IR.evaluate(src, tgt, Tk, D)[0])[0])
+            ratios = PR.pivot_ratios(A)
+            assert len(ratios) == 6 and low <= ratios.min() <= high, (tilt, ratios)
+        assert np.abs(np.linalg.norm(nrm, axis=1) - 1.0).max() < 1e-15 and (src[:, 2] != 0).sum() == len(src) - 300
+    # the sizes: one update or more from six points on, none below; every start is its own
+    starts = set()
+    for i, n in enumerate(PR.SIZES):
+        src, tgt, nrm, start = PR.sized_pair(i, n)
+        assert len(src) == len(tgt) == len(nrm) == n
+        starts.add(start.tobytes())
+        out = PR.icp(src, tgt, nrm, start, D, max_iteration=10)
+        assert IR.evaluate(src, tgt, start, D)[2] == n
+        if n >= 6:
+            assert out[4] >= 1, n
+        else:
+            assert out[4] == 0 and np.array_equal(out[0], start), n
+        off = start @ np.linalg.inv(PR.planted_pose())
+        angle = np.degrees(np.arccos(np.clip((np.trace(off[:3, :3]) - 1) / 2, -1, 1)))
+        assert 0.8 <= angle <= 1.6 and 0.008 <= np.linalg.norm(off[:3, 3]) <= 0.03, (n, angle, off[:3, 3])
+    assert len(starts) == len(PR.SIZES)
+
+
+def test_pivot_ratios_and_step_from_sums_follow_the_solver():
+    rng = np.random.RandomState(11)
+    M = rng.randn(6, 9)
+    A, b = M @ M.T, rng.randn(6)
+    ratios = PR.pivot_ratios(A)
+    assert len(ratios) == 6 and ratios[0] == 1.0 and (ratios > 0).all() and (ratios <= 1).all()
+    s27 = np.concatenate([A[np.triu_indices(6)], b])
+    T = PR.planted_pose()
+    assert np.array_equal(PR.step_from_sums(s27, T), PR.delta_of(PR.solve_ldlt(A, b)) @ T)
+    x = PR.solve_longdouble(A, b)
+    assert np.abs(x.astype(np.float64) - np.linalg.solve(A, b)).max() < 1e-12
+    assert np.abs(PR.delta_longdouble(x).astype(np.float64) - PR.delta_of(x.astype(np.float64))).max() < 1e-15
+    A[2, :] = A[:, 2] = 0.0                                  # rank 5: the last pivot is 0 or rounding noise
+    assert PR.pivot_ratios(A)[-1] <= 1e-13 and PR.step_from_sums(np.concatenate([A[np.triu_indices(6)], b]), T) is None
+
+
 def test_delta_is_open3d_s_vector_to_matrix():
     x = np.array([0.3, -0.2, 0.5, 1.0, 2.0, 3.0])
     D4 = PR.delta_of(x)
