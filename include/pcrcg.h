@@ -1082,6 +1082,64 @@ int pcrcg_icp_batch_ex(const float* src, const int* src_off, int n_total, int n_
                        double* out_transform, double* out_stats, const pcrcg_icp_trace_ex* trace, void* ws, size_t ws_bytes,
                        void* stream);
 
+/* Generalized ICP: batched plane-to-plane refinement (csrc/icp.hip, csrc/gicp_terms.h; added under ABI version 4, which it
+ * does not change) -- Segal, Haehnel, Thrun, "Generalized-ICP" (RSS 2009); open3d's registration_generalized_icp with
+ * TransformationEstimationForGeneralizedICP(epsilon), restated as a deterministic algorithm; no bit parity with open3d is
+ * claimed.  This comment is the definition, DESIGN.md section 23 explains it, tests/gicp_ref.py restates it in numpy.
+ *
+ * pcrcg_covariances_from_normals: normals [n, 3] f64 DEVICE -> cov [n, 6] f64 DEVICE = (xx, xy, xz, yy, yz, zz), the packing
+ *   of pcrcg_estimate_normals_batch's cov, of C = I - (1 - epsilon) n n^T: a disc of unit extent in the tangent plane and
+ *   epsilon along the normal.  s = 1.0 - epsilon; a_r = s n_r; entry (r, c) = (r == c ? 1.0 : 0.0) - a_r n_c, in float64,
+ *   every operation rounded separately.  For a unit normal this is open3d's Rot diag(epsilon, 1, 1) Rot^T, and its
+ *   U diag(1, 1, epsilon) U^T from the neighbourhood covariance's SVD (sum u_i u_i^T = I).  It is even in n, bit for bit.  A
+ *   normal that is not finite gives entries that are not finite (they propagate: see Update).  One thread per row.
+ *   epsilon outside (0, 1] or NaN, a negative n, and a null normals / cov with n > 0 give PCRCG_EBADARG; n = 0 launches nothing.
+ *
+ * pcrcg_gicp_batch: layout, grid, init, n_max, the outputs, the statistics, the NaN rules, empty pairs, the `done` word and
+ *   the launch count are pcrcg_icp_batch's.
+ *   src_cov [n_total, 6] and tgt_cov [m_total, 6] f64 DEVICE, in the clouds' row order, packed as above; each is required
+ *     unless its side has no rows.  The source's covariances belong to the UNMOVED source cloud: the kernel rotates them.
+ *   Evaluate(T) is pcrcg_icp_batch's -- the same moved fp32 point, nearest target, lowest-index tie rule, count, fitness and
+ *     Euclidean rmse -- and convergence is tested on those values, as open3d's loop does.
+ *   Update: over the correspondences (i -> j), with p the moved source point (the float64 value of the fp32 result), q its
+ *     target and R the rotation block of T_k in float64 (row-major r00 .. r22), every operation in float64 and rounded
+ *     separately (csrc/gicp_terms.h):
+ *       X = R C_s[i], the full 3 x 3: X[r][c] = ((R[r][0] S[0][c] + R[r][1] S[1][c]) + R[r][2] S[2][c]);
+ *       M = C_t[j] + X R^T, six entries r <= c: M[r][c] = C_t[r][c] + ((X[r][0] R[c][0] + X[r][1] R[c][1]) + X[r][2] R[c][2]);
+ *       W = M^-1 by the adjugate: c00 = m11 m22 - m12 m12, c01 = m02 m12 - m01 m22, c02 = m01 m12 - m02 m11,
+ *         c11 = m00 m22 - m02 m02, c12 = m01 m02 - m00 m12, c22 = m00 m11 - m01 m01, det = ((m00 c00 + m01 c01) + m02 c02),
+ *         W = c / det (six divisions);
+ *       d = p - q; J0 = [-[p]x | I] (3 x 6), the rows of -[p]x being (0, pz, -py), (-pz, 0, px), (py, -px, 0): fast global
+ *         registration's Jacobian, about the origin;
+ *       with w_r the rows of W: g_r = p x w_r (the rows of W (-[p]x); a cross product is a b - c d per component); the
+ *         rotation block of J0^T W J0, row a and columns c >= a: the a-th component of p x (g_0[c], g_1[c], g_2[c]); the mixed
+ *         block [a][3 + c] = g_c[a]; the translation block = W; e_r = ((w_r0 d0 + w_r1 d1) + w_r2 d2); the terms of the right
+ *         side are -(p x e) and -e.
+ *     A = sum J0^T W J0 (the 21 entries of the upper triangle, row by row) and b = -sum J0^T W d (6), in float64 and in the
+ *     fixed order of the other sums (shuffle tree, the eight wavefronts in order, the workgroups in order).  A x = b is solved
+ *     by pcrcg_icp_batch_ex's LDL^T (csrc/smallsolve.h, its 1e-12 pivot rule) in the one lane that runs the other fits;
+ *     delta = Rz(x2) Ry(x1) Rx(x0) | (x3, x4, x5) and T <- delta T, as point-to-plane's.
+ *     The pair stops, keeping T, if count < 3 or the solve is refused.  A bad M has no special case: a covariance that is not
+ *     finite, or det M = 0 (zero covariances on both sides), makes the pair's sums not finite, the solve refuses and the pair
+ *     stops as a degenerate one -- the rule of a normal that is not finite in point-to-plane.  A row that is nobody's
+ *     correspondence is not read.
+ *   With C_s = C_t = I (epsilon = 1) the update is a Gauss-Newton step of point-to-point; nothing depends on the covariances'
+ *     common scale but the size of W.
+ *   Range: J0 takes the moved point about the ORIGIN, as point-to-plane's J does, so A's rotation block grows with |p|^2 and
+ *     cond(A) with (distance from the origin / extent of the cloud)^2; the pivot rule refuses a pair that is far enough out,
+ *     and callers re-centre such clouds ("Range" of pcrcg_icp_batch_ex; DESIGN.md section 23 has the numbers).
+ *   trace: pcrcg_icp_trace_ex's members; sums27 [B, max_iteration + 1, 27] = A's upper triangle then b of Evaluate(T_k).
+ *   Workspace: pcrcg_gicp_batch_ws_bytes(B, n_total, m_total, max_iteration) = pcrcg_icp_batch_ex_ws_bytes' value (28 terms a
+ *   slot); 0 as pcrcg_icp_batch_ws_bytes.  Bad arguments (pcrcg_icp_batch's, a missing src_cov with n_total > 0 or tgt_cov with
+ *   m_total > 0) give PCRCG_EBADARG, a short workspace PCRCG_EWORKSPACE, before anything launches. */
+int pcrcg_covariances_from_normals(const double* normals, long n, double epsilon, double* cov, void* stream);
+size_t pcrcg_gicp_batch_ws_bytes(int B, int n_total, int m_total, int max_iteration);
+int pcrcg_gicp_batch(const float* src, const int* src_off, int n_total, int n_max, const int* tgt_off, int m_total,
+                     const void* grid, const double* init, int B, double max_correspondence_distance, int max_iteration,
+                     double relative_fitness, double relative_rmse, const double* src_cov, const double* tgt_cov,
+                     double* out_transform, double* out_stats, const pcrcg_icp_trace_ex* trace, void* ws, size_t ws_bytes,
+                     void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Fast global registration
  * The other half of the classical global-registration recipe that FPFH feeds: Zhou, Park, Koltun, "Fast Global

@@ -175,6 +175,12 @@ SIGNATURES = {
     "pcrcg_icp_batch_ex": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, ctypes.c_double,
                                    c_int, ctypes.c_double, ctypes.c_double, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                    c_void_p, c_size_t, c_void_p]),
+    # Generalized ICP (registration.covariances_from_normals, generalized_icp_batch)
+    "pcrcg_covariances_from_normals": (c_int, [c_void_p, ctypes.c_long, ctypes.c_double, c_void_p, c_void_p]),
+    "pcrcg_gicp_batch_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "pcrcg_gicp_batch": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, ctypes.c_double,
+                                 c_int, ctypes.c_double, ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                 c_void_p, c_size_t, c_void_p]),
     # fast global registration (registration.mutual_match_batch, fast_global_registration_batch)
     "pcrcg_mutual_match_batch_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
     "pcrcg_mutual_match_batch": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int,

@@ -19,12 +19,17 @@
 // sum J J^T and -sum J r with r = (p - q) . n, J = [p x n, n] from the targets' normals (normals.hip), and the update solves
 // the 6 x 6 system by a pivoted LDL^T (smallsolve.h) and applies Rz Ry Rx | t of the solution.
 //
+// pcrcg_gicp_batch adds Generalized ICP as a third (EST = 2): the same evaluation again; every correspondence gathers the
+// covariances of its two points, W = (C_t + R C_s R^T)^-1 and the 27 terms of J0^T W J0 and -J0^T W d come from gicp_terms.h,
+// and the update is point-to-plane's solve and delta.  k_cov_from_normals builds such covariances from normals.
+//
 // All max_iteration + 1 evaluations are enqueued ahead; the host reads nothing in between.  The workgroups of a pair whose
 // `done` word is set leave at once.  No floating-point atomics: a pair's bits depend on its own points and T_0 alone.
 //
 // Compiled with -ffp-contract=off (every operation rounds where the source says).
 #include "cellgrid.h"
 #include "common.h"
+#include "gicp_terms.h"
 #include "kabsch.h"
 #include "smallsolve.h"
 
@@ -34,8 +39,10 @@ namespace {
 constexpr int kIcpThreads = 512;                  // evaluation workgroup: 512 consecutive source rows of one pair
 constexpr int kIcpWaves = kIcpThreads / kWave;
 constexpr int kIcpTerms = 16;                     // sum d2 | sum p [3] | sum q [3] | sum p q^T [9]
-constexpr int kIcpPlaneTerms = 28;                // sum d2 | sum J J^T, upper triangle [21] | -sum J r [6]
-template <int EST> constexpr int icp_terms() { return EST == 0 ? kIcpTerms : kIcpPlaneTerms; }   // EST 0: point-to-point, 1: point-to-plane
+constexpr int kIcpPlaneTerms = 28;                // sum d2 | sum J J^T, upper triangle [21] | -sum J r [6]; EST 2: J0^T W J0 | -J0^T W d
+// EST 0: point-to-point, 1: point-to-plane, 2: generalized
+template <int EST> constexpr int icp_terms() { return EST == 0 ? kIcpTerms : kIcpPlaneTerms; }
+constexpr int kEstGeneralized = 2;                // EST of pcrcg_gicp_batch; pcrcg_icp_batch_ex takes 0 or 1
 constexpr int kIcpMaxIteration = 1 << 16;
 constexpr int kIcpMaxBatch = 65535;               // pairs ride on a grid dimension
 
@@ -61,10 +68,12 @@ struct IcpArgs {
     double* tr_sums;      // [B, max_iteration + 1] or null
     int* tr_corr;         // [max_iteration + 1, n_total] or null
     const double* tgt_nrm;// [m_total, 3] point-to-plane: the targets' normals
-    double* tr_sums27;    // [B, max_iteration + 1, 27] or null (point-to-plane)
+    double* tr_sums27;    // [B, max_iteration + 1, 27] or null (point-to-plane, generalized)
     int n_total, n_max, max_iteration;
     float thr2;
     double rel_fitness, rel_rmse;
+    const double* src_cov;// [n_total, 6] generalized: the covariances of the unmoved sources ...
+    const double* tgt_cov;// [m_total, 6] ... and of the targets
 };
 
 __device__ inline long first_slot(const IcpArgs& a, int p) { return (long)(a.src_off[p] / kIcpThreads) + p; }
@@ -146,6 +155,23 @@ __global__ void __launch_bounds__(kIcpThreads) k_icp_evaluate(IcpArgs a, GridVie
             v[4 + r] = hit ? Q[r] : 0.0;
 #pragma unroll
             for (int c = 0; c < 3; ++c) v[7 + 3 * r + c] = hit ? P[r] * Q[c] : 0.0;
+        }
+    } else if constexpr (EST == 2) {
+        // W = (C_t[j] + R C_s[i] R^T)^-1 with R of T_k in float64; the terms of J0^T W J0 and -J0^T W d (gicp_terms.h)
+        if (hit) {
+            double R[9], Cs[6], Ct[6];
+#pragma unroll
+            for (int r = 0; r < 3; ++r)
+#pragma unroll
+                for (int c = 0; c < 3; ++c) R[3 * r + c] = st->T[4 * r + c];
+            const double* cs = a.src_cov + 6 * (long)(i0 + i);
+            const double* ct = a.tgt_cov + 6 * (long)bj;
+#pragma unroll
+            for (int e = 0; e < 6; ++e) { Cs[e] = cs[e]; Ct[e] = ct[e]; }
+            gicp_terms(P, Q, R, Cs, Ct, v + 1);
+        } else {
+#pragma unroll
+            for (int e = 1; e < kTerms; ++e) v[e] = 0.0;
         }
     } else {
         // residual r = (p - q) . n and its Jacobian J = [p x n, n] about the moved point; both even in n as J J^T and J r
@@ -242,16 +268,16 @@ __global__ void __launch_bounds__(kWave) k_icp_update(IcpArgs a, int it) {
     const bool converged = it > 0 && fabs(fitness - st->fitness) < a.rel_fitness && fabs(rmse - st->rmse) < a.rel_rmse;
     st->fitness = fitness;
     st->rmse = rmse;
-    if constexpr (EST == 1) {
+    if constexpr (EST != 0) {
         if (a.tr_sums27)
             for (int e = 0; e < 27; ++e) a.tr_sums27[27 * tslot + e] = s_tot[1 + e];
     }
-    if (converged || it >= a.max_iteration || count < (EST == 0 ? 3 : 6)) {
+    if (converged || it >= a.max_iteration || count < (EST == 1 ? 6 : 3)) {
         icp_finish(a, p, st, T, fitness, rmse, count, it);
         return;
     }
-    if constexpr (EST == 1) {
-        // Gauss-Newton step of sum r^2: (sum J J^T) x = -sum J r; delta = Rz(x2) Ry(x1) Rx(x0) | (x3, x4, x5)
+    if constexpr (EST != 0) {
+        // Gauss-Newton step of sum r^2 (EST 2: of sum d^T W d): (sum J J^T) x = -sum J r; delta = Rz(x2) Ry(x1) Rx(x0) | (x3, x4, x5)
         double x[6];
         if (!solve_ldlt6(s_tot + 1, s_tot + 22, x)) {
             icp_finish(a, p, st, T, fitness, rmse, count, it);
@@ -289,6 +315,20 @@ __global__ void __launch_bounds__(kWave) k_icp_update(IcpArgs a, int it) {
             const double v = (R[3 * r] * T[c] + R[3 * r + 1] * T[4 + c]) + R[3 * r + 2] * T[8 + c];
             st->T[4 * r + c] = c == 3 ? v + t[r] : v;
         }
+}
+
+// C = I - s n n^T of every normal (gicp_terms.h); one thread per row
+constexpr int kCovThreads = 256;
+constexpr int kCovMaxBlocks = 0x7FFFFFFF;
+
+__global__ void __launch_bounds__(kCovThreads) k_cov_from_normals(const double* normals, long n, double s, double* cov) {
+    const long i = (long)blockIdx.x * kCovThreads + threadIdx.x;
+    if (i >= n) return;
+    const double nr[3] = {normals[3 * i], normals[3 * i + 1], normals[3 * i + 2]};
+    double c[6];
+    gicp_cov_of_normal(nr, s, c);
+#pragma unroll
+    for (int e = 0; e < 6; ++e) cov[6 * i + e] = c[e];
 }
 
 struct IcpWs {
@@ -332,8 +372,9 @@ int icp_enqueue(const IcpArgs& a, const GridView& g, int B, hipStream_t st) {
 
 int icp_run(const char* who, const float* src, const int* src_off, int n_total, int n_max, const int* tgt_off, int m_total,
             const void* grid, const double* init, int B, double max_correspondence_distance, int max_iteration,
-            double relative_fitness, double relative_rmse, int estimation, const double* tgt_normals, double* out_transform,
-            double* out_stats, const pcrcg_icp_trace_ex& trace, void* ws, size_t ws_bytes, void* stream) {
+            double relative_fitness, double relative_rmse, int estimation, const double* tgt_normals, const double* src_cov,
+            const double* tgt_cov, double* out_transform, double* out_stats, const pcrcg_icp_trace_ex& trace, void* ws,
+            size_t ws_bytes, void* stream) {
     ICP_CHECK_ARG(src_off && tgt_off && grid && out_transform && out_stats && ws);
     ICP_CHECK_ARG(B >= 1 && B <= kIcpMaxBatch);
     ICP_CHECK_ARG(n_total >= 0 && m_total >= 0 && n_max >= 0 && n_max <= n_total);
@@ -341,8 +382,13 @@ int icp_run(const char* who, const float* src, const int* src_off, int n_total, 
     ICP_CHECK_ARG(max_correspondence_distance > 0.0 && max_correspondence_distance < 1e18);
     ICP_CHECK_ARG(max_iteration >= 1 && max_iteration <= kIcpMaxIteration);
     ICP_CHECK_ARG(relative_fitness >= 0.0 && relative_rmse >= 0.0);      // (false for a NaN)
-    ICP_CHECK_ARG(estimation == 0 || estimation == 1);
-    ICP_CHECK_ARG(estimation == 0 || m_total == 0 || tgt_normals);
+    if (estimation != kEstGeneralized) {       // (pcrcg_gicp_batch's own value: the _ex entry takes 0 or 1)
+        ICP_CHECK_ARG(estimation == 0 || estimation == 1);
+        ICP_CHECK_ARG(estimation == 0 || m_total == 0 || tgt_normals);
+    } else {
+        ICP_CHECK_ARG(n_total == 0 || src_cov);
+        ICP_CHECK_ARG(m_total == 0 || tgt_cov);
+    }
     Carver cv(ws, ws_bytes);
     IcpWs w = carve_icp(cv, B, n_total, estimation == 0 ? kIcpTerms : kIcpPlaneTerms);
     if (!cv.ok()) {
@@ -357,10 +403,12 @@ int icp_run(const char* who, const float* src, const int* src_off, int n_total, 
     a.out_t = out_transform; a.out_stats = out_stats;
     a.tr_t = trace.transforms; a.tr_counts = trace.counts; a.tr_sums = trace.sums; a.tr_corr = trace.corr;
     a.tgt_nrm = tgt_normals;
-    a.tr_sums27 = estimation == 1 ? trace.sums27 : nullptr;
+    a.tr_sums27 = estimation != 0 ? trace.sums27 : nullptr;
+    a.src_cov = src_cov; a.tgt_cov = tgt_cov;
     a.n_total = n_total; a.n_max = n_max; a.max_iteration = max_iteration;
     a.thr2 = (float)(max_correspondence_distance * max_correspondence_distance);
     a.rel_fitness = relative_fitness; a.rel_rmse = relative_rmse;
+    if (estimation == kEstGeneralized) return icp_enqueue<2>(a, g, B, as_stream(stream));
     return estimation == 0 ? icp_enqueue<0>(a, g, B, as_stream(stream)) : icp_enqueue<1>(a, g, B, as_stream(stream));
 }
 #undef ICP_CHECK_ARG
@@ -386,7 +434,8 @@ int pcrcg_icp_batch(const float* src, const int* src_off, int n_total, int n_max
     pcrcg_icp_trace_ex tr = {nullptr, nullptr, nullptr, nullptr, nullptr};
     if (trace) { tr.transforms = trace->transforms; tr.counts = trace->counts; tr.sums = trace->sums; tr.corr = trace->corr; }
     return icp_run(__func__, src, src_off, n_total, n_max, tgt_off, m_total, grid, init, B, max_correspondence_distance,
-                   max_iteration, relative_fitness, relative_rmse, 0, nullptr, out_transform, out_stats, tr, ws, ws_bytes, stream);
+                   max_iteration, relative_fitness, relative_rmse, 0, nullptr, nullptr, nullptr, out_transform, out_stats, tr, ws, ws_bytes,
+                   stream);
 }
 
 size_t pcrcg_icp_batch_ex_ws_bytes(int B, int n_total, int m_total, int max_iteration) {
@@ -402,9 +451,38 @@ int pcrcg_icp_batch_ex(const float* src, const int* src_off, int n_total, int n_
                        double* out_transform, double* out_stats, const pcrcg_icp_trace_ex* trace, void* ws, size_t ws_bytes,
                        void* stream) {
     const pcrcg_icp_trace_ex none = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    // this entry's estimators are 0 and 1: the generalized one's number is as bad a value here as any other, and icp_run
+    // rejects it where it always checked `estimation`
+    const int est = estimation == kEstGeneralized ? -1 : estimation;
     return icp_run(__func__, src, src_off, n_total, n_max, tgt_off, m_total, grid, init, B, max_correspondence_distance,
-                   max_iteration, relative_fitness, relative_rmse, estimation, tgt_normals, out_transform, out_stats,
+                   max_iteration, relative_fitness, relative_rmse, est, tgt_normals, nullptr, nullptr, out_transform, out_stats,
                    trace ? *trace : none, ws, ws_bytes, stream);
+}
+
+int pcrcg_covariances_from_normals(const double* normals, long n, double epsilon, double* cov, void* stream) {
+    PCRCG_CHECK_ARG(epsilon > 0.0 && epsilon <= 1.0);      // (false for a NaN)
+    PCRCG_CHECK_ARG(n >= 0 && n <= (long)kCovMaxBlocks * kCovThreads);
+    PCRCG_CHECK_ARG(n == 0 || (normals && cov));
+    if (n == 0) return PCRCG_OK;
+    hipLaunchKernelGGL(k_cov_from_normals, dim3((unsigned)((n + kCovThreads - 1) / kCovThreads)), dim3(kCovThreads), 0,
+                       as_stream(stream), normals, n, 1.0 - epsilon, cov);
+    PCRCG_CHECK_LAUNCH();
+    return PCRCG_OK;
+}
+
+size_t pcrcg_gicp_batch_ws_bytes(int B, int n_total, int m_total, int max_iteration) {
+    return pcrcg_icp_batch_ex_ws_bytes(B, n_total, m_total, max_iteration);
+}
+
+int pcrcg_gicp_batch(const float* src, const int* src_off, int n_total, int n_max, const int* tgt_off, int m_total,
+                     const void* grid, const double* init, int B, double max_correspondence_distance, int max_iteration,
+                     double relative_fitness, double relative_rmse, const double* src_cov, const double* tgt_cov,
+                     double* out_transform, double* out_stats, const pcrcg_icp_trace_ex* trace, void* ws, size_t ws_bytes,
+                     void* stream) {
+    const pcrcg_icp_trace_ex none = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    return icp_run(__func__, src, src_off, n_total, n_max, tgt_off, m_total, grid, init, B, max_correspondence_distance,
+                   max_iteration, relative_fitness, relative_rmse, kEstGeneralized, nullptr, src_cov, tgt_cov, out_transform,
+                   out_stats, trace ? *trace : none, ws, ws_bytes, stream);
 }
 
 }  // extern "C"

@@ -18,6 +18,10 @@
   * `refine_batch`           -- ICP of many pairs in one set of launches (`BatchRefinementResult`), the local pass after
                                 RANSAC's global one: point-to-point, or point-to-plane on the targets' normals;
                                 `refine` is the same for one pair.
+  * `generalized_icp_batch`  -- Generalized ICP (Segal, Haehnel, Thrun 2009; open3d's registration_generalized_icp) of many
+                                pairs in one set of launches: refine_batch's loop with a 3 x 3 metric per correspondence
+                                from both clouds' covariances; `generalized_icp` is the same for one pair, and
+                                `covariances_from_normals` builds the covariances of a cloud's normals.
   * `estimate_normals_batch` -- the normals of many clouds in one launch (open3d's hybrid-search estimate_normals),
                                 float64 device tensors; `estimate_normals` is the same for one cloud.
   * `compute_fpfh_feature_batch` -- the FPFH descriptors of many clouds in one set of launches (open3d's hybrid-search
@@ -621,7 +625,9 @@ class BatchRefinementResult:
     [B, max_iteration + 1] of Evaluate(T_k), corr: per pair [max_iteration + 1, n_b] int32, the target of every source row
     or -1 (entries past a pair's last evaluation keep their fill: NaN / -1 / -2).  Point-to-plane adds sums27
     [B, max_iteration + 1, 27] (the upper triangle of sum J J^T, then -sum J r) and normals: per pair the [M_b,3] float64
-    target normals the updates read."""
+    target normals the updates read.  `generalized_icp_batch` returns the same class: sums27 holds the upper triangle of
+    sum J0^T W J0, then -sum J0^T W d, and src_covariances / tgt_covariances (per pair [N_b,6] / [M_b,6] float64) stand where the
+    normals do."""
 
     def __init__(self, buf, host, B, trace=None):
         self.transformations = buf[:16 * B].view(B, 4, 4)
@@ -933,6 +939,169 @@ def refine(src_pcd, tgt_pcd, init, max_correspondence_distance, *, max_iteration
                                          relative_rmse=relative_rmse, trace=trace, estimation=estimation,
                                          tgt_normals=None if tgt_normals is None else [tgt_normals],
                                          normal_radius=normal_radius, normal_max_nn=normal_max_nn))
+
+
+_COV_PACK = (0, 1, 2, 4, 5, 8)   # (xx, xy, xz, yy, yz, zz) of a row-major 3 x 3 (include/pcrcg.h)
+
+
+def _check_epsilon(who, epsilon):
+    eps = float(epsilon)
+    if not 0.0 < eps <= 1.0:
+        raise ValueError(f"{who}: epsilon must lie in (0, 1], got {epsilon}")
+    return eps
+
+
+def _covariances_of(L, nrm, rows, eps):
+    """pcrcg_covariances_from_normals on normals [rows,3] float64 already on the device, on the current stream -> [rows,6]."""
+    cov = torch.empty((rows, 6), dtype=torch.float64, device=nrm.device)
+    _lib.check(L.pcrcg_covariances_from_normals(nrm.data_ptr() if rows else None, rows, eps, cov.data_ptr() if rows else None,
+                                                _stream()), "pcrcg_covariances_from_normals")
+    return cov
+
+
+def covariances_from_normals(normals, epsilon=1e-3):
+    """The Generalized-ICP covariances of [N,3] normals (numpy, CPU or HIP) -> float64 [N,6] device tensor, rows
+    (xx, xy, xz, yy, yz, zz) of C = I - (1 - epsilon) n n^T (pcrcg_covariances_from_normals; include/pcrcg.h "Generalized ICP"):
+    unit extent in the tangent plane, epsilon along the normal.  The normals' signs do not matter, bit for bit; nothing is
+    read back."""
+    eps = _check_epsilon("covariances_from_normals", epsilon)
+    shape = shape_of(normals)
+    if len(shape) != 2 or shape[1] != 3:
+        raise ValueError(f"covariances_from_normals: normals must be an [N, 3] array, got shape {shape}")
+    dev = _device(normals)
+    nrm = ragged.upload([normals], dev, torch.float64, 3, "normals")
+    return _covariances_of(_lib.lib(), nrm, shape[0], eps)
+
+
+def _gicp_side(who, side, covariances, normals, normal_radius, B, rows):
+    """One side's argument rule: exactly one of its covariances, its normals and the call's normal_radius -> which."""
+    if covariances is not None and normals is not None:
+        raise ValueError(f"{who}: give {side}_covariances or {side}_normals, not both")
+    given = covariances if covariances is not None else normals
+    if given is None:
+        if normal_radius is None:
+            raise ValueError(f"{who}: the {side} side needs {side}_covariances, {side}_normals or a normal_radius to estimate "
+                             "its normals with")
+        return "radius"
+    name = "covariances" if covariances is not None else "normals"
+    if len(given) != B:
+        raise ValueError(f"{who}: {len(given)} sets of {side} {name} for {B} pairs")
+    for b, x in enumerate(given):
+        shape = shape_of(x)
+        want = (rows[b], 3, 3) if covariances is not None else (rows[b], 3)
+        if shape != want:
+            raise ValueError(f"{who}: pair {b}: the {side} {name} must be {list(want)} (one per point), got shape {shape}")
+    return name
+
+
+def generalized_icp_batch(src_pcds, tgt_pcds, init, max_correspondence_distance, *, epsilon=1e-3, src_covariances=None,
+                          tgt_covariances=None, src_normals=None, tgt_normals=None, normal_radius=None, normal_max_nn=30,
+                          max_iteration=30, relative_fitness=1e-6, relative_rmse=1e-6, pairs_per_call=None, trace=False):
+    """Generalized ICP for B pairs at once (pcrcg_gicp_batch; include/pcrcg.h "Generalized ICP") ->
+    BatchRefinementResult.  open3d's registration_generalized_icp with TransformationEstimationForGeneralizedICP(epsilon),
+    deterministic: pair b's result depends on its clouds, covariances and start alone, bit for bit.  The evaluation and the
+    convergence test are refine_batch's; the update minimises sum d^T (C_t + R C_s R^T)^-1 d over the correspondences.
+
+    Inputs, init, the distance, the cap, the bounds, pairs_per_call: as refine_batch's.  Each side takes exactly one of
+      its covariances: a list of per-pair [N_b,3,3] symmetric arrays (open3d's layout; the upper triangle is read);
+      its normals: a list of per-pair [N_b,3] arrays -> C = I - (1 - epsilon) n n^T (covariances_from_normals);
+      normal_radius (with normal_max_nn): the side's normals are estimated in the same call on the same stream
+      (estimate_normals_batch's, viewpoint at the origin; the source's on the unmoved cloud).
+    Every size is checked on the host before anything is uploaded or launched; all chunks write into one device buffer, read
+    ONCE at the end.  trace=True: refine_batch's point-to-plane trace (sums27: the upper triangle of sum J0^T W J0, then
+    -sum J0^T W d) with src_covariances / tgt_covariances, per pair the [N_b,6] / [M_b,6] float64 rows the updates read, in
+    the place of the normals."""
+    who = "generalized_icp_batch"
+    B = len(src_pcds)
+    if len(tgt_pcds) != B:
+        raise ValueError(f"{who}: list lengths differ ({B}, {len(tgt_pcds)})")
+    if B == 0:
+        raise ValueError(f"{who}: no pairs")
+    eps = _check_epsilon(who, epsilon)
+    if isinstance(init, BatchRegistrationResult):
+        init = init.transformations
+    if init is not None and shape_of(init) != (B, 4, 4):
+        raise ValueError(f"{who}: init must be [{B}, 4, 4] (one start per pair), got shape {shape_of(init)}")
+    d = float(max_correspondence_distance)
+    if not 0.0 < d < 1e18:
+        raise ValueError(f"{who}: max_correspondence_distance must be positive")
+    mi = int(max_iteration)
+    if not 1 <= mi <= _MAX_ICP_ITERATION:
+        raise ValueError(f"{who}: max_iteration = {mi}, need 1..{_MAX_ICP_ITERATION}")
+    rf, rr = float(relative_fitness), float(relative_rmse)
+    if not (rf >= 0.0 and rr >= 0.0):
+        raise ValueError(f"{who}: relative_fitness and relative_rmse must be >= 0")
+    ns = [_cloud_rows(x, who, "the source", b) for b, x in enumerate(src_pcds)]
+    ms = [_cloud_rows(x, who, "the target", b) for b, x in enumerate(tgt_pcds)]
+    src_kind = _gicp_side(who, "src", src_covariances, src_normals, normal_radius, B, ns)
+    tgt_kind = _gicp_side(who, "tgt", tgt_covariances, tgt_normals, normal_radius, B, ms)
+    if "radius" in (src_kind, tgt_kind):
+        nr, nk = _check_normal_search(who, normal_radius, normal_max_nn)
+    elif normal_radius is not None:
+        raise ValueError(f"{who}: both sides have their covariances or normals; normal_radius belongs to a side without")
+    chunks = ragged.chunks(B, pairs_per_call, _MAX_BATCH, who, ns, ms)
+    given = [x for xs in (src_covariances, src_normals, tgt_covariances, tgt_normals) if xs is not None for x in xs]
+    dev = _device(*src_pcds, *tgt_pcds, *([init] if init is not None else []), *given)
+    L = _lib.lib()
+    wsb = max(L.pcrcg_gicp_batch_ws_bytes(b1 - b0, sum(ns[b0:b1]), sum(ms[b0:b1]), mi) for b0, b1 in chunks)
+    if wsb == 0:
+        raise ValueError(f"{who}: sizes out of range for the batch workspace")
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    out = torch.empty(B * (16 + _N_ICP_STATS), dtype=torch.float64, device=dev)
+    init_d = ragged.upload_f64(init, dev) if init is not None else None
+    tr = None
+    if trace:
+        tr = {"transforms": torch.full((B, mi + 1, 4, 4), float("nan"), dtype=torch.float64, device=dev),
+              "counts": torch.full((B, mi + 1), -1, dtype=torch.int32, device=dev),
+              "sums": torch.full((B, mi + 1), float("nan"), dtype=torch.float64, device=dev), "corr": [],
+              "sums27": torch.full((B, mi + 1, 27), float("nan"), dtype=torch.float64, device=dev),
+              "src_covariances": [], "tgt_covariances": []}
+
+    def side(kind, covariances, normals, pts, off, lengths, rows, b0, b1):
+        tot = sum(rows[b0:b1])
+        if kind == "covariances":
+            return ragged.join(ragged.tensors(covariances[b0:b1]), dev, torch.float64,
+                               lambda t: t.reshape(-1, 9)[:, list(_COV_PACK)]).reshape(tot, 6)
+        if kind == "normals":
+            nrm = ragged.upload(normals[b0:b1], dev, torch.float64, 3, "normals")
+        else:
+            nrm = _normals_of(L, pts, off, lengths, tot, b1 - b0, max(rows[b0:b1]), nr, nk, None, False)[0]
+        return _covariances_of(L, nrm, tot, eps)
+
+    for b0, b1 in chunks:
+        nb = b1 - b0
+        n_tot, m_tot = sum(ns[b0:b1]), sum(ms[b0:b1])
+        src = _cat(src_pcds[b0:b1], dev, "src_pcds", 3)
+        tgt = _cat(tgt_pcds[b0:b1], dev, "tgt_pcds", 3)
+        src_off, tgt_off, m_len, n_len = ragged.offsets(dev, ns[b0:b1], ms[b0:b1], lengths=[ms[b0:b1], ns[b0:b1]])
+        grid = ragged.cell_grid(tgt, m_tot, m_len, nb, d, _stream())
+        cs = side(src_kind, src_covariances, src_normals, src, src_off, n_len, ns, b0, b1)
+        ct = side(tgt_kind, tgt_covariances, tgt_normals, tgt, tgt_off, m_len, ms, b0, b1)
+        tr_ptr = None
+        if trace:
+            corr = torch.full((mi + 1, n_tot), -2, dtype=torch.int32, device=dev)
+            tr["corr"] += list(corr.split(ns[b0:b1], dim=1))
+            tr["src_covariances"] += list(cs.split(ns[b0:b1]))
+            tr["tgt_covariances"] += list(ct.split(ms[b0:b1]))
+            tr_ptr = ctypes.byref(_IcpTraceEx(tr["transforms"][b0:].data_ptr(), tr["counts"][b0:].data_ptr(),
+                                              tr["sums"][b0:].data_ptr(), corr.data_ptr(), tr["sums27"][b0:].data_ptr()))
+        _lib.check(L.pcrcg_gicp_batch(src.data_ptr() if n_tot else None, src_off.data_ptr(), n_tot, max(ns[b0:b1]),
+                                      tgt_off.data_ptr(), m_tot, grid.data_ptr(),
+                                      init_d[b0:].data_ptr() if init_d is not None else None, nb, d, mi, rf, rr,
+                                      cs.data_ptr() if n_tot else None, ct.data_ptr() if m_tot else None,
+                                      out[16 * b0:].data_ptr(), out[16 * B + _N_ICP_STATS * b0:].data_ptr(), tr_ptr,
+                                      ws.data_ptr(), wsb, _stream()), "pcrcg_gicp_batch")
+    return BatchRefinementResult(out, _read(out), B, tr)
+
+
+def generalized_icp(src_pcd, tgt_pcd, init, max_correspondence_distance, **kw):
+    """Generalized ICP of one pair -> RefinementResult: generalized_icp_batch with a batch of one (init: None or a [4,4] start;
+    src_covariances / tgt_covariances / src_normals / tgt_normals: None or the cloud's own array)."""
+    init = ragged.lift(init, (4, 4), "generalized_icp: init must be a [4, 4] transform")
+    for key in ("src_covariances", "tgt_covariances", "src_normals", "tgt_normals"):
+        if kw.get(key) is not None:
+            kw[key] = [kw[key]]
+    return RefinementResult(generalized_icp_batch([src_pcd], [tgt_pcd], init, max_correspondence_distance, **kw))
 
 
 def refine_ground_truth(xyz0, xyz1, M):

@@ -159,10 +159,14 @@ def register_record(record, n_points=5000, distance_threshold=0.05, ransac_n=3, 
 def _refine_poses(records, res, refine, icp_estimation="point_to_point", normal_radius=None):
     """register_batch's poses refined by ICP on the records' FULL clouds (registration.refine_batch, correspondence
     distance `refine`), started from the device transforms of `res` -> list of float64 numpy [4,4].  icp_estimation,
-    normal_radius: refine_batch's estimation and normal_radius (point-to-plane estimates the targets' normals in the call)."""
-    from .registration import refine_batch
+    normal_radius: refine_batch's estimation and normal_radius (point-to-plane estimates the targets' normals in the call);
+    icp_estimation="generalized" goes to registration.generalized_icp_batch instead, which estimates both clouds' normals with
+    normal_radius and takes its default epsilon."""
+    from .registration import generalized_icp_batch, refine_batch
     src = [r["pcd"][:r["len_src"]] for r in records]
     tgt = [r["pcd"][r["len_src"]:] for r in records]
+    if icp_estimation == "generalized":
+        return list(generalized_icp_batch(src, tgt, res, refine, normal_radius=normal_radius).matrices)
     if icp_estimation == "point_to_point" and normal_radius is None:
         return list(refine_batch(src, tgt, res, refine).matrices)
     return list(refine_batch(src, tgt, res, refine, estimation=icp_estimation, normal_radius=normal_radius).matrices)
@@ -181,7 +185,8 @@ def register_records(records, n_points=5000, distance_threshold=0.05, ransac_n=3
     refine=<distance>: every pose is then refined by point-to-point ICP on the record's full clouds with that
     correspondence distance (registration.refine_batch, its defaults); None (the default): RANSAC's pose as it is.
     icp_estimation="point_to_plane" with normal_radius=<radius> refines by point-to-plane ICP instead, on target normals
-    estimated with that radius (both are read only when `refine` is set)."""
+    estimated with that radius; icp_estimation="generalized" by Generalized ICP on both clouds' normals estimated with it
+    (all of them are read only when `refine` is set)."""
     from .registration import register_batch
     src_pcds, tgt_pcds, src_feats, tgt_feats = _sample_records(records, n_points, sampler, sample_seeds)
     res = register_batch(src_pcds, tgt_pcds, src_feats, tgt_feats, distance_threshold, ransac_n, seeds=seeds)

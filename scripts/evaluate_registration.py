@@ -14,13 +14,15 @@ and added to the summary.
 
   python scripts/evaluate_registration.py --source_path snapshot/.../test/pth --gt_folder configs/benchmarks/3DMatch \\
       --exp_dir snapshot/.../est_traj [--n_points 250 500 1000 2500 5000] [--inlier_ratio] [--sampler device] [--icp DIST]
-      [--icp-estimation point_to_plane --normal-radius R]
+      [--icp-estimation point_to_plane|generalized --normal-radius R]
 
 --sampler device draws the interest points of all records on the GPU in one launch (registration.sample_batch: the same
 distribution from its own seeded stream, record b with sample seed --seed + b) instead of on the host generator.
 --icp DIST refines every RANSAC pose by point-to-point ICP on the record's full clouds with correspondence distance DIST
 (registration.refine_batch); without it the poses are RANSAC's, as before.  --icp-estimation point_to_plane makes that
-refinement point-to-plane, on target normals estimated with --normal-radius (required then) in the same call.
+refinement point-to-plane, on target normals estimated with --normal-radius (required then) in the same call;
+--icp-estimation generalized makes it Generalized ICP (registration.generalized_icp_batch) on the normals of both clouds,
+estimated with --normal-radius (required too).
 """
 import argparse
 import json
@@ -57,15 +59,15 @@ def main():
     ap.add_argument("--fmr_threshold", type=float, default=0.05, help="inlier ratio above which a pair counts for FMR")
     ap.add_argument("--icp", type=float, default=None, metavar="DIST",
                     help="refine every pose by ICP on the full clouds with this correspondence distance (default: off)")
-    ap.add_argument("--icp-estimation", choices=("point_to_point", "point_to_plane"), default="point_to_point",
+    ap.add_argument("--icp-estimation", choices=("point_to_point", "point_to_plane", "generalized"), default="point_to_point",
                     help="the estimator of --icp (default: point_to_point)")
     ap.add_argument("--normal-radius", type=float, default=None, metavar="R",
-                    help="point_to_plane: the radius the target normals are estimated with (at most 30 neighbours)")
+                    help="point_to_plane, generalized: the radius the normals are estimated with (at most 30 neighbours)")
     a = ap.parse_args()
-    if a.icp_estimation == "point_to_plane" and (a.icp is None or a.normal_radius is None):
-        ap.error("--icp-estimation point_to_plane needs --icp DIST and --normal-radius R")
+    if a.icp_estimation != "point_to_point" and (a.icp is None or a.normal_radius is None):
+        ap.error(f"--icp-estimation {a.icp_estimation} needs --icp DIST and --normal-radius R")
     if a.icp_estimation == "point_to_point" and a.normal_radius is not None:
-        ap.error("--normal-radius belongs to --icp-estimation point_to_plane")
+        ap.error("--normal-radius belongs to --icp-estimation point_to_plane or generalized")
 
     files = sorted((f for f in os.listdir(a.source_path) if f.endswith(".pth")), key=natural_key)
     records = [torch.load(os.path.join(a.source_path, f)) for f in files]
