@@ -427,6 +427,18 @@ void pcrcg_thread_shares_gpu(int on);
 
 /* ------------------------------------------------------------------------------------------------
  * Point-wise blocks
+ *
+ * Non-finite values.  A NaN or an infinity in a FEATURE value (an activation, a weight, a pixel) goes where torch's
+ * operation sends it: every maximum (pcrcg_gather_max, the edge convolution's emax, the 2-D backbone's ReLU and max-pool)
+ * returns NaN when an operand is NaN, as torch.max / F.relu / F.max_pool2d do; pcrcg_l2norm_rows and the feature head give
+ * an all-NaN row for a row that holds a NaN, as F.normalize does (clamp_min keeps NaN); the InstanceNorm entries make a
+ * column that holds a non-finite value non-finite in every row and leave every other column alone; the copies
+ * (pcrcg_gather_first*, pcrcg_copy2d) move the bits.  Only the two score heads scrub (nan_to_num, as the reference).
+ * Kernels that contain a product (the GEMMs, KPConv, the convolutions, attention) keep the SET of finite outputs and turn a
+ * NaN into a NaN, but may turn an infinity into a NaN where torch keeps the infinity: the split-term products form
+ * inf - inf.  tests/test_nonfinite_forward_gpu.py holds the entries to this against float64 torch on the CPU.
+ * Non-finite COORDINATES (points, kernel points, kNN coordinates) are outside the contract: the front end defines no
+ * tables for them, and the KPConv influence clamp max(1 - d / extent, 0) is an fmaxf that sends a NaN distance to 0.
  * ---------------------------------------------------------------------------------------------- */
 /* max_pool (ref:models/blocks.py:86-102): out[q,c] = max_h xpad[idx[q,h],c], shadow row = 0. */
 int pcrcg_gather_max(const float* x, int ns, int c, const int64_t* idx, int nq, int h, int ld_idx,
@@ -543,7 +555,8 @@ int pcrcg_superglue_valid_maps(const float* keypoints0, int n0, const float* key
                                void* stream);
 
 /* ------------------------------------------------------------------------------------------------
- * GNN head helpers (ref:models/gcn.py)
+ * GNN head helpers (ref:models/gcn.py).  Non-finite feature values: the rule under "Point-wise blocks" (emax is a
+ * NaN-propagating maximum; kNN selection on non-finite coordinates is undefined).
  * ---------------------------------------------------------------------------------------------- */
 /* get_graph_feature's kNN (ref:models/gcn.py:15-34,48-51): dist = -2ab + a^2 + b^2 clamped at 1e-12,
  * each step rounded as the reference's CPU run rounds it; the k+1 smallest, first dropped.  Among exactly equal
@@ -1366,6 +1379,8 @@ int pcrcg_chamfer_batch(const float* src, const int* src_off, int n_total, const
  *       one (n updates, in image order; num_batches_tracked += n) -- PCR-CG's per-image calls; joint_stats = 1: one set of
  *       statistics over all n images (torch's training-mode BatchNorm2d on the batch; num_batches_tracked += 1).
  *     training = 0: the running statistics; nothing is written but out.
+ *   Non-finite pixels or weights: the rule under "Point-wise blocks" -- the ReLU and the stem's max-pool keep NaN, so a
+ *   poisoned input gives a non-finite output as in torch, never a finite one.
  *   Workspace: pcrcg_res50unet_ws_bytes(n, h, w) (0 for an unsupported shape).  Nothing is allocated or synchronised.
  *   Bad arguments (null pointers, n_tensors != 392, n outside 1..65535, h or w outside 1..8192, a training call in which a
  *   statistics segment would hold a single value) are rejected with PCRCG_EBADARG before anything launches. */

@@ -40,6 +40,10 @@ int exclusive_scan_i32(const int* in, int* out, int n, int* total, void* ws, hip
 
 constexpr int kWave = 64;
 
+// max(a, b) as torch.max, F.relu and F.max_pool2d compute it: NaN when either operand is NaN (fmaxf returns the other one).
+// The rule of include/pcrcg.h "Non-finite values"; one v_maximum3_f32 on gfx950.
+__device__ __forceinline__ float max_nan(float a, float b) { return __builtin_elementwise_maximum(a, b); }
+
 // pointops.hip: InstanceNorm + LeakyReLU that also leaves the KPConv support records of its output (kpconv.hip: pk)
 bool instnorm_pack_ok(int c, int ldx, int ldy);
 int instnorm_apply_pack(const float* x, int n, int c, int ldx, const float* stats, const double* sums, double count, float eps,

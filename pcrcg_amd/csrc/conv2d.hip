@@ -403,7 +403,7 @@ __global__ void k_bn_apply(Apply p) {
     }
     if (p.relu) {
 #pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] = fmaxf(v[j], 0.f);
+        for (int j = 0; j < 4; ++j) v[j] = max_nan(v[j], 0.f);   // F.relu keeps NaN
     }
     if (p.skip) v += *reinterpret_cast<const f32x4*>(p.skip + r * p.C + c);
     *reinterpret_cast<f32x4*>(p.y + r * p.C + c) = v;
@@ -432,7 +432,7 @@ __global__ void k_bn_relu_maxpool(const float* __restrict__ x, int H, int W, int
             if (ix < 0 || ix >= W) continue;
             const f32x4 v = sc * *reinterpret_cast<const f32x4*>(x + (((long)img * H + iy) * W + ix) * C + c) + sh;
 #pragma unroll
-            for (int j = 0; j < 4; ++j) m[j] = fmaxf(m[j], fmaxf(v[j], 0.f));
+            for (int j = 0; j < 4; ++j) m[j] = max_nan(m[j], max_nan(v[j], 0.f));
         }
     }
     *reinterpret_cast<f32x4*>(y + i * 4) = m;

@@ -38,7 +38,8 @@ __global__ void __launch_bounds__(256) k_l2norm_rows(const float* __restrict__ s
     }
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) s += __shfl_xor(s, d, 64);
-    const float inv = 1.0f / fmaxf(sqrtf(s), 1e-12f);   // F.normalize: x / max(||x||, eps)
+    const float nrm = sqrtf(s);
+    const float inv = 1.0f / (nrm != nrm ? nrm : fmaxf(nrm, 1e-12f));   // F.normalize: x / clamp_min(||x||, eps), which keeps NaN
     for (int c = lane; c < cols; c += 64) dst[(long)r * ld_dst + c] = src[(long)r * ld_src + c] * inv;
 }
 
@@ -68,7 +69,8 @@ __global__ void __launch_bounds__(256) k_heads(HeadsMulti mm, int ld, int fd) {
     }
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) s += __shfl_xor(s, d, 64);
-    const float inv = 1.0f / fmaxf(sqrtf(s), 1e-12f);
+    const float nrm = sqrtf(s);
+    const float inv = 1.0f / (nrm != nrm ? nrm : fmaxf(nrm, 1e-12f));
     float* dst = mm.feats[g] + (long)r * fd;
     for (int c = lane; c < fd; c += 64) dst[c] = src[c] * inv;
     if (lane < 2) {

@@ -660,7 +660,7 @@ __global__ void __launch_bounds__(256) k_edgeconv_rows(EdgeMulti a) {
                 if (j0 + u >= cl.k) continue;
                 const float e[4] = {q.x + v[u].x, q.y + v[u].y, q.z + v[u].z, q.w + v[u].w};
                 if (j0 + u == 0) m = make_float4(e[0], e[1], e[2], e[3]);
-                else { m.x = fmaxf(m.x, e[0]); m.y = fmaxf(m.y, e[1]); m.z = fmaxf(m.z, e[2]); m.w = fmaxf(m.w, e[3]); }
+                else { m.x = max_nan(m.x, e[0]); m.y = max_nan(m.y, e[1]); m.z = max_nan(m.z, e[2]); m.w = max_nan(m.w, e[3]); }
 #pragma unroll
                 for (int t = 0; t < 4; ++t) { s[t] += (double)e[t]; sq[t] += (double)e[t] * (double)e[t]; }
             }
@@ -707,7 +707,7 @@ __global__ void __launch_bounds__(256) k_edgeconv_reduce(const float* __restrict
             float m = 0.f;
             for (int j = 0; j < k; ++j) {
                 const float v = q + nbr[(long)idx[(long)r * k + j] * ld_nbr + ch];
-                m = j == 0 ? v : fmaxf(m, v);
+                m = j == 0 ? v : max_nan(m, v);
                 s += (double)v;
                 sq += (double)v * (double)v;
             }

@@ -56,7 +56,7 @@ __global__ void __launch_bounds__(kWavesPerBlock * 64) k_gather_max(GatherMulti 
             float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
             if (i >= 0 && i < ns) v = reinterpret_cast<const float4*>(x + i * c)[cb];
             if (!any) { m = v; any = true; }
-            else { m.x = fmaxf(m.x, v.x); m.y = fmaxf(m.y, v.y); m.z = fmaxf(m.z, v.z); m.w = fmaxf(m.w, v.w); }
+            else { m.x = max_nan(m.x, v.x); m.y = max_nan(m.y, v.y); m.z = max_nan(m.z, v.z); m.w = max_nan(m.w, v.w); }
         }
         reinterpret_cast<float4*>(out + (long)q * c)[cb] = m;
     } else {
@@ -68,7 +68,7 @@ __global__ void __launch_bounds__(kWavesPerBlock * 64) k_gather_max(GatherMulti 
         for (int j = 0; j < h; ++j) {
             const long long i = row[j];
             const float v = (i >= 0 && i < ns) ? x[i * c + cc] : 0.f;
-            m = any ? fmaxf(m, v) : v;
+            m = any ? max_nan(m, v) : v;
             any = true;
         }
         out[(long)q * c + cc] = m;

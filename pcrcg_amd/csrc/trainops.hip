@@ -479,7 +479,7 @@ __global__ void __launch_bounds__(256) k_edge_bwd_sums(const float* __restrict__
         float m = 0.f;
         for (int j = 0; j < k; ++j) {
             const float v = q + nbr[(long)idx[(long)r * k + j] * c + ch];
-            m = j == 0 ? v : fmaxf(m, v);
+            m = j == 0 ? v : max_nan(m, v);       // the forward's max, bit for bit (gnn.hip)
         }
         const float nm = (m - mean) * rstd;
         const float dn = dy[(long)r * c + ch] * (nm > 0.f ? 1.0f : slope);
