@@ -1153,6 +1153,85 @@ int pcrcg_gicp_batch(const float* src, const int* src_off, int n_total, int n_ma
                      double* out_transform, double* out_stats, const pcrcg_icp_trace_ex* trace, void* ws, size_t ws_bytes,
                      void* stream);
 
+/* Colored ICP: batched joint colour / geometry refinement (csrc/colored.hip, csrc/icp.hip, csrc/colored_terms.h; added under
+ * ABI version 4, which it does not change) -- Park, Zhou, Koltun, "Colored Point Cloud Registration Revisited" (ICCV 2017);
+ * open3d 0.10's registration_colored_icp (ColoredICP.cpp), restated as a deterministic algorithm; no bit parity with open3d is
+ * claimed.  This comment is the definition, DESIGN.md section 24 explains it, tests/colored_icp_ref.py restates it in numpy.
+ * The intensity of a point is I = ((r + g) + b) / 3.0 in float64; the entries take intensities, not colours.
+ *
+ * pcrcg_color_gradients_batch: the colour gradients of B ragged (target) clouds in ONE launch, open3d's
+ *   InitializePointCloudForColoredICP.  One wavefront per point.
+ *   Layout: pts, off, n_max and grid as pcrcg_estimate_normals_batch (the grid is built at THIS radius); open3d passes
+ *   radius = 2 max_correspondence_distance and max_nn = 30.  normals [n_total, 3] f64 and intensity [n_total] f64 DEVICE, in the
+ *   clouds' row order, required.
+ *   Outputs: rec [n_total, 8] f64, one packed 64-byte record per point: (n [3], g [3], I, 0) -- the point's normal and
+ *   intensity as they were given, and its gradient g -- which pcrcg_colored_icp_batch reads with one aligned load per
+ *   correspondence; optional (NULL: not written), for tests: count [n_total] i32 and sums [n_total, 9] f64.
+ *   Definition, per point k of a cloud with vt = (double)p_k, nt its normal, in float64, every operation rounded separately,
+ *   dot products as ((x + y) + z) (csrc/colored_terms.h):
+ *     Neighbours: exactly the list of "Normal estimation" above (fp32 unfused d2 < (float)radius * (float)radius, ascending
+ *       (d2, cloud-local index), cut to the first max_nn); nn = its length = count.
+ *     nn < 4: g = 0 and sums = 0.
+ *     Otherwise the entries e = 1 .. nn - 1 (entry 0 is dropped whichever point it is: for distinct points it is k itself, among
+ *       coincident points it is the lowest index), with a = (double)p_e: dot = ((a - vt) . nt); A_e = (a - dot nt) - vt,
+ *       b_e = I[a] - I[k]; the row adds (A0 A0, A0 A1, A0 A2, A1 A1, A1 A2, A2 A2, A0 b, A1 b, A2 b).  Lane e of the wavefront
+ *       holds entry e's nine products (zero elsewhere) and a 64-lane shuffle tree adds them: a function of the row alone.  No
+ *       floating-point atomics.
+ *     Last row (nn - 1) nt with right side 0: w = (double)(nn - 1), r = w nt, and r_r r_c is added to the six entries of A^T A.
+ *       sums = A^T A's upper triangle (00 01 02 11 12 22), then A^T b, at this point.
+ *     g = the solution of (A^T A) g = A^T b by LDL^T with diagonal pivoting (csrc/smallsolve.h solve_ldlt3: pcrcg_icp_batch_ex's
+ *       solve with 6 read as 3, the same 1e-12 pivot rule); a refused solve gives g = 0.
+ *   NaN rules: an intensity that is not finite makes b, and so g, not finite in every row whose entries 1 .. nn - 1 hold the
+ *     point, and in the point's own row; every other row keeps its bits.  A normal that is not finite makes A^T A not finite,
+ *     the solve refuses, and the row gets g = 0 beside the normal as given.
+ *   A row's bits depend on its cloud's points, normals and intensities alone.  The entry allocates nothing, synchronises
+ *   nothing and reads nothing back.  The argument rules are pcrcg_estimate_normals_batch's (max_nn in 1..64), with normals,
+ *   intensity and rec required when n_total > 0.  Workspace: pcrcg_color_gradients_ws_bytes(B, n_total) (256 bytes today: the
+ *   lists live in LDS); 0 for B outside 1..65535 or a negative n_total.
+ *
+ * pcrcg_colored_icp_batch: layout, grid, init, n_max, the outputs, the statistics, empty pairs, the `done` word and the launch
+ *   count are pcrcg_icp_batch's.
+ *   lambda_geometric in [0, 1] (open3d: 0.968): sg = sqrt(lambda_geometric), sp = sqrt(1.0 - lambda_geometric), on the host.
+ *   tgt_rec [m_total, 8] f64 DEVICE: the targets' records above, 64-byte aligned; src_intensity [n_total] f64 DEVICE; each is
+ *     required unless its side has no rows.
+ *   Evaluate(T) is pcrcg_icp_batch's -- the same moved fp32 point, nearest target, lowest-index tie rule, count, fitness and
+ *     Euclidean (point-to-point) rmse -- and convergence is tested on those values, as open3d's loop does.
+ *   Update: over the correspondences (i -> j), with p the moved source point (the float64 value of the fp32 result), q its
+ *     target, (n, g, It) the target's record and Is = src_intensity[i] (csrc/colored_terms.h):
+ *       rG = ((p - q) . n); J = [p x n | n] (a cross product is a b - c d per component); JG = sg J, rg = sg rG;
+ *       e = (p - rG n) - q; I0 = ((g . e)) + It; ri = sp (Is - I0);
+ *       gn = ((g . n)); gM = -(g - gn n); JI = sp [p x gM | gM];
+ *       the 27 terms: JG_r JG_c + JI_r JI_c over the upper triangle row by row (21), then -(JG_r rg + JI_r ri) (6).
+ *     They are added in float64 in the fixed order of the other sums (shuffle tree, the eight wavefronts in order, the
+ *     workgroups in order); A x = b is solved by pcrcg_icp_batch_ex's LDL^T (its 1e-12 pivot rule) in the one lane that runs the
+ *     other fits; delta = Rz(x2) Ry(x1) Rx(x0) | (x3, x4, x5) and T <- delta T, as point-to-plane's.
+ *     The pair stops, keeping T, if count < 3 (every correspondence carries two equations), if an entry of b is not finite
+ *     (an intensity touches b alone, which the pivots never see) or if the solve is refused: anything degenerate is for the
+ *     pivot rule to refuse.
+ *   With lambda_geometric = 1 and finite records and intensities, the terms are point-to-plane's as values (sp = 0), and a pair
+ *     whose count stays >= 6 gets pcrcg_icp_batch_ex(estimation = 1)'s outputs.
+ *   NaN rules: a record or an intensity that is not finite in a row that IS a correspondence makes the pair's sums not finite,
+ *     the solve refuses (or b fails its test) and the pair stops with T kept; a row that is nobody's correspondence is not read and changes nothing.
+ *     The other NaN rules are pcrcg_icp_batch's.
+ *   Range: J takes the moved point about the ORIGIN, as point-to-plane's does, so A's rotation block grows with |p|^2 and
+ *     cond(A) with (distance from the origin / extent of the cloud)^2; the pivot rule refuses a pair that is far enough out,
+ *     and callers re-centre such clouds ("Range" of pcrcg_icp_batch_ex).
+ *   trace: pcrcg_icp_trace_ex's members; sums27 [B, max_iteration + 1, 27] = A's upper triangle then b of Evaluate(T_k).
+ *   Workspace: pcrcg_colored_icp_batch_ws_bytes(B, n_total, m_total, max_iteration) = pcrcg_icp_batch_ex_ws_bytes' value; 0 as
+ *   pcrcg_icp_batch_ws_bytes.  Bad arguments (pcrcg_icp_batch's, lambda_geometric outside [0, 1] or NaN, a missing
+ *   src_intensity with n_total > 0 or tgt_rec with m_total > 0) give PCRCG_EBADARG under this entry's name, a short workspace
+ *   PCRCG_EWORKSPACE, before anything launches. */
+size_t pcrcg_color_gradients_ws_bytes(int B, int n_total);
+int pcrcg_color_gradients_batch(const float* pts, const int* off, int n_total, int n_max, const void* grid, int B, double radius,
+                                int max_nn, const double* normals, const double* intensity, double* rec, int* count, double* sums,
+                                void* ws, size_t ws_bytes, void* stream);
+size_t pcrcg_colored_icp_batch_ws_bytes(int B, int n_total, int m_total, int max_iteration);
+int pcrcg_colored_icp_batch(const float* src, const int* src_off, int n_total, int n_max, const int* tgt_off, int m_total,
+                            const void* grid, const double* init, int B, double max_correspondence_distance, int max_iteration,
+                            double relative_fitness, double relative_rmse, double lambda_geometric, const double* tgt_rec,
+                            const double* src_intensity, double* out_transform, double* out_stats,
+                            const pcrcg_icp_trace_ex* trace, void* ws, size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Fast global registration
  * The other half of the classical global-registration recipe that FPFH feeds: Zhou, Park, Koltun, "Fast Global

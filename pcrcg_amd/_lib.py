@@ -181,6 +181,14 @@ SIGNATURES = {
     "pcrcg_gicp_batch": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, ctypes.c_double,
                                  c_int, ctypes.c_double, ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                  c_void_p, c_size_t, c_void_p]),
+    # colored ICP (registration.color_gradients_batch, colored_icp_batch)
+    "pcrcg_color_gradients_ws_bytes": (c_size_t, [c_int, c_int]),
+    "pcrcg_color_gradients_batch": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, ctypes.c_double, c_int, c_void_p,
+                                            c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "pcrcg_colored_icp_batch_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "pcrcg_colored_icp_batch": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int,
+                                        ctypes.c_double, c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_void_p,
+                                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     # fast global registration (registration.mutual_match_batch, fast_global_registration_batch)
     "pcrcg_mutual_match_batch_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
     "pcrcg_mutual_match_batch": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int,

@@ -23,11 +23,16 @@
 // covariances of its two points, W = (C_t + R C_s R^T)^-1 and the 27 terms of J0^T W J0 and -J0^T W d come from gicp_terms.h,
 // and the update is point-to-plane's solve and delta.  k_cov_from_normals builds such covariances from normals.
 //
+// pcrcg_colored_icp_batch adds colored ICP as a fourth (EST = 3): the same evaluation; every correspondence loads its target's
+// packed record (normal, colour gradient, intensity: colored.hip) and its source's intensity, the 27 terms of the joint
+// colour / geometry objective come from colored_terms.h, and the update is point-to-plane's solve and delta again.
+//
 // All max_iteration + 1 evaluations are enqueued ahead; the host reads nothing in between.  The workgroups of a pair whose
 // `done` word is set leave at once.  No floating-point atomics: a pair's bits depend on its own points and T_0 alone.
 //
 // Compiled with -ffp-contract=off (every operation rounds where the source says).
 #include "cellgrid.h"
+#include "colored_terms.h"
 #include "common.h"
 #include "gicp_terms.h"
 #include "kabsch.h"
@@ -40,9 +45,10 @@ constexpr int kIcpThreads = 512;                  // evaluation workgroup: 512 c
 constexpr int kIcpWaves = kIcpThreads / kWave;
 constexpr int kIcpTerms = 16;                     // sum d2 | sum p [3] | sum q [3] | sum p q^T [9]
 constexpr int kIcpPlaneTerms = 28;                // sum d2 | sum J J^T, upper triangle [21] | -sum J r [6]; EST 2: J0^T W J0 | -J0^T W d
-// EST 0: point-to-point, 1: point-to-plane, 2: generalized
+// EST 0: point-to-point, 1: point-to-plane, 2: generalized, 3: colored
 template <int EST> constexpr int icp_terms() { return EST == 0 ? kIcpTerms : kIcpPlaneTerms; }
 constexpr int kEstGeneralized = 2;                // EST of pcrcg_gicp_batch; pcrcg_icp_batch_ex takes 0 or 1
+constexpr int kEstColored = 3;                    // EST of pcrcg_colored_icp_batch
 constexpr int kIcpMaxIteration = 1 << 16;
 constexpr int kIcpMaxBatch = 65535;               // pairs ride on a grid dimension
 
@@ -72,6 +78,9 @@ struct IcpArgs {
     int n_total, n_max, max_iteration;
     float thr2;
     double rel_fitness, rel_rmse;
+    const double* tgt_rec;// [m_total, 8] colored: the targets' records (n [3], g [3], I, 0) ...
+    const double* src_int;// [n_total] ... the sources' intensities ...
+    double sg, sp;        // ... and sqrt(lambda_geometric), sqrt(1 - lambda_geometric)
     const double* src_cov;// [n_total, 6] generalized: the covariances of the unmoved sources ...
     const double* tgt_cov;// [m_total, 6] ... and of the targets
 };
@@ -169,6 +178,18 @@ __global__ void __launch_bounds__(kIcpThreads) k_icp_evaluate(IcpArgs a, GridVie
 #pragma unroll
             for (int e = 0; e < 6; ++e) { Cs[e] = cs[e]; Ct[e] = ct[e]; }
             gicp_terms(P, Q, R, Cs, Ct, v + 1);
+        } else {
+#pragma unroll
+            for (int e = 1; e < kTerms; ++e) v[e] = 0.0;
+        }
+    } else if constexpr (EST == 3) {
+        // the target's record in one aligned 64-byte read; the terms of JG JG^T + JI JI^T and -(JG rg + JI ri) (colored_terms.h)
+        if (hit) {
+            double rec[8];
+            const double* tr = a.tgt_rec + 8 * (long)bj;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) rec[e] = tr[e];
+            colored_terms(P, Q, rec, a.src_int[i0 + i], a.sg, a.sp, v + 1);
         } else {
 #pragma unroll
             for (int e = 1; e < kTerms; ++e) v[e] = 0.0;
@@ -277,9 +298,14 @@ __global__ void __launch_bounds__(kWave) k_icp_update(IcpArgs a, int it) {
         return;
     }
     if constexpr (EST != 0) {
-        // Gauss-Newton step of sum r^2 (EST 2: of sum d^T W d): (sum J J^T) x = -sum J r; delta = Rz(x2) Ry(x1) Rx(x0) | (x3, x4, x5)
+        // Gauss-Newton step of sum r^2 (EST 2: of sum d^T W d; EST 3: of sum rg^2 + ri^2): (sum J J^T) x = -sum J r;
+        // delta = Rz(x2) Ry(x1) Rx(x0) | (x3, x4, x5)
         double x[6];
-        if (!solve_ldlt6(s_tot + 1, s_tot + 22, x)) {
+        // (EST 3: a source's or a target's intensity touches the right side alone, which the solve's pivots never see)
+        bool rhs_finite = true;
+        if constexpr (EST == 3)
+            for (int e = 22; e < 28; ++e) rhs_finite = rhs_finite && fabs(s_tot[e]) <= 1.79769313486231570815e308;
+        if (!rhs_finite || !solve_ldlt6(s_tot + 1, s_tot + 22, x)) {
             icp_finish(a, p, st, T, fitness, rmse, count, it);
             return;
         }
@@ -373,8 +399,8 @@ int icp_enqueue(const IcpArgs& a, const GridView& g, int B, hipStream_t st) {
 int icp_run(const char* who, const float* src, const int* src_off, int n_total, int n_max, const int* tgt_off, int m_total,
             const void* grid, const double* init, int B, double max_correspondence_distance, int max_iteration,
             double relative_fitness, double relative_rmse, int estimation, const double* tgt_normals, const double* src_cov,
-            const double* tgt_cov, double* out_transform, double* out_stats, const pcrcg_icp_trace_ex& trace, void* ws,
-            size_t ws_bytes, void* stream) {
+            const double* tgt_cov, const double* tgt_rec, const double* src_intensity, double lambda_geometric,
+            double* out_transform, double* out_stats, const pcrcg_icp_trace_ex& trace, void* ws, size_t ws_bytes, void* stream) {
     ICP_CHECK_ARG(src_off && tgt_off && grid && out_transform && out_stats && ws);
     ICP_CHECK_ARG(B >= 1 && B <= kIcpMaxBatch);
     ICP_CHECK_ARG(n_total >= 0 && m_total >= 0 && n_max >= 0 && n_max <= n_total);
@@ -382,7 +408,11 @@ int icp_run(const char* who, const float* src, const int* src_off, int n_total, 
     ICP_CHECK_ARG(max_correspondence_distance > 0.0 && max_correspondence_distance < 1e18);
     ICP_CHECK_ARG(max_iteration >= 1 && max_iteration <= kIcpMaxIteration);
     ICP_CHECK_ARG(relative_fitness >= 0.0 && relative_rmse >= 0.0);      // (false for a NaN)
-    if (estimation != kEstGeneralized) {       // (pcrcg_gicp_batch's own value: the _ex entry takes 0 or 1)
+    if (estimation == kEstColored) {           // (pcrcg_colored_icp_batch's own value)
+        ICP_CHECK_ARG(lambda_geometric >= 0.0 && lambda_geometric <= 1.0);   // (false for a NaN)
+        ICP_CHECK_ARG(n_total == 0 || src_intensity);
+        ICP_CHECK_ARG(m_total == 0 || tgt_rec);
+    } else if (estimation != kEstGeneralized) {       // (pcrcg_gicp_batch's own value: the _ex entry takes 0 or 1)
         ICP_CHECK_ARG(estimation == 0 || estimation == 1);
         ICP_CHECK_ARG(estimation == 0 || m_total == 0 || tgt_normals);
     } else {
@@ -405,10 +435,14 @@ int icp_run(const char* who, const float* src, const int* src_off, int n_total, 
     a.tgt_nrm = tgt_normals;
     a.tr_sums27 = estimation != 0 ? trace.sums27 : nullptr;
     a.src_cov = src_cov; a.tgt_cov = tgt_cov;
+    a.tgt_rec = tgt_rec; a.src_int = src_intensity;
+    a.sg = estimation == kEstColored ? sqrt(lambda_geometric) : 0.0;
+    a.sp = estimation == kEstColored ? sqrt(1.0 - lambda_geometric) : 0.0;
     a.n_total = n_total; a.n_max = n_max; a.max_iteration = max_iteration;
     a.thr2 = (float)(max_correspondence_distance * max_correspondence_distance);
     a.rel_fitness = relative_fitness; a.rel_rmse = relative_rmse;
     if (estimation == kEstGeneralized) return icp_enqueue<2>(a, g, B, as_stream(stream));
+    if (estimation == kEstColored) return icp_enqueue<3>(a, g, B, as_stream(stream));
     return estimation == 0 ? icp_enqueue<0>(a, g, B, as_stream(stream)) : icp_enqueue<1>(a, g, B, as_stream(stream));
 }
 #undef ICP_CHECK_ARG
@@ -434,8 +468,8 @@ int pcrcg_icp_batch(const float* src, const int* src_off, int n_total, int n_max
     pcrcg_icp_trace_ex tr = {nullptr, nullptr, nullptr, nullptr, nullptr};
     if (trace) { tr.transforms = trace->transforms; tr.counts = trace->counts; tr.sums = trace->sums; tr.corr = trace->corr; }
     return icp_run(__func__, src, src_off, n_total, n_max, tgt_off, m_total, grid, init, B, max_correspondence_distance,
-                   max_iteration, relative_fitness, relative_rmse, 0, nullptr, nullptr, nullptr, out_transform, out_stats, tr, ws, ws_bytes,
-                   stream);
+                   max_iteration, relative_fitness, relative_rmse, 0, nullptr, nullptr, nullptr, nullptr, nullptr, 0.0, out_transform, out_stats,
+                   tr, ws, ws_bytes, stream);
 }
 
 size_t pcrcg_icp_batch_ex_ws_bytes(int B, int n_total, int m_total, int max_iteration) {
@@ -451,12 +485,12 @@ int pcrcg_icp_batch_ex(const float* src, const int* src_off, int n_total, int n_
                        double* out_transform, double* out_stats, const pcrcg_icp_trace_ex* trace, void* ws, size_t ws_bytes,
                        void* stream) {
     const pcrcg_icp_trace_ex none = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    // this entry's estimators are 0 and 1: the generalized one's number is as bad a value here as any other, and icp_run
-    // rejects it where it always checked `estimation`
-    const int est = estimation == kEstGeneralized ? -1 : estimation;
+    // this entry's estimators are 0 and 1: the generalized and the colored one's numbers are as bad a value here as any other,
+    // and icp_run rejects them where it always checked `estimation`
+    const int est = estimation == kEstGeneralized || estimation == kEstColored ? -1 : estimation;
     return icp_run(__func__, src, src_off, n_total, n_max, tgt_off, m_total, grid, init, B, max_correspondence_distance,
-                   max_iteration, relative_fitness, relative_rmse, est, tgt_normals, nullptr, nullptr, out_transform, out_stats,
-                   trace ? *trace : none, ws, ws_bytes, stream);
+                   max_iteration, relative_fitness, relative_rmse, est, tgt_normals, nullptr, nullptr, nullptr, nullptr, 0.0,
+                   out_transform, out_stats, trace ? *trace : none, ws, ws_bytes, stream);
 }
 
 int pcrcg_covariances_from_normals(const double* normals, long n, double epsilon, double* cov, void* stream) {
@@ -481,8 +515,23 @@ int pcrcg_gicp_batch(const float* src, const int* src_off, int n_total, int n_ma
                      void* stream) {
     const pcrcg_icp_trace_ex none = {nullptr, nullptr, nullptr, nullptr, nullptr};
     return icp_run(__func__, src, src_off, n_total, n_max, tgt_off, m_total, grid, init, B, max_correspondence_distance,
-                   max_iteration, relative_fitness, relative_rmse, kEstGeneralized, nullptr, src_cov, tgt_cov, out_transform,
-                   out_stats, trace ? *trace : none, ws, ws_bytes, stream);
+                   max_iteration, relative_fitness, relative_rmse, kEstGeneralized, nullptr, src_cov, tgt_cov, nullptr, nullptr, 0.0,
+                   out_transform, out_stats, trace ? *trace : none, ws, ws_bytes, stream);
+}
+
+size_t pcrcg_colored_icp_batch_ws_bytes(int B, int n_total, int m_total, int max_iteration) {
+    return pcrcg_icp_batch_ex_ws_bytes(B, n_total, m_total, max_iteration);
+}
+
+int pcrcg_colored_icp_batch(const float* src, const int* src_off, int n_total, int n_max, const int* tgt_off, int m_total,
+                            const void* grid, const double* init, int B, double max_correspondence_distance, int max_iteration,
+                            double relative_fitness, double relative_rmse, double lambda_geometric, const double* tgt_rec,
+                            const double* src_intensity, double* out_transform, double* out_stats,
+                            const pcrcg_icp_trace_ex* trace, void* ws, size_t ws_bytes, void* stream) {
+    const pcrcg_icp_trace_ex none = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    return icp_run(__func__, src, src_off, n_total, n_max, tgt_off, m_total, grid, init, B, max_correspondence_distance,
+                   max_iteration, relative_fitness, relative_rmse, kEstColored, nullptr, nullptr, nullptr, tgt_rec, src_intensity,
+                   lambda_geometric, out_transform, out_stats, trace ? *trace : none, ws, ws_bytes, stream);
 }
 
 }  // extern "C"

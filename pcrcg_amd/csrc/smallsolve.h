@@ -1,5 +1,6 @@
-// smallsolve.h -- two float64 dense solvers that run in ONE lane: the eigenvector of a symmetric 3 x 3 matrix's smallest
-// eigenvalue (normals.hip) and the diagonally pivoted LDL^T solve of a symmetric 6 x 6 system (icp.hip, point-to-plane).
+// smallsolve.h -- three float64 dense solvers that run in ONE lane: the eigenvector of a symmetric 3 x 3 matrix's smallest
+// eigenvalue (normals.hip), the diagonally pivoted LDL^T solve of a symmetric 6 x 6 system (icp.hip, point-to-plane) and the
+// same solve of a 3 x 3 system (colored.hip).
 // Plain C++ (host and device): both files are compiled with -ffp-contract=off.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -102,6 +103,55 @@ __host__ __device__ inline bool solve_ldlt6(const double* upper, const double* b
     for (int r = 4; r >= 0; --r)
         for (int c = r + 1; c < 6; ++c) y[r] = y[r] - A[c][r] * y[c];
     for (int r = 0; r < 6; ++r) x[perm[r]] = y[r];
+    return true;
+}
+
+// rows / columns i and j of the symmetric 3 x 3 system exchanged (i, j constants where solve_ldlt3 calls this)
+__host__ __device__ inline void ldlt3_swap(double (&A)[3][3], double (&y)[3], int (&perm)[3], int i, int j) {
+    for (int c = 0; c < 3; ++c) { const double t = A[i][c]; A[i][c] = A[j][c]; A[j][c] = t; }
+    for (int r = 0; r < 3; ++r) { const double t = A[r][i]; A[r][i] = A[r][j]; A[r][j] = t; }
+    { const double t = y[i]; y[i] = y[j]; y[j] = t; }
+    { const int t = perm[i]; perm[i] = perm[j]; perm[j] = t; }
+}
+
+// The same solve for a symmetric 3 x 3 A (upper triangle 00 01 02 11 12 22): the colour gradient's normal equations
+// (colored.hip).  solve_ldlt6's pivoting, 1e-12 rule and order of operations with 6 read as 3; every array index is a
+// constant once the loops are unrolled (the pivot's exchange is chosen by comparisons), so the kernel keeps it in registers.
+__host__ __device__ inline bool solve_ldlt3(const double* upper, const double* b, double* x) {
+    double A[3][3], y[3];
+    int perm[3] = {0, 1, 2};
+    for (int r = 0, e = 0; r < 3; ++r)
+        for (int c = r; c < 3; ++c, ++e) { A[r][c] = upper[e]; A[c][r] = upper[e]; }
+    for (int r = 0; r < 3; ++r) y[r] = b[r];
+    double dmax = 0.0;
+    // step 0: the largest of the three diagonal entries, the lowest index among equal ones
+    if (A[1][1] > A[0][0]) {
+        if (A[2][2] > A[1][1]) ldlt3_swap(A, y, perm, 0, 2); else ldlt3_swap(A, y, perm, 0, 1);
+    } else if (A[2][2] > A[0][0]) {
+        ldlt3_swap(A, y, perm, 0, 2);
+    }
+    for (int k = 0; k < 3; ++k) {
+        if (k == 1 && A[2][2] > A[1][1]) ldlt3_swap(A, y, perm, 1, 2);
+        const double d = A[k][k];
+        if (d > dmax) dmax = d;
+        if (!(d > 1e-12 * dmax) || !(d > 0.0)) return false;
+        for (int r = k + 1; r < 3; ++r) A[r][k] = A[r][k] / d;
+        for (int r = k + 1; r < 3; ++r)
+            for (int c = k + 1; c <= r; ++c) {
+                const double v = A[r][c] - A[r][k] * (d * A[c][k]);
+                A[r][c] = v;
+                A[c][r] = v;
+            }
+    }
+    // L z = y, D w = z, L^T u = w; x[perm] = u
+    for (int r = 1; r < 3; ++r)
+        for (int c = 0; c < r; ++c) y[r] = y[r] - A[r][c] * y[c];
+    for (int r = 0; r < 3; ++r) y[r] = y[r] / A[r][r];
+    for (int r = 1; r >= 0; --r)
+        for (int c = r + 1; c < 3; ++c) y[r] = y[r] - A[c][r] * y[c];
+    for (int r = 0; r < 3; ++r)
+        for (int j = 0; j < 3; ++j)
+            if (perm[r] == j) x[j] = y[r];
     return true;
 }
 

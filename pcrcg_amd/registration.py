@@ -22,6 +22,11 @@
                                 pairs in one set of launches: refine_batch's loop with a 3 x 3 metric per correspondence
                                 from both clouds' covariances; `generalized_icp` is the same for one pair, and
                                 `covariances_from_normals` builds the covariances of a cloud's normals.
+  * `colored_icp_batch`      -- colored ICP (Park, Zhou, Koltun 2017; open3d's registration_colored_icp) of many pairs in
+                                one set of launches: refine_batch's loop on a joint colour / geometry objective, for the
+                                planar scenes where geometry alone leaves the in-plane motion free; `colored_icp` is the
+                                same for one pair, and `color_gradients_batch` / `color_gradients` give the targets' colour
+                                gradients it reads.
   * `estimate_normals_batch` -- the normals of many clouds in one launch (open3d's hybrid-search estimate_normals),
                                 float64 device tensors; `estimate_normals` is the same for one cloud.
   * `compute_fpfh_feature_batch` -- the FPFH descriptors of many clouds in one set of launches (open3d's hybrid-search
@@ -1102,6 +1107,236 @@ def generalized_icp(src_pcd, tgt_pcd, init, max_correspondence_distance, **kw):
         if kw.get(key) is not None:
             kw[key] = [kw[key]]
     return RefinementResult(generalized_icp_batch([src_pcd], [tgt_pcd], init, max_correspondence_distance, **kw))
+
+
+_RECORD = 8        # include/pcrcg.h "Colored ICP": (n [3], g [3], I, 0), one 64-byte record per target point
+
+
+def _color_rows(x, who, name, b):
+    shape = shape_of(x)
+    if len(shape) == 1 or (len(shape) == 2 and shape[1] == 3):
+        return shape[0]
+    raise ValueError(f"{who}: pair {b}: {name} must be [N, 3] RGB or [N] intensities, got shape {shape}")
+
+
+def _check_colors(who, side, colors, B, rows):
+    if len(colors) != B:
+        raise ValueError(f"{who}: {len(colors)} sets of {side} colours for {B} clouds")
+    for b, x in enumerate(colors):
+        if _color_rows(x, who, f"the {side} colours", b) != rows[b]:
+            raise ValueError(f"{who}: pair {b}: the {side} colours must have one row per point")
+
+
+def _check_gradient_search(who, radius, max_nn):
+    r, k = float(radius), int(max_nn)
+    if not 0.0 < r < 1e18:
+        raise ValueError(f"{who}: the gradient radius must be positive and finite, got {radius}")
+    if not 1 <= k <= _MAX_NORMAL_NN:
+        raise ValueError(f"{who}: gradient max_nn = {k}, need 1..{_MAX_NORMAL_NN}")
+    return r, k
+
+
+def _intensity(t):
+    """[N,3] RGB -> I = ((r + g) + b) / 3.0 in float64; [N] intensities as they are.  The divisor is a tensor: a device tensor
+    over a Python number is multiplied by the number's reciprocal, which rounds differently from the division of the
+    definition, and an intensity must not depend on where its colours happened to live."""
+    t = t.to(torch.float64)
+    if t.dim() != 2:
+        return t
+    s = (t[:, 0] + t[:, 1]) + t[:, 2]
+    return s / torch.full_like(s, 3.0)
+
+
+def _intensities(colors, dev):
+    return ragged.join(ragged.tensors(colors), dev, torch.float64, _intensity)
+
+
+def _gradients_of(L, pts, off, lengths, n_tot, nb, n_max, radius, max_nn, nrm, inten, trace):
+    """pcrcg_color_gradients_batch over nb concatenated clouds already on the device, on the current stream ->
+    (records [n_tot,8] float64, counts or None, sums or None).  Nothing is read back."""
+    dev = pts.device
+    grid = ragged.cell_grid(pts, n_tot, lengths, nb, radius, _stream())
+    wsb = L.pcrcg_color_gradients_ws_bytes(nb, n_tot)
+    ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device=dev)
+    rec = torch.empty((n_tot, _RECORD), dtype=torch.float64, device=dev)
+    cnt = torch.empty(n_tot, dtype=torch.int32, device=dev) if trace else None
+    sums = torch.empty((n_tot, 9), dtype=torch.float64, device=dev) if trace else None
+    some = n_tot > 0
+    _lib.check(L.pcrcg_color_gradients_batch(pts.data_ptr() if some else None, off.data_ptr(), n_tot, n_max, grid.data_ptr(), nb,
+                                             radius, max_nn, nrm.data_ptr() if some else None, inten.data_ptr() if some else None,
+                                             rec.data_ptr() if some else None, cnt.data_ptr() if trace else None,
+                                             sums.data_ptr() if trace else None, ws.data_ptr(), wsb, _stream()),
+               "pcrcg_color_gradients_batch")
+    return rec, cnt, sums
+
+
+def color_gradients_batch(pcds, colors, normals, radius, max_nn=30, *, pairs_per_call=None, trace=False):
+    """The colour gradients of B clouds in one launch (pcrcg_color_gradients_batch; include/pcrcg.h "Colored ICP", DESIGN.md
+    section 24) -> a list of float64 [N_b,3] device tensors, each a view (columns 3..5) of the cloud's packed [N_b,8] records
+    (normal, gradient, intensity, 0) that colored ICP reads; with trace=True -> (gradients, counts, sums), the last two lists of
+    int32 [N_b] and float64 [N_b,9] device tensors (the neighbour lists' lengths; A^T A's upper triangle and A^T b of the fit).
+    open3d's InitializePointCloudForColoredICP, deterministic: cloud b's result depends on its points, normals and colours
+    alone, bit for bit.
+
+    Inputs: lists of [N_b,3] points, of [N_b,3] RGB colours or [N_b] intensities (I = ((r + g) + b) / 3 in float64) and of
+    [N_b,3] normals (numpy, CPU or HIP tensors; empty clouds are allowed).  open3d searches with radius = 2 x the ICP's
+    max_correspondence_distance and max_nn = 30.  pairs_per_call bounds the clouds per launch (default: all).  Every size is
+    checked on the host before anything is uploaded or launched; nothing is read back."""
+    who = "color_gradients_batch"
+    B = len(pcds)
+    if B == 0:
+        raise ValueError(f"{who}: no clouds")
+    r, k = _check_gradient_search(who, radius, max_nn)
+    ns = [_cloud_rows(x, who, "the cloud", b) for b, x in enumerate(pcds)]
+    _check_colors(who, "cloud's", colors, B, ns)
+    if len(normals) != B:
+        raise ValueError(f"{who}: {len(normals)} sets of normals for {B} clouds")
+    for b, x in enumerate(normals):
+        if _cloud_rows(x, who, "the normals", b) != ns[b]:
+            raise ValueError(f"{who}: pair {b}: the normals must have one row per point")
+    chunks = ragged.chunks(B, pairs_per_call, _MAX_BATCH, who, ns)
+    dev = _device(*pcds, *colors, *normals)
+    L = _lib.lib()
+    grads, counts, sums = [], [], []
+    for b0, b1 in chunks:
+        nb, n_tot = b1 - b0, sum(ns[b0:b1])
+        pts = _cat(pcds[b0:b1], dev, "pcds", 3)
+        off, lengths = ragged.offsets(dev, ns[b0:b1], lengths=[ns[b0:b1]])
+        nrm = ragged.upload(normals[b0:b1], dev, torch.float64, 3, "normals")
+        rec, cnt, sm = _gradients_of(L, pts, off, lengths, n_tot, nb, max(ns[b0:b1]), r, k, nrm,
+                                     _intensities(colors[b0:b1], dev), trace)
+        grads += [x[:, 3:6] for x in rec.split(ns[b0:b1])]
+        if trace:
+            counts += list(cnt.split(ns[b0:b1]))
+            sums += list(sm.split(ns[b0:b1]))
+    return (grads, counts, sums) if trace else grads
+
+
+def color_gradients(pcd, colors, normals, radius, max_nn=30, *, trace=False):
+    """The colour gradients of one cloud: color_gradients_batch with a batch of one -> float64 [N,3] device tensor; with
+    trace=True -> (gradients, counts, sums)."""
+    out = color_gradients_batch([pcd], [colors], [normals], radius, max_nn, trace=trace)
+    return tuple(x[0] for x in out) if trace else out[0]
+
+
+def colored_icp_batch(src_pcds, tgt_pcds, src_colors, tgt_colors, init, max_correspondence_distance, *, lambda_geometric=0.968,
+                      tgt_normals=None, normal_radius=None, normal_max_nn=30, gradient_radius=None, gradient_max_nn=30,
+                      max_iteration=30, relative_fitness=1e-6, relative_rmse=1e-6, pairs_per_call=None, trace=False):
+    """Colored ICP for B pairs at once (pcrcg_color_gradients_batch + pcrcg_colored_icp_batch; include/pcrcg.h "Colored ICP",
+    DESIGN.md section 24) -> BatchRefinementResult.  open3d 0.10's registration_colored_icp (Park, Zhou, Koltun 2017) with
+    lambda_geometric, deterministic: pair b's result depends on its clouds, colours, normals and start alone, bit for bit.  The
+    evaluation and the convergence test are refine_batch's; the update minimises, over the correspondences,
+    lambda_geometric x (the squared distance to the target's tangent plane) + (1 - lambda_geometric) x (the squared difference
+    between the source's intensity and the target's intensity carried along its colour gradient in the tangent plane): colour
+    fixes the in-plane motion that geometry leaves free on walls, floors and table tops.
+
+    Inputs, init, the distance, the cap, the bounds, pairs_per_call: as refine_batch's.  src_colors / tgt_colors: lists of
+    per-pair [N_b,3] / [M_b,3] RGB arrays or [N_b] / [M_b] intensities (I = ((r + g) + b) / 3 in float64).  The target side takes
+    exactly one of tgt_normals (a list of per-pair [M_b,3] arrays) or normal_radius (with normal_max_nn: the normals are
+    estimated in the same call, estimate_normals_batch's, viewpoint at the origin).  gradient_radius (None: 2 x
+    max_correspondence_distance, as open3d) and gradient_max_nn are the search of the targets' colour gradients.  One call
+    runs, on one stream: the normals when they are not given, the cell grids at the gradient radius and at the correspondence
+    distance, the gradient kernel and the ICP loop.  Every size and shape is checked on the host before anything is uploaded
+    or launched; all chunks write into one device buffer, read ONCE at the end.  trace=True: refine_batch's point-to-plane
+    trace (sums27: the upper triangle of sum JG JG^T + JI JI^T, then -sum (JG rg + JI ri)) plus tgt_records (per pair the
+    [M_b,8] float64 records the updates read) and src_intensities (per pair [N_b] float64)."""
+    who = "colored_icp_batch"
+    B = len(src_pcds)
+    if len(tgt_pcds) != B:
+        raise ValueError(f"{who}: list lengths differ ({B}, {len(tgt_pcds)})")
+    if B == 0:
+        raise ValueError(f"{who}: no pairs")
+    lam = float(lambda_geometric)
+    if not 0.0 <= lam <= 1.0:
+        raise ValueError(f"{who}: lambda_geometric must lie in [0, 1], got {lambda_geometric}")
+    if tgt_normals is None:
+        if normal_radius is None:
+            raise ValueError(f"{who}: needs tgt_normals or a normal_radius to estimate them with")
+        nr, nk = _check_normal_search(who, normal_radius, normal_max_nn)
+    else:
+        if normal_radius is not None:
+            raise ValueError(f"{who}: give tgt_normals or normal_radius, not both")
+        if len(tgt_normals) != B:
+            raise ValueError(f"{who}: {len(tgt_normals)} sets of target normals for {B} pairs")
+    if isinstance(init, BatchRegistrationResult):
+        init = init.transformations
+    if init is not None and shape_of(init) != (B, 4, 4):
+        raise ValueError(f"{who}: init must be [{B}, 4, 4] (one start per pair), got shape {shape_of(init)}")
+    d = float(max_correspondence_distance)
+    if not 0.0 < d < 1e18:
+        raise ValueError(f"{who}: max_correspondence_distance must be positive")
+    gr, gk = _check_gradient_search(who, 2.0 * d if gradient_radius is None else gradient_radius, gradient_max_nn)
+    mi = int(max_iteration)
+    if not 1 <= mi <= _MAX_ICP_ITERATION:
+        raise ValueError(f"{who}: max_iteration = {mi}, need 1..{_MAX_ICP_ITERATION}")
+    rf, rr = float(relative_fitness), float(relative_rmse)
+    if not (rf >= 0.0 and rr >= 0.0):
+        raise ValueError(f"{who}: relative_fitness and relative_rmse must be >= 0")
+    ns = [_cloud_rows(x, who, "the source", b) for b, x in enumerate(src_pcds)]
+    ms = [_cloud_rows(x, who, "the target", b) for b, x in enumerate(tgt_pcds)]
+    _check_colors(who, "source", src_colors, B, ns)
+    _check_colors(who, "target", tgt_colors, B, ms)
+    if tgt_normals is not None:
+        for b, x in enumerate(tgt_normals):
+            if _cloud_rows(x, who, "the target normals", b) != ms[b]:
+                raise ValueError(f"{who}: pair {b}: the target normals must have one row per target point")
+    chunks = ragged.chunks(B, pairs_per_call, _MAX_BATCH, who, ns, ms)
+    dev = _device(*src_pcds, *tgt_pcds, *([init] if init is not None else []), *src_colors, *tgt_colors,
+                  *(tgt_normals if tgt_normals is not None else []))
+    L = _lib.lib()
+    wsb = max(L.pcrcg_colored_icp_batch_ws_bytes(b1 - b0, sum(ns[b0:b1]), sum(ms[b0:b1]), mi) for b0, b1 in chunks)
+    if wsb == 0:
+        raise ValueError(f"{who}: sizes out of range for the batch workspace")
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    out = torch.empty(B * (16 + _N_ICP_STATS), dtype=torch.float64, device=dev)
+    init_d = ragged.upload_f64(init, dev) if init is not None else None
+    tr = None
+    if trace:
+        tr = {"transforms": torch.full((B, mi + 1, 4, 4), float("nan"), dtype=torch.float64, device=dev),
+              "counts": torch.full((B, mi + 1), -1, dtype=torch.int32, device=dev),
+              "sums": torch.full((B, mi + 1), float("nan"), dtype=torch.float64, device=dev), "corr": [],
+              "sums27": torch.full((B, mi + 1, 27), float("nan"), dtype=torch.float64, device=dev),
+              "normals": [], "tgt_records": [], "src_intensities": []}
+    for b0, b1 in chunks:
+        nb = b1 - b0
+        n_tot, m_tot = sum(ns[b0:b1]), sum(ms[b0:b1])
+        src = _cat(src_pcds[b0:b1], dev, "src_pcds", 3)
+        tgt = _cat(tgt_pcds[b0:b1], dev, "tgt_pcds", 3)
+        src_off, tgt_off, lengths = ragged.offsets(dev, ns[b0:b1], ms[b0:b1], lengths=[ms[b0:b1]])
+        if tgt_normals is None:
+            nrm = _normals_of(L, tgt, tgt_off, lengths, m_tot, nb, max(ms[b0:b1]), nr, nk, None, False)[0]
+        else:
+            nrm = ragged.upload(tgt_normals[b0:b1], dev, torch.float64, 3, "tgt_normals")
+        src_int = _intensities(src_colors[b0:b1], dev)
+        rec = _gradients_of(L, tgt, tgt_off, lengths, m_tot, nb, max(ms[b0:b1]), gr, gk, nrm,
+                            _intensities(tgt_colors[b0:b1], dev), False)[0]
+        grid = ragged.cell_grid(tgt, m_tot, lengths, nb, d, _stream())
+        tr_ptr = None
+        if trace:
+            corr = torch.full((mi + 1, n_tot), -2, dtype=torch.int32, device=dev)
+            tr["corr"] += list(corr.split(ns[b0:b1], dim=1))
+            tr["normals"] += list(nrm.split(ms[b0:b1]))
+            tr["tgt_records"] += list(rec.split(ms[b0:b1]))
+            tr["src_intensities"] += list(src_int.split(ns[b0:b1]))
+            tr_ptr = ctypes.byref(_IcpTraceEx(tr["transforms"][b0:].data_ptr(), tr["counts"][b0:].data_ptr(),
+                                              tr["sums"][b0:].data_ptr(), corr.data_ptr(), tr["sums27"][b0:].data_ptr()))
+        _lib.check(L.pcrcg_colored_icp_batch(src.data_ptr() if n_tot else None, src_off.data_ptr(), n_tot, max(ns[b0:b1]),
+                                             tgt_off.data_ptr(), m_tot, grid.data_ptr(),
+                                             init_d[b0:].data_ptr() if init_d is not None else None, nb, d, mi, rf, rr, lam,
+                                             rec.data_ptr() if m_tot else None, src_int.data_ptr() if n_tot else None,
+                                             out[16 * b0:].data_ptr(), out[16 * B + _N_ICP_STATS * b0:].data_ptr(), tr_ptr,
+                                             ws.data_ptr(), wsb, _stream()), "pcrcg_colored_icp_batch")
+    return BatchRefinementResult(out, _read(out), B, tr)
+
+
+def colored_icp(src_pcd, tgt_pcd, src_colors, tgt_colors, init, max_correspondence_distance, **kw):
+    """Colored ICP of one pair -> RefinementResult: colored_icp_batch with a batch of one (init: None or a [4,4] start;
+    tgt_normals: None or the target's [M,3] normals)."""
+    init = ragged.lift(init, (4, 4), "colored_icp: init must be a [4, 4] transform")
+    if kw.get("tgt_normals") is not None:
+        kw["tgt_normals"] = [kw["tgt_normals"]]
+    return RefinementResult(colored_icp_batch([src_pcd], [tgt_pcd], [src_colors], [tgt_colors], init,
+                                              max_correspondence_distance, **kw))
 
 
 def refine_ground_truth(xyz0, xyz1, M):
