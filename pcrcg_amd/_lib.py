@@ -22,6 +22,12 @@ ABI_VERSION = 4      # PCRCG_ABI_VERSION of the include/pcrcg.h these signatures
 
 c_int, c_float, c_void_p, c_size_t = ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t
 
+# What the four ICP entries share: clouds, offsets, totals, grid, start, B, distance, cap, bounds | an estimator's own
+# arguments stand here | outputs, trace, workspace, stream
+_ICP_HEAD = [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, ctypes.c_double, c_int,
+             ctypes.c_double, ctypes.c_double]
+_ICP_TAIL = [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
+
 # name -> (restype, argtypes); mirrors include/pcrcg.h and include/pcrcg_train.h one to one
 SIGNATURES = {
     "pcrcg_last_error": (ctypes.c_char_p, []),
@@ -160,9 +166,7 @@ SIGNATURES = {
                                          c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     # ICP refinement (registration.refine_batch)
     "pcrcg_icp_batch_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
-    "pcrcg_icp_batch": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, ctypes.c_double,
-                                c_int, ctypes.c_double, ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
-                                c_void_p]),
+    "pcrcg_icp_batch": (c_int, _ICP_HEAD + _ICP_TAIL),
     # normals and the estimator choice of the ICP refinement (registration.estimate_normals_batch, refine_batch)
     "pcrcg_estimate_normals_ws_bytes": (c_size_t, [c_int, c_int]),
     "pcrcg_estimate_normals_batch": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, ctypes.c_double, c_int, c_void_p,
@@ -172,23 +176,17 @@ SIGNATURES = {
     "pcrcg_fpfh_batch": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, ctypes.c_double, c_int, c_void_p, c_void_p,
                                  c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "pcrcg_icp_batch_ex_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
-    "pcrcg_icp_batch_ex": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, ctypes.c_double,
-                                   c_int, ctypes.c_double, ctypes.c_double, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
-                                   c_void_p, c_size_t, c_void_p]),
+    "pcrcg_icp_batch_ex": (c_int, _ICP_HEAD + [c_int, c_void_p] + _ICP_TAIL),
     # Generalized ICP (registration.covariances_from_normals, generalized_icp_batch)
     "pcrcg_covariances_from_normals": (c_int, [c_void_p, ctypes.c_long, ctypes.c_double, c_void_p, c_void_p]),
     "pcrcg_gicp_batch_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
-    "pcrcg_gicp_batch": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, ctypes.c_double,
-                                 c_int, ctypes.c_double, ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                 c_void_p, c_size_t, c_void_p]),
+    "pcrcg_gicp_batch": (c_int, _ICP_HEAD + [c_void_p, c_void_p] + _ICP_TAIL),
     # colored ICP (registration.color_gradients_batch, colored_icp_batch)
     "pcrcg_color_gradients_ws_bytes": (c_size_t, [c_int, c_int]),
     "pcrcg_color_gradients_batch": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, ctypes.c_double, c_int, c_void_p,
                                             c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "pcrcg_colored_icp_batch_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
-    "pcrcg_colored_icp_batch": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int,
-                                        ctypes.c_double, c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_void_p,
-                                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "pcrcg_colored_icp_batch": (c_int, _ICP_HEAD + [ctypes.c_double, c_void_p, c_void_p] + _ICP_TAIL),
     # fast global registration (registration.mutual_match_batch, fast_global_registration_batch)
     "pcrcg_mutual_match_batch_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
     "pcrcg_mutual_match_batch": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int,

@@ -27,6 +27,12 @@
 // packed record (normal, colour gradient, intensity: colored.hip) and its source's intensity, the 27 terms of the joint
 // colour / geometry objective come from colored_terms.h, and the update is point-to-plane's solve and delta again.
 //
+// Host side: every extern "C" entry fills one IcpCall -- the arguments all entries share, its estimator, and that
+// estimator's own inputs by name -- and hands it to icp_run, the one place for the argument rules, the workspace carve, the
+// fill of the kernels' IcpArgs and the dispatch to icp_enqueue<EST>.  A further estimator is one more entry that fills an
+// IcpCall, its fields there and in IcpArgs (appended: the member order is the kernels' argument layout), one case in each of
+// icp_run's two switches, and one `if constexpr` branch in each kernel.
+//
 // All max_iteration + 1 evaluations are enqueued ahead; the host reads nothing in between.  The workgroups of a pair whose
 // `done` word is set leave at once.  No floating-point atomics: a pair's bits depend on its own points and T_0 alone.
 //
@@ -47,7 +53,8 @@ constexpr int kIcpTerms = 16;                     // sum d2 | sum p [3] | sum q 
 constexpr int kIcpPlaneTerms = 28;                // sum d2 | sum J J^T, upper triangle [21] | -sum J r [6]; EST 2: J0^T W J0 | -J0^T W d
 // EST 0: point-to-point, 1: point-to-plane, 2: generalized, 3: colored
 template <int EST> constexpr int icp_terms() { return EST == 0 ? kIcpTerms : kIcpPlaneTerms; }
-constexpr int kEstGeneralized = 2;                // EST of pcrcg_gicp_batch; pcrcg_icp_batch_ex takes 0 or 1
+constexpr int kEstPoint = 0, kEstPlane = 1;       // EST of pcrcg_icp_batch; pcrcg_icp_batch_ex takes either
+constexpr int kEstGeneralized = 2;                // EST of pcrcg_gicp_batch
 constexpr int kEstColored = 3;                    // EST of pcrcg_colored_icp_batch
 constexpr int kIcpMaxIteration = 1 << 16;
 constexpr int kIcpMaxBatch = 65535;               // pairs ride on a grid dimension
@@ -365,7 +372,7 @@ struct IcpWs {
 
 size_t icp_slots(int B, int n_total) { return (size_t)n_total / kIcpThreads + (size_t)B + 1; }
 
-IcpWs carve_icp(Carver& cv, int B, int n_total, int terms = kIcpTerms) {
+IcpWs carve_icp(Carver& cv, int B, int n_total, int terms) {
     IcpWs w;
     w.state = cv.take<IcpPair>((size_t)B);
     w.p_cnt = cv.take<int>(icp_slots(B, n_total));
@@ -373,7 +380,7 @@ IcpWs carve_icp(Carver& cv, int B, int n_total, int terms = kIcpTerms) {
     return w;
 }
 
-// the launches of either estimator: init, then max_iteration + 1 evaluate / update pairs
+// the launches of any estimator: init, then max_iteration + 1 evaluate / update pairs
 template <int EST>
 int icp_enqueue(const IcpArgs& a, const GridView& g, int B, hipStream_t st) {
     hipLaunchKernelGGL(k_icp_init, dim3((B + 255) / 256), dim3(256), 0, st, a, B);
@@ -387,7 +394,40 @@ int icp_enqueue(const IcpArgs& a, const GridView& g, int B, hipStream_t st) {
     return PCRCG_OK;
 }
 
-// Both entries: the argument rules (reported under the entry's own name `who`), the workspace, the launches
+// One call of any entry.  First what every entry takes, in the order of the ABI's argument lists (an entry initialises
+// these from its own arguments, in that order); then its estimator and that estimator's own inputs, set by name.
+struct IcpCall {
+    const float* src;
+    const int* src_off;
+    int n_total, n_max;
+    const int* tgt_off;
+    int m_total;
+    const void* grid;
+    const double* init;
+    int B;
+    double max_correspondence_distance;
+    int max_iteration;
+    double relative_fitness, relative_rmse;
+    double *out_transform, *out_stats;
+    const pcrcg_icp_trace_ex* trace;                                // or null
+    void* ws;
+    size_t ws_bytes;
+    void* stream;
+    int estimation = kEstPoint;                                     // EST of the kernels
+    const double* tgt_normals = nullptr;                            // point-to-plane
+    const double *src_cov = nullptr, *tgt_cov = nullptr;            // generalized
+    const double *tgt_rec = nullptr, *src_intensity = nullptr;      // colored
+    double lambda_geometric = 0.0;
+};
+
+// Every entry's *_ws_bytes: 0 for sizes out of range
+size_t icp_ws_bytes(int B, int n_total, int m_total, int max_iteration, int terms) {
+    if (B < 1 || B > kIcpMaxBatch || n_total < 0 || m_total < 0 || max_iteration < 1 || max_iteration > kIcpMaxIteration) return 0;
+    Carver cv(nullptr, 0);
+    carve_icp(cv, B, n_total, terms);
+    return cv.off;
+}
+
 #define ICP_CHECK_ARG(cond)                                          \
     do {                                                             \
         if (!(cond)) {                                               \
@@ -396,56 +436,58 @@ int icp_enqueue(const IcpArgs& a, const GridView& g, int B, hipStream_t st) {
         }                                                            \
     } while (0)
 
-int icp_run(const char* who, const float* src, const int* src_off, int n_total, int n_max, const int* tgt_off, int m_total,
-            const void* grid, const double* init, int B, double max_correspondence_distance, int max_iteration,
-            double relative_fitness, double relative_rmse, int estimation, const double* tgt_normals, const double* src_cov,
-            const double* tgt_cov, const double* tgt_rec, const double* src_intensity, double lambda_geometric,
-            double* out_transform, double* out_stats, const pcrcg_icp_trace_ex& trace, void* ws, size_t ws_bytes, void* stream) {
-    ICP_CHECK_ARG(src_off && tgt_off && grid && out_transform && out_stats && ws);
-    ICP_CHECK_ARG(B >= 1 && B <= kIcpMaxBatch);
-    ICP_CHECK_ARG(n_total >= 0 && m_total >= 0 && n_max >= 0 && n_max <= n_total);
-    ICP_CHECK_ARG(n_total == 0 || src);
-    ICP_CHECK_ARG(max_correspondence_distance > 0.0 && max_correspondence_distance < 1e18);
-    ICP_CHECK_ARG(max_iteration >= 1 && max_iteration <= kIcpMaxIteration);
-    ICP_CHECK_ARG(relative_fitness >= 0.0 && relative_rmse >= 0.0);      // (false for a NaN)
-    if (estimation == kEstColored) {           // (pcrcg_colored_icp_batch's own value)
-        ICP_CHECK_ARG(lambda_geometric >= 0.0 && lambda_geometric <= 1.0);   // (false for a NaN)
-        ICP_CHECK_ARG(n_total == 0 || src_intensity);
-        ICP_CHECK_ARG(m_total == 0 || tgt_rec);
-    } else if (estimation != kEstGeneralized) {       // (pcrcg_gicp_batch's own value: the _ex entry takes 0 or 1)
-        ICP_CHECK_ARG(estimation == 0 || estimation == 1);
-        ICP_CHECK_ARG(estimation == 0 || m_total == 0 || tgt_normals);
-    } else {
-        ICP_CHECK_ARG(n_total == 0 || src_cov);
-        ICP_CHECK_ARG(m_total == 0 || tgt_cov);
+// Every entry: the argument rules (reported under the entry's own name `who`), the workspace, the kernels' arguments, the launches
+int icp_run(const char* who, const IcpCall& c) {
+    ICP_CHECK_ARG(c.src_off && c.tgt_off && c.grid && c.out_transform && c.out_stats && c.ws);
+    ICP_CHECK_ARG(c.B >= 1 && c.B <= kIcpMaxBatch);
+    ICP_CHECK_ARG(c.n_total >= 0 && c.m_total >= 0 && c.n_max >= 0 && c.n_max <= c.n_total);
+    ICP_CHECK_ARG(c.n_total == 0 || c.src);
+    ICP_CHECK_ARG(c.max_correspondence_distance > 0.0 && c.max_correspondence_distance < 1e18);
+    ICP_CHECK_ARG(c.max_iteration >= 1 && c.max_iteration <= kIcpMaxIteration);
+    ICP_CHECK_ARG(c.relative_fitness >= 0.0 && c.relative_rmse >= 0.0);      // (false for a NaN)
+    if (c.estimation == kEstPlane) ICP_CHECK_ARG(c.m_total == 0 || c.tgt_normals);
+    if (c.estimation == kEstGeneralized) {
+        ICP_CHECK_ARG(c.n_total == 0 || c.src_cov);
+        ICP_CHECK_ARG(c.m_total == 0 || c.tgt_cov);
     }
-    Carver cv(ws, ws_bytes);
-    IcpWs w = carve_icp(cv, B, n_total, estimation == 0 ? kIcpTerms : kIcpPlaneTerms);
+    if (c.estimation == kEstColored) {
+        ICP_CHECK_ARG(c.lambda_geometric >= 0.0 && c.lambda_geometric <= 1.0);   // (false for a NaN)
+        ICP_CHECK_ARG(c.n_total == 0 || c.src_intensity);
+        ICP_CHECK_ARG(c.m_total == 0 || c.tgt_rec);
+    }
+    const bool point = c.estimation == kEstPoint;
+    Carver cv(c.ws, c.ws_bytes);
+    IcpWs w = carve_icp(cv, c.B, c.n_total, point ? kIcpTerms : kIcpPlaneTerms);
     if (!cv.ok()) {
         set_error("%s: workspace too small (%zu needed, %zu given)", who, cv.off, cv.cap);
         return PCRCG_EWORKSPACE;
     }
     bool ok;
-    GridView g = grid_view(const_cast<void*>(grid), grid_bytes(m_total, B), m_total, B, &ok);
+    GridView g = grid_view(const_cast<void*>(c.grid), grid_bytes(c.m_total, c.B), c.m_total, c.B, &ok);
+    const bool colored = c.estimation == kEstColored;
+    const pcrcg_icp_trace_ex none = {nullptr, nullptr, nullptr, nullptr, nullptr}, &tr = c.trace ? *c.trace : none;
     IcpArgs a;
-    a.src = src; a.src_off = src_off; a.tgt_off = tgt_off; a.init = init;
+    a.src = c.src; a.src_off = c.src_off; a.tgt_off = c.tgt_off; a.init = c.init;
     a.state = w.state; a.p_cnt = w.p_cnt; a.p_sum = w.p_sum;
-    a.out_t = out_transform; a.out_stats = out_stats;
-    a.tr_t = trace.transforms; a.tr_counts = trace.counts; a.tr_sums = trace.sums; a.tr_corr = trace.corr;
-    a.tgt_nrm = tgt_normals;
-    a.tr_sums27 = estimation != 0 ? trace.sums27 : nullptr;
-    a.src_cov = src_cov; a.tgt_cov = tgt_cov;
-    a.tgt_rec = tgt_rec; a.src_int = src_intensity;
-    a.sg = estimation == kEstColored ? sqrt(lambda_geometric) : 0.0;
-    a.sp = estimation == kEstColored ? sqrt(1.0 - lambda_geometric) : 0.0;
-    a.n_total = n_total; a.n_max = n_max; a.max_iteration = max_iteration;
-    a.thr2 = (float)(max_correspondence_distance * max_correspondence_distance);
-    a.rel_fitness = relative_fitness; a.rel_rmse = relative_rmse;
-    if (estimation == kEstGeneralized) return icp_enqueue<2>(a, g, B, as_stream(stream));
-    if (estimation == kEstColored) return icp_enqueue<3>(a, g, B, as_stream(stream));
-    return estimation == 0 ? icp_enqueue<0>(a, g, B, as_stream(stream)) : icp_enqueue<1>(a, g, B, as_stream(stream));
+    a.out_t = c.out_transform; a.out_stats = c.out_stats;
+    a.tr_t = tr.transforms; a.tr_counts = tr.counts; a.tr_sums = tr.sums; a.tr_corr = tr.corr;
+    a.tgt_nrm = c.tgt_normals;
+    a.tr_sums27 = point ? nullptr : tr.sums27;
+    a.n_total = c.n_total; a.n_max = c.n_max; a.max_iteration = c.max_iteration;
+    a.thr2 = (float)(c.max_correspondence_distance * c.max_correspondence_distance);
+    a.rel_fitness = c.relative_fitness; a.rel_rmse = c.relative_rmse;
+    a.tgt_rec = c.tgt_rec; a.src_int = c.src_intensity;
+    a.sg = colored ? sqrt(c.lambda_geometric) : 0.0;
+    a.sp = colored ? sqrt(1.0 - c.lambda_geometric) : 0.0;
+    a.src_cov = c.src_cov; a.tgt_cov = c.tgt_cov;
+    const hipStream_t st = as_stream(c.stream);
+    switch (c.estimation) {     // (the cases' order is the kernels' order in the code object: append)
+    case kEstGeneralized: return icp_enqueue<kEstGeneralized>(a, g, c.B, st);
+    case kEstColored: return icp_enqueue<kEstColored>(a, g, c.B, st);
+    case kEstPoint: return icp_enqueue<kEstPoint>(a, g, c.B, st);
+    default: return icp_enqueue<kEstPlane>(a, g, c.B, st);
+    }
 }
-#undef ICP_CHECK_ARG
 
 }  // namespace
 }  // namespace pcrcg
@@ -455,10 +497,7 @@ using namespace pcrcg;
 extern "C" {
 
 size_t pcrcg_icp_batch_ws_bytes(int B, int n_total, int m_total, int max_iteration) {
-    if (B < 1 || B > kIcpMaxBatch || n_total < 0 || m_total < 0 || max_iteration < 1 || max_iteration > kIcpMaxIteration) return 0;
-    Carver cv(nullptr, 0);
-    carve_icp(cv, B, n_total);
-    return cv.off;
+    return icp_ws_bytes(B, n_total, m_total, max_iteration, kIcpTerms);
 }
 
 int pcrcg_icp_batch(const float* src, const int* src_off, int n_total, int n_max, const int* tgt_off, int m_total,
@@ -467,16 +506,13 @@ int pcrcg_icp_batch(const float* src, const int* src_off, int n_total, int n_max
                     const pcrcg_icp_trace* trace, void* ws, size_t ws_bytes, void* stream) {
     pcrcg_icp_trace_ex tr = {nullptr, nullptr, nullptr, nullptr, nullptr};
     if (trace) { tr.transforms = trace->transforms; tr.counts = trace->counts; tr.sums = trace->sums; tr.corr = trace->corr; }
-    return icp_run(__func__, src, src_off, n_total, n_max, tgt_off, m_total, grid, init, B, max_correspondence_distance,
-                   max_iteration, relative_fitness, relative_rmse, 0, nullptr, nullptr, nullptr, nullptr, nullptr, 0.0, out_transform, out_stats,
-                   tr, ws, ws_bytes, stream);
+    IcpCall c = {src, src_off, n_total, n_max, tgt_off, m_total, grid, init, B, max_correspondence_distance, max_iteration,
+                 relative_fitness, relative_rmse, out_transform, out_stats, &tr, ws, ws_bytes, stream};
+    return icp_run(__func__, c);
 }
 
 size_t pcrcg_icp_batch_ex_ws_bytes(int B, int n_total, int m_total, int max_iteration) {
-    if (B < 1 || B > kIcpMaxBatch || n_total < 0 || m_total < 0 || max_iteration < 1 || max_iteration > kIcpMaxIteration) return 0;
-    Carver cv(nullptr, 0);
-    carve_icp(cv, B, n_total, kIcpPlaneTerms);
-    return cv.off;
+    return icp_ws_bytes(B, n_total, m_total, max_iteration, kIcpPlaneTerms);
 }
 
 int pcrcg_icp_batch_ex(const float* src, const int* src_off, int n_total, int n_max, const int* tgt_off, int m_total,
@@ -484,13 +520,13 @@ int pcrcg_icp_batch_ex(const float* src, const int* src_off, int n_total, int n_
                        double relative_fitness, double relative_rmse, int estimation, const double* tgt_normals,
                        double* out_transform, double* out_stats, const pcrcg_icp_trace_ex* trace, void* ws, size_t ws_bytes,
                        void* stream) {
-    const pcrcg_icp_trace_ex none = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    // this entry's estimators are 0 and 1: the generalized and the colored one's numbers are as bad a value here as any other,
-    // and icp_run rejects them where it always checked `estimation`
-    const int est = estimation == kEstGeneralized || estimation == kEstColored ? -1 : estimation;
-    return icp_run(__func__, src, src_off, n_total, n_max, tgt_off, m_total, grid, init, B, max_correspondence_distance,
-                   max_iteration, relative_fitness, relative_rmse, est, tgt_normals, nullptr, nullptr, nullptr, nullptr, 0.0,
-                   out_transform, out_stats, trace ? *trace : none, ws, ws_bytes, stream);
+    const char* who = __func__;
+    ICP_CHECK_ARG(estimation == 0 || estimation == 1);       // this entry's two: point-to-point and point-to-plane
+    IcpCall c = {src, src_off, n_total, n_max, tgt_off, m_total, grid, init, B, max_correspondence_distance, max_iteration,
+                 relative_fitness, relative_rmse, out_transform, out_stats, trace, ws, ws_bytes, stream};
+    c.estimation = estimation;
+    c.tgt_normals = tgt_normals;
+    return icp_run(who, c);
 }
 
 int pcrcg_covariances_from_normals(const double* normals, long n, double epsilon, double* cov, void* stream) {
@@ -505,7 +541,7 @@ int pcrcg_covariances_from_normals(const double* normals, long n, double epsilon
 }
 
 size_t pcrcg_gicp_batch_ws_bytes(int B, int n_total, int m_total, int max_iteration) {
-    return pcrcg_icp_batch_ex_ws_bytes(B, n_total, m_total, max_iteration);
+    return icp_ws_bytes(B, n_total, m_total, max_iteration, kIcpPlaneTerms);
 }
 
 int pcrcg_gicp_batch(const float* src, const int* src_off, int n_total, int n_max, const int* tgt_off, int m_total,
@@ -513,14 +549,16 @@ int pcrcg_gicp_batch(const float* src, const int* src_off, int n_total, int n_ma
                      double relative_fitness, double relative_rmse, const double* src_cov, const double* tgt_cov,
                      double* out_transform, double* out_stats, const pcrcg_icp_trace_ex* trace, void* ws, size_t ws_bytes,
                      void* stream) {
-    const pcrcg_icp_trace_ex none = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    return icp_run(__func__, src, src_off, n_total, n_max, tgt_off, m_total, grid, init, B, max_correspondence_distance,
-                   max_iteration, relative_fitness, relative_rmse, kEstGeneralized, nullptr, src_cov, tgt_cov, nullptr, nullptr, 0.0,
-                   out_transform, out_stats, trace ? *trace : none, ws, ws_bytes, stream);
+    IcpCall c = {src, src_off, n_total, n_max, tgt_off, m_total, grid, init, B, max_correspondence_distance, max_iteration,
+                 relative_fitness, relative_rmse, out_transform, out_stats, trace, ws, ws_bytes, stream};
+    c.estimation = kEstGeneralized;
+    c.src_cov = src_cov;
+    c.tgt_cov = tgt_cov;
+    return icp_run(__func__, c);
 }
 
 size_t pcrcg_colored_icp_batch_ws_bytes(int B, int n_total, int m_total, int max_iteration) {
-    return pcrcg_icp_batch_ex_ws_bytes(B, n_total, m_total, max_iteration);
+    return icp_ws_bytes(B, n_total, m_total, max_iteration, kIcpPlaneTerms);
 }
 
 int pcrcg_colored_icp_batch(const float* src, const int* src_off, int n_total, int n_max, const int* tgt_off, int m_total,
@@ -528,10 +566,15 @@ int pcrcg_colored_icp_batch(const float* src, const int* src_off, int n_total, i
                             double relative_fitness, double relative_rmse, double lambda_geometric, const double* tgt_rec,
                             const double* src_intensity, double* out_transform, double* out_stats,
                             const pcrcg_icp_trace_ex* trace, void* ws, size_t ws_bytes, void* stream) {
-    const pcrcg_icp_trace_ex none = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    return icp_run(__func__, src, src_off, n_total, n_max, tgt_off, m_total, grid, init, B, max_correspondence_distance,
-                   max_iteration, relative_fitness, relative_rmse, kEstColored, nullptr, nullptr, nullptr, tgt_rec, src_intensity,
-                   lambda_geometric, out_transform, out_stats, trace ? *trace : none, ws, ws_bytes, stream);
+    IcpCall c = {src, src_off, n_total, n_max, tgt_off, m_total, grid, init, B, max_correspondence_distance, max_iteration,
+                 relative_fitness, relative_rmse, out_transform, out_stats, trace, ws, ws_bytes, stream};
+    c.estimation = kEstColored;
+    c.lambda_geometric = lambda_geometric;
+    c.tgt_rec = tgt_rec;
+    c.src_intensity = src_intensity;
+    return icp_run(__func__, c);
 }
+
+#undef ICP_CHECK_ARG
 
 }  // extern "C"

@@ -50,7 +50,15 @@ seed fixes every draw, and two runs give the same bits.  `register` reads the de
 Every batched entry here is its own argument rules, its library call and its result; what they share -- joining and uploading
 lists of arrays, offsets, chunk lists, cell grids, the counted read, the small checkers -- is in ragged.py.  The device is
 looked up through this module's `_device`, after the host checks, and handed to those helpers.
+
+The ICP entries (`refine_batch`, `generalized_icp_batch`, `colored_icp_batch`) share more, and keep it here: the small
+checkers `_check_pairs`, `_check_start`, `_check_distance`, `_check_loop` and `_check_tgt_normals` /
+`_check_tgt_normal_rows`, which each entry calls in its own order between its own rules, and one driver, `_icp_batch`, for
+everything from the chunk list to the result -- workspace, output buffer, start, trace buffers, per chunk the uploads, the
+ICP cell grid and the library call, then the one read.  An estimator joins it with its entry's name and one per-chunk
+function that returns the arguments its entry takes between the bounds and the outputs, and what it adds to the trace.
 """
+import collections
 import ctypes
 
 import numpy as np
@@ -827,6 +835,120 @@ def compute_fpfh_feature(pcd, radius, max_nn=100, *, normals=None, normal_radius
     return tuple(x[0] for x in out) if trace else out[0]
 
 
+def _check_pairs(who, src_pcds, tgt_pcds):
+    B = len(src_pcds)
+    if len(tgt_pcds) != B:
+        raise ValueError(f"{who}: list lengths differ ({B}, {len(tgt_pcds)})")
+    if B == 0:
+        raise ValueError(f"{who}: no pairs")
+    return B
+
+
+def _check_start(who, init, B):
+    """The starts: None, [B,4,4], or a BatchRegistrationResult -> None or the [B,4,4] array (its device transforms)."""
+    if isinstance(init, BatchRegistrationResult):
+        init = init.transformations
+    if init is not None and shape_of(init) != (B, 4, 4):
+        raise ValueError(f"{who}: init must be [{B}, 4, 4] (one start per pair), got shape {shape_of(init)}")
+    return init
+
+
+def _check_distance(who, max_correspondence_distance):
+    d = float(max_correspondence_distance)
+    if not 0.0 < d < 1e18:
+        raise ValueError(f"{who}: max_correspondence_distance must be positive")
+    return d
+
+
+def _check_loop(who, max_iteration, relative_fitness, relative_rmse):
+    mi = int(max_iteration)
+    if not 1 <= mi <= _MAX_ICP_ITERATION:
+        raise ValueError(f"{who}: max_iteration = {mi}, need 1..{_MAX_ICP_ITERATION}")
+    rf, rr = float(relative_fitness), float(relative_rmse)
+    if not (rf >= 0.0 and rr >= 0.0):
+        raise ValueError(f"{who}: relative_fitness and relative_rmse must be >= 0")
+    return mi, rf, rr
+
+
+def _check_tgt_normals(who, tgt_normals, normal_radius, normal_max_nn, B, what=""):
+    """The targets' normals are given, one set per pair, or estimated with normal_radius, not both -> None or the search."""
+    if tgt_normals is None:
+        if normal_radius is None:
+            raise ValueError(f"{who}: {what}needs tgt_normals or a normal_radius to estimate them with")
+        return _check_normal_search(who, normal_radius, normal_max_nn)
+    if normal_radius is not None:
+        raise ValueError(f"{who}: give tgt_normals or normal_radius, not both")
+    if len(tgt_normals) != B:
+        raise ValueError(f"{who}: {len(tgt_normals)} sets of target normals for {B} pairs")
+    return None
+
+
+def _check_tgt_normal_rows(who, tgt_normals, ms):
+    for b, x in enumerate(tgt_normals if tgt_normals is not None else ()):
+        if _cloud_rows(x, who, "the target normals", b) != ms[b]:
+            raise ValueError(f"{who}: pair {b}: the target normals must have one row per target point")
+
+
+# One call's pairs b0..b1 on the device: what an ICP estimator's per-chunk function is handed
+_IcpChunk = collections.namedtuple("_IcpChunk", "b0 b1 nb ns ms n_tot m_tot src tgt src_off tgt_off n_len m_len")
+
+
+def _tgt_normals_of(L, c, tgt_normals, search):
+    """Chunk c's target normals [m_tot,3] float64: the caller's, uploaded, or estimated with `search` (_check_tgt_normals')."""
+    if tgt_normals is None:
+        return _normals_of(L, c.tgt, c.tgt_off, c.m_len, c.m_tot, c.nb, max(c.ms), *search, None, False)[0]
+    return ragged.upload(tgt_normals[c.b0:c.b1], c.tgt.device, torch.float64, 3, "tgt_normals")
+
+
+def _icp_batch(who, entry, src_pcds, tgt_pcds, ns, ms, init, criteria, pairs_per_call, trace, given, estimator):
+    """The ICP entries' shared path, from the chunk list to the result: library entry `entry` (and its `_ws_bytes`) over the
+    pairs, already checked, with row counts ns / ms, start `init` (_check_start's) and criteria (d, max_iteration,
+    relative_fitness, relative_rmse).  `given` are the estimator's own arrays, for the device lookup.  Per chunk, after the
+    clouds are uploaded and the ICP cell grid is built, estimator(L, chunk: _IcpChunk) -> (args, traced): the arguments the
+    entry takes between the bounds and the outputs, and {name: (tensor, rows per pair)} of what it adds to the trace."""
+    B, (d, mi, rf, rr) = len(ns), criteria
+    chunks = ragged.chunks(B, pairs_per_call, _MAX_BATCH, who, ns, ms)
+    dev = _device(*src_pcds, *tgt_pcds, *([init] if init is not None else []), *given)
+    L = _lib.lib()
+    ws_bytes = getattr(L, entry + "_ws_bytes")
+    wsb = max(ws_bytes(b1 - b0, sum(ns[b0:b1]), sum(ms[b0:b1]), mi) for b0, b1 in chunks)
+    if wsb == 0:
+        raise ValueError(f"{who}: sizes out of range for the batch workspace")
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    out = torch.empty(B * (16 + _N_ICP_STATS), dtype=torch.float64, device=dev)
+    init_d = ragged.upload_f64(init, dev) if init is not None else None
+    point = entry == "pcrcg_icp_batch"      # the one entry with pcrcg_icp_trace: its update has no 27 sums
+    tr = None
+    if trace:
+        tr = {"transforms": torch.full((B, mi + 1, 4, 4), float("nan"), dtype=torch.float64, device=dev),
+              "counts": torch.full((B, mi + 1), -1, dtype=torch.int32, device=dev),
+              "sums": torch.full((B, mi + 1), float("nan"), dtype=torch.float64, device=dev), "corr": []}
+        if not point:
+            tr["sums27"] = torch.full((B, mi + 1, 27), float("nan"), dtype=torch.float64, device=dev)
+    for b0, b1 in chunks:
+        nb, n_tot, m_tot = b1 - b0, sum(ns[b0:b1]), sum(ms[b0:b1])
+        src = _cat(src_pcds[b0:b1], dev, "src_pcds", 3)
+        tgt = _cat(tgt_pcds[b0:b1], dev, "tgt_pcds", 3)
+        src_off, tgt_off, n_len, m_len = ragged.offsets(dev, ns[b0:b1], ms[b0:b1], lengths=[ns[b0:b1], ms[b0:b1]])
+        grid = ragged.cell_grid(tgt, m_tot, m_len, nb, d, _stream())
+        args, traced = estimator(L, _IcpChunk(b0, b1, nb, ns[b0:b1], ms[b0:b1], n_tot, m_tot, src, tgt, src_off, tgt_off,
+                                              n_len, m_len))
+        tr_ptr = None
+        if trace:
+            corr = torch.full((mi + 1, n_tot), -2, dtype=torch.int32, device=dev)
+            tr["corr"] += list(corr.split(ns[b0:b1], dim=1))
+            for name, (t, rows) in traced.items():
+                tr.setdefault(name, []).extend(t.split(rows))
+            members = [tr["transforms"][b0:].data_ptr(), tr["counts"][b0:].data_ptr(), tr["sums"][b0:].data_ptr(), corr.data_ptr()]
+            tr_ptr = ctypes.byref(_IcpTrace(*members) if point else _IcpTraceEx(*members, tr["sums27"][b0:].data_ptr()))
+        _lib.check(getattr(L, entry)(src.data_ptr() if n_tot else None, src_off.data_ptr(), n_tot, max(ns[b0:b1]),
+                                     tgt_off.data_ptr(), m_tot, grid.data_ptr(),
+                                     init_d[b0:].data_ptr() if init_d is not None else None, nb, d, mi, rf, rr, *args,
+                                     out[16 * b0:].data_ptr(), out[16 * B + _N_ICP_STATS * b0:].data_ptr(), tr_ptr,
+                                     ws.data_ptr(), wsb, _stream()), entry)
+    return BatchRefinementResult(out, _read(out), B, tr)
+
+
 def refine_batch(src_pcds, tgt_pcds, init, max_correspondence_distance, *, max_iteration=30, relative_fitness=1e-6,
                  relative_rmse=1e-6, pairs_per_call=None, trace=False, estimation="point_to_point", tgt_normals=None,
                  normal_radius=None, normal_max_nn=30):
@@ -846,91 +968,26 @@ def refine_batch(src_pcds, tgt_pcds, init, max_correspondence_distance, *, max_i
     the distances to the targets' tangent planes.  It reads the targets' normals: tgt_normals, a list of per-pair [M_b,3]
     arrays (their signs do not matter), or, without it, normal_radius (required then) and normal_max_nn: the normals are
     estimated in the same call on the same stream (estimate_normals_batch's, viewpoint at the origin)."""
-    B = len(src_pcds)
-    if len(tgt_pcds) != B:
-        raise ValueError(f"refine_batch: list lengths differ ({B}, {len(tgt_pcds)})")
-    if B == 0:
-        raise ValueError("refine_batch: no pairs")
+    who = "refine_batch"
+    B = _check_pairs(who, src_pcds, tgt_pcds)
     if estimation not in _ESTIMATIONS:
-        raise ValueError(f"refine_batch: estimation must be one of {sorted(_ESTIMATIONS)}, got {estimation!r}")
+        raise ValueError(f"{who}: estimation must be one of {sorted(_ESTIMATIONS)}, got {estimation!r}")
     plane = _ESTIMATIONS[estimation] == 1
     if not plane and (tgt_normals is not None or normal_radius is not None):
-        raise ValueError("refine_batch: tgt_normals / normal_radius belong to estimation='point_to_plane'")
-    if plane and tgt_normals is None:
-        if normal_radius is None:
-            raise ValueError("refine_batch: point_to_plane needs tgt_normals or a normal_radius to estimate them with")
-        nr, nk = _check_normal_search("refine_batch", normal_radius, normal_max_nn)
-    elif plane:
-        if normal_radius is not None:
-            raise ValueError("refine_batch: give tgt_normals or normal_radius, not both")
-        if len(tgt_normals) != B:
-            raise ValueError(f"refine_batch: {len(tgt_normals)} sets of target normals for {B} pairs")
-    if isinstance(init, BatchRegistrationResult):
-        init = init.transformations
-    if init is not None and shape_of(init) != (B, 4, 4):
-        raise ValueError(f"refine_batch: init must be [{B}, 4, 4] (one start per pair), got shape {shape_of(init)}")
-    d = float(max_correspondence_distance)
-    if not 0.0 < d < 1e18:
-        raise ValueError("refine_batch: max_correspondence_distance must be positive")
-    mi = int(max_iteration)
-    if not 1 <= mi <= _MAX_ICP_ITERATION:
-        raise ValueError(f"refine_batch: max_iteration = {mi}, need 1..{_MAX_ICP_ITERATION}")
-    rf, rr = float(relative_fitness), float(relative_rmse)
-    if not (rf >= 0.0 and rr >= 0.0):
-        raise ValueError("refine_batch: relative_fitness and relative_rmse must be >= 0")
-    ns = [_cloud_rows(x, "refine_batch", "the source", b) for b, x in enumerate(src_pcds)]
-    ms = [_cloud_rows(x, "refine_batch", "the target", b) for b, x in enumerate(tgt_pcds)]
-    if plane and tgt_normals is not None:
-        for b, x in enumerate(tgt_normals):
-            if _cloud_rows(x, "refine_batch", "the target normals", b) != ms[b]:
-                raise ValueError(f"refine_batch: pair {b}: the target normals must have one row per target point")
-    chunks = ragged.chunks(B, pairs_per_call, _MAX_BATCH, "refine_batch", ns, ms)
-    dev = _device(*src_pcds, *tgt_pcds, *([init] if init is not None else []))
-    L = _lib.lib()
-    ws_bytes = L.pcrcg_icp_batch_ex_ws_bytes if plane else L.pcrcg_icp_batch_ws_bytes
-    wsb = max(ws_bytes(b1 - b0, sum(ns[b0:b1]), sum(ms[b0:b1]), mi) for b0, b1 in chunks)
-    if wsb == 0:
-        raise ValueError("refine_batch: sizes out of range for the batch workspace")
-    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-    out = torch.empty(B * (16 + _N_ICP_STATS), dtype=torch.float64, device=dev)
-    init_d = ragged.upload_f64(init, dev) if init is not None else None
-    tr = None
-    if trace:
-        tr = {"transforms": torch.full((B, mi + 1, 4, 4), float("nan"), dtype=torch.float64, device=dev),
-              "counts": torch.full((B, mi + 1), -1, dtype=torch.int32, device=dev),
-              "sums": torch.full((B, mi + 1), float("nan"), dtype=torch.float64, device=dev), "corr": []}
-        if plane:
-            tr["sums27"] = torch.full((B, mi + 1, 27), float("nan"), dtype=torch.float64, device=dev)
-            tr["normals"] = []
-    entry = "pcrcg_icp_batch_ex" if plane else "pcrcg_icp_batch"
-    for b0, b1 in chunks:
-        nb = b1 - b0
-        n_tot, m_tot = sum(ns[b0:b1]), sum(ms[b0:b1])
-        src = _cat(src_pcds[b0:b1], dev, "src_pcds", 3)
-        tgt = _cat(tgt_pcds[b0:b1], dev, "tgt_pcds", 3)
-        src_off, tgt_off, lengths = ragged.offsets(dev, ns[b0:b1], ms[b0:b1], lengths=[ms[b0:b1]])
-        grid = ragged.cell_grid(tgt, m_tot, lengths, nb, d, _stream())
-        tr_ptr = None
-        if trace:
-            corr = torch.full((mi + 1, n_tot), -2, dtype=torch.int32, device=dev)
-            tr["corr"] += list(corr.split(ns[b0:b1], dim=1))
-            members = [tr["transforms"][b0:].data_ptr(), tr["counts"][b0:].data_ptr(), tr["sums"][b0:].data_ptr(), corr.data_ptr()]
-            tr_ptr = ctypes.byref(_IcpTraceEx(*members, tr["sums27"][b0:].data_ptr()) if plane else _IcpTrace(*members))
-        plane_args = ()     # pcrcg_icp_batch_ex's two more: the estimation and the targets' normals
-        if plane:
-            if tgt_normals is None:
-                nrm = _normals_of(L, tgt, tgt_off, lengths, m_tot, nb, max(ms[b0:b1]), nr, nk, None, False)[0]
-            else:
-                nrm = ragged.upload(tgt_normals[b0:b1], dev, torch.float64, 3, "tgt_normals")
-            if trace:
-                tr["normals"] += list(nrm.split(ms[b0:b1]))
-            plane_args = (1, nrm.data_ptr() if m_tot else None)
-        _lib.check(getattr(L, entry)(src.data_ptr() if n_tot else None, src_off.data_ptr(), n_tot, max(ns[b0:b1]),
-                                     tgt_off.data_ptr(), m_tot, grid.data_ptr(),
-                                     init_d[b0:].data_ptr() if init_d is not None else None, nb, d, mi, rf, rr, *plane_args,
-                                     out[16 * b0:].data_ptr(), out[16 * B + _N_ICP_STATS * b0:].data_ptr(), tr_ptr,
-                                     ws.data_ptr(), wsb, _stream()), entry)
-    return BatchRefinementResult(out, _read(out), B, tr)
+        raise ValueError(f"{who}: tgt_normals / normal_radius belong to estimation='point_to_plane'")
+    search = _check_tgt_normals(who, tgt_normals, normal_radius, normal_max_nn, B, "point_to_plane ") if plane else None
+    init = _check_start(who, init, B)
+    criteria = (_check_distance(who, max_correspondence_distance), *_check_loop(who, max_iteration, relative_fitness, relative_rmse))
+    ns = [_cloud_rows(x, who, "the source", b) for b, x in enumerate(src_pcds)]
+    ms = [_cloud_rows(x, who, "the target", b) for b, x in enumerate(tgt_pcds)]
+    _check_tgt_normal_rows(who, tgt_normals, ms)
+
+    def point_to_plane(L, c):       # pcrcg_icp_batch_ex's two more: the estimation and the targets' normals
+        nrm = _tgt_normals_of(L, c, tgt_normals, search)
+        return (1, nrm.data_ptr() if c.m_tot else None), {"normals": (nrm, c.ms)}
+
+    return _icp_batch(who, "pcrcg_icp_batch_ex" if plane else "pcrcg_icp_batch", src_pcds, tgt_pcds, ns, ms, init, criteria,
+                      pairs_per_call, trace, (), point_to_plane if plane else lambda L, c: ((), {}))
 
 
 def refine(src_pcd, tgt_pcd, init, max_correspondence_distance, *, max_iteration=30, relative_fitness=1e-6,
@@ -1017,86 +1074,39 @@ def generalized_icp_batch(src_pcds, tgt_pcds, init, max_correspondence_distance,
     -sum J0^T W d) with src_covariances / tgt_covariances, per pair the [N_b,6] / [M_b,6] float64 rows the updates read, in
     the place of the normals."""
     who = "generalized_icp_batch"
-    B = len(src_pcds)
-    if len(tgt_pcds) != B:
-        raise ValueError(f"{who}: list lengths differ ({B}, {len(tgt_pcds)})")
-    if B == 0:
-        raise ValueError(f"{who}: no pairs")
+    B = _check_pairs(who, src_pcds, tgt_pcds)
     eps = _check_epsilon(who, epsilon)
-    if isinstance(init, BatchRegistrationResult):
-        init = init.transformations
-    if init is not None and shape_of(init) != (B, 4, 4):
-        raise ValueError(f"{who}: init must be [{B}, 4, 4] (one start per pair), got shape {shape_of(init)}")
-    d = float(max_correspondence_distance)
-    if not 0.0 < d < 1e18:
-        raise ValueError(f"{who}: max_correspondence_distance must be positive")
-    mi = int(max_iteration)
-    if not 1 <= mi <= _MAX_ICP_ITERATION:
-        raise ValueError(f"{who}: max_iteration = {mi}, need 1..{_MAX_ICP_ITERATION}")
-    rf, rr = float(relative_fitness), float(relative_rmse)
-    if not (rf >= 0.0 and rr >= 0.0):
-        raise ValueError(f"{who}: relative_fitness and relative_rmse must be >= 0")
+    init = _check_start(who, init, B)
+    criteria = (_check_distance(who, max_correspondence_distance), *_check_loop(who, max_iteration, relative_fitness, relative_rmse))
     ns = [_cloud_rows(x, who, "the source", b) for b, x in enumerate(src_pcds)]
     ms = [_cloud_rows(x, who, "the target", b) for b, x in enumerate(tgt_pcds)]
     src_kind = _gicp_side(who, "src", src_covariances, src_normals, normal_radius, B, ns)
     tgt_kind = _gicp_side(who, "tgt", tgt_covariances, tgt_normals, normal_radius, B, ms)
     if "radius" in (src_kind, tgt_kind):
-        nr, nk = _check_normal_search(who, normal_radius, normal_max_nn)
+        search = _check_normal_search(who, normal_radius, normal_max_nn)
     elif normal_radius is not None:
         raise ValueError(f"{who}: both sides have their covariances or normals; normal_radius belongs to a side without")
-    chunks = ragged.chunks(B, pairs_per_call, _MAX_BATCH, who, ns, ms)
-    given = [x for xs in (src_covariances, src_normals, tgt_covariances, tgt_normals) if xs is not None for x in xs]
-    dev = _device(*src_pcds, *tgt_pcds, *([init] if init is not None else []), *given)
-    L = _lib.lib()
-    wsb = max(L.pcrcg_gicp_batch_ws_bytes(b1 - b0, sum(ns[b0:b1]), sum(ms[b0:b1]), mi) for b0, b1 in chunks)
-    if wsb == 0:
-        raise ValueError(f"{who}: sizes out of range for the batch workspace")
-    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-    out = torch.empty(B * (16 + _N_ICP_STATS), dtype=torch.float64, device=dev)
-    init_d = ragged.upload_f64(init, dev) if init is not None else None
-    tr = None
-    if trace:
-        tr = {"transforms": torch.full((B, mi + 1, 4, 4), float("nan"), dtype=torch.float64, device=dev),
-              "counts": torch.full((B, mi + 1), -1, dtype=torch.int32, device=dev),
-              "sums": torch.full((B, mi + 1), float("nan"), dtype=torch.float64, device=dev), "corr": [],
-              "sums27": torch.full((B, mi + 1, 27), float("nan"), dtype=torch.float64, device=dev),
-              "src_covariances": [], "tgt_covariances": []}
 
-    def side(kind, covariances, normals, pts, off, lengths, rows, b0, b1):
-        tot = sum(rows[b0:b1])
+    def side(L, c, kind, covariances, normals, pts, off, lengths, rows):
+        tot = pts.shape[0]
         if kind == "covariances":
-            return ragged.join(ragged.tensors(covariances[b0:b1]), dev, torch.float64,
+            return ragged.join(ragged.tensors(covariances[c.b0:c.b1]), pts.device, torch.float64,
                                lambda t: t.reshape(-1, 9)[:, list(_COV_PACK)]).reshape(tot, 6)
         if kind == "normals":
-            nrm = ragged.upload(normals[b0:b1], dev, torch.float64, 3, "normals")
+            nrm = ragged.upload(normals[c.b0:c.b1], pts.device, torch.float64, 3, "normals")
         else:
-            nrm = _normals_of(L, pts, off, lengths, tot, b1 - b0, max(rows[b0:b1]), nr, nk, None, False)[0]
+            nrm = _normals_of(L, pts, off, lengths, tot, c.nb, max(rows), *search, None, False)[0]
         return _covariances_of(L, nrm, tot, eps)
 
-    for b0, b1 in chunks:
-        nb = b1 - b0
-        n_tot, m_tot = sum(ns[b0:b1]), sum(ms[b0:b1])
-        src = _cat(src_pcds[b0:b1], dev, "src_pcds", 3)
-        tgt = _cat(tgt_pcds[b0:b1], dev, "tgt_pcds", 3)
-        src_off, tgt_off, m_len, n_len = ragged.offsets(dev, ns[b0:b1], ms[b0:b1], lengths=[ms[b0:b1], ns[b0:b1]])
-        grid = ragged.cell_grid(tgt, m_tot, m_len, nb, d, _stream())
-        cs = side(src_kind, src_covariances, src_normals, src, src_off, n_len, ns, b0, b1)
-        ct = side(tgt_kind, tgt_covariances, tgt_normals, tgt, tgt_off, m_len, ms, b0, b1)
-        tr_ptr = None
-        if trace:
-            corr = torch.full((mi + 1, n_tot), -2, dtype=torch.int32, device=dev)
-            tr["corr"] += list(corr.split(ns[b0:b1], dim=1))
-            tr["src_covariances"] += list(cs.split(ns[b0:b1]))
-            tr["tgt_covariances"] += list(ct.split(ms[b0:b1]))
-            tr_ptr = ctypes.byref(_IcpTraceEx(tr["transforms"][b0:].data_ptr(), tr["counts"][b0:].data_ptr(),
-                                              tr["sums"][b0:].data_ptr(), corr.data_ptr(), tr["sums27"][b0:].data_ptr()))
-        _lib.check(L.pcrcg_gicp_batch(src.data_ptr() if n_tot else None, src_off.data_ptr(), n_tot, max(ns[b0:b1]),
-                                      tgt_off.data_ptr(), m_tot, grid.data_ptr(),
-                                      init_d[b0:].data_ptr() if init_d is not None else None, nb, d, mi, rf, rr,
-                                      cs.data_ptr() if n_tot else None, ct.data_ptr() if m_tot else None,
-                                      out[16 * b0:].data_ptr(), out[16 * B + _N_ICP_STATS * b0:].data_ptr(), tr_ptr,
-                                      ws.data_ptr(), wsb, _stream()), "pcrcg_gicp_batch")
-    return BatchRefinementResult(out, _read(out), B, tr)
+    def generalized(L, c):          # pcrcg_gicp_batch's two more: both clouds' covariances
+        cs = side(L, c, src_kind, src_covariances, src_normals, c.src, c.src_off, c.n_len, c.ns)
+        ct = side(L, c, tgt_kind, tgt_covariances, tgt_normals, c.tgt, c.tgt_off, c.m_len, c.ms)
+        return ((cs.data_ptr() if c.n_tot else None, ct.data_ptr() if c.m_tot else None),
+                {"src_covariances": (cs, c.ns), "tgt_covariances": (ct, c.ms)})
+
+    given = [x for xs in (src_covariances, src_normals, tgt_covariances, tgt_normals) if xs is not None for x in xs]
+    return _icp_batch(who, "pcrcg_gicp_batch", src_pcds, tgt_pcds, ns, ms, init, criteria, pairs_per_call, trace, given,
+                      generalized)
 
 
 def generalized_icp(src_pcd, tgt_pcd, init, max_correspondence_distance, **kw):
@@ -1235,98 +1245,39 @@ def colored_icp_batch(src_pcds, tgt_pcds, src_colors, tgt_colors, init, max_corr
     exactly one of tgt_normals (a list of per-pair [M_b,3] arrays) or normal_radius (with normal_max_nn: the normals are
     estimated in the same call, estimate_normals_batch's, viewpoint at the origin).  gradient_radius (None: 2 x
     max_correspondence_distance, as open3d) and gradient_max_nn are the search of the targets' colour gradients.  One call
-    runs, on one stream: the normals when they are not given, the cell grids at the gradient radius and at the correspondence
-    distance, the gradient kernel and the ICP loop.  Every size and shape is checked on the host before anything is uploaded
+    runs, on one stream: the cell grid at the correspondence distance, the normals when they are not given, the cell grid at
+    the gradient radius, the gradient kernel and the ICP loop.  Every size and shape is checked on the host before anything is uploaded
     or launched; all chunks write into one device buffer, read ONCE at the end.  trace=True: refine_batch's point-to-plane
     trace (sums27: the upper triangle of sum JG JG^T + JI JI^T, then -sum (JG rg + JI ri)) plus tgt_records (per pair the
     [M_b,8] float64 records the updates read) and src_intensities (per pair [N_b] float64)."""
     who = "colored_icp_batch"
-    B = len(src_pcds)
-    if len(tgt_pcds) != B:
-        raise ValueError(f"{who}: list lengths differ ({B}, {len(tgt_pcds)})")
-    if B == 0:
-        raise ValueError(f"{who}: no pairs")
+    B = _check_pairs(who, src_pcds, tgt_pcds)
     lam = float(lambda_geometric)
     if not 0.0 <= lam <= 1.0:
         raise ValueError(f"{who}: lambda_geometric must lie in [0, 1], got {lambda_geometric}")
-    if tgt_normals is None:
-        if normal_radius is None:
-            raise ValueError(f"{who}: needs tgt_normals or a normal_radius to estimate them with")
-        nr, nk = _check_normal_search(who, normal_radius, normal_max_nn)
-    else:
-        if normal_radius is not None:
-            raise ValueError(f"{who}: give tgt_normals or normal_radius, not both")
-        if len(tgt_normals) != B:
-            raise ValueError(f"{who}: {len(tgt_normals)} sets of target normals for {B} pairs")
-    if isinstance(init, BatchRegistrationResult):
-        init = init.transformations
-    if init is not None and shape_of(init) != (B, 4, 4):
-        raise ValueError(f"{who}: init must be [{B}, 4, 4] (one start per pair), got shape {shape_of(init)}")
-    d = float(max_correspondence_distance)
-    if not 0.0 < d < 1e18:
-        raise ValueError(f"{who}: max_correspondence_distance must be positive")
+    search = _check_tgt_normals(who, tgt_normals, normal_radius, normal_max_nn, B)
+    init = _check_start(who, init, B)
+    d = _check_distance(who, max_correspondence_distance)
     gr, gk = _check_gradient_search(who, 2.0 * d if gradient_radius is None else gradient_radius, gradient_max_nn)
-    mi = int(max_iteration)
-    if not 1 <= mi <= _MAX_ICP_ITERATION:
-        raise ValueError(f"{who}: max_iteration = {mi}, need 1..{_MAX_ICP_ITERATION}")
-    rf, rr = float(relative_fitness), float(relative_rmse)
-    if not (rf >= 0.0 and rr >= 0.0):
-        raise ValueError(f"{who}: relative_fitness and relative_rmse must be >= 0")
+    criteria = (d, *_check_loop(who, max_iteration, relative_fitness, relative_rmse))
     ns = [_cloud_rows(x, who, "the source", b) for b, x in enumerate(src_pcds)]
     ms = [_cloud_rows(x, who, "the target", b) for b, x in enumerate(tgt_pcds)]
     _check_colors(who, "source", src_colors, B, ns)
     _check_colors(who, "target", tgt_colors, B, ms)
-    if tgt_normals is not None:
-        for b, x in enumerate(tgt_normals):
-            if _cloud_rows(x, who, "the target normals", b) != ms[b]:
-                raise ValueError(f"{who}: pair {b}: the target normals must have one row per target point")
-    chunks = ragged.chunks(B, pairs_per_call, _MAX_BATCH, who, ns, ms)
-    dev = _device(*src_pcds, *tgt_pcds, *([init] if init is not None else []), *src_colors, *tgt_colors,
-                  *(tgt_normals if tgt_normals is not None else []))
-    L = _lib.lib()
-    wsb = max(L.pcrcg_colored_icp_batch_ws_bytes(b1 - b0, sum(ns[b0:b1]), sum(ms[b0:b1]), mi) for b0, b1 in chunks)
-    if wsb == 0:
-        raise ValueError(f"{who}: sizes out of range for the batch workspace")
-    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-    out = torch.empty(B * (16 + _N_ICP_STATS), dtype=torch.float64, device=dev)
-    init_d = ragged.upload_f64(init, dev) if init is not None else None
-    tr = None
-    if trace:
-        tr = {"transforms": torch.full((B, mi + 1, 4, 4), float("nan"), dtype=torch.float64, device=dev),
-              "counts": torch.full((B, mi + 1), -1, dtype=torch.int32, device=dev),
-              "sums": torch.full((B, mi + 1), float("nan"), dtype=torch.float64, device=dev), "corr": [],
-              "sums27": torch.full((B, mi + 1, 27), float("nan"), dtype=torch.float64, device=dev),
-              "normals": [], "tgt_records": [], "src_intensities": []}
-    for b0, b1 in chunks:
-        nb = b1 - b0
-        n_tot, m_tot = sum(ns[b0:b1]), sum(ms[b0:b1])
-        src = _cat(src_pcds[b0:b1], dev, "src_pcds", 3)
-        tgt = _cat(tgt_pcds[b0:b1], dev, "tgt_pcds", 3)
-        src_off, tgt_off, lengths = ragged.offsets(dev, ns[b0:b1], ms[b0:b1], lengths=[ms[b0:b1]])
-        if tgt_normals is None:
-            nrm = _normals_of(L, tgt, tgt_off, lengths, m_tot, nb, max(ms[b0:b1]), nr, nk, None, False)[0]
-        else:
-            nrm = ragged.upload(tgt_normals[b0:b1], dev, torch.float64, 3, "tgt_normals")
-        src_int = _intensities(src_colors[b0:b1], dev)
-        rec = _gradients_of(L, tgt, tgt_off, lengths, m_tot, nb, max(ms[b0:b1]), gr, gk, nrm,
-                            _intensities(tgt_colors[b0:b1], dev), False)[0]
-        grid = ragged.cell_grid(tgt, m_tot, lengths, nb, d, _stream())
-        tr_ptr = None
-        if trace:
-            corr = torch.full((mi + 1, n_tot), -2, dtype=torch.int32, device=dev)
-            tr["corr"] += list(corr.split(ns[b0:b1], dim=1))
-            tr["normals"] += list(nrm.split(ms[b0:b1]))
-            tr["tgt_records"] += list(rec.split(ms[b0:b1]))
-            tr["src_intensities"] += list(src_int.split(ns[b0:b1]))
-            tr_ptr = ctypes.byref(_IcpTraceEx(tr["transforms"][b0:].data_ptr(), tr["counts"][b0:].data_ptr(),
-                                              tr["sums"][b0:].data_ptr(), corr.data_ptr(), tr["sums27"][b0:].data_ptr()))
-        _lib.check(L.pcrcg_colored_icp_batch(src.data_ptr() if n_tot else None, src_off.data_ptr(), n_tot, max(ns[b0:b1]),
-                                             tgt_off.data_ptr(), m_tot, grid.data_ptr(),
-                                             init_d[b0:].data_ptr() if init_d is not None else None, nb, d, mi, rf, rr, lam,
-                                             rec.data_ptr() if m_tot else None, src_int.data_ptr() if n_tot else None,
-                                             out[16 * b0:].data_ptr(), out[16 * B + _N_ICP_STATS * b0:].data_ptr(), tr_ptr,
-                                             ws.data_ptr(), wsb, _stream()), "pcrcg_colored_icp_batch")
-    return BatchRefinementResult(out, _read(out), B, tr)
+    _check_tgt_normal_rows(who, tgt_normals, ms)
+
+    def colored(L, c):              # pcrcg_colored_icp_batch's three more: lambda, the targets' records, the sources' intensities
+        dev = c.tgt.device
+        nrm = _tgt_normals_of(L, c, tgt_normals, search)
+        src_int = _intensities(src_colors[c.b0:c.b1], dev)
+        rec = _gradients_of(L, c.tgt, c.tgt_off, c.m_len, c.m_tot, c.nb, max(c.ms), gr, gk, nrm,
+                            _intensities(tgt_colors[c.b0:c.b1], dev), False)[0]
+        return ((lam, rec.data_ptr() if c.m_tot else None, src_int.data_ptr() if c.n_tot else None),
+                {"normals": (nrm, c.ms), "tgt_records": (rec, c.ms), "src_intensities": (src_int, c.ns)})
+
+    given = [*src_colors, *tgt_colors, *(tgt_normals if tgt_normals is not None else [])]
+    return _icp_batch(who, "pcrcg_colored_icp_batch", src_pcds, tgt_pcds, ns, ms, init, criteria, pairs_per_call, trace, given,
+                      colored)
 
 
 def colored_icp(src_pcd, tgt_pcd, src_colors, tgt_colors, init, max_correspondence_distance, **kw):

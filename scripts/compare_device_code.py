@@ -3,9 +3,9 @@
 
     python scripts/compare_device_code.py REV [file.hip ...]      (default: every .hip file of pcrcg_amd/csrc)
 
-Each file is compiled twice, from REV (`git archive` into a temporary directory) and from the working tree, with the
-Makefile's flags for it plus `-S --cuda-device-only`.  Lines that contain `__hip_cuid_` (a hash of the source text) are
-dropped; the two assembly files must then be byte-identical, kernel order included (a file whose template instances come
+Each file is compiled twice, from REV (`git archive` into a temporary directory) and from the working tree, each with the
+flags its own tree's Makefile gives the file (EXACT_SRC there: -ffp-contract=off) plus `-S --cuda-device-only`.  Lines
+that contain `__hip_cuid_` (a hash of the source text) are dropped; the two assembly files must then be byte-identical, kernel order included (a file whose template instances come
 out in another order fails here and needs a comparison per symbol by hand).  Exit status 0: every file identical.
 """
 import concurrent.futures
@@ -16,13 +16,21 @@ import tempfile
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-EXACT = {"grid_subsample.hip", "radius.hip", "tieorder.hip", "register.hip", "icp.hip", "projection.hip", "chamfer.hip"}   # Makefile: EXACT_SRC
+
+
+def exact_sources(root):
+    """The files a tree compiles with -ffp-contract=off: EXACT_SRC of ITS Makefile."""
+    with open(os.path.join(root, "pcrcg_amd", "csrc", "Makefile")) as f:
+        for ln in f:
+            if ln.startswith("EXACT_SRC"):
+                return set(ln.split(":=", 1)[1].split())
+    sys.exit("no EXACT_SRC in the Makefile of " + root)
 
 
 def assembly(root, src, out):
     csrc = os.path.join(root, "pcrcg_amd", "csrc")
     cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I" + os.path.join(root, "include"), "-I" + csrc]
-    if src in EXACT:
+    if src in exact_sources(root):
         cmd.append("-ffp-contract=off")
     cmd += ["-S", "--cuda-device-only", os.path.join(csrc, src), "-o", out]
     subprocess.run(cmd, check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)

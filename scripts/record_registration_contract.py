@@ -209,6 +209,163 @@ def _rows():
     add(e, P, Q, EYE, 0.1)                                               # valid
     add(e, P, Q, {"zeros": [4, 4], "dtype": "float64"}, 0.1, estimation="point_to_plane", normal_radius=0.2)    # valid
 
+    M64, C5, C4 = Z(4, 3, "float64"), {"zeros": [5, 3, 3], "dtype": "float64"}, {"zeros": [4, 3, 3], "dtype": "float64"}
+    e = "registration.generalized_icp_batch"
+    add(e, [P], [Q, Q], None, 0.1, normal_radius=0.2)
+    add(e, [], [Q], None, 0.1, normal_radius=0.2)                        # two wrong: lengths before "no pairs"
+    add(e, [], [], None, 0.1, normal_radius=0.2)
+    for bad in (0.0, -1e-3, 1.5, NAN):
+        add(e, [P], [Q], None, 0.1, epsilon=bad, normal_radius=0.2)
+    add(e, [P], [Q], [EYE, EYE], 0.1, epsilon=0.0, normal_radius=0.2)    # two wrong: epsilon before init
+    add(e, [P], [Q], [EYE, EYE], 0.1, normal_radius=0.2)
+    add(e, [P], [Q], EYE, 0.1, normal_radius=0.2)
+    add(e, [P], [Q], {"zeros": [1, 4, 3], "dtype": "float64"}, 0.0, normal_radius=0.2)       # two wrong: init before the distance
+    for bad in (0.0, NAN, INF):
+        add(e, [P], [Q], None, bad, normal_radius=0.2)
+    for bad in (0, (1 << 16) + 1):
+        add(e, [P], [Q], None, 0.1, max_iteration=bad, normal_radius=0.2)
+    add(e, [P], [Q], None, 0.0, max_iteration=0, normal_radius=0.2)      # two wrong: the distance before max_iteration
+    add(e, [P], [Q], None, 0.1, relative_fitness=-1.0, normal_radius=0.2)
+    add(e, [P], [Q], None, 0.1, relative_rmse=NAN, normal_radius=0.2)
+    add(e, [Z(5, 2)], [Q], None, 0.1, relative_rmse=-1.0, normal_radius=0.2)                 # two wrong: the bounds before the clouds
+    add(e, [Z(5, 2)], [Q], None, 0.1, normal_radius=0.2)
+    add(e, [P], [Z(4, 4)], None, 0.1, normal_radius=0.2)
+    add(e, [Z(5, 2)], [Z(4, 4)], None, 0.1, normal_radius=0.2)           # two wrong: the source before the target
+    add(e, [Z(5, 2)], [Q], None, 0.1)                                    # two wrong: the cloud rows before the per-side rule
+    add(e, [P], [Q], None, 0.1, src_covariances=[C5], src_normals=[N64], tgt_normals=[M64])
+    add(e, [P], [Q], None, 0.1, src_normals=[N64], tgt_covariances=[C4], tgt_normals=[M64])
+    add(e, [P], [Q], None, 0.1)
+    add(e, [P], [Q], None, 0.1, src_normals=[N64])
+    add(e, [P], [Q], None, 0.1, tgt_covariances=[C4])
+    add(e, [P], [Q], None, 0.1, src_covariances=[], tgt_normals=[M64])
+    add(e, [P], [Q], None, 0.1, src_normals=[N64, N64], tgt_normals=[M64])
+    add(e, [P], [Q], None, 0.1, src_normals=[N64], tgt_covariances=[C4, C4])
+    add(e, [P], [Q], None, 0.1, src_covariances=[C4], tgt_covariances=[C4])
+    add(e, [P], [Q], None, 0.1, src_covariances=[Z(5, 6, "float64")], tgt_covariances=[C4])
+    add(e, [P], [Q], None, 0.1, src_covariances=[C5], tgt_covariances=[{"zeros": [4, 3, 2], "dtype": "float64"}])
+    add(e, [P], [Q], None, 0.1, src_normals=[M64], tgt_normals=[M64])
+    add(e, [P], [Q], None, 0.1, src_normals=[N64], tgt_normals=[Z(4, 2, "float64")])
+    add(e, [P], [Q], None, 0.1, src_normals=[M64], tgt_normals=[N64])    # two wrong: the source side before the target side
+    add(e, [P], [Q], None, 0.1, src_normals=[N64], normal_radius=0.0)
+    add(e, [P], [Q], None, 0.1, tgt_covariances=[C4], normal_radius=0.2, normal_max_nn=65)
+    add(e, [P], [Q], None, 0.1, src_normals=[M64], normal_radius=0.0)    # two wrong: the side's shape before the normal search
+    add(e, [P], [Q], None, 0.1, src_normals=[N64], tgt_covariances=[C4], normal_radius=0.2)
+    add(e, [S(BIG, 3), S(BIG, 3)], [Q, Q], None, 0.1, normal_radius=0.2)
+    add(e, [P, P], [S(BIG, 3), S(BIG, 3)], None, 0.1, normal_radius=0.2)
+    add(e, [S(BIG, 3), S(BIG, 3)], [Q, Q], None, 0.1, normal_radius=0.2, normal_max_nn=0)    # two wrong: the normal search before the rows
+    add(e, [P, Z(0)], [Q, Q], None, 0.1, normal_radius=0.2, max_iteration=3, trace=True, pairs_per_call=1)      # valid
+    add(e, [P], [Q], [EYE], 0.1, epsilon=1.0, src_covariances=[C5], tgt_normals=[M64])                          # valid
+    add(e, [P], [Z(0)], None, 0.1, src_normals=[N64], normal_radius=0.2)                                        # valid
+
+    e = "registration.generalized_icp"
+    add(e, P, Q, {"zeros": [3, 4], "dtype": "float64"}, 0.1, normal_radius=0.2)
+    add(e, P, Q, [EYE], 0.0, normal_radius=0.2)                          # two wrong: init before the distance
+    add(e, P, Q, None, 0.0, normal_radius=0.2)
+    add(e, P, Q, None, 0.1, src_normals=M64, tgt_normals=M64)
+    add(e, P, Q, None, 0.1, epsilon=0.0)                                 # two wrong: epsilon before the per-side rule
+    add(e, P, Q, EYE, 0.1, src_covariances=C5, tgt_normals=M64)          # valid
+    add(e, P, Q, {"zeros": [4, 4], "dtype": "float64"}, 0.1, normal_radius=0.2)              # valid
+
+    I5, I4 = {"zeros": [5], "dtype": "float64"}, {"zeros": [4], "dtype": "float64"}
+    e = "registration.colored_icp_batch"
+    add(e, [P], [Q, Q], [N64], [M64], None, 0.1, normal_radius=0.2)
+    add(e, [], [Q], [], [], None, 0.1, normal_radius=0.2)                # two wrong: lengths before "no pairs"
+    add(e, [], [], [], [], None, 0.1, normal_radius=0.2)
+    for bad in (-0.1, 1.5, NAN):
+        add(e, [P], [Q], [N64], [M64], None, 0.1, lambda_geometric=bad, normal_radius=0.2)
+    add(e, [P], [Q], [N64], [M64], None, 0.1, lambda_geometric=2.0)      # two wrong: lambda before the normals rule
+    add(e, [P], [Q], [N64], [M64], None, 0.1)
+    add(e, [P], [Q], [N64], [M64], None, 0.1, normal_radius=0.0)
+    add(e, [P], [Q], [N64], [M64], None, 0.1, normal_radius=0.2, normal_max_nn=0)
+    add(e, [P], [Q], [N64], [M64], None, 0.1, normal_radius=0.2, tgt_normals=[M64])
+    add(e, [P], [Q], [N64], [M64], None, 0.1, tgt_normals=[])
+    add(e, [P], [Q], [N64], [M64], [EYE, EYE], 0.1, tgt_normals=[])      # two wrong: the normals rule before init
+    add(e, [P], [Q], [N64], [M64], [EYE, EYE], 0.1, normal_radius=0.2)
+    add(e, [P], [Q], [N64], [M64], EYE, 0.1, normal_radius=0.2)
+    add(e, [P], [Q], [N64], [M64], {"zeros": [1, 4, 3], "dtype": "float64"}, 0.0, normal_radius=0.2)           # two wrong: init before the distance
+    for bad in (0.0, NAN, INF):
+        add(e, [P], [Q], [N64], [M64], None, bad, normal_radius=0.2)
+    for bad in (0.0, -1.0, NAN, INF):
+        add(e, [P], [Q], [N64], [M64], None, 0.1, normal_radius=0.2, gradient_radius=bad)
+    for bad in (0, 65):
+        add(e, [P], [Q], [N64], [M64], None, 0.1, normal_radius=0.2, gradient_max_nn=bad)
+    add(e, [P], [Q], [N64], [M64], None, 0.0, normal_radius=0.2, gradient_radius=0.0)        # two wrong: the distance before the gradient search
+    add(e, [P], [Q], [N64], [M64], None, 0.1, normal_radius=0.2, gradient_max_nn=0, max_iteration=0)           # two wrong: the gradient search before max_iteration
+    for bad in (0, (1 << 16) + 1):
+        add(e, [P], [Q], [N64], [M64], None, 0.1, normal_radius=0.2, max_iteration=bad)
+    add(e, [P], [Q], [N64], [M64], None, 0.1, normal_radius=0.2, relative_fitness=-1.0)
+    add(e, [P], [Q], [N64], [M64], None, 0.1, normal_radius=0.2, relative_rmse=NAN)
+    add(e, [Z(5, 2)], [Q], [N64], [M64], None, 0.1, normal_radius=0.2, relative_rmse=-1.0)   # two wrong: the bounds before the clouds
+    add(e, [Z(5, 2)], [Q], [N64], [M64], None, 0.1, normal_radius=0.2)
+    add(e, [P], [Z(4, 4)], [N64], [M64], None, 0.1, normal_radius=0.2)
+    add(e, [Z(5, 2)], [Z(4, 4)], [N64], [M64], None, 0.1, normal_radius=0.2)                 # two wrong: the source before the target
+    add(e, [P], [Q], [N64, N64], [M64], None, 0.1, normal_radius=0.2)
+    add(e, [P], [Q], [N64], [], None, 0.1, normal_radius=0.2)
+    add(e, [P], [Q], [Z(5, 2, "float64")], [M64], None, 0.1, normal_radius=0.2)
+    add(e, [P], [Q], [M64], [M64], None, 0.1, normal_radius=0.2)
+    add(e, [P], [Q], [I4], [I4], None, 0.1, normal_radius=0.2)
+    add(e, [P], [Q], [N64], [N64], None, 0.1, normal_radius=0.2)
+    add(e, [P], [Q], [I5], [{"zeros": [4, 1, 1], "dtype": "float64"}], None, 0.1, normal_radius=0.2)
+    add(e, [P], [Q], [M64], [N64], None, 0.1, normal_radius=0.2)         # two wrong: the source colours before the target colours
+    add(e, [P], [Q], [N64], [N64], None, 0.1, tgt_normals=[N64])         # two wrong: the colours before the normals' rows
+    add(e, [P], [Q], [N64], [M64], None, 0.1, tgt_normals=[Z(4, 2, "float64")])
+    add(e, [P], [Q], [N64], [M64], None, 0.1, tgt_normals=[N64])
+    add(e, [S(BIG, 3), S(BIG, 3)], [Q, Q], [S(BIG, 3), S(BIG)], [M64, I4], None, 0.1, normal_radius=0.2)
+    add(e, [P, P], [S(BIG, 3), S(BIG, 3)], [N64, I5], [S(BIG), S(BIG, 3)], None, 0.1, normal_radius=0.2)
+    add(e, [P, Z(0)], [Q, Q], [N64, Z(0, 3, "float64")], [M64, I4], None, 0.1, normal_radius=0.2, max_iteration=3, trace=True,
+        pairs_per_call=1)                                                # valid
+    add(e, [P], [Q], [I5], [M64], [EYE], 0.1, lambda_geometric=1.0, tgt_normals=[M64], gradient_radius=0.3)     # valid
+    add(e, [P], [Z(0)], [N64], [{"zeros": [0], "dtype": "float64"}], None, 0.1, normal_radius=0.2)              # valid
+
+    e = "registration.colored_icp"
+    add(e, P, Q, N64, M64, {"zeros": [3, 4], "dtype": "float64"}, 0.1, normal_radius=0.2)
+    add(e, P, Q, N64, M64, [EYE], 0.0, normal_radius=0.2)                # two wrong: init before the distance
+    add(e, P, Q, N64, M64, None, 0.0, normal_radius=0.2)
+    add(e, P, Q, N64, M64, None, 0.1, tgt_normals=N64)
+    add(e, P, Q, I5, I4, EYE, 0.1, tgt_normals=M64)                      # valid
+    add(e, P, Q, N64, M64, {"zeros": [4, 4], "dtype": "float64"}, 0.1, normal_radius=0.2)    # valid
+
+    e = "registration.color_gradients_batch"
+    add(e, [], [], [], 0.2)
+    for bad in (0.0, -1.0, NAN, INF):
+        add(e, [P], [N64], [N64], bad)
+    for bad in (0, 65):
+        add(e, [P], [N64], [N64], 0.2, bad)
+    add(e, [P], [N64], [N64], 0.0, 0)                                    # two wrong: radius before max_nn
+    add(e, [Z(5, 2)], [N64], [N64], 0.0)                                 # two wrong: radius before the cloud
+    add(e, [Z(5, 2)], [N64], [N64], 0.2)
+    add(e, [P, {"zeros": [5]}], [N64, N64], [N64, N64], 0.2)
+    add(e, [P], [N64, N64], [N64], 0.2)
+    add(e, [P], [], [N64], 0.2)
+    add(e, [P], [Z(5, 2, "float64")], [N64], 0.2)
+    add(e, [P], [M64], [N64], 0.2)
+    add(e, [P], [I4], [N64], 0.2)
+    add(e, [P], [M64], [N64, N64], 0.2)                                  # two wrong: the colours before the normals
+    add(e, [P], [N64], [N64, N64], 0.2)
+    add(e, [P], [N64], [Z(5, 2, "float64")], 0.2)
+    add(e, [P], [I5], [M64], 0.2)
+    add(e, [S(BIG, 3), S(BIG, 3)], [S(BIG, 3), S(BIG)], [S(BIG, 3), S(BIG, 3)], 0.2)
+    add(e, [S(BIG, 3), S(BIG, 3)], [S(BIG, 3), S(BIG)], [S(BIG, 3), S(BIG, 3)], 0.2, pairs_per_call=1)         # valid sizes: one cloud per call
+    add(e, [P, Z(0)], [N64, {"zeros": [0], "dtype": "float64"}], [N64, Z(0, 3, "float64")], 0.2, trace=True)    # valid
+    add(e, [P, P], [I5, N64], [N64, N64], 0.2, 20, pairs_per_call=1)     # valid
+
+    e = "registration.color_gradients"
+    add(e, P, N64, N64, 0.0)
+    add(e, P, M64, N64, 0.2)
+    add(e, P, I5, M64, 0.2)
+    add(e, Z(5, 2), N64, N64, 0.2, 0)                                    # two wrong: max_nn before the cloud
+    add(e, P, I5, N64, 0.2, trace=True)                                  # valid
+
+    e = "registration.covariances_from_normals"
+    for bad in (0.0, -1e-3, 1.5, NAN):
+        add(e, N64, bad)
+    add(e, Z(5, 2, "float64"), 0.0)                                      # two wrong: epsilon before the shape
+    add(e, Z(5, 2, "float64"))
+    add(e, {"zeros": [5], "dtype": "float64"})
+    add(e, {"zeros": [5, 3, 3], "dtype": "float64"})
+    add(e, N64)                                                          # valid
+    add(e, Z(0, 3, "float64"), 1.0)                                      # valid
+
     e = "registration.inlier_ratio_batch"
     add(e, [P], [Q], [F], [G], [ROT], [])
     add(e, [], [], [], [], [], [ROT])                                    # two wrong: lengths before "no pairs"

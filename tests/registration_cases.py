@@ -34,9 +34,15 @@ def _poses(rng, n):
     return out
 
 
+def _spd(rng, n):
+    """n symmetric positive-definite 3 x 3 matrices, float64 [n,3,3]: A A^T + 0.01 I."""
+    a = rng.uniform(-0.3, 0.3, (n, 3, 3))
+    return a @ a.transpose(0, 2, 1) + 0.01 * np.eye(3)
+
+
 def inputs(sizes=SIZES, seed=20):
     """Host arrays for every case: clouds in the unit cube (the target of a pair repeats source rows where it can, so ICP and the
-    inlier counts have something to find), descriptors of width 32 and 33, normals, viewpoints, starts, poses, scores."""
+    inlier counts have something to find), descriptors of width 32 and 33, normals, viewpoints, starts, poses, scores, colours, covariances."""
     rng = np.random.RandomState(seed)
     d = {"src": [], "tgt": [], "ns": [n for n, _ in sizes], "ms": [m for _, m in sizes]}
     for n, m in sizes:
@@ -58,6 +64,13 @@ def inputs(sizes=SIZES, seed=20):
     d["trans"] = np.ascontiguousarray(d["gt"][:, :3, 3])
     d["scores"] = [rng.rand(n).astype(np.float32) for n in d["ns"]]
     d["directions"] = _unit(rng.randn(len(sizes), 3))
+    # (drawn after everything above, which so keeps its values) colours as RGB and as intensities, SPD covariances
+    d["src_rgb"] = [rng.rand(n, 3) for n in d["ns"]]
+    d["tgt_rgb"] = [rng.rand(m, 3) for m in d["ms"]]
+    d["src_gray"] = [rng.rand(n) for n in d["ns"]]
+    d["tgt_gray"] = [rng.rand(m) for m in d["ms"]]
+    d["src_cov"] = [_spd(rng, n) for n in d["ns"]]
+    d["tgt_cov"] = [_spd(rng, m) for m in d["ms"]]
     return d
 
 
@@ -117,6 +130,29 @@ def cases(form, dev):
                 Q("src"), Q("tgt"), None, 0.1, normal_radius=0.3, normal_max_nn=20, **plane)),
             ("refine_batch/plane_estimated_trace" + tag, lambda Q=Q: REG.refine_batch(
                 Q("src"), Q("tgt"), Q("init"), 0.1, normal_radius=0.3, trace=True, **plane)),
+            ("generalized_icp_batch/covariances" + tag, lambda Q=Q: REG.generalized_icp_batch(
+                Q("src"), Q("tgt"), Q("init"), 0.1, src_covariances=Q("src_cov"), tgt_covariances=Q("tgt_cov"), **icp)),
+            ("generalized_icp_batch/normals" + tag, lambda Q=Q: REG.generalized_icp_batch(
+                Q("src"), Q("tgt"), None, 0.1, src_normals=Q("src_normals"), tgt_normals=Q("tgt_normals"), **icp)),
+            ("generalized_icp_batch/estimated" + tag, lambda Q=Q: REG.generalized_icp_batch(
+                Q("src"), Q("tgt"), None, 0.1, normal_radius=0.3, normal_max_nn=20, **icp)),
+            ("generalized_icp_batch/one_side_estimated" + tag, lambda Q=Q: REG.generalized_icp_batch(
+                Q("src"), Q("tgt"), Q("init"), 0.1, epsilon=0.01, src_covariances=Q("src_cov"), normal_radius=0.3, **icp)),
+            ("generalized_icp_batch/trace" + tag, lambda Q=Q: REG.generalized_icp_batch(
+                Q("src"), Q("tgt"), Q("init"), 0.1, src_normals=Q("src_normals"), normal_radius=0.3, trace=True, **icp)),
+            ("colored_icp_batch/normals_rgb" + tag, lambda Q=Q: REG.colored_icp_batch(
+                Q("src"), Q("tgt"), Q("src_rgb"), Q("tgt_rgb"), Q("init"), 0.1, tgt_normals=Q("tgt_normals"), **icp)),
+            ("colored_icp_batch/estimated_gray" + tag, lambda Q=Q: REG.colored_icp_batch(
+                Q("src"), Q("tgt"), Q("src_gray"), Q("tgt_gray"), None, 0.1, normal_radius=0.3, normal_max_nn=20, **icp)),
+            ("colored_icp_batch/gradient_radius" + tag, lambda Q=Q: REG.colored_icp_batch(
+                Q("src"), Q("tgt"), Q("src_rgb"), Q("tgt_gray"), None, 0.1, lambda_geometric=0.5, tgt_normals=Q("tgt_normals"),
+                gradient_radius=0.3, gradient_max_nn=20, **icp)),
+            ("colored_icp_batch/trace" + tag, lambda Q=Q: REG.colored_icp_batch(
+                Q("src"), Q("tgt"), Q("src_rgb"), Q("tgt_rgb"), Q("init"), 0.1, normal_radius=0.3, trace=True, **icp)),
+            ("color_gradients_batch" + tag, lambda Q=Q: REG.color_gradients_batch(
+                Q("src"), Q("src_rgb"), Q("src_normals"), 0.3, 20, pairs_per_call=PER_CALL)),
+            ("color_gradients_batch/trace" + tag, lambda Q=Q: REG.color_gradients_batch(
+                Q("src"), Q("src_gray"), Q("src_normals"), 0.3, pairs_per_call=PER_CALL, trace=True)),
             ("voxel_down_sample_batch" + tag, lambda Q=Q: kitti.voxel_down_sample_batch(Q("src") + Q("tgt"), 0.2, with_index=True)),
         ]
     out.append(("refine_batch/all_in_one_call", lambda: REG.refine_batch(P("src"), P("tgt"), None, 0.1, max_iteration=3)))
@@ -127,6 +163,15 @@ def cases(form, dev):
                                                                    viewpoint=place(d["viewpoints"][one], form, dev))),
         ("refine", lambda: REG.refine(P("src")[one], P("tgt")[one], place(d["init"][one], form, dev), 0.1, max_iteration=3,
                                       estimation="point_to_plane", tgt_normals=P("tgt_normals")[one])),
+        ("generalized_icp", lambda: REG.generalized_icp(P("src")[one], P("tgt")[one], place(d["init"][one], form, dev), 0.1,
+                                                        max_iteration=3, src_covariances=P("src_cov")[one],
+                                                        tgt_normals=P("tgt_normals")[one])),
+        ("colored_icp", lambda: REG.colored_icp(P("src")[one], P("tgt")[one], P("src_rgb")[one], P("tgt_gray")[one],
+                                                place(d["init"][one], form, dev), 0.1, max_iteration=3,
+                                                tgt_normals=P("tgt_normals")[one])),
+        ("color_gradients", lambda: REG.color_gradients(P("src")[one], P("src_rgb")[one], P("src_normals")[one], 0.3, trace=True)),
+        ("covariances_from_normals", lambda: REG.covariances_from_normals(P("src_normals")[one], 0.01)),
+        ("covariances_from_normals/empty", lambda: REG.covariances_from_normals(place(e["src_normals"][0], form, dev))),
         ("register", lambda: REG.register(P("src")[one], P("tgt")[one], P("fs32")[one], P("ft32")[one], max_iteration=64,
                                           max_validation=8, seed=9, trace=True)),
         ("sample_batch", lambda: REG.sample_batch(P("scores"), 50, list(range(B)))),

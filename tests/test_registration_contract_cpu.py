@@ -1,7 +1,8 @@
 """The argument contract of the ragged-batch entries (registration, tester, modelnet, kitti, modelnet_prep): for every row of
 tests/golden/registration_errors.json -- a call with small literal arguments -- the exception type and the exact message.
 The file was recorded by scripts/record_registration_contract.py at the commit before the marshalling moved to
-pcrcg_amd/ragged.py, so it pins the messages and the ORDER of the host checks (the rows with two things wrong), and, with one
+pcrcg_amd/ragged.py -- the rows of generalized and colored ICP, the colour gradients and covariances_from_normals at the commit
+before the ICP entries were folded onto one driver --, so it pins the messages and the ORDER of the host checks (the rows with two things wrong), and, with one
 valid call per entry, that nothing past the device lookup runs without a device."""
 import importlib.util
 import json
@@ -21,7 +22,10 @@ with open(os.path.join(GOLDEN, "registration_errors.json")) as f:
 
 ENTRIES = ("registration.feature_match_batch", "registration.register_batch", "registration.estimate_normals_batch",
            "registration.estimate_normals", "registration.compute_fpfh_feature_batch", "registration.compute_fpfh_feature",
-           "registration.refine_batch", "registration.refine", "registration.inlier_ratio_batch", "registration.sample_batch",
+           "registration.refine_batch", "registration.refine", "registration.generalized_icp_batch", "registration.generalized_icp",
+           "registration.colored_icp_batch", "registration.colored_icp", "registration.color_gradients_batch",
+           "registration.color_gradients", "registration.covariances_from_normals", "registration.inlier_ratio_batch",
+           "registration.sample_batch",
            "tester.probabilistic_sample_batch", "modelnet.chamfer_batch", "kitti.voxel_down_sample_batch",
            "modelnet_prep.crop_batch")
 
