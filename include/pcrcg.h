@@ -61,7 +61,9 @@ const char* pcrcg_last_error(void);
  *   and the interest-point sampler (pcrcg_weighted_sample_ws_bytes, pcrcg_weighted_sample_batch), added after those,
  *   and the voxel down-sampling of raw scans (pcrcg_voxel_down_sample_ws_bytes, pcrcg_voxel_down_sample_batch), added after
  *   that, and the decoded-frame conversion (pcrcg_prepare_frames), and the ModelNet pair preparation (pcrcg_modelnet_crop,
- *   pcrcg_modelnet_assemble), added after those. */
+ *   pcrcg_modelnet_assemble), added after those, and the robust ICP entries (pcrcg_icp_plane_robust_batch_ws_bytes,
+ *   pcrcg_icp_plane_robust_batch, pcrcg_colored_icp_robust_batch_ws_bytes, pcrcg_colored_icp_robust_batch), added under
+ *   version 4, additive. */
 #define PCRCG_ABI_VERSION 4
 int pcrcg_abi_version(void);
 
@@ -1231,6 +1233,59 @@ int pcrcg_colored_icp_batch(const float* src, const int* src_off, int n_total, i
                             double relative_fitness, double relative_rmse, double lambda_geometric, const double* tgt_rec,
                             const double* src_intensity, double* out_transform, double* out_stats,
                             const pcrcg_icp_trace_ex* trace, void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Robust kernels
+ * Point-to-plane and colored ICP under a robust loss kernel (csrc/icp.hip, csrc/robust_kernel.h, csrc/colored_terms.h; added
+ * under ABI version 4, which it does not change) -- open3d's RobustKernel passed to TransformationEstimationPointToPlane and
+ * TransformationEstimationForColoredICP: every row of the Gauss-Newton system is multiplied with a weight of its own
+ * residual, so that the correspondences inside the gate which are not true matches (another surface, a moving object) pull
+ * the step less than the true ones do.  This comment is the definition, tests/robust_ref.py restates it in numpy.
+ *
+ *   kernel (the kind) and kernel_k (its scale k, in the residual's unit) are shared by all pairs of a call.  The weight of a
+ *   residual r, in float64, basic IEEE operations in the order written (csrc/robust_kernel.h robust_weight):
+ *     0 L2      1.0
+ *     1 L1      1.0 / max(|r|, 1e-12)
+ *     2 Huber   k / max(|r|, k)
+ *     3 Cauchy  1.0 / (1.0 + (r / k) (r / k))
+ *     4 GM      k / ((k + r r) (k + r r))
+ *     5 Tukey   t = min(1.0, |r| / k); u = 1.0 - t t; u u
+ *   max and min keep a NaN: a residual that is not a number gives a weight that is not a number (L2: 1.0), an infinite one 0.
+ *   The L1 floor (kL1Floor = 1e-12) is the one departure from open3d, whose L1 weight is 1 / |r|: infinite for a
+ *   correspondence that lies exactly on its target's plane, where it turns the pair's system into NaN.
+ *
+ * pcrcg_icp_plane_robust_batch: pcrcg_icp_batch_ex(estimation = 1) -- every argument, rule and output -- with the terms of a
+ *   correspondence, res = ((p - q) . n) and J = [p x n | n] as there, w = weight(res):
+ *     w (J_r J_c) over the upper triangle row by row (21), then w (-(J_r res)) (6).
+ *   The weight multiplies the finished term of the plain estimator: kernel 0 gives pcrcg_icp_batch_ex's bits.
+ * pcrcg_colored_icp_robust_batch: pcrcg_colored_icp_batch -- every argument, rule and output -- with the two rows of a
+ *   correspondence weighted separately on their scaled residuals, as open3d does, wg = weight(rg), wi = weight(ri):
+ *     wg (JG_r JG_c) + wi (JI_r JI_c) over the upper triangle (21), then -(wg (JG_r rg) + wi (JI_r ri)) (6).
+ *   Kernel 0 gives pcrcg_colored_icp_batch's bits.
+ * What stays unweighted, in both: the correspondence search and the gate, the count, the d2 sum, fitness and the Euclidean
+ *   rmse and so the convergence test; the count < 6 (colored: count < 3) rule; colored ICP's finiteness test of b; the
+ *   order of the sums; the LDL^T solve with its 1e-12 pivot rule; the delta.  A system that the weights make singular --
+ *   Tukey with every |r| >= k: all weights 0 -- or not finite is refused by the solve and the pair stops with T kept, as any
+ *   degenerate pair does.
+ *   trace: pcrcg_icp_trace_ex's members; sums27 holds the WEIGHTED sums.
+ *   Workspace: the *_ws_bytes of the plain entries' values.  Bad arguments: the plain entry's, a kernel outside 0..5, and for
+ *   kernels 2..5 a kernel_k that is not positive and finite (NaN included; kernels 0 and 1 do not read kernel_k), give
+ *   PCRCG_EBADARG under the robust entry's name; a short workspace PCRCG_EWORKSPACE, before anything launches.
+ *   Generalized ICP has no robust entry: open3d weights the three rows of M^(-1/2) d separately, which takes the inverse
+ *   square root of the 3 x 3 metric per correspondence -- another term computation than csrc/gicp_terms.h's J0^T W J0. */
+size_t pcrcg_icp_plane_robust_batch_ws_bytes(int B, int n_total, int m_total, int max_iteration);
+int pcrcg_icp_plane_robust_batch(const float* src, const int* src_off, int n_total, int n_max, const int* tgt_off, int m_total,
+                                 const void* grid, const double* init, int B, double max_correspondence_distance,
+                                 int max_iteration, double relative_fitness, double relative_rmse, const double* tgt_normals,
+                                 int kernel, double kernel_k, double* out_transform, double* out_stats,
+                                 const pcrcg_icp_trace_ex* trace, void* ws, size_t ws_bytes, void* stream);
+size_t pcrcg_colored_icp_robust_batch_ws_bytes(int B, int n_total, int m_total, int max_iteration);
+int pcrcg_colored_icp_robust_batch(const float* src, const int* src_off, int n_total, int n_max, const int* tgt_off, int m_total,
+                                   const void* grid, const double* init, int B, double max_correspondence_distance,
+                                   int max_iteration, double relative_fitness, double relative_rmse, double lambda_geometric,
+                                   const double* tgt_rec, const double* src_intensity, int kernel, double kernel_k,
+                                   double* out_transform, double* out_stats, const pcrcg_icp_trace_ex* trace, void* ws,
+                                   size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Fast global registration

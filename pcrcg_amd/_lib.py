@@ -22,7 +22,7 @@ ABI_VERSION = 4      # PCRCG_ABI_VERSION of the include/pcrcg.h these signatures
 
 c_int, c_float, c_void_p, c_size_t = ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t
 
-# What the four ICP entries share: clouds, offsets, totals, grid, start, B, distance, cap, bounds | an estimator's own
+# What the ICP entries share: clouds, offsets, totals, grid, start, B, distance, cap, bounds | an estimator's own
 # arguments stand here | outputs, trace, workspace, stream
 _ICP_HEAD = [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, ctypes.c_double, c_int,
              ctypes.c_double, ctypes.c_double]
@@ -187,6 +187,12 @@ SIGNATURES = {
                                             c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "pcrcg_colored_icp_batch_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "pcrcg_colored_icp_batch": (c_int, _ICP_HEAD + [ctypes.c_double, c_void_p, c_void_p] + _ICP_TAIL),
+    # robust kernels on point-to-plane and colored ICP (registration.RobustKernel; robust_refine_batch, robust_colored_icp_batch)
+    "pcrcg_icp_plane_robust_batch_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "pcrcg_icp_plane_robust_batch": (c_int, _ICP_HEAD + [c_void_p, c_int, ctypes.c_double] + _ICP_TAIL),
+    "pcrcg_colored_icp_robust_batch_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "pcrcg_colored_icp_robust_batch": (c_int, _ICP_HEAD + [ctypes.c_double, c_void_p, c_void_p, c_int, ctypes.c_double]
+                                       + _ICP_TAIL),
     # fast global registration (registration.mutual_match_batch, fast_global_registration_batch)
     "pcrcg_mutual_match_batch_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
     "pcrcg_mutual_match_batch": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int,

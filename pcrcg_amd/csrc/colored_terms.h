@@ -1,9 +1,11 @@
 // colored_terms.h -- the per-point and per-correspondence arithmetic of colored ICP (colored.hip; icp.hip, EST = 3;
 // include/pcrcg.h "Colored ICP"): one row of a target point's colour-gradient fit, the fit's last row, and the 27 terms one
-// correspondence adds to the 6 x 6 Gauss-Newton system of the joint colour / geometry objective.
+// correspondence adds to the 6 x 6 Gauss-Newton system of the joint colour / geometry objective, plain or under a robust kernel.
 // Plain C++ with no HIP types (host and device): both kernels are compiled with -ffp-contract=off, and
 // tests/host/colored_terms_driver.cpp compiles this text for the host, so every operation below rounds where it is written.
 #pragma once
+
+#include "robust_kernel.h"
 
 #ifndef PCRCG_HD
 #if defined(__HIPCC__) || defined(__CUDACC__)
@@ -57,8 +59,13 @@ PCRCG_HD inline void colored_gradient_last_row(const double* nt, int nn, double*
 //   pproj = p - rG n; I0 = (((g . (pproj - q))) + It); gn = ((g . n)); gM = -(g - gn n);
 //   JI = sp [p x gM | gM]; ri = sp (Is - I0).
 // Dot products are ((x + y) + z).  Nothing is tested: a value that is not finite gives terms that are not finite.
-PCRCG_HD inline void colored_terms(const double* p, const double* q, const double* rec, double Is, double sg, double sp,
-                                   double* out) {
+// ROBUST: each of the two rows carries the weight of its own scaled residual, wg = robust_weight(kind, k, rg) and
+// wi = robust_weight(kind, k, ri) (robust_kernel.h), as open3d weights them: the terms are
+// wg (JG_r JG_c) + wi (JI_r JI_c) and -(wg (JG_r rg) + wi (JI_r ri)), in the order of operations of the plain terms, so kind 0
+// (both weights 1.0) gives their bits.
+template <bool ROBUST>
+PCRCG_HD inline void colored_terms_of(const double* p, const double* q, const double* rec, double Is, double sg, double sp,
+                                      int kind, double k, double* out) {
     const double px = p[0], py = p[1], pz = p[2];
     const double n0 = rec[0], n1 = rec[1], n2 = rec[2];
     const double g0 = rec[3], g1 = rec[4], g2 = rec[5];
@@ -72,9 +79,26 @@ PCRCG_HD inline void colored_terms(const double* p, const double* q, const doubl
     const double JG[6] = {sg * (py * n2 - pz * n1), sg * (pz * n0 - px * n2), sg * (px * n1 - py * n0), sg * n0, sg * n1, sg * n2};
     const double JI[6] = {sp * (py * m2 - pz * m1), sp * (pz * m0 - px * m2), sp * (px * m1 - py * m0), sp * m0, sp * m1, sp * m2};
     int e = 0;
-    for (int r = 0; r < 6; ++r)
-        for (int c = r; c < 6; ++c) out[e++] = JG[r] * JG[c] + JI[r] * JI[c];
-    for (int r = 0; r < 6; ++r) out[21 + r] = -(JG[r] * rg + JI[r] * ri);
+    if constexpr (ROBUST) {
+        const double wg = robust_weight(kind, k, rg), wi = robust_weight(kind, k, ri);
+        for (int r = 0; r < 6; ++r)
+            for (int c = r; c < 6; ++c) out[e++] = wg * (JG[r] * JG[c]) + wi * (JI[r] * JI[c]);
+        for (int r = 0; r < 6; ++r) out[21 + r] = -(wg * (JG[r] * rg) + wi * (JI[r] * ri));
+    } else {
+        for (int r = 0; r < 6; ++r)
+            for (int c = r; c < 6; ++c) out[e++] = JG[r] * JG[c] + JI[r] * JI[c];
+        for (int r = 0; r < 6; ++r) out[21 + r] = -(JG[r] * rg + JI[r] * ri);
+    }
+}
+
+PCRCG_HD inline void colored_terms(const double* p, const double* q, const double* rec, double Is, double sg, double sp,
+                                   double* out) {
+    colored_terms_of<false>(p, q, rec, Is, sg, sp, 0, 0.0, out);
+}
+
+PCRCG_HD inline void colored_terms_robust(const double* p, const double* q, const double* rec, double Is, double sg, double sp,
+                                          int kind, double k, double* out) {
+    colored_terms_of<true>(p, q, rec, Is, sg, sp, kind, k, out);
 }
 
 }  // namespace

@@ -27,6 +27,12 @@
 // packed record (normal, colour gradient, intensity: colored.hip) and its source's intensity, the 27 terms of the joint
 // colour / geometry objective come from colored_terms.h, and the update is point-to-plane's solve and delta again.
 //
+// pcrcg_icp_plane_robust_batch and pcrcg_colored_icp_robust_batch put a robust loss kernel (robust_kernel.h: open3d's
+// RobustKernel, a kind and a scale, uniform over the call) on EST = 1 and EST = 3: a second instantiation of the evaluation
+// (ROBUST) multiplies every correspondence's terms with the weight of its residual where they are formed -- plane_terms_robust,
+// colored_terms_robust.  Everything else is the plain estimator's: the search, the count, the d2 sum, the reductions, and
+// k_icp_update<1> / <3>, which see only sums.
+//
 // Host side: every extern "C" entry fills one IcpCall -- the arguments all entries share, its estimator, and that
 // estimator's own inputs by name -- and hands it to icp_run, the one place for the argument rules, the workspace carve, the
 // fill of the kernels' IcpArgs and the dispatch to icp_enqueue<EST>.  A further estimator is one more entry that fills an
@@ -42,6 +48,7 @@
 #include "common.h"
 #include "gicp_terms.h"
 #include "kabsch.h"
+#include "robust_kernel.h"
 #include "smallsolve.h"
 
 namespace pcrcg {
@@ -90,6 +97,8 @@ struct IcpArgs {
     double sg, sp;        // ... and sqrt(lambda_geometric), sqrt(1 - lambda_geometric)
     const double* src_cov;// [n_total, 6] generalized: the covariances of the unmoved sources ...
     const double* tgt_cov;// [m_total, 6] ... and of the targets
+    int kernel;           // the robust evaluation (point-to-plane, colored): the kind of robust_kernel.h ...
+    double kernel_k;      // ... and its scale
 };
 
 __device__ inline long first_slot(const IcpArgs& a, int p) { return (long)(a.src_off[p] / kIcpThreads) + p; }
@@ -105,8 +114,8 @@ __global__ void __launch_bounds__(256) k_icp_init(IcpArgs a, int B) {
     st->pad = 0;
 }
 
-// Evaluate(T_it) of every live pair; grid (row blocks, pair)
-template <int EST>
+// Evaluate(T_it) of every live pair; grid (row blocks, pair).  ROBUST (EST 1 and 3): the terms under the call's kernel
+template <int EST, bool ROBUST = false>
 __global__ void __launch_bounds__(kIcpThreads) k_icp_evaluate(IcpArgs a, GridView g, int it) {
     constexpr int kTerms = icp_terms<EST>();
     __shared__ double s_sum[kIcpWaves][kTerms];
@@ -196,7 +205,18 @@ __global__ void __launch_bounds__(kIcpThreads) k_icp_evaluate(IcpArgs a, GridVie
             const double* tr = a.tgt_rec + 8 * (long)bj;
 #pragma unroll
             for (int e = 0; e < 8; ++e) rec[e] = tr[e];
-            colored_terms(P, Q, rec, a.src_int[i0 + i], a.sg, a.sp, v + 1);
+            if constexpr (ROBUST) colored_terms_robust(P, Q, rec, a.src_int[i0 + i], a.sg, a.sp, a.kernel, a.kernel_k, v + 1);
+            else colored_terms(P, Q, rec, a.src_int[i0 + i], a.sg, a.sp, v + 1);
+        } else {
+#pragma unroll
+            for (int e = 1; e < kTerms; ++e) v[e] = 0.0;
+        }
+    } else if constexpr (ROBUST) {
+        // point-to-plane under the kernel: the terms below, each times the weight of the residual (robust_kernel.h)
+        if (hit) {
+            const double* nr = a.tgt_nrm + 3 * (long)bj;
+            const double N[3] = {nr[0], nr[1], nr[2]};
+            plane_terms_robust(P, Q, N, a.kernel, a.kernel_k, v + 1);
         } else {
 #pragma unroll
             for (int e = 1; e < kTerms; ++e) v[e] = 0.0;
@@ -381,13 +401,13 @@ IcpWs carve_icp(Carver& cv, int B, int n_total, int terms) {
 }
 
 // the launches of any estimator: init, then max_iteration + 1 evaluate / update pairs
-template <int EST>
+template <int EST, bool ROBUST = false>
 int icp_enqueue(const IcpArgs& a, const GridView& g, int B, hipStream_t st) {
     hipLaunchKernelGGL(k_icp_init, dim3((B + 255) / 256), dim3(256), 0, st, a, B);
     PCRCG_CHECK_LAUNCH();
     const dim3 eval_grid(a.n_max > 0 ? (a.n_max + kIcpThreads - 1) / kIcpThreads : 1, B);
     for (int it = 0; it <= a.max_iteration; ++it) {
-        hipLaunchKernelGGL(k_icp_evaluate<EST>, eval_grid, dim3(kIcpThreads), 0, st, a, g, it);
+        hipLaunchKernelGGL((k_icp_evaluate<EST, ROBUST>), eval_grid, dim3(kIcpThreads), 0, st, a, g, it);
         hipLaunchKernelGGL(k_icp_update<EST>, dim3(B), dim3(kWave), 0, st, a, it);
     }
     PCRCG_CHECK_LAUNCH();
@@ -418,6 +438,9 @@ struct IcpCall {
     const double *src_cov = nullptr, *tgt_cov = nullptr;            // generalized
     const double *tgt_rec = nullptr, *src_intensity = nullptr;      // colored
     double lambda_geometric = 0.0;
+    bool robust = false;                                            // the robust entries: point-to-plane or colored under ...
+    int kernel = kRobustL2;                                         // ... a kind of robust_kernel.h ...
+    double kernel_k = 0.0;                                          // ... and its scale (kinds 2..5)
 };
 
 // Every entry's *_ws_bytes: 0 for sizes out of range
@@ -455,6 +478,8 @@ int icp_run(const char* who, const IcpCall& c) {
         ICP_CHECK_ARG(c.n_total == 0 || c.src_intensity);
         ICP_CHECK_ARG(c.m_total == 0 || c.tgt_rec);
     }
+    ICP_CHECK_ARG(c.kernel >= 0 && c.kernel < kRobustKinds);
+    ICP_CHECK_ARG(c.kernel < kRobustHuber || (c.kernel_k > 0.0 && c.kernel_k <= 1.79769313486231570815e308));  // (false for a NaN)
     const bool point = c.estimation == kEstPoint;
     Carver cv(c.ws, c.ws_bytes);
     IcpWs w = carve_icp(cv, c.B, c.n_total, point ? kIcpTerms : kIcpPlaneTerms);
@@ -480,7 +505,10 @@ int icp_run(const char* who, const IcpCall& c) {
     a.sg = colored ? sqrt(c.lambda_geometric) : 0.0;
     a.sp = colored ? sqrt(1.0 - c.lambda_geometric) : 0.0;
     a.src_cov = c.src_cov; a.tgt_cov = c.tgt_cov;
+    a.kernel = c.kernel; a.kernel_k = c.kernel_k;
     const hipStream_t st = as_stream(c.stream);
+    if (c.robust)               // (after the plain estimators' kernels in the code object)
+        return c.estimation == kEstColored ? icp_enqueue<kEstColored, true>(a, g, c.B, st) : icp_enqueue<kEstPlane, true>(a, g, c.B, st);
     switch (c.estimation) {     // (the cases' order is the kernels' order in the code object: append)
     case kEstGeneralized: return icp_enqueue<kEstGeneralized>(a, g, c.B, st);
     case kEstColored: return icp_enqueue<kEstColored>(a, g, c.B, st);
@@ -572,6 +600,47 @@ int pcrcg_colored_icp_batch(const float* src, const int* src_off, int n_total, i
     c.lambda_geometric = lambda_geometric;
     c.tgt_rec = tgt_rec;
     c.src_intensity = src_intensity;
+    return icp_run(__func__, c);
+}
+
+size_t pcrcg_icp_plane_robust_batch_ws_bytes(int B, int n_total, int m_total, int max_iteration) {
+    return icp_ws_bytes(B, n_total, m_total, max_iteration, kIcpPlaneTerms);
+}
+
+int pcrcg_icp_plane_robust_batch(const float* src, const int* src_off, int n_total, int n_max, const int* tgt_off, int m_total,
+                                 const void* grid, const double* init, int B, double max_correspondence_distance,
+                                 int max_iteration, double relative_fitness, double relative_rmse, const double* tgt_normals,
+                                 int kernel, double kernel_k, double* out_transform, double* out_stats,
+                                 const pcrcg_icp_trace_ex* trace, void* ws, size_t ws_bytes, void* stream) {
+    IcpCall c = {src, src_off, n_total, n_max, tgt_off, m_total, grid, init, B, max_correspondence_distance, max_iteration,
+                 relative_fitness, relative_rmse, out_transform, out_stats, trace, ws, ws_bytes, stream};
+    c.estimation = kEstPlane;
+    c.tgt_normals = tgt_normals;
+    c.robust = true;
+    c.kernel = kernel;
+    c.kernel_k = kernel_k;
+    return icp_run(__func__, c);
+}
+
+size_t pcrcg_colored_icp_robust_batch_ws_bytes(int B, int n_total, int m_total, int max_iteration) {
+    return icp_ws_bytes(B, n_total, m_total, max_iteration, kIcpPlaneTerms);
+}
+
+int pcrcg_colored_icp_robust_batch(const float* src, const int* src_off, int n_total, int n_max, const int* tgt_off, int m_total,
+                                   const void* grid, const double* init, int B, double max_correspondence_distance,
+                                   int max_iteration, double relative_fitness, double relative_rmse, double lambda_geometric,
+                                   const double* tgt_rec, const double* src_intensity, int kernel, double kernel_k,
+                                   double* out_transform, double* out_stats, const pcrcg_icp_trace_ex* trace, void* ws,
+                                   size_t ws_bytes, void* stream) {
+    IcpCall c = {src, src_off, n_total, n_max, tgt_off, m_total, grid, init, B, max_correspondence_distance, max_iteration,
+                 relative_fitness, relative_rmse, out_transform, out_stats, trace, ws, ws_bytes, stream};
+    c.estimation = kEstColored;
+    c.lambda_geometric = lambda_geometric;
+    c.tgt_rec = tgt_rec;
+    c.src_intensity = src_intensity;
+    c.robust = true;
+    c.kernel = kernel;
+    c.kernel_k = kernel_k;
     return icp_run(__func__, c);
 }
 

@@ -18,6 +18,11 @@
   * `refine_batch`           -- ICP of many pairs in one set of launches (`BatchRefinementResult`), the local pass after
                                 RANSAC's global one: point-to-point, or point-to-plane on the targets' normals;
                                 `refine` is the same for one pair.
+  * `RobustKernel`           -- open3d's robust loss kernels (`L2Loss`, `L1Loss`, `HuberLoss`, `CauchyLoss`, `GMLoss`,
+                                `TukeyLoss`) for `robust_refine_batch` (point-to-plane) and `robust_colored_icp_batch`, and
+                                for `kernel=` of `refine` / `colored_icp`: targets of another surface inside the distance
+                                pull the step less.  `generalized_icp_batch` takes none: open3d's robust GICP weights the three rows
+                                of M^(-1/2) d, another term computation than this one's J0^T W J0.
   * `generalized_icp_batch`  -- Generalized ICP (Segal, Haehnel, Thrun 2009; open3d's registration_generalized_icp) of many
                                 pairs in one set of launches: refine_batch's loop with a 3 x 3 metric per correspondence
                                 from both clouds' covariances; `generalized_icp` is the same for one pair, and
@@ -56,7 +61,8 @@ checkers `_check_pairs`, `_check_start`, `_check_distance`, `_check_loop` and `_
 `_check_tgt_normal_rows`, which each entry calls in its own order between its own rules, and one driver, `_icp_batch`, for
 everything from the chunk list to the result -- workspace, output buffer, start, trace buffers, per chunk the uploads, the
 ICP cell grid and the library call, then the one read.  An estimator joins it with its entry's name and one per-chunk
-function that returns the arguments its entry takes between the bounds and the outputs, and what it adds to the trace.
+function that returns the arguments its entry takes between the bounds and the outputs, and what it adds to the trace.  A
+robust kernel is the same estimator under its robust entry's name, with the kind and the scale among those arguments.
 """
 import collections
 import ctypes
@@ -629,6 +635,66 @@ class _IcpTraceEx(ctypes.Structure):
 _ESTIMATIONS = {"point_to_point": 0, "point_to_plane": 1}
 _MAX_NORMAL_NN = 64   # include/pcrcg.h: one neighbour per lane
 
+_KERNEL_KINDS = ("L2", "L1", "Huber", "Cauchy", "GM", "Tukey")   # include/pcrcg.h "Robust kernels": the kind is the index
+
+
+class RobustKernel(collections.namedtuple("RobustKernel", "kind k")):
+    """open3d's RobustKernel for `robust_refine_batch`, `robust_colored_icp_batch` and kernel= of `refine` / `colored_icp`:
+    an immutable (kind, k) -- the kind 0..5 of include/pcrcg.h "Robust kernels" and its scale k, in the residual's unit.  Made
+    by L2Loss(), L1Loss(), HuberLoss(k), CauchyLoss(k), GMLoss(k), TukeyLoss(k), which check k: a positive finite number
+    (L2 and L1 have none and carry 1.0, which nothing reads)."""
+    __slots__ = ()
+
+    def __new__(cls, kind, k=1.0):
+        if isinstance(kind, bool) or not isinstance(kind, (int, np.integer)) or not 0 <= kind < len(_KERNEL_KINDS):
+            raise ValueError(f"RobustKernel: kind must be 0..{len(_KERNEL_KINDS) - 1} {_KERNEL_KINDS}, got {kind!r}")
+        try:
+            scale = float(k)
+        except (TypeError, ValueError):
+            raise ValueError(f"{_KERNEL_KINDS[kind]}Loss: k must be a positive finite number, got {k!r}") from None
+        if not 0.0 < scale < float("inf"):
+            raise ValueError(f"{_KERNEL_KINDS[kind]}Loss: k must be a positive finite number, got {k!r}")
+        return super().__new__(cls, int(kind), scale)
+
+    def __repr__(self):
+        return f"{_KERNEL_KINDS[self.kind]}Loss({'' if self.kind < 2 else repr(self.k)})"
+
+
+def L2Loss():
+    """The plain least squares as a kernel: every weight 1.0 (the robust entry then gives the plain entry's bits)."""
+    return RobustKernel(0)
+
+
+def L1Loss():
+    """weight 1 / max(|r|, 1e-12): open3d's L1Loss but for the floor, which keeps an exact zero residual finite."""
+    return RobustKernel(1)
+
+
+def HuberLoss(k):
+    """weight k / max(|r|, k)."""
+    return RobustKernel(2, k)
+
+
+def CauchyLoss(k):
+    """weight 1 / (1 + (r / k)^2)."""
+    return RobustKernel(3, k)
+
+
+def GMLoss(k):
+    """Geman-McClure: weight k / (k + r^2)^2."""
+    return RobustKernel(4, k)
+
+
+def TukeyLoss(k):
+    """weight (1 - min(1, |r| / k)^2)^2: zero from |r| = k on."""
+    return RobustKernel(5, k)
+
+
+def _check_kernel(who, kernel):
+    if kernel is not None and not isinstance(kernel, RobustKernel):
+        raise TypeError(f"{who}: kernel must be a RobustKernel (L2Loss(), L1Loss(), HuberLoss(k), CauchyLoss(k), GMLoss(k), "
+                        f"TukeyLoss(k)) or None, got {type(kernel).__name__}")
+
 
 class BatchRefinementResult:
     """Results of `refine_batch` for B pairs.  transformations: float64 [B,4,4] device tensor; matrices: the same as numpy
@@ -638,7 +704,8 @@ class BatchRefinementResult:
     [B, max_iteration + 1] of Evaluate(T_k), corr: per pair [max_iteration + 1, n_b] int32, the target of every source row
     or -1 (entries past a pair's last evaluation keep their fill: NaN / -1 / -2).  Point-to-plane adds sums27
     [B, max_iteration + 1, 27] (the upper triangle of sum J J^T, then -sum J r) and normals: per pair the [M_b,3] float64
-    target normals the updates read.  `generalized_icp_batch` returns the same class: sums27 holds the upper triangle of
+    target normals the updates read (under a robust kernel, sums27 holds the weighted sums).  `generalized_icp_batch` returns the
+    same class: sums27 holds the upper triangle of
     sum J0^T W J0, then -sum J0^T W d, and src_covariances / tgt_covariances (per pair [N_b,6] / [M_b,6] float64) stand where the
     normals do."""
 
@@ -967,8 +1034,32 @@ def refine_batch(src_pcds, tgt_pcds, init, max_correspondence_distance, *, max_i
     TransformationEstimationPointToPlane -- the same evaluation and convergence test, the update a Gauss-Newton step on
     the distances to the targets' tangent planes.  It reads the targets' normals: tgt_normals, a list of per-pair [M_b,3]
     arrays (their signs do not matter), or, without it, normal_radius (required then) and normal_max_nn: the normals are
-    estimated in the same call on the same stream (estimate_normals_batch's, viewpoint at the origin)."""
-    who = "refine_batch"
+    estimated in the same call on the same stream (estimate_normals_batch's, viewpoint at the origin).  Point-to-plane under a
+    robust loss kernel is robust_refine_batch."""
+    return _refine_batch("refine_batch", src_pcds, tgt_pcds, init, max_correspondence_distance, max_iteration, relative_fitness,
+                         relative_rmse, pairs_per_call, trace, estimation, tgt_normals, normal_radius, normal_max_nn, None)
+
+
+def robust_refine_batch(src_pcds, tgt_pcds, init, max_correspondence_distance, kernel, *, max_iteration=30, relative_fitness=1e-6,
+                        relative_rmse=1e-6, pairs_per_call=None, trace=False, tgt_normals=None, normal_radius=None,
+                        normal_max_nn=30):
+    """refine_batch(estimation="point_to_plane") under a robust loss kernel (pcrcg_icp_plane_robust_batch; include/pcrcg.h
+    "Robust kernels") -> BatchRefinementResult.  open3d's TransformationEstimationPointToPlane(kernel):
+    every correspondence's row of the Gauss-Newton system is multiplied with the kernel's weight of its residual (p - q) . n, so
+    targets of another surface inside the distance pull the step less.  kernel: a RobustKernel -- L2Loss(), L1Loss(),
+    HuberLoss(k), CauchyLoss(k), GMLoss(k), TukeyLoss(k) -- or None, which is refine_batch's call (the same entry, the same
+    arguments); every other argument is refine_batch's.  The evaluation, the count, fitness, rmse and the convergence test stay
+    unweighted; the trace's sums27 are the weighted sums; L2Loss() gives refine_batch's bits.  Point-to-point has no robust form
+    (open3d has none).  The kernel is an argument of its own entry, not a keyword of refine_batch, because refine_batch's
+    signature is pinned (tests/test_colored_icp_cpu.py)."""
+    return _refine_batch("robust_refine_batch", src_pcds, tgt_pcds, init, max_correspondence_distance, max_iteration,
+                         relative_fitness, relative_rmse, pairs_per_call, trace, "point_to_plane", tgt_normals, normal_radius,
+                         normal_max_nn, kernel)
+
+
+def _refine_batch(who, src_pcds, tgt_pcds, init, max_correspondence_distance, max_iteration, relative_fitness, relative_rmse,
+                  pairs_per_call, trace, estimation, tgt_normals, normal_radius, normal_max_nn, kernel):
+    """refine_batch's and robust_refine_batch's checks, in refine_batch's order with the kernel's after them, and call."""
     B = _check_pairs(who, src_pcds, tgt_pcds)
     if estimation not in _ESTIMATIONS:
         raise ValueError(f"{who}: estimation must be one of {sorted(_ESTIMATIONS)}, got {estimation!r}")
@@ -981,26 +1072,31 @@ def refine_batch(src_pcds, tgt_pcds, init, max_correspondence_distance, *, max_i
     ns = [_cloud_rows(x, who, "the source", b) for b, x in enumerate(src_pcds)]
     ms = [_cloud_rows(x, who, "the target", b) for b, x in enumerate(tgt_pcds)]
     _check_tgt_normal_rows(who, tgt_normals, ms)
+    _check_kernel(who, kernel)
+    if kernel is not None and not plane:
+        raise ValueError(f"{who}: a kernel belongs to estimation='point_to_plane' (point-to-point has no robust form)")
 
     def point_to_plane(L, c):       # pcrcg_icp_batch_ex's two more: the estimation and the targets' normals
         nrm = _tgt_normals_of(L, c, tgt_normals, search)
-        return (1, nrm.data_ptr() if c.m_tot else None), {"normals": (nrm, c.ms)}
+        ptr = nrm.data_ptr() if c.m_tot else None
+        # (pcrcg_icp_plane_robust_batch's three more: the normals, the kernel's kind and its scale)
+        return ((1, ptr) if kernel is None else (ptr, kernel.kind, kernel.k)), {"normals": (nrm, c.ms)}
 
-    return _icp_batch(who, "pcrcg_icp_batch_ex" if plane else "pcrcg_icp_batch", src_pcds, tgt_pcds, ns, ms, init, criteria,
-                      pairs_per_call, trace, (), point_to_plane if plane else lambda L, c: ((), {}))
+    entry = "pcrcg_icp_batch" if not plane else "pcrcg_icp_batch_ex" if kernel is None else "pcrcg_icp_plane_robust_batch"
+    return _icp_batch(who, entry, src_pcds, tgt_pcds, ns, ms, init, criteria, pairs_per_call, trace, (),
+                      point_to_plane if plane else lambda L, c: ((), {}))
 
 
 def refine(src_pcd, tgt_pcd, init, max_correspondence_distance, *, max_iteration=30, relative_fitness=1e-6,
            relative_rmse=1e-6, trace=False, estimation="point_to_point", tgt_normals=None, normal_radius=None,
-           normal_max_nn=30):
+           normal_max_nn=30, kernel=None):
     """ICP of one pair -> RefinementResult: refine_batch with a batch of one (init: None or a [4,4] start; tgt_normals: None
-    or the target's [M,3] normals)."""
+    or the target's [M,3] normals; kernel: None or a RobustKernel for point-to-plane, as robust_refine_batch's -- a kernel
+    with point-to-point raises ValueError)."""
     init = ragged.lift(init, (4, 4), "refine: init must be a [4, 4] transform")
-    return RefinementResult(refine_batch([src_pcd], [tgt_pcd], init, max_correspondence_distance,
-                                         max_iteration=max_iteration, relative_fitness=relative_fitness,
-                                         relative_rmse=relative_rmse, trace=trace, estimation=estimation,
-                                         tgt_normals=None if tgt_normals is None else [tgt_normals],
-                                         normal_radius=normal_radius, normal_max_nn=normal_max_nn))
+    return RefinementResult(_refine_batch("refine_batch", [src_pcd], [tgt_pcd], init, max_correspondence_distance, max_iteration,
+                                          relative_fitness, relative_rmse, None, trace, estimation,
+                                          None if tgt_normals is None else [tgt_normals], normal_radius, normal_max_nn, kernel))
 
 
 _COV_PACK = (0, 1, 2, 4, 5, 8)   # (xx, xy, xz, yy, yz, zz) of a row-major 3 x 3 (include/pcrcg.h)
@@ -1249,8 +1345,34 @@ def colored_icp_batch(src_pcds, tgt_pcds, src_colors, tgt_colors, init, max_corr
     the gradient radius, the gradient kernel and the ICP loop.  Every size and shape is checked on the host before anything is uploaded
     or launched; all chunks write into one device buffer, read ONCE at the end.  trace=True: refine_batch's point-to-plane
     trace (sums27: the upper triangle of sum JG JG^T + JI JI^T, then -sum (JG rg + JI ri)) plus tgt_records (per pair the
-    [M_b,8] float64 records the updates read) and src_intensities (per pair [N_b] float64)."""
-    who = "colored_icp_batch"
+    [M_b,8] float64 records the updates read) and src_intensities (per pair [N_b] float64).  Colored ICP under a robust loss
+    kernel is robust_colored_icp_batch."""
+    return _colored_icp_batch("colored_icp_batch", src_pcds, tgt_pcds, src_colors, tgt_colors, init, max_correspondence_distance,
+                              lambda_geometric, tgt_normals, normal_radius, normal_max_nn, gradient_radius, gradient_max_nn,
+                              max_iteration, relative_fitness, relative_rmse, pairs_per_call, trace, None)
+
+
+def robust_colored_icp_batch(src_pcds, tgt_pcds, src_colors, tgt_colors, init, max_correspondence_distance, kernel, *,
+                             lambda_geometric=0.968, tgt_normals=None, normal_radius=None, normal_max_nn=30, gradient_radius=None,
+                             gradient_max_nn=30, max_iteration=30, relative_fitness=1e-6, relative_rmse=1e-6, pairs_per_call=None,
+                             trace=False):
+    """colored_icp_batch under a robust loss kernel (pcrcg_colored_icp_robust_batch; include/pcrcg.h "Robust kernels", DESIGN.md
+    section 25) -> BatchRefinementResult.  open3d's TransformationEstimationForColoredICP(lambda_geometric, kernel): a
+    correspondence's geometric and colour rows are weighted separately, each with the kernel's weight of its own scaled residual
+    (sqrt(lambda) x the plane distance, sqrt(1 - lambda) x the intensity difference).  kernel: a RobustKernel, or None, which is
+    colored_icp_batch's call; every other argument is colored_icp_batch's.  Evaluation, statistics and convergence stay
+    unweighted, sums27 are the weighted sums, and L2Loss() gives colored_icp_batch's bits.  (An entry of its own for the reason
+    robust_refine_batch gives.)"""
+    return _colored_icp_batch("robust_colored_icp_batch", src_pcds, tgt_pcds, src_colors, tgt_colors, init,
+                              max_correspondence_distance, lambda_geometric, tgt_normals, normal_radius, normal_max_nn,
+                              gradient_radius, gradient_max_nn, max_iteration, relative_fitness, relative_rmse, pairs_per_call, trace,
+                              kernel)
+
+
+def _colored_icp_batch(who, src_pcds, tgt_pcds, src_colors, tgt_colors, init, max_correspondence_distance, lambda_geometric,
+                       tgt_normals, normal_radius, normal_max_nn, gradient_radius, gradient_max_nn, max_iteration, relative_fitness,
+                       relative_rmse, pairs_per_call, trace, kernel):
+    """colored_icp_batch's and robust_colored_icp_batch's checks, in colored_icp_batch's order with the kernel's last, and call."""
     B = _check_pairs(who, src_pcds, tgt_pcds)
     lam = float(lambda_geometric)
     if not 0.0 <= lam <= 1.0:
@@ -1265,6 +1387,7 @@ def colored_icp_batch(src_pcds, tgt_pcds, src_colors, tgt_colors, init, max_corr
     _check_colors(who, "source", src_colors, B, ns)
     _check_colors(who, "target", tgt_colors, B, ms)
     _check_tgt_normal_rows(who, tgt_normals, ms)
+    _check_kernel(who, kernel)
 
     def colored(L, c):              # pcrcg_colored_icp_batch's three more: lambda, the targets' records, the sources' intensities
         dev = c.tgt.device
@@ -1272,22 +1395,28 @@ def colored_icp_batch(src_pcds, tgt_pcds, src_colors, tgt_colors, init, max_corr
         src_int = _intensities(src_colors[c.b0:c.b1], dev)
         rec = _gradients_of(L, c.tgt, c.tgt_off, c.m_len, c.m_tot, c.nb, max(c.ms), gr, gk, nrm,
                             _intensities(tgt_colors[c.b0:c.b1], dev), False)[0]
-        return ((lam, rec.data_ptr() if c.m_tot else None, src_int.data_ptr() if c.n_tot else None),
+        # (pcrcg_colored_icp_robust_batch's two more: the kernel's kind and its scale)
+        return ((lam, rec.data_ptr() if c.m_tot else None, src_int.data_ptr() if c.n_tot else None,
+                 *(() if kernel is None else (kernel.kind, kernel.k))),
                 {"normals": (nrm, c.ms), "tgt_records": (rec, c.ms), "src_intensities": (src_int, c.ns)})
 
     given = [*src_colors, *tgt_colors, *(tgt_normals if tgt_normals is not None else [])]
-    return _icp_batch(who, "pcrcg_colored_icp_batch", src_pcds, tgt_pcds, ns, ms, init, criteria, pairs_per_call, trace, given,
-                      colored)
+    entry = "pcrcg_colored_icp_batch" if kernel is None else "pcrcg_colored_icp_robust_batch"
+    return _icp_batch(who, entry, src_pcds, tgt_pcds, ns, ms, init, criteria, pairs_per_call, trace, given, colored)
 
 
 def colored_icp(src_pcd, tgt_pcd, src_colors, tgt_colors, init, max_correspondence_distance, **kw):
     """Colored ICP of one pair -> RefinementResult: colored_icp_batch with a batch of one (init: None or a [4,4] start;
-    tgt_normals: None or the target's [M,3] normals)."""
+    tgt_normals: None or the target's [M,3] normals); with kernel=a RobustKernel, robust_colored_icp_batch with a batch of one."""
     init = ragged.lift(init, (4, 4), "colored_icp: init must be a [4, 4] transform")
     if kw.get("tgt_normals") is not None:
         kw["tgt_normals"] = [kw["tgt_normals"]]
-    return RefinementResult(colored_icp_batch([src_pcd], [tgt_pcd], [src_colors], [tgt_colors], init,
-                                              max_correspondence_distance, **kw))
+    kernel = kw.pop("kernel", None)
+    if kernel is None:
+        return RefinementResult(colored_icp_batch([src_pcd], [tgt_pcd], [src_colors], [tgt_colors], init,
+                                                  max_correspondence_distance, **kw))
+    return RefinementResult(robust_colored_icp_batch([src_pcd], [tgt_pcd], [src_colors], [tgt_colors], init,
+                                                     max_correspondence_distance, kernel, **kw))
 
 
 def refine_ground_truth(xyz0, xyz1, M):
